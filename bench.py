@@ -99,7 +99,12 @@ def main() -> int:
     ap.add_argument("--no-pipeline", action="store_true", help="time blocking vj_detect calls instead of a two-deep vj_stream")
     ap.add_argument("--pass-split", default=None)
     ap.add_argument("--blocks-per-cu", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, write the rectangles the last timed step returned (the whole job's, gathered) as "
+                         "DIR/rects_<field>.npy, one float array per RECT_DTYPE field")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     import torch
     import torch.distributed as dist
@@ -220,6 +225,7 @@ def main() -> int:
             m["launches"] = r.launches
             m["n_det_total"] = len(rects)
             m["timed_rects"] = r.rects
+            m["last_rects"] = rects
         own = time.perf_counter() - t0        # this rank's own steps (before it waits for the others)
         barrier()
         elapsed = time.perf_counter() - t0
@@ -260,6 +266,8 @@ def main() -> int:
     B, frames_h, dframes, counted = m["B"], m["frames_h"], m["dframes"], m["counted"]
     integral_ms, cascade_ms, pass_ms, launch_ms, launches = m["integral_ms"], m["cascade_ms"], m["pass_ms"], m["launch_ms"], m["launches"]
     n_det_total, timed_rects = m["n_det_total"], m["timed_rects"]
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, m["last_rects"])
 
     out = None
     if rank == 0:
@@ -442,6 +450,26 @@ def main() -> int:
             print("bench.py: PARITY FAILURE on the CPU sample", file=sys.stderr)
             return 4
     return 0
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rects):
+    """The rectangles a caller of the timed path received in its last step, one .npy per RECT_DTYPE field: integer fields
+    as float64, `weight` as float32 (both exact).  Past DUMP_LIMIT_BYTES in all, a fixed seeded sample of rows is written
+    (still in the library's order) with their indices in rects_sample_index.npy."""
+    row_bytes = sum(8 if rects.dtype[k].kind == "i" else 4 for k in rects.dtype.names)
+    idx = None
+    if len(rects) * row_bytes > DUMP_LIMIT_BYTES:
+        n = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)          # (4096: the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(len(rects), n, replace=False))
+        rects = rects[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for k in rects.dtype.names:
+        np.save(os.path.join(out_dir, f"rects_{k}.npy"), rects[k].astype(np.float64 if rects.dtype[k].kind == "i" else np.float32))
+    if idx is not None:
+        np.save(os.path.join(out_dir, "rects_sample_index.npy"), idx.astype(np.float64))
 
 
 def three_states(env, call, torch, timed=8) -> dict:

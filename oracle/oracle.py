@@ -6,8 +6,8 @@ parity-pinning statement.
 
 Contents
   * parse_xml()  — an independent reader of OpenCV's old-format Haar XML, following
-                   icvReadHaarClassifier (tempcv.cpp:1749-2089); used here (where
-                   /root/reference exists) to cross-check the product's C++ loader.
+                   icvReadHaarClassifier (tempcv.cpp:1749-2089); used on the stock XMLs
+                   stored under tests/golden/xml/ to cross-check the product's C++ loader.
   * load_vjc()   — an independent reader of the package's compact .vjc files.
   * Oracle       — ctypes bindings of libvjoracle.so (vj_oracle.c).
 """

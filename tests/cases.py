@@ -3,6 +3,8 @@ tests (oracle vs fixtures) and the GPU tests (HIP path vs oracle and vs fixtures
 from __future__ import annotations
 
 import hashlib
+import lzma
+import os
 
 import numpy as np
 
@@ -136,6 +138,20 @@ def block_grid_frame(transposed: bool = False) -> np.ndarray:
 
 
 BLOCK_GRID_LIMITS = {"min_size": (230, 230), "max_size": (270, 270)}     # scales 26 and 27 only
+
+
+# the 19 stock OpenCV XMLs the cascades in clfacedetection_amd/data/ were converted from, verbatim and xz-compressed
+# (tools/make_xml_golden.py): the loader tests read the XML text itself without the reference checkout
+XML_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "xml")
+STOCK_XMLS = sorted(f[:-len(".xz")] for f in os.listdir(XML_DIR) if f.endswith(".xml.xz"))
+
+
+def stock_xml(xml: str, dest_dir) -> str:
+    """tests/golden/xml/<xml>.xz unpacked into dest_dir; returns the XML's path."""
+    path = os.path.join(str(dest_dir), xml)
+    with open(path, "wb") as f:
+        f.write(lzma.decompress(open(os.path.join(XML_DIR, xml + ".xz"), "rb").read()))
+    return path
 
 
 def sha(a: np.ndarray) -> str:

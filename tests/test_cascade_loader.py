@@ -1,5 +1,6 @@
 """Cascade loading: known answers from the reference's XML text, .vjc round trips,
-and the product's C++ loader against the oracle's independent readers."""
+and the product's C++ loader against the oracle's independent readers (the stock XMLs are
+stored under tests/golden/xml/)."""
 import ctypes as C
 import os
 
@@ -10,7 +11,7 @@ from clfacedetection_amd import Cascade, VjError, load_library
 from clfacedetection_amd.api import DATA_DIR
 from oracle.oracle import load_vjc, parse_xml
 
-REF = "/root/reference/CLFaceDetection"
+from cases import STOCK_XMLS, stock_xml
 NAMES = ["frontalface_default", "frontalface_alt", "frontalface_alt2", "frontalface_alt_tree", "eye"]
 TILTED = ["fullbody", "eye_tree_eyeglasses"]   # shipped for the OpenCV profile's tilted-feature tests
 # win, stages, trees, nodes, maxT, maxN, tilted, 3-rect
@@ -88,20 +89,19 @@ def test_vjc_round_trip(tmp_path, name):
     assert open(p, "rb").read() == open(os.path.join(DATA_DIR, f"haarcascade_{name}.vjc"), "rb").read()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (e.g. on the GPU box)")
-@pytest.mark.parametrize("xml", sorted(f for f in (os.listdir(REF) if os.path.isdir(REF) else []) if f.endswith(".xml")))
+@pytest.mark.parametrize("xml", STOCK_XMLS)
 def test_xml_loader_matches_oracle_parser(tmp_path, xml):
     """All 19 stock XMLs: the C++ XML reader and the oracle's ElementTree reader agree bit for bit."""
-    c = Cascade.load_xml(os.path.join(REF, xml))
+    path = stock_xml(xml, tmp_path)
+    c = Cascade.load_xml(path)
     p = str(tmp_path / "x.vjc")
     c.save(p)
-    assert parse_xml(os.path.join(REF, xml)).same_as(load_vjc(p)) == []
+    assert parse_xml(path).same_as(load_vjc(p)) == []
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
 @pytest.mark.parametrize("name", NAMES + TILTED)
-def test_shipped_vjc_is_current(name):
-    a = parse_xml(os.path.join(REF, f"haarcascade_{name}.xml"))
+def test_shipped_vjc_is_current(tmp_path, name):
+    a = parse_xml(stock_xml(f"haarcascade_{name}.xml", tmp_path))
     assert a.same_as(load_vjc(os.path.join(DATA_DIR, f"haarcascade_{name}.vjc"))) == []
 
 
