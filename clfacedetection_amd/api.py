@@ -143,6 +143,7 @@ _SIGNATURES = {
     "vj_env_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "vj_env_device_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "vj_env_configure": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
+    "vj_env_query": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t]),
     "vj_integral": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vj_integral_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vj_integral_tilted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -354,8 +355,16 @@ class Environment:
         return buf.value.decode()
 
     def configure(self, key: str, value) -> None:
-        """Tunables that never change results: 'pass_split' ("4,9,15"), 'blocks_per_cu'."""
+        """Set a tunable: speed only, results never depend on them.  The keys, their values and defaults are listed in
+        include/vj.h and DESIGN.md §7 (e.g. 'pass_split' "4,9,15", 'blocks_per_cu' 8); configure("defaults", "") puts
+        every tunable back to what a fresh Environment has."""
         _check(load_library().vj_env_configure(self._h, key.encode(), str(value).encode()), f"vj_env_configure({key})")
+
+    def query(self, key: str) -> str:
+        """The current value of a tunable, in the syntax configure accepts."""
+        buf = C.create_string_buffer(1024)
+        _check(load_library().vj_env_query(self._h, key.encode(), buf, len(buf)), f"vj_env_query({key})")
+        return buf.value.decode()
 
     def reserve(self, width: int, height: int, batch: int = 1):
         _check(load_library().vj_env_reserve(self._h, width, height, batch), "vj_env_reserve")

@@ -10,12 +10,15 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
+#include <string>
 #include <tuple>
 
 #include "vj_env_internal.hpp"
@@ -1955,16 +1958,6 @@ int vj_env_create(int device_index, vj_env** out) {
     HIP_TRY(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&e->join_ev, hipEventDisableTiming));
     HIP_TRY(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
-    if (const char* s = getenv("VJ_BLOCKS_PER_CU")) e->blocks_per_cu = std::max(1, atoi(s));
-    if (const char* s = getenv("VJ_PASS_SPLIT")) {  // e.g. "4,9,15"
-        for (const char* q = s; *q;) {
-            char* endp;
-            long v = strtol(q, &endp, 10);
-            if (endp == q) break;
-            e->split_override.push_back((int)v);
-            q = *endp ? endp + 1 : endp;
-        }
-    }
     *out = e.release();
     return VJ_OK;
 }
@@ -2001,362 +1994,296 @@ static void drop_plans(vj_env* e) {
     e->cv_plans.clear();
 }
 
+// ----------------------------------------------------------------------------------------- tunables
+// One row per vj_env_configure key: how its value is parsed, the field it lands in and what a new value invalidates.
+// vj_env_query formats the same field back in the syntax configure accepts.
+namespace {
+
+enum class Kind { Bool, Clamp, Range, Auto, List, Custom };
+//   Bool   atoi(value) != 0                       Range  atoi(value), VJ_ERR_ARG outside [lo, hi]
+//   Clamp  atoi(value) clamped to [lo, hi]        Auto   -1 for negative values ("auto"), else clamped to [lo, hi]
+//   List   comma-separated integers               Custom the row's own set / get (get == nullptr: an action, not a value)
+enum : unsigned {
+    DROP_PLANS = 1,       // the value is baked into plans: sync, then drop every cached plan
+    DROP_CV_PLANS = 2,    // ... into OpenCV-profile plans only
+    SET_THRESHOLDS = 4,   // the tile thresholds were chosen by the caller: no per-frame-size defaults (get_plan)
+    SET_SPLIT = 8,        // the chain balance was chosen by the caller: no feedback
+    CLEAR_BALANCE = 16,   // forget the chain balances found so far
+};
+
+struct Key {
+    const char* name;
+    Kind kind;
+    unsigned effects;
+    int Tunables::*i;                // Bool (an int field), Clamp, Range, Auto
+    bool Tunables::*b;               // Bool
+    std::vector<int> Tunables::*v;   // List
+    int lo, hi;
+    int (*set)(vj_env*, const char*);                  // Custom
+    void (*get)(const vj_env*, std::string&);          // Custom
+};
+
+constexpr int MAX = INT_MAX;
+Key flag(const char* n, bool Tunables::*f, unsigned fx = 0) { return {n, Kind::Bool, fx, nullptr, f}; }
+Key int_flag(const char* n, int Tunables::*f, unsigned fx = 0) { return {n, Kind::Bool, fx, f}; }   // an int field holding 0 / 1
+Key clamped(const char* n, int Tunables::*f, int lo, int hi, unsigned fx = 0) { return {n, Kind::Clamp, fx, f, nullptr, nullptr, lo, hi}; }
+Key bounded(const char* n, int Tunables::*f, int lo, int hi, unsigned fx = 0) { return {n, Kind::Range, fx, f, nullptr, nullptr, lo, hi}; }
+Key with_auto(const char* n, int Tunables::*f, int lo, int hi, unsigned fx = 0) { return {n, Kind::Auto, fx, f, nullptr, nullptr, lo, hi}; }
+Key int_list(const char* n, std::vector<int> Tunables::*f, unsigned fx = 0) { return {n, Kind::List, fx, nullptr, nullptr, f}; }
+Key special(const char* n, int (*set)(vj_env*, const char*), void (*get)(const vj_env*, std::string&), unsigned fx = 0) {
+    return {n, Kind::Custom, fx, nullptr, nullptr, nullptr, 0, 0, set, get};
+}
+
+// "a,b,c" -> integers; at most max_n of them are read (the rest of the string is ignored)
+bool parse_list(const char* s, std::vector<long>& out, size_t max_n = SIZE_MAX) {
+    for (const char* q = s; *q && out.size() < max_n;) {
+        char* end;
+        const long x = strtol(q, &end, 10);
+        if (end == q) return false;
+        out.push_back(x);
+        q = *end == ',' ? end + 1 : end;
+    }
+    return true;
+}
+
+void append_list(std::string& s, const int* v, size_t n) {
+    for (size_t k = 0; k < n; ++k) s += (k ? "," : "") + std::to_string(v[k]);
+}
+
+int set_tile_classes(vj_env* e, const char* value) {   // "36,64,140"; "0,0,0" disables the LDS-tile path
+    std::vector<long> v;
+    bool ok = parse_list(value, v, TILE_CLASSES);
+    for (long x : v) ok = ok && (int)x >= -4 && (int)x <= 140;
+    if (!ok) {
+        set_error("tile_classes_kb: expected up to %d comma-separated values in [-4,140]", TILE_CLASSES);
+        return VJ_ERR_ARG;
+    }
+    for (int k = 0; k < TILE_CLASSES; ++k) e->tile_class_kb[k] = k < (int)v.size() ? (int)v[k] : 0;
+    return VJ_OK;
+}
+
+int set_tile_repack(vj_env* e, const char* value) {   // "3,5": stages before which tiles re-pack ("" = never)
+    std::vector<long> v;
+    bool ok = parse_list(value, v);
+    unsigned long long m = 0;
+    for (long x : v) {
+        ok = ok && x >= 1 && x <= 63;
+        if (ok) m |= 1ull << x;
+    }
+    if (!ok) {
+        set_error("tile_repack: expected comma-separated stage indices in [1,63]");
+        return VJ_ERR_ARG;
+    }
+    e->tile_repack_mask = m;
+    return VJ_OK;
+}
+
+void get_tile_repack(const vj_env* e, std::string& s) {
+    std::vector<int> v;
+    for (int x = 0; x < 64; ++x)
+        if (e->tile_repack_mask >> x & 1) v.push_back(x);
+    append_list(s, v.data(), v.size());
+}
+
+int set_tile_split(vj_env* e, const char* value) {   // one value for every batch size, or "small,mid,large" (<= 4, < 32, >= 32 frames)
+    float a = 0, b = 0, c = 0;
+    if (sscanf(value, "%f,%f,%f", &a, &b, &c) != 3) a = b = c = (float)atof(value);
+    e->tile_split_small = std::max(0.0f, a);
+    e->tile_split_mid = std::max(0.0f, b);
+    e->tile_split = std::max(0.0f, c);
+    return VJ_OK;
+}
+
+int set_det_cap(vj_env* e, const char* value) {   // (re)sets the detection buffer capacity; it still grows on overflow
+    const int v = atoi(value);
+    if (v < 1) {
+        set_error("det_cap must be >= 1");
+        return VJ_ERR_ARG;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->det_cap_init = (uint32_t)v;
+    e->lane0.det_cap = 0;
+    return VJ_OK;
+}
+
+int set_auto_balance(vj_env* e, const char* value) {   // 1: find the chain balance of a batch workload from its first calls' times; "reset": start over
+    if (strcmp(value, "reset") == 0) e->tile_split_set = false;
+    else e->auto_balance = atoi(value) != 0;
+    return VJ_OK;
+}
+
+int set_defaults(vj_env* e, const char*) {   // every tunable as vj_env_create left it
+    static_cast<Tunables&>(*e) = Tunables{};
+    e->lane0.det_cap = 0;   // det_cap_init applies again
+    return VJ_OK;
+}
+
+const Key KEYS[] = {
+    // launch structure
+    int_list("pass_split", &Tunables::split_override, DROP_PLANS),
+    int_list("pass_cut_nodes", &Tunables::pass_cut_nodes, DROP_PLANS),
+    bounded("blocks_per_cu", &Tunables::blocks_per_cu, 1, 16),
+    int_flag("concurrent", &Tunables::concurrent),
+    clamped("concurrent_blocks_per_cu", &Tunables::concurrent_blocks_per_cu, 1, MAX),
+    clamped("max_subbatch", &Tunables::max_subbatch, 0, MAX),
+    special("det_cap", set_det_cap, [](const vj_env* e, std::string& s) { s = std::to_string(e->det_cap_init); }),
+    // LDS tiles
+    special("tile_classes_kb", set_tile_classes, [](const vj_env* e, std::string& s) { append_list(s, e->tile_class_kb, TILE_CLASSES); },
+            DROP_PLANS),
+    clamped("tile_lds_reserve_kb", &Tunables::tile_lds_reserve_kb, 0, 96, DROP_PLANS),
+    bounded("tile_min_windows", &Tunables::tile_min_windows, 0, 65536, DROP_PLANS | SET_THRESHOLDS),
+    bounded("tile_accept_windows", &Tunables::tile_accept_windows, 0, 65536, DROP_PLANS | SET_THRESHOLDS),
+    bounded("tile_max_dwords_per_window", &Tunables::tile_max_dwords_per_window, 0, 65536, DROP_PLANS | SET_THRESHOLDS),
+    bounded("tile_end", &Tunables::tile_end, 0, 65536, DROP_PLANS),
+    bounded("tile_min_lanes", &Tunables::tile_min_lanes, 0, 65536, DROP_PLANS),
+    int_flag("tile_class_order", &Tunables::tile_class_order),
+    int_flag("tile_lds_nest", &Tunables::tile_lds_nest, DROP_PLANS),
+    special("tile_repack", set_tile_repack, get_tile_repack),
+    int_flag("tile_deinterleave", &Tunables::tile_deinterleave, DROP_PLANS),
+    int_flag("tile_stage_x4", &Tunables::tile_stage_x4, DROP_PLANS),
+    int_flag("global_blocks", &Tunables::global_blocks),
+    // tile finish
+    int_flag("tile_finish", &Tunables::tile_finish),
+    clamped("tile_sp_begin", &Tunables::tile_sp_begin, 0, MAX, DROP_PLANS),   // the LDS layout of the tile launches depends on it
+    clamped("tile_sp_max", &Tunables::tile_sp_max, 0, TILE_SP_MAX_WINDOWS),
+    clamped("tile_ws_min", &Tunables::tile_ws_min, 0, TILE_SP_MAX_WINDOWS),
+    clamped("tile_ws_max", &Tunables::tile_ws_max, 0, TILE_WS_MAX_WINDOWS),
+    // chain balance
+    special("tile_split", set_tile_split,
+            [](const vj_env* e, std::string& s) {
+                char b[64];
+                snprintf(b, sizeof(b), "%.9g,%.9g,%.9g", e->tile_split_small, e->tile_split_mid, e->tile_split);
+                s = b;
+            },
+            DROP_PLANS | SET_SPLIT | CLEAR_BALANCE),
+    special("auto_balance", set_auto_balance, [](const vj_env* e, std::string& s) { s = std::to_string((int)e->auto_balance); },
+            CLEAR_BALANCE),
+    flag("balance_exact", &Tunables::balance_exact, CLEAR_BALANCE),
+    special("balance_export", [](vj_env* e, const char* path) { return balance_export(e, path); }, nullptr),
+    special("balance_import", [](vj_env* e, const char* path) { return balance_import(e, path); }, nullptr),
+    // global-gather chain
+    clamped("grid_block_w", &Tunables::grid_block_w, 0, UNIT_WINDOWS, DROP_PLANS),
+    clamped("gather_waves", &Tunables::gather_waves, INT_MIN, MAX),   // 3, 4, or -1 = 4 for calls of >= 8 frames
+    with_auto("gather_pairs", &Tunables::gather_pairs, 0, 2),
+    clamped("sp_tail_max", &Tunables::sp_tail_max, 0, 48),
+    with_auto("wide_tail", &Tunables::wide_tail, 0, 1),
+    clamped("min_chunk", &Tunables::min_chunk, 1, 64),
+    flag("thin_pass_spread", &Tunables::thin_pass_spread),
+    with_auto("q_slices", &Tunables::q_slices, 0, 64),
+    int_flag("xcd_affinity", &Tunables::xcd_affinity),
+    clamped("q_band_px", &Tunables::q_band_px, 0, MAX, DROP_PLANS),
+    clamped("q_group_units", &Tunables::q_group_units, 0, MAX, DROP_PLANS),
+    clamped("q_band_min_frames", &Tunables::q_band_min_frames, 1, MAX),
+    // stage trees
+    int_flag("general_prefix", &Tunables::general_prefix, DROP_PLANS),
+    int_flag("tile_segments", &Tunables::tile_segments),
+    clamped("seg_cut2", &Tunables::seg_cut2, 0, MAX, DROP_PLANS),
+    flag("tree_split_queues", &Tunables::tree_split_queues),
+    // regions / chain
+    flag("rois_on_device", &Tunables::rois_on_device),
+    clamped("roi_tiles", &Tunables::roi_tile_min_windows, 0, MAX),
+    clamped("group_max", &Tunables::group_max, 1, GROUP_MAX),
+    // OpenCV profile
+    flag("cv_tiles", &Tunables::cv_tiles, DROP_CV_PLANS),
+    with_auto("cv_row_blocks", &Tunables::cv_row_blocks, 1, 4, DROP_CV_PLANS),
+    with_auto("cv_tile_min_windows", &Tunables::cv_tile_min_windows, 64, MAX, DROP_CV_PLANS),
+    clamped("cv_tile_min_windows0", &Tunables::cv_tile_min_windows0, 64, MAX, DROP_CV_PLANS),
+    clamped("cv_tile_ws_max", &Tunables::cv_tile_ws_max, 0, CVT_WS_MAX, DROP_CV_PLANS),
+    clamped("cv_row_blocks_tree", &Tunables::cv_row_blocks_tree, 1, 4, DROP_CV_PLANS),
+    clamped("cv_tile_min_windows_tree", &Tunables::cv_tile_min_windows_tree, 64, MAX, DROP_CV_PLANS),
+    flag("cv_tree_chains", &Tunables::cv_tree_chains),
+    clamped("cv_tree_chunk", &Tunables::cv_tree_chunk, 1, MAX),
+    clamped("cv_tree_chain_blocks", &Tunables::cv_tree_chain_blocks, 1, MAX),
+    clamped("cv_tail_max", &Tunables::cv_tail_max, 0, CV_TAIL_MAX, DROP_PLANS),
+    flag("cv_pairs", &Tunables::cv_pairs),
+    clamped("cv_row_band_px", &Tunables::cv_row_band_px, 0, MAX, DROP_PLANS),
+    flag("cv_tree2", &Tunables::cv_tree2, DROP_PLANS),   // (the default balance depends on it)
+    flag("cv_tiles_tilted", &Tunables::cv_tiles_tilted, DROP_PLANS),
+    flag("tilted_bands", &Tunables::tilted_bands),
+    clamped("cv_tree_queue_cap", &Tunables::cv_tree_queue_cap, 0, MAX),
+    // single frames, integral, housekeeping
+    clamped("one_pass_max_frames", &Tunables::one_pass_max_frames, 0, MAX),   // (part of the plan key: nothing to drop)
+    clamped("integral_rows", &Tunables::integral_rows_mode, 0, 2),
+    clamped("plan_cache_max", &Tunables::plan_cache_max, 2, MAX),   // vj_detect_chain holds two plans at once
+    special("defaults", set_defaults, nullptr, DROP_PLANS | CLEAR_BALANCE),
+};
+
+const Key* find_key(const char* name) {
+    for (const Key& k : KEYS)
+        if (strcmp(k.name, name) == 0) return &k;
+    set_error("unknown option '%s'", name);
+    return nullptr;
+}
+
+}  // namespace
+
+int vj_env_query(const vj_env* e, const char* key, char* buf, size_t cap) {
+    if (!e || !key || !buf || cap == 0) return VJ_ERR_ARG;
+    const Key* k = find_key(key);
+    if (!k) return VJ_ERR_ARG;
+    std::string s;
+    switch (k->kind) {
+        case Kind::Bool: s = std::to_string(k->b ? (int)(e->*k->b) : e->*k->i); break;
+        case Kind::List: append_list(s, (e->*k->v).data(), (e->*k->v).size()); break;
+        case Kind::Custom:
+            if (!k->get) {
+                set_error("'%s' is an action, not a value", key);
+                return VJ_ERR_ARG;
+            }
+            k->get(e, s);
+            break;
+        default: s = std::to_string(e->*k->i);
+    }
+    if (s.size() >= cap) {
+        set_error("vj_env_query(%s): the value needs %zu bytes", key, s.size() + 1);
+        return VJ_ERR_ARG;
+    }
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return VJ_OK;
+}
+
 int vj_env_configure(vj_env* e, const char* key, const char* value) {
     if (!e || !key || !value) return VJ_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
-    if (strcmp(key, "pass_cut_nodes") == 0) {   // default pass cuts: after these numbers of cumulative nodes
-        std::vector<int> v;
-        for (const char* q = value; *q;) {
-            char* end = nullptr;
-            const long x = strtol(q, &end, 10);
-            if (end == q) {
-                set_error("pass_cut_nodes: expected comma-separated integers, got '%s'", value);
+    const Key* k = find_key(key);
+    if (!k) return VJ_ERR_ARG;
+    const int v = atoi(value);
+    switch (k->kind) {
+        case Kind::Bool:
+            if (k->b) e->*k->b = v != 0;
+            else e->*k->i = v != 0;
+            break;
+        case Kind::Clamp: e->*k->i = std::max(k->lo, std::min(v, k->hi)); break;
+        case Kind::Auto: e->*k->i = v < 0 ? -1 : std::max(k->lo, std::min(v, k->hi)); break;
+        case Kind::Range:
+            if (v < k->lo || v > k->hi) {
+                set_error("%s must be in [%d,%d]", key, k->lo, k->hi);
                 return VJ_ERR_ARG;
             }
-            v.push_back((int)x);
-            q = *end == ',' ? end + 1 : end;
-        }
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        e->pass_cut_nodes = v;
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "pass_split") == 0) {
-        std::vector<int> v;
-        for (const char* q = value; *q;) {
-            char* endp;
-            long x = strtol(q, &endp, 10);
-            if (endp == q) {
-                set_error("pass_split: expected comma-separated integers, got '%s'", value);
+            e->*k->i = v;
+            break;
+        case Kind::List: {
+            std::vector<long> x;
+            if (!parse_list(value, x)) {
+                set_error("%s: expected comma-separated integers, got '%s'", key, value);
                 return VJ_ERR_ARG;
             }
-            v.push_back((int)x);
-            q = *endp ? endp + 1 : endp;
+            e->*k->v = std::vector<int>(x.begin(), x.end());
+            break;
         }
-        e->split_override = v;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);  // pass bounds are part of a plan
-        return VJ_OK;
+        case Kind::Custom:
+            if (const int rc = k->set(e, value)) return rc;
     }
-    if (strcmp(key, "tile_classes_kb") == 0) {  // "36,64,140"; "0,0,0" disables the LDS-tile path
-        int v[TILE_CLASSES] = {0, 0, 0};
-        const char* q = value;
-        for (int i = 0; i < TILE_CLASSES && *q; ++i) {
-            char* endp;
-            v[i] = (int)strtol(q, &endp, 10);
-            if (endp == q || v[i] < -4 || v[i] > 140) {
-                set_error("tile_classes_kb: expected up to %d values in [0,140]", TILE_CLASSES);
-                return VJ_ERR_ARG;
-            }
-            q = *endp ? endp + 1 : endp;
-        }
-        for (int i = 0; i < TILE_CLASSES; ++i) e->tile_class_kb[i] = v[i];
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_finish") == 0) {
-        e->tile_finish = atoi(value) != 0 ? 1 : 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_ws_min") == 0) {
-        e->tile_ws_min = std::max(0, std::min(atoi(value), (int)TILE_SP_MAX_WINDOWS));
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_ws_max") == 0) {
-        e->tile_ws_max = std::max(0, std::min(atoi(value), (int)TILE_WS_MAX_WINDOWS));
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_sp_max") == 0) {
-        e->tile_sp_max = std::max(0, std::min(atoi(value), (int)TILE_SP_MAX_WINDOWS));
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_lds_nest") == 0) {
-        e->tile_lds_nest = atoi(value) != 0;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "tree_split_queues") == 0) {
-        e->tree_split_queues = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "q_band_px") == 0 || strcmp(key, "q_group_units") == 0) {   // band-major first-pass units and queue pass (0: off)
-        (strcmp(key, "q_band_px") == 0 ? e->q_band_px : e->q_group_units) = std::max(0, atoi(value));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "q_band_min_frames") == 0) {
-        e->q_band_min_frames = std::max(1, atoi(value));
-        return VJ_OK;
-    }
-    if (strcmp(key, "cv_pairs") == 0) {
-        e->cv_pairs = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "cv_tail_max") == 0) {   // (part of the plan: cached plans are dropped)
-        e->cv_tail_max = std::max(0, std::min(atoi(value), (int)CV_TAIL_MAX));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "cv_tree_chunk") == 0 || strcmp(key, "cv_tree_chain_blocks") == 0) {
-        (strcmp(key, "cv_tree_chunk") == 0 ? e->cv_tree_chunk : e->cv_tree_chain_blocks) = std::max(1, atoi(value));
-        return VJ_OK;
-    }
-    if (strcmp(key, "one_pass_max_frames") == 0) {   // (part of the plan key: nothing to drop)
-        e->one_pass_max_frames = std::max(0, atoi(value));
-        return VJ_OK;
-    }
-    if (strcmp(key, "tilted_bands") == 0) {
-        e->tilted_bands = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "cv_tiles_tilted") == 0) {   // (part of the plan: cached plans are dropped)
-        e->cv_tiles_tilted = atoi(value) != 0;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "cv_tree2") == 0) {   // (the default balance depends on it: cached plans are dropped)
-        e->cv_tree2 = atoi(value) != 0;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "cv_row_band_px") == 0) {   // OpenCV profile: row order of cv_profile_pass (part of the plan: cached plans are dropped)
-        e->cv_row_band_px = std::max(0, atoi(value));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "cv_tree_chains") == 0) {   // OpenCV profile, stage trees made of chains: compacting chain sweeps (1) or the per-lane walk (0)
-        e->cv_tree_chains = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "cv_tree_queue_cap") == 0) {
-        e->cv_tree_queue_cap = std::max(0, atoi(value));
-        return VJ_OK;
-    }
-    if (strcmp(key, "roi_tiles") == 0) {   // region pass: smallest (region, scale) grid that runs on LDS tiles (0: none)
-        e->roi_tile_min_windows = std::max(0, atoi(value));
-        return VJ_OK;
-    }
-    if (strcmp(key, "rois_on_device") == 0) {
-        e->rois_on_device = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "cv_tiles") == 0 || strcmp(key, "cv_tile_ws_max") == 0 || strcmp(key, "cv_tile_min_windows") == 0 ||
-        strcmp(key, "cv_row_blocks") == 0 || strcmp(key, "cv_tile_min_windows0") == 0 || strcmp(key, "cv_row_blocks_tree") == 0 ||
-        strcmp(key, "cv_tile_min_windows_tree") == 0) {
-        // OpenCV profile: 0 = every scale on cv_profile_pass; the finish threshold; the smallest tile worth staging
-        const int v = atoi(value);
-        if (strcmp(key, "cv_tiles") == 0) e->cv_tiles = v != 0;
-        else if (strcmp(key, "cv_tile_ws_max") == 0) e->cv_tile_ws_max = std::max(0, std::min(v, (int)CVT_WS_MAX));
-        else if (strcmp(key, "cv_row_blocks") == 0) e->cv_row_blocks = v < 0 ? -1 : std::max(1, std::min(v, 4));
-        else if (strcmp(key, "cv_tile_min_windows0") == 0) e->cv_tile_min_windows0 = std::max(64, v);
-        else if (strcmp(key, "cv_row_blocks_tree") == 0) e->cv_row_blocks_tree = std::max(1, std::min(v, 4));
-        else if (strcmp(key, "cv_tile_min_windows_tree") == 0) e->cv_tile_min_windows_tree = std::max(64, v);
-        else e->cv_tile_min_windows = v < 0 ? -1 : std::max(64, v);
-        HIP_TRY(hipStreamSynchronize(e->stream));
+    if (k->effects & SET_THRESHOLDS) e->tile_thresholds_set = true;
+    if (k->effects & SET_SPLIT) e->tile_split_set = true;
+    if (k->effects & CLEAR_BALANCE) e->balance.clear();
+    if (k->effects & (DROP_PLANS | DROP_CV_PLANS)) HIP_TRY(hipStreamSynchronize(e->stream));
+    if (k->effects & DROP_PLANS) drop_plans(e);
+    if (k->effects & DROP_CV_PLANS) {
         for (auto& kv : e->cv_plans) kv.second->release_device();
         e->cv_plans.clear();
-        return VJ_OK;
     }
-    if (strcmp(key, "wide_tail") == 0) {
-        e->wide_tail = std::max(-1, std::min(atoi(value), 1));   // -1: by batch size
-        return VJ_OK;
-    }
-    if (strcmp(key, "min_chunk") == 0) {
-        e->min_chunk = std::max(1, std::min(atoi(value), 64));
-        return VJ_OK;
-    }
-    if (strcmp(key, "q_slices") == 0) {
-        e->q_slices = std::max(-1, std::min(atoi(value), 64));
-        return VJ_OK;
-    }
-    if (strcmp(key, "thin_pass_spread") == 0) {
-        e->thin_pass_spread = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "group_max") == 0) {
-        e->group_max = std::max(1, std::min(atoi(value), (int)GROUP_MAX));
-        return VJ_OK;
-    }
-    if (strcmp(key, "sp_tail_max") == 0) {
-        e->sp_tail_max = std::max(0, std::min(atoi(value), 48));
-        return VJ_OK;
-    }
-    if (strcmp(key, "gather_pairs") == 0) {
-        e->gather_pairs = std::max(-1, std::min(atoi(value), 2));   // -1: by batch size
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_class_order") == 0) {
-        e->tile_class_order = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_stage_x4") == 0) {
-        e->tile_stage_x4 = atoi(value) != 0;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_deinterleave") == 0) {
-        e->tile_deinterleave = atoi(value) != 0;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_sp_begin") == 0) {
-        e->tile_sp_begin = std::max(0, atoi(value));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);   // the LDS layout of the tile launches depends on it
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_min_windows") == 0 || strcmp(key, "tile_end") == 0 || strcmp(key, "tile_min_lanes") == 0 ||
-        strcmp(key, "tile_accept_windows") == 0 || strcmp(key, "tile_max_dwords_per_window") == 0) {
-        const int v = atoi(value);
-        if (v < 0 || v > 65536) {
-            set_error("%s out of range", key);
-            return VJ_ERR_ARG;
-        }
-        (strcmp(key, "tile_max_dwords_per_window") == 0 ? e->tile_max_dwords_per_window
-         : strcmp(key, "tile_min_windows") == 0      ? e->tile_min_windows
-         : strcmp(key, "tile_end") == 0           ? e->tile_end
-         : strcmp(key, "tile_accept_windows") == 0 ? e->tile_accept_windows
-                                                  : e->tile_min_lanes) = v;
-        if (strcmp(key, "tile_end") != 0 && strcmp(key, "tile_min_lanes") != 0) e->tile_thresholds_set = true;   // the caller's choice holds for every frame size
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "plan_cache_max") == 0) {
-        e->plan_cache_max = std::max(2, atoi(value));   // vj_detect_chain holds two plans at once
-        return VJ_OK;
-    }
-    if (strcmp(key, "max_subbatch") == 0) {
-        e->max_subbatch = std::max(0, atoi(value));
-        return VJ_OK;
-    }
-    if (strcmp(key, "det_cap") == 0) {  // (re)sets the detection buffer capacity; it still grows on overflow
-        const int v = atoi(value);
-        if (v < 1) {
-            set_error("det_cap must be >= 1");
-            return VJ_ERR_ARG;
-        }
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        e->det_cap_init = (uint32_t)v;
-        e->lane0.det_cap = 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "gather_waves") == 0) {   // waves per workgroup of the global-gather kernels: 3, 4, or -1 = 4 for calls of >= 8 frames
-        e->gather_waves = atoi(value);
-        return VJ_OK;
-    }
-    if (strcmp(key, "concurrent_blocks_per_cu") == 0) {
-        e->concurrent_blocks_per_cu = std::max(1, atoi(value));
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_split") == 0) {   // one value for every batch size, or "small,mid,large" (<= 4, < 32, >= 32 frames)
-        float a = 0, b = 0, c3 = 0;
-        const int n = sscanf(value, "%f,%f,%f", &a, &b, &c3);
-        if (n == 3) {
-            e->tile_split_small = std::max(0.0f, a);
-            e->tile_split_mid = std::max(0.0f, b);
-            e->tile_split = std::max(0.0f, c3);
-        } else {
-            e->tile_split_small = e->tile_split_mid = e->tile_split = std::max(0.0f, (float)atof(value));
-        }
-        e->tile_split_set = true;      // the caller's values hold: no feedback
-        e->balance.clear();
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "balance_exact") == 0) {
-        e->balance_exact = atoi(value) != 0;
-        e->balance.clear();
-        return VJ_OK;
-    }
-    if (strcmp(key, "balance_export") == 0) return balance_export(e, value);   // value: a file path
-    if (strcmp(key, "balance_import") == 0) return balance_import(e, value);
-    if (strcmp(key, "auto_balance") == 0) {   // 1: find the chain balance of a batch workload from its first calls' times; "reset": start over
-        if (strcmp(value, "reset") == 0) e->tile_split_set = false;
-        else e->auto_balance = atoi(value) != 0;
-        e->balance.clear();
-        return VJ_OK;
-    }
-    if (strcmp(key, "xcd_affinity") == 0) {
-        e->xcd_affinity = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "seg_cut2") == 0) {   // stage trees: second cut inside a long chain, after this many of its stages (0: none)
-        e->seg_cut2 = std::max(0, atoi(value));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_segments") == 0) {
-        e->tile_segments = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "general_prefix") == 0) {
-        e->general_prefix = atoi(value) != 0;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "grid_block_w") == 0) {
-        e->grid_block_w = std::max(0, std::min(atoi(value), (int)UNIT_WINDOWS));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "global_blocks") == 0) {
-        e->global_blocks = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_lds_reserve_kb") == 0) {
-        e->tile_lds_reserve_kb = std::max(0, std::min(atoi(value), 96));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        drop_plans(e);
-        return VJ_OK;
-    }
-    if (strcmp(key, "concurrent") == 0) {  // 1: tile launches and the global first pass overlap on two streams
-        e->concurrent = atoi(value) != 0;
-        return VJ_OK;
-    }
-    if (strcmp(key, "tile_repack") == 0) {  // "3,5": stages before which tiles re-pack ("" = never)
-        unsigned long long m = 0;
-        for (const char* q = value; *q;) {
-            char* endp;
-            long x = strtol(q, &endp, 10);
-            if (endp == q || x < 1 || x > 63) {
-                set_error("tile_repack: expected comma-separated stage indices in [1,63]");
-                return VJ_ERR_ARG;
-            }
-            m |= 1ull << x;
-            q = *endp ? endp + 1 : endp;
-        }
-        e->tile_repack_mask = m;
-        return VJ_OK;
-    }
-    if (strcmp(key, "integral_rows") == 0) {   // integral: see IntegralArgs::rows_mode
-        e->integral_rows_mode = std::max(0, std::min(atoi(value), 2));
-        return VJ_OK;
-    }
-    if (strcmp(key, "blocks_per_cu") == 0) {
-        const int v = atoi(value);
-        if (v < 1 || v > 16) {
-            set_error("blocks_per_cu must be in [1,16]");
-            return VJ_ERR_ARG;
-        }
-        e->blocks_per_cu = v;
-        return VJ_OK;
-    }
-    set_error("unknown option '%s'", key);
-    return VJ_ERR_ARG;
+    return VJ_OK;
 }
 
 int vj_env_reserve(vj_env* e, int max_w, int max_h, int max_batch) {

@@ -165,12 +165,11 @@ struct Lane {
 
 }  // namespace vj
 
-struct vj_env {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    vj::Lane lane0;                  // the batch of a plain vj_detect call
-    hipEvent_t fork_ev = nullptr, join_ev = nullptr;
-    hipStream_t stream2 = nullptr;   // second chain of the first part of the cascade
+namespace vj {
+
+// What vj_env_configure sets, with the shipped values as initialisers: vj_env_create starts from Tunables{} and
+// vj_env_configure(e, "defaults", "") returns to it.  Speed only — results never depend on them.
+struct Tunables {
     int max_subbatch = 0;      // > 0: cap on frames per sub-batch (tests)
     uint32_t det_cap_init = 1u << 16;  // initial capacity of the detection buffer (grows on overflow)
     int concurrent = 1;   // 1: the tile chain and the global-gather chain overlap on two streams
@@ -207,66 +206,16 @@ struct vj_env {
                                         // faster than grid + queue passes on its own, but it overlaps the tile chain badly
     int tile_lds_reserve_kb = 16;       // LDS per CU the tile classes leave to the other chain (its 3-wave workgroup: 12 KiB + granule
                                         // rounding; with 14 the CU's 160 KiB do not take two class-0 blocks next to it any more)
-    char name[256] = "";
-    int n_cu = 0;
-    // image buffers
-    vj::DevBuf d_sum, d_sqsum, d_band_sum, d_band_sq, d_band_sqp;
-    vj::DevBuf d_tilted;            // tilted integral images (OpenCV profile, cascades with tilted features)
-    vj::DevBuf d_tilt_diag, d_tilt_col;   // ... its band totals (launch_tilted_bands)
     bool tilted_bands = true;       // the tilted integral as three banded prefix sums (0: the row-by-row recurrence, one workgroup per frame)
-    vj::DevBuf d_out;               // scratch for device -> host results (vj_grayscale)
-    int slack_w = 0, slack_h = 0, slack_frames = 0;   // layout whose slack rows are known to be zero
-    void *slack_sum = nullptr, *slack_sq = nullptr;
-    // survivor queues + counters + detections
-    vj::DevBuf d_q[vj::MAX_PASSES];   // d_q[p]: windows waiting to enter pass p (p >= 1)
-    vj::DevBuf d_q2[vj::MAX_PASSES];  // stage trees: the tiles' own queue set (enqueue_cascade: split_sets)
-    vj::DevBuf d_skip_bits;           // P2 skip modes: visited-window bitmaps of the frames in flight
-    vj::DevBuf d_run_table;           // band-major queue pass: where every first-pass unit's survivors sit in their sub-queue
-    vj::DevBuf d_rois, d_roi_units, d_roi_det, d_roi_tiles;   // regions of interest on the device (vj_detect_chain)
-    uint32_t roi_tile_cap = 0;
     int roi_tile_min_windows = 512;   // region pass: (region, scale) grids of at least this many windows run on LDS tiles (0: never)
-    vj::DevBuf d_group;                          // scratch of the device-side grouping (vj_detect_chain, min_neighbors != 0)
-    uint32_t roi_unit_cap = 0, roi_det_cap = 0;
-    typedef std::tuple<uint64_t, int, int, int, int, int, int, uint32_t, uint64_t, uint64_t, uint32_t, uint32_t> PlanKey;
-    std::map<PlanKey, std::unique_ptr<vj::Plan>> plans;
-    // Chain balance per workload (cascade, frame size, parameters, batch-size CLASS): how much tile work goes to the
-    // global-gather chain (Plan::tile_split) is found by a short hill climb on the measured cascade time of the workload's
-    // first calls and then frozen; vj_env_configure("tile_split", ...) or ("auto_balance", "0") keep the static values.
-    // The key names the cascade by CONTENT (two loads of one file share an entry; an exported table fits another process)
-    // and the batch size by class (8-15, 16-31, 32-63, >= 64 frames; below 8 — single large frames — the exact count): a
-    // service whose batch sizes vary searches four times, not once per size.  Only calls of the class's reference size
-    // (n_ref: the first size seen, re-anchored when it stops coming) run candidates and feed the search — times are compared
-    // per frame of ONE size —; every other call of the class runs the best split found so far.
-    struct Balance {
-        float cur = 0, best = 0, best_ms = 0, cand_ms = 0;   // (times: ms per frame)
-        int phase = 0;        // 0: measuring the start value, 1: climbing up, 2: climbing down, 3: frozen, 4: measuring the other tile thresholds, 5: probing a whole scale further
-        int samples = 0, moved = 0, calls = 0;
-        int thr = 0;          // 0: the environment's tile thresholds; 1: scales whose tiles hold >= 384 windows go to tiles too
-        bool thr_tried = false, far_tried = false;
-        int n_ref = 0;        // frames per call of the calls that sample
-        int off_ref = 0;      // calls of other sizes since n_ref was last seen
-        bool first_slow = false;   // the candidate's unrated first call was already > 3 % slower than the best
-        uint64_t last_used = 0;    // (least recently used entries go first when the table is full)
-        uint32_t calls_total = 0, calls_on_candidate = 0;   // every call of the workload / those that ran a split other than the best known
-    };
-    typedef std::tuple<PlanKey, int> BalanceKey;    // the plan key with the cascade's content hash and split = 0, batch-size class
-    std::map<BalanceKey, Balance> balance;
-    uint64_t balance_tick = 0;
     bool balance_exact = false;   // key on the exact frame count, as round 3 did ("balance_exact": for the before / after of tools/balance_service.py)
     int balance_class(int n_frames) const {
         return balance_exact || n_frames < 8 ? n_frames : n_frames < 16 ? 8 : n_frames < 32 ? 16 : n_frames < 64 ? 32 : 64;
     }
     bool auto_balance = true, tile_split_set = false;
-    typedef std::tuple<uint64_t, int, int, int, int, uint64_t, int> CvPlanKey;   // cascade uid, W, H, min size, bits of the scale factor, call of <= 4 frames
-    std::map<CvPlanKey, std::unique_ptr<vj::CvPlan>> cv_plans;
-    vj::DevBuf d_cv_det, d_cv_counts;   // vj_detect_opencv: detection list and counters
-    vj::DevBuf d_cv_accept, d_cv_tq;    // ... stage trees on tiles: accept bitmap, the queue of the prefix's survivors
-    vj::DevBuf d_cv_fail_rows, d_cv_fail_walk;   // ... per-wave fail lists of the chain sweeps (rows kernel / chain pass)
-    uint64_t plan_tick = 0;
     int plan_cache_max = 48;      // plans kept per environment; the least recently used one is released beyond that
                                   // (a stream of ROI sizes — eyes inside faces of any size — would otherwise grow
                                   // device tables without bound)
-    // tunables (env vars, read once)
     int integral_rows_mode = 2;      // band_rows: 0 one wave walks a band's chunks, 1 the chunks of a band side by side, 2 side by side except for batches
     int blocks_per_cu = 8;
     int tile_class_kb[vj::TILE_CLASSES] = {-2, -1, 0};  // image-tile LDS budget per class in KiB; -k = what lets k
@@ -302,7 +251,6 @@ struct vj_env {
     bool cv_tree2 = true;             // ... cascades of two-node trees: the row kernel fetches both nodes of a tree at once
     int cv_row_band_px = 128;         // ... the row kernel's rows in band-major order, bands of this many pixels (0: scale after scale)
     bool cv_tree_chains = true;       // ... stage trees made of chains: compacting chain sweeps (0: the per-lane target-stage walk)
-    int cv_tq_shift = 4;              // ... stage trees: the survivors' queue holds 1 / 2^shift of the tile windows (grows on overflow)
     int cv_tree_queue_cap = 0;        // ... stage trees: capacity of the prefix survivors' queue (0: a quarter of the tile windows)
     int cv_tile_min_windows0 = 2048;   // ... the same for the class with two tile workgroups per CU
     int cv_tile_min_windows = -1;     // ... a scale goes to tiles when a tile of at least this many windows fits the LDS (-1: 2048 for stump cascades, 1536 for trees)
@@ -323,6 +271,66 @@ struct vj_env {
     uint32_t pairs_for(int n_frames) const { return gather_pairs >= 0 ? (uint32_t)gather_pairs : n_frames <= 4 ? 2u : 0u; }
     std::vector<int> split_override;
     std::vector<int> pass_cut_nodes{35};    // default pass cuts, in cumulative nodes (profiles/r03_notes.md #6c: 35 beats 150 on four cascades)
+};
+
+}  // namespace vj
+
+struct vj_env : vj::Tunables {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    vj::Lane lane0;                  // the batch of a plain vj_detect call
+    hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+    hipStream_t stream2 = nullptr;   // second chain of the first part of the cascade
+    char name[256] = "";
+    int n_cu = 0;
+    // image buffers
+    vj::DevBuf d_sum, d_sqsum, d_band_sum, d_band_sq, d_band_sqp;
+    vj::DevBuf d_tilted;            // tilted integral images (OpenCV profile, cascades with tilted features)
+    vj::DevBuf d_tilt_diag, d_tilt_col;   // ... its band totals (launch_tilted_bands)
+    vj::DevBuf d_out;               // scratch for device -> host results (vj_grayscale)
+    int slack_w = 0, slack_h = 0, slack_frames = 0;   // layout whose slack rows are known to be zero
+    void *slack_sum = nullptr, *slack_sq = nullptr;
+    // survivor queues + counters + detections
+    vj::DevBuf d_q[vj::MAX_PASSES];   // d_q[p]: windows waiting to enter pass p (p >= 1)
+    vj::DevBuf d_q2[vj::MAX_PASSES];  // stage trees: the tiles' own queue set (enqueue_cascade: split_sets)
+    vj::DevBuf d_skip_bits;           // P2 skip modes: visited-window bitmaps of the frames in flight
+    vj::DevBuf d_run_table;           // band-major queue pass: where every first-pass unit's survivors sit in their sub-queue
+    vj::DevBuf d_rois, d_roi_units, d_roi_det, d_roi_tiles;   // regions of interest on the device (vj_detect_chain)
+    uint32_t roi_tile_cap = 0;
+    vj::DevBuf d_group;                          // scratch of the device-side grouping (vj_detect_chain, min_neighbors != 0)
+    uint32_t roi_unit_cap = 0, roi_det_cap = 0;
+    typedef std::tuple<uint64_t, int, int, int, int, int, int, uint32_t, uint64_t, uint64_t, uint32_t, uint32_t> PlanKey;
+    std::map<PlanKey, std::unique_ptr<vj::Plan>> plans;
+    // Chain balance per workload (cascade, frame size, parameters, batch-size CLASS): how much tile work goes to the
+    // global-gather chain (Plan::tile_split) is found by a short hill climb on the measured cascade time of the workload's
+    // first calls and then frozen; vj_env_configure("tile_split", ...) or ("auto_balance", "0") keep the static values.
+    // The key names the cascade by CONTENT (two loads of one file share an entry; an exported table fits another process)
+    // and the batch size by class (8-15, 16-31, 32-63, >= 64 frames; below 8 — single large frames — the exact count): a
+    // service whose batch sizes vary searches four times, not once per size.  Only calls of the class's reference size
+    // (n_ref: the first size seen, re-anchored when it stops coming) run candidates and feed the search — times are compared
+    // per frame of ONE size —; every other call of the class runs the best split found so far.
+    struct Balance {
+        float cur = 0, best = 0, best_ms = 0, cand_ms = 0;   // (times: ms per frame)
+        int phase = 0;        // 0: measuring the start value, 1: climbing up, 2: climbing down, 3: frozen, 4: measuring the other tile thresholds, 5: probing a whole scale further
+        int samples = 0, moved = 0, calls = 0;
+        int thr = 0;          // 0: the environment's tile thresholds; 1: scales whose tiles hold >= 384 windows go to tiles too
+        bool thr_tried = false, far_tried = false;
+        int n_ref = 0;        // frames per call of the calls that sample
+        int off_ref = 0;      // calls of other sizes since n_ref was last seen
+        bool first_slow = false;   // the candidate's unrated first call was already > 3 % slower than the best
+        uint64_t last_used = 0;    // (least recently used entries go first when the table is full)
+        uint32_t calls_total = 0, calls_on_candidate = 0;   // every call of the workload / those that ran a split other than the best known
+    };
+    typedef std::tuple<PlanKey, int> BalanceKey;    // the plan key with the cascade's content hash and split = 0, batch-size class
+    std::map<BalanceKey, Balance> balance;
+    uint64_t balance_tick = 0;
+    typedef std::tuple<uint64_t, int, int, int, int, uint64_t, int> CvPlanKey;   // cascade uid, W, H, min size, bits of the scale factor, call of <= 4 frames
+    std::map<CvPlanKey, std::unique_ptr<vj::CvPlan>> cv_plans;
+    vj::DevBuf d_cv_det, d_cv_counts;   // vj_detect_opencv: detection list and counters
+    vj::DevBuf d_cv_accept, d_cv_tq;    // ... stage trees on tiles: accept bitmap, the queue of the prefix's survivors
+    vj::DevBuf d_cv_fail_rows, d_cv_fail_walk;   // ... per-wave fail lists of the chain sweeps (rows kernel / chain pass)
+    uint64_t plan_tick = 0;
+    int cv_tq_shift = 4;              // ... stage trees: the survivors' queue holds 1 / 2^shift of the tile windows (grows on overflow)
 };
 
 namespace vj {

@@ -179,7 +179,7 @@ void vj_env_destroy(vj_env* e);
 int  vj_env_reserve(vj_env* e, int max_w, int max_h, int max_batch);
 int  vj_env_device_name(const vj_env* e, char* buf, size_t cap);
 /* Tunables — speed only: results never depend on them (tests sweep every group).  One line per group here; every key
- * with its values, default and the measurement behind the default is in DESIGN.md §7.
+ * with its values, default and the measurement behind the default is in DESIGN.md §7.  Lists are comma-separated.
  *   launch structure   pass_split, pass_cut_nodes, blocks_per_cu, concurrent, concurrent_blocks_per_cu, max_subbatch, det_cap
  *   LDS tiles          tile_classes_kb, tile_lds_reserve_kb, tile_min_windows, tile_accept_windows, tile_end, tile_min_lanes,
  *                      tile_max_dwords_per_window, tile_class_order, tile_lds_nest, tile_repack, tile_deinterleave, tile_stage_x4,
@@ -199,9 +199,14 @@ int  vj_env_device_name(const vj_env* e, char* buf, size_t cap);
  *                      cv_tree_queue_cap (tests)
  *   single frames      one_pass_max_frames (the gather chain in one pass for calls of few large frames; 0 = off)
  *   integral           integral_rows (0 one wave per band of rows, 1 a band's chunks side by side, 2 by call size)
- *   housekeeping       plan_cache_max
+ *   housekeeping       plan_cache_max, defaults (value ignored: every tunable back to what vj_env_create set, the found
+ *                      chain balances and cached plans dropped)
  * Unknown keys return VJ_ERR_ARG.                                               */
 int  vj_env_configure(vj_env* e, const char* key, const char* value);
+/* The current value of a vj_env_configure key, written to buf in the syntax configure accepts (configure(key, query(key))
+ * changes nothing).  VJ_ERR_ARG for unknown keys, for the actions defaults / balance_export / balance_import, and when
+ * cap is too small.                                                              */
+int  vj_env_query(const vj_env* e, const char* key, char* buf, size_t cap);
 
 /* --------------------------------------------------------------- integral */
 /* clifIntegral (clif.h:63-66, clif.cpp:273-285 → cvIntegral layout):

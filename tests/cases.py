@@ -2,6 +2,7 @@
 tests (oracle vs fixtures) and the GPU tests (HIP path vs oracle and vs fixtures)."""
 from __future__ import annotations
 
+import contextlib
 import hashlib
 import lzma
 import os
@@ -239,3 +240,26 @@ def as_stage_tree(c, split_at: int = 4):
             child[parent[i]] = i
     t.stage_parent, t.stage_next, t.stage_child = parent, nxt, child
     return t
+
+
+# vj_env_configure keys, read from the rows of the key table in vj_env.cpp (each row begins with its maker and the key name)
+CONFIGURE_ACTIONS = ("defaults", "balance_export", "balance_import")   # keys that do something rather than hold a value
+
+
+def configure_keys() -> list[str]:
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                            "clfacedetection_amd", "csrc", "vj_env.cpp")).read()
+    return re.findall(r'^\s+(?:flag|int_flag|clamped|bounded|with_auto|int_list|special)\("([a-z0-9_]+)"', src, re.M)
+
+
+@contextlib.contextmanager
+def tunables(env, *settings):
+    """with tunables(env, ("tile_split", "1"), ...): apply the settings in order; on exit every tunable goes back to its
+    default (configure("defaults", "")), whatever the body did."""
+    try:
+        for k, v in settings:
+            env.configure(k, v)
+        yield env
+    finally:
+        env.configure("defaults", "")

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from cases import DETECT_CASES, HEADLINE_CASE, make_frame, sha
+from cases import DETECT_CASES, HEADLINE_CASE, make_frame, sha, tunables
 from clfacedetection_amd import (VJ_FLAG_COUNTERS, VJ_FLAG_SIGNED_MEAN, DeviceFrames, clodDetectObjects,
                                  default_params, synth)
 
@@ -111,7 +111,7 @@ def test_band_major_queue_pass_equals_the_chunked_one(env, oracle, cascades):
     counts that do not divide by the eight queue parts; a batch below the switch-over keeps the chunked pass."""
     c, a = cascades("frontalface_alt")
     p = default_params(flags=VJ_FLAG_COUNTERS)
-    try:
+    with tunables(env):
         for n_frames, (h, w) in ((11, (300, 420)), (8, (480, 640)), (3, (270, 500))):
             frames = synth.batch(n_frames, h, w, seed0=333, kinds=("noise", "faces", "blocks"))
             env.configure("q_band_px", 0)
@@ -132,11 +132,6 @@ def test_band_major_queue_pass_equals_the_chunked_one(env, oracle, cascades):
                     assert [sum(l["stage_entered"][s] for l in r.launches) for s in range(len(r.stage_entered))] == r.stage_entered
                     r2 = env.detect(c, frames)          # the timed (uncounted) kernel variants
                     assert np.array_equal(r2.rects, base.rects)
-    finally:
-        env.configure("q_band_px", 128)
-        env.configure("q_group_units", 8)
-        env.configure("q_band_min_frames", 8)
-        env.configure("tile_split", "0,1.75,2")
 
 
 def test_pass_split_and_occupancy_do_not_change_results(env, cascades):
@@ -144,28 +139,27 @@ def test_pass_split_and_occupancy_do_not_change_results(env, cascades):
     frames = synth.batch(2, 480, 640, seed0=70)
     p = default_params(flags=VJ_FLAG_COUNTERS)
     base = env.detect(c, frames, p)
-    try:
+    with tunables(env):
         for split in ("1", "2,3,5,8,13", "21", "4,9,15", "0"):
             env.configure("pass_split", split)
             r = env.detect(c, frames, p)
             assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, split
-        env.configure("pass_split", "")
+        env.configure("defaults", "")
         for b in (1, 3, 16):
             env.configure("blocks_per_cu", b)
             r = env.detect(c, frames, p)
             assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, b
-        env.configure("blocks_per_cu", 8)
+        env.configure("defaults", "")
         env.configure("thin_pass_spread", 0)       # every workgroup of a queue pass draws tickets / only the first ones do
         r = env.detect(c, frames, p)
         assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered
-        env.configure("thin_pass_spread", 1)
+        env.configure("defaults", "")
         for de, x4 in ((0, 1), (0, 0), (1, 0)):
             env.configure("tile_deinterleave", de)
             env.configure("tile_stage_x4", x4)
             r = env.detect(c, frames, p)
             assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, (de, x4)
-        env.configure("tile_deinterleave", 1)
-        env.configure("tile_stage_x4", 1)
+        env.configure("defaults", "")
         for conc, reserve, blocks, split, gbw in ((0, 26, 1, 0, 32), (0, 0, 0, 0.4, 0), (1, 0, 1, 1.3, 32), (1, 40, 0, 2.5, 16),
                                                   (1, 26, 0, 0.7, 64), (1, 26, 0, 99, 32)):
             env.configure("concurrent", conc)
@@ -176,11 +170,7 @@ def test_pass_split_and_occupancy_do_not_change_results(env, cascades):
             r = env.detect(c, frames, p)
             assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, (conc, reserve, blocks, split)
             assert [sum(l["stage_entered"][s] for l in r.launches) for s in range(len(r.stage_entered))] == r.stage_entered
-        env.configure("concurrent", 1)
-        env.configure("tile_lds_reserve_kb", 16)
-        env.configure("global_blocks", 0)
-        env.configure("tile_split", "0,1.75,2")
-        env.configure("grid_block_w", 32)
+        env.configure("defaults", "")
         # LDS-tile path off / small / large tiles / shallow / deep: the tile and the
         # global-gather paths agree bit for bit
         for classes, tile_end, minw in (("0,0,0", 10, 1024), ("24,40,60", 3, 1024), ("36,64,140", 10, 1024),
@@ -199,23 +189,6 @@ def test_pass_split_and_occupancy_do_not_change_results(env, cascades):
                 r = env.detect(c, frames, p)
                 assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, \
                     (classes, tile_end, minw, split)
-    finally:
-        env.configure("concurrent", 1)
-        env.configure("tile_lds_reserve_kb", 16)
-        env.configure("global_blocks", 0)
-        env.configure("tile_split", "0,1.75,2")
-        env.configure("grid_block_w", 32)
-        env.configure("pass_split", "")
-        env.configure("blocks_per_cu", 8)
-        env.configure("tile_classes_kb", "-2,-1,0")
-        env.configure("tile_end", 64)
-        env.configure("tile_min_windows", 768)
-        env.configure("tile_min_lanes", 0)
-        env.configure("tile_repack", ",".join(str(i) for i in range(2, 22)))
-        env.configure("tile_sp_begin", 3)
-        env.configure("tile_sp_max", 192)
-        env.configure("tile_finish", 1)
-        env.configure("tile_ws_max", 512)
 
 
 @pytest.mark.parametrize("casc", ["frontalface_alt", "frontalface_alt2"])
@@ -227,10 +200,9 @@ def test_finish_variants_agree(env, cascades, casc):
     frames = np.stack([make_frame("noise", 31, 540, 960), make_frame("smooth", 32, 540, 960),
                        make_frame("blocks", 33, 540, 960)])
     p = default_params(flags=VJ_FLAG_COUNTERS)
-    try:
-        env.configure("tile_sp_begin", 99)
+    with tunables(env, ("tile_sp_begin", 99)):
         base = env.detect(c, frames, p)
-        env.configure("tile_sp_begin", 3)
+        env.configure("defaults", "")
         env.configure("tile_classes_kb", "0,0,0")   # no LDS tiles: every scale runs as grid pass + queue passes
         r = env.detect(c, frames, p)
         assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered
@@ -238,8 +210,7 @@ def test_finish_variants_agree(env, cascades, casc):
         r = env.detect(c, frames, p)
         assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered
         assert [l["kind"] for l in r.launches] == (["block"] if casc == "frontalface_alt" else ["grid", "queue"])
-        env.configure("global_blocks", 0)
-        env.configure("tile_classes_kb", "-2,-1,0")
+        env.configure("defaults", "")
         for finish, begin, ws_max, sp_max, ws_min in ((1, 3, 512, 192, 32), (1, 1, 512, 192, 0), (1, 2, 200, 192, 100),
                                                       (1, 5, 64, 192, 8), (1, 3, 512, 192, 256), (0, 3, 512, 192, 32),
                                                       (0, 4, 512, 256, 32)):
@@ -250,14 +221,6 @@ def test_finish_variants_agree(env, cascades, casc):
             env.configure("tile_sp_max", sp_max)
             r = env.detect(c, frames, p)
             assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, (finish, begin, ws_max)
-    finally:
-        env.configure("global_blocks", 0)
-        env.configure("tile_classes_kb", "-2,-1,0")
-        env.configure("tile_finish", 1)
-        env.configure("tile_sp_begin", 3)
-        env.configure("tile_ws_max", 512)
-        env.configure("tile_ws_min", 48)
-        env.configure("tile_sp_max", 192)
 
 
 def test_scale_mask_partitions_the_result(env, cascades):
@@ -369,18 +332,14 @@ def test_config4_4096_alt_tree(env, oracle, cascades):
     assert as_list(r1.rects[r1.rects["w"] >= 900]) == as_list(ro)
     # the linear prefix of the stage tree (stages 0..4) on the linear kernels + general pass from its queue == the
     # one-pass general kernel
-    try:
-        env.configure("general_prefix", 0)
+    with tunables(env, ("general_prefix", 0)):
         r0 = env.detect(c, img, p)
         assert [l["kind"] for l in r0.launches] == ["grid"] and len(r1.launches) > 3     # prefix + the two chains' passes
         assert np.array_equal(r0.rects, r1.rects) and r0.stage_entered == r1.stage_entered
-        env.configure("general_prefix", 1)
+        env.configure("defaults", "")
         env.configure("tile_segments", 0)        # tiles hand over after the prefix instead of running the chains
         r2 = env.detect(c, img, p)
         assert np.array_equal(r2.rects, r1.rects) and r2.stage_entered == r1.stage_entered
-    finally:
-        env.configure("general_prefix", 1)
-        env.configure("tile_segments", 1)
 
 
 def test_config5_two_cascades_on_rois(env, oracle, cascades):
@@ -441,16 +400,11 @@ def test_subbatching_and_detection_buffer_growth(env, cascades):
     p = default_params(flags=VJ_FLAG_COUNTERS)
     base = env.detect(c, frames, p)
     assert len(base.rects) >= 3
-    try:
-        env.configure("max_subbatch", 3)
-        env.configure("det_cap", 1)
+    with tunables(env, ("max_subbatch", 3), ("det_cap", 1)):
         r = env.detect(c, frames, p)
         assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered
         r = env.detect(c, frames, default_params())
         assert np.array_equal(r.rects, base.rects)
-    finally:
-        env.configure("max_subbatch", 0)
-        env.configure("det_cap", 65536)
 
 
 def test_native_library_is_the_one_running(env):
@@ -538,7 +492,7 @@ def test_balance_is_keyed_by_batch_size_class_and_travels(env, cascades, tmp_pat
     frames = synth.batch(20, 360, 640, seed0=300)
     env.configure("auto_balance", "reset")
     env.configure("auto_balance", "1")
-    try:
+    with tunables(env):
         want12 = env.detect(c, frames[:12])
         r = want12
         for _ in range(60):
@@ -565,8 +519,6 @@ def test_balance_is_keyed_by_batch_size_class_and_travels(env, cascades, tmp_pat
                 e2.configure("balance_import", str(tmp_path / "missing.txt"))
         finally:
             e2.close()
-    finally:
-        env.configure("auto_balance", "reset")
 
 
 def test_chain_balance_feedback_does_not_change_results(env, oracle, cascades):
@@ -587,19 +539,14 @@ def test_chain_balance_feedback_does_not_change_results(env, oracle, cascades):
     assert r.balance_state == 2 and 0 < r.balance_calls <= 45      # the search reports itself: finished, within its budget of measured calls
     ro, _ = oracle.detect(a, frames[5])
     assert as_list(first.rects[first.rects["frame"] == 5]) == as_list(ro)
-    env.configure("tile_split", "0,1.75,2")             # static values: the feedback is off
-    try:
-        assert {env.detect(c, frames).tile_split for _ in range(7)} == {1.75}      # (12 frames: the value for 8 .. 31)
+    with tunables(env, ("tile_split", "0,1.25,2")):     # static values: the feedback is off
+        assert {env.detect(c, frames).tile_split for _ in range(7)} == {1.25}      # (12 frames: the value for 8 .. 31)
         assert np.array_equal(env.detect(c, frames).rects, first.rects)
-    finally:
-        env.configure("auto_balance", "reset")
     # a pyramid with ONE tile scale (frontalface_alt, min size 66: the 69-px scale runs on tiles, everything above on gathers) and
     # a search that starts with that scale moved to the gather chain: a one-chain plan.  The search measures it like any other
     # candidate and goes on (up, then back below the start) — it used to end on such a plan, whatever it cost.
     alt, _ = cascades("frontalface_alt")
-    env.configure("tile_split", "1.0")
-    env.configure("auto_balance", "reset")               # feedback on again, the start values stay
-    try:
+    with tunables(env, ("tile_split", "1.0"), ("auto_balance", "reset")):   # feedback on again, the start values stay
         p = default_params(min_w=66, min_h=66)
         ref = env.detect(alt, frames, p)
         assert ref.tile_split == 1.0 and not any(l["kind"] == "tile" for l in ref.launches)
@@ -609,9 +556,6 @@ def test_chain_balance_feedback_does_not_change_results(env, oracle, cascades):
             assert np.array_equal(r.rects, ref.rects)
             seen.append(r.tile_split)
         assert len(set(seen[-6:])) == 1 and len(set(seen)) >= 3, seen
-    finally:
-        env.configure("tile_split", "0,1.75,2")
-        env.configure("auto_balance", "reset")
     # vj_detect_chain searches the balance of its first cascade the same way: same two results in every call of the search
     eye, _ = cascades("eye")
     c1, c2 = env.detect_chain(c, eye, frames)
@@ -635,4 +579,4 @@ def test_chain_balance_feedback_does_not_change_results(env, oracle, cascades):
     del big
     # a share of the scales (a mask) starts without a move: the default is a fraction of the last tile scale of a WHOLE pyramid
     assert env.detect(c, frames, default_params(scales=[0, 1, 20, 21])).tile_split == 0.0
-    env.configure("auto_balance", "reset")
+    env.configure("defaults", "")

@@ -3,7 +3,7 @@ tempcv.cpp (oc_detect_opencvlike).  OpenCV itself cannot be run here: parity unp
 import numpy as np
 import pytest
 
-from cases import make_frame
+from cases import make_frame, tunables
 from clfacedetection_amd import VJ_FLAG_COUNTERS, cvHaarDetectObjects, synth
 
 pytestmark = pytest.mark.gpu
@@ -100,8 +100,7 @@ def test_tilted_integral_and_gray_image(env, oracle, bands):
     BGR input and the 32-bit wrap-around included — with both kernels: the three banded prefix sums (default) and the row-by-row
     recurrence (`tilted_bands` = 0)."""
     rng = np.random.default_rng(5)
-    env.configure("tilted_bands", bands)
-    try:
+    with tunables(env, ("tilted_bands", bands)):
         for (h, w) in [(1, 1), (3, 5), (2, 9), (9, 2), (8, 8), (17, 1), (1, 40), (64, 300), (251, 333), (480, 640), (1080, 1920)]:
             img = rng.integers(0, 256, (h, w), dtype=np.uint8)
             assert np.array_equal(env.integral_tilted(img), oracle.integral_tilted(img)), (h, w)
@@ -112,8 +111,6 @@ def test_tilted_integral_and_gray_image(env, oracle, bands):
         g = oracle.bgr2gray(bgr)
         assert np.array_equal(env.grayscale(bgr), g)
         assert np.array_equal(env.integral_tilted(bgr), oracle.integral_tilted(g))
-    finally:
-        env.configure("tilted_bands", 1)
     bgra = rng.integers(0, 256, (77, 131, 4), dtype=np.uint8)
     assert np.array_equal(env.grayscale(bgra[20:60, 10:100]), oracle.bgr2gray(np.ascontiguousarray(bgra[20:60, 10:100])))
 
@@ -151,12 +148,9 @@ def test_color_frames_subbatches_and_many_detections(env, oracle, cascades):
     assert len(base.rects) > 100
     r = env.detect_opencv(c, col, flags=VJ_FLAG_COUNTERS, color=True)
     assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered
-    try:
-        env.configure("max_subbatch", 2)
+    with tunables(env, ("max_subbatch", 2)):
         r2 = env.detect_opencv(c, gray, flags=VJ_FLAG_COUNTERS)
         assert np.array_equal(r2.rects, base.rects) and r2.stage_entered == base.stage_entered and r2.windows == base.windows
-    finally:
-        env.configure("max_subbatch", 0)
     ro, st = oracle.detect_opencvlike(a, gray[0])
     assert sorted(rows(base.rects[base.rects["frame"] == 0])) == sorted(rows(ro))
 
@@ -197,15 +191,12 @@ def test_plan_cache_of_the_profile(env, oracle, cascades):
     w4, _ = oracle.detect_opencvlike(a2, img)
     assert sorted(rows(env.detect_opencv(c2, img).rects)) == sorted(rows(w4))
     assert sorted(rows(env.detect_opencv(c, img).rects)) == sorted(rows(want))
-    env.configure("plan_cache_max", 4)
-    try:
+    with tunables(env, ("plan_cache_max", 4)):
         for k in range(12):                                   # more sizes than the cache holds
             sub = np.ascontiguousarray(img[:200 + 5 * k, :300 + 7 * k])
             ws, _ = oracle.detect_opencvlike(a, sub)
             assert sorted(rows(env.detect_opencv(c, sub).rects)) == sorted(rows(ws)), k
         assert sorted(rows(env.detect_opencv(c, img).rects)) == sorted(rows(want))
-    finally:
-        env.configure("plan_cache_max", 48)
 
 
 
@@ -234,11 +225,8 @@ def test_lds_tile_path_equals_the_row_kernel_and_the_oracle(env, oracle, cascade
     frames = np.stack([make_frame(kind, seed + i, h, w, oracle) for i in range(batch)])
     tiled = env.detect_opencv(c, frames, flags=VJ_FLAG_COUNTERS)
     plain_tiled = env.detect_opencv(c, frames)
-    try:
-        env.configure("cv_tiles", 0)
+    with tunables(env, ("cv_tiles", 0)):
         rows_only = env.detect_opencv(c, frames, flags=VJ_FLAG_COUNTERS)
-    finally:
-        env.configure("cv_tiles", 1)
     assert np.array_equal(tiled.rects, rows_only.rects) and np.array_equal(plain_tiled.rects, tiled.rects)
     assert tiled.windows == rows_only.windows and tiled.stage_entered == rows_only.stage_entered
     entered = np.zeros(len(tiled.stage_entered), np.int64)
@@ -250,18 +238,10 @@ def test_lds_tile_path_equals_the_row_kernel_and_the_oracle(env, oracle, cascade
         vis += st["windows"]
     assert tiled.stage_entered == entered.tolist() and tiled.windows == vis
     if casc == "frontalface_alt_tree":       # more prefix survivors than the tree queue holds: the call falls back to the rows
-        try:
-            env.configure("cv_tree_queue_cap", 16)
+        with tunables(env, ("cv_tree_queue_cap", 16)):
             assert np.array_equal(env.detect_opencv(c, frames).rects, tiled.rects)
-        finally:
-            env.configure("cv_tree_queue_cap", 0)
-    defaults = {"cv_tile_ws_max": 512, "cv_tile_min_windows": -1, "cv_tile_min_windows0": 2048, "cv_row_blocks": -1, "concurrent": 1, "cv_row_band_px": 128, "cv_tree2": 1, "cv_tiles_tilted": 1}
     for setting in ({"cv_tile_ws_max": 64}, {"cv_tile_ws_max": 0}, {"cv_tile_min_windows": 64, "cv_tile_min_windows0": 64}, {"cv_row_band_px": 0}, {"cv_row_band_px": 40}, {"cv_tree2": 0}, {"cv_tiles_tilted": 0},
                     {"cv_row_blocks": 1, "cv_tile_min_windows0": 512, "cv_tile_min_windows": 512}, {"concurrent": 0}):
-        try:                         # finish thresholds, small tiles of both LDS classes, other occupancies, one stream: same result
-            for key, val in setting.items():
-                env.configure(key, val)
+        # finish thresholds, small tiles of both LDS classes, other occupancies, one stream: same result
+        with tunables(env, *setting.items()):
             assert np.array_equal(env.detect_opencv(c, frames).rects, tiled.rects), setting
-        finally:
-            for key in setting:
-                env.configure(key, defaults[key])

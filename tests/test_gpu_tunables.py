@@ -1,0 +1,145 @@
+"""vj_env_configure / vj_env_query: every key of the table round-trips, parses and bounds its values as specified below,
+and "defaults" returns an environment to what vj_env_create left."""
+import pytest
+
+from cases import CONFIGURE_ACTIONS, configure_keys
+from clfacedetection_amd import Environment, VjError, synth
+
+ERR = None   # expected: VJ_ERR_ARG, the value stays what it was
+MAX = None   # no upper / lower bound
+
+# scalar keys: (kind, lo, hi).  bool: atoi != 0; clamp: atoi clamped to [lo, hi]; range: atoi, VJ_ERR_ARG outside [lo, hi];
+# auto: -1 for negative values, else clamped to [lo, hi]
+SCALARS = {
+    **{k: ("bool", 0, 1) for k in (
+        "tile_finish", "tile_lds_nest", "tree_split_queues", "cv_pairs", "tilted_bands", "cv_tiles_tilted", "cv_tree2",
+        "cv_tree_chains", "rois_on_device", "cv_tiles", "thin_pass_spread", "tile_class_order", "tile_stage_x4",
+        "tile_deinterleave", "balance_exact", "xcd_affinity", "tile_segments", "general_prefix", "global_blocks", "concurrent")},
+    "tile_ws_min": ("clamp", 0, 256), "tile_ws_max": ("clamp", 0, 512), "tile_sp_max": ("clamp", 0, 256),
+    "q_band_px": ("clamp", 0, MAX), "q_group_units": ("clamp", 0, MAX), "q_band_min_frames": ("clamp", 1, MAX),
+    "cv_tail_max": ("clamp", 0, 64), "cv_tree_chunk": ("clamp", 1, MAX), "cv_tree_chain_blocks": ("clamp", 1, MAX),
+    "one_pass_max_frames": ("clamp", 0, MAX), "cv_row_band_px": ("clamp", 0, MAX), "cv_tree_queue_cap": ("clamp", 0, MAX),
+    "roi_tiles": ("clamp", 0, MAX), "cv_tile_ws_max": ("clamp", 0, 512), "cv_tile_min_windows0": ("clamp", 64, MAX),
+    "cv_row_blocks_tree": ("clamp", 1, 4), "cv_tile_min_windows_tree": ("clamp", 64, MAX), "min_chunk": ("clamp", 1, 64),
+    "group_max": ("clamp", 1, 2048), "sp_tail_max": ("clamp", 0, 48), "tile_sp_begin": ("clamp", 0, MAX),
+    "plan_cache_max": ("clamp", 2, MAX), "max_subbatch": ("clamp", 0, MAX), "concurrent_blocks_per_cu": ("clamp", 1, MAX),
+    "seg_cut2": ("clamp", 0, MAX), "grid_block_w": ("clamp", 0, 512), "tile_lds_reserve_kb": ("clamp", 0, 96),
+    "integral_rows": ("clamp", 0, 2), "gather_waves": ("clamp", MAX, MAX),
+    "cv_row_blocks": ("auto", 1, 4), "cv_tile_min_windows": ("auto", 64, MAX), "wide_tail": ("auto", 0, 1),
+    "q_slices": ("auto", 0, 64), "gather_pairs": ("auto", 0, 2),
+    **{k: ("range", 0, 65536) for k in ("tile_min_windows", "tile_end", "tile_min_lanes", "tile_accept_windows",
+                                        "tile_max_dwords_per_window")},
+    "blocks_per_cu": ("range", 1, 16),
+}
+
+# the other keys: (value, expected query after it, or ERR)
+LISTED = {
+    "pass_split": [("4,9", "4,9"), ("4, 9,", "4,9"), ("-3,100", "-3,100"), ("", ""), ("4,,9", ERR), ("abc", ERR)],
+    "pass_cut_nodes": [("35,150", "35,150"), ("7", "7"), ("-1", "-1"), ("", ""), ("35;150", ERR), ("x", ERR)],
+    "tile_classes_kb": [("36,64,140", "36,64,140"), ("-4,0,140", "-4,0,140"), ("1,2", "1,2,0"), ("", "0,0,0"),
+                        ("1,2,3,abc", "1,2,3"), ("141", ERR), ("-5", ERR), ("abc", ERR)],
+    "tile_repack": [("3,5", "3,5"), ("5,3", "3,5"), ("1,63", "1,63"), ("", ""), ("0", ERR), ("64", ERR), ("x", ERR)],
+    "tile_split": [("0.5,1,1.5", "0.5,1,1.5"), ("1.25", "1.25,1.25,1.25"), ("0,-2,3", "0,0,3"), ("1,2", "1,1,1"),
+                   ("-1", "0,0,0"), ("abc", "0,0,0")],
+    "det_cap": [("1000", "1000"), ("1", "1"), ("0", ERR), ("-4", ERR), ("abc", ERR)],
+    "auto_balance": [("0", "0"), ("reset", "0"), ("7", "1"), ("abc", "0"), ("1", "1")],
+}
+
+
+def _clamp(v, lo, hi):
+    return max(lo if lo is not None else v, min(v, hi if hi is not None else v))
+
+
+def cases(key):
+    """(value, expected query or ERR) for one key: in-range values, values beyond each bound, malformed values."""
+    if key in LISTED:
+        return LISTED[key]
+    kind, lo, hi = SCALARS[key]
+    if kind == "bool":
+        return [("0", "0"), ("1", "1"), ("7", "1"), ("-2", "1"), ("abc", "0"), ("1x", "1"), ("0", "0")]
+    mid = (lo + hi) // 2 if lo is not None and hi is not None else (lo if lo is not None else 0) + 3
+    out = [(str(mid), str(mid))]
+    for v in ([lo - 1] if lo is not None else []) + ([hi + 1] if hi is not None else []) + [0, 12, -5]:
+        if kind == "range":
+            out.append((str(v), str(v) if lo <= v <= hi else ERR))
+        elif kind == "auto" and v < 0:
+            out.append((str(v), "-1"))
+        else:
+            out.append((str(v), str(_clamp(v, lo, hi))))
+    r = _clamp(0, lo, hi) if kind != "range" else 0
+    out += [("abc", str(r) if kind != "range" or lo <= 0 <= hi else ERR), (f"{mid}abc", str(mid))]
+    return out
+
+
+def snapshot(e):
+    return {k: e.query(k) for k in configure_keys() if k not in CONFIGURE_ACTIONS}
+
+
+@pytest.fixture
+def fresh():
+    e = Environment(0)
+    yield e
+    e.close()
+
+
+def test_the_spec_covers_the_table():
+    keys = configure_keys()
+    assert len(keys) == len(set(keys)) and len(keys) > 50
+    assert sorted(set(keys) - set(CONFIGURE_ACTIONS)) == sorted(list(SCALARS) + list(LISTED))
+
+
+@pytest.mark.gpu
+def test_every_key_round_trips(fresh):
+    before = snapshot(fresh)
+    for k, v in before.items():
+        fresh.configure(k, v)
+        assert snapshot(fresh) == before, k
+
+
+@pytest.mark.gpu
+def test_every_key_parses_and_bounds_its_values(fresh):
+    before = snapshot(fresh)
+    for k, v0 in before.items():
+        cur = v0
+        for value, want in cases(k):
+            if want is ERR:
+                with pytest.raises(VjError) as ei:
+                    fresh.configure(k, value)
+                assert ei.value.code == 1, (k, value)
+            else:
+                fresh.configure(k, value)
+                cur = want
+            assert fresh.query(k) == cur, (k, value)
+        fresh.configure(k, v0)
+        assert snapshot(fresh) == before, k     # a key moves its own value only
+    for k in ("no_such_key", *CONFIGURE_ACTIONS):
+        with pytest.raises(VjError):
+            fresh.query(k)
+    with pytest.raises(VjError):
+        fresh.configure("no_such_key", "1")
+
+
+@pytest.mark.gpu
+def test_list_keys_take_commas_only(fresh):
+    for k, v in (("pass_split", "4;9"), ("pass_cut_nodes", "4;9"), ("tile_repack", "3;5"), ("tile_classes_kb", "1;2")):
+        before = fresh.query(k)
+        with pytest.raises(VjError):
+            fresh.configure(k, v)
+        assert fresh.query(k) == before, k
+
+
+@pytest.mark.gpu
+def test_defaults_return_every_key_to_a_fresh_environment(fresh, cascades):
+    shipped = snapshot(fresh)
+    for k, v0 in shipped.items():
+        fresh.configure(k, next(v for v, want in cases(k) if want not in (ERR, v0)))
+    assert all(v != shipped[k] for k, v in snapshot(fresh).items())
+    fresh.configure("defaults", "")
+    assert snapshot(fresh) == shipped
+    # a hand-set tile_split switches the chain-balance feedback off; "defaults" switches it on again
+    c, _ = cascades("frontalface_alt")
+    frames = synth.batch(8, 240, 320, seed0=5)
+    fresh.configure("tile_split", "1")
+    assert fresh.detect(c, frames).balance_state == 0
+    fresh.configure("defaults", "")
+    assert fresh.detect(c, frames).balance_state == 1
