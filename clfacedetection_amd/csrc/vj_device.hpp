@@ -42,8 +42,15 @@ struct ScaleDev {
     float    scale_f;      // s_k itself, and the scaled window: what a region of interest needs to lay out its own grid
     uint32_t win_w, win_h; // ... (setupScale, clod.cpp:371-415, evaluated on the device per region: roi_plan_units)
     uint32_t pos_base;     // != 0: window positions of this scale come from CascadeArgs::pos_tab[pos_base + index] (VJ_FLAG_GRID_F64)
+    // Scale group of the tile kernel (consecutive step-2 de-interleaved scales that share one staged tile, laid out as the
+    // group's largest scale lays out its own): this scale's NodeRec table and equ_rect offsets in the GROUP's pitch / half.
+    // Equal to tile_table_first / te_* when the scale is not grouped or is the group's largest; the ROI pass uses its own.
+    uint32_t grp_table_first;
+    uint32_t grp_te_lt;
+    uint32_t grp_te_dh;
+    int32_t  grp_te_dw;
 };
-static_assert(sizeof(ScaleDev) == 128, "ScaleDev is 128 bytes");
+static_assert(sizeof(ScaleDev) == 144, "ScaleDev is 144 bytes");
 
 // One cascade stage with its resolved successors (tempcv.cpp:834-861 flattened).
 struct StageDev {
@@ -66,7 +73,7 @@ static_assert(sizeof(StageDev) == 48, "StageDev is 48 bytes");
 struct UnitDev {
     uint32_t scale;        // index into ScaleDev[]
     uint32_t first;        // first window index (row-major in the scale's grid), or ix0 | iy0 << 16 of a 2-D block
-    uint32_t count;        // <= UNIT_WINDOWS (2-D block: width * height)
+    uint32_t count;        // <= UNIT_WINDOWS (2-D block: width * height); staged tile: > 1 = a scale group of this many scales from `scale` on
     uint32_t bw;           // 0: a run of consecutive windows; else the width of a 2-D block of windows
 };
 

@@ -152,6 +152,7 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
     const uint32_t tile_header_bytes = TILE_LDS_HEADER + pl->sp_pad * 4u;
     std::vector<NodeRec> table;
     std::vector<uint32_t> pos_tab;
+    std::vector<std::pair<uint32_t, uint32_t>> tile_reach;   // per scale: how far right / down of a window origin its features read
     for (const vj_scale_info& si : pl->scales_all) {
         if (!si.accepted || si.nx <= 0 || si.ny <= 0) continue;
         if ((p.scale_mask[0] | p.scale_mask[1]) != 0) {  // scale subset (multi-GPU sharding of one frame)
@@ -278,6 +279,10 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
             sd.te_dh = (uint32_t)si.equ_h * sd.tile_pitch;
             sd.tiles_x = (sd.nx + sd.tile_tw - 1) / sd.tile_tw;
             sd.tile_row_end = sd.ny;
+            sd.grp_table_first = sd.tile_table_first;
+            sd.grp_te_lt = sd.te_lt;
+            sd.grp_te_dh = sd.te_dh;
+            sd.grp_te_dw = sd.te_dw;
         } else {
             // unstaged in the tile kernel (global_blocks): 2-D blocks of <= 2048 windows, about as wide as high
             sd.tile_tw = std::min<uint32_t>(sd.nx, 48u);
@@ -286,10 +291,47 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
         }
         pl->scales.push_back(sd);
         pl->scales_info.push_back(si);
+        tile_reach.push_back({reach_x, reach_y});
     }
     if (pl->max_reach_elems >= pl->frame_elems) {
         set_error("feature reach %u exceeds the frame allocation %u", pl->max_reach_elems, pl->frame_elems);
         return VJ_ERR_LIMIT;
+    }
+    // Scale groups: up to tile_group consecutive step-2 de-interleaved tile scales share ONE staged tile.  Their window
+    // origins lie on the same lattice (x = 2 ix, y = 2 iy), so the tile the group's largest scale lays out for itself (shape
+    // search above: its windows reach furthest) holds every member's windows at the same tile-local offsets; each member
+    // gets a NodeRec table and equ_rect offsets in that pitch / half.  The members' own tile fields stay for the ROI pass.
+    pl->tile_lead.resize(pl->scales.size());
+    for (uint32_t slot = 0; slot < pl->scales.size(); ++slot) pl->tile_lead[slot] = slot;
+    auto groupable = [&](uint32_t k) {
+        const ScaleDev& sd = pl->scales[k];
+        return sd.tile_rw != 0u && sd.tile_half != 0u && sd.step == 2.0f;
+    };
+    for (uint32_t g0 = 0; e->tile_group > 1 && g0 < pl->scales.size();) {
+        if (!groupable(g0)) { ++g0; continue; }
+        // members in scale order, as long as the reach does not shrink (the last member's tile then covers them all)
+        uint32_t g1 = g0 + 1;
+        while (g1 < pl->scales.size() && g1 - g0 < (uint32_t)e->tile_group && groupable(g1) &&
+               tile_reach[g1].first >= tile_reach[g1 - 1].first && tile_reach[g1].second >= tile_reach[g1 - 1].second)
+            ++g1;
+        const uint32_t lead = g1 - 1;
+        const ScaleDev& L = pl->scales[lead];
+        for (uint32_t k = g0; k < lead; ++k) {
+            ScaleDev& sd = pl->scales[k];
+            const vj_scale_info& si = pl->scales_info[k];
+            sd.grp_table_first = (uint32_t)table.size();
+            table.resize(table.size() + n_nodes);
+            int rc = build_node_table_stride(c, L.tile_pitch, si, table.data() + sd.grp_table_first, L.tile_half);
+            if (rc) return rc;
+            auto col = [&](uint32_t cx) { return (cx & 1u) * L.tile_half + (cx >> 1); };
+            sd.grp_te_lt = (uint32_t)si.equ_y * L.tile_pitch + col((uint32_t)si.equ_x);
+            sd.grp_te_dw = (int32_t)col((uint32_t)(si.equ_x + si.equ_w)) - (int32_t)col((uint32_t)si.equ_x);
+            sd.grp_te_dh = (uint32_t)si.equ_h * L.tile_pitch;
+            pl->tile_lead[k] = lead;
+        }
+        if (getenv("VJ_DEBUG_PLAN") && lead > g0)
+            fprintf(stderr, "vj plan: scales %u..%u share the tile of scale %u\n", pl->scales[g0].scale_idx, L.scale_idx, L.scale_idx);
+        g0 = g1;
     }
     for (size_t s = 0; s < c.stages.size(); ++s) {
         StageDev sd;
@@ -343,7 +385,8 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
             const double move = std::min(1.0, remaining);
             remaining -= move;
             const uint32_t keep_rows = (uint32_t)((double)sd.ny * (1.0 - move));
-            sd.tile_row_end = keep_rows / sd.tile_th * sd.tile_th;
+            const uint32_t th = pl->scales[pl->tile_lead[k]].tile_th;   // (the group's tile rows)
+            sd.tile_row_end = keep_rows / th * th;
         }
     }
     // first-pass units of the global-gather path: whole scales, and the rows of split scales the tiles leave
@@ -474,12 +517,20 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
     for (uint32_t cls = 0; cls < TILE_CLASSES; ++cls) {
         pl->class_first[cls] = (uint32_t)pl->tile_units.size();
         for (uint32_t slot = 0; slot < pl->scales.size(); ++slot) {
-            ScaleDev& sd = pl->scales[slot];
-            if (!sd.tile_rw || sd.tile_class != cls) continue;
-            for (uint32_t iy0 = 0; iy0 < sd.tile_row_end; iy0 += sd.tile_th)
-                for (uint32_t ix0 = 0; ix0 < sd.nx; ix0 += sd.tile_tw)
-                    pl->tile_units.push_back(UnitDev{slot, ix0 | (iy0 << 16), 0, 0});
-            pl->class_lds[cls] = std::max(pl->class_lds[cls], sd.tile_pitch * sd.tile_rows * 4u);
+            const uint32_t lead = pl->tile_lead[slot];
+            const ScaleDev& L = pl->scales[lead];
+            if (!pl->scales[slot].tile_rw || L.tile_class != cls || (slot > 0 && pl->tile_lead[slot - 1] == lead)) continue;
+            // a group's tiles cover the union of its members' tile rows; a member skips the tiles past its own
+            // tile_row_end (rows the balance gave to the gather chain) and past its own grid edge
+            uint32_t row_end = 0, nx = 0;
+            for (uint32_t k = slot; k <= lead; ++k) {
+                row_end = std::max(row_end, pl->scales[k].tile_row_end);
+                nx = std::max(nx, pl->scales[k].nx);
+            }
+            for (uint32_t iy0 = 0; iy0 < row_end; iy0 += L.tile_th)
+                for (uint32_t ix0 = 0; ix0 < nx; ix0 += L.tile_tw)
+                    pl->tile_units.push_back(UnitDev{slot, ix0 | (iy0 << 16), lead > slot ? lead - slot + 1u : 0u, 0});
+            pl->class_lds[cls] = std::max(pl->class_lds[cls], L.tile_pitch * L.tile_rows * 4u);
         }
         if (pl->class_lds[cls]) pl->class_lds[cls] += tile_header_bytes;
     }
@@ -1257,9 +1308,10 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
             li.stage_begin = (int32_t)sb;
             li.stage_end = (int32_t)se;
             li.lds_bytes = lds;
-            for (const ScaleDev& sd : pl->scales) {
+            for (uint32_t slot = 0; slot < pl->scales.size(); ++slot) {
+                const ScaleDev& sd = pl->scales[slot];
                 const bool in = kind == VJ_LAUNCH_QUEUE ||
-                                (kind == VJ_LAUNCH_TILE && sd.tile_rw && sd.tile_row_end > 0 && (int)sd.tile_class == cls) ||
+                                (kind == VJ_LAUNCH_TILE && sd.tile_rw && sd.tile_row_end > 0 && (int)pl->scales[pl->tile_lead[slot]].tile_class == cls) ||
                                 ((kind == VJ_LAUNCH_GRID || kind == VJ_LAUNCH_BLOCK) && sd.tile_row_end < sd.ny);
                 if (in && sd.scale_idx < 128) li.scale_mask[sd.scale_idx >> 6] |= 1ull << (sd.scale_idx & 63);
             }
@@ -1941,6 +1993,7 @@ int vj_env_create(int device_index, vj_env** out) {
         return VJ_ERR_NO_DEVICE;
     }
     e->n_cu = prop.multiProcessorCount;
+    if (const char* g = getenv("VJ_TILE_GROUP")) e->tile_group = std::max(1, std::min(atoi(g), (int)MAX_SCALES));
     if (const int hrc = prepare_tile_kernels()) {
         set_error("raising the dynamic LDS limit on device %d failed: %s", device_index, hipGetErrorString((hipError_t)hrc));
         return VJ_ERR_HIP;

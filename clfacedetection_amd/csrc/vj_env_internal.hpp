@@ -60,6 +60,7 @@ struct Plan {
     std::vector<UnitDev> unit_groups;        // runs of consecutive units of one (band, scale): what a wave of the band-major queue pass draws
     DevBuf d_unit_groups;
     std::vector<UnitDev> tile_units;         // first-pass tiles of one frame, grouped by LDS class
+    std::vector<uint32_t> tile_lead;         // per scale: the largest scale of its tile group (itself when not grouped)
     uint32_t class_first[TILE_CLASSES + 1] = {};  // tile_units range of each class
     uint32_t class_lds[TILE_CLASSES] = {};        // dynamic LDS bytes of each class launch
     uint32_t block_first = 0, n_block_units = 0;  // tile_units range of the unstaged 2-D blocks (global-gather scales)
@@ -277,6 +278,9 @@ struct Tunables {
 
 struct vj_env : vj::Tunables {
     int device = 0;
+    // Scale groups of the tile kernel: up to this many consecutive step-2 tile scales share one staged tile (1 = one
+    // tile per scale).  Not a configure key: read once from VJ_TILE_GROUP by vj_env_create (a diagnostic).
+    int tile_group = 4;
     hipStream_t stream = nullptr;
     vj::Lane lane0;                  // the batch of a plain vj_detect call
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;

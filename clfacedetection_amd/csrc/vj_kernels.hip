@@ -2304,15 +2304,15 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
     while (u < total_units) {
         uint32_t next_u = 0;
         if (threadIdx.x == 0) next_u = draw();
-        uint32_t frame, slot, ix0, iy0, nx, ny, ox = 0, oy = 0, roi = 0;
+        uint32_t frame, slot0, ix0, iy0, roi_nx = 0, roi_ny = 0, ox = 0, oy = 0, roi = 0, n_mem = 1;
         if constexpr (ROI) {
             kptr<RoiTile> rt = as_k(r_->tiles);
             roi = rt[u].roi;
-            slot = rt[u].slot;
+            slot0 = rt[u].slot;
             ix0 = rt[u].first & 0xffffu;
             iy0 = rt[u].first >> 16;
-            nx = rt[u].nxy & 0xffffu;
-            ny = rt[u].nxy >> 16;
+            roi_nx = rt[u].nxy & 0xffffu;
+            roi_ny = rt[u].nxy >> 16;
             const RoiDev R = r_->rois[roi];
             frame = __builtin_amdgcn_readfirstlane((uint32_t)R.frame);
             ox = __builtin_amdgcn_readfirstlane((uint32_t)R.x);
@@ -2320,17 +2320,17 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
         } else {
             frame = u / a.n_tile_units;
             const uint32_t r = u - frame * a.n_tile_units;
-            slot = units[r].scale;
+            slot0 = units[r].scale;
             ix0 = units[r].first & 0xffffu;
             iy0 = units[r].first >> 16;
-            nx = scales[slot].nx;
-            ny = scales[slot].ny;
+            if (STAGED) n_mem = max(units[r].count, 1u);
         }
-        const float step = scales[slot].step;
-        const uint32_t pos_base = scales[slot].pos_base;
-        uint32_t tw = scales[slot].tile_tw, th = scales[slot].tile_th;
-        const uint32_t pitch = STAGED ? scales[slot].tile_pitch : 0u;
-        uint32_t rows = STAGED ? scales[slot].tile_rows : 0u, cols = pitch;   // rows / columns of the image tile that are staged
+        // a scale group (n_mem > 1: scales slot0 .. lead, all of step 2) runs on the tile its largest scale lays out
+        const uint32_t lead = slot0 + n_mem - 1u;
+        const float step = scales[slot0].step;
+        uint32_t tw = scales[lead].tile_tw, th = scales[lead].tile_th;
+        const uint32_t pitch = STAGED ? scales[lead].tile_pitch : 0u;
+        uint32_t rows = STAGED ? scales[lead].tile_rows : 0u, cols = pitch;   // rows / columns of the image tile that are staged
         if constexpr (ROI) {
             // a region's tile may be smaller than the scale's: fewer rows and columns to stage.  The scale's tile spans
             // ceil((t - 1) * step) + margin pixels (host, double); floor(...) + 2 of the smaller shape against floor(...) of the
@@ -2347,17 +2347,18 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
         const size_t frame_off = (size_t)frame * a.frame_elems;
         const rsrc_t sum_f = make_rsrc(a.sum + frame_off, frame_bytes4);
         const rsrc_t sq_f = make_rsrc(a.sqsum + frame_off, frame_bytes4 * 2u);
-        // tile origin in the image: the first window's origin (same expression as below)
-        const uint32_t x0 = ox + __builtin_amdgcn_readfirstlane(window_pos(a, pos_base, ix0, step));
-        const uint32_t y0 = oy + __builtin_amdgcn_readfirstlane(window_pos(a, pos_base, iy0, step));
+        // tile origin in the image: the first window's origin (same expression as below; every member of a group
+        // places index i at 2 i)
+        const uint32_t x0 = ox + __builtin_amdgcn_readfirstlane(window_pos(a, scales[slot0].pos_base, ix0, step));
+        const uint32_t y0 = oy + __builtin_amdgcn_readfirstlane(window_pos(a, scales[slot0].pos_base, iy0, step));
 
         __syncthreads();  // the previous tile's gathers are finished
         STAMP(0);
         // stage the tile: rows round-robin over the waves, 64 consecutive dwords per instruction,
         // straight into LDS (buffer_load ... lds: no VGPR round trip, so every load of the tile is in
         // flight at once instead of one load-wait-store per 256 bytes); the barrier drains them
-        const uint32_t half = STAGED ? scales[slot].tile_half : 0u;
-        const uint32_t x4 = STAGED ? scales[slot].tile_x4 : 0u;
+        const uint32_t half = STAGED ? scales[lead].tile_half : 0u;
+        const uint32_t x4 = STAGED ? scales[lead].tile_x4 : 0u;
         for (uint32_t rr = wib; STAGED && rr < rows; rr += TILE_WAVES) {
             const uint32_t g_row = ((y0 + rr) * a.stride + x0) * 4u;   // uniform
             if (half == 0u && x4 != 0u) {
@@ -2394,224 +2395,238 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                 }
             }
         }
-        // while the tile is in flight: this wave's share of the tile's tw*th windows (a run of consecutive
-        // tile-local indices, at least one full wave per wave), their positions, and the four squared-sum
-        // corners of each (HBM, 8 bytes per lane) — all issued before the barrier that drains the staging
-        q = lds_q + wib * TILE_WAVE_CAP;   // (re-packing below moves the wave's queue base)
-        const uint32_t n_tile = tw * th;
-        const uint32_t per_wave = max(64u, (n_tile + TILE_WAVES - 1u) / TILE_WAVES);   // <= TILE_WAVE_CAP (host)
-        const uint32_t t_begin = min(wib * per_wave, n_tile), t_end = min(t_begin + per_wave, n_tile);
-        const uint32_t te_lt = scales[slot].te_lt * 4u, te_dh = scales[slot].te_dh * 4u, e_dw = scales[slot].e_dw;
-        const uint32_t te_dw = (uint32_t)scales[slot].te_dw * 4u;
-        const uint32_t e_lt = scales[slot].e_lt, e_dh = scales[slot].e_dh;
-        const float area = scales[slot].area;
-        constexpr int NCH = TILE_WAVE_CAP / 64;
-        uint32_t w_lo4[NCH];
-        uint64_t w_q[NCH];
-        bool w_valid[NCH];
+        // The members of a group, smallest scale first, each the whole cascade on the staged tile (a lone scale: one
+        // member).  A member skips a tile past its own grid edge or past its tile_row_end (rows the chain balance gave
+        // to the global-gather chain).
+        for (uint32_t m = 0; m < n_mem; ++m) {
+            const uint32_t slot = slot0 + m;
+            // (opaque per member: what the member's windows derive from the tile shape is recomputed, not kept live
+            // across the members — hoisted, those per-lane values cost 28 VGPRs and a wave of occupancy)
+            asm volatile("" : "+s"(tw), "+s"(th), "+s"(ix0), "+s"(iy0));
+            const uint32_t nx = ROI ? roi_nx : scales[slot].nx, ny = ROI ? roi_ny : scales[slot].ny;
+            if (n_mem > 1u && (ix0 >= nx || iy0 >= scales[slot].tile_row_end)) continue;   // (uniform)
+            const uint32_t pos_base = scales[slot].pos_base;
+            // while the tile is in flight: this wave's share of the tile's tw*th windows (a run of consecutive
+            // tile-local indices, at least one full wave per wave), their positions, and the four squared-sum
+            // corners of each (HBM, 8 bytes per lane) — all issued before the barrier that drains the staging
+            q = lds_q + wib * TILE_WAVE_CAP;   // (re-packing below moves the wave's queue base)
+            const uint32_t n_tile = tw * th;
+            const uint32_t per_wave = max(64u, (n_tile + TILE_WAVES - 1u) / TILE_WAVES);   // <= TILE_WAVE_CAP (host)
+            const uint32_t t_begin = min(wib * per_wave, n_tile), t_end = min(t_begin + per_wave, n_tile);
+            // (the ROI pass lays a scale's tile out for that scale alone; the tile list's tiles in the group's layout)
+            const uint32_t te_lt = (ROI ? scales[slot].te_lt : scales[slot].grp_te_lt) * 4u;
+            const uint32_t te_dh = (ROI ? scales[slot].te_dh : scales[slot].grp_te_dh) * 4u, e_dw = scales[slot].e_dw;
+            const uint32_t te_dw = (uint32_t)(ROI ? scales[slot].te_dw : scales[slot].grp_te_dw) * 4u;
+            const uint32_t e_lt = scales[slot].e_lt, e_dh = scales[slot].e_dh;
+            const float area = scales[slot].area;
+            constexpr int NCH = TILE_WAVE_CAP / 64;
+            uint32_t w_lo4[NCH];
+            uint64_t w_q[NCH];
+            bool w_valid[NCH];
 #pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            const uint32_t t = t_begin + (uint32_t)k * 64u + lane;
-            const uint32_t ty = t / tw, tx = t - ty * tw;
-            const uint32_t iy = iy0 + ty, ix = ix0 + tx;
-            w_valid[k] = t < t_end && iy < ny && ix < nx;
-            if (!ROI && a.skip_bits != nullptr && w_valid[k])   // uniform test
-                w_valid[k] = window_visited(a, frame, scales[slot].skip_base, scales[slot].skip_wpr, nx, ix, iy);
-            w_lo4[k] = 0u;
-            w_q[k] = 0ull;
-            if (w_valid[k]) {
-                const uint32_t x = ox + window_pos(a, pos_base, ix, step);
-                const uint32_t y = oy + window_pos(a, pos_base, iy, step);
-                // byte offset inside the tile (de-interleaved rows: window origins are even columns)
-                const uint32_t e = y * a.stride + x;
-                // unstaged blocks: byte offset in the batch sum image, as in cascade_pass
-                w_lo4[k] = STAGED ? ((y - y0) * pitch + (half ? (x - x0) >> 1 : x - x0)) * 4u : frame_bytes + e * 4u;
-                const uint32_t c0 = e_lt, c1 = e_lt + e_dw, c2 = e_lt + e_dh, c3 = e_lt + e_dh + e_dw;
-                w_q[k] = ld_u64(sq_f, e * 8u, c0 * 8u) - ld_u64(sq_f, e * 8u, c1 * 8u) - ld_u64(sq_f, e * 8u, c2 * 8u) +
-                         ld_u64(sq_f, e * 8u, c3 * 8u);
+            for (int k = 0; k < NCH; ++k) {
+                const uint32_t t = t_begin + (uint32_t)k * 64u + lane;
+                const uint32_t ty = t / tw, tx = t - ty * tw;
+                const uint32_t iy = iy0 + ty, ix = ix0 + tx;
+                w_valid[k] = t < t_end && iy < ny && ix < nx;
+                if (!ROI && a.skip_bits != nullptr && w_valid[k])   // uniform test
+                    w_valid[k] = window_visited(a, frame, scales[slot].skip_base, scales[slot].skip_wpr, nx, ix, iy);
+                w_lo4[k] = 0u;
+                w_q[k] = 0ull;
+                if (w_valid[k]) {
+                    const uint32_t x = ox + window_pos(a, pos_base, ix, step);
+                    const uint32_t y = oy + window_pos(a, pos_base, iy, step);
+                    // byte offset inside the tile (de-interleaved rows: window origins are even columns)
+                    const uint32_t e = y * a.stride + x;
+                    // unstaged blocks: byte offset in the batch sum image, as in cascade_pass
+                    w_lo4[k] = STAGED ? ((y - y0) * pitch + (half ? (x - x0) >> 1 : x - x0)) * 4u : frame_bytes + e * 4u;
+                    const uint32_t c0 = e_lt, c1 = e_lt + e_dw, c2 = e_lt + e_dh, c3 = e_lt + e_dh + e_dw;
+                    w_q[k] = ld_u64(sq_f, e * 8u, c0 * 8u) - ld_u64(sq_f, e * 8u, c1 * 8u) - ld_u64(sq_f, e * 8u, c2 * 8u) +
+                             ld_u64(sq_f, e * 8u, c3 * 8u);
+                }
             }
-        }
-        __syncthreads();
-        STAMP(1);
+            __syncthreads();
+            STAMP(1);
 
-        // computeVariance (clod.cpp:418-446): pixel sum from the LDS tile, squared sum as loaded above
-        uint32_t n = 0;
-        typedef typename std::conditional<STAGED, LdsImg, GlobalImg>::type ImgT;
-        ImgT img;
-        if constexpr (STAGED) img = LdsImg{reinterpret_cast<const char*>(lds_img)};
-        else img = GlobalImg{make_rsrc(a.sum, a.sum_bytes)};
+            // computeVariance (clod.cpp:418-446): pixel sum from the LDS tile, squared sum as loaded above
+            uint32_t n = 0;
+            typedef typename std::conditional<STAGED, LdsImg, GlobalImg>::type ImgT;
+            ImgT img;
+            if constexpr (STAGED) img = LdsImg{reinterpret_cast<const char*>(lds_img)};
+            else img = GlobalImg{make_rsrc(a.sum, a.sum_bytes)};
 #pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            QEntry en{0u, 0.0f};
-            if (w_valid[k]) {
-                const uint32_t lo4 = w_lo4[k];
-                uint32_t s4;
-                if constexpr (STAGED) {
-                    s4 = img.ld(lo4, te_lt) - img.ld(lo4, te_lt + te_dw) - img.ld(lo4, te_lt + te_dh) +
-                         img.ld(lo4, te_lt + te_dh + te_dw);
-                } else {
-                    const uint32_t g_lt = e_lt * 4u, g_dw = e_dw * 4u, g_dh = e_dh * 4u;
-                    s4 = img.ld(lo4, g_lt) - img.ld(lo4, g_lt + g_dw) - img.ld(lo4, g_lt + g_dh) + img.ld(lo4, g_lt + g_dh + g_dw);
-                }
-                const float mean = (a.signed_mean ? (float)(int32_t)s4 : (float)s4) / area;
-                float variance = (float)w_q[k];
-                variance = (variance / area) - (mean * mean);
-                en.var = variance >= 0.0f ? sqrtf(variance) : 1.0f;
-                en.off = lo4;
-            }
-            const unsigned long long mask = __ballot(w_valid[k]);
-            if (w_valid[k]) q[n + mbcnt(mask)] = en;
-            n += (uint32_t)__popcll(mask);
-        }
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t table_first = STAGED ? scales[slot].tile_table_first : scales[slot].table_first;
-        kptr<NodeRecDev> table = as_k(reinterpret_cast<const NodeRecDev*>(a.table)) + table_first;
-        // Sweep the cascade stage by stage.  At the stages named by tile_repack_mask and at every
-        // pass boundary the tile's survivors are re-packed across its waves into runs of full
-        // 64-lane chunks (gathers cost the same for 1 lane as for 64, so 8 thin waves would pay 8x).
-        // At a pass boundary the whole workgroup leaves — handing its survivors to that pass's
-        // queue — when the boundary lies at or beyond tile_end or fewer than tile_min_lanes
-        // windows are left in the tile (the queue passes re-pack windows of the whole batch).
-        STAMP(2);
-        // hand a wave's survivors on: detections (dest == n_pass) or the global queue of pass boundary `dest`;
-        // tile-local offsets become byte offsets in the batch sum image
-        auto flush_wave = [&](const QEntry* qq, uint32_t nn, uint32_t dest_) {
-            if constexpr (ROI) {   // (one pass: whatever survives is a detection of this region)
-                uint32_t g = 0;
-                if (lane == 0) g = atomicAdd(r_->det_count, nn);
-                g = __builtin_amdgcn_readfirstlane(g);
-                for (uint32_t i = lane; i < nn; i += 64u) {
-                    const uint32_t lo = qq[i].off >> 2;
-                    const uint32_t ly = lo / pitch, lc = lo - ly * pitch;
-                    const uint32_t lx = half ? lc * 2u : lc;
-                    if (g + i < r_->det_cap) r_->det[g + i] = RoiDet{frame_bytes + ((y0 + ly) * a.stride + (x0 + lx)) * 4u, slot, roi};
-                }
-                return;
-            }
-            const bool is_det = dest_ == a.n_pass;
-            const uint32_t part = frame_part(a, frame);
-            uint32_t g = 0;
-            if (lane == 0)
-                g = is_det ? atomicAdd(a.det_count, nn) : atomicAdd(a.q_pass_count[dest_] + slot * Q_PARTS + part, nn);
-            g = __builtin_amdgcn_readfirstlane(g);
-            const size_t q_base = (size_t)scales[slot].q_base + (size_t)part * scales[slot].q_cap;
-            QEntry* qd = is_det ? nullptr : a.q_pass[dest_];
-            for (uint32_t i = lane; i < nn; i += 64u) {
-                const QEntry e = qq[i];
-                uint32_t off = e.off;
-                if (STAGED) {
-                    const uint32_t lo = e.off >> 2;
-                    const uint32_t ly = lo / pitch, lc = lo - ly * pitch;
-                    const uint32_t lx = half ? lc * 2u : lc;   // window origins sit in the even plane
-                    off = frame_bytes + ((y0 + ly) * a.stride + (x0 + lx)) * 4u;
-                }
-                if (is_det) {
-                    if (g + i < a.det_cap) a.det[g + i] = DetEntry{off, slot};
-                } else {
-                    qd[q_base + g + i] = QEntry{off, e.var};
-                }
-            }
-        };
-        uint32_t dest = a.n_pass;   // n_pass = ran the whole cascade: survivors are detections
-        uint32_t next_p = 1;        // next pass boundary index
-        const uint32_t n_stages_total = a.pass_begin[a.n_pass];
-        for (uint32_t st = 0; st < n_stages_total; ++st) {
-            const bool at_boundary = next_p < a.n_pass && st == a.pass_begin[next_p];
-            if (st != 0u && (at_boundary || ((a.tile_repack_mask >> st) & 1ull))) {
-                // ---- workgroup-uniform: count, then move every survivor to its packed position
-                if (lane == 0) lds_cnt[wib] = n;
-                __syncthreads();
-                uint32_t before = 0, total = 0;
-#pragma unroll
-                for (uint32_t w = 0; w < TILE_WAVES; ++w) {
-                    const uint32_t c = lds_cnt[w];
-                    before += w < wib ? c : 0u;
-                    total += c;
-                }
-                before = __builtin_amdgcn_readfirstlane(before);
-                total = __builtin_amdgcn_readfirstlane(total);
-                QEntry hold[TILE_WAVE_CAP / 64];
-#pragma unroll
-                for (uint32_t k = 0; k < TILE_WAVE_CAP / 64; ++k)
-                    if (k * 64u + lane < n) hold[k] = q[k * 64u + lane];
-                __syncthreads();   // every wave holds its survivors in registers
-#pragma unroll
-                for (uint32_t k = 0; k < TILE_WAVE_CAP / 64; ++k)
-                    if (k * 64u + lane < n) lds_q[before + k * 64u + lane] = hold[k];
-                __syncthreads();
-                // contiguous shares of whole chunks: wave w owns [w*share, (w+1)*share)
-                const uint32_t share = 64u * (((total + 63u) / 64u + TILE_WAVES - 1u) / TILE_WAVES);
-                const uint32_t first = min(wib * share, total);
-                q = lds_q + first;
-                n = min(share, total - first);
-                STAMP(3 + min(st, 8u));   // time of stage st-1 (incl. waiting for the slowest wave) + this re-pack
-                if (!TREES && a.n_seg != 0u && st == a.tile_end && total != 0u && total <= (uint32_t)TILE_SEG_MAX_WINDOWS) {
-                    // Stage tree (frontalface_alt_tree): the linear prefix ends here; the chains that follow run on the
-                    // packed survivors with the wave-split machinery — a chain's rejects are collected in LDS and
-                    // become the population of the next chain — so the whole tree finishes inside the tile.
-                    QEntry* flist = lds_q + (TILE_WS_MAX_WINDOWS + TILE_WAVES * 160);   // behind the wave-split scratch
-                    uint32_t T = total, posn = st;
-                    for (uint32_t k = 0; k < a.n_seg; ++k) {
-                        const bool chained = ((a.seg_chain >> k) & 1u) != 0u;
-                        uint32_t F_n = 0;
-                        const uint32_t left = tile_wave_split<COUNT, false>(a, img, table, lds_q, lds_cnt, T, posn, a.seg_end[k],
-                                                                            lane, wib, t_last, chained ? flist : nullptr, &F_n);
-                        if (wib == 0u && left != 0u) flush_wave(lds_q, left, a.n_pass);   // the chain's end accepts
-                        if (!chained || F_n == 0u) break;
-                        __syncthreads();
-                        for (uint32_t i = threadIdx.x; i < F_n; i += TILE_WAVES * 64u) lds_q[i] = flist[i];
-                        __syncthreads();
-                        T = F_n;
-                        posn = a.seg_end[k];
+            for (int k = 0; k < NCH; ++k) {
+                QEntry en{0u, 0.0f};
+                if (w_valid[k]) {
+                    const uint32_t lo4 = w_lo4[k];
+                    uint32_t s4;
+                    if constexpr (STAGED) {
+                        s4 = img.ld(lo4, te_lt) - img.ld(lo4, te_lt + te_dw) - img.ld(lo4, te_lt + te_dh) +
+                             img.ld(lo4, te_lt + te_dh + te_dw);
+                    } else {
+                        const uint32_t g_lt = e_lt * 4u, g_dw = e_dw * 4u, g_dh = e_dh * 4u;
+                        s4 = img.ld(lo4, g_lt) - img.ld(lo4, g_lt + g_dw) - img.ld(lo4, g_lt + g_dh) + img.ld(lo4, g_lt + g_dh + g_dw);
                     }
-                    q = lds_q;
-                    n = 0u;
-                    dest = a.n_pass;
-                    STAMP(12);
-                    break;
+                    const float mean = (a.signed_mean ? (float)(int32_t)s4 : (float)s4) / area;
+                    float variance = (float)w_q[k];
+                    variance = (variance / area) - (mean * mean);
+                    en.var = variance >= 0.0f ? sqrtf(variance) : 1.0f;
+                    en.off = lo4;
                 }
-                if ((!TREES || a.tree2) && a.tile_finish == 1u && st >= a.tile_sp_begin && total != 0u && total <= a.tile_ws_max) {
-                    // few windows left: finish the whole cascade with the stage's stumps (or two-node trees) split
-                    // over the waves
-                    uint32_t s_next = st;
-                    uint32_t left = tile_wave_split<COUNT, TREES>(a, img, table, lds_q, lds_cnt, total, s_next, n_stages_total,
-                                                                  lane, wib, t_last);
-                    if (!TREES && left != 0u && s_next < n_stages_total)
-                        left = tile_stump_parallel<COUNT, false>(
-                            a, img, a.table + (size_t)table_first * 16u, lds_q,
-                            reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS), lds_tab, lds_cnt, left, s_next,
-                            n_stages_total, lane, wib, t_last);
-                    q = lds_q;
-                    n = wib == 0u ? left : 0u;
-                    dest = a.n_pass;
-                    STAMP(12);
-                    break;
+                const unsigned long long mask = __ballot(w_valid[k]);
+                if (w_valid[k]) q[n + mbcnt(mask)] = en;
+                n += (uint32_t)__popcll(mask);
+            }
+            __builtin_amdgcn_wave_barrier();
+            const uint32_t table_first = !STAGED ? scales[slot].table_first : ROI ? scales[slot].tile_table_first : scales[slot].grp_table_first;
+            kptr<NodeRecDev> table = as_k(reinterpret_cast<const NodeRecDev*>(a.table)) + table_first;
+            // Sweep the cascade stage by stage.  At the stages named by tile_repack_mask and at every
+            // pass boundary the tile's survivors are re-packed across its waves into runs of full
+            // 64-lane chunks (gathers cost the same for 1 lane as for 64, so 8 thin waves would pay 8x).
+            // At a pass boundary the whole workgroup leaves — handing its survivors to that pass's
+            // queue — when the boundary lies at or beyond tile_end or fewer than tile_min_lanes
+            // windows are left in the tile (the queue passes re-pack windows of the whole batch).
+            STAMP(2);
+            // hand a wave's survivors on: detections (dest == n_pass) or the global queue of pass boundary `dest`;
+            // tile-local offsets become byte offsets in the batch sum image
+            auto flush_wave = [&](const QEntry* qq, uint32_t nn, uint32_t dest_) {
+                if constexpr (ROI) {   // (one pass: whatever survives is a detection of this region)
+                    uint32_t g = 0;
+                    if (lane == 0) g = atomicAdd(r_->det_count, nn);
+                    g = __builtin_amdgcn_readfirstlane(g);
+                    for (uint32_t i = lane; i < nn; i += 64u) {
+                        const uint32_t lo = qq[i].off >> 2;
+                        const uint32_t ly = lo / pitch, lc = lo - ly * pitch;
+                        const uint32_t lx = half ? lc * 2u : lc;
+                        if (g + i < r_->det_cap) r_->det[g + i] = RoiDet{frame_bytes + ((y0 + ly) * a.stride + (x0 + lx)) * 4u, slot, roi};
+                    }
+                    return;
                 }
-                if (!TREES && a.tile_finish == 0u && st >= a.tile_sp_begin && total != 0u && total <= a.tile_sp_max) {
-                    // few windows left: finish the whole cascade stump-parallel; survivors are detections
-                    const uint32_t left = tile_stump_parallel<COUNT, true>(
-                        a, img, a.table + (size_t)table_first * 16u, lds_q,
-                        reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS), lds_tab, lds_cnt, total, st,
-                        n_stages_total, lane, wib, t_last);
-                    q = lds_q;
-                    n = wib == 0u ? left : 0u;
-                    dest = a.n_pass;
-                    STAMP(12);
-                    break;
+                const bool is_det = dest_ == a.n_pass;
+                const uint32_t part = frame_part(a, frame);
+                uint32_t g = 0;
+                if (lane == 0)
+                    g = is_det ? atomicAdd(a.det_count, nn) : atomicAdd(a.q_pass_count[dest_] + slot * Q_PARTS + part, nn);
+                g = __builtin_amdgcn_readfirstlane(g);
+                const size_t q_base = (size_t)scales[slot].q_base + (size_t)part * scales[slot].q_cap;
+                QEntry* qd = is_det ? nullptr : a.q_pass[dest_];
+                for (uint32_t i = lane; i < nn; i += 64u) {
+                    const QEntry e = qq[i];
+                    uint32_t off = e.off;
+                    if (STAGED) {
+                        const uint32_t lo = e.off >> 2;
+                        const uint32_t ly = lo / pitch, lc = lo - ly * pitch;
+                        const uint32_t lx = half ? lc * 2u : lc;   // window origins sit in the even plane
+                        off = frame_bytes + ((y0 + ly) * a.stride + (x0 + lx)) * 4u;
+                    }
+                    if (is_det) {
+                        if (g + i < a.det_cap) a.det[g + i] = DetEntry{off, slot};
+                    } else {
+                        qd[q_base + g + i] = QEntry{off, e.var};
+                    }
                 }
-                if (at_boundary) {
-                    if (total < max(a.tile_min_lanes, 1u) || st >= a.tile_end) {
-                        dest = next_p;
+            };
+            uint32_t dest = a.n_pass;   // n_pass = ran the whole cascade: survivors are detections
+            uint32_t next_p = 1;        // next pass boundary index
+            const uint32_t n_stages_total = a.pass_begin[a.n_pass];
+            for (uint32_t st = 0; st < n_stages_total; ++st) {
+                const bool at_boundary = next_p < a.n_pass && st == a.pass_begin[next_p];
+                if (st != 0u && (at_boundary || ((a.tile_repack_mask >> st) & 1ull))) {
+                    // ---- workgroup-uniform: count, then move every survivor to its packed position
+                    if (lane == 0) lds_cnt[wib] = n;
+                    __syncthreads();
+                    uint32_t before = 0, total = 0;
+#pragma unroll
+                    for (uint32_t w = 0; w < TILE_WAVES; ++w) {
+                        const uint32_t c = lds_cnt[w];
+                        before += w < wib ? c : 0u;
+                        total += c;
+                    }
+                    before = __builtin_amdgcn_readfirstlane(before);
+                    total = __builtin_amdgcn_readfirstlane(total);
+                    QEntry hold[TILE_WAVE_CAP / 64];
+#pragma unroll
+                    for (uint32_t k = 0; k < TILE_WAVE_CAP / 64; ++k)
+                        if (k * 64u + lane < n) hold[k] = q[k * 64u + lane];
+                    __syncthreads();   // every wave holds its survivors in registers
+#pragma unroll
+                    for (uint32_t k = 0; k < TILE_WAVE_CAP / 64; ++k)
+                        if (k * 64u + lane < n) lds_q[before + k * 64u + lane] = hold[k];
+                    __syncthreads();
+                    // contiguous shares of whole chunks: wave w owns [w*share, (w+1)*share)
+                    const uint32_t share = 64u * (((total + 63u) / 64u + TILE_WAVES - 1u) / TILE_WAVES);
+                    const uint32_t first = min(wib * share, total);
+                    q = lds_q + first;
+                    n = min(share, total - first);
+                    STAMP(3 + min(st, 8u));   // time of stage st-1 (incl. waiting for the slowest wave) + this re-pack
+                    if (!TREES && a.n_seg != 0u && st == a.tile_end && total != 0u && total <= (uint32_t)TILE_SEG_MAX_WINDOWS) {
+                        // Stage tree (frontalface_alt_tree): the linear prefix ends here; the chains that follow run on the
+                        // packed survivors with the wave-split machinery — a chain's rejects are collected in LDS and
+                        // become the population of the next chain — so the whole tree finishes inside the tile.
+                        QEntry* flist = lds_q + (TILE_WS_MAX_WINDOWS + TILE_WAVES * 160);   // behind the wave-split scratch
+                        uint32_t T = total, posn = st;
+                        for (uint32_t k = 0; k < a.n_seg; ++k) {
+                            const bool chained = ((a.seg_chain >> k) & 1u) != 0u;
+                            uint32_t F_n = 0;
+                            const uint32_t left = tile_wave_split<COUNT, false>(a, img, table, lds_q, lds_cnt, T, posn, a.seg_end[k],
+                                                                                lane, wib, t_last, chained ? flist : nullptr, &F_n);
+                            if (wib == 0u && left != 0u) flush_wave(lds_q, left, a.n_pass);   // the chain's end accepts
+                            if (!chained || F_n == 0u) break;
+                            __syncthreads();
+                            for (uint32_t i = threadIdx.x; i < F_n; i += TILE_WAVES * 64u) lds_q[i] = flist[i];
+                            __syncthreads();
+                            T = F_n;
+                            posn = a.seg_end[k];
+                        }
+                        q = lds_q;
+                        n = 0u;
+                        dest = a.n_pass;
+                        STAMP(12);
                         break;
                     }
-                    ++next_p;
+                    if ((!TREES || a.tree2) && a.tile_finish == 1u && st >= a.tile_sp_begin && total != 0u && total <= a.tile_ws_max) {
+                        // few windows left: finish the whole cascade with the stage's stumps (or two-node trees) split
+                        // over the waves
+                        uint32_t s_next = st;
+                        uint32_t left = tile_wave_split<COUNT, TREES>(a, img, table, lds_q, lds_cnt, total, s_next, n_stages_total,
+                                                                      lane, wib, t_last);
+                        if (!TREES && left != 0u && s_next < n_stages_total)
+                            left = tile_stump_parallel<COUNT, false>(
+                                a, img, a.table + (size_t)table_first * 16u, lds_q,
+                                reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS), lds_tab, lds_cnt, left, s_next,
+                                n_stages_total, lane, wib, t_last);
+                        q = lds_q;
+                        n = wib == 0u ? left : 0u;
+                        dest = a.n_pass;
+                        STAMP(12);
+                        break;
+                    }
+                    if (!TREES && a.tile_finish == 0u && st >= a.tile_sp_begin && total != 0u && total <= a.tile_sp_max) {
+                        // few windows left: finish the whole cascade stump-parallel; survivors are detections
+                        const uint32_t left = tile_stump_parallel<COUNT, true>(
+                            a, img, a.table + (size_t)table_first * 16u, lds_q,
+                            reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS), lds_tab, lds_cnt, total, st,
+                            n_stages_total, lane, wib, t_last);
+                        q = lds_q;
+                        n = wib == 0u ? left : 0u;
+                        dest = a.n_pass;
+                        STAMP(12);
+                        break;
+                    }
+                    if (at_boundary) {
+                        if (total < max(a.tile_min_lanes, 1u) || st >= a.tile_end) {
+                            dest = next_p;
+                            break;
+                        }
+                        ++next_p;
+                    }
                 }
+                if (n != 0u) n = sweep_stages<TREES, COUNT, true>(a, img, table, q, n, lane, st, st + 1u);
             }
-            if (n != 0u) n = sweep_stages<TREES, COUNT, true>(a, img, table, q, n, lane, st, st + 1u);
+            if (n != 0u) flush_wave(q, n, dest);
+            STAMP(13);
+            __syncthreads();   // the member is finished: its queue may be rewritten, lds_cnt may carry the next ticket
         }
-        if (n != 0u) flush_wave(q, n, dest);
-        STAMP(13);
-        __syncthreads();   // the tile is finished: lds_cnt may carry the next ticket
         if (threadIdx.x == 0) lds_cnt[TILE_WAVES + 8] = next_u;
         __syncthreads();
         u = __builtin_amdgcn_readfirstlane(lds_cnt[TILE_WAVES + 8]);
