@@ -1257,6 +1257,8 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
             ca.q_pass[ps] = (QEntry*)e->d_q[ps].p;
             ca.q_pass_count[ps] = d_qcount[ps];
         }
+        // linear cascades: the kernel sees the configured tile_end, not the plan's clamped pl->tile_end; a tile leaves at the first pass boundary
+        // at or beyond it, and `banded` / `handover` below compare it with pass_bounds[1]
         ca.tile_end = pl->general ? pl->general_prefix : (uint32_t)e->tile_end;   // stage trees: tiles run the linear prefix only
         ca.tile_min_lanes = (uint32_t)e->tile_min_lanes;
         ca.tile_repack_mask = e->tile_repack_mask;
@@ -1329,9 +1331,11 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
         auto pass_is_last = [&](size_t ps) { return pl->seg_last.empty() ? ps + 1 == n_pass : pl->seg_last[ps] != 0; };
         const bool general_kernel = pl->general && pl->seg_last.empty();   // run_stages_general finishes the tree
         // Band-major queue pass: a batch of a linear cascade whose gather chain is grid pass + ONE queue pass that only the grid
-        // pass feeds (the tiles run the whole cascade themselves)
+        // pass feeds.  It reads nothing but the runs the grid pass records in run_table, so the tiles must not feed that queue:
+        // they run the whole cascade themselves only when tile_end lies BEYOND the boundary (at tile_end == pass_bounds[1] they
+        // hand their survivors to q_pass[1], and the chunked pass, which sweeps the whole sub-queue, takes the batch)
         const bool banded = e->q_band_px > 0 && !pl->unit_groups.empty() && !pl->general && n_pass == 2 && nf >= e->q_band_min_frames &&
-                            e->tile_min_lanes == 0 && (uint32_t)e->tile_end >= pl->pass_bounds[1] && !(e->global_blocks && pl->n_block_units > 0 && pl->sp_pad != 0);
+                            e->tile_min_lanes == 0 && (uint32_t)e->tile_end > pl->pass_bounds[1] && !(e->global_blocks && pl->n_block_units > 0 && pl->sp_pad != 0);
         if (banded) {
             if ((rc = e->d_run_table.ensure((size_t)nf * pl->units.size() * 8u))) return rc;
             ca.run_table = (uint32_t*)e->d_run_table.p;
