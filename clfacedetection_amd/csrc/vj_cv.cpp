@@ -552,7 +552,6 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
             a.stage_entered = (unsigned long long*)d_counts.p;
             a.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
             a.tree2 = pl->tree2 && !is_tree && !has_tilted && e->cv_tree2 ? 1u : 0u;
-            a.pairs = e->cv_pairs ? 1u : 0u;
             if (is_tree && pl->chains.n != 0u && !count && e->cv_tree_chains) {   // the rows kernel sweeps the chains too (cv_chain_sweep): a fail list per wave
                 a.chains = pl->chains;
                 const size_t waves = (size_t)std::max(1, e->n_cu * 4) * CV_WAVES_PER_BLOCK;

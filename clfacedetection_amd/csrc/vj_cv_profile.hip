@@ -162,7 +162,6 @@ __device__ __forceinline__ double cv_stage_sum_mode(rsrc_t img, rsrc_t timg, kpt
 // One stump stage on the lane's window, two stumps per step with all of their gathers in flight (a thin sweep pays a memory
 // round trip per step); the leaf values are added in stump order.  Stage trees never take the two_rects f64 branch
 // (StageDev::cv_f64 is 0 for them): int * float products widened to double (:783-788).
-template <bool F64 = false>
 __device__ __forceinline__ double cv_stage_sum_pairs(rsrc_t img, kptr<NodeRecDev> tab, uint32_t n_nodes, uint32_t off, double vnf) {
     double stage_sum = 0.0;
     uint32_t j = 0;
@@ -173,18 +172,12 @@ __device__ __forceinline__ double cv_stage_sum_pairs(rsrc_t img, kptr<NodeRecDev
             const NodeRecDev na = tab[ja], nb = tab[jb];   // the next pair travels meanwhile
             const int32_t a0 = cv_calc_sum(img, off, ra[0], ra[3], ra[6]), a1 = cv_calc_sum(img, off, ra[1], ra[4], ra[7]);
             const int32_t b0 = cv_calc_sum(img, off, rb[0], rb[3], rb[6]), b1 = cv_calc_sum(img, off, rb[1], rb[4], rb[7]);
-            double sa, sb;
-            if (F64) {   // a two_rects stump stage (tempcv.cpp:872-888): f64 products, rect1 + rect0
-                sa = (double)a1 * (double)__uint_as_float(ra[10]) + (double)a0 * (double)__uint_as_float(ra[9]);
-                sb = (double)b1 * (double)__uint_as_float(rb[10]) + (double)b0 * (double)__uint_as_float(rb[9]);
-            } else {
-                sa = (double)((float)a0 * __uint_as_float(ra[9]));
-                sa += (double)((float)a1 * __uint_as_float(ra[10]));
-                sb = (double)((float)b0 * __uint_as_float(rb[9]));
-                sb += (double)((float)b1 * __uint_as_float(rb[10]));
-            }
+            double sa = (double)((float)a0 * __uint_as_float(ra[9]));
+            sa += (double)((float)a1 * __uint_as_float(ra[10]));
+            double sb = (double)((float)b0 * __uint_as_float(rb[9]));
+            sb += (double)((float)b1 * __uint_as_float(rb[10]));
             const float wa2 = __uint_as_float(ra[11]), wb2 = __uint_as_float(rb[11]);
-            if (!F64 && (wa2 != 0.0f || wb2 != 0.0f)) {   // uniform (an absent third rectangle has lt = da = db = 0: four reads of the origin)
+            if (wa2 != 0.0f || wb2 != 0.0f) {   // uniform (an absent third rectangle has lt = da = db = 0: four reads of the origin)
                 const int32_t a2 = cv_calc_sum(img, off, ra[2], ra[5], ra[8]), b2 = cv_calc_sum(img, off, rb[2], rb[5], rb[8]);
                 if (wa2 != 0.0f) sa += (double)((float)a2 * wa2);
                 if (wb2 != 0.0f) sb += (double)((float)b2 * wb2);
@@ -197,7 +190,7 @@ __device__ __forceinline__ double cv_stage_sum_pairs(rsrc_t img, kptr<NodeRecDev
     }
     if (j < n_nodes) {
         const NodeRecDev r = tab[j];
-        const double s = cv_node_sum<F64>(img, img, r, off);
+        const double s = cv_node_sum<false>(img, img, r, off);
         stage_sum += (double)(s < (double)__uint_as_float(r[12]) * vnf ? __uint_as_float(r[13]) : __uint_as_float(r[14]));
     }
     return stage_sum;
@@ -360,7 +353,7 @@ __device__ __forceinline__ void cv_flush(const CvArgs& a, rsrc_t img, rsrc_t tim
         const uint32_t n_nodes = stages[s].n_nodes, f64 = stages[s].cv_f64;
         const double thr = (double)stages[s].threshold;
         uint32_t m = 0;
-        const bool upright = !TREES && a.tilted == nullptr;   // (the pair / stump-parallel forms read the upright sum image only)
+        const bool upright = !TREES && a.tilted == nullptr;   // (the stump-parallel form reads the upright sum image only)
         if (upright && n <= a.tail_max && n_nodes >= 16u && n_nodes <= CV_TAIL_BLOCKS * 64u) {
             // a thin population: the stage stump-parallel (lane = stump), verdict bits replayed in stump order (cv_tail_stage)
             const uint32_t* recs_g = reinterpret_cast<const uint32_t*>((uintptr_t)(table + stages[s].first_node));
@@ -379,8 +372,7 @@ __device__ __forceinline__ void cv_flush(const CvArgs& a, rsrc_t img, rsrc_t tim
             const bool act = i < n;
             const CvQEntry e = q[act ? i : 0u];
             bool pass = false;
-            if (act && upright && a.pairs != 0u) pass = (f64 != 0u ? cv_stage_sum_pairs<true>(img, tab, n_nodes, e.off, e.vnf) : cv_stage_sum_pairs<false>(img, tab, n_nodes, e.off, e.vnf)) >= thr;
-            else if (act) pass = cv_stage_sum_mode<TREES>(img, timg, tab, n_nodes, e.off, e.vnf, f64, a.tree2) >= thr;
+            if (act) pass = cv_stage_sum_mode<TREES>(img, timg, tab, n_nodes, e.off, e.vnf, f64, a.tree2) >= thr;
             const unsigned long long mask = __ballot(pass);
             __builtin_amdgcn_wave_barrier();
             if (pass) q[m + mbcnt(mask)] = e;
@@ -799,71 +791,24 @@ int launch_cv_tree_emit(const CvTreeArgs& a, int n_blocks, void* stream_) {
 }
 
 // ------------------------------------------------------------------------ tilted integral
-// cvIntegral's tilted sum (OpenCV 2.4.2 imgproc; tilted(X, Y) = sum of gray(x, y) over y < Y, |x - X + 1| <= Y - y - 1)
-// by its row recurrence
-//   T[Y][X] = T[Y-1][X-1] + T[Y-1][X+1] - T[Y-2][X] + I(X-1, Y-1) + I(X-1, Y-2),
-//   T[Y][-1] = T[Y-1][0],  T[Y][W+1] = T[Y-1][W]   (a triangle whose apex lies outside the image),
-// exact in 32 bits modulo 2^32 like CV_32S.  Rows depend on the two rows above, columns do not depend on each other:
-// one workgroup per frame walks the rows with the last three rows in LDS, 1024 columns at a time.  Only cascades with
-// tilted features in the OpenCV profile ask for it; it is not on the headline path.
+// cvIntegral's tilted sum (OpenCV 2.4.2 imgproc; tilted(X, Y) = sum of gray(x, y) over y < Y, |x - X + 1| <= Y - y - 1),
+// exact in 32 bits modulo 2^32 like CV_32S.  Only cascades with tilted features in the OpenCV profile ask for it; it is not on the
+// headline path.
 __device__ __forceinline__ uint32_t gray_at(const uint8_t* row, uint32_t x, uint32_t ch) {
     if (ch <= 1u) return row[x];
     const uint8_t* p = row + (size_t)x * ch;
     return (p[0] * 1868u + p[1] * 9617u + p[2] * 4899u + 8192u) >> 14;   // OpenCV's 8-bit BGR2GRAY, as the integral kernels
 }
 
-__global__ __launch_bounds__(1024) void tilted_rows(TiltedArgs a) {
-    extern __shared__ uint32_t lds_rows[];   // 3 rows of (W + 1)
-    const uint32_t frame = blockIdx.x;
-    const uint32_t ow = a.width + 1u;
-    const uint8_t* img = a.gray + (size_t)frame * a.gray_frame_bytes;
-    uint32_t* out = a.tilted + (size_t)frame * a.frame_elems;
-    for (uint32_t x = threadIdx.x; x < ow; x += 1024u) {
-        lds_rows[x] = 0u;   // row 0
-        out[x] = 0u;
-    }
-    __syncthreads();
-    for (uint32_t Y = 1; Y <= a.height; ++Y) {
-        const uint32_t* t1 = lds_rows + ((Y - 1u) % 3u) * ow;
-        const uint32_t* t2 = lds_rows + ((Y + 1u) % 3u) * ow;   // (Y - 2) mod 3
-        uint32_t* cur = lds_rows + (Y % 3u) * ow;
-        const uint8_t* i1 = img + (size_t)(Y - 1u) * a.gray_stride;
-        const uint8_t* i2 = img + (size_t)(Y >= 2u ? Y - 2u : 0u) * a.gray_stride;
-        const bool has2 = Y >= 2u;
-        for (uint32_t X = threadIdx.x; X < ow; X += 1024u) {
-            const uint32_t left = X >= 1u ? t1[X - 1u] : (has2 ? t2[0] : 0u);
-            const uint32_t right = X + 1u < ow ? t1[X + 1u] : (has2 ? t2[a.width] : 0u);
-            const uint32_t up2 = has2 ? t2[X] : 0u;
-            uint32_t px = 0u;
-            if (X >= 1u) px = gray_at(i1, X - 1u, a.channels) + (has2 ? gray_at(i2, X - 1u, a.channels) : 0u);
-            const uint32_t v = left + right - up2 + px;
-            cur[X] = v;
-            out[(size_t)Y * ow + X] = v;
-        }
-        __syncthreads();
-    }
-}
-
-int launch_tilted_integral(const TiltedArgs& a, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const size_t lds = (size_t)3 * (a.width + 1u) * sizeof(uint32_t);
-    if (lds > 160u * 1024u) return (int)hipErrorInvalidValue;
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute((const void*)tilted_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(tilted_rows, dim3(a.n_frames), dim3(1024), lds, stream, a);
-    return (int)hipGetLastError();
-}
-
-// The same image without the row-by-row dependency (1080 barriers deep: 1.25 ms whatever the batch).  With zero outside the frame,
+// Not by cvIntegral's row recurrence (each row depends on the two above: 1080 barriers deep, 1.25 ms whatever the batch).  With zero
+// outside the frame,
 //   A(x, y) = sum_k I(x - k, y - k)   (the "\" diagonal ending at (x, y)),    B(x, y) = sum_k I(x + k, y - k)   (the "/" diagonal),
 // the triangle with its apex at pixel (x, y) is the one with its apex at (x, y - 1) plus both diagonals through (x, y):
 //   Tri(x, y) = Tri(x, y - 1) + A(x, y) + B(x, y) - I(x, y),        tilted(X, Y) = Tri(X - 1, Y - 1)
 // — a column prefix of C = A + B - I, and A and B are column prefixes of the image sheared one way and the other.  Three prefix sums
 // over the rows, each in bands of 8 rows like the upright integral: per-band totals, an exclusive scan over the bands, the rows of a
 // band from its prefix.  Integer adds mod 2^32 in another order: the same image, bit for bit (vj_integral_tilted's tests compare
-// both kernels with the oracle's direct sum).  diag: [frame][band][2][W + H] (A by x - y + H - 1, B by x + y), col: [frame][band][W + 1].
+// it with the oracle's direct sum).  diag: [frame][band][2][W + H] (A by x - y + H - 1, B by x + y), col: [frame][band][W + 1].
 constexpr uint32_t TILT_ROWS = 8;
 __device__ __forceinline__ uint32_t tilt_px(const TiltedArgs& a, const uint8_t* img, int32_t x, int32_t y) {
     if (x < 0 || y < 0 || x >= (int32_t)a.width || y >= (int32_t)a.height) return 0u;

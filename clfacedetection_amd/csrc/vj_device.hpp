@@ -36,7 +36,6 @@ struct ScaleDev {
                            // first, odd columns from element tile_half on (window origins are all even, so a
                            // wave's gathers of one corner touch CONSECUTIVE dwords: no bank conflicts)
     int32_t  te_dw;        // equ_rect left->right distance in tile elements (signed when de-interleaved)
-    uint32_t tile_x4;      // rows are staged 16 bytes per lane (pitch is a multiple of 4 dwords)
     uint32_t skip_base;    // P2 skip modes: first word of this scale in a frame's visited-window bitmap
     uint32_t skip_wpr;     // ... words per window row (VJ_FLAG_SKIP_ROW); 0: one flattened bit list (VJ_FLAG_SKIP_LIST)
     float    scale_f;      // s_k itself, and the scaled window: what a region of interest needs to lay out its own grid
@@ -50,7 +49,7 @@ struct ScaleDev {
     uint32_t grp_te_dh;
     int32_t  grp_te_dw;
 };
-static_assert(sizeof(ScaleDev) == 144, "ScaleDev is 144 bytes");
+static_assert(sizeof(ScaleDev) == 140, "ScaleDev is 140 bytes");
 
 // One cascade stage with its resolved successors (tempcv.cpp:834-861 flattened).
 struct StageDev {
@@ -165,13 +164,11 @@ struct CascadeArgs {
     uint32_t stage_begin, stage_end;  // stages [begin, end) evaluated by this pass
     uint32_t total_waves;       // gridDim.x * gather_waves
     uint32_t gather_waves;      // waves per workgroup of cascade_pass / cascade_roi_pass (3 or 4; stage trees: 3)
-    uint32_t xcd_affinity;      // grid pass: waves of one XCD share a contiguous part of the (frame, unit) list
     const QEntry*   q_in;       // survivor queue read by this pass (passes > 0)
     const uint32_t* q_in_count; // entry counts of q_in, [scale][Q_PARTS]
     uint32_t* q_ticket;         // Q_PARTS chunk-ticket counters of this queue pass (zeroed before the launch)
     uint32_t wide_tail;         // queue passes: the stump-parallel tail keeps several windows' gathers in flight (small batches)
     uint32_t min_chunk;         // queue passes: smallest chunk of windows a wave draws (1..64)
-    uint32_t thin_pass_spread;  // queue passes with fewer chunks than waves: only the first workgroups draw tickets (even load per CU)
     uint32_t q_slices;          // queue passes: a part's chunks are handed out in this many slices of every scale's range (frame-major order)
     // Band-major queue pass (batches; linear cascades): the first pass records where every unit's survivors landed in their
     // (scale, part) sub-queue (run_table[frame * n_units + unit] = {first entry, count}); the queue pass then draws GROUPS of
@@ -195,19 +192,17 @@ struct CascadeArgs {
     uint32_t  tile_end;                     // deepest stage a tile launch may enter
     uint32_t  tile_min_lanes;               // leave at a pass boundary when the whole tile has fewer survivors
     unsigned long long tile_repack_mask;    // bit s: re-pack the tile's survivors across its waves before stage s
-    // Stump-parallel finish (stump cascades): once a tile is down to <= TILE_SP_MAX_WINDOWS windows at a
-    // re-pack point at or after tile_sp_begin, its 512 lanes evaluate (window, stump) pairs in parallel
-    // and one lane per window adds the stump values in cascade order — through the last stage.
+    // Finish of a tile: once it is down to <= tile_ws_max windows at a re-pack point at or after tile_sp_begin, it
+    // runs the rest of the cascade itself with the wave-split finish (tile_wave_split) and, below tile_ws_min windows
+    // (stump cascades), the stump-parallel finish (tile_stump_parallel) — through the last stage.
     uint32_t  tile_sp_begin;                // >= number of stages: disabled
-    uint32_t  tile_sp_pad;                  // dwords of LDS reserved for the finish: two record blocks + leaf values (0 = off)
-    uint32_t  tile_sp_max;                  // enter the finish when at most this many windows are left
+    uint32_t  tile_sp_pad;                  // dwords of LDS reserved for the stump-parallel finish: two record blocks + leaf values (0 = off)
     uint32_t  identity_order;               // StageDev::order is 0, 1, 2, ... (every linear cascade)
     uint32_t  n_seg;                        // stage tree: chains after the linear prefix that a tile may run itself (0: none)
     uint32_t  seg_end[4];                   // ... end position (sweep order) of chain k; it starts where chain k-1 (or the prefix) ends
     uint32_t  seg_chain;                    // ... bit k: the rejects of chain k are the population of chain k+1
     uint32_t  tree2;                        // every tree has exactly two nodes, the second one the child of the first
-    uint32_t  tile_finish;                  // 0: stump-parallel finish, 1: wave-split finish (tile_wave_split)
-    uint32_t  tile_ws_min;                  // ... and hand over to the stump-parallel finish below this many
+    uint32_t  tile_ws_min;                  // the wave-split finish hands over to the stump-parallel finish below this many
     uint32_t  tile_ws_max;                  // enter the wave-split finish when at most this many windows are left
     const SpBlock* sp_blocks;               // per block of <= 64 stumps, all stages in order
     uint32_t  n_sp_blocks;
@@ -256,7 +251,7 @@ constexpr int BAND_ROWS = 8;
 int launch_integral(const IntegralArgs& a, void* stream);
 int launch_cascade_pass(const CascadeArgs& a, bool from_grid, bool trees, bool last, bool count, bool general,
                         int n_blocks, void* stream);
-int launch_cascade_tile_pass(const CascadeArgs& a, bool trees, bool count, bool staged, int n_blocks, void* stream);
+int launch_cascade_tile_pass(const CascadeArgs& a, bool trees, bool count, int n_blocks, void* stream);
 
 // Regions of interest on the device (vj_detect_chain).
 struct RoiArgs {
@@ -421,7 +416,6 @@ struct CvArgs {
     CvChainDev chains;           // stage trees made of chains (else n = 0)
     void* fail_scratch;          // ... CV_QCAP x 16 bytes per wave: where a chain's rejects wait for the next chain
     uint32_t tail_max;           // linear cascades: a wave's queue of at most this many windows evaluates a stage stump-parallel (<= CV_TAIL_MAX)
-    uint32_t pairs;              // ... larger populations evaluate two stumps per step (all gathers in flight)
     uint32_t tree2;              // every tree is a root + its only node child, upright (frontalface_alt2): both nodes' gathers in flight
 };
 
@@ -515,7 +509,8 @@ struct TiltedArgs {
     uint32_t frame_elems;
     uint32_t* tilted;           // [frames][frame_elems], rows of W + 1
 };
-int launch_tilted_integral(const TiltedArgs& a, void* stream);
+// the tilted integral as three banded prefix sums; diag: n_frames x bands x 2 x (W + H) dwords, col: n_frames x bands x (W + 1)
+int launch_tilted_bands(const TiltedArgs& a, uint32_t* diag, uint32_t* col, void* stream);
 int launch_grayscale(const TiltedArgs& a, uint8_t* dst, uint32_t dst_stride, void* stream);
 
 }  // namespace vj

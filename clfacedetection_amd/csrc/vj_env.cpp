@@ -233,12 +233,10 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
                     for (uint32_t th : kTh) {
                         const uint32_t nwt = tw * th;
                         if (nwt > TILE_WAVES * TILE_WAVE_CAP || nwt < 64 || nwt <= best_n) continue;
-                        // rows staged 16 bytes per lane (tile_stage_x4; not the de-interleaved step-2 tiles, whose
-                        // sources are 8 bytes apart): pitch a multiple of 4 dwords, not of 32 (rows would share banks);
-                        // otherwise an odd pitch
-                        const bool x4 = e->tile_stage_x4 && !(e->tile_deinterleave && si.step == 2.0f);
+                        // rows staged 16 bytes per lane (not the de-interleaved step-2 tiles, whose sources are 8 bytes
+                        // apart): pitch a multiple of 4 dwords, not of 32 (rows would share banks); step 2: an odd pitch
                         uint32_t pitch = (uint32_t)std::ceil((double)(tw - 1) * (double)si.step) + 3u + reach_x;
-                        if (x4) {
+                        if (si.step != 2.0f) {
                             pitch = (pitch + 3u) & ~3u;
                             if (pitch % 32u == 0u) pitch += 4u;
                         } else {
@@ -264,13 +262,11 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
             sd.tile_table_first = (uint32_t)table.size();
             table.resize(table.size() + n_nodes);
             // step exactly 2: every window origin is an even column -> de-interleave the tile rows
-            sd.tile_half = (e->tile_deinterleave && si.step == 2.0f) ? (sd.tile_pitch + 1u) / 2u : 0u;
-            sd.tile_x4 = (e->tile_stage_x4 && !sd.tile_half && sd.tile_pitch % 4u == 0u) ? 1u : 0u;
+            sd.tile_half = si.step == 2.0f ? (sd.tile_pitch + 1u) / 2u : 0u;
             if (getenv("VJ_DEBUG_PLAN"))
-                fprintf(stderr, "vj plan: scale %d s=%.3f step=%.2f nx=%u ny=%u class %u tile %ux%u = %u windows, pitch %u rows %u (%u B)%s%s\n",
+                fprintf(stderr, "vj plan: scale %d s=%.3f step=%.2f nx=%u ny=%u class %u tile %ux%u = %u windows, pitch %u rows %u (%u B)%s\n",
                         si.scale_idx, si.scale, si.step, sd.nx, sd.ny, sd.tile_class, sd.tile_tw, sd.tile_th, sd.tile_tw * sd.tile_th,
-                        sd.tile_pitch, sd.tile_rows, sd.tile_pitch * sd.tile_rows * 4u, sd.tile_half ? " deinterleaved" : "",
-                        sd.tile_x4 ? " x4" : "");
+                        sd.tile_pitch, sd.tile_rows, sd.tile_pitch * sd.tile_rows * 4u, sd.tile_half ? " deinterleaved" : " x4");
             rc = build_node_table_stride(c, sd.tile_pitch, si, table.data() + sd.tile_table_first, sd.tile_half);
             if (rc) return rc;
             auto col = [&](uint32_t cx) { return sd.tile_half ? (cx & 1u) * sd.tile_half + (cx >> 1) : cx; };
@@ -283,11 +279,6 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
             sd.grp_te_lt = sd.te_lt;
             sd.grp_te_dh = sd.te_dh;
             sd.grp_te_dw = sd.te_dw;
-        } else {
-            // unstaged in the tile kernel (global_blocks): 2-D blocks of <= 2048 windows, about as wide as high
-            sd.tile_tw = std::min<uint32_t>(sd.nx, 48u);
-            sd.tile_th = std::min<uint32_t>(sd.ny, (uint32_t)(TILE_WAVES * TILE_WAVE_CAP) / sd.tile_tw);
-            sd.tile_row_end = 0;
         }
         pl->scales.push_back(sd);
         pl->scales_info.push_back(si);
@@ -539,32 +530,20 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
     // chain's workgroup holds a block somewhere in the middle of the LDS, so the k workgroups of one class have to
     // fit exactly into the hole the workgroup(s) of the other class leave behind (measured: a class-0 pair 2 KB
     // larger than the class-1 block it follows leaves one tile workgroup per CU idle, + 17 % on that launch).
-    if (e->tile_lds_nest) {
-        const uint32_t lds_cu = (160u - (uint32_t)e->tile_lds_reserve_kb) * 1024u;
-        for (uint32_t cls = 0; cls + 1 < TILE_CLASSES; ++cls) {
-            const int ka = e->tile_class_kb[cls], kb = e->tile_class_kb[cls + 1];
-            if (ka >= 0 || kb >= 0 || !pl->class_lds[cls] || !pl->class_lds[cls + 1]) continue;
-            const uint32_t na = (uint32_t)(-ka), nb = (uint32_t)(-kb);   // workgroups per CU: na > nb
-            if (na <= nb || na % nb != 0u) continue;
-            const uint32_t ratio = na / nb;
-            uint32_t big = std::max(pl->class_lds[cls + 1], ratio * pl->class_lds[cls]);
-            // whole allocation granules (the hardware hands LDS out in 512-byte granules; 1 KiB is safe)
-            big = (big + ratio * 1024u - 1u) / (ratio * 1024u) * (ratio * 1024u);
-            if ((uint64_t)big * nb > lds_cu) continue;
-            pl->class_lds[cls + 1] = big;
-            pl->class_lds[cls] = big / ratio;
-        }
+    const uint32_t lds_cu = (160u - (uint32_t)e->tile_lds_reserve_kb) * 1024u;
+    for (uint32_t cls = 0; cls + 1 < TILE_CLASSES; ++cls) {
+        const int ka = e->tile_class_kb[cls], kb = e->tile_class_kb[cls + 1];
+        if (ka >= 0 || kb >= 0 || !pl->class_lds[cls] || !pl->class_lds[cls + 1]) continue;
+        const uint32_t na = (uint32_t)(-ka), nb = (uint32_t)(-kb);   // workgroups per CU: na > nb
+        if (na <= nb || na % nb != 0u) continue;
+        const uint32_t ratio = na / nb;
+        uint32_t big = std::max(pl->class_lds[cls + 1], ratio * pl->class_lds[cls]);
+        // whole allocation granules (the hardware hands LDS out in 512-byte granules; 1 KiB is safe)
+        big = (big + ratio * 1024u - 1u) / (ratio * 1024u) * (ratio * 1024u);
+        if ((uint64_t)big * nb > lds_cu) continue;
+        pl->class_lds[cls + 1] = big;
+        pl->class_lds[cls] = big / ratio;
     }
-    pl->block_first = (uint32_t)pl->tile_units.size();
-    if (!pl->general && !pl->trees)
-        for (uint32_t slot = 0; slot < pl->scales.size(); ++slot) {
-            const ScaleDev& sd = pl->scales[slot];
-            for (uint32_t iy0 = sd.tile_row_end; iy0 < sd.ny; iy0 += sd.tile_th)
-                for (uint32_t ix0 = 0; ix0 < sd.nx; ix0 += sd.tile_tw)
-                    pl->tile_units.push_back(UnitDev{slot, ix0 | (iy0 << 16), 0, 0});
-        }
-    pl->n_block_units = (uint32_t)pl->tile_units.size() - pl->block_first;
-    pl->block_lds = tile_header_bytes;
 
     // P2 skip modes: one bitmap word per 64 consecutive windows of a recurrence domain — a window row
     // (VJ_FLAG_SKIP_ROW, clod.cpp:1430) or a scale's whole row-major list (VJ_FLAG_SKIP_LIST, clod.cpp:729-732)
@@ -1022,15 +1001,10 @@ int enqueue_tilted(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int str
     ta.n_frames = (uint32_t)frames;
     ta.frame_elems = fe;
     ta.tilted = (uint32_t*)e->d_tilted.p;
-    int hrc;
-    if (e->tilted_bands) {
-        const size_t n_bands = ((size_t)H + 7u) / 8u;
-        if ((rc = e->d_tilt_diag.ensure((size_t)frames * n_bands * 2u * (size_t)(W + H) * 4u))) return rc;
-        if ((rc = e->d_tilt_col.ensure((size_t)frames * n_bands * (size_t)(W + 1) * 4u))) return rc;
-        hrc = launch_tilted_bands(ta, (uint32_t*)e->d_tilt_diag.p, (uint32_t*)e->d_tilt_col.p, e->stream);
-    } else {
-        hrc = launch_tilted_integral(ta, e->stream);
-    }
+    const size_t n_bands = ((size_t)H + 7u) / 8u;
+    if ((rc = e->d_tilt_diag.ensure((size_t)frames * n_bands * 2u * (size_t)(W + H) * 4u))) return rc;
+    if ((rc = e->d_tilt_col.ensure((size_t)frames * n_bands * (size_t)(W + 1) * 4u))) return rc;
+    const int hrc = launch_tilted_bands(ta, (uint32_t*)e->d_tilt_diag.p, (uint32_t*)e->d_tilt_col.p, e->stream);
     if (hrc) {
         set_error("tilted integral launch failed (width %d): %s", W, hipGetErrorString((hipError_t)hrc));
         return hrc == (int)hipErrorInvalidValue ? VJ_ERR_LIMIT : VJ_ERR_HIP;
@@ -1235,7 +1209,7 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
         ca.units = (const UnitDev*)pl->d_units.p;
         ca.n_units = (uint32_t)pl->units.size();
         ca.tile_units = (const UnitDev*)pl->d_tile_units.p;
-        ca.n_tile_units = pl->block_first;   // staged tiles; the unstaged blocks follow them in the list
+        ca.n_tile_units = (uint32_t)pl->tile_units.size();
         ca.n_frames = (uint32_t)nf;
         ca.n_scales = (uint32_t)pl->scales.size();
         ca.frame_elems = pl->frame_elems;
@@ -1271,9 +1245,6 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
         ca.tile_sp_pad = pl->sp_pad;
         ca.sp_blocks = (const SpBlock*)pl->d_sp_blocks.p;
         ca.n_sp_blocks = pl->n_sp_blocks;
-        ca.tile_sp_max = (uint32_t)std::min(e->tile_sp_max, (int)TILE_SP_MAX_WINDOWS);
-        ca.xcd_affinity = (uint32_t)e->xcd_affinity;
-        ca.tile_finish = (uint32_t)e->tile_finish;
         ca.tile_ws_min = pl->sp_pad != 0u ? (uint32_t)e->tile_ws_min : 0u;   // no stump-parallel tables: wave-split to the end
         ca.tile_ws_max = (uint32_t)std::min(e->tile_ws_max, (int)TILE_WS_MAX_WINDOWS);
         ca.pos_mode = pl->pos_mode;
@@ -1314,7 +1285,7 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
                 const ScaleDev& sd = pl->scales[slot];
                 const bool in = kind == VJ_LAUNCH_QUEUE ||
                                 (kind == VJ_LAUNCH_TILE && sd.tile_rw && sd.tile_row_end > 0 && (int)pl->scales[pl->tile_lead[slot]].tile_class == cls) ||
-                                ((kind == VJ_LAUNCH_GRID || kind == VJ_LAUNCH_BLOCK) && sd.tile_row_end < sd.ny);
+                                (kind == VJ_LAUNCH_GRID && sd.tile_row_end < sd.ny);
                 if (in && sd.scale_idx < 128) li.scale_mask[sd.scale_idx >> 6] |= 1ull << (sd.scale_idx & 63);
             }
             linfo.push_back(li);
@@ -1335,7 +1306,7 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
         // they run the whole cascade themselves only when tile_end lies BEYOND the boundary (at tile_end == pass_bounds[1] they
         // hand their survivors to q_pass[1], and the chunked pass, which sweeps the whole sub-queue, takes the batch)
         const bool banded = e->q_band_px > 0 && !pl->unit_groups.empty() && !pl->general && n_pass == 2 && nf >= e->q_band_min_frames &&
-                            e->tile_min_lanes == 0 && (uint32_t)e->tile_end > pl->pass_bounds[1] && !(e->global_blocks && pl->n_block_units > 0 && pl->sp_pad != 0);
+                            e->tile_min_lanes == 0 && (uint32_t)e->tile_end > pl->pass_bounds[1];
         if (banded) {
             if ((rc = e->d_run_table.ensure((size_t)nf * pl->units.size() * 8u))) return rc;
             ca.run_table = (uint32_t*)e->d_run_table.p;
@@ -1352,7 +1323,6 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
             qa.q_in = (const QEntry*)dq[ps].p;
             qa.q_in_count = qc[ps];
             qa.q_ticket = qc[0] + ps * Q_PARTS;   // queue 0 does not exist: its counters serve as tickets
-            qa.thin_pass_spread = e->thin_pass_spread ? 1u : 0u;
             // frame-major order inside a part: one slice per frame of the part's frame group (-1), or as configured
             qa.q_slices = e->q_slices >= 0 ? (uint32_t)std::max(1, e->q_slices)
                                            : (uint32_t)std::max(1, std::min(16, (nf + (int)Q_PARTS - 1) / (int)Q_PARTS));
@@ -1382,14 +1352,13 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
             size_t first_joint_pass = 1;
             if (e->tile_min_lanes == 0)
                 while (first_joint_pass < n_pass && pl->pass_bounds[first_joint_pass] < handover) ++first_joint_pass;
-            const bool use_blocks = e->global_blocks && pl->n_block_units > 0 && pl->sp_pad != 0;
-            const bool two_streams = e->concurrent && pl->block_first > 0 && ca.n_units > 0;
+            const bool two_streams = e->concurrent && ca.n_tile_units > 0 && ca.n_units > 0;
             // Stage tree in chains (seg_last): the chains' queue passes would have to wait for BOTH the grid pass and the
             // tiles, because a crowded tile hands its windows to the same queues — and the tiles take longer than the grid
             // pass (4096 x 4096: 7.8 vs 4.8 ms, then 7.8 ms of queue passes).  So the tiles get a queue set of their own:
             // the grid pass's survivors go down the tree on stream B while the tiles still run, and after the join the same
             // passes run once more on what the tiles left (usually little: thin passes).
-            const bool split_sets = two_streams && pl->general && !pl->seg_last.empty() && e->tree_split_queues && !use_blocks;
+            const bool split_sets = two_streams && pl->general && !pl->seg_last.empty() && e->tree_split_queues;
             if (split_sets) {
                 for (size_t ps = 1; ps < n_pass; ++ps) {
                     if ((rc = e->d_q2[ps].ensure(e->d_q[ps].cap))) return rc;
@@ -1407,7 +1376,9 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
             // chain A: tile launches
             auto chain_a = [&]() -> int {
             for (uint32_t ci = 0; ci < TILE_CLASSES && !hrc && ca.n_tile_units > 0; ++ci) {
-                const uint32_t cls = e->tile_class_order ? TILE_CLASSES - 1u - ci : ci;
+                // largest LDS first: the one-workgroup-per-CU class suffers most from the gather chain, whose first pass is
+                // the heavier one (measured: 48.3 -> 47.2 ms)
+                const uint32_t cls = TILE_CLASSES - 1u - ci;
                 const uint32_t n_cls = pl->class_first[cls + 1] - pl->class_first[cls];
                 if (!n_cls) continue;
                 CascadeArgs ta = ca;
@@ -1421,7 +1392,7 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
                 const uint32_t deepest = std::min<uint32_t>((uint32_t)pl->stages.size(), handover);
                 if ((rc = begin_launch(VJ_LAUNCH_TILE, (int)cls, 0, deepest, ta.tile_lds_bytes, e->stream))) return rc;
                 ta.stage_entered = launch_counters();
-                hrc = launch_cascade_tile_pass(ta, pl->trees, count, true, std::max(1, tb), e->stream);
+                hrc = launch_cascade_tile_pass(ta, pl->trees, count, std::max(1, tb), e->stream);
                 if ((rc = end_launch(e->stream))) return rc;
             }
                 return VJ_OK;
@@ -1431,20 +1402,7 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
             // one wave per SIMD), so that the tile workgroups find their LDS share next to it.
             const int b_blocks = two_streams ? std::max(1, e->n_cu * e->concurrent_blocks_per_cu) : n_blocks;
             auto chain_b = [&]() -> int {
-            if (!hrc && use_blocks) {
-                CascadeArgs ta = ca;
-                ta.tile_units = (const UnitDev*)pl->d_tile_units.p + pl->block_first;
-                ta.n_tile_units = pl->n_block_units;
-                ta.tile_lds_bytes = pl->block_lds;
-                ta.tile_ticket = d_qcount[0] + (q_counts - 8u * (TILE_CLASSES + 1u));
-                const int per_cu = two_streams ? e->concurrent_blocks_per_cu : 2;
-                const int tb = (int)std::min<uint64_t>((uint64_t)pl->n_block_units * (uint64_t)nf, (uint64_t)e->n_cu * (uint64_t)per_cu);
-                const uint32_t deepest = std::min<uint32_t>((uint32_t)pl->stages.size(), handover);
-                if ((rc = begin_launch(VJ_LAUNCH_BLOCK, 0, 0, deepest, ta.tile_lds_bytes, sB))) return rc;
-                ta.stage_entered = launch_counters();
-                hrc = launch_cascade_tile_pass(ta, false, count, false, std::max(1, tb), sB);
-                if ((rc = end_launch(sB))) return rc;
-            } else if (!hrc && ca.n_units > 0) {
+            if (!hrc && ca.n_units > 0) {
                 CascadeArgs ga = queue_args(0);
                 ga.total_waves = (uint32_t)b_blocks * ga.gather_waves;
                 if ((rc = begin_launch(VJ_LAUNCH_GRID, 0, ga.stage_begin, ga.stage_end, 0, sB))) return rc;
@@ -1815,9 +1773,6 @@ static void fill_region_args(vj_env* e, Lane* L, Plan* pl2, const vj_cascade* se
         ca.tile_sp_pad = pl2->sp_pad;
         ca.sp_blocks = (const SpBlock*)pl2->d_sp_blocks.p;
         ca.n_sp_blocks = pl2->n_sp_blocks;
-        ca.tile_sp_max = (uint32_t)std::min(e->tile_sp_max, (int)TILE_SP_MAX_WINDOWS);
-        ca.xcd_affinity = (uint32_t)e->xcd_affinity;
-        ca.tile_finish = (uint32_t)e->tile_finish;
         ca.tile_ws_min = (uint32_t)e->tile_ws_min;
         ca.tile_ws_max = (uint32_t)std::min(e->tile_ws_max, (int)TILE_WS_MAX_WINDOWS);
     }
@@ -2193,16 +2148,9 @@ const Key KEYS[] = {
     bounded("tile_max_dwords_per_window", &Tunables::tile_max_dwords_per_window, 0, 65536, DROP_PLANS | SET_THRESHOLDS),
     bounded("tile_end", &Tunables::tile_end, 0, 65536, DROP_PLANS),
     bounded("tile_min_lanes", &Tunables::tile_min_lanes, 0, 65536, DROP_PLANS),
-    int_flag("tile_class_order", &Tunables::tile_class_order),
-    int_flag("tile_lds_nest", &Tunables::tile_lds_nest, DROP_PLANS),
     special("tile_repack", set_tile_repack, get_tile_repack),
-    int_flag("tile_deinterleave", &Tunables::tile_deinterleave, DROP_PLANS),
-    int_flag("tile_stage_x4", &Tunables::tile_stage_x4, DROP_PLANS),
-    int_flag("global_blocks", &Tunables::global_blocks),
     // tile finish
-    int_flag("tile_finish", &Tunables::tile_finish),
     clamped("tile_sp_begin", &Tunables::tile_sp_begin, 0, MAX, DROP_PLANS),   // the LDS layout of the tile launches depends on it
-    clamped("tile_sp_max", &Tunables::tile_sp_max, 0, TILE_SP_MAX_WINDOWS),
     clamped("tile_ws_min", &Tunables::tile_ws_min, 0, TILE_SP_MAX_WINDOWS),
     clamped("tile_ws_max", &Tunables::tile_ws_max, 0, TILE_WS_MAX_WINDOWS),
     // chain balance
@@ -2215,7 +2163,6 @@ const Key KEYS[] = {
             DROP_PLANS | SET_SPLIT | CLEAR_BALANCE),
     special("auto_balance", set_auto_balance, [](const vj_env* e, std::string& s) { s = std::to_string((int)e->auto_balance); },
             CLEAR_BALANCE),
-    flag("balance_exact", &Tunables::balance_exact, CLEAR_BALANCE),
     special("balance_export", [](vj_env* e, const char* path) { return balance_export(e, path); }, nullptr),
     special("balance_import", [](vj_env* e, const char* path) { return balance_import(e, path); }, nullptr),
     // global-gather chain
@@ -2225,9 +2172,7 @@ const Key KEYS[] = {
     clamped("sp_tail_max", &Tunables::sp_tail_max, 0, 48),
     with_auto("wide_tail", &Tunables::wide_tail, 0, 1),
     clamped("min_chunk", &Tunables::min_chunk, 1, 64),
-    flag("thin_pass_spread", &Tunables::thin_pass_spread),
     with_auto("q_slices", &Tunables::q_slices, 0, 64),
-    int_flag("xcd_affinity", &Tunables::xcd_affinity),
     clamped("q_band_px", &Tunables::q_band_px, 0, MAX, DROP_PLANS),
     clamped("q_group_units", &Tunables::q_group_units, 0, MAX, DROP_PLANS),
     clamped("q_band_min_frames", &Tunables::q_band_min_frames, 1, MAX),
@@ -2252,11 +2197,9 @@ const Key KEYS[] = {
     clamped("cv_tree_chunk", &Tunables::cv_tree_chunk, 1, MAX),
     clamped("cv_tree_chain_blocks", &Tunables::cv_tree_chain_blocks, 1, MAX),
     clamped("cv_tail_max", &Tunables::cv_tail_max, 0, CV_TAIL_MAX, DROP_PLANS),
-    flag("cv_pairs", &Tunables::cv_pairs),
     clamped("cv_row_band_px", &Tunables::cv_row_band_px, 0, MAX, DROP_PLANS),
     flag("cv_tree2", &Tunables::cv_tree2, DROP_PLANS),   // (the default balance depends on it)
     flag("cv_tiles_tilted", &Tunables::cv_tiles_tilted, DROP_PLANS),
-    flag("tilted_bands", &Tunables::tilted_bands),
     clamped("cv_tree_queue_cap", &Tunables::cv_tree_queue_cap, 0, MAX),
     // single frames, integral, housekeeping
     clamped("one_pass_max_frames", &Tunables::one_pass_max_frames, 0, MAX),   // (part of the plan key: nothing to drop)

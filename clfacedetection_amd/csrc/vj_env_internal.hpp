@@ -63,8 +63,6 @@ struct Plan {
     std::vector<uint32_t> tile_lead;         // per scale: the largest scale of its tile group (itself when not grouped)
     uint32_t class_first[TILE_CLASSES + 1] = {};  // tile_units range of each class
     uint32_t class_lds[TILE_CLASSES] = {};        // dynamic LDS bytes of each class launch
-    uint32_t block_first = 0, n_block_units = 0;  // tile_units range of the unstaged 2-D blocks (global-gather scales)
-    uint32_t block_lds = 0;
     uint32_t tile_end = 0;                        // stage at which the tile launches stop
     bool tree2 = false;                           // every tree: two nodes, node 1 the only node child of node 0
     uint32_t sp_pad = 0;                          // LDS pitch of the stump-parallel stage table (0 = off)
@@ -131,8 +129,6 @@ namespace vj {
 // the events that time it.  vj_detect uses the environment's own lane; a vj_stream owns two, so that the upload of
 // batch k+1 can run while the kernels of batch k do.  Integral images, survivor queues and plans are shared: the
 // kernels of successive batches are ordered on the environment's stream.
-// (vj_cv_profile.hip) the tilted integral as three banded prefix sums; diag: n_frames x bands x 2 x (W + H) dwords, col: n_frames x bands x (W + 1)
-int launch_tilted_bands(const TiltedArgs& a, uint32_t* diag, uint32_t* col, void* stream);
 
 struct Lane {
     DevBuf d_gray, d_counts, d_det;
@@ -198,20 +194,15 @@ struct Tunables {
     float split_for(int n_frames, const vj_params& p) const {
         return ((p.scale_mask[0] | p.scale_mask[1]) != 0 && !tile_split_set) ? 0.0f : split_for(n_frames);
     }
-    int xcd_affinity = 1;               // global-gather first pass: one contiguous part of the work per XCD (L2 locality)
     int tile_segments = 1;              // stage trees: tiles run the chains after the prefix themselves
     int seg_cut2 = 0;                   // stage trees: a second cut inside a long chain after this many of its stages (0: none)
     int general_prefix = 1;             // stage trees: run their linear prefix on the linear kernels (0: one general pass)
     int grid_block_w = 32;              // width of the 2-D window blocks of the global-gather first pass (0: row runs)
-    int global_blocks = 0;              // 1: large scales run as unstaged 2-D blocks in the tile kernel (stump cascades): 2.2x
-                                        // faster than grid + queue passes on its own, but it overlaps the tile chain badly
     int tile_lds_reserve_kb = 16;       // LDS per CU the tile classes leave to the other chain (its 3-wave workgroup: 12 KiB + granule
                                         // rounding; with 14 the CU's 160 KiB do not take two class-0 blocks next to it any more)
-    bool tilted_bands = true;       // the tilted integral as three banded prefix sums (0: the row-by-row recurrence, one workgroup per frame)
     int roi_tile_min_windows = 512;   // region pass: (region, scale) grids of at least this many windows run on LDS tiles (0: never)
-    bool balance_exact = false;   // key on the exact frame count, as round 3 did ("balance_exact": for the before / after of tools/balance_service.py)
     int balance_class(int n_frames) const {
-        return balance_exact || n_frames < 8 ? n_frames : n_frames < 16 ? 8 : n_frames < 32 ? 16 : n_frames < 64 ? 32 : 64;
+        return n_frames < 8 ? n_frames : n_frames < 16 ? 8 : n_frames < 32 ? 16 : n_frames < 64 ? 32 : 64;
     }
     bool auto_balance = true, tile_split_set = false;
     int plan_cache_max = 48;      // plans kept per environment; the least recently used one is released beyond that
@@ -228,16 +219,9 @@ struct Tunables {
     int tile_end = 64;            // tile launches never enter a pass that begins at or beyond this stage
     int tile_min_lanes = 0;       // a tile leaves at a pass boundary when fewer windows than this survive in it
     unsigned long long tile_repack_mask = ~3ull;  // stages (2 and later) before which a tile re-packs its survivors
-    int tile_sp_begin = 3;        // first stage at which a tile may switch to the stump-parallel finish (>= 64: never)
-    int tile_sp_max = 192;        // ... once at most this many of its windows survive
-    int tile_finish = 1;          // 0: stump-parallel finish, 1: wave-split finish
+    int tile_sp_begin = 3;        // first stage at which a tile may switch to the wave-split finish (>= 64: never)
     int tile_ws_max = 512;        // windows a tile may carry into the wave-split finish
     int tile_ws_min = 48;         // ... below this many the stump-parallel finish takes over
-    int tile_class_order = 1;     // 1: launch the tile classes largest-LDS first (measured: 48.3 -> 47.2 ms; the one-workgroup-per-CU
-                                  // class suffers most from the gather chain, whose first pass is the heavier one)
-    int tile_lds_nest = 1;        // LDS blocks of consecutive tile classes nest (k blocks of one = one block of the next)
-    int tile_stage_x4 = 1;        // stage tile rows with 16-byte LDS-DMA loads (4x fewer texture-address instructions)
-    int tile_deinterleave = 1;    // de-interleave the LDS tile rows of the step-2 scales
     int group_max = (int)vj::GROUP_MAX;   // vj_detect_chain groups up to this many raw candidates of one frame on the device (more: host path)
     bool tree_split_queues = true; // stage trees: the grid pass's survivors go down the tree while the tiles still run
     bool cv_tiles = true;         // OpenCV profile: small scales of stump cascades on LDS tiles (vj_cv_tile.hip)
@@ -245,7 +229,6 @@ struct Tunables {
     int cv_row_blocks = -1;       // ... workgroups per CU of cv_profile_pass while it runs next to the tiles (their LDS budget shrinks with it);
                                   // -1: 2 for stump cascades (round 4: the row kernel's pair / stump-parallel forms need fewer waves), 3 for multi-node trees
     int cv_row_blocks_tree = 2, cv_tile_min_windows_tree = 256;   // ... the same two for stage trees (swept: profiles/r03_cv_sweeps.log)
-    bool cv_pairs = false;            // ... linear cascades' row kernel: two stumps per step in the sweeps of its queue
     int cv_tail_max = 64;             // ... a population of at most this many windows evaluates a stage stump-parallel (<= 64)
     int cv_tree_chunk = 64, cv_tree_chain_blocks = 2;   // ... windows per chunk and workgroups per CU of cv_tree_chain_pass
     bool cv_tiles_tilted = true;      // ... cascades with tilted features on LDS tiles too (the tilted integral's tile staged behind the sum's)
@@ -263,7 +246,6 @@ struct Tunables {
     int q_group_units = 4;        // ... units per group (their survivors fill a wave's 512-entry queue about once: 2-4 equal, 5 / 6 / 8 / 16 lose 0.5 / 1 / 2-3 / 3-7 ms of 42.5)
     int q_band_min_frames = 8;    // ... batches of at least this many frames (a single frame keeps the thin-pass machinery)
     int q_slices = -1;            // queue passes: slices of a part handed out frame-major (-1: one per frame of the part's frame group)
-    bool thin_pass_spread = true; // queue passes with fewer chunks than waves: only the first workgroups draw tickets
     int sp_tail_max = 48;         // global-gather sweeps switch to the stump-parallel tail when a wave holds at most this many windows (0: never)
     int gather_pairs = -1;        // global-gather sweeps evaluate two stumps per step, all their gathers in flight together: 0 never, 1 for
                                   // waves that hold a single chunk, 2 always, -1 = by batch size: 2 up to 4 frames (a single frame is bound

@@ -1247,7 +1247,7 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
         // share an XCD — and its 4 MiB L2 — take one contiguous eighth of the (frame, unit) list, i.e. they work on
         // the same frame's sum image at the same time instead of on every frame in flight.
         uint32_t u_begin = 0, u_end = total_units, u_step = a.total_waves, u_first = rank;
-        if (a.xcd_affinity != 0u && gridDim.x >= 8u) {
+        if (gridDim.x >= 8u) {
             const uint32_t xcd = blockIdx.x & 7u;
             u_begin = (uint32_t)((unsigned long long)total_units * xcd / 8u);
             u_end = (uint32_t)((unsigned long long)total_units * (xcd + 1u) / 8u);
@@ -1316,7 +1316,7 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
         kptr<UnitDev> groups = as_k(a.q_groups);
         kptr<uint32_t> runs = as_k(a.run_table);
         const uint32_t nG = a.n_q_groups;
-        uint32_t part = a.xcd_affinity != 0u ? (blockIdx.x & (Q_PARTS - 1u)) : 0u;
+        uint32_t part = blockIdx.x & (Q_PARTS - 1u);
         for (uint32_t tries = 0; tries < Q_PARTS;) {
             // frames of this part: frame_part(f) == part  <=>  f in [ceil(part * n / 8), ceil((part + 1) * n / 8))
             // (fewer frames than parts: part = frame)
@@ -1389,20 +1389,18 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
         const uint32_t per_wave = total / a.total_waves;
         const uint32_t chunk = per_wave >= 64u ? min((uint32_t)UNIT_WINDOWS, ((per_wave + 63u) / 64u) * 64u)
                                                : max(min_chunk, ((per_wave + min_chunk - 1u) / min_chunk) * min_chunk);
-        if (a.thin_pass_spread != 0u) {
-            // Fewer chunks than waves (a late pass, a single frame): whichever waves draw the tickets first get the
-            // chunks, and with 24 resident waves per CU some CUs end up with twice the average — the pass then waits for
-            // the CU with the most (measured, 4096 x 4096 stage tree: 6.5 ms with 8 workgroups per CU against 3.9 ms
-            // with 4, same chunks).  Workgroups are dealt round-robin over XCDs and CUs
-            // (tools/microbench/dispatch_order.hip: the first 552 of 2048 sit 2-3 per CU on all 256 CUs), so only the
-            // first ceil(chunks / waves per workgroup) workgroups draw tickets; the others leave.  Speed only: the
-            // remaining waves loop until every part is drained.
-            uint32_t n_chunks = 0;
+        // Fewer chunks than waves (a late pass, a single frame): whichever waves draw the tickets first get the
+        // chunks, and with 24 resident waves per CU some CUs end up with twice the average — the pass then waits for
+        // the CU with the most (measured, 4096 x 4096 stage tree: 6.5 ms with 8 workgroups per CU against 3.9 ms
+        // with 4, same chunks).  Workgroups are dealt round-robin over XCDs and CUs
+        // (tools/microbench/dispatch_order.hip: the first 552 of 2048 sit 2-3 per CU on all 256 CUs), so only the
+        // first ceil(chunks / waves per workgroup) workgroups draw tickets; the others leave.  Speed only: the
+        // remaining waves loop until every part is drained.
+        uint32_t n_chunks = 0;
 #pragma unroll
-            for (uint32_t k = 0; k < N_CNT; ++k) n_chunks += (my_cnt[k] + chunk - 1u) / chunk;
-            n_chunks = wave_total(n_chunks);
-            if (blockIdx.x >= max((n_chunks + wpb - 1u) / wpb, 1u)) return;
-        }
+        for (uint32_t k = 0; k < N_CNT; ++k) n_chunks += (my_cnt[k] + chunk - 1u) / chunk;
+        n_chunks = wave_total(n_chunks);
+        if (blockIdx.x >= max((n_chunks + wpb - 1u) / wpb, 1u)) return;
         // chunks per part (counter i belongs to part i % Q_PARTS, and 64 % Q_PARTS == 0: lane l sums part l % Q_PARTS):
         // an empty or used-up part is left without walking its scales
         uint32_t part_chunks_v = 0;
@@ -1410,7 +1408,7 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
         for (uint32_t k = 0; k < N_CNT; ++k) part_chunks_v += (my_cnt[k] + chunk - 1u) / chunk;
 #pragma unroll
         for (int d = 32; d >= (int)Q_PARTS; d >>= 1) part_chunks_v += __shfl_xor(part_chunks_v, d, 64);
-        uint32_t part = a.xcd_affinity != 0u ? (blockIdx.x & (Q_PARTS - 1u)) : 0u;
+        uint32_t part = blockIdx.x & (Q_PARTS - 1u);
         for (uint32_t tries = 0; tries < Q_PARTS;) {
             const uint32_t part_chunks = __builtin_amdgcn_readfirstlane((uint32_t)__shfl(part_chunks_v, (int)part, 64));   // (uniform: keep the walk scalar)
             uint32_t t = part_chunks;
@@ -1777,7 +1775,7 @@ int launch_roi_chain(const RoiArgs& r, const CascadeArgs& a, bool from_dets, boo
 // instead of through the texture-address unit, the waves pool their survivors before the later stages, and once
 // few windows are left the tile finishes the cascade with the two routines that follow.  What survives is a
 // detection; only a tile that stays crowded hands its windows to the global queues, as {global byte offset,
-// variance}.  The same kernel also runs unstaged (L2 gathers) on 2-D blocks of windows of the large scales.
+// variance}.
 
 // Stump-parallel finish of a tile (stump cascades).  lds_q[0..T) holds the tile's T <= TILE_SP_MAX_WINDOWS
 // surviving windows.  Per stage, in blocks of <= 64 consecutive stumps: the block's node records are copied
@@ -1790,16 +1788,12 @@ int launch_roi_chain(const RoiArgs& r, const CascadeArgs& a, bool from_dets, boo
 // norm_threshold], clod.cl:81) — exactly the sequence of f32 additions a single lane would have made.  The
 // survivors are compacted across the waves.  Replaces the serial tail (one thin wave, ~300 cycles per stump) of
 // the late stages; the wave-split finish (further down) takes the populations above tile_ws_min.
-template <bool COUNT, bool STAMPS = true, typename Img>
+template <bool COUNT, typename Img>
 __device__ __forceinline__ uint32_t tile_stump_parallel(const CascadeArgs& a, const Img& img_by_window,
                                                         const uint32_t* table /* the scale's tile table, global */,
                                                         QEntry* lds_q, unsigned long long* lds_mask, uint32_t* lds_sp,
                                                         uint32_t* lds_cnt, uint32_t T, uint32_t st_begin,
-                                                        uint32_t n_stages, uint32_t lane, uint32_t wib,
-                                                        unsigned long long& t_last) {
-    unsigned long long sp_acc[5] = {0, 0, 0, 0, 0};
-#define SPSTAMP(ph) do { if (VJ_STAMPS && STAMPS && threadIdx.x == 0) { unsigned long long t_ = __builtin_amdgcn_s_memtime(); sp_acc[ph] += t_ - t_last; t_last = t_; } } while (0)
-#define SPFLUSH() do { if (VJ_STAMPS && STAMPS && threadIdx.x == 0) { for (int i_ = 0; i_ < 5; ++i_) atomicAdd(a.stage_entered + 54 + i_, sp_acc[i_]); } } while (0)
+                                                        uint32_t n_stages, uint32_t lane, uint32_t wib) {
     const auto img = img_by_window.by_stump();
     kptr<StageDev> stages = as_k(a.stages);
     kptr<uint32_t> blocks = as_k(reinterpret_cast<const uint32_t*>(a.sp_blocks));   // {first_node, desc} pairs
@@ -1853,7 +1847,6 @@ __device__ __forceinline__ uint32_t tile_stump_parallel(const CascadeArgs& a, co
                 }
             }
             lds_barrier();
-            SPSTAMP(0);
             // refill this slot with the block DEPTH ahead (global-memory latency is ~2 us: with one block in
             // flight the thin late stages would run at one block per round trip)
             if (g + DEPTH < g_end) {
@@ -1904,10 +1897,8 @@ __device__ __forceinline__ uint32_t tile_stump_parallel(const CascadeArgs& a, co
                 }
             }
             ++g;
-            SPSTAMP(1);
             if (b + 1u == nb) {   // last block of stage s (uniform)
                 lds_barrier();   // every verdict of the stage is in lds_mask
-                SPSTAMP(2);
                 // 3. the stage decision: thread t owns window t.  The sequential stage sum (stage_sum += alpha in
                 // stump order, clod.cl:81) and the butterfly-order sum of the same values differ by at most
                 // sp_delta (a rigorous a-priori bound, computed per stage on the host), so when the butterfly sum
@@ -1938,7 +1929,6 @@ __device__ __forceinline__ uint32_t tile_stump_parallel(const CascadeArgs& a, co
                         decided_pass = sum >= thr_s;
                     }
                 }
-                SPSTAMP(3);
                 // 4. survivors: compact lds_q across the waves
                 const bool pass = tid < T && decided_pass;
                 const QEntry e = lds_q[tid < T ? tid : 0u];
@@ -1955,8 +1945,7 @@ __device__ __forceinline__ uint32_t tile_stump_parallel(const CascadeArgs& a, co
                 if (pass) lds_q[before + mbcnt(mask)] = e;
                 T = __builtin_amdgcn_readfirstlane(total);
                 lds_barrier();   // lds_q is repacked; lds_cnt / lds_mask / lds_lr may be rewritten
-                SPSTAMP(4);
-                if (T == 0u || s + 1u >= n_stages) { SPFLUSH(); return T; }
+                if (T == 0u || s + 1u >= n_stages) return T;
                 if (COUNT && tid == 0) atomicAdd(a.stage_entered + s + 1u, (unsigned long long)T);
             }
         }
@@ -2075,7 +2064,8 @@ __device__ __forceinline__ uint32_t tile_wave_split(const CascadeArgs& a, const 
                                                     unsigned long long& t_last, QEntry* fail_list = nullptr,
                                                     uint32_t* fail_n = nullptr) {
     unsigned long long sp_acc[5] = {0, 0, 0, 0, 0};
-    constexpr bool STAMPS = true;
+#define SPSTAMP(ph) do { if (VJ_STAMPS && threadIdx.x == 0) { unsigned long long t_ = __builtin_amdgcn_s_memtime(); sp_acc[ph] += t_ - t_last; t_last = t_; } } while (0)
+#define SPFLUSH() do { if (VJ_STAMPS && threadIdx.x == 0) { for (int i_ = 0; i_ < 5; ++i_) atomicAdd(a.stage_entered + 54 + i_, sp_acc[i_]); } } while (0)
     kptr<StageDev> stages = as_k(a.stages);
     // scratch behind the packed entries: per producing wave 64 range sums + 4 x 64 verdict words
     uint32_t* lds_x = reinterpret_cast<uint32_t*>(lds_q + TILE_WS_MAX_WINDOWS);
@@ -2251,7 +2241,7 @@ __device__ __forceinline__ uint32_t tile_wave_split(const CascadeArgs& a, const 
 // ROI: the tiles come from a device-built list of (region, scale, tile) entries (roi_plan_units) instead of a frame's own
 // tile list: a tile then lies inside a region of interest — its window grid is the region's, its origin the region's
 // corner — and the survivors of the last stage go to the region pass's detection list.  Everything else is the same code.
-template <bool TREES, bool COUNT, bool STAGED, bool ROI>
+template <bool TREES, bool COUNT, bool ROI>
 __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiArgs* r_) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[];
     QEntry* lds_q = reinterpret_cast<QEntry*>(lds_dyn);                   // TILE_WAVES * TILE_WAVE_CAP entries
@@ -2323,14 +2313,14 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
             slot0 = units[r].scale;
             ix0 = units[r].first & 0xffffu;
             iy0 = units[r].first >> 16;
-            if (STAGED) n_mem = max(units[r].count, 1u);
+            n_mem = max(units[r].count, 1u);
         }
         // a scale group (n_mem > 1: scales slot0 .. lead, all of step 2) runs on the tile its largest scale lays out
         const uint32_t lead = slot0 + n_mem - 1u;
         const float step = scales[slot0].step;
         uint32_t tw = scales[lead].tile_tw, th = scales[lead].tile_th;
-        const uint32_t pitch = STAGED ? scales[lead].tile_pitch : 0u;
-        uint32_t rows = STAGED ? scales[lead].tile_rows : 0u, cols = pitch;   // rows / columns of the image tile that are staged
+        const uint32_t pitch = scales[lead].tile_pitch;
+        uint32_t rows = scales[lead].tile_rows, cols = pitch;   // rows / columns of the image tile that are staged
         if constexpr (ROI) {
             // a region's tile may be smaller than the scale's: fewer rows and columns to stage.  The scale's tile spans
             // ceil((t - 1) * step) + margin pixels (host, double); floor(...) + 2 of the smaller shape against floor(...) of the
@@ -2357,27 +2347,18 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
         // stage the tile: rows round-robin over the waves, 64 consecutive dwords per instruction,
         // straight into LDS (buffer_load ... lds: no VGPR round trip, so every load of the tile is in
         // flight at once instead of one load-wait-store per 256 bytes); the barrier drains them
-        const uint32_t half = STAGED ? scales[lead].tile_half : 0u;
-        const uint32_t x4 = STAGED ? scales[lead].tile_x4 : 0u;
-        for (uint32_t rr = wib; STAGED && rr < rows; rr += TILE_WAVES) {
+        const uint32_t half = scales[lead].tile_half;
+        for (uint32_t rr = wib; rr < rows; rr += TILE_WAVES) {
             const uint32_t g_row = ((y0 + rr) * a.stride + x0) * 4u;   // uniform
-            if (half == 0u && x4 != 0u) {
-                // 16 bytes per lane, 1 KiB per instruction: a quarter of the texture-address work of the dword form
-                // (which the global-gather chain on the same CU is competing for)
+            if (half == 0u) {
+                // 16 bytes per lane (the pitch is a multiple of 4 dwords), 1 KiB per instruction: a quarter of the
+                // texture-address work of the dword form (which the global-gather chain on the same CU is competing for)
                 for (uint32_t c0 = 0; c0 < cols; c0 += 256u) {
                     const uint32_t soff = __builtin_amdgcn_readfirstlane(g_row + c0 * 4u);
                     if (c0 + lane * 4u < cols)
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(
                             sum_f, (__attribute__((address_space(3))) uint32_t*)(lds_img + rr * pitch + c0), 16,
                             lane * 16u, soff, 0, 0);
-                }
-            } else if (half == 0u) {
-                for (uint32_t c0 = 0; c0 < cols; c0 += 64u) {
-                    const uint32_t soff = __builtin_amdgcn_readfirstlane(g_row + c0 * 4u);   // keep it scalar
-                    if (c0 + lane < cols)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                            sum_f, (__attribute__((address_space(3))) uint32_t*)(lds_img + rr * pitch + c0), 4,
-                            lane * 4u, soff, 0, 0);
                 }
             } else {
                 // de-interleave while staging: plane 0 takes image columns 0, 2, 4, ..., plane 1 the odd ones
@@ -2438,8 +2419,7 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                     const uint32_t y = oy + window_pos(a, pos_base, iy, step);
                     // byte offset inside the tile (de-interleaved rows: window origins are even columns)
                     const uint32_t e = y * a.stride + x;
-                    // unstaged blocks: byte offset in the batch sum image, as in cascade_pass
-                    w_lo4[k] = STAGED ? ((y - y0) * pitch + (half ? (x - x0) >> 1 : x - x0)) * 4u : frame_bytes + e * 4u;
+                    w_lo4[k] = ((y - y0) * pitch + (half ? (x - x0) >> 1 : x - x0)) * 4u;
                     const uint32_t c0 = e_lt, c1 = e_lt + e_dw, c2 = e_lt + e_dh, c3 = e_lt + e_dh + e_dw;
                     w_q[k] = ld_u64(sq_f, e * 8u, c0 * 8u) - ld_u64(sq_f, e * 8u, c1 * 8u) - ld_u64(sq_f, e * 8u, c2 * 8u) +
                              ld_u64(sq_f, e * 8u, c3 * 8u);
@@ -2450,23 +2430,14 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
 
             // computeVariance (clod.cpp:418-446): pixel sum from the LDS tile, squared sum as loaded above
             uint32_t n = 0;
-            typedef typename std::conditional<STAGED, LdsImg, GlobalImg>::type ImgT;
-            ImgT img;
-            if constexpr (STAGED) img = LdsImg{reinterpret_cast<const char*>(lds_img)};
-            else img = GlobalImg{make_rsrc(a.sum, a.sum_bytes)};
+            const LdsImg img{reinterpret_cast<const char*>(lds_img)};
 #pragma unroll
             for (int k = 0; k < NCH; ++k) {
                 QEntry en{0u, 0.0f};
                 if (w_valid[k]) {
                     const uint32_t lo4 = w_lo4[k];
-                    uint32_t s4;
-                    if constexpr (STAGED) {
-                        s4 = img.ld(lo4, te_lt) - img.ld(lo4, te_lt + te_dw) - img.ld(lo4, te_lt + te_dh) +
-                             img.ld(lo4, te_lt + te_dh + te_dw);
-                    } else {
-                        const uint32_t g_lt = e_lt * 4u, g_dw = e_dw * 4u, g_dh = e_dh * 4u;
-                        s4 = img.ld(lo4, g_lt) - img.ld(lo4, g_lt + g_dw) - img.ld(lo4, g_lt + g_dh) + img.ld(lo4, g_lt + g_dh + g_dw);
-                    }
+                    const uint32_t s4 = img.ld(lo4, te_lt) - img.ld(lo4, te_lt + te_dw) - img.ld(lo4, te_lt + te_dh) +
+                                        img.ld(lo4, te_lt + te_dh + te_dw);
                     const float mean = (a.signed_mean ? (float)(int32_t)s4 : (float)s4) / area;
                     float variance = (float)w_q[k];
                     variance = (variance / area) - (mean * mean);
@@ -2478,7 +2449,7 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                 n += (uint32_t)__popcll(mask);
             }
             __builtin_amdgcn_wave_barrier();
-            const uint32_t table_first = !STAGED ? scales[slot].table_first : ROI ? scales[slot].tile_table_first : scales[slot].grp_table_first;
+            const uint32_t table_first = ROI ? scales[slot].tile_table_first : scales[slot].grp_table_first;
             kptr<NodeRecDev> table = as_k(reinterpret_cast<const NodeRecDev*>(a.table)) + table_first;
             // Sweep the cascade stage by stage.  At the stages named by tile_repack_mask and at every
             // pass boundary the tile's survivors are re-packed across its waves into runs of full
@@ -2512,13 +2483,10 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                 QEntry* qd = is_det ? nullptr : a.q_pass[dest_];
                 for (uint32_t i = lane; i < nn; i += 64u) {
                     const QEntry e = qq[i];
-                    uint32_t off = e.off;
-                    if (STAGED) {
-                        const uint32_t lo = e.off >> 2;
-                        const uint32_t ly = lo / pitch, lc = lo - ly * pitch;
-                        const uint32_t lx = half ? lc * 2u : lc;   // window origins sit in the even plane
-                        off = frame_bytes + ((y0 + ly) * a.stride + (x0 + lx)) * 4u;
-                    }
+                    const uint32_t lo = e.off >> 2;
+                    const uint32_t ly = lo / pitch, lc = lo - ly * pitch;
+                    const uint32_t lx = half ? lc * 2u : lc;   // window origins sit in the even plane
+                    const uint32_t off = frame_bytes + ((y0 + ly) * a.stride + (x0 + lx)) * 4u;
                     if (is_det) {
                         if (g + i < a.det_cap) a.det[g + i] = DetEntry{off, slot};
                     } else {
@@ -2584,29 +2552,17 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                         STAMP(12);
                         break;
                     }
-                    if ((!TREES || a.tree2) && a.tile_finish == 1u && st >= a.tile_sp_begin && total != 0u && total <= a.tile_ws_max) {
+                    if ((!TREES || a.tree2) && st >= a.tile_sp_begin && total != 0u && total <= a.tile_ws_max) {
                         // few windows left: finish the whole cascade with the stage's stumps (or two-node trees) split
                         // over the waves
                         uint32_t s_next = st;
                         uint32_t left = tile_wave_split<COUNT, TREES>(a, img, table, lds_q, lds_cnt, total, s_next, n_stages_total,
                                                                       lane, wib, t_last);
                         if (!TREES && left != 0u && s_next < n_stages_total)
-                            left = tile_stump_parallel<COUNT, false>(
+                            left = tile_stump_parallel<COUNT>(
                                 a, img, a.table + (size_t)table_first * 16u, lds_q,
                                 reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS), lds_tab, lds_cnt, left, s_next,
-                                n_stages_total, lane, wib, t_last);
-                        q = lds_q;
-                        n = wib == 0u ? left : 0u;
-                        dest = a.n_pass;
-                        STAMP(12);
-                        break;
-                    }
-                    if (!TREES && a.tile_finish == 0u && st >= a.tile_sp_begin && total != 0u && total <= a.tile_sp_max) {
-                        // few windows left: finish the whole cascade stump-parallel; survivors are detections
-                        const uint32_t left = tile_stump_parallel<COUNT, true>(
-                            a, img, a.table + (size_t)table_first * 16u, lds_q,
-                            reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS), lds_tab, lds_cnt, total, st,
-                            n_stages_total, lane, wib, t_last);
+                                n_stages_total, lane, wib);
                         q = lds_q;
                         n = wib == 0u ? left : 0u;
                         dest = a.n_pass;
@@ -2634,15 +2590,17 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
     if (VJ_STAMPS && threadIdx.x == 0) atomicAdd(a.stage_entered + 38, ~0ull);
 }
 
+// (STAGED is always true: the name cascade_tile_pass<TREES, COUNT, true> is what profiles and tools match)
 template <bool TREES, bool COUNT, bool STAGED>
 __global__ __launch_bounds__(TILE_WAVES * 64) void cascade_tile_pass(CascadeArgs a) {
-    tile_pass_body<TREES, COUNT, STAGED, false>(a, nullptr);
+    static_assert(STAGED, "the tile kernel always stages its tile in LDS");
+    tile_pass_body<TREES, COUNT, false>(a, nullptr);
 }
 
 // The tile kernel inside regions of interest (vj_detect_chain / vj_detect_rois with many or large regions; stump cascades).
 template <bool COUNT>
 __global__ __launch_bounds__(TILE_WAVES * 64) void cascade_tile_roi_pass(RoiArgs r, CascadeArgs a) {
-    tile_pass_body<false, COUNT, true, true>(a, &r);
+    tile_pass_body<false, COUNT, true>(a, &r);
 }
 
 // The tile kernel uses up to the CU's whole 160 KiB of dynamic LDS; HIP caps a kernel at 64 KiB until the attribute
@@ -2652,8 +2610,7 @@ int prepare_tile_kernels() {
     const int max_lds = 160 * 1024;
     const void* fns[] = {(const void*)cascade_tile_roi_pass<false>, (const void*)cascade_tile_roi_pass<true>,
                          (const void*)cascade_tile_pass<false, false, true>, (const void*)cascade_tile_pass<false, true, true>,
-                         (const void*)cascade_tile_pass<true, false, true>,  (const void*)cascade_tile_pass<true, true, true>,
-                         (const void*)cascade_tile_pass<false, false, false>, (const void*)cascade_tile_pass<false, true, false>};
+                         (const void*)cascade_tile_pass<true, false, true>,  (const void*)cascade_tile_pass<true, true, true>};
     for (const void* f : fns) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
         if (e != hipSuccess) return (int)e;
@@ -2661,14 +2618,11 @@ int prepare_tile_kernels() {
     return 0;
 }
 
-int launch_cascade_tile_pass(const CascadeArgs& a, bool trees, bool count, bool staged, int n_blocks, void* stream_) {
+int launch_cascade_tile_pass(const CascadeArgs& a, bool trees, bool count, int n_blocks, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     dim3 g(n_blocks), b(TILE_WAVES * 64);
     const size_t lds = a.tile_lds_bytes;
-    if (!staged) {   // unstaged blocks: stump cascades only (the host keeps tree cascades on cascade_pass)
-        if (count) hipLaunchKernelGGL((cascade_tile_pass<false, true, false>), g, b, lds, stream, a);
-        else       hipLaunchKernelGGL((cascade_tile_pass<false, false, false>), g, b, lds, stream, a);
-    } else if (trees) {
+    if (trees) {
         if (count) hipLaunchKernelGGL((cascade_tile_pass<true, true, true>), g, b, lds, stream, a);
         else       hipLaunchKernelGGL((cascade_tile_pass<true, false, true>), g, b, lds, stream, a);
     } else {

@@ -182,20 +182,19 @@ int  vj_env_device_name(const vj_env* e, char* buf, size_t cap);
  * with its values, default and the measurement behind the default is in DESIGN.md §7.  Lists are comma-separated.
  *   launch structure   pass_split, pass_cut_nodes, blocks_per_cu, concurrent, concurrent_blocks_per_cu, max_subbatch, det_cap
  *   LDS tiles          tile_classes_kb, tile_lds_reserve_kb, tile_min_windows, tile_accept_windows, tile_end, tile_min_lanes,
- *                      tile_max_dwords_per_window, tile_class_order, tile_lds_nest, tile_repack, tile_deinterleave, tile_stage_x4,
- *                      global_blocks
- *   tile finish        tile_finish, tile_sp_begin, tile_sp_max, tile_ws_min, tile_ws_max
+ *                      tile_max_dwords_per_window, tile_repack
+ *   tile finish        tile_sp_begin, tile_ws_min, tile_ws_max
  *   chain balance      tile_split ("small,mid,large" or one value: static), auto_balance (1 / 0 / "reset": feedback on the
  *                      first calls of a batch workload, keyed by cascade content, frame size, parameters and batch-size class),
  *                      balance_export / balance_import (value: a file path; the found balances as text, for another environment
- *                      or process — import AFTER setting auto_balance, which clears the table), balance_exact (tests)
- *   global-gather      grid_block_w, gather_waves, gather_pairs, sp_tail_max, wide_tail, min_chunk, thin_pass_spread, q_slices,
- *                      xcd_affinity, q_band_px, q_group_units, q_band_min_frames (band-major first-pass units and queue pass)
+ *                      or process — import AFTER setting auto_balance, which clears the table)
+ *   global-gather      grid_block_w, gather_waves, gather_pairs, sp_tail_max, wide_tail, min_chunk, q_slices,
+ *                      q_band_px, q_group_units, q_band_min_frames (band-major first-pass units and queue pass)
  *   stage trees        general_prefix, tile_segments, seg_cut2, tree_split_queues
  *   regions / chain    rois_on_device, roi_tiles, group_max
  *   OpenCV profile     cv_tiles, cv_row_blocks, cv_tile_min_windows, cv_tile_min_windows0, cv_tile_ws_max, cv_row_blocks_tree,
- *                      cv_tile_min_windows_tree, cv_tree_chains, cv_tree_chunk, cv_tree_chain_blocks, cv_tail_max, cv_pairs,
- *                      cv_row_band_px, cv_tree2, cv_tiles_tilted, tilted_bands,
+ *                      cv_tile_min_windows_tree, cv_tree_chains, cv_tree_chunk, cv_tree_chain_blocks, cv_tail_max,
+ *                      cv_row_band_px, cv_tree2, cv_tiles_tilted,
  *                      cv_tree_queue_cap (tests)
  *   single frames      one_pass_max_frames (the gather chain in one pass for calls of few large frames; 0 = off)
  *   integral           integral_rows (0 one wave per band of rows, 1 a band's chunks side by side, 2 by call size)
@@ -262,7 +261,7 @@ typedef struct vj_counters {
 enum { VJ_LAUNCH_GRID = 0,   /* first pass, windows enumerated from the grid, L2 gathers */
        VJ_LAUNCH_QUEUE = 1,  /* later pass over the survivor queue, L2 gathers           */
        VJ_LAUNCH_TILE = 2,   /* whole cascade on image tiles staged in LDS               */
-       VJ_LAUNCH_BLOCK = 3 };/* whole cascade on 2-D window blocks, L2 gathers (large scales) */
+       VJ_LAUNCH_BLOCK = 3 };/* no longer produced (was: 2-D window blocks, L2 gathers)   */
 typedef struct vj_launch {
     int32_t  kind;             /* VJ_LAUNCH_*                                   */
     int32_t  lds_class;        /* tile launches: LDS size class                 */

@@ -150,25 +150,14 @@ def test_pass_split_and_occupancy_do_not_change_results(env, cascades):
             r = env.detect(c, frames, p)
             assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, b
         env.configure("defaults", "")
-        env.configure("thin_pass_spread", 0)       # every workgroup of a queue pass draws tickets / only the first ones do
-        r = env.detect(c, frames, p)
-        assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered
-        env.configure("defaults", "")
-        for de, x4 in ((0, 1), (0, 0), (1, 0)):
-            env.configure("tile_deinterleave", de)
-            env.configure("tile_stage_x4", x4)
-            r = env.detect(c, frames, p)
-            assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, (de, x4)
-        env.configure("defaults", "")
-        for conc, reserve, blocks, split, gbw in ((0, 26, 1, 0, 32), (0, 0, 0, 0.4, 0), (1, 0, 1, 1.3, 32), (1, 40, 0, 2.5, 16),
-                                                  (1, 26, 0, 0.7, 64), (1, 26, 0, 99, 32)):
+        for conc, reserve, split, gbw in ((0, 26, 0, 32), (0, 0, 0.4, 0), (1, 0, 1.3, 32), (1, 40, 2.5, 16), (1, 26, 0.7, 64),
+                                          (1, 26, 99, 32)):
             env.configure("concurrent", conc)
             env.configure("tile_lds_reserve_kb", reserve)
-            env.configure("global_blocks", blocks)
             env.configure("tile_split", split)
             env.configure("grid_block_w", gbw)
             r = env.detect(c, frames, p)
-            assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, (conc, reserve, blocks, split)
+            assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, (conc, reserve, split)
             assert [sum(l["stage_entered"][s] for l in r.launches) for s in range(len(r.stage_entered))] == r.stage_entered
         env.configure("defaults", "")
         # LDS-tile path off / small / large tiles / shallow / deep: the tile and the
@@ -181,8 +170,6 @@ def test_pass_split_and_occupancy_do_not_change_results(env, cascades):
             env.configure("tile_min_lanes", {3: 0, 10: 12, 22: 64, 14: 1, 7: 200}[tile_end])
             env.configure("tile_repack", {3: "", 10: "3,5", 22: "1,2,3,4,5,6,7,9,11,13,17", 14: "2", 7: "6"}[tile_end])
             env.configure("tile_sp_begin", {3: 64, 10: 8, 22: 4, 14: 1, 7: 6}[tile_end])
-            env.configure("tile_sp_max", {3: 96, 10: 48, 22: 256, 14: 200, 7: 45}[tile_end])
-            env.configure("tile_finish", {3: 1, 10: 1, 22: 0, 14: 1, 7: 0}[tile_end])
             env.configure("tile_ws_max", {3: 512, 10: 100, 22: 512, 14: 512, 7: 64}[tile_end])
             for split in ("", "22", "7", "2,4,6,9,12,15,18"):
                 env.configure("pass_split", split)
@@ -193,9 +180,9 @@ def test_pass_split_and_occupancy_do_not_change_results(env, cascades):
 
 @pytest.mark.parametrize("casc", ["frontalface_alt", "frontalface_alt2"])
 def test_finish_variants_agree(env, cascades, casc):
-    """The stump-parallel and the wave-split finish of the tile kernel (and neither) give the same rectangles and
-    per-stage counts as the oracle-checked default, on frames that keep many windows alive (noise) and few (smooth).
-    frontalface_alt2 (two-node trees) takes the wave-split finish only."""
+    """The tile kernel's wave-split finish and its stump-parallel tail, at several thresholds (and no finish, and no tiles),
+    give the same rectangles and per-stage counts as the oracle-checked default, on frames that keep many windows alive
+    (noise) and few (smooth).  frontalface_alt2 (two-node trees) takes the wave-split finish only."""
     c, _ = cascades(casc)
     frames = np.stack([make_frame("noise", 31, 540, 960), make_frame("smooth", 32, 540, 960),
                        make_frame("blocks", 33, 540, 960)])
@@ -206,21 +193,13 @@ def test_finish_variants_agree(env, cascades, casc):
         env.configure("tile_classes_kb", "0,0,0")   # no LDS tiles: every scale runs as grid pass + queue passes
         r = env.detect(c, frames, p)
         assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered
-        env.configure("global_blocks", 1)           # ... and as unstaged 2-D blocks in the tile kernel
-        r = env.detect(c, frames, p)
-        assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered
-        assert [l["kind"] for l in r.launches] == (["block"] if casc == "frontalface_alt" else ["grid", "queue"])
         env.configure("defaults", "")
-        for finish, begin, ws_max, sp_max, ws_min in ((1, 3, 512, 192, 32), (1, 1, 512, 192, 0), (1, 2, 200, 192, 100),
-                                                      (1, 5, 64, 192, 8), (1, 3, 512, 192, 256), (0, 3, 512, 192, 32),
-                                                      (0, 4, 512, 256, 32)):
-            env.configure("tile_finish", finish)
+        for begin, ws_max, ws_min in ((3, 512, 32), (1, 512, 0), (2, 200, 100), (5, 64, 8), (3, 512, 256)):
             env.configure("tile_ws_min", ws_min)
             env.configure("tile_sp_begin", begin)
             env.configure("tile_ws_max", ws_max)
-            env.configure("tile_sp_max", sp_max)
             r = env.detect(c, frames, p)
-            assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, (finish, begin, ws_max)
+            assert np.array_equal(r.rects, base.rects) and r.stage_entered == base.stage_entered, (begin, ws_max, ws_min)
 
 
 def test_scale_mask_partitions_the_result(env, cascades):

@@ -12,10 +12,9 @@ MAX = None   # no upper / lower bound
 # auto: -1 for negative values, else clamped to [lo, hi]
 SCALARS = {
     **{k: ("bool", 0, 1) for k in (
-        "tile_finish", "tile_lds_nest", "tree_split_queues", "cv_pairs", "tilted_bands", "cv_tiles_tilted", "cv_tree2",
-        "cv_tree_chains", "rois_on_device", "cv_tiles", "thin_pass_spread", "tile_class_order", "tile_stage_x4",
-        "tile_deinterleave", "balance_exact", "xcd_affinity", "tile_segments", "general_prefix", "global_blocks", "concurrent")},
-    "tile_ws_min": ("clamp", 0, 256), "tile_ws_max": ("clamp", 0, 512), "tile_sp_max": ("clamp", 0, 256),
+        "tree_split_queues", "cv_tiles_tilted", "cv_tree2", "cv_tree_chains", "rois_on_device", "cv_tiles", "tile_segments",
+        "general_prefix", "concurrent")},
+    "tile_ws_min": ("clamp", 0, 256), "tile_ws_max": ("clamp", 0, 512),
     "q_band_px": ("clamp", 0, MAX), "q_group_units": ("clamp", 0, MAX), "q_band_min_frames": ("clamp", 1, MAX),
     "cv_tail_max": ("clamp", 0, 64), "cv_tree_chunk": ("clamp", 1, MAX), "cv_tree_chain_blocks": ("clamp", 1, MAX),
     "one_pass_max_frames": ("clamp", 0, MAX), "cv_row_band_px": ("clamp", 0, MAX), "cv_tree_queue_cap": ("clamp", 0, MAX),
@@ -31,6 +30,10 @@ SCALARS = {
                                         "tile_max_dwords_per_window")},
     "blocks_per_cu": ("range", 1, 16),
 }
+
+# keys fixed at their shipped values and removed ("Retired keys"): unknown like any other name
+RETIRED = ("global_blocks", "tile_finish", "tile_sp_max", "tile_deinterleave", "tile_stage_x4", "tile_lds_nest",
+           "tile_class_order", "xcd_affinity", "thin_pass_spread", "balance_exact", "cv_pairs", "tilted_bands")
 
 # the other keys: (value, expected query after it, or ERR)
 LISTED = {
@@ -86,6 +89,7 @@ def test_the_spec_covers_the_table():
     keys = configure_keys()
     assert len(keys) == len(set(keys)) and len(keys) > 50
     assert sorted(set(keys) - set(CONFIGURE_ACTIONS)) == sorted(list(SCALARS) + list(LISTED))
+    assert not set(RETIRED) & set(keys)
 
 
 @pytest.mark.gpu
@@ -117,6 +121,17 @@ def test_every_key_parses_and_bounds_its_values(fresh):
             fresh.query(k)
     with pytest.raises(VjError):
         fresh.configure("no_such_key", "1")
+
+
+@pytest.mark.gpu
+def test_retired_keys_are_rejected(fresh):
+    before = snapshot(fresh)
+    for k in RETIRED:
+        for call in (lambda: fresh.configure(k, "1"), lambda: fresh.query(k)):
+            with pytest.raises(VjError, match="unknown option") as ei:
+                call()
+            assert ei.value.code == 1, k
+    assert snapshot(fresh) == before
 
 
 @pytest.mark.gpu

@@ -1,9 +1,9 @@
 """What the chain-balance feedback costs a service whose batch sizes vary: `calls` vj_detect calls of
-8 ... 96 frames of 1280 x 720 (sizes drawn at random, two cascades), once with the balance keyed on the exact frame count
-(round 3: "balance_exact" = 1) and once keyed on the batch-size class (8-15, 16-31, 32-63, >= 64).  Printed per mode: the
-share of calls that ran a split other than the best known (candidates of a search), how many workloads finished their
-search, mean kernel ms per frame over the whole run and over its last third, and a second environment that IMPORTS the
-table the first one exported (its calls must all be on the best split from the first one on).
+8 ... 96 frames of 1280 x 720 (sizes drawn at random, two cascades), the balance keyed on the batch-size class (8-15, 16-31,
+32-63, >= 64).  Printed: the share of calls that ran a split other than the best known (candidates of a search), how many
+workloads finished their search, mean kernel ms per frame over the whole run and over its last third, and the same for a
+second environment that IMPORTS the table the first one exported (its calls must all be on the best split from the first
+one on).  The comparison with round 3's balance keyed on the exact frame count is in profiles/r04_balance_service.log.
 
     python tools/balance_service.py [calls]"""
 import os, sys, tempfile
@@ -47,11 +47,9 @@ def run(env, tag, seed=7):
     return path
 
 
-for tag, exact in (("exact frame count (round 3)", "1"), ("batch-size class", "0")):
-    env = Environment(0)
-    env.configure("balance_exact", exact)
-    path = run(env, "exact" if exact == "1" else "class")
-    env.close()
+env = Environment(0)
+path = run(env, "class")
+env.close()
 env2 = Environment(0)
 env2.configure("balance_import", path)
 run(env2, "class_imported")

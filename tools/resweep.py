@@ -12,9 +12,9 @@ c = Cascade.load("frontalface_alt")
 df = DeviceFrames.from_torch(torch.from_numpy(synth.batch(B, 1080, 1920, seed0=1)).cuda())
 SWEEP = [("pass_cut_nodes", ["35", "10", "50", "75", "150"]), ("blocks_per_cu", ["8", "4", "6", "10", "12"]), ("concurrent_blocks_per_cu", None),
          ("min_chunk", ["32", "16", "48", "64"]), ("q_slices", ["-1", "4", "16", "32"]), ("gather_pairs", ["-1", "0", "2"]),
-         ("sp_tail_max", ["48", "32", "64"]), ("wide_tail", ["-1", "0", "1"]), ("thin_pass_spread", ["1", "0"]), ("grid_block_w", ["32", "16", "64"]),
-         ("tile_ws_max", ["512", "384", "768"]), ("tile_ws_min", ["48", "32", "64"]), ("tile_sp_begin", ["3", "4", "5"]), ("tile_sp_max", ["192", "128", "256"]),
-         ("tile_lds_reserve_kb", ["16", "12", "20", "24"]), ("tile_class_order", ["1", "0"]), ("tile_repack", None)]
+         ("sp_tail_max", ["48", "32", "64"]), ("wide_tail", ["-1", "0", "1"]), ("grid_block_w", ["32", "16", "64"]),
+         ("tile_ws_max", ["512", "384", "768"]), ("tile_ws_min", ["48", "32", "64"]), ("tile_sp_begin", ["3", "4", "5"]),
+         ("tile_lds_reserve_kb", ["16", "12", "20", "24"]), ("tile_repack", None)]
 
 
 def timed():
