@@ -34,6 +34,14 @@ VJ_FLAG_SKIP_LIST = 1 << 2     # the CLOD_PER_STAGE_ITERATIONS CPU variant's ski
 VJ_FLAG_SKIP_ROW = 1 << 3      # the plain CPU variant: round() positions, skip inside a row (clod.cpp:1409-1432)
 VJ_FLAG_GRID_F64 = 1 << 4      # + one of the two above: the same loop of the block variant, whose step is a double (clod.cpp:862)
 VJ_FLAG_TILTED_AS_UPRIGHT = 1 << 5   # clod profile: <tilted>1 rectangles count as upright ones, as in the reference (clod.cpp:448-492); else refused
+VJ_FLAG_CV_CANNY_PRUNING = 1 << 6    # OpenCV profile: CV_HAAR_DO_CANNY_PRUNING (edge map per frame, a pruning test per visited window)
+
+# cvHaarDetectObjects' flags (tempcv.hpp:127-130).  Only CV_HAAR_DO_CANNY_PRUNING stays on the scale-cascade path that
+# vj_detect_opencv implements; the other three are other paths and are refused.
+CV_HAAR_DO_CANNY_PRUNING = 1
+CV_HAAR_SCALE_IMAGE = 2
+CV_HAAR_FIND_BIGGEST_OBJECT = 4
+CV_HAAR_DO_ROUGH_SEARCH = 8
 
 # clod_flags of the reference (clod.h:17-19).  They select among the reference's CPU
 # evaluators; the HIP path has one evaluator, so they are accepted and ignored.
@@ -148,6 +156,7 @@ _SIGNATURES = {
     "vj_integral_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vj_integral_tilted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "vj_grayscale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "vj_canny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vj_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "vj_host_free": (None, [C.c_void_p, C.c_void_p]),
     "vj_detect_chain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params),
@@ -406,6 +415,17 @@ class Environment:
         g = np.empty(img.shape[:2], np.uint8)
         _check(load_library().vj_grayscale(self._h, C.byref(im), g.ctypes.data, g.strides[0]), "vj_grayscale")
         return g
+
+    def canny(self, img, color: bool = False) -> np.ndarray:
+        """vj_canny: cvCanny(gray, edges, 0, 50, 3) on the device, the edge map CV_HAAR_DO_CANNY_PRUNING computes per frame
+        (uint8, 255 on edges, 0 elsewhere).  img: a 2-D uint8 image, a (h, w, 3|4) BGR / BGRA image (color=True), or a
+        one-frame DeviceFrames."""
+        imgs, n, keep = self._images(img, color)
+        if n != 1:
+            raise ValueError("canny takes one image")
+        e = np.empty((imgs[0].height, imgs[0].width), np.uint8)
+        _check(load_library().vj_canny(self._h, C.byref(imgs[0]), e.ctypes.data, e.strides[0]), "vj_canny")
+        return e
 
     def host_alloc(self, shape, dtype=np.uint8) -> np.ndarray:
         """vj_host_alloc: a page-locked numpy array (freed with host_free) for copy-free frame uploads."""
@@ -668,8 +688,11 @@ def clodDetectObjects(image, cascade: Cascade, env: Environment, min_window_size
 def cvHaarDetectObjects(image, cascade: Cascade, env: Environment, scale_factor: float = 1.1, min_neighbors: int = 3,
                         flags: int = 0, min_size=(0, 0), vj_flags: int = 0) -> DetectResult:
     """The reference demo's OpenCV leg (main.cpp:145: cvHaarDetectObjects(img, cascade, storage, 1.1, ...)) as
-    tempcv.cpp:1188-1456 specifies its scale-cascade path, on the device (OpenCV arithmetic profile).  `flags`
-    must be 0: canny pruning, find-biggest-object and scale-image are other paths."""
-    if flags != 0:
-        raise VjError(4, "cvHaarDetectObjects", "only flags = 0 (the scale-cascade path) is implemented")
+    tempcv.cpp:1188-1456 specifies its scale-cascade path, on the device (OpenCV arithmetic profile).  `flags`:
+    0 or CV_HAAR_DO_CANNY_PRUNING; scale-image, find-biggest-object and rough search are other paths."""
+    if flags & ~CV_HAAR_DO_CANNY_PRUNING:
+        raise VjError(4, "cvHaarDetectObjects", "only flags 0 and CV_HAAR_DO_CANNY_PRUNING (the scale-cascade path) are implemented; "
+                      "CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT and CV_HAAR_DO_ROUGH_SEARCH are not")
+    if flags & CV_HAAR_DO_CANNY_PRUNING:
+        vj_flags |= VJ_FLAG_CV_CANNY_PRUNING
     return env.detect_opencv(cascade, image, min_size, scale_factor, min_neighbors, vj_flags)

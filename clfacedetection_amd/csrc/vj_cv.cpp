@@ -59,6 +59,7 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         if (kids != 1 || (n0.left > 0 ? n0.left : n0.right) != 1 || n1.left > 0 || n1.right > 0) tree2 = false;
     }
     pl->tree2 = tree2;
+    pl->prune = (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
     pl->trees = trees;
     pl->is_tree = is_tree;
     pl->has_tilted = has_tilted;
@@ -165,6 +166,7 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     table.reserve(2 * hs.size() * n_nodes);   // tile copies of the small scales' records are appended: no reallocation, `recs` stays valid
     std::vector<UnitDev> rows;
     std::vector<int> tile_class(hs.size(), -1);
+    std::vector<CvPruneDev> prune(pl->prune ? hs.size() : 0);
     bool reach_ok = true;
     const uint32_t frame_elems = frame_elems_for(W, H);
     for (size_t k = 0; k < hs.size(); ++k) {
@@ -253,6 +255,20 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         // window by one column / row (separate rounding): the frame allocation has two zeroed slack rows for that
         const uint64_t origin_max = (uint64_t)(H - hs[k].win_h) * stride + (uint64_t)(W - hs[k].win_w);
         if (origin_max + max_reach >= (uint64_t)frame_elems) reach_ok = false;
+        if (pl->prune) {
+            // CV_HAAR_DO_CANNY_PRUNING (tempcv.cpp:1147-1158): the rectangle [x + ex, + ew) x [y + ey, + eh) of the scaled window, tested at
+            // every visited position BEFORE the border rule — so its furthest corner, from the last grid position, must stay in the frame's
+            // allocation (rows past H read the zeroed slack rows, as OpenCV's pointers read whatever follows)
+            const int px = cv_round(hs[k].win_w * 0.15), py = cv_round(hs[k].win_h * 0.15);
+            const int pw = cv_round(hs[k].win_w * 0.7), ph = cv_round(hs[k].win_h * 0.7);
+            CvPruneDev& pr = prune[k];
+            pr.p0 = (uint32_t)py * stride + (uint32_t)px;
+            pr.p1 = pr.p0 + (uint32_t)pw;
+            pr.p2 = (uint32_t)(py + ph) * stride + (uint32_t)px;
+            pr.p3 = pr.p2 + (uint32_t)pw;
+            const uint64_t last = (uint64_t)cv_round((double)(sd.end_y - 1u) * sd.ystep) * stride + (uint64_t)cv_round((double)(sd.end_x - 1u) * sd.ystep);
+            if (last + pr.p3 >= (uint64_t)frame_elems) reach_ok = false;
+        }
         for (uint32_t iy = 0; iy < sd.end_y; ++iy) rows.push_back(UnitDev{(uint32_t)k, iy, 0, 0});
 
         // ---- LDS-tile path (vj_cv_tile.hip): stump cascades with linear stages and upright features.  A tile is tw x th
@@ -415,6 +431,10 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     if ((rc = pl->d_tiles.ensure(std::max<size_t>(tiles.size(), 1) * sizeof(UnitDev)))) return rc;
     if ((rc = pl->d_rows_rest.ensure(std::max<size_t>(rows_rest.size(), 1) * sizeof(UnitDev)))) return rc;
     if ((rc = pl->d_bit_segs.ensure(std::max<size_t>(bit_segs.size(), 1) * sizeof(UnitDev)))) return rc;
+    if (!prune.empty()) {
+        if ((rc = pl->d_prune.ensure(prune.size() * sizeof(CvPruneDev)))) return rc;
+        HIP_TRY(hipMemcpy(pl->d_prune.p, prune.data(), prune.size() * sizeof(CvPruneDev), hipMemcpyHostToDevice));
+    }
     if (!tiles.empty()) HIP_TRY(hipMemcpy(pl->d_tiles.p, tiles.data(), tiles.size() * sizeof(UnitDev), hipMemcpyHostToDevice));
     if (!rows_rest.empty()) HIP_TRY(hipMemcpy(pl->d_rows_rest.p, rows_rest.data(), rows_rest.size() * sizeof(UnitDev), hipMemcpyHostToDevice));
     if (!bit_segs.empty()) HIP_TRY(hipMemcpy(pl->d_bit_segs.p, bit_segs.data(), bit_segs.size() * sizeof(UnitDev), hipMemcpyHostToDevice));
@@ -432,7 +452,8 @@ static int get_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv
     uint64_t sf_bits;
     memcpy(&sf_bits, &p->scale_factor, 8);
     const bool small_batch = n_frames <= 4;
-    const vj_env::CvPlanKey key(c->uid, W, H, p->min_w, p->min_h, sf_bits, small_batch ? 1 : 0);
+    const bool prune = (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
+    const vj_env::CvPlanKey key(c->uid, W, H, p->min_w, p->min_h, sf_bits, (small_batch ? 1 : 0) | (prune ? 2 : 0));
     auto it = e->cv_plans.find(key);
     if (it != e->cv_plans.end()) {
         it->second->last_used = ++e->plan_tick;
@@ -461,9 +482,120 @@ static int get_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv
     return VJ_OK;
 }
 
+// The edge maps of `nf` frames already on the device (cvCanny(gray, edges, 0, 50, 3), vj_canny.hip) into e->d_edges: 0 / 255 bytes,
+// rows of *pitch bytes, frames pitch * H bytes apart.
+static int enqueue_canny(vj_env* e, const uint8_t* d_gray, size_t gray_frame_bytes, int gray_stride, int W, int H, int nf, int CH,
+                         uint32_t* pitch) {
+    const size_t px = (size_t)W * (size_t)H * (size_t)nf;
+    const uint32_t ep = ((uint32_t)W + 3u) & ~3u;
+    int rc;
+    if ((rc = e->d_canny_cls.ensure(px))) return rc;
+    if ((rc = e->d_canny_label.ensure(px * 4u))) return rc;
+    if ((rc = e->d_canny_flag.ensure(px))) return rc;
+    if ((rc = e->d_edges.ensure((size_t)ep * (size_t)H * (size_t)nf))) return rc;
+    CannyArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.gray = d_gray;
+    ca.gray_frame_bytes = gray_frame_bytes;
+    ca.gray_stride = (uint32_t)gray_stride;
+    ca.channels = (uint32_t)CH;
+    ca.width = (uint32_t)W;
+    ca.height = (uint32_t)H;
+    ca.n_frames = (uint32_t)nf;
+    ca.cls = (uint8_t*)e->d_canny_cls.p;
+    ca.label = (uint32_t*)e->d_canny_label.p;
+    ca.flag = (uint8_t*)e->d_canny_flag.p;
+    ca.edges = (uint8_t*)e->d_edges.p;
+    ca.edge_pitch = ep;
+    ca.edge_frame_bytes = (uint64_t)ep * (uint64_t)H;
+    const int hrc = launch_canny(ca, e->stream);
+    if (hrc) {
+        set_error("canny launch failed: %s", hipGetErrorString((hipError_t)hrc));
+        return VJ_ERR_HIP;
+    }
+    *pitch = ep;
+    return VJ_OK;
+}
+
+// The u32 integral of the edge maps into e->d_edge_sum (d_sum's geometry, zeroed slack rows): the banded integral kernels' sum-only
+// instances (launch_integral_sum); the band arrays are scratch shared with enqueue_integral on the same stream.
+static int enqueue_edge_integral(vj_env* e, uint32_t pitch, int W, int H, int nf) {
+    const uint32_t fe = frame_elems_for(W, H);
+    int rc;
+    if ((rc = e->d_edge_sum.ensure((size_t)fe * 4u * (size_t)nf))) return rc;
+    const size_t used = (size_t)(W + 1) * (size_t)(H + 1);
+    const bool zeroed = e->edge_slack_w == W && e->edge_slack_h == H && e->edge_slack_frames >= nf && e->edge_slack_sum == e->d_edge_sum.p;
+    for (int f = 0; f < nf && !zeroed; ++f)
+        HIP_TRY(hipMemsetAsync((uint32_t*)e->d_edge_sum.p + (size_t)f * fe + used, 0, (fe - used) * 4, e->stream));
+    if (!zeroed) {
+        e->edge_slack_w = W;
+        e->edge_slack_h = H;
+        e->edge_slack_frames = nf;
+        e->edge_slack_sum = e->d_edge_sum.p;
+    }
+    IntegralArgs ia;
+    memset(&ia, 0, sizeof(ia));
+    ia.channels = 1;
+    ia.gray = (const uint8_t*)e->d_edges.p;
+    ia.gray_frame_bytes = (uint64_t)pitch * (uint64_t)H;
+    ia.gray_stride = pitch;
+    ia.width = (uint32_t)W;
+    ia.height = (uint32_t)H;
+    ia.n_frames = (uint32_t)nf;
+    ia.n_bands = ((uint32_t)H + BAND_ROWS - 1) / BAND_ROWS;
+    ia.band_pitch = ((uint32_t)W + 3u) & ~3u;
+    ia.band_sum = (uint32_t*)e->d_band_sum.p;
+    ia.sum = (uint32_t*)e->d_edge_sum.p;
+    ia.frame_elems = fe;
+    const int hrc = launch_integral_sum(ia, e->stream);
+    if (hrc) {
+        set_error("edge integral launch failed: %s", hipGetErrorString((hipError_t)hrc));
+        return VJ_ERR_HIP;
+    }
+    return VJ_OK;
+}
+
+// The prune-bitmap kernels' arguments for the tile scales of this sub-batch (e->d_cv_prune_bits: the skip bitmap's size)
+static CvPruneArgs prune_args(vj_env* e, const CvPlan* pl, const CvArgs& a, int nf, unsigned long long* windows) {
+    CvPruneArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.sum = a.sum;
+    pa.edge_sum = a.edge_sum;
+    pa.scales = a.scales;
+    pa.prune = a.prune;
+    pa.segs = (const UnitDev*)pl->d_bit_segs.p;
+    pa.n_segs = pl->n_bit_segs;
+    pa.n_frames = (uint32_t)nf;
+    pa.frame_elems = a.frame_elems;
+    pa.stride = a.stride;
+    pa.bits_frame_words = pl->bits_frame_words;
+    pa.bits = (unsigned long long*)e->d_skip_bits.p;
+    pa.prune_bits = (unsigned long long*)e->d_cv_prune_bits.p;
+    pa.windows = windows;
+    return pa;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vj_canny(vj_env* e, const vj_image* image, uint8_t* edges, int edges_stride) {
+    if (!e || !image || !image->data || !edges || edges_stride < image->width) return VJ_ERR_ARG;
+    int ch, rc;
+    if ((rc = check_single_image(image, &ch))) return rc;
+    const int w = image->width, h = image->height;
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = ensure_image_buffers(e, w, h, 1, true, ch))) return rc;
+    const uint8_t* d_src;
+    size_t fb;
+    int gs;
+    if ((rc = stage_frames(e, image, 1, w, h, &d_src, &fb, &gs))) return rc;
+    uint32_t pitch = 0;
+    if ((rc = enqueue_canny(e, d_src, fb, gs, w, h, 1, ch, &pitch))) return rc;
+    HIP_TRY(hipMemcpy2DAsync(edges, (size_t)edges_stride, e->d_edges.p, pitch, (size_t)w, (size_t)h, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return VJ_OK;
+}
 
 void vj_cv_params_default(vj_cv_params* p) {
     if (!p) return;
@@ -523,6 +655,11 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
         int gray_stride;
         if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
         HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
+        if (pl->prune) {   // the edge maps and their integral
+            uint32_t pitch = 0;
+            if ((rc = enqueue_canny(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH, &pitch))) return rc;
+            if ((rc = enqueue_edge_integral(e, pitch, W, H, nf))) return rc;
+        }
         if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
         if (has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
         HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
@@ -552,6 +689,10 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
             a.stage_entered = (unsigned long long*)d_counts.p;
             a.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
             a.tree2 = pl->tree2 && !is_tree && !has_tilted && e->cv_tree2 ? 1u : 0u;
+            if (pl->prune) {
+                a.edge_sum = (const uint32_t*)e->d_edge_sum.p;
+                a.prune = (const CvPruneDev*)pl->d_prune.p;
+            }
             if (is_tree && pl->chains.n != 0u && !count && e->cv_tree_chains) {   // the rows kernel sweeps the chains too (cv_chain_sweep): a fail list per wave
                 a.chains = pl->chains;
                 const size_t waves = (size_t)std::max(1, e->n_cu * 4) * CV_WAVES_PER_BLOCK;
@@ -562,6 +703,7 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
             int hrc = 0;
             // (a stage tree's tile path leaves no per-stage counts of the visited windows: counted calls walk the rows)
             const bool tiles = pl->n_tile_scales != 0 && pl->class_first[2] != 0 && !(is_tree && (count || rows_only));
+            if (tiles && pl->prune && (rc = e->d_cv_prune_bits.ensure((size_t)pl->bits_frame_words * 8u * (size_t)nf))) return rc;
             uint32_t tq_cap = 0;
             if (tiles && is_tree) {
                 // Stage tree: the tiles run the linear prefix on every grid window (cv_tile_pass<2>), cv_tree_walk the rest of the
@@ -602,7 +744,7 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                     b.n_rows = pl->n_rows_rest;
                     const int nb = std::max(1, e->n_cu * (two ? pl->row_blocks : 4));
                     b.total_waves = (uint32_t)nb * CV_WAVES_PER_BLOCK;
-                    hrc = launch_cv_profile_pass(b, trees, false, true, nb, sB);
+                    hrc = launch_cv_profile_pass(b, trees, false, true, nb, sB, pl->prune);
                 }
                 uint32_t* tickets = a.det_count + 4;
                 uint32_t* tq_count = tickets + 32;
@@ -679,6 +821,11 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                 } else if (!hrc) {
                     hrc = launch_cv_tree_walk(w, std::max(1, e->n_cu * 4), e->stream);
                 }
+                if (!hrc && pl->prune) {   // pruned windows: rejects of the walk, never accepted
+                    CvPruneArgs pa = prune_args(e, pl, a, nf, nullptr);
+                    pa.accept = (unsigned long long*)e->d_cv_accept.p;
+                    hrc = launch_cv_prune_mark(pa, (int)std::max<uint32_t>(1u, (pa.n_segs * pa.n_frames + 3u) / 4u), e->stream);
+                }
                 if (!hrc) {
                     CascadeArgs ra;
                     memset(&ra, 0, sizeof(ra));
@@ -712,7 +859,7 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                     b.n_rows = pl->n_rows_rest;
                     const int nb = std::max(1, e->n_cu * (two ? pl->row_blocks : 4));
                     b.total_waves = (uint32_t)nb * CV_WAVES_PER_BLOCK;
-                    hrc = launch_cv_profile_pass(b, trees, count, is_tree, nb, sB);
+                    hrc = launch_cv_profile_pass(b, trees, count, is_tree, nb, sB, pl->prune);
                 }
                 CvTileArgs t;
                 memset(&t, 0, sizeof(t));
@@ -750,6 +897,11 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                         const int tb = (int)std::min<uint64_t>((uint64_t)n_cls * (uint64_t)nf, (uint64_t)e->n_cu * (uint64_t)per_cu);
                         hrc = launch_cv_tile_pass(ta, mode, count, pl->tree2, std::max(1, tb), e->stream);
                     }
+                    if (mode == 0 && !hrc && pl->prune) {   // pruned windows are "zeros" of the walk (prune bitmap: cv_prune_mark)
+                        // one wave per window row of a tile scale: the rows' words are latency-bound gathers, thousands of waves hide them
+                        const CvPruneArgs pa = prune_args(e, pl, a, nf, nullptr);
+                        hrc = launch_cv_prune_mark(pa, (int)std::max<uint32_t>(1u, (pa.n_segs * pa.n_frames + 3u) / 4u), e->stream);
+                    }
                     if (mode == 0 && !hrc) {   // reject bits -> visited bits, one recurrence domain per window row (skip_resolve)
                         CascadeArgs ra;
                         memset(&ra, 0, sizeof(ra));
@@ -759,6 +911,10 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                         ra.n_skip_segs = pl->n_bit_segs;
                         ra.n_frames = (uint32_t)nf;
                         hrc = launch_skip_resolve(ra, std::max(1, e->n_cu * 2), e->stream);
+                    }
+                    if (mode == 0 && !hrc && pl->prune) {   // ... visited but not evaluated: out of the visited bits, into counts.windows
+                        CvPruneArgs pa = prune_args(e, pl, a, nf, count ? a.stage_entered + VJ_MAX_STAGES : nullptr);
+                        hrc = launch_cv_prune_visited(pa, std::max(1, e->n_cu * 2), e->stream);
                     }
                 }
                 if (two) {
@@ -770,7 +926,7 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                 // should stay inside its 4 MiB L2 (64 x 1080p: 376 / 235 / 179 / 153 / 173 / 194 / 193 ms for 1 / 2 / 3 / 4 / 5 / 6 / 8)
                 const int n_blocks = std::max(1, e->n_cu * 4);
                 a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
-                hrc = launch_cv_profile_pass(a, trees, count, is_tree, n_blocks, e->stream);
+                hrc = launch_cv_profile_pass(a, trees, count, is_tree, n_blocks, e->stream, pl->prune);
             }
             if (hrc) {
                 set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));

@@ -406,7 +406,10 @@ __device__ __forceinline__ bool cv_visited(unsigned long long F, uint32_t lane, 
     return lane < n_valid && parity == 0u;
 }
 
-template <bool TREES, bool COUNT, bool STAGE_TREE>
+// (cv_pruned: vj_devutil.hpp, shared with the prune-bitmap kernel of the tile scales, vj_canny.hip)
+// PRUNE: CV_HAAR_DO_CANNY_PRUNING.  A pruned position is a "zero" of the walk like a reject (ixstep = 2) but is not evaluated;
+// the test comes before the border rule.  PRUNE = false compiles to the kernels of flags = 0.
+template <bool TREES, bool COUNT, bool STAGE_TREE, bool PRUNE = false>
 __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArgs a) {
     __shared__ CvQEntry lds_q[CV_WAVES_PER_BLOCK * CV_QCAP];
     __shared__ unsigned long long lds_words[CV_WAVES_PER_BLOCK][2][STAGE_TREE ? CV_TREE_SEG_GROUPS : 1];   // stage trees: verdict bits of a row segment
@@ -421,6 +424,7 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
     const uint32_t frame_bytes4 = a.frame_elems * 4u;
     const rsrc_t img = make_rsrc(a.sum, a.n_frames * frame_bytes4);
     const rsrc_t timg = make_rsrc(a.tilted != nullptr ? a.tilted : a.sum, a.n_frames * frame_bytes4);
+    const rsrc_t eimg = make_rsrc(PRUNE ? a.edge_sum : a.sum, a.n_frames * frame_bytes4);
     const uint32_t total = a.n_rows * a.n_frames;
 
     // Blocks are dealt round-robin over the 8 XCDs (observed placement; speed only): the waves that share an XCD — and its
@@ -447,6 +451,14 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
         const uint32_t frame_bytes = frame * frame_bytes4;
         const uint32_t y = (uint32_t)cv_round((double)iy * ystep);
         const bool row_border = y + win_h >= a.sum_h;          // pt.y + height >= sum.height -> -1 (tempcv.cpp:817-820)
+        uint32_t e0 = 0, e1 = 0, e2 = 0, e3 = 0;
+        if (PRUNE) {
+            kptr<CvPruneDev> pr = as_k(a.prune);
+            e0 = pr[slot].p0 * 4u;
+            e1 = pr[slot].p1 * 4u;
+            e2 = pr[slot].p2 * 4u;
+            e3 = pr[slot].p3 * 4u;
+        }
         const double thr0 = (double)stages[0].threshold;
         uint32_t carry = 0;   // parity of the run of rejects that ends at the last position seen
         uint32_t n_q = 0;
@@ -512,7 +524,8 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                     const uint32_t po = y * a.stride + x;
                     const uint32_t off = frame_bytes + po * 4u;
                     double vnf = 1.0;
-                    const bool eval = valid && !border;
+                    const bool pruned = PRUNE && valid && cv_pruned(eimg, img, off, e0, e1, e2, e3);
+                    const bool eval = valid && !border && !pruned;
                     if (eval) {
                         const int32_t isum = (int32_t)(ld_u32(img, off, q0 * 4u) - ld_u32(img, off, q1 * 4u) - ld_u32(img, off, q2 * 4u) +
                                                        ld_u32(img, off, q3 * 4u));
@@ -534,7 +547,7 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                             ptr = pass ? stages[s].on_pass : stages[s].on_fail;
                         }
                     }
-                    const unsigned long long fm = __ballot(ptr == -2), am = __ballot(ptr == -1), wm = __ballot(ptr >= 0);
+                    const unsigned long long fm = __ballot(ptr == -2 || pruned), am = __ballot(ptr == -1), wm = __ballot(ptr >= 0);
                     if (lane == 0) {
                         Fw[(ix0 - seg0) >> 6] = fm;
                         Aw[(ix0 - seg0) >> 6] = am;
@@ -572,7 +585,8 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
             const uint32_t po = y * a.stride + x;
             const uint32_t off = frame_bytes + po * 4u;
             double vnf = 1.0;
-            const bool eval = valid && !border;
+            const bool pruned = PRUNE && valid && cv_pruned(eimg, img, off, e0, e1, e2, e3);
+            const bool eval = valid && !border && !pruned;
             if (eval) {
                 const int32_t isum = (int32_t)(ld_u32(img, off, q0 * 4u) - ld_u32(img, off, q1 * 4u) - ld_u32(img, off, q2 * 4u) +
                                                ld_u32(img, off, q3 * 4u));
@@ -600,7 +614,7 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                         entered |= 1ull << s;
                     }
                 }
-                const unsigned long long F = __ballot(ptr == -2);
+                const unsigned long long F = __ballot(ptr == -2 || pruned);
                 const bool visited = cv_visited(F, lane, n_valid, carry);
                 if (COUNT) {
                     const unsigned long long vm = __ballot(visited);
@@ -624,11 +638,11 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
             if (eval)
                 fail0 = !(cv_stage_sum_mode<TREES>(img, timg, table + stages[0].first_node, stages[0].n_nodes, off, vnf, stages[0].cv_f64, a.tree2) >= thr0);
             // which positions does the sequential walk visit?  parity of the reject run below each lane
-            const unsigned long long F = __ballot(fail0);
+            const unsigned long long F = __ballot(fail0 || pruned);
             const bool visited = cv_visited(F, lane, n_valid, carry);
-            const bool pass0 = visited && !border && !fail0;
+            const bool pass0 = visited && !border && !fail0 && !pruned;
             if (COUNT) {
-                const unsigned long long vm = __ballot(visited), em = __ballot(visited && !border);
+                const unsigned long long vm = __ballot(visited), em = __ballot(visited && !border && !pruned);
                 if (lane == 0) {
                     atomicAdd(a.stage_entered + VJ_MAX_STAGES_DEV, (unsigned long long)__popcll(vm));
                     atomicAdd(a.stage_entered + 0, (unsigned long long)__popcll(em));
@@ -645,15 +659,25 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
     }
 }
 
-template <bool TREES, bool STAGE_TREE>
+template <bool TREES, bool STAGE_TREE, bool PRUNE = false>
 static void cv_launch(const CvArgs& a, bool count, dim3 g, dim3 b, hipStream_t stream) {
-    if (count) hipLaunchKernelGGL((cv_profile_pass<TREES, true, STAGE_TREE>), g, b, 0, stream, a);
-    else       hipLaunchKernelGGL((cv_profile_pass<TREES, false, STAGE_TREE>), g, b, 0, stream, a);
+    if (count) hipLaunchKernelGGL((cv_profile_pass<TREES, true, STAGE_TREE, PRUNE>), g, b, 0, stream, a);
+    else       hipLaunchKernelGGL((cv_profile_pass<TREES, false, STAGE_TREE, PRUNE>), g, b, 0, stream, a);
 }
 
-int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream_) {
+int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream_, bool prune) {
     hipStream_t stream = (hipStream_t)stream_;
     dim3 g(n_blocks), b(CV_WAVES_PER_BLOCK * 64);
+    if (prune) {
+        if (stage_tree) {
+            if (trees) cv_launch<true, true, true>(a, count, g, b, stream);
+            else       cv_launch<false, true, true>(a, count, g, b, stream);
+        } else {
+            if (trees) cv_launch<true, false, true>(a, count, g, b, stream);
+            else       cv_launch<false, false, true>(a, count, g, b, stream);
+        }
+        return (int)hipGetLastError();
+    }
     if (stage_tree) {
         if (trees) cv_launch<true, true>(a, count, g, b, stream);
         else       cv_launch<false, true>(a, count, g, b, stream);

@@ -249,6 +249,7 @@ constexpr int BAND_ROWS = 8;
 
 // Launch wrappers (defined in vj_kernels.hip); stream is a hipStream_t.
 int launch_integral(const IntegralArgs& a, void* stream);
+int launch_integral_sum(const IntegralArgs& a, void* stream);   // sum only (band_colsum_sum / band_scan_sum / band_rows_sum)
 int launch_cascade_pass(const CascadeArgs& a, bool from_grid, bool trees, bool last, bool count, bool general,
                         int n_blocks, void* stream);
 int launch_cascade_tile_pass(const CascadeArgs& a, bool trees, bool count, int n_blocks, void* stream);
@@ -393,6 +394,10 @@ constexpr int CV_WAVES_PER_BLOCK = 4;
 constexpr int VJ_MAX_STAGES_DEV = 64;  // == VJ_MAX_STAGES
 constexpr int CV_QCAP = 320;           // survivors of stage 0 a wave collects before it sweeps the later stages
 
+// CV_HAAR_DO_CANNY_PRUNING's test of a window (tempcv.cpp:1147-1158): element offsets, from the window origin, of the corners of
+// [cvRound(0.15 w), + cvRound(0.7 w)) x [cvRound(0.15 h), + cvRound(0.7 h)) in a (W + 1)-wide integral image
+struct CvPruneDev { uint32_t p0, p1, p2, p3; };
+
 struct CvArgs {
     const uint32_t* sum;
     const uint32_t* tilted;      // tilted integral images, same geometry as sum (null: no tilted features)
@@ -417,9 +422,13 @@ struct CvArgs {
     void* fail_scratch;          // ... CV_QCAP x 16 bytes per wave: where a chain's rejects wait for the next chain
     uint32_t tail_max;           // linear cascades: a wave's queue of at most this many windows evaluates a stage stump-parallel (<= CV_TAIL_MAX)
     uint32_t tree2;              // every tree is a root + its only node child, upright (frontalface_alt2): both nodes' gathers in flight
+    // CV_HAAR_DO_CANNY_PRUNING (read by the prune variants of cv_profile_pass only)
+    const uint32_t* edge_sum;    // integral images of the frames' edge maps, same geometry as sum
+    const CvPruneDev* prune;     // per scale slot: the pruning rectangle's corners
 };
 
-int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream);
+// launch_cv_profile_pass(..., prune): the CV_HAAR_DO_CANNY_PRUNING variants (tempcv.cpp:1147-1158)
+int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream, bool prune = false);
 
 // The profile's LDS-tile kernel (vj_cv_tile.hip): small scales of stump cascades with linear stages and upright features.
 constexpr int CVT_WAVES = 8;            // waves per workgroup
@@ -512,5 +521,41 @@ struct TiltedArgs {
 // the tilted integral as three banded prefix sums; diag: n_frames x bands x 2 x (W + H) dwords, col: n_frames x bands x (W + 1)
 int launch_tilted_bands(const TiltedArgs& a, uint32_t* diag, uint32_t* col, void* stream);
 int launch_grayscale(const TiltedArgs& a, uint8_t* dst, uint32_t dst_stride, void* stream);
+
+// The Canny edge map of CV_HAAR_DO_CANNY_PRUNING (vj_canny.hip): cvCanny(gray, edges, 0, 50, 3) for a batch of frames
+struct CannyArgs {
+    const uint8_t* gray;        // batch of frames (1 / 3 / 4 channels, as IntegralArgs)
+    uint64_t gray_frame_bytes;
+    uint32_t gray_stride;
+    uint32_t channels;
+    uint32_t width, height;
+    uint32_t n_frames;
+    uint8_t* cls;               // [frames][W * H] 0 not a candidate, 1 weak, 2 strong
+    uint32_t* label;            // [frames][W * H] union-find parents (frame-local pixel indices)
+    uint8_t* flag;              // [frames][W * H] 1: a root whose component holds a strong pixel
+    uint8_t* edges;             // [frames] x edge_frame_bytes, rows of edge_pitch bytes: 0 / 255
+    uint32_t edge_pitch;
+    uint64_t edge_frame_bytes;
+};
+int launch_canny(const CannyArgs& a, void* stream);   // four kernels and a memset: a fixed count whatever the content
+
+// CV_HAAR_DO_CANNY_PRUNING on the LDS-tile scales (vj_canny.hip): the pruning test of every grid window of the tile scales into a
+// bitmap of the tiles' layout (one recurrence domain per window row, CvPlan::bit_segs), which feeds the unchanged tile kernels:
+//   cv_prune_mark     prune_bits = the test; bits |= prune_bits (a pruned window is a "zero" of the walk); accept &= ~prune_bits
+//   cv_prune_visited  (after skip_resolve) visited &= ~prune_bits, the pruned visited windows counted into *windows
+struct CvPruneArgs {
+    const uint32_t* sum;
+    const uint32_t* edge_sum;
+    const CvScaleDev* scales;
+    const CvPruneDev* prune;
+    const UnitDev* segs;         // {scale slot, first word, words per row, -}
+    uint32_t n_segs, n_frames, frame_elems, stride, bits_frame_words;
+    unsigned long long* bits;        // reject bits (mark) / visited bits (visited)
+    unsigned long long* accept;      // stage trees: accept bits (null: linear cascade)
+    unsigned long long* prune_bits;
+    unsigned long long* windows;     // VJ_FLAG_COUNTERS: counts.windows (null: not counted)
+};
+int launch_cv_prune_mark(const CvPruneArgs& a, int n_blocks, void* stream);
+int launch_cv_prune_visited(const CvPruneArgs& a, int n_blocks, void* stream);
 
 }  // namespace vj

@@ -1981,7 +1981,9 @@ void vj_env_destroy(vj_env* e) {
     drop_plans(e);
     for (DevBuf* b : {&e->d_sum, &e->d_sqsum, &e->d_band_sum, &e->d_band_sq, &e->d_band_sqp, &e->d_tilted, &e->d_tilt_diag, &e->d_tilt_col, &e->d_out,
                       &e->d_skip_bits, &e->d_rois, &e->d_roi_units, &e->d_roi_det, &e->d_roi_tiles, &e->d_group, &e->d_cv_det, &e->d_cv_counts,
-                      &e->d_cv_accept, &e->d_cv_tq, &e->d_cv_fail_rows, &e->d_cv_fail_walk, &e->d_run_table})
+                      &e->d_cv_accept, &e->d_cv_tq, &e->d_cv_fail_rows, &e->d_cv_fail_walk, &e->d_run_table,
+                      &e->d_canny_cls, &e->d_canny_label, &e->d_canny_flag, &e->d_edges, &e->d_edge_sum,
+                      &e->d_cv_prune_bits})
         b->release();
     e->lane0.destroy();
     for (DevBuf& b : e->d_q) b.release();
@@ -2315,7 +2317,11 @@ int vj_integral_image(vj_env* e, const vj_image* image, uint32_t* sum, uint64_t*
     return VJ_OK;
 }
 
-static int check_single_image(const vj_image* image, int* ch_out) {
+}  // extern "C"
+
+namespace vj {
+// one image of vj_integral_image / vj_integral_tilted / vj_grayscale / vj_canny: channels, row stride, addressing limit
+int check_single_image(const vj_image* image, int* ch_out) {
     const int w = image->width, h = image->height, ch = image_channels(*image);
     if (w <= 0 || h <= 0 || (ch != 1 && ch != 3 && ch != 4) || image->stride < w * ch) return VJ_ERR_ARG;
     if ((uint64_t)(w + 1) * (uint64_t)(h + 3) >= (1ull << 30)) {
@@ -2325,6 +2331,9 @@ static int check_single_image(const vj_image* image, int* ch_out) {
     *ch_out = ch;
     return VJ_OK;
 }
+}  // namespace vj
+
+extern "C" {
 
 int vj_integral_tilted(vj_env* e, const vj_image* image, uint32_t* tilted) {
     if (!e || !image || !image->data || !tilted) return VJ_ERR_ARG;

@@ -110,6 +110,8 @@ struct CvPlan {
     int row_blocks = 1;               // workgroups per CU of cv_profile_pass next to the tiles
     uint32_t tree_prefix = 0;         // stage trees: stages of the linear prefix the tiles run (0: the cascade is linear)
     CvChainDev chains = {};           // stage trees: the part after the prefix as chains (n = 0: not of that shape)
+    bool prune = false;               // CV_HAAR_DO_CANNY_PRUNING: every scale on cv_profile_pass<..., PRUNE>; d_prune per scale slot
+    DevBuf d_prune;
     int tq_shift = -1;                // stage trees on tiles: the prefix survivors' sub-queues hold 1 / 2^shift of the tile windows
                                       // (-1: the environment's start value; lowered for THIS plan when a sub-queue overflows)
     uint64_t tile_windows = 0;        // grid windows of the tile scales, per frame
@@ -117,7 +119,7 @@ struct CvPlan {
     DevBuf d_tiles, d_rows_rest, d_bit_segs;
     uint64_t last_used = 0;
     void release_device() {
-        for (DevBuf* b : {&d_table, &d_scales, &d_stages, &d_rows, &d_tiles, &d_rows_rest, &d_bit_segs}) b->release();
+        for (DevBuf* b : {&d_table, &d_scales, &d_stages, &d_rows, &d_tiles, &d_rows_rest, &d_bit_segs, &d_prune}) b->release();
     }
 };
 
@@ -310,11 +312,17 @@ struct vj_env : vj::Tunables {
     typedef std::tuple<PlanKey, int> BalanceKey;    // the plan key with the cascade's content hash and split = 0, batch-size class
     std::map<BalanceKey, Balance> balance;
     uint64_t balance_tick = 0;
-    typedef std::tuple<uint64_t, int, int, int, int, uint64_t, int> CvPlanKey;   // cascade uid, W, H, min size, bits of the scale factor, call of <= 4 frames
+    typedef std::tuple<uint64_t, int, int, int, int, uint64_t, int> CvPlanKey;   // cascade uid, W, H, min size, bits of the scale factor,
+                                                                                  // call of <= 4 frames (bit 0) | canny pruning (bit 1)
     std::map<CvPlanKey, std::unique_ptr<vj::CvPlan>> cv_plans;
     vj::DevBuf d_cv_det, d_cv_counts;   // vj_detect_opencv: detection list and counters
     vj::DevBuf d_cv_accept, d_cv_tq;    // ... stage trees on tiles: accept bitmap, the queue of the prefix's survivors
     vj::DevBuf d_cv_fail_rows, d_cv_fail_walk;   // ... per-wave fail lists of the chain sweeps (rows kernel / chain pass)
+    // CV_HAAR_DO_CANNY_PRUNING / vj_canny (vj_canny.hip): class bytes, union-find parents, strong-root flags, the 0 / 255 edge
+    // maps and their integral images (a sub-batch's worth each)
+    vj::DevBuf d_canny_cls, d_canny_label, d_canny_flag, d_edges, d_edge_sum, d_cv_prune_bits;   // (+ the tile scales' prune bitmap)
+    int edge_slack_w = 0, edge_slack_h = 0, edge_slack_frames = 0;   // layout whose slack rows of d_edge_sum are known to be zero
+    void* edge_slack_sum = nullptr;
     uint64_t plan_tick = 0;
     int cv_tq_shift = 4;              // ... stage trees: the survivors' queue holds 1 / 2^shift of the tile windows (grows on overflow)
 };
@@ -322,6 +330,7 @@ struct vj_env : vj::Tunables {
 namespace vj {
 // image staging and the integral launches (vj_env.cpp)
 int image_channels(const vj_image& im);
+int check_single_image(const vj_image* image, int* ch_out);   // VJ_ERR_ARG / VJ_ERR_LIMIT, else the channel count
 uint32_t frame_elems_for(int W, int H);
 int ensure_image_buffers(vj_env* e, int W, int H, int frames, bool need_gray, int channels = 1, Lane* lane = nullptr);
 int enqueue_integral(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int stride, int W, int H, int frames,

@@ -78,49 +78,11 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 //                    per row a wave prefix scan along x (DPP) + carry of the chunks to the left.
 // All integers, so the result is exact: sum wraps mod 2^32 like CV_32S, sqsum is u64.
 
-__device__ __forceinline__ uint32_t load_px4(const uint8_t* row, uint32_t x, uint32_t width) {
-    // four pixels x..x+3 packed little-endian; pixels beyond the row read as 0
-    const uint8_t* p = row + x;
-    if (x + 4 <= width && ((uintptr_t)p & 3u) == 0) return *reinterpret_cast<const uint32_t*>(p);
-    uint32_t v = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        if (x + c < width) v |= (uint32_t)p[c] << (8 * c);
-    return v;
-}
+// load_px4 / bgr2gray / load_gray4: vj_devutil.hpp (shared with the Canny kernels, vj_canny.hip)
 
-// Image ingest: 3-channel BGR / 4-channel BGRA frames are converted on the fly with OpenCV's 8-bit
-// fixed-point BGR2GRAY, (1868 B + 9617 G + 4899 R + 8192) >> 14 (OpenCV 2.4.2 imgproc, the cvCvtColor the
-// reference calls at clif.cpp:328 — third-party arithmetic), fused into both pixel reads
-// of the integral so that no gray copy is written.
-__device__ __forceinline__ uint32_t bgr2gray(uint32_t b, uint32_t g, uint32_t r) {
-    return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
-}
-__device__ __forceinline__ uint32_t load_gray4(const uint8_t* row, uint32_t x, uint32_t width, uint32_t ch) {
-    if (ch <= 1u) return load_px4(row, x, width);
-    const uint8_t* p = row + (size_t)x * ch;
-    uint32_t v = 0;
-    if (x + 4 <= width && ((uintptr_t)p & 3u) == 0) {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
-        if (ch == 3u) {   // b0 g0 r0 b1 | g1 r1 b2 g2 | r2 b3 g3 r3
-            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-            v = bgr2gray(w0 & 0xffu, (w0 >> 8) & 0xffu, (w0 >> 16) & 0xffu) |
-                bgr2gray(w0 >> 24, w1 & 0xffu, (w1 >> 8) & 0xffu) << 8 |
-                bgr2gray((w1 >> 16) & 0xffu, w1 >> 24, w2 & 0xffu) << 16 |
-                bgr2gray((w2 >> 8) & 0xffu, (w2 >> 16) & 0xffu, w2 >> 24) << 24;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) v |= bgr2gray(w[c] & 0xffu, (w[c] >> 8) & 0xffu, (w[c] >> 16) & 0xffu) << (8 * c);
-        }
-        return v;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        if (x + c < width) v |= bgr2gray(p[c * ch], p[c * ch + 1u], p[c * ch + 2u]) << (8 * c);
-    return v;
-}
-
-__global__ __launch_bounds__(256) void band_colsum(IntegralArgs a) {
+// SQ = false (band_colsum_sum, band_scan_sum, band_rows_sum): the sum alone — the edge maps of CV_HAAR_DO_CANNY_PRUNING (vj_cv.cpp)
+template <bool SQ>
+__device__ __forceinline__ void band_colsum_body(const IntegralArgs& a) {
     const uint32_t x = (blockIdx.x * 256u + threadIdx.x) * 4u;
     const uint32_t band = blockIdx.y, frame = blockIdx.z;
     if (x >= a.band_pitch) return;
@@ -142,8 +104,10 @@ __global__ __launch_bounds__(256) void band_colsum(IntegralArgs a) {
     }
     const size_t o = ((size_t)frame * a.n_bands + band) * a.band_pitch + x;
     *reinterpret_cast<uint4*>(a.band_sum + o) = make_uint4(s[0], s[1], s[2], s[3]);
-    *reinterpret_cast<uint4*>(a.band_sq + o) = make_uint4(q[0], q[1], q[2], q[3]);
+    if (SQ) *reinterpret_cast<uint4*>(a.band_sq + o) = make_uint4(q[0], q[1], q[2], q[3]);
 }
+__global__ __launch_bounds__(256) void band_colsum(IntegralArgs a) { band_colsum_body<true>(a); }
+__global__ __launch_bounds__(256) void band_colsum_sum(IntegralArgs a) { band_colsum_body<false>(a); }
 
 __global__ __launch_bounds__(256) void band_scan(IntegralArgs a) {
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
@@ -169,6 +133,24 @@ __global__ __launch_bounds__(256) void band_scan(IntegralArgs a) {
             }
             s += ts[k];
             q += tq[k];
+        }
+        o += (size_t)8u * a.band_pitch;
+    }
+}
+// the prefix of the band sums alone (launch_integral_sum)
+__global__ __launch_bounds__(256) void band_scan_sum(IntegralArgs a) {
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= a.band_pitch) return;
+    uint32_t s = 0;
+    size_t o = (size_t)blockIdx.y * a.n_bands * a.band_pitch + x;
+    for (uint32_t b0 = 0; b0 < a.n_bands; b0 += 8u) {
+        uint32_t ts[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) ts[k] = b0 + k < a.n_bands ? a.band_sum[o + (size_t)k * a.band_pitch] : 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; ++k) {
+            if (b0 + k < a.n_bands) a.band_sum[o + (size_t)k * a.band_pitch] = s;
+            s += ts[k];
         }
         o += (size_t)8u * a.band_pitch;
     }
@@ -273,7 +255,7 @@ __device__ __forceinline__ void out_store(V* p, V v) {
 // plus the prefixes along x of the band's rows down to y.  A row's prefix of squares stays below 2^32 for rows of up
 // to 66051 pixels (Q = uint32_t: one 32-bit DPP scan per row and image); wider images scan in 64 bits.  All integer
 // arithmetic: the sum wraps mod 2^32 like CV_32S whatever the order of the additions, the squared sum is exact.
-template <typename Q, bool NT = false>
+template <typename Q, bool NT = false, bool SQ = true>
 __device__ __forceinline__ void band_rows_body(const IntegralArgs& a) {
     const uint32_t lane = lane_id();
     const uint32_t band = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -289,7 +271,7 @@ __device__ __forceinline__ void band_rows_body(const IntegralArgs& a) {
     if (band == 0) {  // row 0 of both outputs is zero
         for (uint32_t x = lane; x < ow; x += 64u) {
             sum[x] = 0u;
-            sqs[x] = 0ull;
+            if (SQ) sqs[x] = 0ull;
         }
     }
     uint32_t rs[BAND_ROWS];  // per row: total of the row left of the current chunk
@@ -313,6 +295,8 @@ __device__ __forceinline__ void band_rows_body(const IntegralArgs& a) {
         if (in) {  // column totals above the band
             const uint4 t = *reinterpret_cast<const uint4*>(a.band_sum + bo + x);
             as[0] = t.x; as[1] = as[0] + t.y; as[2] = as[1] + t.z; as[3] = as[2] + t.w;
+        }
+        if (in && SQ) {
             const ulonglong2 u0 = *reinterpret_cast<const ulonglong2*>(a.band_sq_prefix + bo + x);
             const ulonglong2 u1 = *reinterpret_cast<const ulonglong2*>(a.band_sq_prefix + bo + x + 2);
             aq[0] = u0.x; aq[1] = aq[0] + u0.y; aq[2] = aq[1] + u1.x; aq[3] = aq[2] + u1.y;
@@ -354,20 +338,22 @@ __device__ __forceinline__ void band_rows_body(const IntegralArgs& a) {
                 const size_t ro = (size_t)(y + 1u) * ow;
                 if (x0 == 0 && lane == 0) {  // column 0 is zero
                     sum[ro] = 0u;
-                    sqs[ro] = 0ull;
+                    if (SQ) sqs[ro] = 0ull;
                 }
                 if (x + 4u <= a.width) {
                     // 16 (sum) and 32 (squared sum) contiguous bytes per lane: the wave writes
                     // contiguous 1 KiB / 2 KiB runs; rows are only 4-byte aligned (odd stride)
                     out_store<NT>(reinterpret_cast<u32x4_unaligned*>(sum + ro + x + 1u), u32x4_unaligned{as[0], as[1], as[2], as[3]});
-                    out_store<NT>(reinterpret_cast<u64x2_unaligned*>(sqs + ro + x + 1u), u64x2_unaligned{aq[0], aq[1]});
-                    out_store<NT>(reinterpret_cast<u64x2_unaligned*>(sqs + ro + x + 3u), u64x2_unaligned{aq[2], aq[3]});
+                    if (SQ) {
+                        out_store<NT>(reinterpret_cast<u64x2_unaligned*>(sqs + ro + x + 1u), u64x2_unaligned{aq[0], aq[1]});
+                        out_store<NT>(reinterpret_cast<u64x2_unaligned*>(sqs + ro + x + 3u), u64x2_unaligned{aq[2], aq[3]});
+                    }
                 } else {
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
                         if (x + c < a.width) {
                             sum[ro + x + c + 1u] = as[c];
-                            sqs[ro + x + c + 1u] = aq[c];
+                            if (SQ) sqs[ro + x + c + 1u] = aq[c];
                         }
                 }
                 rs[r] += wave_last(is);
@@ -386,6 +372,7 @@ template <typename Q>
 __global__ __launch_bounds__(256) void band_rows(IntegralArgs a) { band_rows_body<Q>(a); }
 template <typename Q>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void band_rows_w3(IntegralArgs a) { band_rows_body<Q, true>(a); }
+__global__ __launch_bounds__(256) void band_rows_sum(IntegralArgs a) { band_rows_body<uint32_t, false, false>(a); }
 
 // The same rows with the CHUNKS of a band side by side instead of one after the other: a workgroup of up to eight waves takes one
 // band, wave w the 256 columns [x0 + 256 w, x0 + 256 (w + 1)) of every row of the band.  Each wave scans its chunk of the top
@@ -540,6 +527,15 @@ __global__ __launch_bounds__(512) void band_rows_par(IntegralArgs a) {
             }
         }
     }
+}
+
+// The sum alone (sqsum, band_sq and band_sq_prefix untouched): the integral of the edge maps of CV_HAAR_DO_CANNY_PRUNING.
+int launch_integral_sum(const IntegralArgs& a, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(band_colsum_sum, dim3((a.band_pitch / 4u + 255u) / 256u, a.n_bands, a.n_frames), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(band_scan_sum, dim3((a.band_pitch + 255u) / 256u, a.n_frames, 1), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(band_rows_sum, dim3((a.n_bands + 3u) / 4u, a.n_frames, 1), dim3(256), 0, stream, a);
+    return (int)hipGetLastError();
 }
 
 int launch_integral(const IntegralArgs& a, void* stream_) {

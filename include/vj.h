@@ -129,6 +129,14 @@ enum {
                                        cascade (VJ_ERR_UNSUPPORTED: the result is not a meaningful detection); with it they
                                        reproduce the reference's arithmetic.  vj_detect_opencv evaluates tilted features on
                                        the tilted integral as OpenCV does and ignores the flag.                            */
+    VJ_FLAG_CV_CANNY_PRUNING = 1u << 6, /* vj_detect_opencv only (OpenCV profile): cvHaarDetectObjects' CV_HAAR_DO_CANNY_PRUNING
+                                       (tempcv.hpp:127).  One edge map per frame, cvCanny(gray, edges, 0, 50, 3) (:1337-1343, see
+                                       vj_canny), and before the border rule and the cascade a test per visited window (:1147-1158,
+                                       :1385-1400): with (w, h) the scaled window, s = the edge map's sum and sq = the frame's own
+                                       sum over [x + cvRound(0.15 w), + cvRound(0.7 w)) x [y + cvRound(0.15 h), + cvRound(0.7 h)),
+                                       both int; s < 100 || sq < 20 prunes the window: not evaluated, and the walk skips the next
+                                       position as after a reject.  counters.windows counts pruned windows, stage_entered[0] does
+                                       not.  The clod-profile entry points ignore the flag.                                   */
 };
 
 typedef struct vj_params {
@@ -231,6 +239,11 @@ int  vj_grayscale(vj_env* e, const struct vj_image* image, uint8_t* gray, int gr
  * (tempcv.cpp:1335, :743-750): (h+1) x (w+1) u32, tilted(X, Y) = sum of gray(x, y) over y < Y,
  * |x - X + 1| <= Y - y - 1.  HOST output.                                                              */
 int  vj_integral_tilted(vj_env* e, const struct vj_image* image, uint32_t* tilted);
+/* cvCanny(gray, edges, 0, 50, 3) (OpenCV 2.4.2 imgproc; what CV_HAAR_DO_CANNY_PRUNING computes per frame, tempcv.cpp:1337-1343) on
+ * the 8-bit gray image vj_grayscale returns: Sobel 3x3 with replicated borders, |dx| + |dy|, non-maximum suppression, candidates
+ * m > 0, strong m > 50, and as edges every candidate 8-connected to a strong one.  255 / 0 bytes, written to the
+ * HOST buffer `edges` (edges_stride bytes per row).  Host or device input, 1 / 3 / 4 channels, any row stride.                   */
+int  vj_canny(vj_env* e, const struct vj_image* image, uint8_t* edges, int edges_stride);
 typedef struct vj_image {
     const uint8_t* data;       /* 8-bit, interleaved channels                   */
     int32_t width, height;
@@ -272,7 +285,8 @@ typedef struct vj_launch {
     uint64_t stage_entered[VJ_MAX_STAGES];  /* VJ_FLAG_COUNTERS: windows this launch took into each stage */
 } vj_launch;
 typedef struct vj_timing {     /* HIP-event times of the last vj_detect, ms     */
-    float integral_ms;         /* the three integral launches                   */
+    float integral_ms;         /* the three integral launches (vj_detect_opencv with VJ_FLAG_CV_CANNY_PRUNING: and the Canny
+                                  and edge-integral launches before them)                                                */
     float cascade_ms;          /* all cascade passes                            */
     float total_ms;            /* first kernel start → last kernel end          */
     int32_t n_cascade_launches;
@@ -318,7 +332,8 @@ typedef struct vj_cv_params {
     int32_t  min_w, min_h;     /* minSize (0 = none)                              */
     double   scale_factor;     /* 1.1                                             */
     uint32_t min_neighbors;
-    uint32_t flags;            /* VJ_FLAG_COUNTERS                                */
+    uint32_t flags;            /* VJ_FLAG_COUNTERS, VJ_FLAG_CV_CANNY_PRUNING (CV_HAAR_DO_CANNY_PRUNING; the
+                                  other CV_HAAR_* flags are other paths and have no counterpart here) */
 } vj_cv_params;
 void vj_cv_params_default(vj_cv_params* p);
 int  vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
