@@ -60,9 +60,9 @@ struct StageDev {
     int32_t  on_fail;      // next stage, or -2 reject
     uint32_t n_trees;
     uint32_t order;        // stage-tree sweep: the i-th record holds the i-th stage to visit (topological)
-    uint32_t sp_first;     // stump-parallel finish: index of the stage's first block in CascadeArgs::sp_blocks
+    uint32_t sp_first;     // wave-independent tail of a tile: index of the stage's first block in CascadeArgs::sp_blocks
     float    sp_delta;     // ... |tree-order stage sum - sequential stage sum| <= sp_delta for ANY window (see
-                           //     tile_stump_parallel): 4 * n * 2^-24 * sum_k max(|left_k|, |right_k|), rounded up
+                           //     tile_wave_tail): 4 * n * 2^-24 * sum_k max(|left_k|, |right_k|), rounded up
     uint32_t cv_f64;       // OpenCV profile: this stage multiplies in f64 (two_rects stump stage, tempcv.cpp:872-888)
     uint32_t pad[2];
 };
@@ -117,7 +117,7 @@ struct RoiTile {           // one LDS tile inside a region (cascade_tile_roi_pas
                            // of the image such a tile needs are staged
 };
 
-// One block of <= 64 consecutive nodes of a stage (stump-parallel finish of the tile kernel).
+// One block of <= 64 consecutive nodes of a stage (wave-independent tail of the tile kernel).
 struct SpBlock {
     uint32_t first_node;   // flat node index
     uint32_t desc;         // jn | jb << 8 | b << 16 | nb << 20 | stage << 24
@@ -137,12 +137,11 @@ constexpr int TILE_W = 64;           // windows per tile row (= lanes of a wave)
 constexpr int TILE_WAVE_CAP = 256;    // windows (= LDS queue entries) per wave of the tile kernel
 constexpr int TILE_CLASSES = 3;       // LDS size classes, one launch each
 constexpr int TILE_LDS_HEADER = (TILE_WAVES * TILE_WAVE_CAP * 2 + 32) * 4;  // queues + per-wave counts, bytes
-constexpr int TILE_SP_MAX_WINDOWS = 256;  // windows a tile may carry into the finish: entries + verdict masks + partial sums fit the 16 KiB queue area
+constexpr int TILE_SP_MAX_WINDOWS = 256;  // windows a tile may carry into the wave-independent tail (32 per wave): entries, survivors and verdict words fit the 16 KiB queue area
 constexpr int TILE_WS_MAX_WINDOWS = 512;  // wave-split finish: 8 chunks of packed entries (4 KiB) + 8 x 320 dwords of sums and verdict words
 constexpr int TILE_SEG_MAX_WINDOWS = 256;  // stage-tree chains inside a tile: population + reject list (256 entries each) around the scratch
 constexpr int TILE_SP_MAX_BLOCKS = 4;     // blocks of 64 stumps per stage at most (stages of <= 256 nodes)
 constexpr int TILE_SP_BLOCK = 64;         // stumps evaluated per round and window (= lanes of a wave)
-constexpr int TILE_SP_FIELDS = 14;        // dwords of a node record kept in the LDS copy of a stage's table
 
 struct CascadeArgs {
     const uint32_t* sum;        // batch sum images, frame f at f * frame_elems
@@ -194,15 +193,14 @@ struct CascadeArgs {
     unsigned long long tile_repack_mask;    // bit s: re-pack the tile's survivors across its waves before stage s
     // Finish of a tile: once it is down to <= tile_ws_max windows at a re-pack point at or after tile_sp_begin, it
     // runs the rest of the cascade itself with the wave-split finish (tile_wave_split) and, below tile_ws_min windows
-    // (stump cascades), the stump-parallel finish (tile_stump_parallel) — through the last stage.
+    // (stump cascades), the wave-independent tail (tile_wave_tail) — through the last stage.
     uint32_t  tile_sp_begin;                // >= number of stages: disabled
-    uint32_t  tile_sp_pad;                  // dwords of LDS reserved for the stump-parallel finish: two record blocks + leaf values (0 = off)
     uint32_t  identity_order;               // StageDev::order is 0, 1, 2, ... (every linear cascade)
     uint32_t  n_seg;                        // stage tree: chains after the linear prefix that a tile may run itself (0: none)
     uint32_t  seg_end[4];                   // ... end position (sweep order) of chain k; it starts where chain k-1 (or the prefix) ends
     uint32_t  seg_chain;                    // ... bit k: the rejects of chain k are the population of chain k+1
     uint32_t  tree2;                        // every tree has exactly two nodes, the second one the child of the first
-    uint32_t  tile_ws_min;                  // the wave-split finish hands over to the stump-parallel finish below this many
+    uint32_t  tile_ws_min;                  // the wave-split finish hands over to the wave-independent tail below this many
     uint32_t  tile_ws_max;                  // enter the wave-split finish when at most this many windows are left
     const SpBlock* sp_blocks;               // per block of <= 64 stumps, all stages in order
     uint32_t  n_sp_blocks;

@@ -141,15 +141,20 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
     const uint32_t stride = (uint32_t)W + 1u;
     const size_t n_nodes = c.nodes.size();
 
-    // stump-parallel finish: LDS room for two blocks of node records (field-major) and the leaf values of
-    // the largest stage (dwords); stages of more than TILE_SP_MAX_BLOCKS * 64 nodes rule it out
+    // wave-independent tail of a tile (tile_wave_tail): stages of more than TILE_SP_MAX_BLOCKS * 64 nodes rule it out.
+    // It needs no LDS beyond the header.  The tile shapes are still chosen as if the header also held what the former
+    // stump-parallel finish kept there (two blocks of 14-dword records at a pitch of 65, the leaf values of the largest
+    // stage): that LDS is no longer allocated, and growing the tiles into it is a change of its own.
+    uint32_t shape_header_bytes = TILE_LDS_HEADER;
     if (!pl->trees && !pl->general && e->tile_sp_begin < (int)c.stages.size()) {
         uint32_t mx = 0;
         for (size_t s = 0; s < c.stages.size(); ++s) mx = std::max(mx, pl->prog.n_nodes[s]);
-        if (mx <= (uint32_t)TILE_SP_MAX_BLOCKS * TILE_SP_BLOCK)
-            pl->sp_pad = (2u * TILE_SP_FIELDS * (TILE_SP_BLOCK + 1u) + 2u * mx + 3u) & ~3u;
+        if (mx <= (uint32_t)TILE_SP_MAX_BLOCKS * TILE_SP_BLOCK) {
+            pl->wave_tail = true;
+            shape_header_bytes += ((2u * 14u * (TILE_SP_BLOCK + 1u) + 2u * mx + 3u) & ~3u) * 4u;
+        }
     }
-    const uint32_t tile_header_bytes = TILE_LDS_HEADER + pl->sp_pad * 4u;
+    const uint32_t tile_header_bytes = TILE_LDS_HEADER;
     std::vector<NodeRec> table;
     std::vector<uint32_t> pos_tab;
     std::vector<std::pair<uint32_t, uint32_t>> tile_reach;   // per scale: how far right / down of a window origin its features read
@@ -227,8 +232,8 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
                 const uint32_t lds_cu = (160u - (uint32_t)e->tile_lds_reserve_kb) * 1024u;
                 // (2 KiB of the CU's share stay free so that the nested class blocks below can be rounded up to whole
                 // allocation granules)
-                const uint64_t budget = kb < 0 ? ((lds_cu - 2048u) / (uint32_t)(-kb) - tile_header_bytes) & ~63ull
-                                               : std::min<uint64_t>((uint64_t)kb * 1024u, 160u * 1024u - tile_header_bytes);
+                const uint64_t budget = kb < 0 ? ((lds_cu - 2048u) / (uint32_t)(-kb) - shape_header_bytes) & ~63ull
+                                               : std::min<uint64_t>((uint64_t)kb * 1024u, 160u * 1024u - shape_header_bytes);
                 for (uint32_t tw : kTw)
                     for (uint32_t th : kTh) {
                         const uint32_t nwt = tw * th;
@@ -353,7 +358,7 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
     }
     pl->n_order = (uint32_t)order.size();
     for (size_t s2 = 0; s2 < c.stages.size(); ++s2) pl->max_stage_nodes = std::max(pl->max_stage_nodes, pl->prog.n_nodes[s2]);
-    // blocks of <= 64 consecutive nodes per stage, balanced, for the stump-parallel finish of the tile kernel
+    // blocks of <= 64 consecutive nodes per stage, balanced, for the wave-independent tail of the tile kernel
     std::vector<SpBlock> sp_blocks;
     for (size_t s = 0; s < c.stages.size(); ++s) {
         const uint32_t S = pl->prog.n_nodes[s], nb = (S + TILE_SP_BLOCK - 1u) / TILE_SP_BLOCK;
@@ -1236,16 +1241,15 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
         ca.tile_end = pl->general ? pl->general_prefix : (uint32_t)e->tile_end;   // stage trees: tiles run the linear prefix only
         ca.tile_min_lanes = (uint32_t)e->tile_min_lanes;
         ca.tile_repack_mask = e->tile_repack_mask;
-        ca.tile_sp_begin = (!pl->general && (pl->sp_pad || pl->tree2)) ? (uint32_t)e->tile_sp_begin : 0xffffffffu;   // the finishes walk positions linearly: never on a stage tree
+        ca.tile_sp_begin = (!pl->general && (pl->wave_tail || pl->tree2)) ? (uint32_t)e->tile_sp_begin : 0xffffffffu;   // the finishes walk positions linearly: never on a stage tree
         ca.tree2 = pl->tree2 ? 1u : 0u;
         ca.identity_order = pl->general ? 0u : 1u;
         ca.n_seg = e->tile_segments ? pl->tile_n_seg : 0u;
         for (int k = 0; k < 4; ++k) ca.seg_end[k] = pl->tile_seg_end[k];
         ca.seg_chain = pl->tile_seg_chain;
-        ca.tile_sp_pad = pl->sp_pad;
         ca.sp_blocks = (const SpBlock*)pl->d_sp_blocks.p;
         ca.n_sp_blocks = pl->n_sp_blocks;
-        ca.tile_ws_min = pl->sp_pad != 0u ? (uint32_t)e->tile_ws_min : 0u;   // no stump-parallel tables: wave-split to the end
+        ca.tile_ws_min = pl->wave_tail ? (uint32_t)e->tile_ws_min : 0u;   // no wave-independent tail: wave-split to the end
         ca.tile_ws_max = (uint32_t)std::min(e->tile_ws_max, (int)TILE_WS_MAX_WINDOWS);
         ca.pos_mode = pl->pos_mode;
         ca.pos_tab = (const uint32_t*)pl->d_pos_tab.p;
@@ -1753,7 +1757,7 @@ static void fill_region_args(vj_env* e, Lane* L, Plan* pl2, const vj_cascade* se
     // Regions with large grids at the small scales (many raw candidates, big faces) run those grids on the tile kernel
     // (cascade_tile_roi_pass: tiles of the second cascade's two-per-CU tile scales, laid inside the region): stump cascades
     // whose plan has such tiles.  The caller sizes e->d_roi_tiles and zeroes the eight ticket counters.
-    if (e->roi_tile_min_windows > 0 && !pl2->general && !pl2->trees && pl2->sp_pad != 0u && pl2->class_first[1] > pl2->class_first[0] &&
+    if (e->roi_tile_min_windows > 0 && !pl2->general && !pl2->trees && pl2->wave_tail && pl2->class_first[1] > pl2->class_first[0] &&
         e->roi_tile_cap != 0u) {
         ra.tiles = (RoiTile*)e->d_roi_tiles.p;
         ra.n_tiles = roi_counts + 6;
@@ -1770,7 +1774,6 @@ static void fill_region_args(vj_env* e, Lane* L, Plan* pl2, const vj_cascade* se
         ca.tile_min_lanes = 0;
         ca.tile_repack_mask = e->tile_repack_mask;
         ca.tile_sp_begin = (uint32_t)e->tile_sp_begin;
-        ca.tile_sp_pad = pl2->sp_pad;
         ca.sp_blocks = (const SpBlock*)pl2->d_sp_blocks.p;
         ca.n_sp_blocks = pl2->n_sp_blocks;
         ca.tile_ws_min = (uint32_t)e->tile_ws_min;

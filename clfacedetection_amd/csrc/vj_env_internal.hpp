@@ -65,7 +65,7 @@ struct Plan {
     uint32_t class_lds[TILE_CLASSES] = {};        // dynamic LDS bytes of each class launch
     uint32_t tile_end = 0;                        // stage at which the tile launches stop
     bool tree2 = false;                           // every tree: two nodes, node 1 the only node child of node 0
-    uint32_t sp_pad = 0;                          // LDS pitch of the stump-parallel stage table (0 = off)
+    bool wave_tail = false;                       // stump cascade whose stages fit the wave-independent tail's blocks
     std::vector<uint32_t> pass_bounds;       // stage indices: pass p runs [b[p], b[p+1])
     uint64_t windows_per_frame = 0;
     uint32_t frame_elems = 0;
@@ -183,7 +183,7 @@ struct Tunables {
     // frame is bound by the latency of the gather chain's thin queue pass (measured, 1080p / frontalface_alt: 1 frame
     // 1.20 / 1.46 / 1.46 ms at split 0 / 0.5 / 1.25; 4 frames 3.50 / 3.61 / 3.96; 16 frames 12.51 / 12.25 / 12.36;
     // 64 frames — / 48.0 / 54.0), so small batches keep everything they can on the tiles
-    float tile_split = 2.0f;            // batches of >= 32 frames (round 4, band-major queue pass: 64 x 1080p 43.6 / 43.0 / 42.5 / 43.4 / 44.5 ms for 1.5 / 1.75 / 2 / 2.25 / 2.5; round 3: (four gather waves; 64 x 1080p: 46.70 / 46.24 / 45.57 / 45.16 / 45.55 / 46.72 ms for 0.75 / 1 / 1.25 / 1.5 / 1.75 / 2; 32: 23.39 / 23.16 / 22.80 / 22.62 / 22.78 / 23.38)
+    float tile_split = 1.5f;            // batches of >= 32 frames (round 8, wave-independent tile tail: 64 x 1080p 38.94 / 40.14 / 41.00 / 42.35 / 43.60 ms for 1.5 / 1.75 / 2 / 2.25 / 2.5, 32: 19.50 / 20.19 / 20.68 / 21.14 / 21.84; round 4, band-major queue pass: 64 x 1080p 43.6 / 43.0 / 42.5 / 43.4 / 44.5 ms for 1.5 / 1.75 / 2 / 2.25 / 2.5; round 3: (four gather waves; 64 x 1080p: 46.70 / 46.24 / 45.57 / 45.16 / 45.55 / 46.72 ms for 0.75 / 1 / 1.25 / 1.5 / 1.75 / 2; 32: 23.39 / 23.16 / 22.80 / 22.62 / 22.78 / 23.38)
     float tile_split_mid = 1.75f;       // 8 .. 31 frames (round 4, band-major queue pass: 16 x 1080p 11.53 / 11.36 / 11.13 / 11.01 / 10.89 / 10.90 ms for 0.75 ... 2.0; round 3: (16 x 1080p: 11.81 / 11.67 / 11.47 / 11.52 / 11.86 for 0.75 ... 1.75; 8: 6.03 / 5.95 / 5.97 / 6.24); 5 .. 7 frames (three gather waves): at most 0.5
     float tile_split_small = 0.0f;      // <= 4 frames
     int one_pass_max_frames = 0;        // calls of at most this many frames (of 720p and more, stump cascades) run the gather chain in ONE pass; 0: never.
@@ -223,7 +223,7 @@ struct Tunables {
     unsigned long long tile_repack_mask = ~3ull;  // stages (2 and later) before which a tile re-packs its survivors
     int tile_sp_begin = 3;        // first stage at which a tile may switch to the wave-split finish (>= 64: never)
     int tile_ws_max = 512;        // windows a tile may carry into the wave-split finish
-    int tile_ws_min = 48;         // ... below this many the stump-parallel finish takes over
+    int tile_ws_min = 48;         // ... below this many the wave-independent tail takes over
     int group_max = (int)vj::GROUP_MAX;   // vj_detect_chain groups up to this many raw candidates of one frame on the device (more: host path)
     bool tree_split_queues = true; // stage trees: the grid pass's survivors go down the tree while the tiles still run
     bool cv_tiles = true;         // OpenCV profile: small scales of stump cascades on LDS tiles (vj_cv_tile.hip)

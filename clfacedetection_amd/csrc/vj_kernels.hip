@@ -66,8 +66,8 @@ __device__ __forceinline__ float wave_sum_to_lane63(float v) {
 }
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains every outstanding
-// global load (s_waitcnt vmcnt(0)), which would serialise the record prefetches of the stump-parallel
-// finish behind a full memory round trip per block.
+// global load (s_waitcnt vmcnt(0)), which would serialise any global loads in flight (record prefetches)
+// behind a full memory round trip per barrier.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ===================================================================== integral
@@ -1773,179 +1773,131 @@ int launch_roi_chain(const RoiArgs& r, const CascadeArgs& a, bool from_dets, boo
 // detection; only a tile that stays crowded hands its windows to the global queues, as {global byte offset,
 // variance}.
 
-// Stump-parallel finish of a tile (stump cascades).  lds_q[0..T) holds the tile's T <= TILE_SP_MAX_WINDOWS
-// surviving windows.  Per stage, in blocks of <= 64 consecutive stumps: the block's node records are copied
-// to LDS field-major (four blocks are prefetched into registers meanwhile); lane j owns stump j of the
-// block, wave w takes windows w, w + 8, ... two at a time; a (window, block) result is 64 verdict bits — which
-// stumps answered alpha[1], one __ballot — and the block's leaf sum (a DPP butterfly).  After the stage's last
-// block, thread t adds window t's block sums: when that clears the stage threshold by more than sp_delta (the
-// host's bound on the difference between any two summation orders) the stage is decided; otherwise the thread
-// walks the window's bits IN STUMP ORDER and adds the leaf values (stage_sum += alpha[rect_sum >=
-// norm_threshold], clod.cl:81) — exactly the sequence of f32 additions a single lane would have made.  The
-// survivors are compacted across the waves.  Replaces the serial tail (one thin wave, ~300 cycles per stump) of
-// the late stages; the wave-split finish (further down) takes the populations above tile_ws_min.
+// Wave-independent finish of a tile (stump cascades).  lds_q[0..T) holds the tile's T < TILE_SP_MAX_WINDOWS surviving
+// windows.  They are dealt to the waves — wave w takes windows w, w + 8, ..., at most 32, lane k holding its k-th — and
+// from there on a wave runs its own windows to the end of the cascade without a workgroup barrier.  Per stage, in the
+// host's blocks of <= 64 consecutive stumps (CascadeArgs::sp_blocks): lane j holds stump j's record, which the wave loads
+// itself (coalesced, the next block in flight while this one is evaluated); per window of the wave's list a block gives
+// 64 verdict bits — which stumps answered alpha[1], one __ballot — and the block's leaf sum (a DPP butterfly).  After the
+// stage's last block lane k adds window k's block sums: when that clears the stage threshold by more than sp_delta (the
+// host's bound on the difference between any two summation orders) the stage is decided; otherwise the lane walks the
+// window's bits IN STUMP ORDER and adds the leaf values (stage_sum += alpha[rect_sum >= norm_threshold], clod.cl:81) —
+// exactly the sequence of f32 additions a single lane would have made.  The wave's survivors are compacted in registers.
+// Returns how many of the wave's windows survived the last stage (detections), written to out[0, n).
 template <bool COUNT, typename Img>
-__device__ __forceinline__ uint32_t tile_stump_parallel(const CascadeArgs& a, const Img& img_by_window,
-                                                        const uint32_t* table /* the scale's tile table, global */,
-                                                        QEntry* lds_q, unsigned long long* lds_mask, uint32_t* lds_sp,
-                                                        uint32_t* lds_cnt, uint32_t T, uint32_t st_begin,
-                                                        uint32_t n_stages, uint32_t lane, uint32_t wib) {
+__device__ __forceinline__ uint32_t tile_wave_tail(const CascadeArgs& a, const Img& img_by_window,
+                                                   const uint32_t* table /* the scale's tile table, global */,
+                                                   const QEntry* lds_q, QEntry* out, unsigned long long* masks, uint32_t T,
+                                                   uint32_t st_begin, uint32_t n_stages, uint32_t lane, uint32_t wib) {
     const auto img = img_by_window.by_stump();
     kptr<StageDev> stages = as_k(a.stages);
     kptr<uint32_t> blocks = as_k(reinterpret_cast<const uint32_t*>(a.sp_blocks));   // {first_node, desc} pairs
-    const uint32_t tid = wib * 64u + lane;
-    constexpr uint32_t PITCH = TILE_SP_BLOCK + 1u;   // odd pitch: the field-major copy is written conflict-free
-    constexpr uint32_t TABSZ = TILE_SP_FIELDS * PITCH;
-    constexpr uint32_t NT = TILE_WAVES * 64u;
     constexpr uint32_t MAXB = TILE_SP_MAX_BLOCKS;
-    constexpr int DEPTH = 4;                                         // record blocks in flight from global memory
-    uint32_t* lds_tab = lds_sp;                                      // two buffers of TABSZ dwords
-    uint32_t* lds_lx = lds_sp + 2u * TABSZ;   // {left, right} bit patterns of every stump of the stage
-    float* lds_part = reinterpret_cast<float*>(lds_mask + TILE_SP_MAX_WINDOWS * MAXB);   // butterfly partial sums
+    static_assert(TILE_SP_MAX_WINDOWS <= TILE_WAVES * 32, "a wave's list fits 32 lanes");
+    static_assert((TILE_SP_MAX_WINDOWS + TILE_WAVES * 32) * sizeof(QEntry) + TILE_WAVES * 32 * MAXB * 8 <=
+                      TILE_WAVES * TILE_WAVE_CAP * sizeof(QEntry), "windows, survivors and verdict words fit the queue area");
+    uint32_t nw = T > wib ? (T - wib + TILE_WAVES - 1u) / TILE_WAVES : 0u;   // (uniform) windows of this wave, <= 32
+    QEntry e{0u, 0.0f};
+    if (lane < nw) e = lds_q[wib + lane * TILE_WAVES];
+    uint32_t off = e.off;
+    float var = e.var;
+    if (nw == 0u) return 0u;
     const uint32_t g_end = a.n_sp_blocks;
     uint32_t g = stages[st_begin].sp_first;   // running block number over all stages
-    // records of block x: 16 dwords per node, thread t fetches dwords t and t + 512 of the block
-    uint32_t pre0[DEPTH], pre1[DEPTH];
-#pragma unroll
-    for (int u = 0; u < DEPTH; ++u) {
-        pre0[u] = 0u;
-        pre1[u] = 0u;
-        if (g + (uint32_t)u < g_end) {
-            const uint32_t jn = blocks[2u * (g + (uint32_t)u) + 1u] & 0xffu;
-            const uint32_t* src = table + (size_t)blocks[2u * (g + (uint32_t)u)] * 16u;
-            if (tid < jn * 16u) pre0[u] = src[tid];
-            if (tid + NT < jn * 16u) pre1[u] = src[tid + NT];
-        }
-    }
-    if (COUNT && tid == 0) atomicAdd(a.stage_entered + st_begin, (unsigned long long)T);
-    while (true) {
-#pragma unroll
-        for (int u = 0; u < DEPTH; ++u) {
-            const uint32_t desc = blocks[2u * g + 1u];
-            const uint32_t jn = desc & 0xffu, jb = (desc >> 8) & 0xffu, b = (desc >> 16) & 0xfu, nb = (desc >> 20) & 0xfu;
-            const uint32_t s = desc >> 24;
-            uint32_t* tab = lds_tab + (g & 1u) * TABSZ;
-            // 1. this block's records -> LDS field-major (lane j reads field f at tab[f * PITCH + j]); the leaf
-            // values also go to lds_lr in stage order for the accumulation
-            {
-                const uint32_t i0 = tid, i1 = tid + NT;
-                if (i0 < jn * 16u) {
-                    const uint32_t f = i0 & 15u, j = i0 >> 4;
-                    if (f < (uint32_t)TILE_SP_FIELDS) tab[f * PITCH + j] = pre0[u];
-                    if (f == 12u) lds_lx[(jb + j) * 2u] = pre0[u];
-                    if (f == 13u) lds_lx[(jb + j) * 2u + 1u] = pre0[u];
-                }
-                if (i1 < jn * 16u) {
-                    const uint32_t f = i1 & 15u, j = i1 >> 4;
-                    if (f < (uint32_t)TILE_SP_FIELDS) tab[f * PITCH + j] = pre1[u];
-                    if (f == 12u) lds_lx[(jb + j) * 2u] = pre1[u];
-                    if (f == 13u) lds_lx[(jb + j) * 2u + 1u] = pre1[u];
-                }
-            }
-            lds_barrier();
-            // refill this slot with the block DEPTH ahead (global-memory latency is ~2 us: with one block in
-            // flight the thin late stages would run at one block per round trip)
-            if (g + DEPTH < g_end) {
-                const uint32_t njn = blocks[2u * (g + DEPTH) + 1u] & 0xffu;
-                const uint32_t* src = table + (size_t)blocks[2u * (g + DEPTH)] * 16u;
-                if (tid < njn * 16u) pre0[u] = src[tid];
-                if (tid + NT < njn * 16u) pre1[u] = src[tid + NT];
-            }
-            // 2. verdict bits of the block
-            {
-                NodeRecDev r;
-#pragma unroll
-                for (int f = 0; f < TILE_SP_FIELDS; ++f) r[f] = tab[f * PITCH + (lane < jn ? lane : 0u)];
-                r[14] = 0u;
-                r[15] = 0u;
-                const float thr_node = __uint_as_float(r[11]);
-                const float leaf_l = lane < jn ? __uint_as_float(r[12]) : 0.0f;
-                const float leaf_r = lane < jn ? __uint_as_float(r[13]) : 0.0f;
-                // two windows per iteration: their gathers are independent, so the second window's LDS latency
-                // hides behind the first one's arithmetic
-                uint32_t w = wib;
-                for (; w + TILE_WAVES < T; w += 2u * TILE_WAVES) {
-                    const QEntry e0 = lds_q[w], e1 = lds_q[w + TILE_WAVES];   // broadcasts
-                    const float s0 = node_rect_sum(img, r, e0.off), s1 = node_rect_sum(img, r, e1.off);
-                    const bool right0 = lane < jn && s0 >= thr_node * e0.var;
-                    const bool right1 = lane < jn && s1 >= thr_node * e1.var;
-                    const unsigned long long m0 = __ballot(right0), m1 = __ballot(right1);
-                    const float part0 = wave_sum_to_lane63(right0 ? leaf_r : leaf_l);
-                    const float part1 = wave_sum_to_lane63(right1 ? leaf_r : leaf_l);
-                    if (lane == 63) {
-                        lds_mask[w * MAXB + b] = m0;
-                        lds_part[w * MAXB + b] = part0;
-                        lds_mask[(w + TILE_WAVES) * MAXB + b] = m1;
-                        lds_part[(w + TILE_WAVES) * MAXB + b] = part1;
-                    }
-                }
-                if (w < T) {
-                    const QEntry e = lds_q[w];   // broadcast
-                    const bool right = lane < jn && node_rect_sum(img, r, e.off) >= thr_node * e.var;
-                    const unsigned long long m = __ballot(right);
-                    // the block's leaf values summed across the lanes (DPP butterfly order — NOT the cascade's
-                    // order; it only feeds the fast decision below)
-                    const float part = wave_sum_to_lane63(right ? leaf_r : leaf_l);
-                    if (lane == 63) {
-                        lds_mask[w * MAXB + b] = m;
-                        lds_part[w * MAXB + b] = part;
-                    }
+    // the record of stump `lane` of block x (lanes past the block's end take its first stump: gathers stay in the tile)
+    auto fetch = [&](uint32_t x, uint4& r0, uint4& r1, uint4& r2, uint2& r3) {
+        const uint32_t jn = blocks[2u * x + 1u] & 0xffu;
+        const uint32_t* src = table + ((size_t)blocks[2u * x] + (lane < jn ? lane : 0u)) * 16u;
+        r0 = reinterpret_cast<const uint4*>(src)[0];
+        r1 = reinterpret_cast<const uint4*>(src)[1];
+        r2 = reinterpret_cast<const uint4*>(src)[2];
+        r3 = reinterpret_cast<const uint2*>(src)[6];
+    };
+    uint4 c0, c1, c2;
+    uint2 c3;
+    fetch(g, c0, c1, c2, c3);
+    for (uint32_t s = st_begin;; ++s) {
+        if (COUNT && lane == 0) atomicAdd(a.stage_entered + s, (unsigned long long)nw);
+        const uint32_t g0 = g, nb = (blocks[2u * g + 1u] >> 20) & 0xfu;
+        float approx = 0.0f;   // lane k: window k's block sums, added in block order
+        for (uint32_t b = 0; b < nb; ++b, ++g) {
+            const uint32_t jn = blocks[2u * g + 1u] & 0xffu;
+            NodeRecDev r;
+            r[0] = c0.x; r[1] = c0.y; r[2] = c0.z; r[3] = c0.w;
+            r[4] = c1.x; r[5] = c1.y; r[6] = c1.z; r[7] = c1.w;
+            r[8] = c2.x; r[9] = c2.y; r[10] = c2.z; r[11] = c2.w;
+            r[12] = c3.x; r[13] = c3.y; r[14] = 0u; r[15] = 0u;
+            // the next block (possibly the next stage's first) travels while this one is evaluated
+            fetch(g + 1u < g_end ? g + 1u : g, c0, c1, c2, c3);
+            const float thr_node = __uint_as_float(r[11]);
+            const float leaf_l = lane < jn ? __uint_as_float(r[12]) : 0.0f;
+            const float leaf_r = lane < jn ? __uint_as_float(r[13]) : 0.0f;
+            // two windows per iteration: their gathers are independent, so the second window's LDS latency hides behind
+            // the first one's arithmetic
+            uint32_t k = 0;
+            for (; k + 1u < nw; k += 2u) {
+                const uint32_t o0 = __builtin_amdgcn_readlane(off, k), o1 = __builtin_amdgcn_readlane(off, k + 1u);
+                const float v0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(var), k));
+                const float v1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(var), k + 1u));
+                const float s0 = node_rect_sum(img, r, o0), s1 = node_rect_sum(img, r, o1);
+                const bool right0 = lane < jn && s0 >= thr_node * v0;
+                const bool right1 = lane < jn && s1 >= thr_node * v1;
+                const unsigned long long m0 = __ballot(right0), m1 = __ballot(right1);
+                // the block's leaf values summed across the lanes (DPP butterfly order — NOT the cascade's order; it
+                // only feeds the fast decision below)
+                const float p0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_to_lane63(right0 ? leaf_r : leaf_l)), 63));
+                const float p1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_to_lane63(right1 ? leaf_r : leaf_l)), 63));
+                if (lane == k) approx += p0;
+                if (lane == k + 1u) approx += p1;
+                if (lane == 0) {
+                    masks[k * MAXB + b] = m0;
+                    masks[(k + 1u) * MAXB + b] = m1;
                 }
             }
-            ++g;
-            if (b + 1u == nb) {   // last block of stage s (uniform)
-                lds_barrier();   // every verdict of the stage is in lds_mask
-                // 3. the stage decision: thread t owns window t.  The sequential stage sum (stage_sum += alpha in
-                // stump order, clod.cl:81) and the butterfly-order sum of the same values differ by at most
-                // sp_delta (a rigorous a-priori bound, computed per stage on the host), so when the butterfly sum
-                // clears the stage threshold by more than sp_delta either way the reference's comparison is
-                // decided; only the rare windows inside the band walk their verdict bits in stump order.
-                float sum = 0.0f;
-                bool decided_pass = false;
-                if (tid < T) {
-                    float approx = 0.0f;
-                    for (uint32_t bb = 0; bb < nb; ++bb) approx += lds_part[tid * MAXB + bb];
-                    const float thr_s = stages[s].threshold, delta = stages[s].sp_delta;
-                    const float d = approx - thr_s;
-                    const bool clear = d > delta || d < -delta;
-                    decided_pass = d > delta;
-                    if (!clear) {
-                        // exact: sign-extend each verdict bit, pick left or right with and/xor, add in order
-                        const uint2* lx = reinterpret_cast<const uint2*>(lds_lx);
-                        uint32_t k0 = 0;
-                        for (uint32_t bb = 0; bb < nb; ++bb) {
-                            const uint32_t bjn = blocks[2u * (g - nb + bb) + 1u] & 0xffu;
-                            const unsigned long long m = lds_mask[tid * MAXB + bb];
-                            for (uint32_t k = 0; k < bjn; ++k) {
-                                const uint2 v = lx[k0 + k];
-                                sum += (m >> k) & 1ull ? __uint_as_float(v.y) : __uint_as_float(v.x);
-                            }
-                            k0 += bjn;
-                        }
-                        decided_pass = sum >= thr_s;
-                    }
-                }
-                // 4. survivors: compact lds_q across the waves
-                const bool pass = tid < T && decided_pass;
-                const QEntry e = lds_q[tid < T ? tid : 0u];
-                const unsigned long long mask = __ballot(pass);
-                if (lane == 0) lds_cnt[1u + wib] = (uint32_t)__popcll(mask);
-                lds_barrier();   // every entry is in registers, every wave's count is published
-                uint32_t before = 0, total = 0;
-#pragma unroll
-                for (uint32_t w = 0; w < TILE_WAVES; ++w) {
-                    const uint32_t c = lds_cnt[1u + w];
-                    before += w < wib ? c : 0u;
-                    total += c;
-                }
-                if (pass) lds_q[before + mbcnt(mask)] = e;
-                T = __builtin_amdgcn_readfirstlane(total);
-                lds_barrier();   // lds_q is repacked; lds_cnt / lds_mask / lds_lr may be rewritten
-                if (T == 0u || s + 1u >= n_stages) return T;
-                if (COUNT && tid == 0) atomicAdd(a.stage_entered + s + 1u, (unsigned long long)T);
+            if (k < nw) {
+                const uint32_t o0 = __builtin_amdgcn_readlane(off, k);
+                const float v0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(var), k));
+                const bool right0 = lane < jn && node_rect_sum(img, r, o0) >= thr_node * v0;
+                const unsigned long long m0 = __ballot(right0);
+                const float p0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_to_lane63(right0 ? leaf_r : leaf_l)), 63));
+                if (lane == k) approx += p0;
+                if (lane == 0) masks[k * MAXB + b] = m0;
             }
         }
+        // the stage decision, lane k for window k.  The sequential stage sum (stump order, clod.cl:81) and the
+        // butterfly-order sum of the same values differ by at most sp_delta (a rigorous a-priori bound, computed per stage
+        // on the host), so when the butterfly sum clears the stage threshold by more than sp_delta either way the
+        // reference's comparison is decided; only the rare windows inside the band replay their verdict bits in stump order.
+        const bool live = lane < nw;
+        const float thr_s = stages[s].threshold, delta = stages[s].sp_delta;
+        const float d = approx - thr_s;
+        const bool clear = d > delta || d < -delta;
+        bool pass = d > delta;
+        if (__ballot(live && !clear) != 0ull) {
+            __builtin_amdgcn_wave_barrier();   // (the verdict words above are this wave's own LDS writes)
+            float sum = 0.0f;
+            for (uint32_t bb = 0; bb < nb; ++bb) {
+                const uint32_t bjn = blocks[2u * (g0 + bb) + 1u] & 0xffu;
+                const unsigned long long m = masks[(live ? lane : 0u) * MAXB + bb];
+                kptr<uint32_t> lr = as_k(table + (size_t)blocks[2u * (g0 + bb)] * 16u);   // leaf values through the scalar cache
+                for (uint32_t j = 0; j < bjn; ++j)
+                    sum += (m >> j) & 1ull ? __uint_as_float(lr[j * 16u + 13u]) : __uint_as_float(lr[j * 16u + 12u]);
+            }
+            if (!clear) pass = sum >= thr_s;
+        }
+        pass = live && pass;
+        // survivors to the front of the wave's list: passing lanes to their rank, the others behind them (a permutation)
+        const unsigned long long pm = __ballot(pass);
+        const uint32_t below = mbcnt(pm), n_pass = (uint32_t)__popcll(pm);
+        const int dst = (int)(pass ? below : n_pass + lane - below) * 4;
+        off = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)off);
+        var = __int_as_float(__builtin_amdgcn_ds_permute(dst, __float_as_int(var)));
+        nw = n_pass;
+        __builtin_amdgcn_wave_barrier();   // the next stage's verdict words overwrite this one's
+        if (nw == 0u || s + 1u >= n_stages) break;
     }
+    if (lane < nw) out[lane] = QEntry{off, var};
+    return nw;
 }
 
 // Two consecutive stumps on one window with every gather of both in flight together.  The third
@@ -2066,7 +2018,7 @@ __device__ __forceinline__ uint32_t tile_wave_split(const CascadeArgs& a, const 
     // scratch behind the packed entries: per producing wave 64 range sums + 4 x 64 verdict words
     uint32_t* lds_x = reinterpret_cast<uint32_t*>(lds_q + TILE_WS_MAX_WINDOWS);
     uint32_t pos = st_io;   // position in the sweep order (StageDev::order); a linear cascade's order is 0, 1, 2, ...
-    // below tile_ws_min windows a chunk's lanes are mostly empty: the caller continues stump-parallel
+    // below tile_ws_min windows a chunk's lanes are mostly empty: the caller continues with the wave-independent tail
     for (; pos < n_stages && T != 0u && T >= a.tile_ws_min; ++pos) {
         const uint32_t s = a.identity_order != 0u ? pos : stages[pos].order;   // (no dependent load for linear cascades)
         if (COUNT && threadIdx.x == 0) atomicAdd(a.stage_entered + s, (unsigned long long)T);
@@ -2242,8 +2194,7 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[];
     QEntry* lds_q = reinterpret_cast<QEntry*>(lds_dyn);                   // TILE_WAVES * TILE_WAVE_CAP entries
     uint32_t* lds_cnt = lds_dyn + TILE_WAVES * TILE_WAVE_CAP * 2;         // survivors per wave (re-packing)
-    uint32_t* lds_tab = lds_dyn + TILE_LDS_HEADER / 4;                    // stump-parallel: one stage's table, field-major
-    uint32_t* lds_img = lds_tab + a.tile_sp_pad;                          // the image tile (tile_sp_pad: dwords of lds_tab)
+    uint32_t* lds_img = lds_dyn + TILE_LDS_HEADER / 4;                    // the image tile
     const uint32_t lane = lane_id();
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     QEntry* q = lds_q + wib * TILE_WAVE_CAP;
@@ -2552,15 +2503,21 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                         // few windows left: finish the whole cascade with the stage's stumps (or two-node trees) split
                         // over the waves
                         uint32_t s_next = st;
-                        uint32_t left = tile_wave_split<COUNT, TREES>(a, img, table, lds_q, lds_cnt, total, s_next, n_stages_total,
-                                                                      lane, wib, t_last);
-                        if (!TREES && left != 0u && s_next < n_stages_total)
-                            left = tile_stump_parallel<COUNT>(
-                                a, img, a.table + (size_t)table_first * 16u, lds_q,
-                                reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS), lds_tab, lds_cnt, left, s_next,
-                                n_stages_total, lane, wib);
+                        const uint32_t left = tile_wave_split<COUNT, TREES>(a, img, table, lds_q, lds_cnt, total, s_next,
+                                                                            n_stages_total, lane, wib, t_last);
                         q = lds_q;
                         n = wib == 0u ? left : 0u;
+                        if (!TREES && left != 0u && s_next < n_stages_total) {
+                            // below tile_ws_min windows: every wave finishes its share alone.  Behind the packed windows
+                            // [0, TILE_SP_MAX_WINDOWS): the waves' survivors (32 entries each), then their verdict words
+                            // (32 windows x TILE_SP_MAX_BLOCKS each) — all inside the queue area
+                            q = lds_q + TILE_SP_MAX_WINDOWS + wib * 32u;
+                            n = tile_wave_tail<COUNT>(
+                                a, img, a.table + (size_t)table_first * 16u, lds_q, q,
+                                reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS + TILE_WAVES * 32) +
+                                    wib * 32u * TILE_SP_MAX_BLOCKS,
+                                left, s_next, n_stages_total, lane, wib);
+                        }
                         dest = a.n_pass;
                         STAMP(12);
                         break;
@@ -2578,6 +2535,7 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
             if (n != 0u) flush_wave(q, n, dest);
             STAMP(13);
             __syncthreads();   // the member is finished: its queue may be rewritten, lds_cnt may carry the next ticket
+            STAMP(19);         // (waiting here for the workgroup's slowest wave: a tail ends per wave)
         }
         if (threadIdx.x == 0) lds_cnt[TILE_WAVES + 8] = next_u;
         __syncthreads();
