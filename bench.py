@@ -7,19 +7,24 @@ haarcascade_frontalface_alt, 1/2/4/8 GPUs — BASELINE config 3.  A "step" is on
 N > 1 — the all-gather of detection rectangles) over one batch of synthetic frames that
 is already resident in HBM.  BASELINE config 3 is a FIXED batch of 64 frames sharded over the GPUs, so the headline
 line is strong scaling: --frames is the whole job's batch and rank r takes its vj_shard_frames block of whole
-frames (it integrates only its own frames; the only collective is the final gather of rectangles).  For N > 1 the
-same run also times the weak-scaling variant (--frames per GPU) into `weak_scaling` and the same fixed job under the OTHER
-split into `other_sharding` (--shard levels: BASELINE config 3 as worded — the pyramid levels sharded, every rank
+frames (it integrates only its own frames; the only collective is the final gather of rectangles).  For N > 1, with
+--full, the same run also times the weak-scaling variant (--frames per GPU) into `weak_scaling` and the same fixed job under
+the OTHER split into `other_sharding` (--shard levels: BASELINE config 3 as worded — the pyramid levels sharded, every rank
 integrating every frame; --shard frames, the default and the better split, shards whole frames); `per_rank_ms_per_step`,
 `allgather_ms_per_step` and `collectives_per_step` say what every rank did and what the one collective cost.
 `--scaling weak` makes the weak variant the headline instead.  At N = 1 all of them are the same run.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
 
 Rank 0 prints ONE JSON line.  `value` is whole-job windows/s over the K timed steps
 (max over ranks of the wall time, barrier + synchronize on both sides).
+
+A plain run does only what that figure needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+the line, with the figures the timed steps give (`kernel_ms_per_step`, `frames_per_s`, ...).  Everything below takes runs
+of its own and is measured only with --full: `roofline`, `kernels` and `stump_evals_*` (a counted run), `cpu_baseline*`
+and `parity_sample_ok`, `opencv_profile`, `extra`, and for N > 1 `weak_scaling` and `other_sharding`.
 
 `roofline` is for the dominant kernel — the kernel group with the most time per step — against the ceiling that
 binds THAT kernel: the LDS-tile kernel gathers from LDS (`bound: "lds"`, peak = the guide's
@@ -32,7 +37,7 @@ passes) is only reported when profiles/pmc_dominant.json was collected from the 
 `cpu_baseline` is the CPU oracle (oracle/vj_oracle.c, a single-threaded restatement of the reference's clod path)
 timed on a bounded sample of the same frames; the sample doubles as a parity check of the TIMED (uncounted) step.
 
-`extra` (N = 1 only; --extras "" turns it off) measures the other BASELINE configs in the same run:
+`extra` (--full, N = 1 only; --extras "" turns it off) measures the other BASELINE configs in the same run:
   config2  one 1080p frame, host buffer in -> rectangles out: p50 / p90 latency over >= 50 calls
   config3_host_frames  config 3 with the frames in (page-locked) HOST memory: double-buffered vj_stream, H2D included
   config4  one 4096x4096 frame, frontalface_alt_tree
@@ -46,6 +51,7 @@ import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -83,15 +89,20 @@ def main() -> int:
     ap.add_argument("--shard", choices=("frames", "levels"), default="frames",
                     help="what the headline shards for N > 1: whole frames (vj_shard_frames; the better split for a batch) or the "
                          "pyramid levels (vj_shard_scales: BASELINE config 3 as worded — every rank integrates every frame and runs "
-                         "its share of the scales); the other split of the same fixed job is timed in the same run (`other_sharding`)")
+                         "its share of the scales); with --full the other split of the same fixed job is timed in the same run "
+                         "(`other_sharding`)")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong: --frames frames in total, sharded by whole frames (BASELINE config 3 as stated); "
                          "weak: --frames frames per GPU")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--cascade", default="frontalface_alt")
-    ap.add_argument("--cpu-frames", type=int, default=8, help="frames of the batch timed on the CPU oracle (0 = skip)")
-    ap.add_argument("--extras", "--config", default="1,2,3h,4,5", help="other BASELINE configs measured into `extra` "
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline, each with runs of its own: the counted run "
+                         "behind `roofline` / `kernels`, the CPU baselines and parity sample, the OpenCV profile, `extra`, "
+                         "and for N > 1 the other scaling and sharding variants")
+    ap.add_argument("--cpu-frames", type=int, default=8, help="with --full: frames of the batch timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--extras", "--config", default="1,2,3h,4,5", help="with --full: other BASELINE configs measured into `extra` "
                     "(1 = the reference's 640 x 480 case, 2, 3h = config 3 from host frames, 4, 5; \"\" = none)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to "
                     "rehearse the N > 1 path on a box with fewer GPUs than ranks)")
@@ -166,8 +177,11 @@ def main() -> int:
             first, B, job_frames = rank * args.frames, args.frames, args.frames * world
         # global frame g has seed 1 + g and kind g % 3 whatever the number of ranks: the job's result does not depend on N
         frames_h = np.empty((max(B, 1), H, W), np.uint8)
-        for i in range(max(B, 1)):
+
+        def make_frame(i):
             frames_h[i] = synth.frame(kinds[(first + i) % 3], 1 + first + i, H, W)
+        with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0)), len(frames_h)))) as ex:   # (numpy drops the GIL)
+            list(ex.map(make_frame, range(len(frames_h))))
         frames_d = torch.from_numpy(frames_h).to(dev)
         torch.cuda.synchronize()
         dframes = DeviceFrames.from_torch(frames_d[:B]) if B > 0 else None
@@ -183,10 +197,12 @@ def main() -> int:
         def step(params):
             return finish(env.detect(casc, dframes if B > 0 else [], params))
 
-        # one counted run: algorithmic bytes per launch (the counted kernel variants are slower and never timed)
-        pc = default_params(flags=VJ_FLAG_COUNTERS)
-        pc.scale_mask[0], pc.scale_mask[1] = p.scale_mask[0], p.scale_mask[1]
-        counted, _ = step(pc)
+        # --full: one counted run, algorithmic bytes per launch (the counted kernel variants are slower and never timed)
+        counted = None
+        if args.full:
+            pc = default_params(flags=VJ_FLAG_COUNTERS)
+            pc.scale_mask[0], pc.scale_mask[1] = p.scale_mask[0], p.scale_mask[1]
+            counted, _ = step(pc)
         # The timed steps go through a vj_stream (two batches in flight): step k's read-back, decode and sort on the host
         # overlap step k+1's kernels.  Every step still does everything — integral images, all cascade passes, read-back,
         # sorted rectangles (and the all-gather for N > 1) — and all of it completes inside the timed bracket; the frames
@@ -213,7 +229,7 @@ def main() -> int:
         if gather is not None:
             gather.total_ms, g0 = 0.0, gather.n_collectives
         t0 = time.perf_counter()
-        m = {"integral_ms": 0.0, "cascade_ms": 0.0, "pass_ms": None, "launch_ms": None, "launches": None,
+        m = {"integral_ms": 0.0, "cascade_ms": 0.0, "pass_ms": None, "launch_ms": None, "launches": None, "pass_split": None,
              "n_det_total": 0, "timed_rects": None}
         for r, rects in run_steps(args.steps):
             m["integral_ms"] += r.integral_ms
@@ -223,6 +239,7 @@ def main() -> int:
             lm = [l["ms"] for l in r.launches]
             m["launch_ms"] = lm if m["launch_ms"] is None else [a + b for a, b in zip(m["launch_ms"], lm)]
             m["launches"] = r.launches
+            m["pass_split"] = [x[0] for x in r.passes]
             m["n_det_total"] = len(rects)
             m["timed_rects"] = r.rects
             m["last_rects"] = rects
@@ -250,7 +267,7 @@ def main() -> int:
 
     m = measure(args.scaling if args.shard == "frames" else "strong", args.shard)
     other = other_shard = None
-    if world > 1:      # the other variants in the same run, so that every figure comes from the same box and build
+    if world > 1 and args.full:      # the other variants in the same run, so that every figure comes from the same box and build
         brief = lambda o: {"scaling": o["scaling"], "shard": o["shard"], "value": round(o["value"], 1), "unit": "windows/s",
                            "ms_per_step": round(o["ms_per_step"], 4), "frames_per_step_whole_job": o["job_frames"],
                            "per_rank_ms_per_step": o["per_rank_ms"], "allgather_ms_per_step": o["allgather_ms"],
@@ -272,141 +289,149 @@ def main() -> int:
     out = None
     if rank == 0:
         K = max(args.steps, 1)
-        # ---- per-kernel rooflines.  Launches are grouped by kernel (the names rocprofv3 --kernel-trace --stats
-        # reports); algorithmic bytes come from the counted run's PER-LAUNCH counters, time from the
-        # HIP events the library records around every launch on the stream it runs on, averaged over the timed steps.
-        nodes, trees, stages = casc.nodes, casc.trees, casc.stages
-        rects_per_stage = []
-        for st in stages:
-            tr = trees[st["first_tree"]:st["first_tree"] + st["n_trees"]]
-            rects_per_stage.append(int(sum(int(nodes["n_rects"][t["first_node"]:t["first_node"] + t["n_nodes"]].sum())
-                                           for t in tr)))
-        groups = {}
-        for l, ms in zip(launches, launch_ms):
-            g = groups.setdefault(l["kind"], {"ms": 0.0, "n": 0})
-            g["ms"] += ms / K
-            g["n"] += 1
-        per_kernel = {}
-        for kind, grp in groups.items():
-            b = 0
-            for l in counted.launches:
-                if l["kind"] != kind:
-                    continue
-                if kind != "queue":
-                    b += 48 * l["stage_entered"][0]
-                b += 16 * sum(n * rects_per_stage[st] for st, n in enumerate(l["stage_entered"]))
-            name, bound = KERNEL_OF[kind]
-            ach = b / (grp["ms"] * 1e-3) / 1e9 if grp["ms"] > 0 else 0.0
-            per_kernel[kind] = {"kernel": name, "bound": bound, "launches_per_step": grp["n"], "ms_per_step": round(grp["ms"], 3),
-                                "avg_launch_ms": round(grp["ms"] / grp["n"], 4),
-                                "algorithmic_bytes_per_launch": int(b // grp["n"]),
-                                "achieved": round(ach, 1), "peak": PEAK_GBPS[bound], "unit": "GB/s",
-                                "frac": round(ach / PEAK_GBPS[bound], 4)}
-            if bound == "l2":
-                # what binds a global gather is the texture-address unit, one per CU, which takes every lane of an uncoalesced
-                # wave-load in turn: the figure that compares passes is CU-cycles per lane-gather (4 bytes each; profiles/r04_notes.md
-                # has the counters).  Round 3 printed a "ceiling" measured at ONE lane stride here, which a pass that spans strides
-                # 3.8 ... 50 can beat: removed.
-                w_in = sum(l["stage_entered"][0] for l in counted.launches if l["kind"] == kind) if kind != "queue" else 0
-                lane_gathers = (b - 48 * w_in) / 4 + 8 * w_in      # four corners per evaluated rectangle + the variance's 4 + 4 corners
-                per_kernel[kind]["texture_address"] = {
-                    "lane_gathers_per_step": int(lane_gathers),
-                    "cu_ns_per_lane_gather": round(grp["ms"] * 1e6 * 256 / max(lane_gathers, 1), 4),
-                    "note": "launch time x 256 CUs / lane-gathers (rectangle corners + the variance's eight corners); "
-                            "x clock in GHz = texture-address cycles per lane"}
-        int_ach = 13 * W * H * B / (integral_ms / K * 1e-3) / 1e9
-        per_kernel["integral"] = {"kernel": "vj::band_colsum + vj::band_scan + vj::band_rows", "bound": "hbm", "launches_per_step": 3,
-                                  "ms_per_step": round(integral_ms / K, 4), "algorithmic_bytes_per_launch": 13 * W * H * B,
-                                  "achieved": round(int_ach, 1), "peak": PEAK_GBPS["hbm"], "unit": "GB/s",
-                                  "frac": round(int_ach / PEAK_GBPS["hbm"], 4),
-                                  "note": "1 B read + 12 B written per pixel over the three launches together"}
-        dom_kind = max(groups, key=lambda k: groups[k]["ms"])
-        dom = per_kernel[dom_kind]
-        # measured HBM traffic and SQ counters of the dominant kernel: only from a profile of THIS build's kernels
-        traffic, pmc_note, pmc_extra = None, "no rocprofv3 PMC profile of this build's kernels is committed", {}
-        pmc = os.path.join(ROOT, "profiles", "pmc_dominant.json")
-        if os.path.exists(pmc):
-            try:
-                j = json.load(open(pmc))
-                if j.get("kernel_kind") == dom_kind and j.get("kernel_source_hash") == kernel_source_hash():
-                    traffic = j.get("hbm_bytes_per_launch")
-                    pmc_note = f"profiles/pmc_dominant.json (from {j.get('source')}, kernel sources {j.get('kernel_source_hash')})"
-                    pmc_extra = {k: j[k] for k in ("lds_bank_conflict_share", "valu_busy", "lds_busy", "wave_wait_share") if k in j}
-                else:
-                    pmc_note = "profiles/pmc_dominant.json was collected from other kernel sources: not reported"
-            except Exception:
-                pass
-        roofline = {"bound": dom["bound"], "kernel": dom["kernel"], "launches_per_step": dom["launches_per_step"],
-                    "achieved": dom["achieved"], "peak": dom["peak"], "unit": "GB/s", "frac": dom["frac"],
-                    "traffic": traffic, "traffic_source": pmc_note,
-                    "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"], "avg_launch_ms": dom["avg_launch_ms"],
-                    "hbm_frac_of_traffic": round(traffic / (dom["avg_launch_ms"] * 1e-3) / 1e9 / PEAK_GBPS["hbm"], 4) if traffic else None,
-                    **pmc_extra,
-                    "note": "the dominant kernel gathers from image tiles staged in LDS: its ceiling is the LDS gather rate "
-                            "(ds_read_b32), not HBM; measured HBM traffic is `traffic`"}
+        full = {}
+        if args.full:
+            # ---- per-kernel rooflines.  Launches are grouped by kernel (the names rocprofv3 --kernel-trace --stats
+            # reports); algorithmic bytes come from the counted run's PER-LAUNCH counters, time from the
+            # HIP events the library records around every launch on the stream it runs on, averaged over the timed steps.
+            nodes, trees, stages = casc.nodes, casc.trees, casc.stages
+            rects_per_stage = []
+            for st in stages:
+                tr = trees[st["first_tree"]:st["first_tree"] + st["n_trees"]]
+                rects_per_stage.append(int(sum(int(nodes["n_rects"][t["first_node"]:t["first_node"] + t["n_nodes"]].sum())
+                                               for t in tr)))
+            groups = {}
+            for l, ms in zip(launches, launch_ms):
+                g = groups.setdefault(l["kind"], {"ms": 0.0, "n": 0})
+                g["ms"] += ms / K
+                g["n"] += 1
+            per_kernel = {}
+            for kind, grp in groups.items():
+                b = 0
+                for l in counted.launches:
+                    if l["kind"] != kind:
+                        continue
+                    if kind != "queue":
+                        b += 48 * l["stage_entered"][0]
+                    b += 16 * sum(n * rects_per_stage[st] for st, n in enumerate(l["stage_entered"]))
+                name, bound = KERNEL_OF[kind]
+                ach = b / (grp["ms"] * 1e-3) / 1e9 if grp["ms"] > 0 else 0.0
+                per_kernel[kind] = {"kernel": name, "bound": bound, "launches_per_step": grp["n"], "ms_per_step": round(grp["ms"], 3),
+                                    "avg_launch_ms": round(grp["ms"] / grp["n"], 4),
+                                    "algorithmic_bytes_per_launch": int(b // grp["n"]),
+                                    "achieved": round(ach, 1), "peak": PEAK_GBPS[bound], "unit": "GB/s",
+                                    "frac": round(ach / PEAK_GBPS[bound], 4)}
+                if bound == "l2":
+                    # what binds a global gather is the texture-address unit, one per CU, which takes every lane of an uncoalesced
+                    # wave-load in turn: the figure that compares passes is CU-cycles per lane-gather (4 bytes each; profiles/r04_notes.md
+                    # has the counters).  Round 3 printed a "ceiling" measured at ONE lane stride here, which a pass that spans strides
+                    # 3.8 ... 50 can beat: removed.
+                    w_in = sum(l["stage_entered"][0] for l in counted.launches if l["kind"] == kind) if kind != "queue" else 0
+                    lane_gathers = (b - 48 * w_in) / 4 + 8 * w_in      # four corners per evaluated rectangle + the variance's 4 + 4 corners
+                    per_kernel[kind]["texture_address"] = {
+                        "lane_gathers_per_step": int(lane_gathers),
+                        "cu_ns_per_lane_gather": round(grp["ms"] * 1e6 * 256 / max(lane_gathers, 1), 4),
+                        "note": "launch time x 256 CUs / lane-gathers (rectangle corners + the variance's eight corners); "
+                                "x clock in GHz = texture-address cycles per lane"}
+            int_ach = 13 * W * H * B / (integral_ms / K * 1e-3) / 1e9
+            per_kernel["integral"] = {"kernel": "vj::band_colsum + vj::band_scan + vj::band_rows", "bound": "hbm", "launches_per_step": 3,
+                                      "ms_per_step": round(integral_ms / K, 4), "algorithmic_bytes_per_launch": 13 * W * H * B,
+                                      "achieved": round(int_ach, 1), "peak": PEAK_GBPS["hbm"], "unit": "GB/s",
+                                      "frac": round(int_ach / PEAK_GBPS["hbm"], 4),
+                                      "note": "1 B read + 12 B written per pixel over the three launches together"}
+            dom_kind = max(groups, key=lambda k: groups[k]["ms"])
+            dom = per_kernel[dom_kind]
+            # measured HBM traffic and SQ counters of the dominant kernel: only from a profile of THIS build's kernels
+            traffic, pmc_note, pmc_extra = None, "no rocprofv3 PMC profile of this build's kernels is committed", {}
+            pmc = os.path.join(ROOT, "profiles", "pmc_dominant.json")
+            if os.path.exists(pmc):
+                try:
+                    j = json.load(open(pmc))
+                    if j.get("kernel_kind") == dom_kind and j.get("kernel_source_hash") == kernel_source_hash():
+                        traffic = j.get("hbm_bytes_per_launch")
+                        pmc_note = f"profiles/pmc_dominant.json (from {j.get('source')}, kernel sources {j.get('kernel_source_hash')})"
+                        pmc_extra = {k: j[k] for k in ("lds_bank_conflict_share", "valu_busy", "lds_busy", "wave_wait_share") if k in j}
+                    else:
+                        pmc_note = "profiles/pmc_dominant.json was collected from other kernel sources: not reported"
+                except Exception:
+                    pass
+            roofline = {"bound": dom["bound"], "kernel": dom["kernel"], "launches_per_step": dom["launches_per_step"],
+                        "achieved": dom["achieved"], "peak": dom["peak"], "unit": "GB/s", "frac": dom["frac"],
+                        "traffic": traffic, "traffic_source": pmc_note,
+                        "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"], "avg_launch_ms": dom["avg_launch_ms"],
+                        "hbm_frac_of_traffic": round(traffic / (dom["avg_launch_ms"] * 1e-3) / 1e9 / PEAK_GBPS["hbm"], 4) if traffic else None,
+                        **pmc_extra,
+                        "note": "the dominant kernel gathers from image tiles staged in LDS: its ceiling is the LDS gather rate "
+                                "(ds_read_b32), not HBM; measured HBM traffic is `traffic`"}
 
-        # ---- CPU baseline: the oracle, 1 thread, on the first --cpu-frames frames; the same sample checks the
-        # rectangles of the TIMED step (uncounted kernel variants) and of the counted run
-        cpu = cpu_mt = cpu_cv = None
-        parity = None
-        if world == 1 and args.cpu_frames > 0:
-            from oracle.oracle import Oracle, load_vjc
-            from clfacedetection_amd.api import DATA_DIR
-            o = Oracle()
-            a = load_vjc(os.path.join(DATA_DIR, f"haarcascade_{args.cascade}.vjc"))
-            n_cpu = min(args.cpu_frames, B)
-            t1 = time.perf_counter()
-            parity = True
-            for f in range(n_cpu):
-                ro, _ = o.detect(a, frames_h[f])
-                want = rows_of(ro)
-                parity = parity and rows_of(timed_rects, f) == want and rows_of(counted.rects, f) == want
-            cpu_s = time.perf_counter() - t1
-            parity = parity and bool(np.array_equal(timed_rects, counted.rects))   # every frame: timed == counted variants
-            cpu = {"value": round(windows_per_frame * n_cpu / cpu_s, 1), "unit": "windows/s", "cores": 1,
-                   "kind": "port", "sample": f"first {n_cpu} of the {B} frames, {cpu_s:.1f} s, oracle/vj_oracle.c "
-                   f"(gcc -O2 -ffp-contract=off, integral + all scales + all stages)"}
-            # the same oracle on every host core the box gives us (one frame per thread; ctypes drops the GIL)
-            from concurrent.futures import ThreadPoolExecutor
-            n_thr = max(1, min(len(os.sched_getaffinity(0)), B))
-            t2 = time.perf_counter()
-            with ThreadPoolExecutor(n_thr) as ex:
-                list(ex.map(lambda f: o.detect(a, frames_h[f]), range(n_thr)))
-            mt_s = time.perf_counter() - t2
-            cpu_mt = {"value": round(windows_per_frame * n_thr / mt_s, 1), "unit": "windows/s", "cores": n_thr,
-                      "kind": "port", "sample": f"{n_thr} frames, one per thread, {mt_s:.1f} s"}
-            # north_star's other CPU leg: the OpenCV-style scale-cascade path as tempcv.cpp keeps it.  It visits fewer
-            # windows than clod by design, so its honest unit is frames/s; compare with this line's "frames_per_s".
-            t3 = time.perf_counter()
-            vis = 0
-            for f in range(n_cpu):
-                _, st_cv = o.detect_opencvlike(a, frames_h[f])
-                vis += st_cv["windows"]
-            cv_s = time.perf_counter() - t3
-            t4 = time.perf_counter()
-            with ThreadPoolExecutor(n_thr) as ex:
-                list(ex.map(lambda f: o.detect_opencvlike(a, frames_h[f]), range(n_thr)))
-            cvmt_s = time.perf_counter() - t4
-            cpu_cv = {"value": round(n_cpu / cv_s, 3), "unit": "frames/s", "cores": 1, "kind": "port",
-                      "all_cores": {"value": round(n_thr / cvmt_s, 3), "unit": "frames/s", "cores": n_thr},
-                      "windows_visited_per_frame": vis // n_cpu,
-                      "sample": f"first {n_cpu} frames, {cv_s:.1f} s, oc_detect_opencvlike (restates tempcv.cpp "
-                                f"cvHaarDetectObjects; unpinned, timing only)"}
-        # the OpenCV arithmetic profile on the same frames (vj_detect_opencv): what a cvHaarDetectObjects user gets
-        cv_profile = None
-        extra = {}
-        if world == 1:
-            rcv = env.detect_opencv(casc, dframes, flags=VJ_FLAG_COUNTERS)   # (the counted kernel variant is slower: not timed)
-            env.detect_opencv(casc, dframes)
-            cv_t = []
-            for _ in range(3):       # (the GPU idled through the CPU baselines above: one call alone reads the clock ramp)
-                t5 = time.perf_counter()
+            # ---- CPU baseline: the oracle, 1 thread, on the first --cpu-frames frames; the same sample checks the
+            # rectangles of the TIMED step (uncounted kernel variants) and of the counted run
+            cpu = cpu_mt = cpu_cv = None
+            parity = None
+            if world == 1 and args.cpu_frames > 0:
+                from oracle.oracle import Oracle, load_vjc
+                from clfacedetection_amd.api import DATA_DIR
+                o = Oracle()
+                a = load_vjc(os.path.join(DATA_DIR, f"haarcascade_{args.cascade}.vjc"))
+                n_cpu = min(args.cpu_frames, B)
+                t1 = time.perf_counter()
+                parity = True
+                for f in range(n_cpu):
+                    ro, _ = o.detect(a, frames_h[f])
+                    want = rows_of(ro)
+                    parity = parity and rows_of(timed_rects, f) == want and rows_of(counted.rects, f) == want
+                cpu_s = time.perf_counter() - t1
+                parity = parity and bool(np.array_equal(timed_rects, counted.rects))   # every frame: timed == counted variants
+                cpu = {"value": round(windows_per_frame * n_cpu / cpu_s, 1), "unit": "windows/s", "cores": 1,
+                       "kind": "port", "sample": f"first {n_cpu} of the {B} frames, {cpu_s:.1f} s, oracle/vj_oracle.c "
+                       f"(gcc -O2 -ffp-contract=off, integral + all scales + all stages)"}
+                # the same oracle on every host core the box gives us (one frame per thread; ctypes drops the GIL)
+                n_thr = max(1, min(len(os.sched_getaffinity(0)), B))
+                t2 = time.perf_counter()
+                with ThreadPoolExecutor(n_thr) as ex:
+                    list(ex.map(lambda f: o.detect(a, frames_h[f]), range(n_thr)))
+                mt_s = time.perf_counter() - t2
+                cpu_mt = {"value": round(windows_per_frame * n_thr / mt_s, 1), "unit": "windows/s", "cores": n_thr,
+                          "kind": "port", "sample": f"{n_thr} frames, one per thread, {mt_s:.1f} s"}
+                # north_star's other CPU leg: the OpenCV-style scale-cascade path as tempcv.cpp keeps it.  It visits fewer
+                # windows than clod by design, so its honest unit is frames/s; compare with this line's "frames_per_s".
+                t3 = time.perf_counter()
+                vis = 0
+                for f in range(n_cpu):
+                    _, st_cv = o.detect_opencvlike(a, frames_h[f])
+                    vis += st_cv["windows"]
+                cv_s = time.perf_counter() - t3
+                t4 = time.perf_counter()
+                with ThreadPoolExecutor(n_thr) as ex:
+                    list(ex.map(lambda f: o.detect_opencvlike(a, frames_h[f]), range(n_thr)))
+                cvmt_s = time.perf_counter() - t4
+                cpu_cv = {"value": round(n_cpu / cv_s, 3), "unit": "frames/s", "cores": 1, "kind": "port",
+                          "all_cores": {"value": round(n_thr / cvmt_s, 3), "unit": "frames/s", "cores": n_thr},
+                          "windows_visited_per_frame": vis // n_cpu,
+                          "sample": f"first {n_cpu} frames, {cv_s:.1f} s, oc_detect_opencvlike (restates tempcv.cpp "
+                                    f"cvHaarDetectObjects; unpinned, timing only)"}
+            # the OpenCV arithmetic profile on the same frames (vj_detect_opencv): what a cvHaarDetectObjects user gets
+            cv_profile = None
+            extra = {}
+            if world == 1:
+                rcv = env.detect_opencv(casc, dframes, flags=VJ_FLAG_COUNTERS)   # (the counted kernel variant is slower: not timed)
                 env.detect_opencv(casc, dframes)
-                cv_t.append(time.perf_counter() - t5)
-            cv_s = sorted(cv_t)[1]
-            cv_profile = {"frames_per_s": round(B / cv_s, 1), "ms_per_step": round(cv_s * 1e3, 2),
-                          "windows_visited_per_frame": rcv.windows // B, "detections": len(rcv.rects), "dtype": "f64"}
-            extra = run_extras(env, casc, frames_h, [x.strip() for x in args.extras.split(",") if x.strip()], torch)
+                cv_t = []
+                for _ in range(3):       # (the GPU idled through the CPU baselines above: one call alone reads the clock ramp)
+                    t5 = time.perf_counter()
+                    env.detect_opencv(casc, dframes)
+                    cv_t.append(time.perf_counter() - t5)
+                cv_s = sorted(cv_t)[1]
+                cv_profile = {"frames_per_s": round(B / cv_s, 1), "ms_per_step": round(cv_s * 1e3, 2),
+                              "windows_visited_per_frame": rcv.windows // B, "detections": len(rcv.rects), "dtype": "f64"}
+                extra = run_extras(env, casc, frames_h, [x.strip() for x in args.extras.split(",") if x.strip()], torch)
+            full = {
+                ("weak_scaling" if m["scaling"] == "strong" else "strong_scaling"): other,
+                "other_sharding": other_shard,
+                "stump_evals_per_window": round(counted.stump_evals / max(counted.windows, 1), 3),
+                "stump_evals_per_s": round(counted.stump_evals / (ms_per_step * 1e-3), 1),
+                "roofline": roofline, "kernels": per_kernel, "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_mt,
+                "cpu_baseline_opencvlike": cpu_cv, "opencv_profile": cv_profile, "parity_sample_ok": parity, "extra": extra}
         out = {
             "metric": "candidate windows/sec, 1080p, haarcascade_frontalface_alt",
             "value": round(value, 1), "unit": "windows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -420,7 +445,7 @@ def main() -> int:
                        "parallelism": ((f"whole frames sharded over {world} ranks (vj_shard_frames)" if m["shard"] == "frames" else
                                         f"pyramid levels sharded over {world} ranks (vj_shard_scales; every rank integrates every frame)") +
                                        ", no data-path collective, ONE all-gather of fixed-capacity rectangle blocks per step") if world > 1 else "single GPU",
-                       "pass_split": [x[0] for x in counted.passes], "device": env.device_name,
+                       "pass_split": m["pass_split"], "device": env.device_name,
                        "pipeline": "blocking vj_detect calls" if args.no_pipeline else "vj_stream, two batches in flight"},
             "mpix_per_s": round(W * H * m["job_frames"] * args.steps / elapsed / 1e6, 1),
             "frames_per_s": round(m["job_frames"] * args.steps / elapsed, 1),
@@ -428,25 +453,20 @@ def main() -> int:
             "torch_world_size": (dist.get_world_size() if world > 1 else 1),      # (torch's number; the C++ host reads ncclCommCount: include/vj_rccl.h)
             "collective_backend": (args.backend if world > 1 else None),
             "allgather_ms_per_step": m["allgather_ms"], "collectives_per_step": m["collectives_per_step"],
-            ("weak_scaling" if m["scaling"] == "strong" else "strong_scaling"): other,
-            "other_sharding": other_shard,
             "detections_last_step": int(n_det_total),
             "kernel_ms_per_step": {"integral": round(integral_ms / K, 4), "cascade": round(cascade_ms / K, 4),
                                    "cascade_passes": [round(x / K, 4) for x in pass_ms],
                                    "launches": [{"kind": l["kind"], "lds_class": l["lds_class"],
                                                  "stages": [l["stage_begin"], l["stage_end"]], "n_scales": len(l["scales"]),
                                                  "ms": round(ms / K, 4)} for l, ms in zip(launches, launch_ms)]},
-            "stump_evals_per_window": round(counted.stump_evals / max(counted.windows, 1), 3),
-            "stump_evals_per_s": round(counted.stump_evals / (ms_per_step * 1e-3), 1),
-            "roofline": roofline, "kernels": per_kernel, "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_mt,
-            "cpu_baseline_opencvlike": cpu_cv, "opencv_profile": cv_profile, "parity_sample_ok": parity, "extra": extra,
+            **full,
         }
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if out is not None:
         print(json.dumps(out), flush=True)
-        if out["parity_sample_ok"] is False:
+        if out.get("parity_sample_ok") is False:
             print("bench.py: PARITY FAILURE on the CPU sample", file=sys.stderr)
             return 4
     return 0

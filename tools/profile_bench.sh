@@ -6,7 +6,7 @@ set -o pipefail
 STEPS=${STEPS:-5}; WARMUP=${WARMUP:-2}
 cd /tmp; export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 rm -rf gpurun_out/prof; mkdir -p gpurun_out/prof
-B="python bench.py --cpu-frames 0 --extras= --no-pipeline"
+B="python bench.py --full --cpu-frames 0 --extras= --no-pipeline"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/kt -- $B --steps $STEPS --warmup $WARMUP > gpurun_out/prof/kt.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/prof/fetch -- $B --steps 2 --warmup 1 > gpurun_out/prof/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/prof/write -- $B --steps 2 --warmup 1 > gpurun_out/prof/write.log 2>&1
