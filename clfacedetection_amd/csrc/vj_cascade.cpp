@@ -387,6 +387,8 @@ const char* vj_strerror(int code) {
     }
 }
 
+static int validate_cascade(const vj_cascade& c, const char* what);
+
 int vj_cascade_load_xml(const char* path, vj_cascade** out) {
     if (!path || !out) return VJ_ERR_ARG;
     *out = nullptr;
@@ -404,6 +406,7 @@ int vj_cascade_load_xml(const char* path, vj_cascade** out) {
     auto c = std::make_unique<vj_cascade>();
     rc = from_xml(root->kids[0].get(), c.get());
     if (rc) return rc;
+    if ((rc = validate_cascade(*c, path))) return rc;
     c->notice = "Converted from OpenCV " + root->kids[0]->name + ".xml. Original notice:\n" + xp.first_comment;
     vj::finish_cascade(c.get());
     *out = c.release();
@@ -448,6 +451,17 @@ static int validate_cascade(const vj_cascade& c, const char* what) {
                 if (r.x < 0 || r.y < 0 || r.w < 0 || r.h < 0 || r.x > 4096 || r.y > 4096 || r.w > 4096 || r.h > 4096 ||
                     !(r.weight == r.weight)) {
                     set_error("%s: node %d rect %d out of range", what, t.first_node + k, q);
+                    return VJ_ERR_PARSE;
+                }
+                // A rectangle the node uses (the evaluators read every weighted one) lies inside the window, by
+                // icvCreateHidHaarClassifierCascade's rule (tempcv.cpp:372-379): for a tilted one that is all four corners,
+                // (x, y), (x + w, y + w), (x - h, y + h) and (x + w - h, y + w + h).  The tile footprints and the
+                // frame-allocation checks of both profiles rely on it.
+                const bool inside = n.tilted ? r.x - r.h >= 0 && r.x + r.w <= c.win_w && r.y + r.w + r.h <= c.win_h
+                                             : r.x + r.w <= c.win_w && r.y + r.h <= c.win_h;
+                if ((q < n.n_rects || r.weight != 0.0f) && !inside) {
+                    set_error("%s: node %d rect %d (%s, x %d y %d w %d h %d) is not inside the %d x %d window", what,
+                              t.first_node + k, q, n.tilted ? "tilted" : "upright", r.x, r.y, r.w, r.h, c.win_w, c.win_h);
                     return VJ_ERR_PARSE;
                 }
             }

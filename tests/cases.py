@@ -263,3 +263,137 @@ def tunables(env, *settings):
         yield env
     finally:
         env.configure("defaults", "")
+
+
+# ----------------------------------------------------------------------------- feature geometry at the window's edges
+GEOMETRY_WINDOWS = ((20, 20), (24, 24), (45, 11), (14, 28), (7, 5))   # (win_w, win_h)
+GEOMETRY_KINDS = ("upright", "tilted", "tree")
+
+
+def _geometry_nodes(ww: int, wh: int, kind: str):
+    """The nodes of one geometry cascade, as stages of [(tilted, [(x, y, w, h, weight), ...])].  Every rectangle lies
+    inside the window by the loader's rule, most of them on one of its bounds; rect 0 always has an area (the evaluators
+    scale its weight by the others' areas over its own)."""
+    a = max(1, min(ww, wh) // 4)                       # side of the small tilted rectangles
+    hh = min(wh // 2, ww // 2)
+    dia = (hh, 0, min(ww - hh, wh - hh), hh)           # the largest tilted rectangle: x - h == 0, y == 0, on x + w or y + w + h
+    t_low = (a, wh - 2 * a, a, a)                      # x - h == 0, y + w + h == win_h
+    t_right = (ww - a, 0, a, a)                        # x + w == win_w, y == 0
+    t_min = (1, 0, 1, 1)                               # the smallest one, on x - h == 0 and y == 0
+    t_min_br = (ww - 1, wh - 2, 1, 1)                  # ... on x + w == win_w and y + w + h == win_h
+    half_w, half_h = max(1, ww // 2), max(1, wh // 2)
+    full = (0, 0, ww, wh)
+    upright = [
+        [(0, 0, ww, wh, -1.0), (ww // 3, wh // 3, max(1, ww // 3), max(1, wh // 3), 3.0)],           # the full window
+        [(ww - half_w, 0, half_w, wh, -1.0), (ww - 1, 0, 1, wh, 2.0)],                             # flush right, 1-px strip
+        [(0, wh - half_h, ww, half_h, -1.0), (0, wh - 1, ww, 1, 2.0)],                             # flush bottom, 1-px strip
+        [(0, 0, 1, wh, 1.0), (0, 0, ww, 1, -2.0)],                                                 # left / top strips, negative
+        [(ww - 2, wh - 2, 2, 2, -1.0), (0, 0, 2, 2, 1.0), (ww - 2, 0, 2, 2, 1.0)],                 # three corners
+        [(0, wh - 2, 2, 2, -1.0), (ww - 2, wh - 2, 2, 2, 2.0), (0, 0, ww, wh, 0.0)],               # w[2] == 0: rect 2 unused
+        [(1, 1, ww - 2, wh - 2, -1.0), (ww, 0, 0, wh, 2.0), (0, wh // 2, ww, half_h, -1.0)],       # w == 0 on the right bound
+        [(0, 0, half_w, half_h, -1.0), (0, wh, ww, 0, 1.0), (ww - half_w, wh - half_h, half_w, half_h, 2.0)],  # h == 0 at the bottom
+        [(0, 0, ww, wh, 1.0), (ww // 2, 0, ww - ww // 2, wh, -3.0), (0, 0, ww, wh // 2, -1.0)],    # negative weights, three rects
+    ]
+    tilted = [
+        [dia, (hh, 0, 1, 1, 2.0)],
+        [t_low, t_right],
+        [t_min, t_min_br],
+        [(dia[0], dia[1], dia[2], dia[3]), (a, wh - 2 * a, 0, a, 1.0), t_right],   # w == 0 inside, three rects
+        [(t_right[0], t_right[1], t_right[2], t_right[3]), (hh, 0, hh, 0, 1.0)],  # h == 0
+    ]
+    tilted = [[r if len(r) == 5 else (*r, (-1.0, 2.0, 1.5)[i]) for i, r in enumerate(n)] for n in tilted]
+    if kind == "upright":
+        return [[(0, n) for n in upright[:5]], [(0, n) for n in upright[5:]]]
+    if kind == "tilted":
+        return [[(1, n) for n in tilted], [(0, upright[0]), (1, tilted[0]), (0, upright[4]), (1, tilted[2])]]
+    # two-node trees: (root, child), the child hangs off the root's left branch
+    return [[((0, upright[1]), (1, tilted[1])), ((1, tilted[0]), (0, upright[2])), ((0, upright[6]), (0, upright[4]))],
+            [((1, tilted[2]), (1, tilted[3])), ((0, upright[0]), (1, tilted[4])), ((1, tilted[4]), (0, upright[8]))]]
+
+
+def geometry_cascade(ww: int, wh: int, kind: str):
+    """oracle CascadeArrays of a two-stage cascade whose features sit on the edges of a ww x wh window: kind "upright"
+    (stumps), "tilted" (stumps, tilted ones on each of the four tilted bounds) or "tree" (two-node trees mixing upright and
+    tilted nodes).  Node thresholds are 0, leaves 0 / 1 (0.5 on a tree root's right), and a stage passes when its trees' sum
+    reaches three quarters of their number: on noise, blocks and smooth frames some windows pass each stage, most do not."""
+    from oracle.oracle import CascadeArrays
+    c = CascadeArrays()
+    c.win_w, c.win_h = ww, wh
+    c.name = f"geometry_{kind}_{ww}x{wh}"
+    st_first, st_n, st_thr, tr_first, tr_n, tr_alpha = [], [], [], [], [], []
+    rects, weights, thr, left, right, tilted, alpha = [], [], [], [], [], [], []
+    for stage in _geometry_nodes(ww, wh, kind):
+        st_first.append(len(tr_first))
+        st_n.append(len(stage))
+        st_thr.append(0.75 * len(stage) - 0.125)
+        for tree in stage:
+            nodes = [tree] if kind != "tree" else list(tree)
+            tr_first.append(len(thr))
+            tr_n.append(len(nodes))
+            tr_alpha.append(len(alpha))
+            for k, (t, rr) in enumerate(nodes):
+                rr = list(rr) + [(0, 0, 0, 0, 0.0)] * (3 - len(rr))
+                rects += [r[:4] for r in rr]
+                weights += [r[4] for r in rr]
+                thr.append(0.0)
+                tilted.append(t)
+                if len(nodes) == 1:
+                    left.append(0); right.append(-1)
+                elif k == 0:
+                    left.append(1); right.append(0)            # left -> the child node, right -> alpha[0]
+                else:
+                    left.append(-1); right.append(-2)          # alpha[1], alpha[2]
+            alpha += [0.0, 1.0] if len(nodes) == 1 else [0.5, 0.0, 1.0]
+    c.stage_first_tree = np.array(st_first, np.int32)
+    c.stage_n_trees = np.array(st_n, np.int32)
+    c.stage_threshold = np.array(st_thr, np.float32)
+    c.stage_parent = np.arange(-1, len(st_first) - 1, dtype=np.int32)
+    c.stage_next = np.full(len(st_first), -1, np.int32)
+    c.stage_child = np.array(list(range(1, len(st_first))) + [-1], np.int32)
+    c.tree_first_node = np.array(tr_first, np.int32)
+    c.tree_n_nodes = np.array(tr_n, np.int32)
+    c.tree_first_alpha = np.array(tr_alpha, np.int32)
+    c.node_rect = np.array(rects, np.int32).reshape(-1)
+    c.node_weight = np.array(weights, np.float32)
+    c.node_threshold = np.array(thr, np.float32)
+    c.node_left = np.array(left, np.int32)
+    c.node_right = np.array(right, np.int32)
+    c.node_tilted = np.array(tilted, np.int32)
+    c.alpha = np.array(alpha, np.float32)
+    return c
+
+
+def rect_inside_window(x: int, y: int, w: int, h: int, tilted: bool, ww: int, wh: int) -> bool:
+    """The loader's rule (icvCreateHidHaarClassifierCascade's)."""
+    if min(x, y, w, h) < 0:
+        return False
+    if tilted:
+        return x - h >= 0 and x + w <= ww and y + w + h <= wh
+    return x + w <= ww and y + h <= wh
+
+
+def round_f32(v) -> int:
+    """round() of a positive binary32 value, half away from zero, as the plan rounds int * float (vj_plan.cpp)."""
+    return int(np.floor(np.float64(np.float32(v)) + 0.5))
+
+
+def overhangs(c, scales) -> dict:
+    """{"x": [...], "y": [...]}: (scale index, node, rect) of every weighted rectangle whose rounded far edge passes the
+    rounded window by one pixel at one of `scales` (ScaleInfo rows of the clod plan), in the plan's f32 arithmetic:
+    round(x s) + round(w s) == round(win_w s) + 1 (and in y)."""
+    out = {"x": [], "y": []}
+    r = c.node_rect.reshape(-1, 3, 4)
+    wt = c.node_weight.reshape(-1, 3)
+    for si in scales:
+        s = np.float32(si.scale)
+        ex, ey = round_f32(np.float32(c.win_w) * s), round_f32(np.float32(c.win_h) * s)
+        for n in range(c.n_nodes):
+            for q in range(3):
+                if wt[n, q] == 0:
+                    continue
+                x, y, w, h = (round_f32(np.float32(v) * s) for v in r[n, q])
+                if x + w == ex + 1:
+                    out["x"].append((si.scale_idx, n, q))
+                if y + h == ey + 1:
+                    out["y"].append((si.scale_idx, n, q))
+    return out

@@ -62,7 +62,7 @@ static const char* kXml =
     "            <right_val>0.8378106951713562</right_val></_></_>\n        <_>\n          <_>\n            <feature>\n              <rects>\n"
     "                <_>1 2 18 4 -1.</_>\n                <_>7 2 6 4 3.</_></rects>\n              <tilted>0</tilted></feature>\n"
     "            <threshold>0.0151513395830989</threshold>\n            <left_node>1</left_node>\n            <right_val>0.7488812208175659</right_val></_>\n"
-    "          <_>\n            <feature>\n              <rects>\n                <_>1 7 15 9 -1.</_>\n                <_>1 10 15 3 3.</_></rects>\n"
+    "          <_>\n            <feature>\n              <rects>\n                <_>9 2 9 9 -1.</_>\n                <_>9 5 9 3 3.</_></rects>\n"
     "              <tilted>1</tilted></feature>\n            <threshold>4.2109931819140911e-003</threshold>\n            <left_val>0.0900493934750557</left_val>\n"
     "            <right_val>0.6374819874763489</right_val></_></_></trees>\n      <stage_threshold>0.8226894140243530</stage_threshold>\n"
     "      <parent>-1</parent>\n      <next>-1</next></_>\n    <_>\n      <trees>\n        <_>\n          <_>\n            <feature>\n              <rects>\n"
@@ -133,6 +133,18 @@ int main(int argc, char** argv) {
         if (info.n_stages != 2 || info.n_trees != 3 || info.n_nodes != 4 || info.n_tilted != 1 || info.max_nodes_per_tree != 2) return 1;
         exercise(c);
         vj_cascade_free(c);
+    }
+    {   // the same cascade with a tilted rectangle whose corner (x - h, y + h) lies left of the window: refused at load
+        std::string out = xml;
+        const std::string legal = "<_>9 2 9 9 -1.</_>";
+        out.replace(out.find(legal), legal.size(), "<_>1 7 15 9 -1.</_>");
+        spit(xpath, out);
+        vj_cascade* c = nullptr;
+        const int rc = vj_cascade_load_xml(xpath.c_str(), &c);
+        if (rc != VJ_ERR_PARSE || c != nullptr || !strstr(vj_last_error(), "node 2 rect 0")) {
+            fprintf(stderr, "a tilted rectangle outside the window was not refused (%d: %s)\n", rc, vj_last_error());
+            return 1;
+        }
     }
     for (size_t len = 0; len < xml.size(); len += 3) {
         spit(xpath, xml.substr(0, len));

@@ -127,3 +127,128 @@ def test_loader_errors(tmp_path):
     lib = load_library()
     assert lib.vj_cascade_load(None, None) == 1
     assert lib.vj_strerror(3) == b"malformed cascade file"
+
+
+# ----------------------------------------------------------------------------- rectangles inside the window (the loader's rule)
+GEO_W, GEO_H = 20, 16          # not square: a swapped x / y bound shows
+# (tilted, x, y, w, h) of a node's rect 1, each on one or more bounds: x >= 0, y >= 0, x + w <= win_w, y + h <= win_h upright;
+# x - h >= 0, y >= 0, x + w <= win_w, y + w + h <= win_h tilted (icvCreateHidHaarClassifierCascade)
+ON_BOUNDS = [(0, 0, 0, GEO_W, GEO_H), (0, GEO_W - 3, GEO_H - 4, 3, 4), (0, 0, GEO_H - 1, GEO_W, 1), (0, GEO_W - 1, 0, 1, GEO_H),
+             (0, 0, 0, 1, 1), (0, GEO_W, 0, 0, GEO_H), (0, 0, GEO_H, GEO_W, 0),
+             (1, 3, 0, 4, 3), (1, 3, GEO_H - 7, 4, 3), (1, GEO_W - 4, 0, 4, 3), (1, 1, 0, 1, 1), (1, 8, 0, 8, 8),
+             (1, GEO_W - 1, GEO_H - 2, 1, 1), (1, 0, 0, 5, 0), (1, 3, 0, 0, 3)]
+OVER_BY_ONE = [(0, -1, 0, 3, 3), (0, 0, -1, 3, 3), (0, GEO_W - 2, 0, 3, 3), (0, 0, GEO_H - 2, 3, 3), (0, GEO_W + 1, 0, 0, 3),
+               (0, 0, GEO_H + 1, 3, 0), (0, 1, 1, GEO_W, GEO_H - 1), (0, 1, 0, GEO_W - 1, GEO_H + 1),
+               (1, 2, 0, 4, 3), (1, 3, -1, 4, 3), (1, GEO_W - 3, 0, 4, 3), (1, 3, GEO_H - 6, 4, 3), (1, 0, 0, 5, 1),
+               (1, 8, 1, 8, 8), (1, 9, 0, 12, 3)]
+POSITIVE = lambda probes: [p for p in probes if p[3] > 0 and p[4] > 0 and p[1] >= 0 and p[2] >= 0]
+
+
+def _probe_arrays(tilted, x, y, w, h):
+    """One stage, one stump; rect 0 lies inside the window, rect 1 is the probe (weight 2), rect 2 is unused."""
+    from clfacedetection_amd.api import NODE_DTYPE, STAGE_DTYPE, TREE_DTYPE
+    st = np.zeros(1, STAGE_DTYPE)
+    st[0] = (0, 1, 0.5, -1, -1, -1)
+    tr = np.zeros(1, TREE_DTYPE)
+    tr[0] = (0, 1, 0)
+    nd = np.zeros(1, NODE_DTYPE)
+    nd["n_rects"], nd["tilted"], nd["left"], nd["right"] = 2, tilted, 0, -1
+    nd["rect"][0, 0] = (1, 0, 1, 1, -1.0) if tilted else (0, 0, GEO_W, GEO_H, -1.0)
+    nd["rect"][0, 1] = (x, y, w, h, 2.0)
+    return st, tr, nd, np.array([0.0, 1.0], np.float32)
+
+
+def _probe_xml(path, tilted, x, y, w, h):
+    r0 = "1 0 1 1 -1." if tilted else f"0 0 {GEO_W} {GEO_H} -1."
+    path.write_text(f"""<?xml version="1.0"?>
+<opencv_storage>
+<probe type_id="opencv-haar-classifier">
+  <size>{GEO_W} {GEO_H}</size>
+  <stages>
+    <_>
+      <trees>
+        <_>
+          <_>
+            <feature>
+              <rects>
+                <_>{r0}</_>
+                <_>{x} {y} {w} {h} 2.</_></rects>
+              <tilted>{tilted}</tilted></feature>
+            <threshold>0.</threshold>
+            <left_val>0.</left_val>
+            <right_val>1.</right_val></_></_></trees>
+      <stage_threshold>0.5</stage_threshold>
+      <parent>-1</parent>
+      <next>-1</next></_></stages></probe>
+</opencv_storage>
+""")
+    return str(path)
+
+
+def _probe_vjc(tmp_path, tilted, x, y, w, h):
+    """A .vjc written by vj_cascade_save from a legal cascade, whose probe rectangle is then rewritten in the file."""
+    from clfacedetection_amd.api import NODE_DTYPE
+    legal = Cascade.from_arrays(GEO_W, GEO_H, *_probe_arrays(tilted, 1, 0, 1, 1))
+    path = tmp_path / f"probe_{tilted}_{x}_{y}_{w}_{h}.vjc"
+    legal.save(str(path))
+    blob = bytearray(path.read_bytes())
+    at = len(blob) - 2 * 4 - NODE_DTYPE.itemsize                  # the one node sits just before the two leaf values
+    nd = np.frombuffer(bytes(blob[at:at + NODE_DTYPE.itemsize]), NODE_DTYPE).copy()
+    assert (int(nd["rect"][0, 1]["x"]), int(nd["rect"][0, 1]["w"])) == (1, 1)
+    nd["rect"][0, 1] = (x, y, w, h, 2.0)
+    blob[at:at + NODE_DTYPE.itemsize] = nd.tobytes()
+    path.write_bytes(bytes(blob))
+    return str(path)
+
+
+def test_every_shipped_cascade_loads():
+    names = sorted(f for f in os.listdir(DATA_DIR) if f.startswith("haarcascade_") and f.endswith(".vjc"))
+    assert len(names) == 19
+    for f in names:
+        assert Cascade.load(os.path.join(DATA_DIR, f)).info.n_stages > 0, f
+
+
+@pytest.mark.parametrize("probe", ON_BOUNDS, ids=[f"{'tilted' if p[0] else 'upright'}-{p[1]}_{p[2]}_{p[3]}_{p[4]}" for p in ON_BOUNDS])
+def test_rectangles_on_the_bounds_load(tmp_path, probe):
+    c = Cascade.from_arrays(GEO_W, GEO_H, *_probe_arrays(*probe))
+    assert c.nodes["rect"][0, 1]["x"] == probe[1] and c.info.n_tilted == probe[0]
+    assert Cascade.load(_probe_vjc(tmp_path, *probe)).nodes["rect"][0, 1]["w"] == probe[3]
+    if probe in POSITIVE([probe]):               # OpenCV's XML reader wants positive widths and heights
+        assert Cascade.load_xml(_probe_xml(tmp_path / "p.xml", *probe)).info.n_tilted == probe[0]
+
+
+@pytest.mark.parametrize("probe", OVER_BY_ONE, ids=[f"{'tilted' if p[0] else 'upright'}-{p[1]}_{p[2]}_{p[3]}_{p[4]}" for p in OVER_BY_ONE])
+def test_rectangles_one_pixel_outside_are_refused(tmp_path, probe):
+    """from_arrays, .vjc and XML all refuse the cascade with VJ_ERR_PARSE, naming the node and the rectangle."""
+    loaders = [lambda: Cascade.from_arrays(GEO_W, GEO_H, *_probe_arrays(*probe)),
+               lambda: Cascade.load(_probe_vjc(tmp_path, *probe))]
+    if probe in POSITIVE([probe]):
+        loaders.append(lambda: Cascade.load_xml(_probe_xml(tmp_path / "p.xml", *probe)))
+    for load in loaders:
+        with pytest.raises(VjError) as e:
+            load()
+        assert e.value.code == 3, e.value
+        assert "node 0 rect 1" in str(e.value) or "rect exceeds the window" in str(e.value), e.value
+
+
+def test_unused_rectangles_are_not_checked():
+    """A third rectangle with weight 0 is no part of the feature: its geometry does not matter."""
+    st, tr, nd, al = _probe_arrays(0, 0, 0, 3, 3)
+    nd["rect"][0, 2] = (GEO_W - 2, GEO_H - 2, 3, 3, 0.0)
+    Cascade.from_arrays(GEO_W, GEO_H, st, tr, nd, al)
+    nd["rect"][0, 2]["weight"] = 1.0
+    nd["n_rects"] = 3
+    with pytest.raises(VjError):
+        Cascade.from_arrays(GEO_W, GEO_H, st, tr, nd, al)
+
+
+@pytest.mark.parametrize("win", [(20, 20), (24, 24), (45, 11), (14, 28), (7, 5)], ids=lambda w: f"{w[0]}x{w[1]}")
+def test_geometry_cascades_load(win):
+    """The GPU suite's edge-geometry cascades (tests/cases.py) are legal: every rectangle inside the window."""
+    from cases import GEOMETRY_KINDS, cascade_to_product, geometry_cascade, rect_inside_window
+    for kind in GEOMETRY_KINDS:
+        a = geometry_cascade(*win, kind)
+        r, wt = a.node_rect.reshape(-1, 3, 4), a.node_weight.reshape(-1, 3)
+        assert all(rect_inside_window(*r[n, q], bool(a.node_tilted[n]), *win)
+                   for n in range(a.n_nodes) for q in range(3) if wt[n, q] != 0)
+        assert cascade_to_product(a).info.n_nodes == a.n_nodes

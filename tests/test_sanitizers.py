@@ -18,7 +18,9 @@ def _asan_runtime():
 
 
 @pytest.mark.skipif(_asan_runtime() is None, reason="no libasan in this toolchain")
-def test_host_sources_under_asan_ubsan(tmp_path):
+def test_host_sources_under_asan_ubsan_legal_windows(tmp_path):
+    """The driver's embedded XML cascade keeps every rectangle inside the window, and a copy with one tilted rectangle
+    outside it is refused."""
     exe = str(tmp_path / "host_asan")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
            "-DVJ_BUILDING", os.path.join(ROOT, "tests", "host_asan_driver.cpp")] + \
