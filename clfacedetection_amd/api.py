@@ -88,6 +88,12 @@ class CvParams(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class CvPlanInfo(C.Structure):
+    """vj_cv_plan_info: the LDS-tile scales and the stage-tree queue of an OpenCV-profile plan."""
+    _fields_ = [("tile_windows", C.c_uint64), ("n_tile_scales", C.c_uint32), ("tree_prefix", C.c_uint32),
+                ("tree_queue", C.c_int32), ("tq_shift", C.c_int32), ("tq_split_frames", C.c_int32), ("reserved", C.c_int32)]
+
+
 class _Counters(C.Structure):
     _fields_ = [("windows", C.c_uint64), ("stump_evals", C.c_uint64), ("gather_bytes", C.c_uint64),
                 ("stage_entered", C.c_uint64 * VJ_MAX_STAGES)]
@@ -171,6 +177,7 @@ _SIGNATURES = {
     "vj_detect_opencv": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(CvParams),
                                    C.POINTER(_Result)]),
     "vj_cv_params_default": (None, [C.POINTER(CvParams)]),
+    "vj_cv_plan_info_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CvParams), C.POINTER(CvPlanInfo)]),
     "vj_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params),
                             C.POINTER(_Result)]),
     "vj_result_free": (None, [C.POINTER(_Result)]),
@@ -513,6 +520,15 @@ class Environment:
         lib = load_library()
         _check(lib.vj_detect_opencv(self._h, cascade._h, imgs, n, C.byref(p), C.byref(res)), "vj_detect_opencv")
         return self._result(lib, res, cascade)
+
+    def cv_plan_info(self, cascade: Cascade, width: int, height: int, n_frames: int, min_size=(0, 0),
+                     scale_factor: float = 1.1, min_neighbors: int = 0, flags: int = 0) -> CvPlanInfo:
+        """vj_cv_plan_info_get: the plan detect_opencv uses for a batch of n_frames width x height frames."""
+        p = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
+        info = CvPlanInfo()
+        _check(load_library().vj_cv_plan_info_get(self._h, cascade._h, width, height, n_frames, C.byref(p), C.byref(info)),
+               "vj_cv_plan_info_get")
+        return info
 
     def detect(self, cascade: Cascade, frames, params: Params | None = None, color: bool = False) -> DetectResult:
         """frames: 2-D uint8 array, 3-D (n, h, w) array, list of 2-D arrays, or

@@ -603,6 +603,25 @@ void vj_cv_params_default(vj_cv_params* p) {
     p->scale_factor = 1.1;
 }
 
+int vj_cv_plan_info_get(vj_env* e, const vj_cascade* c, int width, int height, int n_frames, const vj_cv_params* p,
+                        vj_cv_plan_info* out) {
+    if (!e || !c || !p || !out || n_frames <= 0 || width <= 0 || height <= 0 || width >= 65535 || height >= 65535) return VJ_ERR_ARG;
+    if (!(p->scale_factor > 1.0)) return VJ_ERR_ARG;
+    memset(out, 0, sizeof(*out));
+    HIP_TRY(hipSetDevice(e->device));
+    CvPlan* pl;
+    const int rc = get_cv_plan(e, c, width, height, p, n_frames, &pl);
+    if (rc) return rc;
+    out->tile_windows = pl->tile_windows;
+    out->n_tile_scales = pl->n_tile_scales;
+    out->tree_prefix = pl->tree_prefix;
+    if (pl->is_tree && pl->n_tile_scales != 0 && pl->class_first[2] != 0)   // as vj_detect_opencv chooses (uncounted calls)
+        out->tree_queue = pl->chains.n != 0u && pl->n_tile_scales <= 64u && e->cv_tree_queue_cap <= 0 && e->cv_tree_chains ? 1 : 2;
+    out->tq_shift = pl->tq_shift;
+    out->tq_split_frames = pl->tq_split_frames;
+    return VJ_OK;
+}
+
 int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_params* p,
                      vj_result* out) {
     if (!e || !c || !p || !out || n_frames < 0 || (n_frames > 0 && !frames)) return VJ_ERR_ARG;
@@ -644,11 +663,21 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
     const bool count = (p->flags & VJ_FLAG_COUNTERS) != 0;
     const uint64_t frame_bytes = (uint64_t)frame_elems * 4u;
     int max_frames = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_frames, 0xfffffff0ull / frame_bytes));
+    {   // the detection counter is 32-bit: a sub-batch holds fewer than 2^32 windows, so it cannot wrap
+        uint64_t frame_windows = 0;
+        for (const CvScaleDev& sd : scales) frame_windows += (uint64_t)sd.end_x * sd.end_y;
+        if (frame_windows > 0xffffffffull) {
+            set_error("vj_detect_opencv: %llu windows per frame, more than a 32-bit detection count holds",
+                      (unsigned long long)frame_windows);
+            return VJ_ERR_LIMIT;
+        }
+        if (frame_windows) max_frames = (int)std::min<uint64_t>((uint64_t)max_frames, 0xffffffffull / frame_windows);
+    }
     if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
     uint32_t det_cap = 1u << 16;
     std::vector<vj_rect> all;
-    for (int f0 = 0; f0 < n_frames && pl->n_rows != 0; f0 += max_frames) {
-        const int nf = std::min(max_frames, n_frames - f0);
+    for (int f0 = 0, nf = 0; f0 < n_frames && pl->n_rows != 0; f0 += nf) {
+        nf = std::min(max_frames, n_frames - f0);
         if ((rc = ensure_image_buffers(e, W, H, nf, true, CH))) return rc;
         const uint8_t* d_gray;
         size_t gray_frame_bytes;
@@ -663,7 +692,7 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
         if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
         if (has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
         HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
-        bool rows_only = false, done = false;
+        bool rows_only = false, done = false, resplit = false;
         for (int attempt = 0; attempt < 2; ++attempt) {
             if ((rc = d_det.ensure((size_t)det_cap * sizeof(CvDet)))) return rc;
             HIP_TRY(hipMemsetAsync(d_counts.p, 0, counts_bytes, e->stream));
@@ -716,10 +745,24 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                 // (the shift belongs to the PLAN: one survivor-heavy workload does not make every later call allocate more)
                 if (pl->tq_shift < 0) pl->tq_shift = e->cv_tq_shift;
                 const bool chain_pass = pl->chains.n != 0u && pl->n_tile_scales <= 64u && e->cv_tree_queue_cap <= 0 && e->cv_tree_chains;
-                const uint64_t want = chain_pass ? cv_tq_first((uint32_t)std::min<uint64_t>(pl->tile_windows, 0xffffffffull), pl->n_tile_scales, (uint32_t)nf, (uint32_t)pl->tq_shift) + 4096u
-                                                 : ((pl->tile_windows * (uint64_t)nf) >> pl->tq_shift) + 4096u;
-                tq_cap = (uint32_t)std::min<uint64_t>(want, 1ull << 28);
-                if (e->cv_tree_queue_cap > 0) tq_cap = (uint32_t)e->cv_tree_queue_cap;
+                // want(n) = ((tile_windows * n) >> shift) + fixed: the flat queue, or every scale's sub-queue end to end
+                const uint64_t fixed = chain_pass ? (uint64_t)pl->n_tile_scales * 4096u + 4096u : 4096u;
+                const uint64_t want = ((pl->tile_windows * (uint64_t)nf) >> pl->tq_shift) + fixed;
+                if (e->cv_tree_queue_cap <= 0 && want > CV_TQ_MAX) {
+                    // A queue of more than CV_TQ_MAX entries: fewer frames per sub-batch (a clamped queue would drop the entries of
+                    // the later scales' sub-queues, which lie past its end), the rows when not even one frame fits
+                    const uint64_t fit = pl->tile_windows ? (((CV_TQ_MAX - fixed + 1u) << pl->tq_shift) - 1u) / pl->tile_windows : 0u;
+                    if (fit == 0u) {
+                        rows_only = true;
+                        --attempt;
+                        continue;
+                    }
+                    max_frames = (int)std::min<uint64_t>(fit, (uint64_t)max_frames);
+                    pl->tq_split_frames = max_frames;
+                    resplit = true;
+                    break;
+                }
+                tq_cap = e->cv_tree_queue_cap > 0 ? (uint32_t)e->cv_tree_queue_cap : (uint32_t)want;
                 {   // never more than a quarter of what the device has free: beyond that the rows take the call
                     size_t free_b = 0, total_b = 0;
                     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)tq_cap * sizeof(CvTreeEntry) > e->d_cv_tq.cap &&
@@ -955,7 +998,7 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                 continue;
             }
             if (n_det > det_cap) {   // overflow: grow and redo this sub-batch's cascade
-                while (det_cap < n_det) det_cap *= 2;
+                det_cap = grown_cap(det_cap, n_det);
                 continue;
             }
             float ms_i = 0, ms_c = 0, ms_t = 0;
@@ -977,6 +1020,10 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                                       0.0f, f0 + (int32_t)d.frame, (int32_t)scales[d.slot].scale_idx});
             done = true;
             break;
+        }
+        if (resplit) {   // the same frames again, in sub-batches of max_frames
+            nf = 0;
+            continue;
         }
         if (!done) {   // (cannot happen: the counts of a repeated pass are the counts that sized its buffers)
             set_error("vj_detect_opencv: the detection buffer overflowed twice");

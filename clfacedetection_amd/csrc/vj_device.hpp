@@ -347,6 +347,9 @@ struct CvScaleDev {
     uint32_t tq_slot;            // this scale's number among the tile scales
 };
 static_assert(sizeof(CvScaleDev) == 88, "CvScaleDev is 88 bytes");
+// entries of the whole tree queue at most (6 GiB of CvTreeEntry): a sub-batch whose queue would need more is split
+// (vj_detect_opencv), so that every sub-queue lies inside the buffer
+constexpr uint64_t CV_TQ_MAX = 1ull << 28;
 // one sub-queue: 1 / 2^shift of the scale's grid windows in the batch, at least 4096 entries
 __host__ __device__ inline uint64_t cv_tq_cap(uint32_t end_x, uint32_t end_y, uint32_t n_frames, uint32_t shift) {
     return (((uint64_t)end_x * end_y * n_frames) >> shift) + 4096u;
@@ -457,7 +460,8 @@ struct CvTileArgs {
     unsigned long long* stage_entered;   // as CvArgs
     // stage trees (mode 2): the survivors of the tree's linear prefix wait here for cv_tree_walk
     struct CvTreeEntry* tq;
-    uint32_t* tq_count;          // one counter per tile scale (CvScaleDev::tq_slot), + [64]: entries that did not fit
+    uint32_t* tq_count;          // one counter per tile scale (CvScaleDev::tq_slot; [0] alone for the flat queue); [64] is the
+                                 // ticket of cv_tree_chain_pass (CvTreeArgs::ticket), not a count of this kernel
     uint32_t tq_cap;             // total entries of the queue buffer (all sub-queues)
     uint32_t tq_shift;
 };

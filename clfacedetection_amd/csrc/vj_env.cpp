@@ -1496,8 +1496,7 @@ static int finish_batch(vj_env* e, Lane* L, Plan* pl, int f0, int W, int H, cons
         HIP_TRY(hipEventElapsedTime(&ms_c, L->ev[2], L->ev[3]));
         HIP_TRY(hipEventElapsedTime(&ms_t, L->ev[0], L->ev[3]));
         if (n_det > L->det_cap) {  // detections overflowed: grow and redo the cascade passes
-            uint32_t want = L->det_cap;
-            while (want < n_det) want *= 2;
+            const uint32_t want = grown_cap(L->det_cap, n_det);
             if ((rc = L->d_det.ensure((size_t)want * sizeof(DetEntry)))) return rc;
             L->det_cap = want;
             if (L->shared_integrals) {
@@ -1860,9 +1859,9 @@ static int detect_rois_on_device(vj_env* e, const vj_cascade* c, const vj_image*
             }
             const uint32_t n_tiles2 = hc[CountsLayout::roi_off_u32 + 6];
             if (n_units > e->roi_unit_cap || n_det2 > e->roi_det_cap || n_tiles2 > e->roi_tile_cap) {
-                while (e->roi_unit_cap < n_units) e->roi_unit_cap *= 2;
-                while (e->roi_det_cap < n_det2) e->roi_det_cap *= 2;
-                while (e->roi_tile_cap < n_tiles2) e->roi_tile_cap *= 2;
+                e->roi_unit_cap = grown_cap(e->roi_unit_cap, n_units);
+                e->roi_det_cap = grown_cap(e->roi_det_cap, n_det2);
+                e->roi_tile_cap = grown_cap(e->roi_tile_cap, n_tiles2);
                 continue;
             }
             HIP_TRY(hipEventElapsedTime(&ms_roi, L->launch_ev[2 * VJ_MAX_LAUNCHES - 2], L->launch_ev[2 * VJ_MAX_LAUNCHES - 1]));
@@ -2709,8 +2708,7 @@ int vj_detect_chain(vj_env* e, const vj_cascade* first, const vj_cascade* second
                 return VJ_ERR_HIP;
             }
             if (n_det1 > L->det_cap) {   // as finish_batch would: grow, and run both cascades again
-                uint32_t want = L->det_cap;
-                while (want < n_det1) want *= 2;
+                const uint32_t want = grown_cap(L->det_cap, n_det1);
                 if ((rc = L->d_det.ensure((size_t)want * sizeof(DetEntry)))) return rc;
                 L->det_cap = want;
                 continue;
@@ -2730,9 +2728,9 @@ int vj_detect_chain(vj_env* e, const vj_cascade* first, const vj_cascade* second
             }
             const uint32_t n_tiles2 = hc[CountsLayout::roi_off_u32 + 6];
             if (n_units > e->roi_unit_cap || n_det2 > e->roi_det_cap || n_tiles2 > e->roi_tile_cap) {
-                while (e->roi_unit_cap < n_units) e->roi_unit_cap *= 2;
-                while (e->roi_det_cap < n_det2) e->roi_det_cap *= 2;
-                while (e->roi_tile_cap < n_tiles2) e->roi_tile_cap *= 2;
+                e->roi_unit_cap = grown_cap(e->roi_unit_cap, n_units);
+                e->roi_det_cap = grown_cap(e->roi_det_cap, n_det2);
+                e->roi_tile_cap = grown_cap(e->roi_tile_cap, n_tiles2);
                 continue;
             }
             HIP_TRY(hipEventElapsedTime(&ms_roi, L->launch_ev[2 * VJ_MAX_LAUNCHES - 2], L->launch_ev[2 * VJ_MAX_LAUNCHES - 1]));

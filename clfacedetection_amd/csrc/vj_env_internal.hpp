@@ -50,6 +50,16 @@ struct DevBuf {
     }
 };
 
+// The capacity a 32-bit device counter's buffer grows to when `need` entries did not fit in `cap`: doubled in 64 bits (a
+// 32-bit doubling wraps to 0 past 2^31 and never reaches `need`), at most 2^32 - 1 — the counters are 32-bit, so `need`
+// itself never exceeds that.  The allocation that follows fails with VJ_ERR_NOMEM rather than loop when it cannot hold it.
+inline uint32_t grown_cap(uint32_t cap, uint64_t need) {
+    if (need <= cap) return cap;   // (a capacity of 0 that nothing asked for stays 0: it may mean "path unused")
+    uint64_t c = std::max<uint64_t>(cap, 1u);
+    while (c < need) c *= 2;
+    return (uint32_t)std::min<uint64_t>(c, 0xffffffffull);
+}
+
 // Everything that depends on (cascade, W, H, params) but not on pixel data.
 struct Plan {
     std::vector<vj_scale_info> scales_all;   // every enumerated scale
@@ -115,6 +125,7 @@ struct CvPlan {
     int tq_shift = -1;                // stage trees on tiles: the prefix survivors' sub-queues hold 1 / 2^shift of the tile windows
                                       // (-1: the environment's start value; lowered for THIS plan when a sub-queue overflows)
     uint64_t tile_windows = 0;        // grid windows of the tile scales, per frame
+    int tq_split_frames = 0;          // frames per sub-batch the tree queue last split a batch to (CV_TQ_MAX; 0: never)
     uint32_t class_first[3] = {0, 0, 0}, class_lds[2] = {0, 0};
     DevBuf d_tiles, d_rows_rest, d_bit_segs;
     uint64_t last_used = 0;

@@ -338,6 +338,22 @@ typedef struct vj_cv_params {
 void vj_cv_params_default(vj_cv_params* p);
 int  vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
                       const vj_cv_params* p, vj_result* out);
+/* What vj_detect_opencv's plan for (c, width x height, p, a batch of n_frames) holds, with the environment's
+ * current settings: the LDS-tile scales and, for stage trees on tiles, the survivors' tree queue.  The
+ * queue's shift and split belong to the plan: they record what earlier calls with that plan did.        */
+typedef struct vj_cv_plan_info {
+    uint64_t tile_windows;     /* grid windows per frame of the scales on LDS tiles                      */
+    uint32_t n_tile_scales;
+    uint32_t tree_prefix;      /* stage trees: leading stages the tiles run (0: linear cascade)          */
+    int32_t  tree_queue;       /* stage trees on tiles: 1 one sub-queue per scale (chain pass), 2 one
+                                  flat queue (tree walk); 0 the rows take the tree                        */
+    int32_t  tq_shift;         /* the queue holds 1 / 2^shift of the tile windows (-1: no call yet)      */
+    int32_t  tq_split_frames;  /* frames per sub-batch a call last split its batch to so that the queue
+                                  fits in 2^28 entries (0: no call had to)                               */
+    int32_t  reserved;
+} vj_cv_plan_info;
+int  vj_cv_plan_info_get(vj_env* e, const vj_cascade* c, int width, int height, int n_frames,
+                         const vj_cv_params* p, vj_cv_plan_info* out);
 
 /* A second cascade on regions of interest (BASELINE config 5: haarcascade_eye inside every face;
  * the reference's caller would hand clodDetectObjects a sub-image header: pointer + widthStep).

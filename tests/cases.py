@@ -397,3 +397,114 @@ def overhangs(c, scales) -> dict:
                 if y + h == ey + 1:
                     out["y"].append((si.scale_idx, n, q))
     return out
+
+
+# ----------------------------------------------------------------------------- survivor-heavy cascades
+SURVIVOR_SPOTS = ((8, 8, 4, 4), (4, 12, 4, 4))   # (x, y, w, h) in the 20 x 20 window: the selective stages look here
+SURVIVOR_SPOT_THRESHOLD = 0.05                    # node threshold of a selective node (times the variance norm factor)
+SURVIVOR_FORMS = ("stumps", "trees", "chain_tree", "branch_tree", "accept_all")
+
+
+def _spot_node(spot: int, thr: float):
+    """(rects, weights, threshold) of a node that compares the mean under SURVIVOR_SPOTS[spot] with the window's: rect 0 is
+    the whole window (the evaluators set its weight from rect 1's area), rect 1 the spot."""
+    return [(0, 0, 20, 20), SURVIVOR_SPOTS[spot], (0, 0, 0, 0)], [-1.0, 1.0, 0.0], thr
+
+
+def survivor_cascade(form: str = "stumps", n_pass: int = 2):
+    """oracle CascadeArrays of a 20 x 20 cascade whose first n_pass stages accept every window (leaves 0 / 1, stage
+    threshold -1: far below any sum they reach in either profile), followed by stages that pass a window only when a bright
+    pixel lies under a small spot of it (a node threshold that dot_frame()'s dark noise never reaches).  On dot_frame()
+    content every window reaches the selective stages; detections follow the dots.
+
+    form: "stumps" (one selective stump stage), "trees" (every stage one two-node tree: the root tests spot 0, its left
+    branch spot 1), "chain_tree" (stumps re-linked by as_stage_tree after the prefix: two chains, made of chains),
+    "branch_tree" (stumps, a stage tree whose part after the prefix is NOT made of chains: one stage's rejects go to its
+    sibling, its parent's to another), "accept_all" (every stage, the last one too, accepts every window)."""
+    from oracle.oracle import CascadeArrays
+    assert form in SURVIVOR_FORMS and n_pass >= 1
+    # stages: [trees], a tree: [(rects, weights, threshold, left, right)] with left / right as in the node arrays
+    # (> 0: node index inside the tree, <= 0: -alpha index inside the tree), alphas per tree
+    def stump(spot, thr, lo=0.0, hi=1.0):
+        rr, ww, t = _spot_node(spot, thr)
+        return [(rr, ww, t, 0, -1)], [lo, hi]
+    pass_stage = ([stump(0, 0.0)], -1.0)
+    if form == "trees":
+        r0, w0, t0 = _spot_node(0, SURVIVOR_SPOT_THRESHOLD)
+        r1, w1, t1 = _spot_node(1, SURVIVOR_SPOT_THRESHOLD)
+        pass_tree = ([(r0, w0, 0.0, 1, 0), (r1, w1, 0.0, -1, -2)], [0.5, 0.0, 1.0])
+        sel_tree = ([(r0, w0, t0, 1, 0), (r1, w1, t1, -1, -2)], [1.0, 0.0, 1.0])   # spot 0 bright: 1; else spot 1 decides
+        stages = [([pass_tree], -1.0)] * n_pass + [([sel_tree], 0.5)]
+    elif form == "accept_all":
+        stages = [pass_stage] * (n_pass + 1)
+    else:
+        sel = [([stump(0, SURVIVOR_SPOT_THRESHOLD)], 0.5), ([stump(1, SURVIVOR_SPOT_THRESHOLD)], 0.5)]
+        if form == "stumps":
+            stages = [pass_stage] * n_pass + [sel[0]]
+        elif form == "chain_tree":           # chains {P, P+2} and {P+1, P+3}: spot 0 then all-pass, or spot 1 then all-pass
+            stages = [pass_stage] * n_pass + [sel[0], sel[1], pass_stage, pass_stage]
+        else:                                # X = P (spot 0), its children Y1 = P+1 (spot 1), Y2 = P+2 (all-pass); X.next = Z = P+3 (spot 1)
+            stages = [pass_stage] * n_pass + [sel[0], sel[1], pass_stage, sel[1]]
+    c = CascadeArrays()
+    c.win_w = c.win_h = 20
+    c.name = f"survivor_{form}_{n_pass}"
+    st_first, st_n, st_thr, tr_first, tr_n, tr_alpha = [], [], [], [], [], []
+    rects, weights, thr, left, right, alpha = [], [], [], [], [], []
+    for trees, sthr in stages:
+        st_first.append(len(tr_first))
+        st_n.append(len(trees))
+        st_thr.append(sthr)
+        for nodes, al in trees:
+            tr_first.append(len(thr))
+            tr_n.append(len(nodes))
+            tr_alpha.append(len(alpha))
+            for rr, ww, t, lf, rt in nodes:
+                rects += [list(r) for r in rr]
+                weights += ww
+                thr.append(t)
+                left.append(lf)
+                right.append(rt)
+            alpha += al
+    n = len(stages)
+    c.stage_first_tree = np.array(st_first, np.int32)
+    c.stage_n_trees = np.array(st_n, np.int32)
+    c.stage_threshold = np.array(st_thr, np.float32)
+    c.stage_parent = np.arange(-1, n - 1, dtype=np.int32)
+    c.stage_next = np.full(n, -1, np.int32)
+    c.stage_child = np.array(list(range(1, n)) + [-1], np.int32)
+    c.tree_first_node = np.array(tr_first, np.int32)
+    c.tree_n_nodes = np.array(tr_n, np.int32)
+    c.tree_first_alpha = np.array(tr_alpha, np.int32)
+    c.node_rect = np.array(rects, np.int32).reshape(-1)
+    c.node_weight = np.array(weights, np.float32)
+    c.node_threshold = np.array(thr, np.float32)
+    c.node_left = np.array(left, np.int32)
+    c.node_right = np.array(right, np.int32)
+    c.node_tilted = np.zeros(len(thr), np.int32)
+    c.alpha = np.array(alpha, np.float32)
+    if form == "chain_tree":
+        c = as_stage_tree(c, split_at=n_pass - 1)
+    elif form == "branch_tree":
+        p = n_pass
+        parent = np.arange(-1, n - 1, dtype=np.int32)
+        parent[p + 1] = parent[p + 2] = p
+        parent[p + 3] = p - 1
+        nxt = np.full(n, -1, np.int32)
+        nxt[p], nxt[p + 1] = p + 3, p + 2
+        child = np.full(n, -1, np.int32)
+        for i in range(n):
+            if parent[i] != -1 and child[parent[i]] == -1:
+                child[parent[i]] = i
+        c.stage_parent, c.stage_next, c.stage_child = parent, nxt, child
+    return c
+
+
+def dot_frame(seed: int, h: int, w: int, n_dots: int, dot: int = 4) -> np.ndarray:
+    """A dark frame (16 + uniform noise of 0..16: the variance norm factor stays well above 0) with n_dots bright (255)
+    squares of dot x dot pixels at seeded positions.  survivor_cascade()'s selective stages pass only windows with a dot under
+    their spot, so the detections follow the dots and the small scales, not the number of windows."""
+    rng = np.random.default_rng(seed)
+    img = (16 + rng.integers(0, 17, (h, w))).astype(np.uint8)
+    for y, x in zip(rng.integers(0, h - dot, n_dots), rng.integers(0, w - dot, n_dots)):
+        img[y:y + dot, x:x + dot] = 255
+    return img

@@ -1,0 +1,248 @@
+"""Survivor-heavy content at default settings, against the C oracle frame by frame.  The shipped cascades on synthetic
+frames let a few percent of the windows past stage 0; every device buffer is sized for that.  survivor_cascade() lets EVERY
+window through a prefix of stages and dot_frame() keeps the detections few, so the capacities are reached the natural way:
+the detection buffer's growth past det_cap_init (65536), the OpenCV profile's stage-tree queue escalating tq_shift 4 -> 2
+-> 0 and, at shift 0, a batch whose queue would exceed CV_TQ_MAX (2^28) entries, and vj_detect_chain's device grouping at
+GROUP_MAX (2048) candidates per frame.  Large batches repeat a few distinct frames; the oracle runs once per distinct frame."""
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+from cases import cascade_to_product, dot_frame, survivor_cascade, tunables
+from clfacedetection_amd import VJ_FLAG_COUNTERS, Environment, default_params
+
+pytestmark = pytest.mark.gpu
+
+CAP = 1 << 21                        # oracle detection buffer (default 1 << 20): accept-all frames hold every window
+N_DISTINCT = 4
+_CASC, _FRAMES, _ORACLE = {}, {}, {}
+
+
+def casc(form):
+    if form not in _CASC:
+        a = survivor_cascade(form)
+        _CASC[form] = (cascade_to_product(a), a)
+    return _CASC[form]
+
+
+def distinct_frames(h, w):
+    if (h, w) not in _FRAMES:
+        _FRAMES[(h, w)] = [dot_frame(7000 + i, h, w, n_dots=(h * w) // 4000) for i in range(N_DISTINCT)]
+    return _FRAMES[(h, w)]
+
+
+def batch(h, w, n):
+    d = distinct_frames(h, w)
+    return [d[i % N_DISTINCT] for i in range(n)]
+
+
+def oracle_of(oracle, form, h, w, profile):
+    """[(rects, stats)] of the oracle for each distinct frame (the C entry point releases the GIL)."""
+    key = (form, h, w, profile)
+    if key not in _ORACLE:
+        _, a = casc(form)
+        fn = oracle.detect if profile == "clod" else oracle.detect_opencvlike
+        with ThreadPoolExecutor(N_DISTINCT) as ex:
+            _ORACLE[key] = list(ex.map(lambda f: fn(a, f, cap=CAP), distinct_frames(h, w)))
+    return _ORACLE[key]
+
+
+def rows_of(rects):
+    return sorted(tuple(int(r[k]) for k in ("scale_idx", "x", "y", "w", "h")) for r in rects)
+
+
+def check(r, want, n, label, counted):
+    """r: a result of n frames of batch(); want: the oracle per distinct frame."""
+    frame = r.rects["frame"]
+    order = np.argsort(frame, kind="stable")
+    bounds = np.searchsorted(frame[order], np.arange(n + 1))
+    got_rows = {}
+    for i in range(n):
+        mine = rows_of(r.rects[order[bounds[i]:bounds[i + 1]]])
+        ro = want[i % N_DISTINCT][0]
+        key = i % N_DISTINCT
+        if key not in got_rows:
+            got_rows[key] = rows_of(ro)
+        assert mine == got_rows[key], f"{label}: frame {i}: {len(mine)} rectangles, the oracle {len(ro)}"
+    if counted:
+        entered = [sum(want[i % N_DISTINCT][1]["stage_entered"][s] for i in range(n)) for s in range(len(r.stage_entered))]
+        windows = sum(want[i % N_DISTINCT][1]["windows"] for i in range(n))
+        assert r.stage_entered == entered, f"{label}: stage_entered {r.stage_entered}, the oracle {entered}"
+        assert r.windows == windows, f"{label}: {r.windows} windows, the oracle {windows}"
+
+
+# ----------------------------------------------------------------------------- a. clod profile
+CLOD_SETTINGS = [
+    ("defaults", ()),
+    ("tile_end2", (("tile_end", 2),)),
+    ("lanes64", (("tile_min_lanes", 64),)),
+    ("band0", (("q_band_px", 0),)),
+    ("split99", (("tile_split", "99"),)),
+]
+CLOD_CELLS = [(form, size, n) for form in ("stumps", "trees") for size in ((480, 640), (479, 641)) for n in (1, 7, 8, 11, 64)
+              if not (size == (479, 641) and n == 64)]
+
+
+@pytest.mark.parametrize("sid,settings", CLOD_SETTINGS, ids=[s[0] for s in CLOD_SETTINGS])
+def test_clod_all_pass_prefix(env, oracle, sid, settings):
+    """Every window passes the prefix: the tiles' hand-offs and the queues carry every window of the batch."""
+    for form, (h, w), n in CLOD_CELLS:
+        c, _ = casc(form)
+        want = oracle_of(oracle, form, h, w, "clod")
+        frames = batch(h, w, n)
+        label = f"{form} {h}x{w} n={n} {sid}"
+        with tunables(env, *settings):
+            check(env.detect(c, frames, default_params(flags=VJ_FLAG_COUNTERS)), want, n, label + " counted", True)
+            check(env.detect(c, frames), want, n, label + " timed", False)
+
+
+def test_clod_all_pass_prefix_1080p_batch(env, oracle):
+    h, w, n = 1080, 1920, 64
+    for form in ("stumps", "trees"):
+        c, _ = casc(form)
+        want = oracle_of(oracle, form, h, w, "clod")
+        env.configure("defaults", "")
+        check(env.detect(c, batch(h, w, n)), want, n, f"{form} 64 x 1080p timed", False)
+        check(env.detect(c, batch(h, w, n), default_params(flags=VJ_FLAG_COUNTERS)), want, n, f"{form} 64 x 1080p counted", True)
+
+
+def test_detection_buffer_grows_past_its_initial_capacity(oracle):
+    """Every window is a detection: one 480 x 640 frame has more than det_cap_init (65536), and the buffer grows on its own.
+    A fresh environment, so that every buffer (the region pass's too) starts at its initial capacity whatever ran before."""
+    env = Environment(0)
+    try:
+        assert int(env.query("det_cap")) == 65536
+        c, _ = casc("accept_all")
+        h, w = 480, 640
+        want = oracle_of(oracle, "accept_all", h, w, "clod")
+        assert len(want[0][0]) > 65536
+        for n in (1, 3):
+            check(env.detect(c, batch(h, w, n)), want, n, f"accept_all n={n} timed", False)
+            check(env.detect(c, batch(h, w, n), default_params(flags=VJ_FLAG_COUNTERS)), want, n, f"accept_all n={n} counted", True)
+        s = env.stream(c, w, h, 3)
+        try:
+            for _ in range(2):
+                s.submit(batch(h, w, 3))
+                check(s.collect(), want, 3, "accept_all vj_stream", False)
+        finally:
+            s.close()
+        # one region per distinct frame, the whole frame: the region pass's detection buffer (first sized 65536) grows too
+        rois = [(i, 0, 0, w, h) for i in range(N_DISTINCT)]
+        check(env.detect_rois(c, distinct_frames(h, w), rois), want, N_DISTINCT, "accept_all vj_detect_rois", False)
+    finally:
+        env.close()
+
+
+# ----------------------------------------------------------------------------- b. OpenCV profile, stage trees on tiles
+CV_ROUTES = [("defaults", ()), ("cv_tiles0", (("cv_tiles", 0),)), ("cv_tree_chains0", (("cv_tree_chains", 0),))]
+
+
+@pytest.mark.parametrize("form", ("chain_tree", "branch_tree"))
+def test_opencv_tree_queue_escalates(env, oracle, form):
+    """Every tile window survives the tree's prefix: the queue of 1/16 of them overflows, tq_shift escalates to 0 on its own
+    (the plan records it: vj_cv_plan_info_get), and the result equals the oracle, the rows (cv_tiles 0) and the flat queue
+    (cv_tree_chains 0).  chain_tree's tree is made of chains (one sub-queue per scale), branch_tree's is not (one flat queue)."""
+    c, _ = casc(form)
+    h, w = 480, 640
+    want = oracle_of(oracle, form, h, w, "cv")
+    queue = {"defaults": 1 if form == "chain_tree" else 2, "cv_tiles0": 0, "cv_tree_chains0": 2}
+    for n in (1, 8, 11):
+        frames = batch(h, w, n)
+        for rid, settings in CV_ROUTES:
+            with tunables(env, *settings):
+                info = env.cv_plan_info(c, w, h, n)
+                assert info.tree_queue == queue[rid], f"{form} n={n} {rid}: tree queue {info.tree_queue}"
+                check(env.detect_opencv(c, frames), want, n, f"{form} n={n} {rid}", False)
+                info = env.cv_plan_info(c, w, h, n)
+                if queue[rid]:
+                    assert info.tq_shift == 0, f"{form} n={n} {rid}: tq_shift {info.tq_shift}, not escalated to 0"
+                    assert info.tq_split_frames == 0, f"{form} n={n} {rid}: a small batch was split"
+        counted = env.detect_opencv(c, frames, flags=VJ_FLAG_COUNTERS)   # counted stage-tree calls take the rows
+        check(counted, want, n, f"{form} n={n} counted", True)
+
+
+@pytest.mark.parametrize("form,settings,queue", [("chain_tree", (), 1), ("chain_tree", (("cv_tree_chains", 0),), 2), ("branch_tree", (), 2)],
+                         ids=["chain_pass", "flat_queue_chains0", "flat_queue_branch"])
+def test_opencv_tree_queue_beyond_its_clamp(env, oracle, form, settings, queue):
+    """96 x 1080p: every tile window passes the prefix, so the queue escalates to tq_shift 0 and would need
+    tile_windows x 96 entries (about 5.85M x 96), more than CV_TQ_MAX (2^28).  The call must split the batch and keep the
+    tiles.  Before the split existed, the per-scale sub-queues of the later scales lay past the clamped queue and their
+    windows went missing (cv_tree_chain_pass); the flat queue (cv_tree_walk) overflowed and fell back to the rows with the
+    right result, which is why the plan's record of the split is checked as well as the rectangles."""
+    c, _ = casc(form)
+    h, w, n = 1080, 1920, 96
+    want = oracle_of(oracle, form, h, w, "cv")
+    with tunables(env, *settings):
+        info = env.cv_plan_info(c, w, h, n)
+        assert info.tree_queue == queue and info.tq_split_frames == 0
+        fixed = 4096 * (info.n_tile_scales + 1) if queue == 1 else 4096
+        assert info.tile_windows * n > (1 << 28), \
+            f"the precondition does not hold: {info.tile_windows} tile windows per frame x {n} frames"
+        check(env.detect_opencv(c, batch(h, w, n)), want, n, f"{form} {n} x 1080p {settings}", False)
+        info = env.cv_plan_info(c, w, h, n)
+        assert info.tq_shift == 0, f"tq_shift {info.tq_shift}"
+        assert 0 < info.tq_split_frames < n, f"the batch was not split: {info.tq_split_frames}"
+        assert info.tile_windows * info.tq_split_frames + fixed <= (1 << 28)
+
+
+# ----------------------------------------------------------------------------- c. device grouping at GROUP_MAX
+def sized_for(c, nx, ny, k):
+    """(W, H) whose scale k has a grid of exactly nx x ny windows, from the product's plan (vj_plan_scales)."""
+    p = default_params(scales=[k])
+
+    def grid(W, H):
+        s = [x for x in c.plan_scales(W, H, p) if x.scale_idx == k and x.accepted]
+        return (s[0].nx, s[0].ny) if s else (0, 0)
+    W = next(W for W in range(c.info.win_w, 4000) if grid(W, 4000)[0] == nx)
+    H = next(H for H in range(c.info.win_h, 4000) if grid(4000, H)[1] == ny)
+    assert grid(W, H) == (nx, ny), (W, H, grid(W, H))
+    return W, H
+
+
+# (scale, nx, ny): 0, 1, 2047 and 2048 candidates per frame, GROUP_MAX = 2048, on the device; 2049 and 2050 on the host.
+# Scale 0's grid is at least 6 x 6: the 1 x 1 grid is scale 20's (145 x 145), 3 x 683 scale 12's (73 x 2205).
+GROUP_GRIDS = ((None, 0, 0), (20, 1, 1), (0, 23, 89), (0, 32, 64), (12, 3, 683), (0, 25, 82))
+
+
+@pytest.mark.parametrize("mn", (1, 3))
+def test_chain_grouping_at_group_max(env, oracle, cascades, mn):
+    """The accept-all cascade on one scale: every window is a raw candidate, in a dense grid of equal rectangles (long
+    chains for the label propagation, a full bitonic sort at 2048).  Each count is a batch of two frames of one size; all
+    results equal the oracle's grouping, vj_detect + vj_detect_rois, and the group_max 50 route (every count but 0 and 1
+    grouped on the host).  Which route a call took is not visible in its result: a count the device kernel did not hold
+    would show as a wrong grouping, not as a different route."""
+    c, a = casc("accept_all")
+    eye, _ = cascades("eye")
+    p2 = default_params(flags=VJ_FLAG_COUNTERS)
+    key = lambda rr: [tuple(int(r[f]) for f in ("frame", "scale_idx", "y", "x", "w", "h")) for r in rr]
+    for k, nx, ny in GROUP_GRIDS:
+        n_cand = nx * ny
+        scales = [] if k is None else [k]                        # no scale: no candidate
+        W, H = (64, 64) if k is None else sized_for(c, nx, ny, k)
+        frames = [dot_frame(s, H, W, 4) for s in (1, 2)]
+        p1 = default_params(min_neighbors=mn, scales=scales)
+        label = f"{n_cand} candidates (scale {k}, {W}x{H}) min_neighbors={mn}"
+        raw = env.detect(c, frames, default_params(scales=scales))
+        assert all((raw.rects["frame"] == i).sum() == n_cand for i in range(len(frames))), label
+        r1, r2 = env.detect_chain(c, eye, frames, p1, p2)
+        want = []
+        for f in range(len(frames)):
+            ro, _ = oracle.detect(a, frames[f], cap=CAP)
+            ro = ro[ro["scale_idx"] == k] if n_cand else ro[:0]
+            assert len(ro) == n_cand, label
+            xywh = np.stack([ro[q] for q in ("x", "y", "w", "h")], 1) if len(ro) else np.zeros((0, 4), np.int32)
+            g, wgt = oracle.group_rectangles(xywh, max(mn, 1))
+            want += [(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(m), f) for r, m in zip(g, wgt)]
+        got = [(int(r["x"]), int(r["y"]), int(r["w"]), int(r["h"]), int(r["weight"]), int(r["frame"])) for r in r1.rects]
+        assert got == want, f"{label}: grouped {got[:4]}..., the oracle {want[:4]}..."
+        rois = [(int(r["frame"]), int(r["x"]), int(r["y"]), int(r["w"]), int(r["h"])) for r in r1.rects]
+        if rois:
+            host = env.detect_rois(eye, frames, rois, p2)
+            assert key(r2.rects) == key(host.rects), f"{label}: second cascade differs from vj_detect_rois"
+            assert r2.stage_entered == host.stage_entered, label
+        else:
+            assert len(r2.rects) == 0, label
+        with tunables(env, ("group_max", 50)):
+            g1, g2 = env.detect_chain(c, eye, frames, p1, p2)
+        assert np.array_equal(g1.rects, r1.rects) and key(g2.rects) == key(r2.rects), f"{label}: group_max 50 route differs"
