@@ -254,7 +254,9 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
                         best_cls = cls; best_n = nwt; b_tw = tw; b_th = th; b_pitch = pitch; b_rows = rows;
                     }
             }
-            if (best_n >= (uint32_t)thresholds.accept_windows) {
+            // (best_n == 0: no shape fits any class — with tile_accept_windows 0 that scale once became a tile scale of a 0 x 0 tile,
+            // and tiles_x below divided by zero)
+            if (best_n != 0u && best_n >= (uint32_t)thresholds.accept_windows) {
                 sd.tile_rw = 1;
                 sd.tile_tw = b_tw;
                 sd.tile_th = b_th;

@@ -186,7 +186,8 @@ void vj_env_destroy(vj_env* e);
  * pre-size device buffers; optional — vj_detect grows them on demand.          */
 int  vj_env_reserve(vj_env* e, int max_w, int max_h, int max_batch);
 int  vj_env_device_name(const vj_env* e, char* buf, size_t cap);
-/* Tunables — speed only: results never depend on them (tests sweep every group).  One line per group here; every key
+/* Tunables — speed only: results never depend on them (tests/test_gpu_tunable_parity.py runs every key at values other than
+ * its default against the oracle, and fails when a key has no row in its table).  One line per group here; every key
  * with its values, default and the measurement behind the default is in DESIGN.md §7.  Lists are comma-separated.
  *   launch structure   pass_split, pass_cut_nodes, blocks_per_cu, concurrent, concurrent_blocks_per_cu, max_subbatch, det_cap
  *   LDS tiles          tile_classes_kb, tile_lds_reserve_kb, tile_min_windows, tile_accept_windows, tile_end, tile_min_lanes,

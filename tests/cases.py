@@ -508,3 +508,146 @@ def dot_frame(seed: int, h: int, w: int, n_dots: int, dot: int = 4) -> np.ndarra
     for y, x in zip(rng.integers(0, h - dot, n_dots), rng.integers(0, w - dot, n_dots)):
         img[y:y + dot, x:x + dot] = 255
     return img
+
+
+# ----------------------------------------------------------------------------- a call against the oracle, frame by frame
+def rows_of(rects):
+    return [tuple(int(r[k]) for k in ("scale_idx", "x", "y", "w", "h")) for r in rects]
+
+
+def first_difference(got, want):
+    s = next(s for s, (x, y) in enumerate(zip(got, want)) if x != y)
+    return f"stage {s}: {got[s]} entered, the oracle {want[s]}"
+
+
+def check_against_oracle(env, c, frames, want, label):
+    """One counted and one timed detect of `frames` against the oracle's per-frame results `want`; returns the counted
+    result and the oracle's per-stage totals."""
+    from clfacedetection_amd import VJ_FLAG_COUNTERS, default_params
+    r = env.detect(c, frames, default_params(flags=VJ_FLAG_COUNTERS))
+    n_st = c.info.n_stages
+    entered, windows = [0] * n_st, 0
+    for i, (ro, st) in enumerate(want):
+        mine = rows_of(r.rects[r.rects["frame"] == i])
+        assert mine == rows_of(ro), f"{label}: frame {i}: {len(mine)} rectangles, the oracle {len(ro)}"
+        entered = [x + y for x, y in zip(entered, st["stage_entered"])]
+        windows += st["windows"]
+    assert r.stage_entered == entered, f"{label}: {first_difference(r.stage_entered, entered)}"
+    assert r.windows == windows, f"{label}: {r.windows} windows, the oracle {windows}"
+    per_launch = [sum(l["stage_entered"][s] for l in r.launches) for s in range(n_st)]
+    assert per_launch == r.stage_entered, f"{label}: per-launch counters do not add up ({first_difference(per_launch, r.stage_entered)})"
+    r2 = env.detect(c, frames)
+    assert np.array_equal(r2.rects, r.rects), f"{label}: the timed kernels' rectangles differ from the counted ones"
+    return r, entered
+
+
+# ----------------------------------------------------------------------------- every configure key against the oracle
+# tests/test_gpu_tunable_parity.py runs the table below cell by cell; tests/soak_gpu.py draws its settings from it.
+TUNABLE_KINDS = ("noise", "faces", "blocks")      # every batch is a prefix of one set of DISTINCT frames of these kinds
+# name -> (api, cascades, sizes (h, w), batch prefixes, first seed).  api: "clod" vj_detect, "cv" vj_detect_opencv,
+# "chain" vj_detect_chain (the cascade's faces grouped with min_neighbors 3, haarcascade_eye inside each) + vj_detect_rois
+TUNABLE_WORKLOADS = {
+    # >= 800000 px, the second size a multiple of nothing: what one_pass_max_frames applies to
+    "lin_few": ("clod", ("frontalface_alt",), ((720, 1280), (750, 1100)), (1, 3), 6000),
+    # stumps and two-node trees; 8 and 11 frames take the band-major queue pass, 11 does not divide by the eight queue parts
+    "lin_batch": ("clod", ("frontalface_alt", "frontalface_alt2"), ((479, 641),), (1, 8, 11), 6100),
+    # the one shipped stage tree: prefix 0..4, then two chains of about twenty stages each
+    "tree": ("clod", ("frontalface_alt_tree",), ((480, 640),), (1, 3, 9), 6200),
+    "cv_tree": ("cv", ("frontalface_alt_tree",), ((480, 640),), (1, 5), 6300),   # (tree_queue == 1 at the defaults: asserted)
+    "cv_lin": ("cv", ("frontalface_alt",), ((480, 640),), (1, 5), 6400),
+    "cv_lin2": ("cv", ("frontalface_alt2",), ((300, 420),), (1, 5), 6500),       # two-node trees (cv_tree2)
+    "cv_tilted": ("cv", ("fullbody",), ((300, 420),), (1, 5), 6600),             # tilted features (cv_tiles_tilted)
+    "regions": ("chain", ("frontalface_alt2",), ((360, 640),), (2, 4), 6700),    # (frame 1 is the first drawn-faces frame)
+}
+
+
+class Sweep:
+    """Values of one key (all different from its default, in configure's syntax), the workloads that reach the code the key
+    steers, and settings applied before it when the key only acts next to them."""
+    def __init__(self, values, *workloads, also=()):
+        self.values, self.workloads, self.also = tuple(values), tuple(workloads), tuple(also)
+
+
+TUNABLE_SWEEPS = {
+    # ---- launch structure
+    "pass_split": [Sweep(("3", "3,9", "2,5,12"), "lin_batch")],
+    # asserted: r.passes are the rule's (cumulative nodes) for the value and differ from the default's
+    "pass_cut_nodes": [Sweep(("150", "7", "35,150", "-1"), "lin_batch")],
+    "blocks_per_cu": [Sweep(("1", "3"), "lin_batch", "tree")],
+    "concurrent": [Sweep(("0",), "lin_batch", "tree", "cv_lin", "cv_tree")],
+    # asserted: a tile, a grid and a queue launch exist and the queue launch entered windows (the grid's size is not reported)
+    "concurrent_blocks_per_cu": [Sweep(("2", "8"), "lin_batch")],
+    "max_subbatch": [Sweep(("2", "3"), "lin_batch", "cv_lin")],
+    "det_cap": [Sweep(("1", "7"), "lin_batch", "tree", "regions")],                 # the regrow path
+    # ---- LDS tiles
+    "tile_classes_kb": [Sweep(("0,0,0", "24,40,60"), "lin_batch", "tree")],
+    "tile_lds_reserve_kb": [Sweep(("0", "48"), "lin_batch")],
+    "tile_min_windows": [Sweep(("64", "2048"), "lin_batch")],
+    # asserted: the scales of the tile launches differ from the default's
+    "tile_accept_windows": [Sweep(("0", "65536"), "lin_batch")],
+    "tile_max_dwords_per_window": [Sweep(("100", "8000"), "lin_batch")],
+    "tile_end": [Sweep(("2", "3", "5"), "lin_batch")],
+    "tile_min_lanes": [Sweep(("64", "512"), "lin_batch")],
+    "tile_repack": [Sweep(("3,5", ""), "lin_batch")],
+    "tile_sp_begin": [Sweep(("64", "5"), "lin_batch")],
+    "tile_ws_min": [Sweep(("0", "256"), "lin_batch")],
+    "tile_ws_max": [Sweep(("0", "100"), "lin_batch")],
+    # ---- chain balance
+    "tile_split": [Sweep(("0", "0.5", "0,1.5,2"), "lin_batch")],                    # a static split
+    "auto_balance": [Sweep(("0",), "lin_batch")],
+    # ---- global-gather chain
+    "grid_block_w": [Sweep(("0", "16"), "lin_batch", "tree")],
+    # 3 on 8 and 11 frames and 4 on one frame are the pairings the default never makes; the kernels take 1 and 2 as well (every
+    # index is per wave, blockDim gives the waves per workgroup).  asserted: a queue launch entered windows
+    "gather_waves": [Sweep(("1", "2", "3", "4"), "lin_batch")],
+    "gather_pairs": [Sweep(("0", "1", "2"), "lin_batch")],
+    "sp_tail_max": [Sweep(("0", "16"), "lin_batch", "tree")],
+    "wide_tail": [Sweep(("0", "1"), "lin_batch")],
+    "min_chunk": [Sweep(("64", "5"), "lin_batch", "tree")],
+    # the slices belong to the chunk-by-chunk queue pass: one frame at the defaults, every batch with q_band_px 0.
+    # asserted: a queue launch entered windows (which walk it took is not reported)
+    "q_slices": [Sweep(("1", "5"), "lin_batch"), Sweep(("1", "5"), "lin_batch", also=(("q_band_px", "0"),))],
+    "q_band_px": [Sweep(("0", "32", "700"), "lin_batch")],
+    "q_group_units": [Sweep(("1", "16"), "lin_batch")],
+    "q_band_min_frames": [Sweep(("1", "2"), "lin_batch")],
+    # ---- stage trees
+    "general_prefix": [Sweep(("0",), "tree")],
+    "tile_segments": [Sweep(("0",), "tree")],
+    # asserted: r.passes are build_plan's rule — every chain longer than value + 4 stages gets a boundary at its start + value
+    # (8, 4); 3 (not > 3) and 40 (no chain that long) leave the passes alone.  tile_segments and tree_split_queues choose who
+    # feeds the new pass
+    "seg_cut2": [Sweep(("8", "4", "3", "40"), "tree"), Sweep(("8",), "tree", also=(("tile_segments", "0"),)),
+                 Sweep(("8",), "tree", also=(("tree_split_queues", "0"),))],
+    "tree_split_queues": [Sweep(("0",), "tree")],
+    # ---- regions / chain (which route a call took is not visible in its result)
+    "rois_on_device": [Sweep(("0",), "regions")],
+    "roi_tiles": [Sweep(("64", "0"), "regions")],
+    "group_max": [Sweep(("30", "50"), "regions")],
+    # ---- OpenCV profile
+    "cv_tiles": [Sweep(("0",), "cv_lin", "cv_tree")],
+    "cv_row_blocks": [Sweep(("1", "3"), "cv_lin", "cv_lin2")],
+    "cv_tile_min_windows": [Sweep(("64", "256"), "cv_lin", "cv_lin2")],
+    "cv_tile_min_windows0": [Sweep(("64", "512"), "cv_lin", "cv_tree")],
+    "cv_tile_ws_max": [Sweep(("0", "100"), "cv_lin")],
+    # asserted for the three tree-queue keys: the plan has tile scales and takes the chain pass over the tree queue
+    # (tree_queue == 1), or the flat queue (2) next to cv_tree_chains 0
+    "cv_row_blocks_tree": [Sweep(("1", "4"), "cv_tree")],
+    # asserted: the plan's number of tile scales differs from the default's
+    "cv_tile_min_windows_tree": [Sweep(("64", "2048"), "cv_tree")],
+    "cv_tree_chains": [Sweep(("0",), "cv_tree")],
+    # (64 is the default and runs as the default call of every cell; 100 is not a multiple of the wave; 256 is the most the chain
+    # pass takes)
+    "cv_tree_chunk": [Sweep(("100", "256"), "cv_tree"), Sweep(("100",), "cv_tree", also=(("cv_tree_chains", "0"),))],
+    "cv_tree_chain_blocks": [Sweep(("1", "4"), "cv_tree")],
+    "cv_tail_max": [Sweep(("0", "20"), "cv_lin", "cv_tree")],
+    "cv_row_band_px": [Sweep(("0", "37"), "cv_lin", "cv_tree")],
+    "cv_tree2": [Sweep(("0",), "cv_lin2")],
+    "cv_tiles_tilted": [Sweep(("0",), "cv_tilted")],
+    "cv_tree_queue_cap": [Sweep(("16", "100000"), "cv_tree")],                      # 16 overflows: the call falls back to the rows
+    # ---- single frames, integral, housekeeping
+    # asserted: for n_frames <= value the gather chain is ONE grid pass over [0, n_stages) and no queue launch; with more
+    # frames the default passes (the other refusals: test_one_pass_refusals_keep_the_default_passes)
+    "one_pass_max_frames": [Sweep(("1", "4"), "lin_few")],
+    "integral_rows": [Sweep(("0", "1"), "lin_batch", "cv_lin")],
+    "plan_cache_max": [Sweep(("2",), "lin_batch", "regions")],                      # the chain holds two plans at once
+}

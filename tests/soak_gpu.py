@@ -2,8 +2,9 @@
 `python tests/soak_gpu.py [seconds] [first seed] [max width] [max height]`; not collected by pytest).  Every case draws a cascade, a frame kind
 and size, size limits, a scale factor, a mode (exhaustive grid, the four CPU variants' skip sets incl. the block variant's f64
 grids, the OpenCV profile on tiles and rows, the two-cascade chain with or without grouping, host-supplied regions incl. stage
-trees, a batch workload repeated while the chain-balance search runs), a batch size and a few tunables; rectangles and per-stage counts must equal
-the oracle's.  Prints one line per failure and a summary; exit code 1 if anything differed."""
+trees, a batch workload repeated while the chain-balance search runs), a batch size and a few tunables (every key's default and the
+values of cases.TUNABLE_SWEEPS); batches are DISTINCT frames, each compared with its own oracle result; rectangles and per-stage counts
+must equal the oracle's.  Prints one line per failure and a summary; exit code 1 if anything differed."""
 import os
 import sys
 import time
@@ -17,7 +18,7 @@ try:
     import torch  # noqa: F401  (first: see conftest.py)
 except Exception:
     pass
-from cases import make_frame  # noqa: E402
+from cases import TUNABLE_SWEEPS, make_frame  # noqa: E402
 from clfacedetection_amd import (VJ_FLAG_COUNTERS, VJ_FLAG_GRID_F64, VJ_FLAG_SKIP_LIST, VJ_FLAG_SKIP_ROW, VJ_FLAG_TILTED_AS_UPRIGHT, Cascade, Environment,  # noqa: E402
                                  default_params)
 from clfacedetection_amd.api import DATA_DIR  # noqa: E402
@@ -35,17 +36,13 @@ NAMES = ["frontalface_alt", "frontalface_default", "frontalface_alt2", "eye", "f
          "lefteye_2splits", "lowerbody", "mcs_eyepair_big", "mcs_eyepair_small", "mcs_lefteye", "mcs_mouth", "mcs_nose", "mcs_righteye",
          "mcs_upperbody", "profileface", "righteye_2splits", "upperbody"]
 CASC = {n: (Cascade.load(n), load_vjc(os.path.join(DATA_DIR, f"haarcascade_{n}.vjc"))) for n in NAMES}
-TUNABLES = [("tile_split", ["0", "0.5", "1.3", "0,1.5,2"]), ("blocks_per_cu", ["1", "3", "8"]), ("gather_pairs", ["-1", "0", "2"]),
-            ("sp_tail_max", ["0", "16", "48"]), ("tree_split_queues", ["0", "1"]), ("concurrent", ["0", "1"]),
-            ("tile_classes_kb", ["-2,-1,0", "0,0,0", "24,40,60"]), ("grid_block_w", ["0", "32"]), ("max_subbatch", ["0", "2"]),
-            ("group_max", ["2048", "30"]), ("rois_on_device", ["1", "0"]), ("roi_tiles", ["512", "64", "0"]), ("integral_rows", ["2", "0", "1"]), ("wide_tail", ["-1", "0", "1"]), ("min_chunk", ["32", "64", "5"]),
-            ("q_slices", ["-1", "1", "5"]), ("gather_waves", ["-1", "3", "4"]), ("cv_tiles", ["1", "0"]), ("cv_tile_ws_max", ["512", "100", "0"]), ("cv_row_blocks", ["-1", "3", "1"]),
-            ("cv_tile_min_windows", ["-1", "1536", "256", "64"]), ("cv_tile_min_windows0", ["2048", "512", "64"]), ("auto_balance", ["1", "0"]),
-            # round 4: band-major queue pass (switched on for any batch size so that the soak's small batches reach it), chain sweeps of the
-            # OpenCV profile's stage trees
-            ("q_band_px", ["128", "0", "32", "700"]), ("q_group_units", ["4", "1", "16"]), ("q_band_min_frames", ["8", "1", "2"]),
-            ("cv_tree_chains", ["1", "0"]), ("cv_tree_chunk", ["64", "256", "100"]), ("cv_tail_max", ["64", "0", "20"]), ("cv_row_band_px", ["128", "0", "37"]), ("cv_tree2", ["1", "0"]), ("cv_tiles_tilted", ["1", "0"]), ("one_pass_max_frames", ["0", "4", "1"]),
-            ("cv_tree_chain_blocks", ["2", "1"]), ("cv_tile_min_windows_tree", ["256", "64", "2048"])]
+# every key's default and the values of its rows in cases.TUNABLE_SWEEPS (the table tests/test_gpu_tunable_parity.py runs cell by cell)
+TUNABLES = [(k, [env.query(k)] + sorted({v for sw in sweeps for v in sw.values})) for k, sweeps in TUNABLE_SWEEPS.items()]
+
+
+def distinct(kind, nb, h, w):
+    """nb DISTINCT frames (seeds 9000 + seed + k): a window that lands in the wrong frame, queue part or slice shows."""
+    return [make_frame(kind, 9000 + seed + k, h, w) for k in range(nb)]
 
 
 def rows(r):
@@ -106,22 +103,34 @@ while time.time() < t_end:
             flags = VJ_FLAG_COUNTERS | tflag | {"grid": 0, "skip_list": VJ_FLAG_SKIP_LIST, "skip_row": VJ_FLAG_SKIP_ROW,
                                         "block_row": VJ_FLAG_SKIP_ROW | VJ_FLAG_GRID_F64, "block_list": VJ_FLAG_SKIP_LIST | VJ_FLAG_GRID_F64}[mode]
             p = default_params(flags=flags, min_w=mn[0], min_h=mn[1], max_w=mx[0], max_h=mx[1], scale_factor=sf)
-            r = env.detect(c, [img] * nb if nb > 1 else img, p)
-            ro, st = o.detect(a, img, min_size=mn, max_size=mx, scale_factor=sf, mode={"grid": None, "skip_list": 2, "skip_row": 3, "block_row": 4, "block_list": 5}[mode])
-            for f in range(nb):
+            imgs = distinct(kind, nb, h, w)
+            r = env.detect(c, imgs if nb > 1 else imgs[0], p)
+            entered = np.zeros(len(r.stage_entered), np.int64)
+            evals = gbytes = 0
+            for f in range(nb):          # every frame against its own oracle result
+                ro, st = o.detect(a, imgs[f], min_size=mn, max_size=mx, scale_factor=sf, mode={"grid": None, "skip_list": 2, "skip_row": 3, "block_row": 4, "block_list": 5}[mode])
                 ok &= rows(r.rects[r.rects["frame"] == f]) == rows(ro)
-            ok &= r.stage_entered == [v * nb for v in st["stage_entered"]]
+                entered += np.array(st["stage_entered"], np.int64)
+                evals += st["stump_evals"]
+                gbytes += st["gather_bytes"]
+            ok &= r.stage_entered == entered.tolist() and len(r.rects) == sum((r.rects["frame"] == f).sum() for f in range(nb))
             if mode == "grid":      # node evaluations / algorithmic bytes by the oracle's definition (visited nodes), trees included
-                ok &= r.stump_evals == st["stump_evals"] * nb and r.gather_bytes == st["gather_bytes"] * nb
+                ok &= r.stump_evals == evals and r.gather_bytes == gbytes
             desc += (mn, mx, sf)
         elif mode == "opencv":
             sf = [1.1, 1.2, 1.3][int(rng.integers(0, 3))]
             mn = (0, 0) if rng.random() < 0.7 else (int(rng.integers(24, 60)),) * 2
-            r = env.detect_opencv(c, [img] * nb if nb > 1 else img, min_size=mn, scale_factor=sf, flags=VJ_FLAG_COUNTERS)
-            ro, st = o.detect_opencvlike(a, img, min_size=mn, scale_factor=sf)
+            imgs = distinct(kind, nb, h, w)
+            r = env.detect_opencv(c, imgs if nb > 1 else imgs[0], min_size=mn, scale_factor=sf, flags=VJ_FLAG_COUNTERS)
+            rt = env.detect_opencv(c, imgs if nb > 1 else imgs[0], min_size=mn, scale_factor=sf)   # (a stage tree's timed call takes the tiles and the tree queue)
+            entered = np.zeros(len(r.stage_entered), np.int64)
+            visited = 0
             for f in range(nb):
-                ok &= sorted(rows(r.rects[r.rects["frame"] == f])) == sorted(rows(ro))
-            ok &= r.stage_entered == [v * nb for v in st["stage_entered"]] and r.windows == st["windows"] * nb
+                ro, st = o.detect_opencvlike(a, imgs[f], min_size=mn, scale_factor=sf)
+                ok &= sorted(rows(r.rects[r.rects["frame"] == f])) == sorted(rows(ro)) == sorted(rows(rt.rects[rt.rects["frame"] == f]))
+                entered += np.array(st["stage_entered"], np.int64)
+                visited += st["windows"]
+            ok &= r.stage_entered == entered.tolist() and r.windows == visited
             desc += (mn, sf)
         elif mode == "rois":                      # host-supplied regions of random sizes in a small batch
             if tilted:                            # (stage trees are welcome: the region pass walks them)
@@ -155,19 +164,23 @@ while time.time() < t_end:
             mnb = 0 if mode == "chain" else int(rng.integers(1, 4))
             skip = int(rng.integers(0, 6)) if mode == "chain" else 0      # 1: row skip rule, 2: list skip rule on both cascades (host hand-off)
             flag1, omode = {1: (VJ_FLAG_SKIP_ROW, 3), 2: (VJ_FLAG_SKIP_LIST, 2)}.get(skip, (0, None))
-            r1, r2 = env.detect_chain(c, c2, [img] * nb if nb > 1 else img, default_params(min_neighbors=mnb, flags=flag1), default_params(flags=flag1))
-            ro, _ = o.detect(a, img, mode=omode)
-            if mnb:
-                xywh = np.stack([ro[k] for k in ("x", "y", "w", "h")], 1) if len(ro) else np.zeros((0, 4), np.int32)
-                g, wt = o.group_rectangles(xywh, mnb)
-                want1 = [(int(q[0]), int(q[1]), int(q[2]), int(q[3]), int(n)) for q, n in zip(g, wt)]
-                got1 = [(int(q["x"]), int(q["y"]), int(q["w"]), int(q["h"]), int(q["weight"])) for q in r1.rects[r1.rects["frame"] == 0]]
-            else:
-                want1 = [(int(q["x"]), int(q["y"]), int(q["w"]), int(q["h"]), 0) for q in ro]
-                got1 = [(int(q["x"]), int(q["y"]), int(q["w"]), int(q["h"]), 0) for q in r1.rects[r1.rects["frame"] == 0]]
+            imgs = distinct(kind, nb, h, w)
+            r1, r2 = env.detect_chain(c, c2, imgs if nb > 1 else imgs[0], default_params(min_neighbors=mnb, flags=flag1), default_params(flags=flag1))
+            want1 = []                            # (x, y, w, h, neighbours, frame) of every frame's own candidates, in frame order
+            for f in range(nb):
+                ro, _ = o.detect(a, imgs[f], mode=omode)
+                if mnb:
+                    xywh = np.stack([ro[k] for k in ("x", "y", "w", "h")], 1) if len(ro) else np.zeros((0, 4), np.int32)
+                    g, wt = o.group_rectangles(xywh, mnb)
+                    want1 += [(int(q[0]), int(q[1]), int(q[2]), int(q[3]), int(n), f) for q, n in zip(g, wt)]
+                else:
+                    want1 += [(int(q["x"]), int(q["y"]), int(q["w"]), int(q["h"]), 0, f) for q in ro]
+            got1 = [(int(q["x"]), int(q["y"]), int(q["w"]), int(q["h"]), int(q["weight"]) if mnb else 0, int(q["frame"])) for q in r1.rects]
             ok &= got1 == want1
-            for i, (x, y, ww, hh, _) in enumerate(want1[:6]):
-                r2o, _ = o.detect(a2, np.ascontiguousarray(img[y:y + hh, x:x + ww]), mode=omode)
+            # regions spread over the whole list, so that every frame's are among them (the oracle on each costs a call)
+            for i in list(range(0, len(want1), max(1, len(want1) // 8)))[:8]:
+                x, y, ww, hh, _, f = want1[i]
+                r2o, _ = o.detect(a2, np.ascontiguousarray(imgs[f][y:y + hh, x:x + ww]), mode=omode)
                 ok &= rows(r2.rects[r2.rects["frame"] == i]) == rows(r2o)
             desc += (mnb, len(want1), skip)
     except Exception as e:   # noqa: BLE001

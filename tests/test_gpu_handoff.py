@@ -13,8 +13,8 @@ from dataclasses import dataclass
 import numpy as np
 import pytest
 
-from cases import tunables
-from clfacedetection_amd import VJ_FLAG_COUNTERS, Environment, default_params, synth
+from cases import check_against_oracle, tunables   # (check_against_oracle: shared with test_gpu_tunable_parity.py)
+from clfacedetection_amd import Environment, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -94,35 +94,6 @@ def oracle_set(oracle, cascades, casc, size):
         with ThreadPoolExecutor(8) as ex:
             _ORACLE[key] = list(ex.map(lambda i: oracle.detect(a, f[i]), range(N_SET)))
     return _ORACLE[key]
-
-
-def rows_of(rects):
-    return [tuple(int(r[k]) for k in ("scale_idx", "x", "y", "w", "h")) for r in rects]
-
-
-def first_difference(got, want):
-    s = next(s for s, (x, y) in enumerate(zip(got, want)) if x != y)
-    return f"stage {s}: {got[s]} entered, the oracle {want[s]}"
-
-
-def check_against_oracle(env, c, frames, want, label):
-    """One counted and one timed detect of `frames` against the oracle's per-frame results `want`; returns the counted
-    result and the oracle's per-stage totals."""
-    r = env.detect(c, frames, default_params(flags=VJ_FLAG_COUNTERS))
-    n_st = c.info.n_stages
-    entered, windows = [0] * n_st, 0
-    for i, (ro, st) in enumerate(want):
-        mine = rows_of(r.rects[r.rects["frame"] == i])
-        assert mine == rows_of(ro), f"{label}: frame {i}: {len(mine)} rectangles, the oracle {len(ro)}"
-        entered = [x + y for x, y in zip(entered, st["stage_entered"])]
-        windows += st["windows"]
-    assert r.stage_entered == entered, f"{label}: {first_difference(r.stage_entered, entered)}"
-    assert r.windows == windows, f"{label}: {r.windows} windows, the oracle {windows}"
-    per_launch = [sum(l["stage_entered"][s] for l in r.launches) for s in range(n_st)]
-    assert per_launch == r.stage_entered, f"{label}: per-launch counters do not add up ({first_difference(per_launch, r.stage_entered)})"
-    r2 = env.detect(c, frames)
-    assert np.array_equal(r2.rects, r.rects), f"{label}: the timed kernels' rectangles differ from the counted ones"
-    return r, entered
 
 
 def tile_counts(r, n_st):
