@@ -651,3 +651,285 @@ TUNABLE_SWEEPS = {
     "integral_rows": [Sweep(("0", "1"), "lin_batch", "cv_lin")],
     "plan_cache_max": [Sweep(("2",), "lin_batch", "regions")],                      # the chain holds two plans at once
 }
+
+
+# ----------------------------------------------------------------------------- arithmetic edges: stage sums, variances, sums
+# tests/test_arithmetic_cases_cpu.py proves on the CPU that these inputs are decisive; tests/test_gpu_arithmetic_edges.py runs
+# them through every path.  Both walk ORDER_CELLS / TIE_CELLS.
+ORDER_FORMS = ("stumps", "trees", "two_stage", "huge")
+ORDER_PREFIX = 3            # stages in front of the decisive one(s): accept-all, thinning, accept-all
+THIN_STUMPS = 4             # the thinning stage passes a window when all of its stumps say yes: 1 in 16 on noise
+
+
+def _small_spot(k: int):
+    """The k-th 3 x 3 spot of the 20 x 20 window (18 x 18 positions, visited with a stride coprime to 324)."""
+    p = (k * 89 + 7) % 324
+    return (p % 18, p // 18, 3, 3)
+
+
+def _mean_node(spot, left, right):
+    """A node that compares the mean under `spot` with the window's at node threshold 0 (rect 0 is the whole window: the
+    evaluators set its weight from rect 1's area)."""
+    return ([(0, 0, 20, 20), spot, (0, 0, 0, 0)], [-1.0, 1.0, 0.0], 0.0, left, right)
+
+
+def _linear_cascade(name: str, stages):
+    """oracle CascadeArrays of a linear 20 x 20 cascade.  stages: [(trees, stage threshold)], a tree: (nodes, leaf values),
+    a node: (rects, weights, threshold, left, right) with left / right as in the node arrays."""
+    from oracle.oracle import CascadeArrays
+    c = CascadeArrays()
+    c.win_w = c.win_h = 20
+    c.name = name
+    st_first, st_n, st_thr, tr_first, tr_n, tr_alpha = [], [], [], [], [], []
+    rects, weights, thr, left, right, alpha = [], [], [], [], [], []
+    for trees, sthr in stages:
+        st_first.append(len(tr_first))
+        st_n.append(len(trees))
+        st_thr.append(sthr)
+        for nodes, al in trees:
+            tr_first.append(len(thr))
+            tr_n.append(len(nodes))
+            tr_alpha.append(len(alpha))
+            for rr, ww, t, lf, rt in nodes:
+                rects += [list(r) for r in rr]
+                weights += ww
+                thr.append(t)
+                left.append(lf)
+                right.append(rt)
+            alpha += list(al)
+    n = len(stages)
+    c.stage_first_tree = np.array(st_first, np.int32)
+    c.stage_n_trees = np.array(st_n, np.int32)
+    c.stage_threshold = np.array(st_thr, np.float32)
+    c.stage_parent = np.arange(-1, n - 1, dtype=np.int32)
+    c.stage_next = np.full(n, -1, np.int32)
+    c.stage_child = np.array(list(range(1, n)) + [-1], np.int32)
+    c.tree_first_node = np.array(tr_first, np.int32)
+    c.tree_n_nodes = np.array(tr_n, np.int32)
+    c.tree_first_alpha = np.array(tr_alpha, np.int32)
+    c.node_rect = np.array(rects, np.int32).reshape(-1)
+    c.node_weight = np.array(weights, np.float32)
+    c.node_threshold = np.array(thr, np.float32)
+    c.node_left = np.array(left, np.int32)
+    c.node_right = np.array(right, np.int32)
+    c.node_tilted = np.zeros(len(thr), np.int32)
+    c.alpha = np.array(alpha, np.float32)
+    return c
+
+
+def _thinning_prefix(trees: bool = False):
+    """Stage 0 accepts every window (the decisive stage is not stage 0, and the OpenCV profile's walk never skips a
+    window), stage 1 passes one window in sixteen on noise (all THIN_STUMPS spots brighter than the window's mean), stage 2
+    accepts every window again.  The tile kernel's wave-split finish and wave-independent tail — where a stage's leaves are
+    added in another order than the reference's — take a tile over at a re-pack point at or after tile_sp_begin (3) once at
+    most tile_ws_max (512) of its up to 2048 windows are left: the thinning stage is what gets the decisive stage there.
+    trees: the same verdicts from two-node trees (the root decides; both leaves of its child are 0), because the kernels'
+    two-node forms (TREE2, cv_tree2) are only taken by cascades made of such trees throughout."""
+    def item(k):
+        if trees:
+            return ([_mean_node(_small_spot(k), 1, 0), _mean_node(_small_spot(k + 7), -1, -2)], [1.0, 0.0, 0.0])
+        return ([_mean_node(_small_spot(k), 0, -1)], [0.0, 1.0])
+    all_pass = ([item(300)], -1.0)
+    thin = ([item(310 + k) for k in range(THIN_STUMPS)], THIN_STUMPS - 0.5)
+    return [all_pass, thin, all_pass]
+
+
+def _median_in_order(values, dtype):
+    """Median attained running sum (dtype additions, column order) of the rows of `values`."""
+    from oracle.np_oracle import in_order_sum
+    s = in_order_sum(values, dtype)
+    return np.sort(s)[len(s) // 2]
+
+
+def _order_stage(rng, form: str, n: int, spot0: int):
+    """One decisive stage of order_cascade: ([trees], threshold)."""
+    f32 = np.float32
+    if form == "huge":
+        # three classes: around 2^100 (both leaves equal: the part every window shares, which takes the running f64 sum to
+        # where one ulp is 2^48 and more), around 2^60 (right = left + j 2^48: the lattice of attained sums, whose low bits
+        # the large partial sums round away in an order-dependent way) and around 1 (lost in every order)
+        cls = rng.choice(3, n, p=[0.3, 0.55, 0.15])
+        left = (np.array([2.0 ** 100, 2.0 ** 60, 1.0])[cls] * rng.uniform(1, 2, n) * rng.choice([-1, 1], n)).astype(f32)
+        top = np.nonzero(cls == 0)[0]
+        left[top[1::2]] = -left[top[0:2 * (len(top) // 2):2]]      # the large leaves cancel in pairs: the sum ends near 2^63,
+        if len(top) % 2:                                           # where a float threshold is fine enough
+            left[top[-1]], cls[top[-1]] = f32(2.0 ** 60), 1
+        step = np.array([0.0, 2.0 ** 48, 1.0])[cls]
+        extra = [(left + rng.integers(1, 64, n) * step).astype(f32) for _ in range(2)]
+    else:
+        left = (rng.choice([3000.0, 700.0, 90.0, 11.0], n) * rng.choice([-1, 1], n) + rng.uniform(-1, 1, n)).astype(f32)
+        coarse = rng.choice(n, min(14, n), replace=False)
+        extra = []
+        for _ in range(2):
+            if n < 16:   # a handful of items: the band is a few ulps of the sum, so the leaves differ by 1..3 of them
+                r = (left + rng.integers(1, 4, n) * np.spacing(f32(np.abs(left).sum()))).astype(f32)
+            else:
+                r = (left + rng.integers(1, 64, n) * f32(2.0 ** -12)).astype(f32)
+                r[coarse] = (left[coarse] + rng.integers(1, 64, len(coarse)) * f32(2.0 ** -9)).astype(f32)
+            extra.append(r)
+    # the threshold: the median attained in-order sum under independent fair bits (what the nodes give on noise), in the
+    # arithmetic of the profile the form is for (f64 for "huge", else f32)
+    sim = 20000
+    if form == "trees":      # root right: leaf 0; root left -> child: leaves 1 / 2
+        code = rng.choice(3, (sim, n), p=[0.5, 0.25, 0.25])
+        leaves = np.stack([left, extra[0], extra[1]], 1)                 # (n, 3)
+        vals = leaves[np.arange(n)[None, :], code]
+        trees = [([_mean_node(_small_spot(spot0 + 2 * k), 1, 0), _mean_node(_small_spot(spot0 + 2 * k + 1), -1, -2)],
+                  [float(v) for v in leaves[k]]) for k in range(n)]
+    else:
+        vals = np.where(rng.integers(0, 2, (sim, n)).astype(bool), extra[0][None, :], left[None, :])
+        trees = [([_mean_node(_small_spot(spot0 + k), 0, -1)], [float(left[k]), float(extra[0][k])]) for k in range(n)]
+    thr = _median_in_order(vals, np.float64 if form == "huge" else f32)
+    return trees, float(f32(thr))
+
+
+def order_cascade(form: str, n: int, seed: int = 0):
+    """oracle CascadeArrays of a 20 x 20 cascade whose decisive stage (index ORDER_PREFIX) has n stumps — n two-node trees
+    for "trees" — whose running sum depends on the order of addition, behind _thinning_prefix().  Every item compares its
+    own 3 x 3 spot with the window's mean at node threshold 0, so on noise the verdict bits are close to independent and
+    every window takes its own rounding path.  Leaves: a magnitude from {3000, 700, 90, 11} +- 1 with a random sign on the
+    left, the left one plus a small multiple of 2^-12 (for up to 14 items 2^-9) on the right; the stage threshold is the
+    median attained in-order sum, so the attained sums form a fine lattice around it and every window lies within sp_delta
+    of it.  "two_stage": two such stages in a row (the survivors of a replayed stage enter another one).  "huge": leaves
+    around +-2^100, +-2^60 and +-1, for which the f64 sum of the OpenCV profile depends on the order too; sp_delta is
+    about 2^90 there, still a finite float."""
+    assert form in ORDER_FORMS and 1 <= n <= 256
+    rng = np.random.default_rng([seed, n, ORDER_FORMS.index(form)])
+    stages = _thinning_prefix(form == "trees") + [_order_stage(rng, form, n, 0)]
+    if form == "two_stage":
+        stages.append(_order_stage(rng, form, n, 150))
+    return _linear_cascade(f"order_{form}_{n}_{seed}", stages)
+
+
+TIE_STUMPS = 70
+
+
+def tie_cascade(strict: bool = False, seed: int = 0):
+    """Like order_cascade("stumps", 70), with leaves that are multiples of 2^-6 of magnitude <= 2: every order of addition
+    gives the same exact sum, the attained sums lie 2^-6 apart and sp_delta (about 8e-4) is far below that, so a window is
+    inside the band only when its sum EQUALS the threshold.  strict=False: the stage threshold is an attained sum (those
+    windows pass: sum >= thr); strict=True: the next float above it (the same windows fail)."""
+    rng = np.random.default_rng([seed, 4242])
+    n = TIE_STUMPS
+    left = rng.integers(-96, 97, n) / 64.0
+    right = np.clip(left + rng.integers(1, 9, n) * rng.choice([-1, 1], n) / 64.0, -2.0, 2.0)
+    vals = np.where(rng.integers(0, 2, (20000, n)).astype(bool), right[None, :], left[None, :])
+    thr = np.float32(_median_in_order(vals, np.float32))
+    if strict:
+        thr = np.nextafter(thr, np.float32(np.inf))
+    trees = [([_mean_node(_small_spot(k), 0, -1)], [float(left[k]), float(right[k])]) for k in range(n)]
+    return _linear_cascade(f"tie_{'gt' if strict else 'ge'}_{seed}", _thinning_prefix() + [(trees, float(thr))])
+
+
+def sp_delta(c, stage: int) -> np.float32:
+    """The documented band of a stage: 4 n 2^-24 sum over trees of max|leaf| * 1.001 + 1e-30 (n: the stage's nodes), as a float."""
+    t0, nt = int(c.stage_first_tree[stage]), int(c.stage_n_trees[stage])
+    amax = sum(float(np.abs(c.alpha[int(c.tree_first_alpha[t]):int(c.tree_first_alpha[t]) + int(c.tree_n_nodes[t]) + 1].astype(np.float64)).max())
+               for t in range(t0, t0 + nt))
+    n = sum(int(c.tree_n_nodes[t]) for t in range(t0, t0 + nt))
+    return np.float32(4.0 * n * 2.0 ** -24 * amax * 1.001 + 1e-30)
+
+
+def alternative_orders(n: int):
+    """{name: function(leaves (windows, n), dtype) -> sums}: the orders in which the kernels add a stage's n leaf values
+    when they do not follow the reference — reversed; a butterfly inside balanced blocks of up to 64, the blocks in order
+    (tile_wave_tail); K even ranges, each in order, for K in 2, 4, 8 (tile_wave_split) — leaving out those whose sequence of
+    additions IS the reference's for this n (K ranges of one range, or whose second range is empty)."""
+    from oracle.np_oracle import in_order_sum as in_order
+
+    def butterfly(v, dt):
+        nb = (n + 63) // 64
+        out, jb = np.zeros(len(v), dt), 0
+        for b in range(nb):
+            jn = n // nb + (1 if b < n % nb else 0)
+            x = np.zeros((len(v), 64), dt)
+            x[:, :jn] = v[:, jb:jb + jn]
+            jb += jn
+            w = 64
+            while w > 1:
+                x = (x[:, :w // 2] + x[:, w // 2:w]).astype(dt)
+                w //= 2
+            out = (out + x[:, 0]).astype(dt)
+        return out
+
+    def ranges(K):
+        rs = ((n + K - 1) // K + 1) & ~1
+        def f(v, dt):
+            out = np.zeros(len(v), dt)
+            for j0 in range(0, n, rs):
+                out = (out + in_order(v[:, j0:j0 + rs], dt)).astype(dt)
+            return out
+        return rs, f
+    orders = {"reversed": lambda v, dt: in_order(v[:, ::-1], dt), "butterfly": butterfly}
+    for K in (2, 4, 8):
+        rs, f = ranges(K)
+        if n - rs >= 2:   # a second range of one value adds it last, as the running sum does
+            orders[f"ranges{K}"] = f
+    return orders
+
+
+def near_flat_frame(seed: int, h: int, w: int, level: int, n_off: int) -> np.ndarray:
+    """A constant frame of grey `level` with n_off pixels one level off (below at 255, above otherwise): in most windows
+    the f32 expression Q / area - mean * mean cancels to a small negative, zero or positive value."""
+    rng = np.random.default_rng([seed, level])
+    img = np.full((h, w), level, np.uint8)
+    flat = rng.choice(h * w, n_off, replace=False)
+    img.reshape(-1)[flat] = level - 1 if level == 255 else level + 1
+    return img
+
+
+BRIGHT_SIDE = 4608
+
+
+def bright_frame(seed: int, side: int = BRIGHT_SIDE) -> np.ndarray:
+    """side x side pixels of 230..255 (noise of 230..235 under three large drawn faces): the sum integral passes 2^32 (side^2 * 242.5 = 5.1e9 at 4608) and the largest windows
+    hold more than 2^31, where VJ_FLAG_SIGNED_MEAN reads the sum as negative.  The profiles accept about 32 k a side
+    ((W + 1)(H + 3) < 2^30); such a frame is 1 GiB and its integrals 12 GiB in the oracle, so the side is the smallest round
+    one that meets both premises with room to spare (tests/test_arithmetic_cases_cpu.py asserts them)."""
+    img = np.random.default_rng([seed, side]).integers(230, 236, (side, side), dtype=np.uint8)
+    # drawn faces as large as the largest windows, their contrast pressed into 236..255: on plain noise every large window
+    # fails stage 0 with or without the flag; a face takes windows deep into the cascade, where the norm factor decides
+    for size, at in ((3437, 300), (3781, 500), (4159, 200)):
+        face = np.clip(synth.crude_face(size), 0, 255) * (19.0 / 255.0)
+        img[at:at + size, at:at + size] = np.maximum(img[at:at + size, at:at + size], (236 + face).astype(np.uint8))
+    return img
+
+
+# (id, form, n, cascade seed, (h, w), first frame seed): batches are the first 1 and all ARITH_FRAMES noise frames
+ARITH_FRAMES = 8
+ORDER_CELLS = [
+    ("stumps3", "stumps", 3, 5, (240, 320), 100),
+    ("stumps64", "stumps", 64, 0, (240, 320), 110),
+    ("stumps65", "stumps", 65, 0, (240, 320), 120),
+    ("stumps130", "stumps", 130, 0, (240, 320), 130),
+    ("stumps200", "stumps", 200, 0, (240, 320), 140),
+    ("trees65", "trees", 65, 0, (240, 320), 150),
+    ("trees130", "trees", 130, 0, (240, 320), 160),
+    ("two_stage130", "two_stage", 130, 0, (240, 320), 170),
+    ("huge130", "huge", 130, 7, (240, 320), 180),
+]
+TIE_CELLS = [("tie_ge", False, 0, (240, 320), 190), ("tie_gt", True, 0, (240, 320), 190)]
+
+
+def arith_frames(size, seed0: int, n: int = ARITH_FRAMES) -> np.ndarray:
+    return np.stack([synth.frame("noise", seed0 + k, size[0], size[1]) for k in range(n)])
+
+
+# (id, cascade — a shipped one or ("geometry", win, kind) —, (h, w), pixels off): a cell's frames are near_flat_frame at each
+# of NEAR_FLAT_LEVELS (seed = the level's index), one batch of distinct frames
+NEAR_FLAT_LEVELS = (255, 128, 1)
+NEAR_FLAT_CELLS = [
+    ("alt", "frontalface_alt", (150, 200), 60),
+    ("alt2", "frontalface_alt2", (150, 200), 60),
+    ("alt_tree", "frontalface_alt_tree", (150, 200), 60),
+    ("geometry", ("geometry", (24, 24), "upright"), (150, 200), 60),
+    ("alt_sparse", "frontalface_alt", (131, 177), 25),
+]
+
+
+def near_flat_frames(size, n_off: int) -> np.ndarray:
+    return np.stack([near_flat_frame(k, size[0], size[1], level, n_off) for k, level in enumerate(NEAR_FLAT_LEVELS)])
+
+
+BRIGHT_MIN = 3000           # min_w / min_h of the bright-frame calls: the five largest scales (windows of 3125 .. 4575 pixels)
+BRIGHT_CASCADES = ("frontalface_alt", "frontalface_alt_tree")

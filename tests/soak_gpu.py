@@ -2,7 +2,8 @@
 `python tests/soak_gpu.py [seconds] [first seed] [max width] [max height]`; not collected by pytest).  Every case draws a cascade, a frame kind
 and size, size limits, a scale factor, a mode (exhaustive grid, the four CPU variants' skip sets incl. the block variant's f64
 grids, the OpenCV profile on tiles and rows, the two-cascade chain with or without grouping, host-supplied regions incl. stage
-trees, a batch workload repeated while the chain-balance search runs), a batch size and a few tunables (every key's default and the
+trees, a batch workload repeated while the chain-balance search runs, the order / tie cascades and near-flat and bright frames of
+tests/test_gpu_arithmetic_edges.py in both profiles), a batch size and a few tunables (every key's default and the
 values of cases.TUNABLE_SWEEPS); batches are DISTINCT frames, each compared with its own oracle result; rectangles and per-stage counts
 must equal the oracle's.  Prints one line per failure and a summary; exit code 1 if anything differed."""
 import os
@@ -18,8 +19,9 @@ try:
     import torch  # noqa: F401  (first: see conftest.py)
 except Exception:
     pass
-from cases import TUNABLE_SWEEPS, make_frame  # noqa: E402
-from clfacedetection_amd import (VJ_FLAG_COUNTERS, VJ_FLAG_GRID_F64, VJ_FLAG_SKIP_LIST, VJ_FLAG_SKIP_ROW, VJ_FLAG_TILTED_AS_UPRIGHT, Cascade, Environment,  # noqa: E402
+from cases import (BRIGHT_MIN, ORDER_CELLS, TIE_CELLS, TUNABLE_SWEEPS, bright_frame, cascade_to_product, make_frame, near_flat_frame,  # noqa: E402
+                   order_cascade, tie_cascade)
+from clfacedetection_amd import (VJ_FLAG_COUNTERS, VJ_FLAG_GRID_F64, VJ_FLAG_SIGNED_MEAN, VJ_FLAG_SKIP_LIST, VJ_FLAG_SKIP_ROW, VJ_FLAG_TILTED_AS_UPRIGHT, Cascade, Environment,  # noqa: E402
                                  default_params)
 from clfacedetection_amd.api import DATA_DIR  # noqa: E402
 from oracle.oracle import Oracle, load_vjc  # noqa: E402
@@ -36,6 +38,7 @@ NAMES = ["frontalface_alt", "frontalface_default", "frontalface_alt2", "eye", "f
          "lefteye_2splits", "lowerbody", "mcs_eyepair_big", "mcs_eyepair_small", "mcs_lefteye", "mcs_mouth", "mcs_nose", "mcs_righteye",
          "mcs_upperbody", "profileface", "righteye_2splits", "upperbody"]
 CASC = {n: (Cascade.load(n), load_vjc(os.path.join(DATA_DIR, f"haarcascade_{n}.vjc"))) for n in NAMES}
+ARITH = {}      # cell id -> (product Cascade, oracle CascadeArrays) of the order / tie cascades, built on first use
 # every key's default and the values of its rows in cases.TUNABLE_SWEEPS (the table tests/test_gpu_tunable_parity.py runs cell by cell)
 TUNABLES = [(k, [env.query(k)] + sorted({v for sw in sweeps for v in sw.values})) for k, sweeps in TUNABLE_SWEEPS.items()]
 
@@ -56,7 +59,7 @@ seed = seed0
 while time.time() < t_end:
     rng = np.random.default_rng(770000 + seed)
     mode = ["grid", "grid", "grid", "skip_list", "skip_row", "block_row", "block_list", "opencv", "opencv", "chain", "chain_grouped", "rois",
-            "rois", "feedback"][int(rng.integers(0, 14))]
+            "rois", "feedback", "arith"][int(rng.integers(0, 15))]
     name = NAMES[int(rng.integers(0, len(NAMES)))]
     c, a = CASC[name]
     linear = bool(np.all(a.stage_next == -1))
@@ -82,7 +85,38 @@ while time.time() < t_end:
     desc = (seed, mode, name, kind, h, w, nb, tun)
     ok = True
     try:
-        if mode == "feedback":                    # a batch workload repeated: the chain-balance search moves between plans, never the result
+        if mode == "arith":                       # stage sums inside sp_delta of the threshold, sums on it, nearly flat windows, sums past 2^31
+            cell = (ORDER_CELLS + TIE_CELLS)[int(rng.integers(0, len(ORDER_CELLS) + len(TIE_CELLS)))]
+            draw = int(rng.integers(0, 8))
+            sm = False
+            if draw == 0:                         # a shipped cascade on the bright frame, large scales only
+                c, a = CASC[["frontalface_alt", "frontalface_alt_tree"][int(rng.integers(0, 2))]]
+                imgs, mn, sm = [bright_frame(seed % 3)], (BRIGHT_MIN, BRIGHT_MIN), bool(rng.integers(0, 2))
+            elif draw < 3:                        # a shipped cascade on nearly flat frames
+                c, a = CASC[["frontalface_alt", "frontalface_alt2", "frontalface_alt_tree"][int(rng.integers(0, 3))]]
+                imgs, mn = [near_flat_frame(seed + k, h, w, [255, 128, 1][int(rng.integers(0, 3))], int(rng.integers(1, 200))) for k in range(nb)], (0, 0)
+            else:
+                if cell[0] not in ARITH:
+                    aa = order_cascade(*cell[1:4]) if len(cell) == 6 else tie_cascade(*cell[1:3])
+                    ARITH[cell[0]] = (cascade_to_product(aa), aa)
+                c, a = ARITH[cell[0]]
+                imgs, mn = [make_frame("noise", 9000 + seed + k, h, w) for k in range(nb)], (0, 0)
+            r = env.detect(c, imgs, default_params(flags=VJ_FLAG_COUNTERS | (VJ_FLAG_SIGNED_MEAN if sm else 0), min_w=mn[0], min_h=mn[1]))
+            rc = env.detect_opencv(c, imgs, min_size=mn, flags=VJ_FLAG_COUNTERS)
+            entered, entered_cv = np.zeros(len(r.stage_entered), np.int64), np.zeros(len(r.stage_entered), np.int64)
+            windows = windows_cv = 0
+            for f in range(len(imgs)):
+                ro, st = o.detect(a, imgs[f], min_size=mn, signed_mean=sm)
+                rv, sv = o.detect_opencvlike(a, imgs[f], min_size=mn)
+                windows += st["windows"]
+                windows_cv += sv["windows"]
+                ok &= rows(r.rects[r.rects["frame"] == f]) == rows(ro) and sorted(rows(rc.rects[rc.rects["frame"] == f])) == sorted(rows(rv))
+                entered += np.array(st["stage_entered"], np.int64)
+                entered_cv += np.array(sv["stage_entered"], np.int64)
+            ok &= r.stage_entered == entered.tolist() and rc.stage_entered == entered_cv.tolist()
+            ok &= r.windows == windows and rc.windows == windows_cv
+            desc += (cell[0], draw, sm)
+        elif mode == "feedback":                    # a batch workload repeated: the chain-balance search moves between plans, never the result
             nb = int(rng.integers(8, 12))
             imgs = np.stack([make_frame(kind, 9000 + seed + k, min(h, 420), min(w, 520)) for k in range(nb)])
             p = default_params(scale_factor=[1.1, 1.2][int(rng.integers(0, 2))])
