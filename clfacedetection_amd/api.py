@@ -35,6 +35,7 @@ VJ_FLAG_SKIP_ROW = 1 << 3      # the plain CPU variant: round() positions, skip 
 VJ_FLAG_GRID_F64 = 1 << 4      # + one of the two above: the same loop of the block variant, whose step is a double (clod.cpp:862)
 VJ_FLAG_TILTED_AS_UPRIGHT = 1 << 5   # clod profile: <tilted>1 rectangles count as upright ones, as in the reference (clod.cpp:448-492); else refused
 VJ_FLAG_CV_CANNY_PRUNING = 1 << 6    # OpenCV profile: CV_HAAR_DO_CANNY_PRUNING (edge map per frame, a pruning test per visited window)
+VJ_FLAG_CV_SCALE_IMAGE = 1 << 7      # OpenCV profile: CV_HAAR_SCALE_IMAGE (the image is scaled, the cascade runs at base size on every grid position)
 
 # cvHaarDetectObjects' flags (tempcv.hpp:127-130).  Only CV_HAAR_DO_CANNY_PRUNING stays on the scale-cascade path that
 # vj_detect_opencv implements; the other three are other paths and are refused.
@@ -163,6 +164,7 @@ _SIGNATURES = {
     "vj_integral_tilted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "vj_grayscale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vj_canny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "vj_resize_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "vj_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "vj_host_free": (None, [C.c_void_p, C.c_void_p]),
     "vj_detect_chain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params),
@@ -434,6 +436,17 @@ class Environment:
         _check(load_library().vj_canny(self._h, C.byref(imgs[0]), e.ctypes.data, e.strides[0]), "vj_canny")
         return e
 
+    def resize_linear(self, img, dst_w: int, dst_h: int, color: bool = False) -> np.ndarray:
+        """vj_resize_linear: cvResize(gray, dst, CV_INTER_LINEAR) of the 8-bit gray image on the device, one level of the
+        pyramid VJ_FLAG_CV_SCALE_IMAGE builds; returns a (dst_h, dst_w) uint8 array.  img as for canny."""
+        imgs, n, keep = self._images(img, color)
+        if n != 1:
+            raise ValueError("resize_linear takes one image")
+        d = np.empty((int(dst_h), int(dst_w)), np.uint8)
+        _check(load_library().vj_resize_linear(self._h, C.byref(imgs[0]), int(dst_w), int(dst_h), d.ctypes.data, d.strides[0]),
+               "vj_resize_linear")
+        return d
+
     def host_alloc(self, shape, dtype=np.uint8) -> np.ndarray:
         """vj_host_alloc: a page-locked numpy array (freed with host_free) for copy-free frame uploads."""
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
@@ -513,7 +526,9 @@ class Environment:
     def detect_opencv(self, cascade: Cascade, frames, min_size=(0, 0), scale_factor: float = 1.1, min_neighbors: int = 0,
                       flags: int = 0, color: bool = False) -> DetectResult:
         """vj_detect_opencv: cvHaarDetectObjects' scale-cascade path (OpenCV arithmetic profile: f64 sums, threshold
-        bias, ystep = max(2, factor), skip after a stage-0 reject, border rule).  result.windows = visited positions."""
+        bias, ystep = max(2, factor), skip after a stage-0 reject, border rule).  result.windows = visited positions.
+        flags: VJ_FLAG_COUNTERS, VJ_FLAG_CV_CANNY_PRUNING, or VJ_FLAG_CV_SCALE_IMAGE for the CV_HAAR_SCALE_IMAGE branch (an image
+        pyramid, the cascade at base size on every grid position; result.windows = grid positions; the canny flag is ignored)."""
         imgs, n, keep = self._images(frames, color)
         p = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
         res = _Result()
@@ -705,7 +720,9 @@ def cvHaarDetectObjects(image, cascade: Cascade, env: Environment, scale_factor:
                         flags: int = 0, min_size=(0, 0), vj_flags: int = 0) -> DetectResult:
     """The reference demo's OpenCV leg (main.cpp:145: cvHaarDetectObjects(img, cascade, storage, 1.1, ...)) as
     tempcv.cpp:1188-1456 specifies its scale-cascade path, on the device (OpenCV arithmetic profile).  `flags`:
-    0 or CV_HAAR_DO_CANNY_PRUNING; scale-image, find-biggest-object and rough search are other paths."""
+    0 or CV_HAAR_DO_CANNY_PRUNING; find-biggest-object and rough search are other paths and are refused.  CV_HAAR_SCALE_IMAGE in
+    `flags` is refused here too; that branch (tempcv.cpp:1257-1329) is reached with vj_flags=VJ_FLAG_CV_SCALE_IMAGE, which this
+    function forwards, or through Environment.detect_opencv(flags=VJ_FLAG_CV_SCALE_IMAGE)."""
     if flags & ~CV_HAAR_DO_CANNY_PRUNING:
         raise VjError(4, "cvHaarDetectObjects", "only flags 0 and CV_HAAR_DO_CANNY_PRUNING (the scale-cascade path) are implemented; "
                       "CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT and CV_HAAR_DO_ROUGH_SEARCH are not")

@@ -7,6 +7,8 @@
 //   stage threshold bias               tempcv.cpp:262, 419
 //   hidden-cascade flags               tempcv.cpp:410-470 (isStumpBased, is_tree, per-stage two_rects) — they select
 //                                        the arithmetic of a node sum (vj_cv_profile.hip: cv_node_sum)
+//   CV_HAAR_SCALE_IMAGE branch         tempcv.cpp:1257-1329, invoker :989-1113 (VJ_FLAG_CV_SCALE_IMAGE: the image pyramid in one canvas per
+//                                        frame, vj_pyramid.hip; ONE node table at factor 1; exhaustive-grid tile and row kernels)
 // Stumps or multi-node trees, linear cascades or stage trees, upright or tilted features (tilted integral).
 // Second arithmetic profile.  OpenCV itself is not available here or on the GPU box, so
 // parity is against the oracle's restatement of the same lines (oc_detect_opencvlike): unpinned.
@@ -27,7 +29,41 @@ struct CvScaleHost {
     double factor;
     int idx;
     int win_w, win_h, end_x, end_y;
+    // CV_HAAR_SCALE_IMAGE: a level of the pyramid — its size, its place in the canvas and its grid step
+    int lw = 0, lh = 0, ox = 0, oy = 0, step = 0;
 };
+
+// cvResize(CV_INTER_LINEAR), 8-bit: source indices and 11-bit weights of the `dst` columns (rows = false) or rows
+// of a `src` -> `dst` resize.  Columns past the last source column take it alone (fx = 0); rows keep their fraction and clamp the
+// two indices instead.  area: the 2 x 2 mean's taps.
+void build_taps(int src, int dst, bool rows, bool area, PyrTap* out) {
+    const double scale = 1. / ((double)dst / src);
+    for (int d = 0; d < dst; ++d) {
+        PyrTap& t = out[d];
+        if (area) {
+            t.i0 = (uint16_t)std::min(2 * d, src - 1);
+            t.i1 = (uint16_t)std::min(2 * d + 1, src - 1);
+            t.c0 = t.c1 = 0;
+            continue;
+        }
+        float f = (float)((d + 0.5) * scale - 0.5);
+        int i = (int)std::floor(f);
+        f -= (float)i;
+        if (!rows) {
+            if (i < 0) { i = 0; f = 0.f; }
+            if (i >= src - 1) { i = src - 1; f = 0.f; }
+        }
+        t.i0 = (uint16_t)std::min(std::max(i, 0), src - 1);
+        t.i1 = (uint16_t)std::min(std::max(i + 1, 0), src - 1);
+        auto coef = [](float v) { return (int16_t)std::min(32767, std::max(-32768, cv_round((double)(v * 2048.f)))); };
+        t.c0 = coef(1.f - f);
+        t.c1 = coef(f);
+    }
+}
+bool resize_is_area(int sw, int sh, int dw, int dh) {
+    const double sx = 1. / ((double)dw / sw), sy = 1. / ((double)dh / sh);
+    return std::fabs(sx - 2.) < 2.220446049250313e-16 && std::fabs(sy - 2.) < 2.220446049250313e-16;
+}
 
 // Everything that depends on (cascade, frame size, parameters) only: scales, feature tables, stage records, row list.
 static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv_params* p, bool small_batch, CvPlan* pl) {
@@ -59,7 +95,10 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         if (kids != 1 || (n0.left > 0 ? n0.left : n0.right) != 1 || n1.left > 0 || n1.right > 0) tree2 = false;
     }
     pl->tree2 = tree2;
-    pl->prune = (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
+    // CV_HAAR_SCALE_IMAGE never reads doCannyPruning (tempcv.cpp:1257-1329)
+    const bool si = (p->flags & VJ_FLAG_CV_SCALE_IMAGE) != 0u;
+    pl->scale_image = si;
+    pl->prune = !si && (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
     pl->trees = trees;
     pl->is_tree = is_tree;
     pl->has_tilted = has_tilted;
@@ -76,9 +115,65 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
             }
         }
     // ---- the scale loop (tempcv.cpp:1344-1377)
-    const uint32_t stride = (uint32_t)W + 1u;
     std::vector<CvScaleHost> hs;
-    {
+    int IW = W, IH = H;   // what the integral images are computed of: the frame, or the canvas of the pyramid's levels
+    if (si) {
+        // ---- the level loop (tempcv.cpp:1268-1288; maxSize is the image)
+        double factor = 1;
+        for (int k = 0;; ++k, factor *= p->scale_factor) {
+            if (k > 65536) {
+                set_error("scale_factor %.17g gives more than 65536 pyramid levels", p->scale_factor);
+                return VJ_ERR_LIMIT;
+            }
+            CvScaleHost s;
+            s.factor = factor;
+            s.idx = k;
+            s.win_w = cv_round(c->win_w * factor);
+            s.win_h = cv_round(c->win_h * factor);
+            s.lw = cv_round(W / factor);
+            s.lh = cv_round(H / factor);
+            if (s.lw - c->win_w + 1 <= 0 || s.lh - c->win_h + 1 <= 0) break;
+            if (s.win_w > W || s.win_h > H) break;
+            if (s.win_w < p->min_w || s.win_h < p->min_h) continue;
+            // x, y = 0, ystep, ... < size - window (:1015-1020, :1079-1080)
+            s.step = factor > 2 ? 1 : 2;
+            s.end_x = (s.lw - c->win_w + s.step - 1) / s.step;
+            s.end_y = (s.lh - c->win_h + s.step - 1) / s.step;
+            if (s.end_x <= 0 || s.end_y <= 0) continue;   // (a level exactly one window wide or high: no position)
+            hs.push_back(s);
+        }
+        // One canvas per frame holds every level (levels come in decreasing size): shelves of the canvas's width, a level goes to the
+        // first shelf that has room beside what it holds, else it opens a new one below.  A rectangle sum does not depend on where the
+        // integral image starts (u32 wrap-around cancels, the u64 square sums are exact), and the four corners of a tilted rectangle
+        // give the sum of the pixels INSIDE it whatever lies beside it: neighbours need no gap.
+        struct Shelf { int y, h, used; };
+        std::vector<Shelf> shelves;
+        IW = hs.empty() ? 1 : hs[0].lw;
+        IH = 0;
+        for (CvScaleHost& s : hs) {
+            Shelf* fit = nullptr;
+            for (Shelf& sh : shelves)
+                if (sh.used + s.lw <= IW && s.lh <= sh.h) { fit = &sh; break; }
+            if (!fit) {
+                shelves.push_back(Shelf{IH, s.lh, 0});
+                IH += s.lh;
+                fit = &shelves.back();
+            }
+            s.ox = fit->used;
+            s.oy = fit->y;
+            fit->used += s.lw;
+        }
+        IH = std::max(IH, 1);
+        if (IH >= 65535 || (uint64_t)(IW + 1) * (uint64_t)(IH + 3) >= (1ull << 30)) {
+            set_error("the image pyramid (%d x %d for %zu levels) does not fit 32-bit offsets", IW, IH, hs.size());
+            return VJ_ERR_LIMIT;
+        }
+        pl->canvas_w = (uint32_t)IW;
+        pl->canvas_h = (uint32_t)IH;
+        pl->canvas_pitch = ((uint32_t)IW + 3u) & ~3u;
+    }
+    const uint32_t stride = (uint32_t)IW + 1u;
+    if (!si) {
         int n_factors = 0;
         double factor = 1;
         for (; factor * c->win_w < W - 10 && factor * c->win_h < H - 10; n_factors++, factor *= p->scale_factor) {}
@@ -162,19 +257,22 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     const size_t n_nodes = c->nodes.size();
     std::vector<CvScaleDev>& scales = pl->scales;
     scales.assign(hs.size(), CvScaleDev{});
-    std::vector<CvNodeRec> table(hs.size() * n_nodes);
+    std::vector<CvNodeRec> table((si ? std::min<size_t>(hs.size(), 1) : hs.size()) * n_nodes);   // (the levels share the table of factor 1)
     table.reserve(2 * hs.size() * n_nodes);   // tile copies of the small scales' records are appended: no reallocation, `recs` stays valid
     std::vector<UnitDev> rows;
     std::vector<int> tile_class(hs.size(), -1);
     std::vector<CvPruneDev> prune(pl->prune ? hs.size() : 0);
     bool reach_ok = true;
-    const uint32_t frame_elems = frame_elems_for(W, H);
+    const uint32_t frame_elems = frame_elems_for(IW, IH);
+    uint64_t max_reach = 0;   // furthest element a feature of this scale touches, from the window origin
+    pl->level_factor.clear();
     for (size_t k = 0; k < hs.size(); ++k) {
-        uint64_t max_reach = 0;   // furthest element a feature of this scale touches, from the window origin
-        const double scale = hs[k].factor;
+        if (!si || k == 0) max_reach = 0;
+        const double scale = si ? 1. : hs[k].factor;   // cvSetImagesForHaarClassifierCascade(.., 1.) for every level (:1321)
+        pl->level_factor.push_back(hs[k].factor);
         CvScaleDev& sd = scales[k];
         memset(&sd, 0, sizeof(sd));
-        sd.ystep = std::max(2., scale);
+        sd.ystep = si ? (double)hs[k].step : std::max(2., scale);
         // equRect (tempcv.cpp:607-611): x = y = cvRound(scale), (orig - 2) * scale rounded
         const int ex = cv_round(scale), ew = cv_round((c->win_w - 2) * scale), eh = cv_round((c->win_h - 2) * scale);
         const double weight_scale = 1. / (ew * eh);
@@ -187,10 +285,10 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         sd.q1 = sd.q0 + (uint32_t)ew;
         sd.q2 = (uint32_t)(ex + eh) * stride + (uint32_t)ex;
         sd.q3 = sd.q2 + (uint32_t)ew;
-        sd.table_first = (uint32_t)(k * n_nodes);
+        sd.table_first = si ? 0u : (uint32_t)(k * n_nodes);
         sd.scale_idx = (uint32_t)hs[k].idx;
-        CvNodeRec* recs = table.data() + k * n_nodes;
-        for (size_t t = 0; t < c->trees.size(); ++t) {
+        CvNodeRec* recs = table.data() + sd.table_first;
+        for (size_t t = 0; t < (si && k != 0 ? 0u : c->trees.size()); ++t) {
             const vj_tree_desc& td = c->trees[t];
             for (int j = 0; j < td.n_nodes; ++j) {
                 const vj_node_desc& nd = c->nodes[td.first_node + j];
@@ -253,7 +351,9 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         }
         // evaluated windows satisfy x + win_w <= W and y + win_h <= H (border rule); a feature may overshoot its
         // window by one column / row (separate rounding): the frame allocation has two zeroed slack rows for that
-        const uint64_t origin_max = (uint64_t)(H - hs[k].win_h) * stride + (uint64_t)(W - hs[k].win_w);
+        // (a level: its windows lie inside it, and it inside the canvas)
+        const uint64_t origin_max = si ? (uint64_t)(hs[k].oy + hs[k].lh - c->win_h) * stride + (uint64_t)(hs[k].ox + hs[k].lw - c->win_w)
+                                       : (uint64_t)(H - hs[k].win_h) * stride + (uint64_t)(W - hs[k].win_w);
         if (origin_max + max_reach >= (uint64_t)frame_elems) reach_ok = false;
         if (pl->prune) {
             // CV_HAAR_DO_CANNY_PRUNING (tempcv.cpp:1147-1158): the rectangle [x + ex, + ew) x [y + ey, + eh) of the scaled window, tested at
@@ -269,7 +369,8 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
             const uint64_t last = (uint64_t)cv_round((double)(sd.end_y - 1u) * sd.ystep) * stride + (uint64_t)cv_round((double)(sd.end_x - 1u) * sd.ystep);
             if (last + pr.p3 >= (uint64_t)frame_elems) reach_ok = false;
         }
-        for (uint32_t iy = 0; iy < sd.end_y; ++iy) rows.push_back(UnitDev{(uint32_t)k, iy, 0, 0});
+        for (uint32_t iy = 0; iy < sd.end_y; ++iy)
+            rows.push_back(UnitDev{(uint32_t)k, iy, si ? (uint32_t)hs[k].oy * stride + (uint32_t)hs[k].ox : 0u, 0});
 
         // ---- LDS-tile path (vj_cv_tile.hip): stump cascades with linear stages and upright features.  A tile is tw x th
         // windows (tw divides 64, so a tile row never straddles a word of the reject / visited bitmap); its footprint is
@@ -279,7 +380,9 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         // rows: a tilted rectangle's corners (y, x), (y + h, x - h), (y + w, x + w), (y + w + h, x + w - h) lie inside the window's box), a
         // tilted node's record carries that distance in its corner offsets, and the kernel's node code does not change.
         const bool tiles_tilted = has_tilted && e->cv_tiles_tilted && !is_tree;
-        if (e->cv_tiles && (!trees || (tree2 && !is_tree)) && (!is_tree || tree_prefix != 0u) && (!has_tilted || tiles_tilted) && sd.end_x < 65536u &&
+        // CV_HAAR_SCALE_IMAGE: the levels of linear cascades whose grid fills a tile run cv_tile_pass<3> (the exhaustive grid; step 1 or 2);
+        // stage trees stay on the exhaustive-grid row kernel (their tile path is built around the tree queue and the accept bitmap)
+        if (!(si && is_tree) && e->cv_tiles && (!trees || (tree2 && !is_tree)) && (!is_tree || tree_prefix != 0u) && (!has_tilted || tiles_tilted) && sd.end_x < 65536u &&
             sd.end_y < 65536u) {
             uint32_t reach_x = (uint32_t)(ex + ew), reach_y = (uint32_t)(ex + eh);
             for (size_t n = 0; n < n_nodes; ++n) {
@@ -325,8 +428,17 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
                 sd.tile_th = b_th;
                 sd.tile_pitch = b_pitch;
                 sd.tile_rows = b_rows;
-                sd.tile_table_first = (uint32_t)table.size();
                 tile_class[k] = b_cls;
+                if (si) {   // levels whose tiles have one shape share one table in that pitch: every level is the cascade at factor 1
+                    bool shared = false;
+                    for (size_t j = 0; j < k && !shared; ++j)
+                        if (scales[j].tile_th != 0u && scales[j].tile_pitch == b_pitch && scales[j].tile_rows == b_rows) {
+                            sd.tile_table_first = scales[j].tile_table_first;
+                            shared = true;
+                        }
+                    if (shared) continue;
+                }
+                sd.tile_table_first = (uint32_t)table.size();
                 table.resize(table.size() + n_nodes);   // (within the reserved capacity)
                 CvNodeRec* trec = table.data() + sd.tile_table_first;
                 for (size_t n = 0; n < n_nodes; ++n) {
@@ -376,7 +488,8 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
                 if (sd.tile_th == 0u || tile_class[k] != cls) continue;
                 lds = std::max(lds, (uint32_t)CVT_LDS_HEADER + sd.tile_pitch * sd.tile_rows * 4u * (has_tilted ? 2u : 1u));
                 for (uint32_t iy0 = 0; iy0 < sd.end_y; iy0 += sd.tile_th)
-                    for (uint32_t ix0 = 0; ix0 < sd.end_x; ix0 += sd.tile_tw) tiles.push_back(UnitDev{(uint32_t)k, ix0 | (iy0 << 16), 0, 0});
+                    for (uint32_t ix0 = 0; ix0 < sd.end_x; ix0 += sd.tile_tw)
+                        tiles.push_back(UnitDev{(uint32_t)k, ix0 | (iy0 << 16), si ? (uint32_t)hs[k].oy * stride + (uint32_t)hs[k].ox : 0u, 0});
             }
             pl->class_lds[cls] = lds;
         }
@@ -388,7 +501,9 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         if (e->cv_row_band_px > 0) {
             const double band = (double)e->cv_row_band_px;
             std::stable_sort(rows.begin(), rows.end(), [&](const UnitDev& x, const UnitDev& y) {
-                const uint32_t bx = (uint32_t)((double)x.first * scales[x.scale].ystep / band), by = (uint32_t)((double)y.first * scales[y.scale].ystep / band);
+                // (levels: bands of the canvas)
+                const uint32_t bx = (uint32_t)(((double)x.first * scales[x.scale].ystep + hs[x.scale].oy) / band),
+                               by = (uint32_t)(((double)y.first * scales[y.scale].ystep + hs[y.scale].oy) / band);
                 return bx != by ? bx < by : x.scale != y.scale ? x.scale < y.scale : x.first < y.first;
             });
         }
@@ -445,6 +560,34 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     HIP_TRY(hipMemcpy(pl->d_stages.p, stages.data(), stages.size() * sizeof(StageDev), hipMemcpyHostToDevice));
     if (!rows.empty()) HIP_TRY(hipMemcpy(pl->d_rows.p, rows.data(), rows.size() * sizeof(UnitDev), hipMemcpyHostToDevice));
     pl->n_rows = (uint32_t)rows.size();
+    if (si && !hs.empty()) {
+        // the pyramid launch's level table and taps (vj_pyramid.hip): per level its columns' taps, then its rows'
+        std::vector<PyrLevelDev> lv(hs.size());
+        size_t n_taps = 0;
+        for (const CvScaleHost& s : hs) n_taps += (size_t)s.lw + (size_t)s.lh;
+        std::vector<PyrTap> taps(n_taps);
+        uint32_t tap = 0, unit = 0;
+        for (size_t k = 0; k < hs.size(); ++k) {
+            const CvScaleHost& s = hs[k];
+            const bool area = resize_is_area(W, H, s.lw, s.lh);
+            lv[k] = PyrLevelDev{(uint32_t)s.ox, (uint32_t)s.oy, (uint32_t)s.lw, (uint32_t)s.lh, tap, tap + (uint32_t)s.lw, unit, area ? 1u : 0u};
+            build_taps(W, s.lw, false, area, taps.data() + tap);
+            build_taps(H, s.lh, true, area, taps.data() + tap + s.lw);
+            tap += (uint32_t)(s.lw + s.lh);
+            const uint64_t units = (uint64_t)((s.lw + PYR_UNIT_PX - 1) / PYR_UNIT_PX) * (uint64_t)s.lh;
+            if (unit + units > 0x7fffffffull) {
+                set_error("the image pyramid has too many work units");
+                return VJ_ERR_LIMIT;
+            }
+            unit += (uint32_t)units;
+        }
+        if ((rc = pl->d_pyr_levels.ensure(lv.size() * sizeof(PyrLevelDev)))) return rc;
+        if ((rc = pl->d_pyr_taps.ensure(taps.size() * sizeof(PyrTap)))) return rc;
+        HIP_TRY(hipMemcpy(pl->d_pyr_levels.p, lv.data(), lv.size() * sizeof(PyrLevelDev), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(pl->d_pyr_taps.p, taps.data(), taps.size() * sizeof(PyrTap), hipMemcpyHostToDevice));
+        pl->n_pyr_levels = (uint32_t)lv.size();
+        pl->n_pyr_units = unit;
+    }
     return VJ_OK;
 }
 
@@ -452,8 +595,9 @@ static int get_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv
     uint64_t sf_bits;
     memcpy(&sf_bits, &p->scale_factor, 8);
     const bool small_batch = n_frames <= 4;
-    const bool prune = (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
-    const vj_env::CvPlanKey key(c->uid, W, H, p->min_w, p->min_h, sf_bits, (small_batch ? 1 : 0) | (prune ? 2 : 0));
+    const bool si = (p->flags & VJ_FLAG_CV_SCALE_IMAGE) != 0u;
+    const bool prune = !si && (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
+    const vj_env::CvPlanKey key(c->uid, W, H, p->min_w, p->min_h, sf_bits, (small_batch ? 1 : 0) | (prune ? 2 : 0) | (si ? 4 : 0));
     auto it = e->cv_plans.find(key);
     if (it != e->cv_plans.end()) {
         it->second->last_used = ++e->plan_tick;
@@ -555,6 +699,46 @@ static int enqueue_edge_integral(vj_env* e, uint32_t pitch, int W, int H, int nf
     return VJ_OK;
 }
 
+// What stage_frames needs of ensure_image_buffers: the lane's staging buffer for `frames` frames at the device's pitch
+int ensure_gray_staging(vj_env* e, int W, int H, int frames, int channels) {
+    const size_t gstride = ((size_t)W * (size_t)channels + 3) & ~(size_t)3;
+    return e->lane0.d_gray.ensure(gstride * (size_t)H * (size_t)frames);
+}
+
+// The pyramid launch (vj_pyramid.hip): the levels `d_levels` / `d_taps` describe, of `nf` frames already on the device, into
+// e->d_pyr: canvases of pitch * ch bytes.  What no level covers is left as it is: the integral kernels read it, but no rectangle sum
+// inside a level depends on it.
+int enqueue_pyramid(vj_env* e, const uint8_t* d_gray, size_t gray_frame_bytes, int gray_stride, int W, int H, int nf, int CH,
+                    const void* d_levels, const void* d_taps, uint32_t n_levels, uint32_t n_units, uint32_t cw, uint32_t ch, uint32_t pitch) {
+    const size_t bytes = (size_t)pitch * (size_t)ch * (size_t)nf;
+    int rc;
+    if ((rc = e->d_pyr.ensure(bytes))) return rc;
+    PyrArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.gray = d_gray;
+    pa.gray_frame_bytes = gray_frame_bytes;
+    pa.gray_stride = (uint32_t)gray_stride;
+    pa.channels = (uint32_t)CH;
+    pa.width = (uint32_t)W;
+    pa.height = (uint32_t)H;
+    pa.n_frames = (uint32_t)nf;
+    pa.levels = (const PyrLevelDev*)d_levels;
+    pa.n_levels = n_levels;
+    pa.n_units = n_units;
+    pa.taps = (const PyrTap*)d_taps;
+    pa.canvas = (uint8_t*)e->d_pyr.p;
+    pa.canvas_pitch = pitch;
+    pa.canvas_w = cw;
+    pa.canvas_h = ch;
+    pa.canvas_frame_bytes = (uint64_t)pitch * (uint64_t)ch;
+    const int hrc = launch_pyramid(pa, e->stream);
+    if (hrc) {
+        set_error("pyramid launch failed: %s", hipGetErrorString((hipError_t)hrc));
+        return VJ_ERR_HIP;
+    }
+    return VJ_OK;
+}
+
 // The prune-bitmap kernels' arguments for the tile scales of this sub-batch (e->d_cv_prune_bits: the skip bitmap's size)
 static CvPruneArgs prune_args(vj_env* e, const CvPlan* pl, const CvArgs& a, int nf, unsigned long long* windows) {
     CvPruneArgs pa;
@@ -593,6 +777,43 @@ int vj_canny(vj_env* e, const vj_image* image, uint8_t* edges, int edges_stride)
     uint32_t pitch = 0;
     if ((rc = enqueue_canny(e, d_src, fb, gs, w, h, 1, ch, &pitch))) return rc;
     HIP_TRY(hipMemcpy2DAsync(edges, (size_t)edges_stride, e->d_edges.p, pitch, (size_t)w, (size_t)h, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return VJ_OK;
+}
+
+int vj_resize_linear(vj_env* e, const vj_image* image, int dst_w, int dst_h, uint8_t* dst, int dst_stride) {
+    if (!e || !image || !image->data || !dst || dst_w <= 0 || dst_h <= 0 || dst_stride < dst_w) return VJ_ERR_ARG;
+    int ch, rc;
+    if ((rc = check_single_image(image, &ch))) return rc;
+    const int w = image->width, h = image->height;
+    if (w > 65535 || h > 65535 || dst_w > 65535 || dst_h > 65535 || (uint64_t)(dst_w + 3) * (uint64_t)dst_h >= (1ull << 31)) {
+        set_error("vj_resize_linear: sizes up to 65535 x 65535 and 2^31 bytes");
+        return VJ_ERR_LIMIT;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = ensure_gray_staging(e, w, h, 1, ch))) return rc;
+    const uint8_t* d_src;
+    size_t fb;
+    int gs;
+    if ((rc = stage_frames(e, image, 1, w, h, &d_src, &fb, &gs))) return rc;
+    // one level at the canvas's origin: level record, then the columns' and the rows' taps
+    const bool area = resize_is_area(w, h, dst_w, dst_h);
+    static_assert(sizeof(PyrLevelDev) % sizeof(PyrTap) == 0, "the taps follow the level record");
+    const size_t lv_taps = sizeof(PyrLevelDev) / sizeof(PyrTap);
+    std::vector<PyrTap> tab(lv_taps + (size_t)dst_w + (size_t)dst_h);
+    const PyrLevelDev lv{0u, 0u, (uint32_t)dst_w, (uint32_t)dst_h, 0u, (uint32_t)dst_w, 0u, area ? 1u : 0u};
+    memcpy(tab.data(), &lv, sizeof(lv));
+    build_taps(w, dst_w, false, area, tab.data() + lv_taps);
+    build_taps(h, dst_h, true, area, tab.data() + lv_taps + dst_w);
+    if ((rc = e->d_pyr_tab.ensure(tab.size() * sizeof(PyrTap)))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_pyr_tab.p, tab.data(), tab.size() * sizeof(PyrTap), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));   // (`tab` is pageable and leaves scope)
+    const uint32_t pitch = ((uint32_t)dst_w + 3u) & ~3u;
+    const uint32_t units = (uint32_t)((dst_w + PYR_UNIT_PX - 1) / PYR_UNIT_PX) * (uint32_t)dst_h;
+    if ((rc = enqueue_pyramid(e, d_src, fb, gs, w, h, 1, ch, e->d_pyr_tab.p, (const PyrTap*)e->d_pyr_tab.p + lv_taps, 1u, units,
+                              (uint32_t)dst_w, (uint32_t)dst_h, pitch)))
+        return rc;
+    HIP_TRY(hipMemcpy2DAsync(dst, (size_t)dst_stride, e->d_pyr.p, pitch, (size_t)dst_w, (size_t)dst_h, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return VJ_OK;
 }
@@ -651,8 +872,11 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
     const std::vector<CvScaleDev>& scales = pl->scales;
     const StageProgram& prog = pl->prog;
     const bool trees = pl->trees, is_tree = pl->is_tree, has_tilted = pl->has_tilted;
-    const uint32_t stride = (uint32_t)W + 1u;
-    const uint32_t frame_elems = frame_elems_for(W, H);
+    // CV_HAAR_SCALE_IMAGE: the integral images are those of the canvas that holds the pyramid's levels
+    const bool si = pl->scale_image;
+    const int IW = si ? (int)pl->canvas_w : W, IH = si ? (int)pl->canvas_h : H;
+    const uint32_t stride = (uint32_t)IW + 1u;
+    const uint32_t frame_elems = frame_elems_for(IW, IH);
     DevBuf& d_det = e->d_cv_det;
     DevBuf& d_counts = e->d_cv_counts;
     // counters: stage_entered[VJ_MAX_STAGES] | visited | ... | detection count | pad | 4 x 8 tile ticket counters
@@ -678,19 +902,34 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
     std::vector<vj_rect> all;
     for (int f0 = 0, nf = 0; f0 < n_frames && pl->n_rows != 0; f0 += nf) {
         nf = std::min(max_frames, n_frames - f0);
-        if ((rc = ensure_image_buffers(e, W, H, nf, true, CH))) return rc;
+        if (si) {   // the frames' gray staging alone; the integral buffers are the canvases'
+            if ((rc = ensure_gray_staging(e, W, H, nf, CH))) return rc;
+            if ((rc = ensure_image_buffers(e, IW, IH, nf, false))) return rc;
+        } else if ((rc = ensure_image_buffers(e, W, H, nf, true, CH))) {
+            return rc;
+        }
         const uint8_t* d_gray;
         size_t gray_frame_bytes;
         int gray_stride;
+        int gray_ch = CH;
         if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
         HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
+        if (si) {   // every level of every frame; from here on the "frames" are the gray canvases
+            if ((rc = enqueue_pyramid(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH, pl->d_pyr_levels.p, pl->d_pyr_taps.p,
+                                      pl->n_pyr_levels, pl->n_pyr_units, pl->canvas_w, pl->canvas_h, pl->canvas_pitch)))
+                return rc;
+            d_gray = (const uint8_t*)e->d_pyr.p;
+            gray_frame_bytes = (size_t)pl->canvas_pitch * (size_t)IH;
+            gray_stride = (int)pl->canvas_pitch;
+            gray_ch = 1;
+        }
         if (pl->prune) {   // the edge maps and their integral
             uint32_t pitch = 0;
             if ((rc = enqueue_canny(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH, &pitch))) return rc;
             if ((rc = enqueue_edge_integral(e, pitch, W, H, nf))) return rc;
         }
-        if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
-        if (has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
+        if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, IW, IH, nf, gray_ch))) return rc;
+        if (has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, IW, IH, nf, gray_ch))) return rc;
         HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
         bool rows_only = false, done = false, resplit = false;
         for (int attempt = 0; attempt < 2; ++attempt) {
@@ -711,7 +950,7 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
             a.n_stages = pl->n_stages;
             a.frame_elems = frame_elems;
             a.stride = stride;
-            a.sum_h = (uint32_t)H + 1u;
+            a.sum_h = (uint32_t)IH + 1u;
             a.det = (CvDet*)d_det.p;
             a.det_count = (uint32_t*)((unsigned long long*)d_counts.p + 2 * VJ_MAX_STAGES);
             a.det_cap = det_cap;
@@ -884,6 +1123,60 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                     HIP_TRY(hipEventRecord(e->join_ev, e->stream2));
                     HIP_TRY(hipStreamWaitEvent(e->stream, e->join_ev, 0));
                 }
+            } else if (tiles && si) {
+                // CV_HAAR_SCALE_IMAGE: the levels whose grid fills a tile on cv_tile_pass<3> — one launch per LDS class, every grid window,
+                // no bitmap passes —, the small levels on the exhaustive-grid row kernel, concurrently on two streams as below
+                const bool two = e->concurrent && pl->n_rows_rest != 0;
+                hipStream_t sB = two ? e->stream2 : e->stream;
+                if (two) {
+                    HIP_TRY(hipEventRecord(e->fork_ev, e->stream));
+                    HIP_TRY(hipStreamWaitEvent(e->stream2, e->fork_ev, 0));
+                }
+                if (pl->n_rows_rest != 0) {
+                    CvArgs b = a;
+                    b.rows = (const UnitDev*)pl->d_rows_rest.p;
+                    b.n_rows = pl->n_rows_rest;
+                    const int nb = std::max(1, e->n_cu * (two ? pl->row_blocks : 4));
+                    b.total_waves = (uint32_t)nb * CV_WAVES_PER_BLOCK;
+                    hrc = launch_cv_profile_pass(b, trees, count, false, nb, sB, false, true);
+                }
+                CvTileArgs t;
+                memset(&t, 0, sizeof(t));
+                t.sum = a.sum;
+                t.tilted = a.tilted;
+                t.sqsum = a.sqsum;
+                t.table = a.table;
+                t.scales = a.scales;
+                t.stages = a.stages;
+                t.n_frames = (uint32_t)nf;
+                t.n_stages = pl->n_stages;
+                t.frame_elems = frame_elems;
+                t.stride = stride;
+                t.sum_h = a.sum_h;
+                t.repack_mask = ~3ull;
+                t.ws_begin = 3;
+                t.ws_max = (uint32_t)e->cv_tile_ws_max;
+                t.det = a.det;
+                t.det_count = a.det_count;
+                t.det_cap = det_cap;
+                t.stage_entered = a.stage_entered;
+                uint32_t* tickets = a.det_count + 4;
+                for (int cls = 0; cls < 2 && !hrc; ++cls) {
+                    const uint32_t n_cls = pl->class_first[cls + 1] - pl->class_first[cls];
+                    if (!n_cls) continue;
+                    CvTileArgs ta = t;
+                    ta.tiles = (const UnitDev*)pl->d_tiles.p + pl->class_first[cls];
+                    ta.n_tiles = n_cls;
+                    ta.lds_bytes = pl->class_lds[cls];
+                    ta.ticket = tickets + 8 * cls;
+                    const int per_cu = std::max(1, std::min(2, (int)((160u * 1024u - (uint32_t)pl->row_blocks * 20u * 1024u) / ta.lds_bytes)));
+                    const int tb = (int)std::min<uint64_t>((uint64_t)n_cls * (uint64_t)nf, (uint64_t)e->n_cu * (uint64_t)per_cu);
+                    hrc = launch_cv_tile_pass(ta, 3, count, pl->tree2, std::max(1, tb), e->stream);
+                }
+                if (two) {
+                    HIP_TRY(hipEventRecord(e->join_ev, e->stream2));
+                    HIP_TRY(hipStreamWaitEvent(e->stream, e->join_ev, 0));
+                }
             } else if (tiles) {
                 // The small scales on LDS tiles (vj_cv_tile.hip), the rest on cv_profile_pass, concurrently on two streams:
                 // the row kernel is bound by the texture-address unit, the tile kernel by LDS and VALU.  The row kernel is
@@ -969,7 +1262,7 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
                 // should stay inside its 4 MiB L2 (64 x 1080p: 376 / 235 / 179 / 153 / 173 / 194 / 193 ms for 1 / 2 / 3 / 4 / 5 / 6 / 8)
                 const int n_blocks = std::max(1, e->n_cu * 4);
                 a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
-                hrc = launch_cv_profile_pass(a, trees, count, is_tree, n_blocks, e->stream, pl->prune);
+                hrc = launch_cv_profile_pass(a, trees, count, is_tree, n_blocks, e->stream, pl->prune, si);
             }
             if (hrc) {
                 set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
@@ -1016,6 +1309,11 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
             std::vector<CvDet> raw(n_det);
             if (n_det) HIP_TRY(hipMemcpy(raw.data(), d_det.p, (size_t)n_det * sizeof(CvDet), hipMemcpyDeviceToHost));
             for (const CvDet& d : raw)
+                if (si)   // Rect(cvRound(x * factor), cvRound(y * factor), winSize) (tempcv.cpp:1099-1100)
+                    all.push_back(vj_rect{cv_round((double)d.x * pl->level_factor[d.slot]), cv_round((double)d.y * pl->level_factor[d.slot]),
+                                          (int32_t)scales[d.slot].win_w, (int32_t)scales[d.slot].win_h, 0.0f, f0 + (int32_t)d.frame,
+                                          (int32_t)scales[d.slot].scale_idx});
+                else
                 all.push_back(vj_rect{(int32_t)d.x, (int32_t)d.y, (int32_t)scales[d.slot].win_w, (int32_t)scales[d.slot].win_h,
                                       0.0f, f0 + (int32_t)d.frame, (int32_t)scales[d.slot].scale_idx});
             done = true;

@@ -409,7 +409,12 @@ __device__ __forceinline__ bool cv_visited(unsigned long long F, uint32_t lane, 
 // (cv_pruned: vj_devutil.hpp, shared with the prune-bitmap kernel of the tile scales, vj_canny.hip)
 // PRUNE: CV_HAAR_DO_CANNY_PRUNING.  A pruned position is a "zero" of the walk like a reject (ixstep = 2) but is not evaluated;
 // the test comes before the border rule.  PRUNE = false compiles to the kernels of flags = 0.
-template <bool TREES, bool COUNT, bool STAGE_TREE, bool PRUNE = false>
+// EXH: CV_HAAR_SCALE_IMAGE's exhaustive grid (HaarDetectObjects_ScaleImage_Invoker, tempcv.cpp:1079-1102).  A "scale" is a level of
+// the image pyramid inside the canvas (rows[r].count: element offset of its origin in the canvas's integral images), ystep is 1 or 2,
+// EVERY grid position is visited — a reject skips nothing — and the border rule cannot fire (x < level width - window width).
+// Positions and detections are in the level's own coordinates (the host scales them by the level's factor).  Per-window arithmetic:
+// the same code.  EXH = false compiles to the kernels as they were.
+template <bool TREES, bool COUNT, bool STAGE_TREE, bool PRUNE = false, bool EXH = false>
 __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArgs a) {
     __shared__ CvQEntry lds_q[CV_WAVES_PER_BLOCK * CV_QCAP];
     __shared__ unsigned long long lds_words[CV_WAVES_PER_BLOCK][2][STAGE_TREE ? CV_TREE_SEG_GROUPS : 1];   // stage trees: verdict bits of a row segment
@@ -443,6 +448,7 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
         const uint32_t frame = u / a.n_rows;
         const uint32_t r = u - frame * a.n_rows;
         const uint32_t slot = rows[r].scale, iy = rows[r].first;
+        const uint32_t org = EXH ? rows[r].count : 0u;
         const double ystep = scales[slot].ystep, inv_area = scales[slot].inv_area;
         const uint32_t win_w = scales[slot].win_w, win_h = scales[slot].win_h, end_x = scales[slot].end_x;
         const uint32_t q0 = scales[slot].q0, q1 = scales[slot].q1, q2 = scales[slot].q2, q3 = scales[slot].q3;
@@ -450,7 +456,7 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
         const rsrc_t sq_f = make_rsrc(a.sqsum + (size_t)frame * a.frame_elems, frame_bytes4 * 2u);
         const uint32_t frame_bytes = frame * frame_bytes4;
         const uint32_t y = (uint32_t)cv_round((double)iy * ystep);
-        const bool row_border = y + win_h >= a.sum_h;          // pt.y + height >= sum.height -> -1 (tempcv.cpp:817-820)
+        const bool row_border = !EXH && y + win_h >= a.sum_h;  // pt.y + height >= sum.height -> -1 (tempcv.cpp:817-820)
         uint32_t e0 = 0, e1 = 0, e2 = 0, e3 = 0;
         if (PRUNE) {
             kptr<CvPruneDev> pr = as_k(a.prune);
@@ -520,8 +526,8 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                     const uint32_t ix = ix0 + lane;
                     const bool valid = ix < end_x;
                     const uint32_t x = (uint32_t)cv_round((double)(valid ? ix : 0u) * ystep);
-                    const bool border = row_border || x + win_w >= a.stride;
-                    const uint32_t po = y * a.stride + x;
+                    const bool border = row_border || (!EXH && x + win_w >= a.stride);
+                    const uint32_t po = org + y * a.stride + x;
                     const uint32_t off = frame_bytes + po * 4u;
                     double vnf = 1.0;
                     const bool pruned = PRUNE && valid && cv_pruned(eimg, img, off, e0, e1, e2, e3);
@@ -562,7 +568,7 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                 for (uint32_t ix0 = seg0; ix0 < seg_end; ix0 += 64u) {
                     const uint32_t ix = ix0 + lane;
                     const unsigned long long F = Fw[(ix0 - seg0) >> 6], A = Aw[(ix0 - seg0) >> 6];
-                    const bool visited = cv_visited(F, lane, min(64u, end_x - ix0), carry);
+                    const bool visited = EXH ? ix < end_x : cv_visited(F, lane, min(64u, end_x - ix0), carry);
                     const bool hit = visited && ((A >> lane) & 1ull) != 0ull;
                     const unsigned long long hm = __ballot(hit);
                     if (hm != 0ull) {
@@ -581,8 +587,8 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
             const uint32_t ix = ix0 + lane;
             const bool valid = ix < end_x;
             const uint32_t x = (uint32_t)cv_round((double)(valid ? ix : 0u) * ystep);
-            const bool border = row_border || x + win_w >= a.stride;
-            const uint32_t po = y * a.stride + x;
+            const bool border = row_border || (!EXH && x + win_w >= a.stride);
+            const uint32_t po = org + y * a.stride + x;
             const uint32_t off = frame_bytes + po * 4u;
             double vnf = 1.0;
             const bool pruned = PRUNE && valid && cv_pruned(eimg, img, off, e0, e1, e2, e3);
@@ -615,7 +621,7 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                     }
                 }
                 const unsigned long long F = __ballot(ptr == -2 || pruned);
-                const bool visited = cv_visited(F, lane, n_valid, carry);
+                const bool visited = EXH ? valid : cv_visited(F, lane, n_valid, carry);
                 if (COUNT) {
                     const unsigned long long vm = __ballot(visited);
                     if (lane == 0) atomicAdd(a.stage_entered + VJ_MAX_STAGES_DEV, (unsigned long long)__popcll(vm));
@@ -639,7 +645,7 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                 fail0 = !(cv_stage_sum_mode<TREES>(img, timg, table + stages[0].first_node, stages[0].n_nodes, off, vnf, stages[0].cv_f64, a.tree2) >= thr0);
             // which positions does the sequential walk visit?  parity of the reject run below each lane
             const unsigned long long F = __ballot(fail0 || pruned);
-            const bool visited = cv_visited(F, lane, n_valid, carry);
+            const bool visited = EXH ? valid : cv_visited(F, lane, n_valid, carry);
             const bool pass0 = visited && !border && !fail0 && !pruned;
             if (COUNT) {
                 const unsigned long long vm = __ballot(visited), em = __ballot(visited && !border && !pruned);
@@ -659,15 +665,25 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
     }
 }
 
-template <bool TREES, bool STAGE_TREE, bool PRUNE = false>
+template <bool TREES, bool STAGE_TREE, bool PRUNE = false, bool EXH = false>
 static void cv_launch(const CvArgs& a, bool count, dim3 g, dim3 b, hipStream_t stream) {
-    if (count) hipLaunchKernelGGL((cv_profile_pass<TREES, true, STAGE_TREE, PRUNE>), g, b, 0, stream, a);
-    else       hipLaunchKernelGGL((cv_profile_pass<TREES, false, STAGE_TREE, PRUNE>), g, b, 0, stream, a);
+    if (count) hipLaunchKernelGGL((cv_profile_pass<TREES, true, STAGE_TREE, PRUNE, EXH>), g, b, 0, stream, a);
+    else       hipLaunchKernelGGL((cv_profile_pass<TREES, false, STAGE_TREE, PRUNE, EXH>), g, b, 0, stream, a);
 }
 
-int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream_, bool prune) {
+int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream_, bool prune, bool exhaustive) {
     hipStream_t stream = (hipStream_t)stream_;
     dim3 g(n_blocks), b(CV_WAVES_PER_BLOCK * 64);
+    if (exhaustive) {   // (never together with pruning: the scale-image branch does not read doCannyPruning)
+        if (stage_tree) {
+            if (trees) cv_launch<true, true, false, true>(a, count, g, b, stream);
+            else       cv_launch<false, true, false, true>(a, count, g, b, stream);
+        } else {
+            if (trees) cv_launch<true, false, false, true>(a, count, g, b, stream);
+            else       cv_launch<false, false, false, true>(a, count, g, b, stream);
+        }
+        return (int)hipGetLastError();
+    }
     if (prune) {
         if (stage_tree) {
             if (trees) cv_launch<true, true, true>(a, count, g, b, stream);

@@ -386,6 +386,9 @@ __device__ __forceinline__ uint32_t cvt_wave_split(const CvTileArgs& a, const ch
 // every grid window): the tree's linear prefix — a.n_stages stages, 95 % of the rejects — on every grid window of the
 // tile; a window's reject bit starts set and is cleared when it survives the prefix; the survivors go to a global queue
 // for cv_tree_walk (vj_cv_profile.hip), which sets their reject or accept bit; skip_resolve and cv_tree_emit follow.
+// MODE 3 (CV_HAAR_SCALE_IMAGE, tempcv.cpp:1079-1102): the cascade on EVERY grid window of the tile — no reject bitmap, no visited
+// bitmap, no border rule.  The tile's scale is a level of the image pyramid inside the canvas (tiles[r].count: element offset of the
+// level's origin in the canvas's integral images), ystep is 1 or 2, detections leave in the level's own coordinates.
 template <int MODE, bool COUNT, bool TREE2>
 __global__ __launch_bounds__(CVT_WAVES * 64) void cv_tile_pass(CvTileArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[];
@@ -449,7 +452,9 @@ __global__ __launch_bounds__(CVT_WAVES * 64) void cv_tile_pass(CvTileArgs a) {
         const rsrc_t sum_f = make_rsrc(a.sum + frame_off, frame_bytes4);
         const rsrc_t sq_f = make_rsrc(a.sqsum + frame_off, frame_bytes4 * 2u);
         unsigned long long* bits = a.bits + (size_t)frame * a.bits_frame_words + scales[slot].bits_base;
-        const uint32_t x0 = (uint32_t)cvt_round((double)ix0 * ystep), y0 = (uint32_t)cvt_round((double)iy0 * ystep);
+        const uint32_t org = MODE == 3 ? tiles[r].count : 0u;
+        const uint32_t org_y = MODE == 3 ? org / a.stride : 0u, org_x = MODE == 3 ? org - org_y * a.stride : 0u;
+        const uint32_t x0 = (uint32_t)cvt_round((double)ix0 * ystep) + org_x, y0 = (uint32_t)cvt_round((double)iy0 * ystep) + org_y;
 
         cvt_barrier();   // the previous tile's gathers are finished
         // stage the tile's footprint of the sum image: 16 bytes per lane straight into LDS (buffer_load ... lds); the
@@ -487,9 +492,10 @@ __global__ __launch_bounds__(CVT_WAVES * 64) void cv_tile_pass(CvTileArgs a) {
             const uint32_t ty = wib * (uint32_t)NCH + (uint32_t)k;
             const uint32_t iy = iy0 + ty, ix = ix0 + lane;
             const bool valid = lane < tw && ty < th && ix < end_x && iy < end_y;
-            const uint32_t x = (uint32_t)cvt_round((double)ix * ystep), y = (uint32_t)cvt_round((double)iy * ystep);
-            const bool border = y + win_h >= a.sum_h || x + win_w >= a.stride;   // pt + real_window_size >= sum size -> -1 (:817-820)
+            const uint32_t x = (uint32_t)cvt_round((double)ix * ystep) + org_x, y = (uint32_t)cvt_round((double)iy * ystep) + org_y;
+            const bool border = MODE != 3 && (y + win_h >= a.sum_h || x + win_w >= a.stride);   // pt + real_window_size >= sum size -> -1 (:817-820)
             bool take = valid;
+            if (MODE == 3 && COUNT) n_visited += (uint32_t)__popcll(__ballot(valid));
             if (MODE == 1 && ty < th && iy < end_y) {
                 const unsigned long long V = bits[iy * wpr + (ix0 >> 6)];   // uniform: a tile row never straddles a word
                 take = valid && ((V >> (ix & 63u)) & 1ull) != 0ull;
@@ -509,7 +515,7 @@ __global__ __launch_bounds__(CVT_WAVES * 64) void cv_tile_pass(CvTileArgs a) {
                          ld_u64(sq_f, po * 8u, q3 * 8u);
             }
         }
-        if (MODE == 1 && COUNT && lane == 0 && n_visited != 0u) atomicAdd(a.stage_entered + VJ_MAX_STAGES_DEV, (unsigned long long)n_visited);
+        if ((MODE == 1 || MODE == 3) && COUNT && lane == 0 && n_visited != 0u) atomicAdd(a.stage_entered + VJ_MAX_STAGES_DEV, (unsigned long long)n_visited);
         cvt_barrier();   // the tile is in LDS
 
         const char* img = reinterpret_cast<const char*>(lds_img);
@@ -566,7 +572,7 @@ __global__ __launch_bounds__(CVT_WAVES * 64) void cv_tile_pass(CvTileArgs a) {
                 for (uint32_t i = lane; i < nn; i += 64u) {
                     const uint32_t lo = fo[i] >> 2;
                     const uint32_t ly = lo / pitch, lx = lo - ly * pitch;
-                    if (g + i < a.det_cap) a.det[g + i] = CvDet{x0 + lx, y0 + ly, slot, frame};
+                    if (g + i < a.det_cap) a.det[g + i] = CvDet{x0 + lx - org_x, y0 + ly - org_y, slot, frame};
                 }
             };
             bool finished = false;
@@ -666,7 +672,9 @@ int prepare_cv_tile_kernels() {
     const void* fns[] = {(const void*)cv_tile_pass<0, false, false>, (const void*)cv_tile_pass<1, false, false>,
                          (const void*)cv_tile_pass<1, true, false>,  (const void*)cv_tile_pass<2, false, false>,
                          (const void*)cv_tile_pass<0, false, true>,  (const void*)cv_tile_pass<1, false, true>,
-                         (const void*)cv_tile_pass<1, true, true>};
+                         (const void*)cv_tile_pass<1, true, true>,   (const void*)cv_tile_pass<3, false, false>,
+                         (const void*)cv_tile_pass<3, true, false>,  (const void*)cv_tile_pass<3, false, true>,
+                         (const void*)cv_tile_pass<3, true, true>};
     for (const void* f : fns) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
         if (e != hipSuccess) return (int)e;
@@ -677,6 +685,16 @@ int prepare_cv_tile_kernels() {
 int launch_cv_tile_pass(const CvTileArgs& a, int mode, bool count, bool tree2, int n_blocks, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     dim3 g(n_blocks), b(CVT_WAVES * 64);
+    if (mode == 3) {   // the exhaustive grid of a pyramid level
+        if (tree2) {
+            if (count) hipLaunchKernelGGL((cv_tile_pass<3, true, true>), g, b, a.lds_bytes, stream, a);
+            else hipLaunchKernelGGL((cv_tile_pass<3, false, true>), g, b, a.lds_bytes, stream, a);
+        } else {
+            if (count) hipLaunchKernelGGL((cv_tile_pass<3, true, false>), g, b, a.lds_bytes, stream, a);
+            else hipLaunchKernelGGL((cv_tile_pass<3, false, false>), g, b, a.lds_bytes, stream, a);
+        }
+        return (int)hipGetLastError();
+    }
     if (tree2) {
         if (mode == 0) hipLaunchKernelGGL((cv_tile_pass<0, false, true>), g, b, a.lds_bytes, stream, a);
         else if (mode == 2) return (int)hipErrorInvalidValue;      // stage trees on tiles are stump cascades

@@ -406,7 +406,8 @@ struct CvArgs {
     const uint32_t* table;       // NodeRec[] (offsets in bytes, f32 weights per tempcv.cpp:700-768)
     const CvScaleDev* scales;
     const StageDev* stages;      // threshold = stage threshold - 0.0001f (tempcv.cpp:262, 419)
-    const UnitDev* rows;         // one unit per (scale, window row): {scale slot, iy}
+    const UnitDev* rows;         // one unit per (scale, window row): {scale slot, iy}; the exhaustive-grid kernels (scale-image levels): {level
+                                 // slot, iy, element offset of the level's origin in the canvas's integral images}
     uint32_t n_rows;             // per frame
     uint32_t n_frames;
     uint32_t n_stages;
@@ -429,7 +430,10 @@ struct CvArgs {
 };
 
 // launch_cv_profile_pass(..., prune): the CV_HAAR_DO_CANNY_PRUNING variants (tempcv.cpp:1147-1158)
-int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream, bool prune = false);
+// exhaustive: CV_HAAR_SCALE_IMAGE's grid (tempcv.cpp:1079-1102) — every position is evaluated, a reject skips nothing, no border rule;
+// a scale is a pyramid level in the canvas (ystep 1 or 2, positions and detections in the level's own coordinates)
+int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream, bool prune = false,
+                           bool exhaustive = false);
 
 // The profile's LDS-tile kernel (vj_cv_tile.hip): small scales of stump cascades with linear stages and upright features.
 constexpr int CVT_WAVES = 8;            // waves per workgroup
@@ -443,7 +447,8 @@ struct CvTileArgs {
     const uint32_t* table;       // CvNodeRec[] (the tile scales' records carry offsets in the tile's pitch)
     const CvScaleDev* scales;
     const StageDev* stages;      // as CvArgs::stages, plus sp_delta (order-independence bound of a stage's leaf sum)
-    const UnitDev* tiles;        // tiles of ONE frame in this launch's LDS class: {scale slot, ix0 | iy0 << 16}
+    const UnitDev* tiles;        // tiles of ONE frame in this launch's LDS class: {scale slot, ix0 | iy0 << 16}; mode 3: {level slot, ix0 | iy0 << 16,
+                                 // element offset of the level's origin in the canvas's integral images}
     uint32_t n_tiles;
     uint32_t* ticket;            // eight ticket counters of this launch (zeroed before it)
     uint32_t n_frames, n_stages, frame_elems;
@@ -474,7 +479,7 @@ struct CvTreeEntry {
     double   vnf;        // variance norm factor
 };
 int launch_cv_tile_pass(const CvTileArgs& a, int mode /* 0: reject bits of stage 0, 1: the cascade on the visited windows, 2: stage trees:
-                        the linear prefix on every grid window */, bool count, bool tree2 /* every tree: a root and one node child */, int n_blocks, void* stream);
+                        the linear prefix on every grid window, 3: CV_HAAR_SCALE_IMAGE: the cascade on every grid window of a pyramid level */, bool count, bool tree2 /* every tree: a root and one node child */, int n_blocks, void* stream);
 // Stage trees on tiles: the rest of the tree for the prefix's survivors (reject / accept bits), then — after skip_resolve — the
 // accepted windows the walk visits become detections (vj_cv_profile.hip).
 struct CvTreeArgs {
@@ -559,5 +564,38 @@ struct CvPruneArgs {
 };
 int launch_cv_prune_mark(const CvPruneArgs& a, int n_blocks, void* stream);
 int launch_cv_prune_visited(const CvPruneArgs& a, int n_blocks, void* stream);
+
+// CV_HAAR_SCALE_IMAGE (VJ_FLAG_CV_SCALE_IMAGE; vj_pyramid.hip): every level of every frame's pyramid in ONE launch, written into
+// one canvas per frame that holds all levels (shelf-packed; the integral kernels then run on the canvas as on a frame).
+// cvResize(CV_INTER_LINEAR) of 8-bit gray, DESIGN.md §4.8: coefficient tables built on the host per plan.
+struct alignas(8) PyrTap {  // one destination column or row of a level
+    uint16_t i0, i1;       // the two source columns / rows (clamped to the source)
+    int16_t  c0, c1;       // their 11-bit weights (2048 = 1.0); area levels do not read them
+};
+struct PyrLevelDev {
+    uint32_t ox, oy;       // the level's origin in the canvas
+    uint32_t w, h;         // its size
+    uint32_t xtab, ytab;   // first PyrTap of its columns / rows in PyrArgs::taps
+    uint32_t unit_first;   // first work unit (PYR_UNIT_PX pixels of one row) of this level within a frame
+    uint32_t area;         // != 0: the source is exactly 2 w x 2 h: dst = (2 x 2 sum + 2) >> 2
+};
+constexpr uint32_t PYR_UNIT_PX = 256;   // pixels per workgroup: one thread each
+struct PyrArgs {
+    const uint8_t* gray;        // batch of frames (1 / 3 / 4 channels, as IntegralArgs)
+    uint64_t gray_frame_bytes;
+    uint32_t gray_stride;
+    uint32_t channels;
+    uint32_t width, height;     // of a frame
+    uint32_t n_frames;
+    const PyrLevelDev* levels;
+    uint32_t n_levels;
+    uint32_t n_units;           // per frame
+    const PyrTap* taps;
+    uint8_t* canvas;            // [frames] x canvas_frame_bytes, rows of canvas_pitch bytes
+    uint32_t canvas_pitch;
+    uint32_t canvas_w, canvas_h;
+    uint64_t canvas_frame_bytes;
+};
+int launch_pyramid(const PyrArgs& a, void* stream);
 
 }  // namespace vj

@@ -1987,7 +1987,7 @@ void vj_env_destroy(vj_env* e) {
                       &e->d_skip_bits, &e->d_rois, &e->d_roi_units, &e->d_roi_det, &e->d_roi_tiles, &e->d_group, &e->d_cv_det, &e->d_cv_counts,
                       &e->d_cv_accept, &e->d_cv_tq, &e->d_cv_fail_rows, &e->d_cv_fail_walk, &e->d_run_table,
                       &e->d_canny_cls, &e->d_canny_label, &e->d_canny_flag, &e->d_edges, &e->d_edge_sum,
-                      &e->d_cv_prune_bits})
+                      &e->d_cv_prune_bits, &e->d_pyr, &e->d_pyr_tab})
         b->release();
     e->lane0.destroy();
     for (DevBuf& b : e->d_q) b.release();

@@ -128,9 +128,15 @@ struct CvPlan {
     int tq_split_frames = 0;          // frames per sub-batch the tree queue last split a batch to (CV_TQ_MAX; 0: never)
     uint32_t class_first[3] = {0, 0, 0}, class_lds[2] = {0, 0};
     DevBuf d_tiles, d_rows_rest, d_bit_segs;
+    // CV_HAAR_SCALE_IMAGE (VJ_FLAG_CV_SCALE_IMAGE): `scales` are the evaluated LEVELS of the image pyramid, which share ONE node
+    // table at factor 1 in the canvas's pitch; every level's place in the canvas, its taps (vj_pyramid.hip) and output factor
+    bool scale_image = false;
+    std::vector<double> level_factor;   // per scale slot: what a position of the level is multiplied by
+    uint32_t canvas_w = 0, canvas_h = 0, canvas_pitch = 0, n_pyr_levels = 0, n_pyr_units = 0;
+    DevBuf d_pyr_levels, d_pyr_taps;
     uint64_t last_used = 0;
     void release_device() {
-        for (DevBuf* b : {&d_table, &d_scales, &d_stages, &d_rows, &d_tiles, &d_rows_rest, &d_bit_segs, &d_prune}) b->release();
+        for (DevBuf* b : {&d_table, &d_scales, &d_stages, &d_rows, &d_tiles, &d_rows_rest, &d_bit_segs, &d_prune, &d_pyr_levels, &d_pyr_taps}) b->release();
     }
 };
 
@@ -324,7 +330,7 @@ struct vj_env : vj::Tunables {
     std::map<BalanceKey, Balance> balance;
     uint64_t balance_tick = 0;
     typedef std::tuple<uint64_t, int, int, int, int, uint64_t, int> CvPlanKey;   // cascade uid, W, H, min size, bits of the scale factor,
-                                                                                  // call of <= 4 frames (bit 0) | canny pruning (bit 1)
+                                                                                  // call of <= 4 frames (bit 0) | canny pruning (bit 1) | scale image (bit 2)
     std::map<CvPlanKey, std::unique_ptr<vj::CvPlan>> cv_plans;
     vj::DevBuf d_cv_det, d_cv_counts;   // vj_detect_opencv: detection list and counters
     vj::DevBuf d_cv_accept, d_cv_tq;    // ... stage trees on tiles: accept bitmap, the queue of the prefix's survivors
@@ -332,6 +338,7 @@ struct vj_env : vj::Tunables {
     // CV_HAAR_DO_CANNY_PRUNING / vj_canny (vj_canny.hip): class bytes, union-find parents, strong-root flags, the 0 / 255 edge
     // maps and their integral images (a sub-batch's worth each)
     vj::DevBuf d_canny_cls, d_canny_label, d_canny_flag, d_edges, d_edge_sum, d_cv_prune_bits;   // (+ the tile scales' prune bitmap)
+    vj::DevBuf d_pyr, d_pyr_tab;      // CV_HAAR_SCALE_IMAGE: the pyramid canvases of a sub-batch; level table + taps of vj_resize_linear
     int edge_slack_w = 0, edge_slack_h = 0, edge_slack_frames = 0;   // layout whose slack rows of d_edge_sum are known to be zero
     void* edge_slack_sum = nullptr;
     uint64_t plan_tick = 0;

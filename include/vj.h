@@ -137,6 +137,21 @@ enum {
                                        both int; s < 100 || sq < 20 prunes the window: not evaluated, and the walk skips the next
                                        position as after a reject.  counters.windows counts pruned windows, stage_entered[0] does
                                        not.  The clod-profile entry points ignore the flag.                                   */
+    VJ_FLAG_CV_SCALE_IMAGE = 1u << 7,   /* vj_detect_opencv only (OpenCV profile): cvHaarDetectObjects' CV_HAAR_SCALE_IMAGE branch
+                                       (tempcv.hpp:128; tempcv.cpp:1257-1329, invoker :989-1113).  The IMAGE is scaled, not the
+                                       cascade: for factor = 1, scale_factor, ... the frame is resized to (cvRound(W / factor),
+                                       cvRound(H / factor)) (cvResize CV_INTER_LINEAR, see vj_resize_linear), integrated, and the
+                                       cascade runs at its base size (cvSetImagesForHaarClassifierCascade with scale 1) on EVERY
+                                       position x, y = 0, ystep, ... < size - window with ystep = factor > 2 ? 1 : 2 — a reject
+                                       skips nothing, the border rule cannot fire.  A pass reports (cvRound(x * factor),
+                                       cvRound(y * factor), cvRound(win_w * factor), cvRound(win_h * factor)).  The loop ends at the
+                                       first level smaller than the window or whose scaled window exceeds the frame; levels whose
+                                       scaled window is below min_w / min_h are skipped and keep their scale_idx.
+                                       counters.windows = grid positions of all evaluated levels.  VJ_FLAG_CV_CANNY_PRUNING is
+                                       ignored under this flag (the reference never reads doCannyPruning in this branch): no edge
+                                       map is computed.  Stumps, multi-node trees, stage trees and tilted features all run (linear cascades: large levels on LDS tiles).  A
+                                       pyramid that does not fit the 32-bit offsets returns VJ_ERR_LIMIT.  The clod-profile entry
+                                       points ignore the flag.                                                                */
 };
 
 typedef struct vj_params {
@@ -245,6 +260,12 @@ int  vj_integral_tilted(vj_env* e, const struct vj_image* image, uint32_t* tilte
  * m > 0, strong m > 50, and as edges every candidate 8-connected to a strong one.  255 / 0 bytes, written to the
  * HOST buffer `edges` (edges_stride bytes per row).  Host or device input, 1 / 3 / 4 channels, any row stride.                   */
 int  vj_canny(vj_env* e, const struct vj_image* image, uint8_t* edges, int edges_stride);
+/* cvResize(gray, dst, CV_INTER_LINEAR) for 8-bit single-channel images (OpenCV 2.4.2 imgproc; what CV_HAAR_SCALE_IMAGE computes
+ * per level, tempcv.cpp:1301) on the gray image vj_grayscale returns: one level of VJ_FLAG_CV_SCALE_IMAGE's pyramid.  Fixed-point
+ * bilinear with 11-bit coefficients (cvRound((1 - f) * 2048), cvRound(f * 2048)), the 2 x 2 mean (sum + 2) >> 2 when the source is
+ * exactly twice the destination in both directions; the definition is DESIGN.md §4.8.  dst_w x dst_h bytes, written to the HOST
+ * buffer `dst` (dst_stride bytes per row).  Host or device input, 1 / 3 / 4 channels, any row stride.                            */
+int  vj_resize_linear(vj_env* e, const struct vj_image* image, int dst_w, int dst_h, uint8_t* dst, int dst_stride);
 typedef struct vj_image {
     const uint8_t* data;       /* 8-bit, interleaved channels                   */
     int32_t width, height;
@@ -286,7 +307,8 @@ typedef struct vj_launch {
     uint64_t stage_entered[VJ_MAX_STAGES];  /* VJ_FLAG_COUNTERS: windows this launch took into each stage */
 } vj_launch;
 typedef struct vj_timing {     /* HIP-event times of the last vj_detect, ms     */
-    float integral_ms;         /* the three integral launches (vj_detect_opencv with VJ_FLAG_CV_CANNY_PRUNING: and the Canny
+    float integral_ms;         /* the three integral launches (vj_detect_opencv with VJ_FLAG_CV_SCALE_IMAGE: and the pyramid
+                                  launch; with VJ_FLAG_CV_CANNY_PRUNING: and the Canny
                                   and edge-integral launches before them)                                                */
     float cascade_ms;          /* all cascade passes                            */
     float total_ms;            /* first kernel start → last kernel end          */
@@ -333,8 +355,10 @@ typedef struct vj_cv_params {
     int32_t  min_w, min_h;     /* minSize (0 = none)                              */
     double   scale_factor;     /* 1.1                                             */
     uint32_t min_neighbors;
-    uint32_t flags;            /* VJ_FLAG_COUNTERS, VJ_FLAG_CV_CANNY_PRUNING (CV_HAAR_DO_CANNY_PRUNING; the
-                                  other CV_HAAR_* flags are other paths and have no counterpart here) */
+    uint32_t flags;            /* VJ_FLAG_COUNTERS, VJ_FLAG_CV_CANNY_PRUNING (CV_HAAR_DO_CANNY_PRUNING),
+                                  VJ_FLAG_CV_SCALE_IMAGE (CV_HAAR_SCALE_IMAGE: the other branch of
+                                  cvHaarDetectObjects, described at the flag); CV_HAAR_FIND_BIGGEST_OBJECT and
+                                  CV_HAAR_DO_ROUGH_SEARCH are other paths and have no counterpart here */
 } vj_cv_params;
 void vj_cv_params_default(vj_cv_params* p);
 int  vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
