@@ -36,9 +36,12 @@ VJ_FLAG_GRID_F64 = 1 << 4      # + one of the two above: the same loop of the bl
 VJ_FLAG_TILTED_AS_UPRIGHT = 1 << 5   # clod profile: <tilted>1 rectangles count as upright ones, as in the reference (clod.cpp:448-492); else refused
 VJ_FLAG_CV_CANNY_PRUNING = 1 << 6    # OpenCV profile: CV_HAAR_DO_CANNY_PRUNING (edge map per frame, a pruning test per visited window)
 VJ_FLAG_CV_SCALE_IMAGE = 1 << 7      # OpenCV profile: CV_HAAR_SCALE_IMAGE (the image is scaled, the cascade runs at base size on every grid position)
+VJ_FLAG_CV_FIND_BIGGEST = 1 << 8     # OpenCV profile: CV_HAAR_FIND_BIGGEST_OBJECT (largest window first, one grouped object per frame, then its surroundings only)
+VJ_FLAG_CV_ROUGH_SEARCH = 1 << 9     # OpenCV profile: CV_HAAR_DO_ROUGH_SEARCH (with find-biggest: the search stops at 0.6 of the object's size, not 0.4)
 
-# cvHaarDetectObjects' flags (tempcv.hpp:127-130).  Only CV_HAAR_DO_CANNY_PRUNING stays on the scale-cascade path that
-# vj_detect_opencv implements; the other three are other paths and are refused.
+# cvHaarDetectObjects' flags (tempcv.hpp:127-130).  cvHaarDetectObjects below takes only CV_HAAR_DO_CANNY_PRUNING in its `flags`
+# argument and refuses the other three values there; their paths are reached through `vj_flags` (VJ_FLAG_CV_SCALE_IMAGE,
+# VJ_FLAG_CV_FIND_BIGGEST, VJ_FLAG_CV_ROUGH_SEARCH) or Environment.detect_opencv(flags=...).
 CV_HAAR_DO_CANNY_PRUNING = 1
 CV_HAAR_SCALE_IMAGE = 2
 CV_HAAR_FIND_BIGGEST_OBJECT = 4
@@ -528,7 +531,10 @@ class Environment:
         """vj_detect_opencv: cvHaarDetectObjects' scale-cascade path (OpenCV arithmetic profile: f64 sums, threshold
         bias, ystep = max(2, factor), skip after a stage-0 reject, border rule).  result.windows = visited positions.
         flags: VJ_FLAG_COUNTERS, VJ_FLAG_CV_CANNY_PRUNING, or VJ_FLAG_CV_SCALE_IMAGE for the CV_HAAR_SCALE_IMAGE branch (an image
-        pyramid, the cascade at base size on every grid position; result.windows = grid positions; the canny flag is ignored)."""
+        pyramid, the cascade at base size on every grid position; result.windows = grid positions; the canny flag is ignored), or
+        VJ_FLAG_CV_FIND_BIGGEST for CV_HAAR_FIND_BIGGEST_OBJECT (the scales from the largest window down, searched on the device; at
+        most one rectangle per frame with weight = neighbors and scale_idx = -1; min_neighbors 0 counts as 1; the canny and
+        scale-image flags are ignored), with VJ_FLAG_CV_ROUGH_SEARCH for CV_HAAR_DO_ROUGH_SEARCH next to it."""
         imgs, n, keep = self._images(frames, color)
         p = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
         res = _Result()
@@ -720,12 +726,13 @@ def cvHaarDetectObjects(image, cascade: Cascade, env: Environment, scale_factor:
                         flags: int = 0, min_size=(0, 0), vj_flags: int = 0) -> DetectResult:
     """The reference demo's OpenCV leg (main.cpp:145: cvHaarDetectObjects(img, cascade, storage, 1.1, ...)) as
     tempcv.cpp:1188-1456 specifies its scale-cascade path, on the device (OpenCV arithmetic profile).  `flags`:
-    0 or CV_HAAR_DO_CANNY_PRUNING; find-biggest-object and rough search are other paths and are refused.  CV_HAAR_SCALE_IMAGE in
-    `flags` is refused here too; that branch (tempcv.cpp:1257-1329) is reached with vj_flags=VJ_FLAG_CV_SCALE_IMAGE, which this
-    function forwards, or through Environment.detect_opencv(flags=VJ_FLAG_CV_SCALE_IMAGE)."""
+    0 or CV_HAAR_DO_CANNY_PRUNING.  The values CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT and CV_HAAR_DO_ROUGH_SEARCH are refused
+    in `flags` only: their paths are reached through `vj_flags`, which this function forwards — VJ_FLAG_CV_SCALE_IMAGE for the
+    scale-image branch (tempcv.cpp:1257-1329), VJ_FLAG_CV_FIND_BIGGEST (| VJ_FLAG_CV_ROUGH_SEARCH) for the find-biggest search
+    (tempcv.cpp:1353-1490) — or through Environment.detect_opencv(flags=...)."""
     if flags & ~CV_HAAR_DO_CANNY_PRUNING:
-        raise VjError(4, "cvHaarDetectObjects", "only flags 0 and CV_HAAR_DO_CANNY_PRUNING (the scale-cascade path) are implemented; "
-                      "CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT and CV_HAAR_DO_ROUGH_SEARCH are not")
+        raise VjError(4, "cvHaarDetectObjects", "only flags 0 and CV_HAAR_DO_CANNY_PRUNING (the scale-cascade path) are taken in `flags`; "
+                      "CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT and CV_HAAR_DO_ROUGH_SEARCH are reached through vj_flags")
     if flags & CV_HAAR_DO_CANNY_PRUNING:
         vj_flags |= VJ_FLAG_CV_CANNY_PRUNING
     return env.detect_opencv(cascade, image, min_size, scale_factor, min_neighbors, vj_flags)

@@ -9,6 +9,8 @@
 //                                        the arithmetic of a node sum (vj_cv_profile.hip: cv_node_sum)
 //   CV_HAAR_SCALE_IMAGE branch         tempcv.cpp:1257-1329, invoker :989-1113 (VJ_FLAG_CV_SCALE_IMAGE: the image pyramid in one canvas per
 //                                        frame, vj_pyramid.hip; ONE node table at factor 1; exhaustive-grid tile and row kernels)
+//   CV_HAAR_FIND_BIGGEST_OBJECT        tempcv.cpp:1353-1490 (VJ_FLAG_CV_FIND_BIGGEST, with VJ_FLAG_CV_ROUGH_SEARCH: the descending scale list, one round per
+//                                        scale, per-frame search state on the device; detect_biggest below, vj_cv_biggest.hip)
 // Stumps or multi-node trees, linear cascades or stage trees, upright or tilted features (tilted integral).
 // Second arithmetic profile.  OpenCV itself is not available here or on the GPU box, so
 // parity is against the oracle's restatement of the same lines (oc_detect_opencvlike): unpinned.
@@ -96,9 +98,12 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     }
     pl->tree2 = tree2;
     // CV_HAAR_SCALE_IMAGE never reads doCannyPruning (tempcv.cpp:1257-1329)
-    const bool si = (p->flags & VJ_FLAG_CV_SCALE_IMAGE) != 0u;
+    // CV_HAAR_FIND_BIGGEST_OBJECT clears both (tempcv.cpp:1227, :1254)
+    const bool fb = (p->flags & VJ_FLAG_CV_FIND_BIGGEST) != 0u;
+    const bool si = !fb && (p->flags & VJ_FLAG_CV_SCALE_IMAGE) != 0u;
+    pl->find_biggest = fb;
     pl->scale_image = si;
-    pl->prune = !si && (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
+    pl->prune = !fb && !si && (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
     pl->trees = trees;
     pl->is_tree = is_tree;
     pl->has_tilted = has_tilted;
@@ -173,7 +178,30 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         pl->canvas_pitch = ((uint32_t)IW + 3u) & ~3u;
     }
     const uint32_t stride = (uint32_t)IW + 1u;
-    if (!si) {
+    if (fb) {
+        // find-biggest (tempcv.cpp:1344-1380): the factors are counted upwards, then walked DOWN from the last one by repeated
+        // multiplication with the reciprocal — other doubles than the ascending ones in general.  The loop BREAKS at the first window
+        // below minSize, but minSize is the frame's own from its first grouped object on (:1450-1452, possibly smaller than the
+        // call's): every scale is planned, and the waves of cv_biggest_pass apply the break per frame (windows only shrink, so a
+        // frame that broke stays out).  Slot k is the k-th scale of the walk; scale_idx = n_factors - 1 - k.
+        int n_factors = 0;
+        double factor = 1;
+        for (; factor * c->win_w < W - 10 && factor * c->win_h < H - 10; n_factors++, factor *= p->scale_factor) {}
+        const double down = 1. / p->scale_factor;
+        factor *= down;
+        for (int k = 0; k < n_factors; ++k, factor *= down) {
+            const double ystep = std::max(2., factor);
+            CvScaleHost s;
+            s.factor = factor;
+            s.idx = n_factors - 1 - k;
+            s.win_w = cv_round(c->win_w * factor);
+            s.win_h = cv_round(c->win_h * factor);
+            s.end_x = cv_round((W - s.win_w) / ystep);
+            s.end_y = cv_round((H - s.win_h) / ystep);
+            if (s.end_x <= 0 || s.end_y <= 0) continue;   // (no position: nothing to walk, and no new candidate to group)
+            hs.push_back(s);
+        }
+    } else if (!si) {
         int n_factors = 0;
         double factor = 1;
         for (; factor * c->win_w < W - 10 && factor * c->win_h < H - 10; n_factors++, factor *= p->scale_factor) {}
@@ -203,7 +231,7 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     pl->tree_prefix = tree_prefix;
     // Is the rest of the tree a sequence of chains (CvChainDev)?  A chain is a run of sweep positions whose pass edges follow
     // the order and end in an accept, whose rejects all go to ONE place: nowhere (final) or the first stage of the NEXT chain.
-    if (is_tree && tree_prefix != 0u && prog.on_pass[order[tree_prefix - 1u]] == (int)order[tree_prefix]) {
+    if (!fb && is_tree && tree_prefix != 0u && prog.on_pass[order[tree_prefix - 1u]] == (int)order[tree_prefix]) {   // (find-biggest: no chain sweep)
         CvChainDev ch;
         memset(&ch, 0, sizeof(ch));
         bool ok = true;
@@ -369,7 +397,7 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
             const uint64_t last = (uint64_t)cv_round((double)(sd.end_y - 1u) * sd.ystep) * stride + (uint64_t)cv_round((double)(sd.end_x - 1u) * sd.ystep);
             if (last + pr.p3 >= (uint64_t)frame_elems) reach_ok = false;
         }
-        for (uint32_t iy = 0; iy < sd.end_y; ++iy)
+        for (uint32_t iy = 0; iy < sd.end_y && !fb; ++iy)   // (find-biggest: cv_biggest_pass lays out a scale's rows itself)
             rows.push_back(UnitDev{(uint32_t)k, iy, si ? (uint32_t)hs[k].oy * stride + (uint32_t)hs[k].ox : 0u, 0});
 
         // ---- LDS-tile path (vj_cv_tile.hip): stump cascades with linear stages and upright features.  A tile is tw x th
@@ -382,7 +410,7 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         const bool tiles_tilted = has_tilted && e->cv_tiles_tilted && !is_tree;
         // CV_HAAR_SCALE_IMAGE: the levels of linear cascades whose grid fills a tile run cv_tile_pass<3> (the exhaustive grid; step 1 or 2);
         // stage trees stay on the exhaustive-grid row kernel (their tile path is built around the tree queue and the accept bitmap)
-        if (!(si && is_tree) && e->cv_tiles && (!trees || (tree2 && !is_tree)) && (!is_tree || tree_prefix != 0u) && (!has_tilted || tiles_tilted) && sd.end_x < 65536u &&
+        if (!fb && !(si && is_tree) && e->cv_tiles && (!trees || (tree2 && !is_tree)) && (!is_tree || tree_prefix != 0u) && (!has_tilted || tiles_tilted) && sd.end_x < 65536u &&
             sd.end_y < 65536u) {
             uint32_t reach_x = (uint32_t)(ex + ew), reach_y = (uint32_t)(ex + eh);
             for (size_t n = 0; n < n_nodes; ++n) {
@@ -595,9 +623,12 @@ static int get_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv
     uint64_t sf_bits;
     memcpy(&sf_bits, &p->scale_factor, 8);
     const bool small_batch = n_frames <= 4;
-    const bool si = (p->flags & VJ_FLAG_CV_SCALE_IMAGE) != 0u;
-    const bool prune = !si && (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
-    const vj_env::CvPlanKey key(c->uid, W, H, p->min_w, p->min_h, sf_bits, (small_batch ? 1 : 0) | (prune ? 2 : 0) | (si ? 4 : 0));
+    const bool fb = (p->flags & VJ_FLAG_CV_FIND_BIGGEST) != 0u;   // (rough search changes no table: it is read per call)
+    const bool si = !fb && (p->flags & VJ_FLAG_CV_SCALE_IMAGE) != 0u;
+    const bool prune = !fb && !si && (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
+    // (a find-biggest plan depends on neither minSize — the break is the waves' — nor the batch-size class: one plan for all)
+    const vj_env::CvPlanKey key(c->uid, W, H, fb ? 0 : p->min_w, fb ? 0 : p->min_h, sf_bits,
+                                fb ? 8 : (small_batch ? 1 : 0) | (prune ? 2 : 0) | (si ? 4 : 0));
     auto it = e->cv_plans.find(key);
     if (it != e->cv_plans.end()) {
         it->second->last_used = ++e->plan_tick;
@@ -759,6 +790,191 @@ static CvPruneArgs prune_args(vj_env* e, const CvPlan* pl, const CvArgs& a, int 
     return pa;
 }
 
+
+// CV_HAAR_FIND_BIGGEST_OBJECT (VJ_FLAG_CV_FIND_BIGGEST; tempcv.cpp:1353-1490).  Per sub-batch: the integrals, then
+// one round per scale of the descending list — cv_biggest_pass and the grouping step cv_biggest_update — all enqueued up front;
+// the frames' search states live on the device and steer the kernels, the host reads nothing until the last round is done.  Then
+// step 5 on the host: a frame's candidates in the walk's order, maxRect behind the scale that found it, groupRectangles, the
+// first group of strictly greatest area.
+static int detect_biggest(vj_env* e, const vj_cascade* c, CvPlan* pl, const vj_image* frames, int n_frames, int W, int H, int CH,
+                          const vj_cv_params* p, vj_result* out) {
+    const std::vector<CvScaleDev>& scales = pl->scales;
+    const StageProgram& prog = pl->prog;
+    const uint32_t stride = (uint32_t)W + 1u;
+    const uint32_t frame_elems = frame_elems_for(W, H);
+    const bool count = (p->flags & VJ_FLAG_COUNTERS) != 0;
+    const int threshold = (int)std::max<uint32_t>(p->min_neighbors, 1u);
+    DevBuf& d_det = e->d_cv_det;
+    DevBuf& d_counts = e->d_cv_counts;
+    const size_t counts_bytes = 2 * VJ_MAX_STAGES * sizeof(uint64_t);   // stage_entered | visited
+    int rc;
+    if ((rc = d_counts.ensure(counts_bytes))) return rc;
+    const uint64_t frame_bytes = (uint64_t)frame_elems * 4u;
+    int max_frames = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_frames, 0xfffffff0ull / frame_bytes));
+    if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
+    // a frame's segment of the detection buffer: what a search may hold before its first grouped object (GROUP_MAX) and as much
+    // again for the scanROI's candidates, or the configured start ("det_cap"); a fuller frame repeats the sub-batch with more room
+    uint32_t frame_cap = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(e->det_cap_init, 2u * GROUP_MAX));
+    std::vector<vj_rect> all;
+    std::vector<unsigned long long> h(counts_bytes / 8);
+    std::vector<CvBigState> st;
+    std::vector<uint32_t> fc;
+    std::vector<CvDet> raw;
+    out->timing.n_cascade_launches = 0;
+    for (int f0 = 0, nf = 0; f0 < n_frames && !scales.empty(); f0 += nf) {
+        nf = std::min(max_frames, n_frames - f0);
+        if ((rc = ensure_image_buffers(e, W, H, nf, true, CH))) return rc;
+        const uint8_t* d_gray;
+        size_t gray_frame_bytes;
+        int gray_stride;
+        if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
+        HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
+        if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
+        if (pl->has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
+        HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
+        const size_t state_bytes = (size_t)nf * sizeof(CvBigState), big_bytes = state_bytes + (size_t)nf * sizeof(uint32_t);
+        if ((rc = e->d_cv_big.ensure(big_bytes))) return rc;
+        st.resize((size_t)nf);
+        fc.resize((size_t)nf);
+        for (;;) {
+            if ((uint64_t)frame_cap * (uint64_t)nf * sizeof(CvDet) > (1ull << 40)) {
+                set_error("vj_detect_opencv: the candidate buffer of the find-biggest search would exceed 1 TiB");
+                return VJ_ERR_LIMIT;
+            }
+            if ((rc = d_det.ensure((size_t)frame_cap * (size_t)nf * sizeof(CvDet)))) return rc;
+            HIP_TRY(hipMemsetAsync(d_counts.p, 0, counts_bytes, e->stream));
+            HIP_TRY(hipMemsetAsync(e->d_cv_big.p, 0, big_bytes, e->stream));
+            CvBigArgs b;
+            memset(&b, 0, sizeof(b));
+            CvArgs& a = b.cv;
+            a.sum = (const uint32_t*)e->d_sum.p;
+            a.sqsum = (const uint64_t*)e->d_sqsum.p;
+            a.tilted = pl->has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
+            a.n_order = pl->n_order;
+            a.table = (const uint32_t*)pl->d_table.p;
+            a.scales = (const CvScaleDev*)pl->d_scales.p;
+            a.stages = (const StageDev*)pl->d_stages.p;
+            a.n_frames = (uint32_t)nf;
+            a.n_stages = pl->n_stages;
+            a.frame_elems = frame_elems;
+            a.stride = stride;
+            a.sum_h = (uint32_t)H + 1u;
+            a.det = (CvDet*)d_det.p;
+            a.det_cap = frame_cap;
+            a.stage_entered = (unsigned long long*)d_counts.p;
+            a.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
+            a.tree2 = pl->tree2 && !pl->is_tree && !pl->has_tilted && e->cv_tree2 ? 1u : 0u;
+            b.state = (CvBigState*)e->d_cv_big.p;
+            b.frame_count = (uint32_t*)((char*)e->d_cv_big.p + state_bytes);
+            b.min_w = p->min_w;
+            b.min_h = p->min_h;
+            b.width = (uint32_t)W;
+            b.height = (uint32_t)H;
+            b.threshold = threshold;
+            b.rough = (p->flags & VJ_FLAG_CV_ROUGH_SEARCH) != 0u ? 1u : 0u;
+            b.eps = 0.2;
+            HIP_TRY(hipEventRecord(e->lane0.ev[2], e->stream));
+            int launches = 0;
+            for (size_t k = 0; k < scales.size(); ++k) {
+                b.slot = (uint32_t)k;
+                // one wave per (frame, window row) of the scale, at most four workgroups per CU (the rest by stride)
+                const uint64_t waves = (uint64_t)scales[k].end_y * (uint64_t)nf;
+                const int n_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((waves + CV_WAVES_PER_BLOCK - 1) / CV_WAVES_PER_BLOCK, (uint64_t)std::max(1, e->n_cu * 4)));
+                a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
+                // (the grouping step follows EVERY scale, the last one too, :1422-1454: a frame that first groups there still gets its
+                // maxRect pushed before step 5, which counts it among the neighbors)
+                const int hrc = launch_cv_biggest_round(b, pl->trees, count, pl->is_tree, n_blocks, true, e->stream);
+                if (hrc) {
+                    set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
+                    return VJ_ERR_HIP;
+                }
+                launches += 2;
+            }
+            HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
+            HIP_TRY(hipMemcpyAsync(h.data(), d_counts.p, counts_bytes, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipMemcpyAsync(st.data(), b.state, state_bytes, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipMemcpyAsync(fc.data(), b.frame_count, (size_t)nf * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            uint32_t most = 0;
+            for (int f = 0; f < nf; ++f) {
+                most = std::max(most, fc[(size_t)f]);
+                if (st[(size_t)f].flags & CV_BIG_LIMIT) {
+                    set_error("vj_detect_opencv: frame %d holds %u candidates before its first grouped object; the find-biggest search groups at most %u on the device",
+                              f0 + f, fc[(size_t)f], GROUP_MAX);
+                    return VJ_ERR_LIMIT;
+                }
+            }
+            if (most > frame_cap) {   // some frame's segment overflowed: the sub-batch's rounds again with room for it
+                frame_cap = grown_cap(frame_cap, most);
+                continue;
+            }
+            float ms_i = 0, ms_c = 0, ms_t = 0;
+            HIP_TRY(hipEventElapsedTime(&ms_i, e->lane0.ev[0], e->lane0.ev[1]));
+            HIP_TRY(hipEventElapsedTime(&ms_c, e->lane0.ev[2], e->lane0.ev[3]));
+            HIP_TRY(hipEventElapsedTime(&ms_t, e->lane0.ev[0], e->lane0.ev[3]));
+            out->timing.integral_ms += ms_i;
+            out->timing.cascade_ms += ms_c;
+            out->timing.total_ms += ms_t;
+            out->timing.n_cascade_launches += launches;
+            if (count) {
+                for (size_t s = 0; s < pl->n_stages; ++s) out->counters.stage_entered[s] += h[s];
+                out->counters.windows += h[VJ_MAX_STAGES];
+            }
+            break;
+        }
+        // ---- step 5 (tempcv.cpp:1458-1490), frame by frame
+        // (one strided copy of the head of every segment, as long as the fullest frame's list — not the whole segments; none at all
+        // when no frame has a candidate)
+        uint32_t most = 0;
+        for (int f = 0; f < nf; ++f) most = std::max(most, fc[(size_t)f]);   // (<= frame_cap here)
+        raw.resize((size_t)most * (size_t)nf);
+        if (most != 0u)
+            HIP_TRY(hipMemcpy2D(raw.data(), (size_t)most * sizeof(CvDet), d_det.p, (size_t)frame_cap * sizeof(CvDet), (size_t)most * sizeof(CvDet),
+                                (size_t)nf, hipMemcpyDeviceToHost));
+        for (int f = 0; f < nf; ++f) {
+            const uint32_t n = fc[(size_t)f];
+            if (n == 0u) continue;
+            CvDet* d0 = raw.data() + (size_t)f * most;
+            std::sort(d0, d0 + n, [](const CvDet& x, const CvDet& y) { return std::tie(x.slot, x.y, x.x) < std::tie(y.slot, y.y, y.x); });
+            const CvBigState& s = st[(size_t)f];
+            std::vector<vj_rect> cand;
+            cand.reserve(n + 1u);
+            bool pushed = s.phase != 1u;
+            for (uint32_t i = 0; i <= n; ++i) {
+                if (!pushed && (i == n || d0[i].slot > s.hit_slot)) {   // maxRect follows the candidates of the scale that found it
+                    cand.push_back(vj_rect{s.max_x, s.max_y, s.max_w, s.max_h, 0.0f, f0 + f, -1});
+                    pushed = true;
+                }
+                if (i < n)
+                    cand.push_back(vj_rect{(int32_t)d0[i].x, (int32_t)d0[i].y, (int32_t)scales[d0[i].slot].win_w, (int32_t)scales[d0[i].slot].win_h, 0.0f,
+                                           f0 + f, -1});
+            }
+            uint32_t m = (uint32_t)cand.size();
+            if ((rc = vj_group_rectangles(cand.data(), &m, threshold, 0.2))) return rc;
+            const vj_rect* best = nullptr;
+            for (uint32_t i = 0; i < m; ++i)
+                if ((int64_t)cand[i].w * cand[i].h > (best ? (int64_t)best->w * best->h : 0)) best = &cand[i];
+            if (best) all.push_back(*best);
+        }
+    }
+    out->count = (uint32_t)all.size();
+    if (!all.empty()) {
+        out->rects = (vj_rect*)malloc(all.size() * sizeof(vj_rect));
+        if (!out->rects) return VJ_ERR_NOMEM;
+        memcpy(out->rects, all.data(), all.size() * sizeof(vj_rect));
+    }
+    if (count) {
+        vj_counters& k = out->counters;
+        uint64_t rect_evals = 0;
+        for (size_t s = 0; s < pl->n_stages; ++s) {
+            k.stump_evals += k.stage_entered[s] * prog.n_nodes[s];
+            rect_evals += k.stage_entered[s] * prog.n_rects[s];
+        }
+        k.gather_bytes = 48ull * k.stage_entered[0] + 16ull * rect_evals;
+    }
+    return VJ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -869,6 +1085,7 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
     CvPlan* pl;
     int rc = get_cv_plan(e, c, W, H, p, n_frames, &pl);
     if (rc) return rc;
+    if (pl->find_biggest) return detect_biggest(e, c, pl, frames, n_frames, W, H, CH, p, out);
     const std::vector<CvScaleDev>& scales = pl->scales;
     const StageProgram& prog = pl->prog;
     const bool trees = pl->trees, is_tree = pl->is_tree, has_tilted = pl->has_tilted;

@@ -435,6 +435,39 @@ struct CvArgs {
 int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream, bool prune = false,
                            bool exhaustive = false);
 
+// CV_HAAR_FIND_BIGGEST_OBJECT (VJ_FLAG_CV_FIND_BIGGEST; vj_cv_biggest.hip): the scales run from the largest window
+// down, one round each, and every frame carries its own search state on the device — written by cv_biggest_update only, read by
+// the waves of cv_biggest_pass (wave-uniform: through the scalar cache).  Zeroed per call and sub-batch.
+struct CvBigState {
+    uint32_t phase;          // 0: searching (the whole grid; scanROI is empty), 1: inside scanROI, 2: stopped on a limit (`flags`)
+    uint32_t flags;          // CV_BIG_OVERFLOW: the frame's candidate segment was full when it had to be grouped; CV_BIG_LIMIT: more
+                             // than GROUP_MAX candidates before the first grouped object
+    int32_t  roi_x, roi_y, roi_w, roi_h;   // scanROI (tempcv.cpp:1442-1448)
+    int32_t  min_w, min_h;   // minSize from the hit on (:1450-1452); phase 0: the call's
+    int32_t  max_x, max_y, max_w, max_h;   // maxRect, as pushed onto the frame's candidates (:1440)
+    uint32_t hit_slot;       // the scale slot after which it was found: maxRect follows that scale's candidates in the list
+    uint32_t n_seen;         // candidates at the last grouping that found nothing (no new candidate: no new grouping)
+    uint32_t pad[2];
+};
+static_assert(sizeof(CvBigState) == 64, "CvBigState is 64 bytes");
+constexpr uint32_t CV_BIG_OVERFLOW = 1u, CV_BIG_LIMIT = 2u;
+struct CvBigArgs {
+    CvArgs cv;               // images, tables, stages, counters as for cv_profile_pass; rows / n_rows / chains / prune are not read;
+                             // det: n_frames segments of det_cap candidates each (CvDet::slot = scale slot, in walk order)
+    CvBigState* state;       // [n_frames]
+    uint32_t* frame_count;   // [n_frames] candidates of each frame (may exceed det_cap: the call is repeated with more room)
+    uint32_t slot;           // the round's scale (CvScaleDev slot; slots are in walk order: descending factor)
+    int32_t  min_w, min_h;   // the call's minSize
+    uint32_t width, height;  // of a frame
+    int32_t  threshold;      // max(minNeighbors, 1)
+    uint32_t rough;          // CV_HAAR_DO_ROUGH_SEARCH: minSize = 0.6 of the hit instead of 0.4
+    double   eps;            // GROUP_EPS = 0.2
+};
+// one round: the scale `slot` on every frame that still searches or whose scanROI takes it, then the grouping step of the frames
+// still searching (`update`); both on `stream`, in this order
+int launch_cv_biggest_round(const CvBigArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, bool update, void* stream);
+int prepare_cv_biggest_kernels();   // per device: the dynamic-LDS cap of cv_biggest_update
+
 // The profile's LDS-tile kernel (vj_cv_tile.hip): small scales of stump cascades with linear stages and upright features.
 constexpr int CVT_WAVES = 8;            // waves per workgroup
 constexpr int CVT_WAVE_CAP = 256;       // windows (queue entries) per wave: four tile rows of <= 64 windows

@@ -1969,6 +1969,10 @@ int vj_env_create(int device_index, vj_env** out) {
         set_error("raising the dynamic LDS limit on device %d failed: %s", device_index, hipGetErrorString((hipError_t)hrc));
         return VJ_ERR_HIP;
     }
+    if (const int hrc = prepare_cv_biggest_kernels()) {
+        set_error("raising the dynamic LDS limit on device %d failed: %s", device_index, hipGetErrorString((hipError_t)hrc));
+        return VJ_ERR_HIP;
+    }
     HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     { const int lrc = e->lane0.create(); if (lrc) return lrc; }
     HIP_TRY(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
@@ -1987,7 +1991,7 @@ void vj_env_destroy(vj_env* e) {
                       &e->d_skip_bits, &e->d_rois, &e->d_roi_units, &e->d_roi_det, &e->d_roi_tiles, &e->d_group, &e->d_cv_det, &e->d_cv_counts,
                       &e->d_cv_accept, &e->d_cv_tq, &e->d_cv_fail_rows, &e->d_cv_fail_walk, &e->d_run_table,
                       &e->d_canny_cls, &e->d_canny_label, &e->d_canny_flag, &e->d_edges, &e->d_edge_sum,
-                      &e->d_cv_prune_bits, &e->d_pyr, &e->d_pyr_tab})
+                      &e->d_cv_prune_bits, &e->d_pyr, &e->d_pyr_tab, &e->d_cv_big})
         b->release();
     e->lane0.destroy();
     for (DevBuf& b : e->d_q) b.release();

@@ -130,6 +130,9 @@ struct CvPlan {
     DevBuf d_tiles, d_rows_rest, d_bit_segs;
     // CV_HAAR_SCALE_IMAGE (VJ_FLAG_CV_SCALE_IMAGE): `scales` are the evaluated LEVELS of the image pyramid, which share ONE node
     // table at factor 1 in the canvas's pitch; every level's place in the canvas, its taps (vj_pyramid.hip) and output factor
+    // CV_HAAR_FIND_BIGGEST_OBJECT (VJ_FLAG_CV_FIND_BIGGEST): `scales` are the DESCENDING factors (repeated multiplication by the reciprocal),
+    // slot = position in the walk, scale_idx = n_factors - 1 - slot; every scale on cv_biggest_pass (no tiles, no pruning, no pyramid)
+    bool find_biggest = false;
     bool scale_image = false;
     std::vector<double> level_factor;   // per scale slot: what a position of the level is multiplied by
     uint32_t canvas_w = 0, canvas_h = 0, canvas_pitch = 0, n_pyr_levels = 0, n_pyr_units = 0;
@@ -330,7 +333,7 @@ struct vj_env : vj::Tunables {
     std::map<BalanceKey, Balance> balance;
     uint64_t balance_tick = 0;
     typedef std::tuple<uint64_t, int, int, int, int, uint64_t, int> CvPlanKey;   // cascade uid, W, H, min size, bits of the scale factor,
-                                                                                  // call of <= 4 frames (bit 0) | canny pruning (bit 1) | scale image (bit 2)
+                                                                                  // call of <= 4 frames (bit 0) | canny pruning (bit 1) | scale image (bit 2) | find biggest (bit 3)
     std::map<CvPlanKey, std::unique_ptr<vj::CvPlan>> cv_plans;
     vj::DevBuf d_cv_det, d_cv_counts;   // vj_detect_opencv: detection list and counters
     vj::DevBuf d_cv_accept, d_cv_tq;    // ... stage trees on tiles: accept bitmap, the queue of the prefix's survivors
@@ -339,6 +342,7 @@ struct vj_env : vj::Tunables {
     // maps and their integral images (a sub-batch's worth each)
     vj::DevBuf d_canny_cls, d_canny_label, d_canny_flag, d_edges, d_edge_sum, d_cv_prune_bits;   // (+ the tile scales' prune bitmap)
     vj::DevBuf d_pyr, d_pyr_tab;      // CV_HAAR_SCALE_IMAGE: the pyramid canvases of a sub-batch; level table + taps of vj_resize_linear
+    vj::DevBuf d_cv_big;              // CV_HAAR_FIND_BIGGEST_OBJECT: a sub-batch's search states (CvBigState), then its frames' candidate counts
     int edge_slack_w = 0, edge_slack_h = 0, edge_slack_frames = 0;   // layout whose slack rows of d_edge_sum are known to be zero
     void* edge_slack_sum = nullptr;
     uint64_t plan_tick = 0;

@@ -152,6 +152,29 @@ enum {
                                        map is computed.  Stumps, multi-node trees, stage trees and tilted features all run (linear cascades: large levels on LDS tiles).  A
                                        pyramid that does not fit the 32-bit offsets returns VJ_ERR_LIMIT.  The clod-profile entry
                                        points ignore the flag.                                                                */
+    VJ_FLAG_CV_FIND_BIGGEST = 1u << 8,  /* vj_detect_opencv only (OpenCV profile): cvHaarDetectObjects' CV_HAAR_FIND_BIGGEST_OBJECT
+                                       (tempcv.hpp:129; tempcv.cpp:1353-1490).  VJ_FLAG_CV_SCALE_IMAGE and VJ_FLAG_CV_CANNY_PRUNING
+                                       are ignored under this flag (:1227, :1254).  The factors are counted as on the plain path and
+                                       then walked DOWN from the largest by repeated multiplication with 1 / scale_factor; the loop
+                                       breaks at the first window below min_w / min_h.  After every scale a frame that has
+                                       candidates and no object yet groups all of them (groupRectangles(max(min_neighbors, 1),
+                                       0.2)); the first group of strictly greatest area becomes maxRect, is appended to the
+                                       candidates, and from then on the frame is searched only inside scanROI = maxRect widened by
+                                       cvRound(0.2 w), cvRound(0.2 h) (clamped to the frame, :1445-1448), with minSize =
+                                       cvRound(0.4 w), cvRound(0.4 h).  At the end all candidates are grouped and the first group of
+                                       strictly greatest area is the result: at most ONE vj_rect per frame, sorted by frame, weight
+                                       = its neighbors, scale_idx = -1; min_neighbors 0 counts as 1.  The search state of every
+                                       frame lives on the device and steers the kernels: one round per scale, all enqueued up
+                                       front, no host round trip in between.  counters.windows = positions the walks
+                                       visited over all evaluated scales of all frames.  vj_timing: integral_ms and cascade_ms as
+                                       always (cascade_ms covers all rounds), n_cascade_launches the true count, n_launches = 0 —
+                                       the path leaves no per-launch records: it has more launches than VJ_MAX_LAUNCHES.  A frame
+                                       that gathers more than 2048 candidates before its first grouped object returns
+                                       VJ_ERR_LIMIT.  The clod-profile entry points ignore the flag.                          */
+    VJ_FLAG_CV_ROUGH_SEARCH = 1u << 9,  /* vj_detect_opencv only (OpenCV profile): cvHaarDetectObjects' CV_HAAR_DO_ROUGH_SEARCH
+                                       (tempcv.hpp:130), read only by the find-biggest search (:1450): minSize after the first
+                                       grouped object is cvRound(0.6 w), cvRound(0.6 h) instead of 0.4.  Without
+                                       VJ_FLAG_CV_FIND_BIGGEST it changes nothing.  The clod-profile entry points ignore it.    */
 };
 
 typedef struct vj_params {
@@ -357,8 +380,9 @@ typedef struct vj_cv_params {
     uint32_t min_neighbors;
     uint32_t flags;            /* VJ_FLAG_COUNTERS, VJ_FLAG_CV_CANNY_PRUNING (CV_HAAR_DO_CANNY_PRUNING),
                                   VJ_FLAG_CV_SCALE_IMAGE (CV_HAAR_SCALE_IMAGE: the other branch of
-                                  cvHaarDetectObjects, described at the flag); CV_HAAR_FIND_BIGGEST_OBJECT and
-                                  CV_HAAR_DO_ROUGH_SEARCH are other paths and have no counterpart here */
+                                  cvHaarDetectObjects), VJ_FLAG_CV_FIND_BIGGEST (CV_HAAR_FIND_BIGGEST_OBJECT) and
+                                  VJ_FLAG_CV_ROUGH_SEARCH (CV_HAAR_DO_ROUGH_SEARCH), each described at the flag:
+                                  every flag of the function */
 } vj_cv_params;
 void vj_cv_params_default(vj_cv_params* p);
 int  vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
