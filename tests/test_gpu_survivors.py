@@ -3,7 +3,9 @@ frames let a few percent of the windows past stage 0; every device buffer is siz
 window through a prefix of stages and dot_frame() keeps the detections few, so the capacities are reached the natural way:
 the detection buffer's growth past det_cap_init (65536), the OpenCV profile's stage-tree queue escalating tq_shift 4 -> 2
 -> 0 and, at shift 0, a batch whose queue would exceed CV_TQ_MAX (2^28) entries, and vj_detect_chain's device grouping at
-GROUP_MAX (2048) candidates per frame.  Large batches repeat a few distinct frames; the oracle runs once per distinct frame."""
+GROUP_MAX (2048) candidates per frame.  Large batches repeat a few distinct frames; the oracle runs once per distinct frame.
+The OpenCV profile's linear forms and its three modes (canny pruning, scale image, find-biggest) on the same cascades and frames
+are in tests/test_gpu_cv_modes_heavy.py."""
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
