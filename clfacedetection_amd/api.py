@@ -181,6 +181,10 @@ _SIGNATURES = {
                                  C.POINTER(_Result)]),
     "vj_detect_opencv": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(CvParams),
                                    C.POINTER(_Result)]),
+    "vj_detect_opencv_rois": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(CvParams),
+                                        C.POINTER(_Result)]),
+    "vj_detect_opencv_chain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(CvParams),
+                                         C.POINTER(CvParams), C.POINTER(_Result), C.POINTER(_Result)]),
     "vj_cv_params_default": (None, [C.POINTER(CvParams)]),
     "vj_cv_plan_info_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CvParams), C.POINTER(CvPlanInfo)]),
     "vj_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params),
@@ -541,6 +545,39 @@ class Environment:
         lib = load_library()
         _check(lib.vj_detect_opencv(self._h, cascade._h, imgs, n, C.byref(p), C.byref(res)), "vj_detect_opencv")
         return self._result(lib, res, cascade)
+
+    def detect_opencv_rois(self, cascade: Cascade, frames, rois, min_size=(0, 0), scale_factor: float = 1.1, min_neighbors: int = 0,
+                           flags: int = 0, color: bool = False) -> DetectResult:
+        """vj_detect_opencv_rois: `cascade` in the OpenCV profile inside `rois` = rows of (frame, x, y, w, h); the result equals
+        detect_opencv on every region as a sub-image (what cvSetImageROI gives an OpenCV caller): rects['frame'] is the region's
+        row, x / y are relative to its origin, regions are grouped one by one.  flags 0 / VJ_FLAG_COUNTERS and frames of one size:
+        the frames are integrated once and all regions run in one pass on those integral images; other flags or mixed frame
+        sizes: one detect_opencv call per region size.  Same result either way."""
+        imgs, n, keep = self._images(frames, color)
+        r = np.ascontiguousarray(np.asarray(rois, np.int32).reshape(-1, 5))
+        p = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
+        res = _Result()
+        lib = load_library()
+        _check(lib.vj_detect_opencv_rois(self._h, cascade._h, imgs, n, r.ctypes.data, len(r), C.byref(p), C.byref(res)),
+               "vj_detect_opencv_rois")
+        return self._result(lib, res, cascade)
+
+    def detect_opencv_chain(self, first: Cascade, second: Cascade, frames, min_size=(0, 0), scale_factor: float = 1.1,
+                            min_neighbors: int = 0, flags: int = 0, min_size_second=(0, 0), scale_factor_second: float = 1.1,
+                            min_neighbors_second: int = 0, flags_second: int = 0, color: bool = False):
+        """vj_detect_opencv_chain: `first` as detect_opencv runs it, then `second` inside everything it finds (its raw candidates
+        when min_neighbors == 0, else its grouped objects) as detect_opencv_rois would; with flags within VJ_FLAG_COUNTERS the
+        frames are uploaded and integrated once for both.  Returns (result_first, result_second); result_second.rects['frame']
+        indexes result_first.rects, x / y are relative to that region.  frames: numpy arrays or DeviceFrames."""
+        imgs, n, keep = self._images(frames, color)
+        p1 = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
+        p2 = CvParams(int(min_size_second[0]), int(min_size_second[1]), float(scale_factor_second), int(min_neighbors_second),
+                      int(flags_second))
+        r1, r2 = _Result(), _Result()
+        lib = load_library()
+        _check(lib.vj_detect_opencv_chain(self._h, first._h, second._h, imgs, n, C.byref(p1), C.byref(p2), C.byref(r1), C.byref(r2)),
+               "vj_detect_opencv_chain")
+        return self._result(lib, r1, first), self._result(lib, r2, second)
 
     def cv_plan_info(self, cascade: Cascade, width: int, height: int, n_frames: int, min_size=(0, 0),
                      scale_factor: float = 1.1, min_neighbors: int = 0, flags: int = 0) -> CvPlanInfo:

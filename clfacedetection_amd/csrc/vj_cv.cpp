@@ -15,17 +15,17 @@
 // Second arithmetic profile.  OpenCV itself is not available here or on the GPU box, so
 // parity is against the oracle's restatement of the same lines (oc_detect_opencvlike): unpinned.
 #include "vj_env_internal.hpp"
+#include "vj_cv_roi_host.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 
 using namespace vj;
 
 namespace {
-
-inline int cv_round(double v) { return (int)std::lrint(v); }   // cvRound: round half to even
 
 struct CvScaleHost {
     double factor;
@@ -67,6 +67,137 @@ bool resize_is_area(int sw, int sh, int dw, int dh) {
     return std::fabs(sx - 2.) < 2.220446049250313e-16 && std::fabs(sy - 2.) < 2.220446049250313e-16;
 }
 
+// icvCreateHidHaarClassifierCascade's flags (tempcv.cpp:410-470) and the tree shape the kernels have a fast form for
+struct CvShape {
+    bool trees = false, is_tree = false, has_tilted = false, tree2 = false;
+    std::vector<uint8_t> two_rects;   // per stage: no node has a third rectangle (:452-457)
+};
+static CvShape cv_shape_of(const vj_cascade* c) {
+    CvShape sh;
+    for (const auto& st : c->stages) sh.is_tree |= st.next != -1;
+    for (const auto& t : c->trees)
+        if (t.n_nodes != 1) sh.trees = true;
+    for (const auto& nd : c->nodes) sh.has_tilted |= nd.tilted != 0;
+    // two-node trees (frontalface_alt2): root + one node child — the shape the tile kernel's tree path knows
+    sh.tree2 = sh.trees;
+    for (const auto& t : c->trees) {
+        if (!sh.tree2) break;
+        if (t.n_nodes != 2) { sh.tree2 = false; break; }
+        const vj_node_desc& n0 = c->nodes[t.first_node];
+        const vj_node_desc& n1 = c->nodes[t.first_node + 1];
+        const int kids = (n0.left > 0) + (n0.right > 0);
+        if (kids != 1 || (n0.left > 0 ? n0.left : n0.right) != 1 || n1.left > 0 || n1.right > 0) sh.tree2 = false;
+    }
+    sh.two_rects.assign(c->stages.size(), 1);
+    for (size_t s2 = 0; s2 < c->stages.size(); ++s2)
+        for (int t = 0; t < c->stages[s2].n_trees; ++t) {
+            const vj_tree_desc& td = c->trees[c->stages[s2].first_tree + t];
+            for (int l = 0; l < td.n_nodes; ++l) {
+                const vj_rect_desc& r2 = c->nodes[td.first_node + l].rect[2];
+                // :452-457: the third rectangle counts unless |weight| < DBL_EPSILON or it is empty
+                if (!(std::fabs((double)r2.weight) < 2.220446049250313e-16 || r2.w == 0 || r2.h == 0)) sh.two_rects[s2] = 0;
+            }
+        }
+    return sh;
+}
+
+// cvSetImagesForHaarClassifierCascade's node records for one factor (tempcv.cpp:632-768): cvRound-ed rectangles as byte offsets from the
+// window origin in a `stride`-wide integral image, f32 weights with rect 0's derived from the others (:752-767; CV_ADJUST_WEIGHTS = 0).
+// Nothing here depends on the image beyond its row step.  *max_reach: furthest element a feature touches, from the window origin.
+static int build_cv_node_recs(const vj_cascade* c, double scale, uint32_t stride, double weight_scale, CvNodeRec* recs, uint64_t* max_reach) {
+    for (size_t t = 0; t < c->trees.size(); ++t) {
+        const vj_tree_desc& td = c->trees[t];
+        for (int j = 0; j < td.n_nodes; ++j) {
+            const vj_node_desc& nd = c->nodes[td.first_node + j];
+            CvNodeRec& r = recs[td.first_node + j];
+            memset(&r, 0, sizeof(r));
+            if (nd.rect[0].weight == 0.0f || nd.rect[1].weight == 0.0f) {
+                set_error("node %d: rect 0 and rect 1 must both be weighted", td.first_node + j);
+                return VJ_ERR_UNSUPPORTED;
+            }
+            double sum0 = 0, area0 = 0;
+            const double correction_ratio = weight_scale * (!nd.tilted ? 1 : 0.5);   // :731
+            for (int q = 0; q < 3; ++q) {
+                // hidfeature->rect[k].p0 == 0 ends the list (tempcv.cpp:663): only a third rectangle can be absent (:452-455)
+                if (q == 2 && (std::fabs((double)nd.rect[2].weight) < 2.220446049250313e-16 || nd.rect[2].w == 0 || nd.rect[2].h == 0))
+                    break;
+                const int tx = cv_round(nd.rect[q].x * scale), ty = cv_round(nd.rect[q].y * scale);
+                const int tw = cv_round(nd.rect[q].w * scale), th = cv_round(nd.rect[q].h * scale);
+                // corners p0, p1 = p0 + da, p2 = p0 + db, p3 = p0 + da + db (element offsets)
+                const int64_t p0 = (int64_t)ty * stride + tx;
+                int64_t da, db;
+                if (!nd.tilted) {         // :735-741
+                    da = tw;
+                    db = (int64_t)th * stride;
+                } else {                  // :743-750: p1 = (y + h, x - h), p2 = (y + w, x + w), p3 = (y + w + h, x + w - h)
+                    da = (int64_t)th * stride - th;
+                    db = (int64_t)tw * stride + tw;
+                }
+                if (p0 < 0 || da < 0 || db < 0 || (p0 + da + db) * 4 > 0x7fffffffll) {
+                    set_error("feature offsets exceed the device record range");
+                    return VJ_ERR_LIMIT;
+                }
+                r.lt[q] = (uint32_t)(p0 * 4);
+                r.da[q] = (uint32_t)(da * 4);
+                r.db[q] = (uint32_t)(db * 4);
+                r.w[q] = (float)(nd.rect[q].weight * correction_ratio);
+                if (q == 0)
+                    area0 = tw * th;
+                else
+                    sum0 += r.w[q] * tw * th;                          // float * int * int, added to a double (:756)
+                *max_reach = std::max<uint64_t>(*max_reach, (uint64_t)(p0 + da + db));
+                *max_reach = std::max<uint64_t>(*max_reach, (uint64_t)(p0 + db));
+            }
+            r.w[0] = (float)(-sum0 / area0);
+            r.thr = nd.threshold;
+            uint32_t flags = nd.tilted ? CV_NODE_TILTED : 0u;
+            auto leaf_or_node = [&](int v, uint32_t flag, uint32_t* dst) {
+                if (v > 0) {
+                    flags |= flag;
+                    *dst = (uint32_t)v;
+                } else {
+                    const float a = c->alpha[td.first_alpha - v];
+                    memcpy(dst, &a, 4);
+                }
+            };
+            leaf_or_node(nd.left, NODE_LEFT_IS_NODE, &r.left);
+            leaf_or_node(nd.right, NODE_RIGHT_IS_NODE, &r.right);
+            if (j == td.n_nodes - 1) flags |= NODE_TREE_LAST;
+            r.flags = flags;
+        }
+    }
+    return VJ_OK;
+}
+
+// The stage records of the profile: threshold - 0.0001f, resolved successors, sweep order, the arithmetic mode of a node sum
+static std::vector<StageDev> build_cv_stage_recs(const vj_cascade* c, const StageProgram& prog, const std::vector<uint32_t>& order,
+                                                 const std::vector<uint8_t>& two_rects, bool trees, bool is_tree) {
+    std::vector<StageDev> stages(c->stages.size());
+    for (size_t s = 0; s < c->stages.size(); ++s) {
+        memset(&stages[s], 0, sizeof(StageDev));
+        stages[s].first_node = prog.first_node[s];
+        stages[s].n_nodes = prog.n_nodes[s];
+        stages[s].threshold = c->stages[s].threshold - 0.0001f;   // icv_stage_threshold_bias, in f32
+        stages[s].n_trees = (uint32_t)c->stages[s].n_trees;
+        stages[s].on_pass = prog.on_pass[s];
+        stages[s].on_fail = prog.on_fail[s];
+        stages[s].order = s < order.size() ? order[s] : 0u;
+        // an f64 product per rectangle only on cvRunHaarClassifierCascadeSum's stump path (:863-888)
+        stages[s].cv_f64 = (two_rects[s] && !trees && !is_tree) ? 1u : 0u;
+        // wave-split finish of the tile kernel: bound on the difference between any two summation orders of the stage's
+        // leaf values (the f32 form of the clod profile's bound, build_plan; the kernel scales it to f64's unit roundoff)
+        double amax = 0.0;
+        for (int t = 0; t < c->stages[s].n_trees; ++t) {
+            const vj_tree_desc& td = c->trees[c->stages[s].first_tree + t];
+            double m = 0.0;
+            for (int k = 0; k <= td.n_nodes; ++k) m = std::max(m, (double)std::fabs(c->alpha[td.first_alpha + k]));
+            amax += m;
+        }
+        stages[s].sp_delta = (float)(4.0 * (double)prog.n_nodes[s] * std::ldexp(1.0, -24) * amax * 1.001 + 1e-30);
+    }
+    return stages;
+}
+
 // Everything that depends on (cascade, frame size, parameters) only: scales, feature tables, stage records, row list.
 static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv_params* p, bool small_batch, CvPlan* pl) {
     if ((int)c->stages.size() > VJ_MAX_STAGES || c->stages.empty()) {
@@ -80,22 +211,9 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         set_error("stage links form a cycle");
         return VJ_ERR_UNSUPPORTED;
     }
-    // icvCreateHidHaarClassifierCascade's flags (tempcv.cpp:410-470)
-    bool trees = false, is_tree = false, has_tilted = false;
-    for (const auto& st : c->stages) is_tree |= st.next != -1;
-    for (const auto& t : c->trees)
-        if (t.n_nodes != 1) trees = true;
-    for (const auto& nd : c->nodes) has_tilted |= nd.tilted != 0;
-    // two-node trees (frontalface_alt2): root + one node child — the shape the tile kernel's tree path knows
-    bool tree2 = trees;
-    for (const auto& t : c->trees) {
-        if (!tree2) break;
-        if (t.n_nodes != 2) { tree2 = false; break; }
-        const vj_node_desc& n0 = c->nodes[t.first_node];
-        const vj_node_desc& n1 = c->nodes[t.first_node + 1];
-        const int kids = (n0.left > 0) + (n0.right > 0);
-        if (kids != 1 || (n0.left > 0 ? n0.left : n0.right) != 1 || n1.left > 0 || n1.right > 0) tree2 = false;
-    }
+    const CvShape shape = cv_shape_of(c);
+    const bool trees = shape.trees, is_tree = shape.is_tree, has_tilted = shape.has_tilted, tree2 = shape.tree2;
+    const std::vector<uint8_t>& two_rects = shape.two_rects;
     pl->tree2 = tree2;
     // CV_HAAR_SCALE_IMAGE never reads doCannyPruning (tempcv.cpp:1257-1329)
     // CV_HAAR_FIND_BIGGEST_OBJECT clears both (tempcv.cpp:1227, :1254)
@@ -109,16 +227,6 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     pl->has_tilted = has_tilted;
     pl->n_order = (uint32_t)order.size();
     pl->n_stages = (uint32_t)c->stages.size();
-    std::vector<uint8_t> two_rects(c->stages.size(), 1);
-    for (size_t s2 = 0; s2 < c->stages.size(); ++s2)
-        for (int t = 0; t < c->stages[s2].n_trees; ++t) {
-            const vj_tree_desc& td = c->trees[c->stages[s2].first_tree + t];
-            for (int l = 0; l < td.n_nodes; ++l) {
-                const vj_rect_desc& r2 = c->nodes[td.first_node + l].rect[2];
-                // :452-457: the third rectangle counts unless |weight| < DBL_EPSILON or it is empty
-                if (!(std::fabs((double)r2.weight) < 2.220446049250313e-16 || r2.w == 0 || r2.h == 0)) two_rects[s2] = 0;
-            }
-        }
     // ---- the scale loop (tempcv.cpp:1344-1377)
     std::vector<CvScaleHost> hs;
     int IW = W, IH = H;   // what the integral images are computed of: the frame, or the canvas of the pyramid's levels
@@ -316,66 +424,9 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         sd.table_first = si ? 0u : (uint32_t)(k * n_nodes);
         sd.scale_idx = (uint32_t)hs[k].idx;
         CvNodeRec* recs = table.data() + sd.table_first;
-        for (size_t t = 0; t < (si && k != 0 ? 0u : c->trees.size()); ++t) {
-            const vj_tree_desc& td = c->trees[t];
-            for (int j = 0; j < td.n_nodes; ++j) {
-                const vj_node_desc& nd = c->nodes[td.first_node + j];
-                CvNodeRec& r = recs[td.first_node + j];
-                memset(&r, 0, sizeof(r));
-                if (nd.rect[0].weight == 0.0f || nd.rect[1].weight == 0.0f) {
-                    set_error("node %d: rect 0 and rect 1 must both be weighted", td.first_node + j);
-                    return VJ_ERR_UNSUPPORTED;
-                }
-                double sum0 = 0, area0 = 0;
-                const double correction_ratio = weight_scale * (!nd.tilted ? 1 : 0.5);   // :731
-                for (int q = 0; q < 3; ++q) {
-                    // hidfeature->rect[k].p0 == 0 ends the list (tempcv.cpp:663): only a third rectangle can be absent (:452-455)
-                    if (q == 2 && (std::fabs((double)nd.rect[2].weight) < 2.220446049250313e-16 || nd.rect[2].w == 0 || nd.rect[2].h == 0))
-                        break;
-                    const int tx = cv_round(nd.rect[q].x * scale), ty = cv_round(nd.rect[q].y * scale);
-                    const int tw = cv_round(nd.rect[q].w * scale), th = cv_round(nd.rect[q].h * scale);
-                    // corners p0, p1 = p0 + da, p2 = p0 + db, p3 = p0 + da + db (element offsets)
-                    const int64_t p0 = (int64_t)ty * stride + tx;
-                    int64_t da, db;
-                    if (!nd.tilted) {         // :735-741
-                        da = tw;
-                        db = (int64_t)th * stride;
-                    } else {                  // :743-750: p1 = (y + h, x - h), p2 = (y + w, x + w), p3 = (y + w + h, x + w - h)
-                        da = (int64_t)th * stride - th;
-                        db = (int64_t)tw * stride + tw;
-                    }
-                    if (p0 < 0 || da < 0 || db < 0 || (p0 + da + db) * 4 > 0x7fffffffll) {
-                        set_error("feature offsets exceed the device record range");
-                        return VJ_ERR_LIMIT;
-                    }
-                    r.lt[q] = (uint32_t)(p0 * 4);
-                    r.da[q] = (uint32_t)(da * 4);
-                    r.db[q] = (uint32_t)(db * 4);
-                    r.w[q] = (float)(nd.rect[q].weight * correction_ratio);
-                    if (q == 0)
-                        area0 = tw * th;
-                    else
-                        sum0 += r.w[q] * tw * th;                          // float * int * int, added to a double (:756)
-                    max_reach = std::max<uint64_t>(max_reach, (uint64_t)(p0 + da + db));
-                    max_reach = std::max<uint64_t>(max_reach, (uint64_t)(p0 + db));
-                }
-                r.w[0] = (float)(-sum0 / area0);
-                r.thr = nd.threshold;
-                uint32_t flags = nd.tilted ? CV_NODE_TILTED : 0u;
-                auto leaf_or_node = [&](int v, uint32_t flag, uint32_t* dst) {
-                    if (v > 0) {
-                        flags |= flag;
-                        *dst = (uint32_t)v;
-                    } else {
-                        const float a = c->alpha[td.first_alpha - v];
-                        memcpy(dst, &a, 4);
-                    }
-                };
-                leaf_or_node(nd.left, NODE_LEFT_IS_NODE, &r.left);
-                leaf_or_node(nd.right, NODE_RIGHT_IS_NODE, &r.right);
-                if (j == td.n_nodes - 1) flags |= NODE_TREE_LAST;
-                r.flags = flags;
-            }
+        if (!(si && k != 0)) {
+            const int nrc = build_cv_node_recs(c, scale, stride, weight_scale, recs, &max_reach);
+            if (nrc) return nrc;
         }
         // evaluated windows satisfy x + win_w <= W and y + win_h <= H (border rule); a feature may overshoot its
         // window by one column / row (separate rounding): the frame allocation has two zeroed slack rows for that
@@ -538,29 +589,7 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         for (const UnitDev& r : rows)
             if (scales[r.scale].tile_th == 0u) rows_rest.push_back(r);
     }
-    std::vector<StageDev> stages(c->stages.size());
-    for (size_t s = 0; s < c->stages.size(); ++s) {
-        memset(&stages[s], 0, sizeof(StageDev));
-        stages[s].first_node = prog.first_node[s];
-        stages[s].n_nodes = prog.n_nodes[s];
-        stages[s].threshold = c->stages[s].threshold - 0.0001f;   // icv_stage_threshold_bias, in f32
-        stages[s].n_trees = (uint32_t)c->stages[s].n_trees;
-        stages[s].on_pass = prog.on_pass[s];
-        stages[s].on_fail = prog.on_fail[s];
-        stages[s].order = s < order.size() ? order[s] : 0u;
-        // an f64 product per rectangle only on cvRunHaarClassifierCascadeSum's stump path (:863-888)
-        stages[s].cv_f64 = (two_rects[s] && !trees && !is_tree) ? 1u : 0u;
-        // wave-split finish of the tile kernel: bound on the difference between any two summation orders of the stage's
-        // leaf values (the f32 form of the clod profile's bound, build_plan; the kernel scales it to f64's unit roundoff)
-        double amax = 0.0;
-        for (int t = 0; t < c->stages[s].n_trees; ++t) {
-            const vj_tree_desc& td = c->trees[c->stages[s].first_tree + t];
-            double m = 0.0;
-            for (int k = 0; k <= td.n_nodes; ++k) m = std::max(m, (double)std::fabs(c->alpha[td.first_alpha + k]));
-            amax += m;
-        }
-        stages[s].sp_delta = (float)(4.0 * (double)prog.n_nodes[s] * std::ldexp(1.0, -24) * amax * 1.001 + 1e-30);
-    }
+    const std::vector<StageDev> stages = build_cv_stage_recs(c, prog, order, two_rects, trees, is_tree);
     if (!reach_ok) {
         set_error("feature reach exceeds the frame allocation");
         return VJ_ERR_LIMIT;
@@ -1059,8 +1088,18 @@ int vj_cv_plan_info_get(vj_env* e, const vj_cascade* c, int width, int height, i
     return VJ_OK;
 }
 
-int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_params* p,
-                     vj_result* out) {
+}  // extern "C"
+
+namespace {
+
+// vj_detect_opencv_chain's hook into vj_detect_opencv: called after every sub-batch of frames [f0, f0 + nf) while its integral images
+// (sum, sqsum and, with need_tilted, the tilted integral) are still on the device, with the sub-batch's raw candidates (unsorted;
+// rect.frame counts from the call's first frame).
+typedef std::function<int(int f0, int nf, const vj_rect* raw, size_t n_raw)> CvSubBatchHook;
+
+// vj_detect_opencv.  need_tilted: compute the tilted integral even when `c` has no tilted feature (someone after it reads it).
+int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_params* p, vj_result* out,
+                       bool need_tilted, const CvSubBatchHook* hook) {
     if (!e || !c || !p || !out || n_frames < 0 || (n_frames > 0 && !frames)) return VJ_ERR_ARG;
     memset(out, 0, sizeof(*out));
     if (n_frames == 0) return VJ_OK;
@@ -1146,9 +1185,10 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
             if ((rc = enqueue_edge_integral(e, pitch, W, H, nf))) return rc;
         }
         if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, IW, IH, nf, gray_ch))) return rc;
-        if (has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, IW, IH, nf, gray_ch))) return rc;
+        if ((has_tilted || need_tilted) && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, IW, IH, nf, gray_ch))) return rc;
         HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
         bool rows_only = false, done = false, resplit = false;
+        const size_t sub_first = all.size();
         for (int attempt = 0; attempt < 2; ++attempt) {
             if ((rc = d_det.ensure((size_t)det_cap * sizeof(CvDet)))) return rc;
             HIP_TRY(hipMemsetAsync(d_counts.p, 0, counts_bytes, e->stream));
@@ -1544,6 +1584,7 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
             set_error("vj_detect_opencv: the detection buffer overflowed twice");
             return VJ_ERR_LIMIT;
         }
+        if (hook && (rc = (*hook)(f0, nf, all.data() + sub_first, all.size() - sub_first))) return rc;
     }
     std::sort(all.begin(), all.end(), [](const vj_rect& a, const vj_rect& b) {
         return std::tie(a.frame, a.scale_idx, a.y, a.x) < std::tie(b.frame, b.scale_idx, b.y, b.x);
@@ -1568,6 +1609,333 @@ int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int
         k.gather_bytes = 48ull * k.stage_entered[0] + 16ull * rect_evals;
     }
     return VJ_OK;
+}
+
+// ------------------------------------------------------------------------ a cascade inside regions
+// (what needs no device — argument checks, factors, the unit list, grouping by size, result shaping — is vj_cv_roi_host.cpp)
+
+// The region pass's tables for (cascade, frame width, scale factor) with at least n_factors factors.  cvSetImagesForHaarClassifierCascade
+// (tempcv.cpp:549-768) reads the image only through its row step — equRect, the rectangles and the weights come from the factor and the
+// window alone — so a factor's records serve every region of every frame of this width.
+int get_cv_roi_plan(vj_env* e, const vj_cascade* c, int W, const vj_cv_params* p, int n_factors, CvRoiPlan** out) {
+    uint64_t sf_bits;
+    memcpy(&sf_bits, &p->scale_factor, 8);
+    const vj_env::CvRoiPlanKey key(c->uid, W, sf_bits);
+    auto it = e->cv_roi_plans.find(key);
+    CvRoiPlan* pl = it != e->cv_roi_plans.end() ? it->second.get() : nullptr;
+    if (pl && (int)pl->factors.size() >= n_factors) {
+        pl->last_used = ++e->plan_tick;
+        *out = pl;
+        return VJ_OK;
+    }
+    if ((int)c->stages.size() > VJ_MAX_STAGES || c->stages.empty()) {
+        set_error("cascade has %zu stages; 1..%d are supported", c->stages.size(), VJ_MAX_STAGES);
+        return VJ_ERR_LIMIT;
+    }
+    const size_t n_nodes = c->nodes.size();
+    if ((uint64_t)n_factors * n_nodes > (1ull << 26)) {
+        set_error("scale_factor %.17g gives %d factors: the node tables would exceed 4 GiB", p->scale_factor, n_factors);
+        return VJ_ERR_LIMIT;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));   // (tables are released below)
+    std::unique_ptr<CvRoiPlan> fresh;
+    if (!pl) {
+        while (!e->cv_roi_plans.empty() && (int)e->cv_roi_plans.size() >= std::max(1, e->plan_cache_max)) {   // least recently used first
+            auto lru = e->cv_roi_plans.begin();
+            for (auto i = e->cv_roi_plans.begin(); i != e->cv_roi_plans.end(); ++i)
+                if (i->second->last_used < lru->second->last_used) lru = i;
+            lru->second->release_device();
+            e->cv_roi_plans.erase(lru);
+        }
+        fresh = std::make_unique<CvRoiPlan>();
+        pl = fresh.get();
+        pl->prog = build_stage_program(*c);
+        std::vector<uint32_t> order;
+        if (!stage_sweep_order(pl->prog, &order)) {
+            set_error("stage links form a cycle");
+            return VJ_ERR_UNSUPPORTED;
+        }
+        const CvShape shape = cv_shape_of(c);
+        pl->trees = shape.trees;
+        pl->is_tree = shape.is_tree;
+        pl->has_tilted = shape.has_tilted;
+        pl->tree2 = shape.tree2;
+        pl->n_order = (uint32_t)order.size();
+        pl->n_stages = (uint32_t)c->stages.size();
+        const std::vector<StageDev> stages = build_cv_stage_recs(c, pl->prog, order, shape.two_rects, shape.trees, shape.is_tree);
+        int rc = pl->d_stages.ensure(stages.size() * sizeof(StageDev));
+        if (!rc && hipMemcpy(pl->d_stages.p, stages.data(), stages.size() * sizeof(StageDev), hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("uploading the stage records failed");
+            rc = VJ_ERR_HIP;
+        }
+        if (rc) {
+            pl->release_device();
+            return rc;
+        }
+    }
+    // every factor again (the table is one allocation): the doubles of the enumeration, factor *= scale_factor
+    const uint32_t stride = (uint32_t)W + 1u;
+    std::vector<CvScaleDev> scales((size_t)n_factors);
+    std::vector<CvRoiFactor> factors((size_t)n_factors);
+    std::vector<CvNodeRec> table((size_t)n_factors * n_nodes);
+    double factor = 1;
+    int rc = VJ_OK;
+    for (int k = 0; k < n_factors && !rc; ++k, factor *= p->scale_factor) {
+        CvScaleDev& sd = scales[(size_t)k];
+        memset(&sd, 0, sizeof(sd));
+        CvRoiFactor& f = factors[(size_t)k];
+        f = cv_roi_factor(c->win_w, c->win_h, factor);
+        sd.ystep = f.ystep;
+        // equRect (tempcv.cpp:607-611): x = y = cvRound(scale), (orig - 2) * scale rounded
+        const int ex = cv_round(factor), ew = cv_round((c->win_w - 2) * factor), eh = cv_round((c->win_h - 2) * factor);
+        const double weight_scale = 1. / (ew * eh);
+        sd.inv_area = weight_scale;
+        sd.win_w = (uint32_t)f.win_w;
+        sd.win_h = (uint32_t)f.win_h;
+        sd.q0 = (uint32_t)ex * stride + (uint32_t)ex;
+        sd.q1 = sd.q0 + (uint32_t)ew;
+        sd.q2 = (uint32_t)(ex + eh) * stride + (uint32_t)ex;
+        sd.q3 = sd.q2 + (uint32_t)ew;
+        sd.table_first = (uint32_t)((size_t)k * n_nodes);
+        sd.scale_idx = (uint32_t)k;
+        rc = build_cv_node_recs(c, factor, stride, weight_scale, table.data() + sd.table_first, &f.max_reach);
+    }
+    if (!rc) rc = pl->d_table.ensure(std::max<size_t>(table.size(), 1) * sizeof(CvNodeRec));
+    if (!rc) rc = pl->d_scales.ensure(std::max<size_t>(scales.size(), 1) * sizeof(CvScaleDev));
+    if (!rc && !table.empty() &&
+        (hipMemcpy(pl->d_table.p, table.data(), table.size() * sizeof(CvNodeRec), hipMemcpyHostToDevice) != hipSuccess ||
+         hipMemcpy(pl->d_scales.p, scales.data(), scales.size() * sizeof(CvScaleDev), hipMemcpyHostToDevice) != hipSuccess)) {
+        set_error("uploading the region pass's tables failed");
+        rc = VJ_ERR_HIP;
+    }
+    if (rc) {   // (a plan that failed to grow is dropped: its tables may be gone)
+        pl->release_device();
+        if (!fresh) e->cv_roi_plans.erase(key);
+        return rc;
+    }
+    pl->factors = std::move(factors);
+    pl->last_used = ++e->plan_tick;
+    if (fresh) e->cv_roi_plans[key] = std::move(fresh);
+    *out = pl;
+    return VJ_OK;
+}
+
+// `second` inside `regs`, regions of the nf frames whose integral images (W x H; sum, sqsum, the tilted integral when the cascade
+// has tilted nodes) are on the device: one launch of cv_roi_pass for all of them.  Appends the raw candidates (rect.frame = the
+// region's id, x / y relative to the region) to *all, adds counters and times to *out.  *plan_out: the tables used (prog, n_stages).
+int run_cv_roi_pass(vj_env* e, const vj_cascade* c, int W, int H, int nf, const std::vector<CvRoiHost>& regs, const vj_cv_params* p,
+                    std::vector<vj_rect>* all, vj_result* out, CvRoiPlan** plan_out) {
+    const int cap = (int)((1ull << 26) / std::max<size_t>(c->nodes.size(), 1));   // (what get_cv_roi_plan's tables may hold)
+    // the tables are sized once for the frame's own last factor: no region inside it takes more, so a plan grows only when a
+    // taller frame of the same width comes, never in the middle of a batch
+    const int n_factors = cv_count_factors(c->win_w, c->win_h, W, H, p->scale_factor, cap);
+    if (n_factors == 0) return VJ_OK;   // the frame, so every region, is too small for any scale
+    CvRoiPlan* pl;
+    int rc = get_cv_roi_plan(e, c, W, p, n_factors, &pl);
+    if (rc) return rc;
+    *plan_out = pl;
+    const uint32_t stride = (uint32_t)W + 1u;
+    const uint32_t frame_elems = frame_elems_for(W, H);
+    const bool count = (p->flags & VJ_FLAG_COUNTERS) != 0;
+    std::vector<CvRoiDev> rois;
+    std::vector<CvRoiUnit> units;
+    uint64_t windows = 0;
+    if ((rc = cv_roi_build_units(regs, c->win_w, c->win_h, p->scale_factor, pl->factors, stride, frame_elems, p->min_w, p->min_h, &rois, &units,
+                                 &windows)))
+        return rc;
+    if (units.empty()) return VJ_OK;
+    if ((rc = e->d_cv_rois.ensure(rois.size() * sizeof(CvRoiDev)))) return rc;
+    if ((rc = e->d_cv_roi_units.ensure(units.size() * sizeof(CvRoiUnit)))) return rc;
+    HIP_TRY(hipMemcpy(e->d_cv_rois.p, rois.data(), rois.size() * sizeof(CvRoiDev), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_cv_roi_units.p, units.data(), units.size() * sizeof(CvRoiUnit), hipMemcpyHostToDevice));
+    DevBuf& d_det = e->d_cv_det;
+    DevBuf& d_counts = e->d_cv_counts;
+    const size_t counts_bytes = 2 * VJ_MAX_STAGES * sizeof(uint64_t) + 16;   // stage_entered | visited ... | detection count
+    if ((rc = d_counts.ensure(counts_bytes))) return rc;
+    uint32_t det_cap = 1u << 16;
+    for (int attempt = 0;; ++attempt) {
+        if (attempt == 2) {   // (cannot happen: the count of a repeated pass is the count that sized its buffer)
+            set_error("vj_detect_opencv_rois: the detection buffer overflowed twice");
+            return VJ_ERR_LIMIT;
+        }
+        if ((rc = d_det.ensure((size_t)det_cap * sizeof(CvDet)))) return rc;
+        HIP_TRY(hipMemsetAsync(d_counts.p, 0, counts_bytes, e->stream));
+        CvRoiArgs ra;
+        memset(&ra, 0, sizeof(ra));
+        CvArgs& a = ra.cv;
+        a.sum = (const uint32_t*)e->d_sum.p;
+        a.sqsum = (const uint64_t*)e->d_sqsum.p;
+        a.tilted = pl->has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
+        a.n_order = pl->n_order;
+        a.table = (const uint32_t*)pl->d_table.p;
+        a.scales = (const CvScaleDev*)pl->d_scales.p;
+        a.stages = (const StageDev*)pl->d_stages.p;
+        a.n_frames = (uint32_t)nf;
+        a.n_stages = pl->n_stages;
+        a.frame_elems = frame_elems;
+        a.stride = stride;
+        a.sum_h = (uint32_t)H + 1u;
+        a.det = (CvDet*)d_det.p;
+        a.det_count = (uint32_t*)((unsigned long long*)d_counts.p + 2 * VJ_MAX_STAGES);
+        a.det_cap = det_cap;
+        a.stage_entered = (unsigned long long*)d_counts.p;
+        a.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
+        a.tree2 = pl->tree2 && !pl->is_tree && !pl->has_tilted && e->cv_tree2 ? 1u : 0u;
+        ra.rois = (const CvRoiDev*)e->d_cv_rois.p;
+        ra.units = (const CvRoiUnit*)e->d_cv_roi_units.p;
+        ra.n_units = (uint32_t)units.size();
+        // one wave per unit, at most four workgroups (16 waves) per CU; the rest by stride
+        const int n_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((units.size() + CV_WAVES_PER_BLOCK - 1) / CV_WAVES_PER_BLOCK, (uint64_t)std::max(1, e->n_cu * 4)));
+        a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
+        HIP_TRY(hipEventRecord(e->lane0.ev[2], e->stream));
+        const int hrc = launch_cv_roi_pass(ra, pl->trees, count, pl->is_tree, n_blocks, e->stream);
+        if (hrc) {
+            set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
+            return VJ_ERR_HIP;
+        }
+        HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
+        std::vector<unsigned long long> h((counts_bytes + 7) / 8);
+        HIP_TRY(hipMemcpyAsync(h.data(), d_counts.p, counts_bytes, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const uint32_t n_det = (uint32_t)(h[2 * VJ_MAX_STAGES] & 0xffffffffull);
+        if (n_det > det_cap) {   // overflow: grow and run the pass again
+            det_cap = grown_cap(det_cap, n_det);
+            continue;
+        }
+        float ms_c = 0;
+        HIP_TRY(hipEventElapsedTime(&ms_c, e->lane0.ev[2], e->lane0.ev[3]));
+        out->timing.cascade_ms += ms_c;
+        out->timing.total_ms += ms_c;
+        out->timing.n_cascade_launches += 1;
+        if (count) {
+            for (size_t s = 0; s < pl->n_stages; ++s) out->counters.stage_entered[s] += h[s];
+            out->counters.windows += h[VJ_MAX_STAGES];
+        }
+        std::vector<CvDet> raw(n_det);
+        if (n_det) HIP_TRY(hipMemcpy(raw.data(), d_det.p, (size_t)n_det * sizeof(CvDet), hipMemcpyDeviceToHost));
+        return cv_roi_rects_of(raw.data(), raw.size(), pl->factors, regs, all);
+    }
+}
+
+const uint32_t CV_ROI_FAST_FLAGS = VJ_FLAG_COUNTERS;   // a flag word within these takes the region pass
+
+}  // namespace
+
+extern "C" {
+
+int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_params* p,
+                     vj_result* out) {
+    return detect_opencv_impl(e, c, frames, n_frames, p, out, false, nullptr);
+}
+
+int vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_roi* rois, int n_rois,
+                          const vj_cv_params* p, vj_result* out) {
+    if (!e || !c || !p || !out || n_frames < 0 || n_rois < 0 || (n_rois > 0 && (!frames || !rois))) return VJ_ERR_ARG;
+    memset(out, 0, sizeof(*out));
+    if (!(p->scale_factor > 1.0)) {
+        set_error("scale_factor must be > 1");
+        return VJ_ERR_ARG;
+    }
+    for (int i = 0; i < n_rois; ++i)
+        if (!cv_roi_inside(rois[i], frames, n_frames)) {
+            set_error("roi %d lies outside its frame", i);
+            return VJ_ERR_ARG;
+        }
+    if (n_rois == 0) return VJ_OK;
+    int W, H, CH;
+    if ((p->flags & ~CV_ROI_FAST_FLAGS) == 0u && cv_frames_uniform(frames, n_frames, &W, &H, &CH)) {
+        // ---- every region in one pass per sub-batch, on the frames' own integral images
+        HIP_TRY(hipSetDevice(e->device));
+        const std::vector<int> by_frame = cv_rois_by_frame(rois, n_rois);
+        bool has_tilted = false;
+        for (const auto& nd : c->nodes) has_tilted |= nd.tilted != 0;
+        const uint64_t frame_bytes = (uint64_t)frame_elems_for(W, H) * 4u;
+        int max_frames = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_frames, 0xfffffff0ull / frame_bytes));
+        if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
+        std::vector<vj_rect> all;
+        std::vector<CvRoiHost> regs;
+        CvRoiPlan* pl = nullptr;
+        size_t next = 0;
+        int rc;
+        for (int f0 = 0; f0 < n_frames && next < by_frame.size(); f0 += max_frames) {
+            const int nf = std::min(max_frames, n_frames - f0);
+            cv_rois_of_subbatch(rois, by_frame, &next, f0, nf, &regs);
+            if (regs.empty()) continue;   // (a sub-batch no region looks at is not uploaded; within one, every frame is)
+            if ((rc = ensure_image_buffers(e, W, H, nf, true, CH))) return rc;
+            const uint8_t* d_gray;
+            size_t gray_frame_bytes;
+            int gray_stride;
+            if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
+            HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
+            if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
+            if (has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
+            HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
+            if ((rc = run_cv_roi_pass(e, c, W, H, nf, regs, p, &all, out, &pl))) return rc;   // (ends in a stream synchronise)
+            HIP_TRY(hipEventSynchronize(e->lane0.ev[1]));   // (so this returns at once, also when the pass had nothing to launch)
+            float ms_i = 0;
+            HIP_TRY(hipEventElapsedTime(&ms_i, e->lane0.ev[0], e->lane0.ev[1]));
+            out->timing.integral_ms += ms_i;
+            out->timing.total_ms += ms_i;
+        }
+        return finish_cv_roi_result(all, pl ? &pl->prog : nullptr, p, out);
+    }
+    // ---- frames of differing sizes, or a flag whose result on a crop is not a crop of its result on the frame (the edge map, the
+    // resized image, the find-biggest search): one vj_detect_opencv call per region size (and channel count) on the sub-images
+    std::vector<vj_rect> all;
+    for (const CvRoiSizeGroup& g : cv_roi_size_groups(frames, rois, n_rois)) {
+        vj_result part;
+        int rc = vj_detect_opencv(e, c, g.views.data(), (int)g.views.size(), p, &part);
+        if (!rc) rc = cv_roi_take_part(part, g.idx, &all, out);
+        vj_result_free(&part);
+        if (rc) return rc;
+    }
+    return cv_roi_emit_parts(all, out);
+}
+
+int vj_detect_opencv_chain(vj_env* e, const vj_cascade* first, const vj_cascade* second, const vj_image* frames, int n_frames,
+                           const vj_cv_params* p_first, const vj_cv_params* p_second, vj_result* out_first, vj_result* out_second) {
+    if (!e || !first || !second || !p_first || !p_second || !out_first || !out_second || n_frames < 0 || (n_frames > 0 && !frames))
+        return VJ_ERR_ARG;
+    memset(out_first, 0, sizeof(*out_first));
+    memset(out_second, 0, sizeof(*out_second));
+    if (n_frames == 0) return VJ_OK;
+    if (!(p_first->scale_factor > 1.0) || !(p_second->scale_factor > 1.0)) {
+        set_error("scale_factor must be > 1");
+        return VJ_ERR_ARG;
+    }
+    if (((p_first->flags | p_second->flags) & ~CV_ROI_FAST_FLAGS) != 0u) {
+        // the two public calls back to back: what `first` finds are the regions
+        int rc = vj_detect_opencv(e, first, frames, n_frames, p_first, out_first);
+        if (rc) return rc;
+        std::vector<vj_roi> rois(out_first->count);
+        for (uint32_t i = 0; i < out_first->count; ++i) {
+            const vj_rect& r = out_first->rects[i];
+            rois[i] = vj_roi{r.frame, r.x, r.y, r.w, r.h};
+        }
+        return vj_detect_opencv_rois(e, second, frames, n_frames, rois.data(), (int)rois.size(), p_second, out_second);
+    }
+    // ---- per sub-batch: the frames' integral images once (with the tilted integral when either cascade reads it), `first` on the
+    // frames, its candidates — sorted, grouped per frame when p_first asks for it — as regions, `second` inside them
+    bool second_tilted = false;
+    for (const auto& nd : second->nodes) second_tilted |= nd.tilted != 0;
+    const int W = frames[0].width, H = frames[0].height;
+    std::vector<vj_rect> all, regions;
+    std::vector<CvRoiHost> regs;
+    CvRoiPlan* pl = nullptr;
+    const CvSubBatchHook hook = [&](int f0, int nf, const vj_rect* raw, size_t n_raw) -> int {
+        const int hrc = cv_chain_regions(raw, n_raw, p_first->min_neighbors, W, H, f0, nf, &regs, &regions);
+        if (hrc) return hrc;
+        if (regs.empty()) return VJ_OK;
+        return run_cv_roi_pass(e, second, W, H, nf, regs, p_second, &all, out_second, &pl);
+    };
+    int rc = detect_opencv_impl(e, first, frames, n_frames, p_first, out_first, second_tilted, &hook);
+    if (rc) return rc;
+    // (grouping is per frame and the sub-batches are runs of frames: the regions are out_first's rectangles, in order)
+    if (!cv_chain_regions_match(regions, *out_first)) {
+        set_error("vj_detect_opencv_chain: the regions are not the first cascade's rectangles");
+        return VJ_ERR_UNSUPPORTED;
+    }
+    return finish_cv_roi_result(all, pl ? &pl->prog : nullptr, p_second, out_second);
 }
 
 }  // extern "C"

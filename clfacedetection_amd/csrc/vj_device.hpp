@@ -3,6 +3,7 @@
 // field a wave needs is uniform across its 64 lanes.
 #pragma once
 #include <stdint.h>
+#include "vj_cv_roi_units.hpp"
 
 namespace vj {
 
@@ -358,10 +359,6 @@ __host__ __device__ inline uint64_t cv_tq_first(uint32_t tq_win_first, uint32_t 
     return (((uint64_t)tq_win_first * n_frames) >> shift) + (uint64_t)tq_slot * 4096u;
 }
 
-struct CvDet {
-    uint32_t x, y, slot, frame;
-};
-
 // Node record of the OpenCV profile (64 bytes, fetched through the scalar cache like NodeRec): corner q of
 // rectangle k sits at lt[k] + {0, da[k], db[k], da[k] + db[k]} bytes from the window origin — upright rectangles
 // da = width, db = height * stride; tilted ones (tempcv.cpp:743-750) da = height * (stride - 1), db = width *
@@ -467,6 +464,20 @@ struct CvBigArgs {
 // still searching (`update`); both on `stream`, in this order
 int launch_cv_biggest_round(const CvBigArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, bool update, void* stream);
 int prepare_cv_biggest_kernels();   // per device: the dynamic-LDS cap of cv_biggest_update
+
+// The profile's region pass (vj_detect_opencv_rois / vj_detect_opencv_chain; vj_cv_roi.hip): a cascade inside regions of
+// the frames, on the frames' own integral images.  A region is the sub-image an OpenCV caller would hand over: factors, grid ends and
+// the border rule come from its w x h.
+// CvRoiDev, CvRoiUnit (and CvDet): vj_cv_roi_units.hpp
+struct CvRoiArgs {
+    CvArgs cv;               // images, stages, counters, detections as for cv_profile_pass (CvDet::frame = the region's index in `rois`); rows /
+                             // n_rows / chains / prune are not read; scales: one record per FACTOR slot (win, equRect corners, ystep,
+                             // table_first; its end_x / end_y are not read: the grid is the region's)
+    const CvRoiDev* rois;
+    const CvRoiUnit* units;  // ordered by (frame, region, factor, row)
+    uint32_t n_units;
+};
+int launch_cv_roi_pass(const CvRoiArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream);
 
 // The profile's LDS-tile kernel (vj_cv_tile.hip): small scales of stump cascades with linear stages and upright features.
 constexpr int CVT_WAVES = 8;            // waves per workgroup

@@ -1991,7 +1991,7 @@ void vj_env_destroy(vj_env* e) {
                       &e->d_skip_bits, &e->d_rois, &e->d_roi_units, &e->d_roi_det, &e->d_roi_tiles, &e->d_group, &e->d_cv_det, &e->d_cv_counts,
                       &e->d_cv_accept, &e->d_cv_tq, &e->d_cv_fail_rows, &e->d_cv_fail_walk, &e->d_run_table,
                       &e->d_canny_cls, &e->d_canny_label, &e->d_canny_flag, &e->d_edges, &e->d_edge_sum,
-                      &e->d_cv_prune_bits, &e->d_pyr, &e->d_pyr_tab, &e->d_cv_big})
+                      &e->d_cv_prune_bits, &e->d_pyr, &e->d_pyr_tab, &e->d_cv_big, &e->d_cv_rois, &e->d_cv_roi_units})
         b->release();
     e->lane0.destroy();
     for (DevBuf& b : e->d_q) b.release();
@@ -2014,6 +2014,8 @@ static void drop_plans(vj_env* e) {
     e->plans.clear();
     for (auto& kv : e->cv_plans) kv.second->release_device();
     e->cv_plans.clear();
+    for (auto& kv : e->cv_roi_plans) kv.second->release_device();
+    e->cv_roi_plans.clear();
 }
 
 // ----------------------------------------------------------------------------------------- tunables
@@ -2292,6 +2294,8 @@ int vj_env_configure(vj_env* e, const char* key, const char* value) {
     if (k->effects & DROP_CV_PLANS) {
         for (auto& kv : e->cv_plans) kv.second->release_device();
         e->cv_plans.clear();
+        for (auto& kv : e->cv_roi_plans) kv.second->release_device();
+        e->cv_roi_plans.clear();
     }
     return VJ_OK;
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include "vj_internal.hpp"
 #include "vj_device.hpp"
+#include "vj_cv_roi_host.hpp"
 
 #include <hip/hip_runtime_api.h>
 
@@ -140,6 +141,21 @@ struct CvPlan {
     uint64_t last_used = 0;
     void release_device() {
         for (DevBuf* b : {&d_table, &d_scales, &d_stages, &d_rows, &d_tiles, &d_rows_rest, &d_bit_segs, &d_prune, &d_pyr_levels, &d_pyr_taps}) b->release();
+    }
+};
+
+// What the region pass (vj_detect_opencv_rois / _chain; vj_cv_roi.hip) derives from (cascade, frame stride, scale factor): the node
+// tables depend on the factor and the frame's stride only, never on a region's size, so ONE table per factor — up to the last
+// factor of the FRAME (no region inside it takes more) — serves every region of every call; it grows only when a taller frame of the width comes.
+struct CvRoiPlan {
+    std::vector<CvRoiFactor> factors;        // per factor slot k (scale_idx = k): window, step and feature reach
+    StageProgram prog;
+    uint32_t n_stages = 0, n_order = 0;
+    bool trees = false, is_tree = false, has_tilted = false, tree2 = false;
+    DevBuf d_table, d_scales, d_stages;
+    uint64_t last_used = 0;
+    void release_device() {
+        for (DevBuf* b : {&d_table, &d_scales, &d_stages}) b->release();
     }
 };
 
@@ -335,6 +351,9 @@ struct vj_env : vj::Tunables {
     typedef std::tuple<uint64_t, int, int, int, int, uint64_t, int> CvPlanKey;   // cascade uid, W, H, min size, bits of the scale factor,
                                                                                   // call of <= 4 frames (bit 0) | canny pruning (bit 1) | scale image (bit 2) | find biggest (bit 3)
     std::map<CvPlanKey, std::unique_ptr<vj::CvPlan>> cv_plans;
+    typedef std::tuple<uint64_t, int, uint64_t> CvRoiPlanKey;   // cascade uid, frame width (the tables' stride), bits of the scale factor
+    std::map<CvRoiPlanKey, std::unique_ptr<vj::CvRoiPlan>> cv_roi_plans;
+    vj::DevBuf d_cv_rois, d_cv_roi_units;   // region pass of the OpenCV profile: a sub-batch's regions and work units
     vj::DevBuf d_cv_det, d_cv_counts;   // vj_detect_opencv: detection list and counters
     vj::DevBuf d_cv_accept, d_cv_tq;    // ... stage trees on tiles: accept bitmap, the queue of the prefix's survivors
     vj::DevBuf d_cv_fail_rows, d_cv_fail_walk;   // ... per-wave fail lists of the chain sweeps (rows kernel / chain pass)

@@ -432,6 +432,38 @@ int  vj_detect_chain(vj_env* e, const vj_cascade* first, const vj_cascade* secon
                      int n_frames, const vj_params* p_first, const vj_params* p_second, vj_result* out_first,
                      vj_result* out_second);
 
+/* The same two in the OpenCV arithmetic profile: every cascade vj_detect_opencv runs — stumps, multi-node
+ * trees, stage trees, tilted features — as the second one.
+ *
+ * vj_detect_opencv_rois: the result equals what vj_detect_opencv returns for region i given as a sub-image of its frame,
+ * {data + y * stride + x * channels, w, h, stride, on_device, channels} — what an OpenCV caller gets from cvSetImageROI or a
+ * sub-image header: rect.frame = i, x / y relative to the region's origin, scale_idx = the factor's index in THAT call's
+ * enumeration; with min_neighbors != 0 every region is grouped on its own; counters are the sums over the regions; rectangles sorted
+ * by (frame, scale_idx, y, x).  Everything cvHaarDetectObjects derives from the image size comes from the region's w x h
+ * (tempcv.cpp:1344-1373, :817-820): the number of factors (factor * win < size - 10), endX / endY, the border rule x + win_w >= w + 1,
+ * y + win_h >= h + 1.  Regions too small for any scale contribute nothing; n_rois == 0 is VJ_OK with no rectangles; a region that
+ * is not inside its frame or has w <= 0 or h <= 0 is VJ_ERR_ARG.  Which route a call takes, by p->flags:
+ *   0, VJ_FLAG_COUNTERS         frames of one size: they are uploaded and integrated ONCE (sum, sqsum, and the tilted integral when
+ *                               the cascade has tilted nodes) and all regions of all frames run in ONE region pass on those
+ *                               integral images (a rectangle sum does not depend on where the integral image starts; a tilted
+ *                               rectangle's four corners give the sum over the same pixels in the frame's tilted integral as in the
+ *                               crop's).  Frames of differing sizes: the route below.
+ *   VJ_FLAG_CV_CANNY_PRUNING    } one vj_detect_opencv call per region size on the sub-images: the Canny map of a crop is not the
+ *   VJ_FLAG_CV_SCALE_IMAGE      } crop of the Canny map (replicated borders, hysteresis connectivity), a resized crop is not a crop
+ *   VJ_FLAG_CV_FIND_BIGGEST     } of the resized frame, and the find-biggest search keeps its state per image.
+ *   any other bit               the same route (vj_detect_opencv ignores what it does not know).
+ * The result is the same either way, by definition.                                                                              */
+int  vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_roi* rois, int n_rois,
+                           const vj_cv_params* p, vj_result* out);
+/* vj_detect_opencv_chain mirrors vj_detect_chain: out_first is what vj_detect_opencv(first, p_first) returns, and its rectangles are
+ * the regions — the raw candidates when p_first->min_neighbors == 0, the grouped objects otherwise; out_second is what
+ * vj_detect_opencv_rois(second, those regions, p_second) returns, rect.frame indexing out_first->rects.  Both flag words within
+ * VJ_FLAG_COUNTERS: the frames are uploaded and integrated once for both cascades (per sub-batch when the batch is split; with the
+ * tilted integral when either cascade has tilted nodes), and `second` runs in the region pass before the sub-batch's images are
+ * replaced; the rectangle list travels through the host in between.  Any other flag: the two public calls back to back.          */
+int  vj_detect_opencv_chain(vj_env* e, const vj_cascade* first, const vj_cascade* second, const vj_image* frames, int n_frames,
+                            const vj_cv_params* p_first, const vj_cv_params* p_second, vj_result* out_first, vj_result* out_second);
+
 /* ------------------------------------------------------------ frame streams */
 /* Video-style use (the demo's per-frame loop, main.cpp:104-125): batches of host frames are uploaded into
  * one of two device buffers by DMA on a copy stream while the kernels of the previous batch run, and the
