@@ -11,5 +11,6 @@ from .api import (  # noqa: F401
     VJ_FLAG_COUNTERS, VJ_FLAG_SIGNED_MEAN, VJ_FLAG_GRID_F64, VJ_FLAG_TILTED_AS_UPRIGHT, VJ_FLAG_SKIP_LIST, VJ_FLAG_SKIP_ROW, Cascade, DetectResult, DeviceFrames, Environment,
     FrameStream, Params, VjError,
     clifIntegral, clodDetectObjects, clodInitBuffers, clodInitEnvironment, clodReleaseBuffers,
-    clodReleaseEnvironment, cvHaarDetectObjects, default_params, group_rectangles, load_library,
+    clodReleaseEnvironment, cvHaarDetectObjects, cvHaarDetectObjectsForROC, default_params, group_rectangles,
+    group_rectangles_levels, load_library,
 )

@@ -126,6 +126,16 @@ class _Result(C.Structure):
     _fields_ = [("rects", C.c_void_p), ("count", C.c_uint32), ("counters", _Counters), ("timing", _Timing)]
 
 
+class CvRocParams(C.Structure):
+    """vj_cv_roc_params: cvHaarDetectObjectsForROC's arguments (minSize, maxSize, scaleFactor, minNeighbors, flags)."""
+    _fields_ = [("min_w", C.c_int32), ("min_h", C.c_int32), ("max_w", C.c_int32), ("max_h", C.c_int32),
+                ("scale_factor", C.c_double), ("min_neighbors", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class _RocResult(C.Structure):
+    _fields_ = [("r", _Result), ("reject_levels", C.c_void_p), ("level_weights", C.c_void_p)]
+
+
 RECT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("weight", "<f4"),
                        ("frame", "<i4"), ("scale_idx", "<i4")])
 STAGE_DTYPE = np.dtype([("first_tree", "<i4"), ("n_trees", "<i4"), ("threshold", "<f4"), ("parent", "<i4"),
@@ -186,11 +196,16 @@ _SIGNATURES = {
     "vj_detect_opencv_chain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(CvParams),
                                          C.POINTER(CvParams), C.POINTER(_Result), C.POINTER(_Result)]),
     "vj_cv_params_default": (None, [C.POINTER(CvParams)]),
+    "vj_cv_roc_params_default": (None, [C.POINTER(CvRocParams)]),
+    "vj_detect_opencv_roc": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(CvRocParams),
+                                       C.POINTER(_RocResult)]),
+    "vj_roc_result_free": (None, [C.POINTER(_RocResult)]),
     "vj_cv_plan_info_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CvParams), C.POINTER(CvPlanInfo)]),
     "vj_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params),
                             C.POINTER(_Result)]),
     "vj_result_free": (None, [C.POINTER(_Result)]),
     "vj_group_rectangles": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_double]),
+    "vj_group_rectangles_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double]),
     "vj_count_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(C.c_uint64)]),
     "vj_shard_frames": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vj_shard_scales": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
@@ -359,6 +374,8 @@ class DetectResult:
     tile_split: float = 0.0      # the chain balance the call's plan was built for
     balance_state: int = 0       # 0 static, 1 the workload's feedback search is running, 2 finished
     balance_calls: int = 0       # calls the search has measured so far
+    reject_levels: np.ndarray = None   # detect_opencv_roc only: int32, parallel to rects — the stage each window reached
+    level_weights: np.ndarray = None   # ... float64: the stage sum it reached it with
 
     @property
     def match_count(self) -> int:
@@ -579,6 +596,30 @@ class Environment:
                "vj_detect_opencv_chain")
         return self._result(lib, r1, first), self._result(lib, r2, second)
 
+    def detect_opencv_roc(self, cascade: Cascade, frames, min_size=(0, 0), max_size=(0, 0), scale_factor: float = 1.1,
+                          min_neighbors: int = 0, flags: int = VJ_FLAG_CV_SCALE_IMAGE, color: bool = False) -> DetectResult:
+        """vj_detect_opencv_roc: cvHaarDetectObjectsForROC with outputRejectLevels (the CV_HAAR_SCALE_IMAGE branch).  Every grid
+        window that passes the cascade or fails one of its last three stages comes back with .reject_levels (the stage it reached;
+        the stage count for a pass) and .level_weights (that stage's f64 sum); stage trees report accepted windows only.
+        max_size: the level loop ends at the first window larger than it ((0, 0), or a zero member: the frame).  min_neighbors != 0
+        groups with groupRectangles' level overload (group_rectangles_levels).  flags must hold VJ_FLAG_CV_SCALE_IMAGE;
+        VJ_FLAG_CV_FIND_BIGGEST and cascades of fewer than 4 stages are refused (VJ_ERR_UNSUPPORTED)."""
+        imgs, n, keep = self._images(frames, color)
+        p = CvRocParams(int(min_size[0]), int(min_size[1]), int(max_size[0]), int(max_size[1]), float(scale_factor),
+                        int(min_neighbors), int(flags))
+        res = _RocResult()
+        lib = load_library()
+        _check(lib.vj_detect_opencv_roc(self._h, cascade._h, imgs, n, C.byref(p), C.byref(res)), "vj_detect_opencv_roc")
+        try:
+            m = int(res.r.count)
+            levels = np.ctypeslib.as_array((C.c_int32 * m).from_address(res.reject_levels)).copy() if m else np.zeros(0, np.int32)
+            weights = np.ctypeslib.as_array((C.c_double * m).from_address(res.level_weights)).copy() if m else np.zeros(0, np.float64)
+            out = self._result(lib, res.r, cascade)   # (copies the rectangles and frees them: vj_result_free leaves rects null)
+        finally:
+            lib.vj_roc_result_free(C.byref(res))
+        out.reject_levels, out.level_weights = levels, weights
+        return out
+
     def cv_plan_info(self, cascade: Cascade, width: int, height: int, n_frames: int, min_size=(0, 0),
                      scale_factor: float = 1.1, min_neighbors: int = 0, flags: int = 0) -> CvPlanInfo:
         """vj_cv_plan_info_get: the plan detect_opencv uses for a batch of n_frames width x height frames."""
@@ -711,6 +752,21 @@ def group_rectangles(rects: np.ndarray, group_threshold: int, eps: float = 0.2) 
     return buf[:n.value]
 
 
+def group_rectangles_levels(rects: np.ndarray, levels, weights, group_threshold: int, eps: float = 0.2):
+    """groupRectangles(rectList, rejectLevels, levelWeights, groupThreshold, eps) (tempcv.cpp:255-258) on a RECT_DTYPE array sorted
+    by frame with its reject levels and level weights (host logic).  Returns (rects, levels, weights) of the kept classes."""
+    buf = np.ascontiguousarray(rects, RECT_DTYPE).copy()
+    lv = np.ascontiguousarray(levels, np.int32).copy()
+    lw = np.ascontiguousarray(weights, np.float64).copy()
+    if not (len(buf) == len(lv) == len(lw)):
+        raise VjError(1, "group_rectangles_levels", "rects, levels and weights must have one length")
+    n = load_library().vj_group_rectangles_levels(buf.ctypes.data if len(buf) else None, lv.ctypes.data if len(buf) else None,
+                                                  lw.ctypes.data if len(buf) else None, len(buf), int(group_threshold), float(eps))
+    if n < 0:
+        _check(-n, "vj_group_rectangles_levels")
+    return buf[:n], lv[:n], lw[:n]
+
+
 # ------------------------------------------------- reference-named entry points
 def clodInitEnvironment(device_index: int = 0) -> Environment:
     """clod.h:61-62 / clod.cpp:72-100."""
@@ -773,3 +829,17 @@ def cvHaarDetectObjects(image, cascade: Cascade, env: Environment, scale_factor:
     if flags & CV_HAAR_DO_CANNY_PRUNING:
         vj_flags |= VJ_FLAG_CV_CANNY_PRUNING
     return env.detect_opencv(cascade, image, min_size, scale_factor, min_neighbors, vj_flags)
+
+
+def cvHaarDetectObjectsForROC(image, cascade: Cascade, env: Environment, scale_factor: float = 1.1, min_neighbors: int = 3,
+                              flags: int = CV_HAAR_SCALE_IMAGE, min_size=(0, 0), max_size=(0, 0)) -> DetectResult:
+    """cvHaarDetectObjectsForROC(image, cascade, storage, rejectLevels, levelWeights, scale_factor, min_neighbors, flags, min_size,
+    max_size, outputRejectLevels = true) (tempcv.hpp:282-286; tempcv.cpp:1188-1503), on the device: the result's .reject_levels and
+    .level_weights are the two vectors the reference fills.  `flags` takes the CV_HAAR_* values; without CV_HAAR_SCALE_IMAGE, or
+    with CV_HAAR_FIND_BIGGEST_OBJECT, the call is refused (Environment.detect_opencv_roc says why)."""
+    vj_flags = 0
+    for cv_bit, vj_bit in ((CV_HAAR_DO_CANNY_PRUNING, VJ_FLAG_CV_CANNY_PRUNING), (CV_HAAR_SCALE_IMAGE, VJ_FLAG_CV_SCALE_IMAGE),
+                           (CV_HAAR_FIND_BIGGEST_OBJECT, VJ_FLAG_CV_FIND_BIGGEST), (CV_HAAR_DO_ROUGH_SEARCH, VJ_FLAG_CV_ROUGH_SEARCH)):
+        if flags & cv_bit:
+            vj_flags |= vj_bit
+    return env.detect_opencv_roc(cascade, image, min_size, max_size, scale_factor, min_neighbors, vj_flags)

@@ -198,8 +198,28 @@ static std::vector<StageDev> build_cv_stage_recs(const vj_cascade* c, const Stag
     return stages;
 }
 
+// What vj_detect_opencv_roc adds to a scale-image call: maxSize, already resolved (a zero member means the frame,
+// tempcv.cpp:1230-1234), and where the levels and weights of the reported windows go, parallel to the call's rectangles.
+struct CvRocCall {
+    int max_w, max_h;
+    std::vector<int32_t>* levels;
+    std::vector<double>* weights;
+};
+
+// The level k at which `winSize > maxSize` ends the scale-image level loop (tempcv.cpp:1268-1286), -1 when the loop ends on the
+// level's size first: what a plan's key records of maxSize.
+static int cv_max_level_end(const vj_cascade* c, int W, int H, double scale_factor, int max_w, int max_h) {
+    double factor = 1;
+    for (int k = 0; k <= 65536; ++k, factor *= scale_factor) {
+        if (cv_round(W / factor) - c->win_w + 1 <= 0 || cv_round(H / factor) - c->win_h + 1 <= 0) return -1;
+        if (cv_round(c->win_w * factor) > max_w || cv_round(c->win_h * factor) > max_h) return k;
+    }
+    return -1;
+}
+
 // Everything that depends on (cascade, frame size, parameters) only: scales, feature tables, stage records, row list.
-static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv_params* p, bool small_batch, CvPlan* pl) {
+static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv_params* p, bool small_batch, CvPlan* pl,
+                         const CvRocCall* roc = nullptr) {
     if ((int)c->stages.size() > VJ_MAX_STAGES || c->stages.empty()) {
         set_error("cascade has %zu stages; 1..%d are supported", c->stages.size(), VJ_MAX_STAGES);
         return VJ_ERR_LIMIT;
@@ -221,6 +241,7 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     const bool si = !fb && (p->flags & VJ_FLAG_CV_SCALE_IMAGE) != 0u;
     pl->find_biggest = fb;
     pl->scale_image = si;
+    pl->roc = roc != nullptr;
     pl->prune = !fb && !si && (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
     pl->trees = trees;
     pl->is_tree = is_tree;
@@ -231,7 +252,8 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     std::vector<CvScaleHost> hs;
     int IW = W, IH = H;   // what the integral images are computed of: the frame, or the canvas of the pyramid's levels
     if (si) {
-        // ---- the level loop (tempcv.cpp:1268-1288; maxSize is the image)
+        // ---- the level loop (tempcv.cpp:1268-1288; maxSize is the image unless a ROC call brings one)
+        const int max_w = roc ? roc->max_w : W, max_h = roc ? roc->max_h : H;
         double factor = 1;
         for (int k = 0;; ++k, factor *= p->scale_factor) {
             if (k > 65536) {
@@ -246,7 +268,7 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
             s.lw = cv_round(W / factor);
             s.lh = cv_round(H / factor);
             if (s.lw - c->win_w + 1 <= 0 || s.lh - c->win_h + 1 <= 0) break;
-            if (s.win_w > W || s.win_h > H) break;
+            if (s.win_w > max_w || s.win_h > max_h) break;
             if (s.win_w < p->min_w || s.win_h < p->min_h) continue;
             // x, y = 0, ystep, ... < size - window (:1015-1020, :1079-1080)
             s.step = factor > 2 ? 1 : 2;
@@ -461,7 +483,8 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
         const bool tiles_tilted = has_tilted && e->cv_tiles_tilted && !is_tree;
         // CV_HAAR_SCALE_IMAGE: the levels of linear cascades whose grid fills a tile run cv_tile_pass<3> (the exhaustive grid; step 1 or 2);
         // stage trees stay on the exhaustive-grid row kernel (their tile path is built around the tree queue and the accept bitmap)
-        if (!fb && !(si && is_tree) && e->cv_tiles && (!trees || (tree2 && !is_tree)) && (!is_tree || tree_prefix != 0u) && (!has_tilted || tiles_tilted) && sd.end_x < 65536u &&
+        // (a ROC call keeps every level on the rows: the tile kernel has no form that reports reject levels)
+        if (!fb && !(si && is_tree) && !roc && e->cv_tiles && (!trees || (tree2 && !is_tree)) && (!is_tree || tree_prefix != 0u) && (!has_tilted || tiles_tilted) && sd.end_x < 65536u &&
             sd.end_y < 65536u) {
             uint32_t reach_x = (uint32_t)(ex + ew), reach_y = (uint32_t)(ex + eh);
             for (size_t n = 0; n < n_nodes; ++n) {
@@ -648,7 +671,8 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     return VJ_OK;
 }
 
-static int get_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv_params* p, int n_frames, CvPlan** out) {
+static int get_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv_params* p, int n_frames, CvPlan** out,
+                       const CvRocCall* roc = nullptr) {
     uint64_t sf_bits;
     memcpy(&sf_bits, &p->scale_factor, 8);
     const bool small_batch = n_frames <= 4;
@@ -657,7 +681,8 @@ static int get_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv
     const bool prune = !fb && !si && (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
     // (a find-biggest plan depends on neither minSize — the break is the waves' — nor the batch-size class: one plan for all)
     const vj_env::CvPlanKey key(c->uid, W, H, fb ? 0 : p->min_w, fb ? 0 : p->min_h, sf_bits,
-                                fb ? 8 : (small_batch ? 1 : 0) | (prune ? 2 : 0) | (si ? 4 : 0));
+                                fb ? 8 : (small_batch ? 1 : 0) | (prune ? 2 : 0) | (si ? 4 : 0) | (roc ? 16 : 0),
+                                roc ? cv_max_level_end(c, W, H, p->scale_factor, roc->max_w, roc->max_h) : -1);
     auto it = e->cv_plans.find(key);
     if (it != e->cv_plans.end()) {
         it->second->last_used = ++e->plan_tick;
@@ -675,7 +700,7 @@ static int get_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv
         }
     }
     auto pl = std::make_unique<CvPlan>();
-    const int rc = build_cv_plan(e, c, W, H, p, small_batch, pl.get());
+    const int rc = build_cv_plan(e, c, W, H, p, small_batch, pl.get(), roc);
     if (rc) {
         pl->release_device();
         return rc;
@@ -1098,8 +1123,10 @@ namespace {
 typedef std::function<int(int f0, int nf, const vj_rect* raw, size_t n_raw)> CvSubBatchHook;
 
 // vj_detect_opencv.  need_tilted: compute the tilted integral even when `c` has no tilted feature (someone after it reads it).
+// roc: vj_detect_opencv_roc's scale-image call — the kernels report CvRocDet records; the rectangles come back raw (ungrouped),
+// sorted, with their levels and weights in roc's vectors.
 int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_params* p, vj_result* out,
-                       bool need_tilted, const CvSubBatchHook* hook) {
+                       bool need_tilted, const CvSubBatchHook* hook, const CvRocCall* roc = nullptr) {
     if (!e || !c || !p || !out || n_frames < 0 || (n_frames > 0 && !frames)) return VJ_ERR_ARG;
     memset(out, 0, sizeof(*out));
     if (n_frames == 0) return VJ_OK;
@@ -1122,7 +1149,7 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         }
     HIP_TRY(hipSetDevice(e->device));
     CvPlan* pl;
-    int rc = get_cv_plan(e, c, W, H, p, n_frames, &pl);
+    int rc = get_cv_plan(e, c, W, H, p, n_frames, &pl, roc);
     if (rc) return rc;
     if (pl->find_biggest) return detect_biggest(e, c, pl, frames, n_frames, W, H, CH, p, out);
     const std::vector<CvScaleDev>& scales = pl->scales;
@@ -1154,8 +1181,12 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         if (frame_windows) max_frames = (int)std::min<uint64_t>((uint64_t)max_frames, 0xffffffffull / frame_windows);
     }
     if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
-    uint32_t det_cap = 1u << 16;
+    // (a ROC call reports several times as many windows: its buffer starts at the configured "det_cap" and grows the same way)
+    uint32_t det_cap = roc ? std::max(1u, e->det_cap_init) : 1u << 16;
+    const size_t det_bytes = roc ? sizeof(CvRocDet) : sizeof(CvDet);
     std::vector<vj_rect> all;
+    std::vector<int32_t> all_levels;   // (ROC) parallel to `all`
+    std::vector<double> all_weights;
     for (int f0 = 0, nf = 0; f0 < n_frames && pl->n_rows != 0; f0 += nf) {
         nf = std::min(max_frames, n_frames - f0);
         if (si) {   // the frames' gray staging alone; the integral buffers are the canvases'
@@ -1190,7 +1221,7 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         bool rows_only = false, done = false, resplit = false;
         const size_t sub_first = all.size();
         for (int attempt = 0; attempt < 2; ++attempt) {
-            if ((rc = d_det.ensure((size_t)det_cap * sizeof(CvDet)))) return rc;
+            if ((rc = d_det.ensure((size_t)det_cap * det_bytes))) return rc;
             HIP_TRY(hipMemsetAsync(d_counts.p, 0, counts_bytes, e->stream));
             CvArgs a;
             memset(&a, 0, sizeof(a));
@@ -1519,7 +1550,7 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
                 // should stay inside its 4 MiB L2 (64 x 1080p: 376 / 235 / 179 / 153 / 173 / 194 / 193 ms for 1 / 2 / 3 / 4 / 5 / 6 / 8)
                 const int n_blocks = std::max(1, e->n_cu * 4);
                 a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
-                hrc = launch_cv_profile_pass(a, trees, count, is_tree, n_blocks, e->stream, pl->prune, si);
+                hrc = launch_cv_profile_pass(a, trees, count, is_tree, n_blocks, e->stream, pl->prune, si, roc != nullptr);
             }
             if (hrc) {
                 set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
@@ -1563,6 +1594,19 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
                 for (size_t s = 0; s < pl->n_stages; ++s) out->counters.stage_entered[s] += h[s];
                 out->counters.windows += h[VJ_MAX_STAGES];
             }
+            if (roc) {
+                std::vector<CvRocDet> rraw(n_det);
+                if (n_det) HIP_TRY(hipMemcpy(rraw.data(), d_det.p, (size_t)n_det * sizeof(CvRocDet), hipMemcpyDeviceToHost));
+                for (const CvRocDet& d : rraw) {
+                    all.push_back(vj_rect{cv_round((double)d.x * pl->level_factor[d.slot]), cv_round((double)d.y * pl->level_factor[d.slot]),
+                                          (int32_t)scales[d.slot].win_w, (int32_t)scales[d.slot].win_h, 0.0f, f0 + (int32_t)d.frame,
+                                          (int32_t)scales[d.slot].scale_idx});
+                    all_levels.push_back((int32_t)d.level);
+                    all_weights.push_back(d.weight);
+                }
+                done = true;
+                break;
+            }
             std::vector<CvDet> raw(n_det);
             if (n_det) HIP_TRY(hipMemcpy(raw.data(), d_det.p, (size_t)n_det * sizeof(CvDet), hipMemcpyDeviceToHost));
             for (const CvDet& d : raw)
@@ -1586,6 +1630,22 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         }
         if (hook && (rc = (*hook)(f0, nf, all.data() + sub_first, all.size() - sub_first))) return rc;
     }
+    if (roc) {   // the key is unique (one report per grid position of a level): levels and weights follow their rectangles
+        std::vector<size_t> idx(all.size());
+        for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
+        std::sort(idx.begin(), idx.end(), [&](size_t i, size_t j) {
+            return std::tie(all[i].frame, all[i].scale_idx, all[i].y, all[i].x) < std::tie(all[j].frame, all[j].scale_idx, all[j].y, all[j].x);
+        });
+        std::vector<vj_rect> sorted(all.size());
+        roc->levels->resize(all.size());
+        roc->weights->resize(all.size());
+        for (size_t i = 0; i < idx.size(); ++i) {
+            sorted[i] = all[idx[i]];
+            (*roc->levels)[i] = all_levels[idx[i]];
+            (*roc->weights)[i] = all_weights[idx[i]];
+        }
+        all.swap(sorted);
+    } else
     std::sort(all.begin(), all.end(), [](const vj_rect& a, const vj_rect& b) {
         return std::tie(a.frame, a.scale_idx, a.y, a.x) < std::tie(b.frame, b.scale_idx, b.y, b.x);
     });
@@ -1595,7 +1655,7 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         if (!out->rects) return VJ_ERR_NOMEM;
         memcpy(out->rects, all.data(), all.size() * sizeof(vj_rect));
     }
-    if (p->min_neighbors != 0 && out->count) {   // groupRectangles(rectList, max(minNeighbors, 1), GROUP_EPS)
+    if (!roc && p->min_neighbors != 0 && out->count) {   // groupRectangles(rectList, max(minNeighbors, 1), GROUP_EPS)
         rc = vj_group_rectangles(out->rects, &out->count, (int)std::max<uint32_t>(p->min_neighbors, 1u), 0.2);
         if (rc) return rc;
     }
@@ -1826,6 +1886,87 @@ extern "C" {
 int vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_params* p,
                      vj_result* out) {
     return detect_opencv_impl(e, c, frames, n_frames, p, out, false, nullptr);
+}
+
+void vj_cv_roc_params_default(vj_cv_roc_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->scale_factor = 1.1;
+    p->flags = VJ_FLAG_CV_SCALE_IMAGE;
+}
+
+void vj_roc_result_free(vj_roc_result* r) {
+    if (!r) return;
+    free(r->r.rects);
+    free(r->reject_levels);
+    free(r->level_weights);
+    r->r.rects = nullptr;
+    r->r.count = 0;
+    r->reject_levels = nullptr;
+    r->level_weights = nullptr;
+}
+
+// cvHaarDetectObjectsForROC(..., outputRejectLevels = true) (tempcv.cpp:1188-1503)
+int vj_detect_opencv_roc(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_roc_params* p, vj_roc_result* out) {
+    if (!e || !c || !p || !out) return VJ_ERR_ARG;
+    memset(out, 0, sizeof(*out));
+    if (p->max_w < 0 || p->max_h < 0) {
+        set_error("max_w / max_h must be >= 0");
+        return VJ_ERR_ARG;
+    }
+    if ((p->flags & VJ_FLAG_CV_FIND_BIGGEST) != 0u) {   // clears scale-image (:1227), then reads an empty rweights (:1486)
+        set_error("vj_detect_opencv_roc: reject levels with VJ_FLAG_CV_FIND_BIGGEST are not a meaningful result");
+        return VJ_ERR_UNSUPPORTED;
+    }
+    if ((p->flags & VJ_FLAG_CV_SCALE_IMAGE) == 0u) {    // the scale-cascade invoker (:1116-1185) never pushes a level
+        set_error("vj_detect_opencv_roc: reject levels exist in the VJ_FLAG_CV_SCALE_IMAGE branch only");
+        return VJ_ERR_UNSUPPORTED;
+    }
+    if (c->stages.size() < 4) {                         // n + result < 4 would hold for rejects at stage 0: every grid position
+        set_error("vj_detect_opencv_roc: a cascade of %zu stages; reject levels need at least 4", c->stages.size());
+        return VJ_ERR_UNSUPPORTED;
+    }
+    if (n_frames < 0 || (n_frames > 0 && !frames)) return VJ_ERR_ARG;
+    if (n_frames == 0) return VJ_OK;
+    vj_cv_params q;
+    memset(&q, 0, sizeof(q));
+    q.min_w = p->min_w;
+    q.min_h = p->min_h;
+    q.scale_factor = p->scale_factor;
+    q.min_neighbors = p->min_neighbors;
+    q.flags = p->flags & (VJ_FLAG_COUNTERS | VJ_FLAG_CV_SCALE_IMAGE);   // (canny pruning and rough search: not read by this branch)
+    std::vector<int32_t> levels;
+    std::vector<double> weights;
+    const bool whole = p->max_w == 0 || p->max_h == 0;   // maxSize with a zero member is the frame (:1230-1234)
+    const CvRocCall roc{whole ? frames[0].width : p->max_w, whole ? frames[0].height : p->max_h, &levels, &weights};
+    int rc = detect_opencv_impl(e, c, frames, n_frames, &q, &out->r, false, nullptr, &roc);
+    if (rc) {
+        vj_roc_result_free(out);
+        return rc;
+    }
+    int n = (int)out->r.count;
+    if (p->min_neighbors != 0 && n != 0) {   // groupRectangles(rectList, rejectLevels, levelWeights, minNeighbors, GROUP_EPS) (:1466)
+        n = vj_group_rectangles_levels(out->r.rects, levels.data(), weights.data(), n, (int)std::min<uint32_t>(p->min_neighbors, 0x7fffffffu), 0.2);
+        if (n < 0) {
+            vj_roc_result_free(out);
+            return -n;
+        }
+        out->r.count = (uint32_t)n;
+    }
+    if (n != 0) {
+        out->reject_levels = (int32_t*)malloc((size_t)n * sizeof(int32_t));
+        out->level_weights = (double*)malloc((size_t)n * sizeof(double));
+        if (!out->reject_levels || !out->level_weights) {
+            vj_roc_result_free(out);
+            return VJ_ERR_NOMEM;
+        }
+        memcpy(out->reject_levels, levels.data(), (size_t)n * sizeof(int32_t));
+        memcpy(out->level_weights, weights.data(), (size_t)n * sizeof(double));
+    } else {
+        free(out->r.rects);
+        out->r.rects = nullptr;
+    }
+    return VJ_OK;
 }
 
 int vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_roi* rois, int n_rois,

@@ -42,7 +42,9 @@ __device__ __forceinline__ E cv_load_entry_l2(const E* p) {
 // Sweep the chains of `ch` over the windows q[0, n) (LDS; entries carry .off and .vnf), all of one scale.  `final_(e, mine,
 // accepted)` is called in wave-uniform control flow for windows whose walk ends: lanes with `mine` set hold such a window.
 // `fail_g`: room for the population in global memory (this wave's own).
-template <bool TREES, typename E, typename Final>
+// SUMS (ROC calls): final_ takes a fourth argument, the sum of the stage that ended the walk; who passes a chain's last stage is
+// handed to it right there, where the lane still holds that sum, instead of after the compaction.
+template <bool TREES, bool SUMS = false, typename E, typename Final>
 __device__ __forceinline__ void cv_chain_sweep(const CvChainDev& ch, kptr<StageDev> stages, rsrc_t img, rsrc_t timg, bool tail_ok, const uint32_t* table_g,
                                                kptr<NodeRecDev> table, E* q, uint32_t n, E* fail_g, unsigned long long* masks, uint32_t lane,
                                                Final final_) {
@@ -55,17 +57,32 @@ __device__ __forceinline__ void cv_chain_sweep(const CvChainDev& ch, kptr<StageD
             const double thr = (double)stages[s].threshold;
             kptr<NodeRecDev> tab = table + first_node;
             if (!TREES && tail_ok && n <= ch.tail_max && n_nodes >= 16u && n_nodes <= CV_TAIL_BLOCKS * 64u) {   // uniform
-                const unsigned long long pm = cv_tail_stage(img, table_g + (size_t)first_node * 16u, tab, n_nodes, thr, q, n, masks, lane);
+                unsigned long long pm;
+                double ssum = 0.0;
+                if constexpr (SUMS) {
+                    ssum = cv_tail_stage_sum(img, table_g + (size_t)first_node * 16u, tab, n_nodes, q, n, masks, lane);
+                    pm = __ballot(lane < n && ssum >= thr);
+                } else {
+                    pm = cv_tail_stage(img, table_g + (size_t)first_node * 16u, tab, n_nodes, thr, q, n, masks, lane);
+                }
                 const bool have = lane < n;
                 const E e = q[have ? lane : 0u];
-                const bool pass = ((pm >> lane) & 1ull) != 0ull;
+                bool pass = ((pm >> lane) & 1ull) != 0ull;
                 const unsigned long long fm = __ballot(have && !pass);
                 if (fm != 0ull) {
                     if (chained) {
                         if (have && !pass) fail_g[nf + mbcnt(fm)] = e;
                         nf += (uint32_t)__popcll(fm);
                     } else {
-                        final_(e, have && !pass, false);
+                        if constexpr (SUMS) final_(e, have && !pass, false, ssum);
+                        else final_(e, have && !pass, false);
+                    }
+                }
+                if constexpr (SUMS) {
+                    if (pos + 1u == ch.end[k]) {   // the chain's last stage: its passers are accepted, with this sum
+                        if (pm != 0ull) final_(e, pass, true, ssum);
+                        pass = false;
+                        pm = 0ull;
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -79,11 +96,12 @@ __device__ __forceinline__ void cv_chain_sweep(const CvChainDev& ch, kptr<StageD
                 const uint32_t i = base + lane;
                 const bool act = i < n;
                 const E e = q[act ? i : 0u];
+                double ssum = 0.0;
                 bool pass = false;
                 if (act) {
-                    if (TREES) pass = cv_stage_sum<true, false>(img, timg, tab, n_nodes, e.off, e.vnf) >= thr;
-                    else if (tail_ok) pass = cv_stage_sum_pairs(img, tab, n_nodes, e.off, e.vnf) >= thr;
-                    else pass = cv_stage_sum<false, false>(img, timg, tab, n_nodes, e.off, e.vnf) >= thr;   // (tilted features)
+                    if (TREES) pass = (ssum = cv_stage_sum<true, false>(img, timg, tab, n_nodes, e.off, e.vnf)) >= thr;
+                    else if (tail_ok) pass = (ssum = cv_stage_sum_pairs(img, tab, n_nodes, e.off, e.vnf)) >= thr;
+                    else pass = (ssum = cv_stage_sum<false, false>(img, timg, tab, n_nodes, e.off, e.vnf)) >= thr;   // (tilted features)
                 }
                 const unsigned long long fm = __ballot(act && !pass);
                 if (fm != 0ull) {
@@ -91,7 +109,14 @@ __device__ __forceinline__ void cv_chain_sweep(const CvChainDev& ch, kptr<StageD
                         if (act && !pass) fail_g[nf + mbcnt(fm)] = e;
                         nf += (uint32_t)__popcll(fm);
                     } else {
-                        final_(e, act && !pass, false);
+                        if constexpr (SUMS) final_(e, act && !pass, false, ssum);
+                        else final_(e, act && !pass, false);
+                    }
+                }
+                if constexpr (SUMS) {
+                    if (pos + 1u == ch.end[k]) {   // the chain's last stage: its passers are accepted, with this sum
+                        if (__ballot(pass) != 0ull) final_(e, pass, true, ssum);
+                        pass = false;
                     }
                 }
                 const unsigned long long mask = __ballot(pass);
@@ -102,10 +127,12 @@ __device__ __forceinline__ void cv_chain_sweep(const CvChainDev& ch, kptr<StageD
             }
             n = m;
         }
-        for (uint32_t base = 0; base < n; base += 64u) {   // passed the chain's last stage: accepted
-            const bool act = base + lane < n;
-            const E e = q[act ? base + lane : 0u];
-            final_(e, act, true);
+        if constexpr (!SUMS) {
+            for (uint32_t base = 0; base < n; base += 64u) {   // passed the chain's last stage: accepted
+                const bool act = base + lane < n;
+                const E e = q[act ? base + lane : 0u];
+                final_(e, act, true);
+            }
         }
         if (!chained) break;
         // the chain's rejects are the next chain's population
@@ -138,8 +165,13 @@ __device__ __forceinline__ void cv_flush(const CvArgs& a, rsrc_t img, rsrc_t tim
 // EVERY grid position is visited — a reject skips nothing — and the border rule cannot fire (x < level width - window width).
 // Positions and detections are in the level's own coordinates (the host scales them by the level's factor).  Per-window arithmetic:
 // the same code.  EXH = false compiles to the kernels as they were.
-template <bool TREES, bool COUNT, bool STAGE_TREE, bool PRUNE = false, bool EXH = false>
+// ROC (with EXH): cvHaarDetectObjectsForROC's outputRejectLevels (tempcv.cpp:1084-1095).  The records are CvRocDet:
+// a linear cascade reports from its sweep of the later stages (cv_flush_roc); a stage tree reports an accepted window where the stage
+// whose pass ended its walk was summed — every position is visited, so no walk has to be resolved first.  ROC = false compiles to
+// the kernels as they were.
+template <bool TREES, bool COUNT, bool STAGE_TREE, bool PRUNE = false, bool EXH = false, bool ROC = false>
 __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArgs a) {
+    static_assert(!ROC || (EXH && !PRUNE), "reject levels exist on the exhaustive grid only");
     __shared__ CvQEntry lds_q[CV_WAVES_PER_BLOCK * CV_QCAP];
     __shared__ unsigned long long lds_words[CV_WAVES_PER_BLOCK][2][STAGE_TREE ? CV_TREE_SEG_GROUPS : 1];   // stage trees: verdict bits of a row segment
     const uint32_t lane = lane_id();
@@ -209,6 +241,15 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
             auto drain = [&](uint32_t seg0) {
                 if (a.chains.n != 0u) {
                     // the tree is made of chains: compacting sweeps (every queued window sits at the first stage of chain 0)
+                    if constexpr (ROC)
+                        cv_chain_sweep<TREES, true>(a.chains, stages, img, timg, a.tilted == nullptr, a.table + (size_t)scales[slot].table_first * 16u, table, q,
+                                                    n_q, fail_g, reinterpret_cast<unsigned long long*>(q + CV_TAIL_MAX), lane,
+                                                    [&](const CvQEntry& e, bool mine, bool accepted, double ssum) {
+                                                        if (accepted)   // (uniform)
+                                                            cv_roc_report(a, mine, (uint32_t)cv_round((double)(e.xy & 0xffffu) * ystep), y, slot, frame,
+                                                                          a.n_stages, ssum, lane);
+                                                    });
+                    else
                     cv_chain_sweep<TREES>(a.chains, stages, img, timg, a.tilted == nullptr, a.table + (size_t)scales[slot].table_first * 16u, table, q, n_q,
                                           fail_g, reinterpret_cast<unsigned long long*>(q + CV_TAIL_MAX), lane,
                                           [&](const CvQEntry& e, bool mine, bool accepted) {
@@ -225,15 +266,21 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                     const bool act = base + lane < n_q;
                     const CvQEntry e = q[act ? base + lane : 0u];
                     int32_t ptr = act ? (int32_t)(e.xy >> 16) : -3;
+                    double last_sum = 0.0;   // (ROC) of the last stage this window was in
                     for (uint32_t oi = prefix; oi < a.n_order; ++oi) {
                         const uint32_t s = stages[oi].order;
                         const bool here = ptr == (int32_t)s;
                         if (__ballot(here) == 0ull) continue;
                         if (here) {
-                            const bool pass = cv_stage_sum<TREES, false>(img, timg, table + stages[s].first_node, stages[s].n_nodes, e.off, e.vnf) >=
-                                              (double)stages[s].threshold;
+                            const double ssum = cv_stage_sum<TREES, false>(img, timg, table + stages[s].first_node, stages[s].n_nodes, e.off, e.vnf);
+                            const bool pass = ssum >= (double)stages[s].threshold;
                             ptr = pass ? stages[s].on_pass : stages[s].on_fail;
+                            if (ROC) last_sum = ssum;
                         }
+                    }
+                    if constexpr (ROC) {
+                        cv_roc_report(a, act && ptr == -1, (uint32_t)cv_round((double)(e.xy & 0xffffu) * ystep), y, slot, frame, a.n_stages, last_sum, lane);
+                        continue;
                     }
                     if (act) {
                         const uint32_t rel = (e.xy & 0xffffu) - seg0;
@@ -267,16 +314,19 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                         vnf = vnf >= 0.0 ? sqrt(vnf) : 1.0;
                     }
                     int32_t ptr = eval ? (int32_t)stages[0].order : -3;   // -1 accepted, -2 rejected, -3 not evaluated
+                    double last_sum = 0.0;   // (ROC) of the last stage this window was in
                     for (uint32_t oi = 0; oi < prefix; ++oi) {
                         const uint32_t s = stages[oi].order;
                         const bool here = ptr == (int32_t)s;
                         if (__ballot(here) == 0ull) break;   // (nobody left in the prefix)
                         if (here) {
-                            const bool pass = cv_stage_sum<TREES, false>(img, timg, table + stages[s].first_node, stages[s].n_nodes, off, vnf) >=
-                                              (double)stages[s].threshold;
+                            const double ssum = cv_stage_sum<TREES, false>(img, timg, table + stages[s].first_node, stages[s].n_nodes, off, vnf);
+                            const bool pass = ssum >= (double)stages[s].threshold;
                             ptr = pass ? stages[s].on_pass : stages[s].on_fail;
+                            if (ROC) last_sum = ssum;
                         }
                     }
+                    if constexpr (ROC) cv_roc_report(a, ptr == -1, x, y, slot, frame, a.n_stages, last_sum, lane);   // (accepted inside the prefix)
                     const unsigned long long fm = __ballot(ptr == -2 || pruned), am = __ballot(ptr == -1), wm = __ballot(ptr >= 0);
                     if (lane == 0) {
                         Fw[(ix0 - seg0) >> 6] = fm;
@@ -288,8 +338,8 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                     if (n_q > (uint32_t)CV_QCAP - 64u) drain(seg0);
                 }
                 drain(seg0);
-                // every position of the segment has its verdict: the sequential walk, group by group
-                for (uint32_t ix0 = seg0; ix0 < seg_end; ix0 += 64u) {
+                // every position of the segment has its verdict: the sequential walk, group by group (ROC: reported already)
+                for (uint32_t ix0 = seg0; ix0 < seg_end && !ROC; ix0 += 64u) {
                     const uint32_t ix = ix0 + lane;
                     const unsigned long long F = Fw[(ix0 - seg0) >> 6], A = Aw[(ix0 - seg0) >> 6];
                     const bool visited = EXH ? ix < end_x : cv_visited(F, lane, min(64u, end_x - ix0), carry);
@@ -333,15 +383,17 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                 // stage it visits next; stages are swept once in a topological order of the pass / fail graph
                 int32_t ptr = eval ? (int32_t)stages[0].order : -3;   // -1 accepted, -2 rejected, -3 not evaluated
                 unsigned long long entered = 0ull;
+                double last_sum = 0.0;   // (ROC) of the last stage this window was in
                 for (uint32_t oi = 0; oi < a.n_order; ++oi) {
                     const uint32_t s = stages[oi].order;
                     const bool here = ptr == (int32_t)s;
                     if (__ballot(here) == 0ull) continue;
                     if (here) {
-                        const bool pass = cv_stage_sum<TREES, false>(img, timg, table + stages[s].first_node, stages[s].n_nodes, off, vnf) >=
-                                          (double)stages[s].threshold;
+                        const double ssum = cv_stage_sum<TREES, false>(img, timg, table + stages[s].first_node, stages[s].n_nodes, off, vnf);
+                        const bool pass = ssum >= (double)stages[s].threshold;
                         ptr = pass ? stages[s].on_pass : stages[s].on_fail;
                         entered |= 1ull << s;
+                        if (ROC) last_sum = ssum;
                     }
                 }
                 const unsigned long long F = __ballot(ptr == -2 || pruned);
@@ -353,6 +405,10 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
                         const unsigned long long em = __ballot(visited && ((entered >> s) & 1ull) != 0ull);
                         if (lane == 0 && em != 0ull) atomicAdd(a.stage_entered + s, (unsigned long long)__popcll(em));
                     }
+                }
+                if constexpr (ROC) {
+                    cv_roc_report(a, visited && ptr == -1, x, y, slot, frame, a.n_stages, last_sum, lane);
+                    continue;
                 }
                 const unsigned long long am = __ballot(visited && ptr == -1);
                 if (am != 0ull) {
@@ -382,22 +438,40 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_profile_pass(CvArg
             if (pass0) q[n_q + mbcnt(pm)] = CvQEntry{off, x | (y << 16), vnf};
             n_q += (uint32_t)__popcll(pm);
             __builtin_amdgcn_wave_barrier();
-            if (n_q > (uint32_t)CV_QCAP - 64u) cv_flush<TREES, COUNT>(a, img, timg, table, q, n_q, slot, frame, lane);
+            if (n_q > (uint32_t)CV_QCAP - 64u) {
+                if constexpr (ROC) cv_flush_roc<TREES, COUNT>(a, img, timg, table, q, n_q, slot, frame, lane);
+                else cv_flush<TREES, COUNT>(a, img, timg, table, q, n_q, slot, frame, lane);
+            }
         }
-        if (!STAGE_TREE && n_q != 0u) cv_flush<TREES, COUNT>(a, img, timg, table, q, n_q, slot, frame, lane);
+        if (!STAGE_TREE && n_q != 0u) {
+            if constexpr (ROC) cv_flush_roc<TREES, COUNT>(a, img, timg, table, q, n_q, slot, frame, lane);
+            else cv_flush<TREES, COUNT>(a, img, timg, table, q, n_q, slot, frame, lane);
+        }
         __builtin_amdgcn_wave_barrier();
     }
 }
 
-template <bool TREES, bool STAGE_TREE, bool PRUNE = false, bool EXH = false>
+template <bool TREES, bool STAGE_TREE, bool PRUNE = false, bool EXH = false, bool ROC = false>
 static void cv_launch(const CvArgs& a, bool count, dim3 g, dim3 b, hipStream_t stream) {
-    if (count) hipLaunchKernelGGL((cv_profile_pass<TREES, true, STAGE_TREE, PRUNE, EXH>), g, b, 0, stream, a);
-    else       hipLaunchKernelGGL((cv_profile_pass<TREES, false, STAGE_TREE, PRUNE, EXH>), g, b, 0, stream, a);
+    if (count) hipLaunchKernelGGL((cv_profile_pass<TREES, true, STAGE_TREE, PRUNE, EXH, ROC>), g, b, 0, stream, a);
+    else       hipLaunchKernelGGL((cv_profile_pass<TREES, false, STAGE_TREE, PRUNE, EXH, ROC>), g, b, 0, stream, a);
 }
 
-int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream_, bool prune, bool exhaustive) {
+int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream_, bool prune, bool exhaustive,
+                           bool roc) {
     hipStream_t stream = (hipStream_t)stream_;
     dim3 g(n_blocks), b(CV_WAVES_PER_BLOCK * 64);
+    if (roc) {   // (the host asks for reject levels on the exhaustive grid only)
+        if (!exhaustive || prune) return (int)hipErrorInvalidValue;
+        if (stage_tree) {
+            if (trees) cv_launch<true, true, false, true, true>(a, count, g, b, stream);
+            else       cv_launch<false, true, false, true, true>(a, count, g, b, stream);
+        } else {
+            if (trees) cv_launch<true, false, false, true, true>(a, count, g, b, stream);
+            else       cv_launch<false, false, false, true, true>(a, count, g, b, stream);
+        }
+        return (int)hipGetLastError();
+    }
     if (exhaustive) {   // (never together with pruning: the scale-image branch does not read doCannyPruning)
         if (stage_tree) {
             if (trees) cv_launch<true, true, false, true>(a, count, g, b, stream);

@@ -186,10 +186,10 @@ __device__ __forceinline__ double cv_stage_sum_pairs(rsrc_t img, kptr<NodeRecDev
 // with four coalesced 16-byte loads), every window is evaluated by all lanes at once (window offset uniform, corner offsets
 // per lane), a __ballot gives the block's verdict bits; then lane w adds window w's leaf values IN STUMP ORDER (the leaf values
 // come through the scalar cache).  Returns the pass mask (bit w: window w passes).  Upright features only (the caller checks).
-// `masks`: n x CV_TAIL_BLOCKS words of LDS scratch.
+// `masks`: n x CV_TAIL_BLOCKS words of LDS scratch.  cv_tail_stage_sum: lane w's return value is window w's stage sum (0 from n on).
 template <bool F64 = false, typename E>
-__device__ __forceinline__ unsigned long long cv_tail_stage(rsrc_t img, const uint32_t* recs_g, kptr<NodeRecDev> tab, uint32_t n_nodes, double thr_stage,
-                                                            const E* q, uint32_t n, unsigned long long* masks, uint32_t lane) {
+__device__ __forceinline__ double cv_tail_stage_sum(rsrc_t img, const uint32_t* recs_g, kptr<NodeRecDev> tab, uint32_t n_nodes, const E* q, uint32_t n,
+                                                    unsigned long long* masks, uint32_t lane) {
     const uint32_t n_blocks = (n_nodes + 63u) >> 6;
     for (uint32_t b = 0; b < n_blocks; ++b) {
         const uint32_t j = b * 64u + lane;
@@ -235,7 +235,14 @@ __device__ __forceinline__ unsigned long long cv_tail_stage(rsrc_t img, const ui
         }
     }
     __builtin_amdgcn_wave_barrier();   // every lane has read its masks
-    return __ballot(have && stage_sum >= thr_stage);
+    return stage_sum;
+}
+
+template <bool F64 = false, typename E>
+__device__ __forceinline__ unsigned long long cv_tail_stage(rsrc_t img, const uint32_t* recs_g, kptr<NodeRecDev> tab, uint32_t n_nodes, double thr_stage,
+                                                            const E* q, uint32_t n, unsigned long long* masks, uint32_t lane) {
+    const double stage_sum = cv_tail_stage_sum<F64>(img, recs_g, tab, n_nodes, q, n, masks, lane);
+    return __ballot(lane < n && stage_sum >= thr_stage);
 }
 
 // variance_norm_factor of the window at `off` bytes / `po` elements (cvRunHaarClassifierCascadeSum, tempcv.cpp:822-832): mean and
@@ -293,6 +300,73 @@ __device__ __forceinline__ void cv_flush_to(const CvArgs& a, rsrc_t img, rsrc_t 
         n = m;
     }
     if (n != 0u) emit(q, n);
+    n = 0;
+}
+
+// cvHaarDetectObjectsForROC's report of a window (tempcv.cpp:1084-1095): the lanes with `mine` set append a CvRocDet each through the
+// detection ticket (a.det holds CvRocDet records in a ROC call, a.det_cap counts them).  Wave-uniform control flow.
+__device__ __forceinline__ void cv_roc_report(const CvArgs& a, bool mine, uint32_t x, uint32_t y, uint32_t slot, uint32_t frame, uint32_t level,
+                                              double weight, uint32_t lane) {
+    const unsigned long long rm = __ballot(mine);
+    if (rm == 0ull) return;
+    uint32_t g = 0;
+    if (lane == 0) g = atomicAdd(a.det_count, (uint32_t)__popcll(rm));
+    g = __builtin_amdgcn_readfirstlane(g);
+    const uint32_t pos = g + mbcnt(rm);
+    if (mine && pos < a.det_cap) reinterpret_cast<CvRocDet*>(a.det)[pos] = CvRocDet{x, y, slot, frame, level, 0u, weight};
+}
+
+// cv_flush_to for a ROC call: the same sweep, the same sums; from stage n_stages - 3 on, who fails a stage is reported with (that stage,
+// its sum) before the compaction drops it, and who passes the last stage with (n_stages, the last stage's sum) — `n + result < 4`,
+// -result and stage_sum of tempcv.cpp:1086-1093.  The host refuses cascades of fewer than 4 stages, so stage 0 never reports.
+template <bool TREES, bool COUNT>
+__device__ __forceinline__ void cv_flush_roc(const CvArgs& a, rsrc_t img, rsrc_t timg, kptr<NodeRecDev> table, CvQEntry* q, uint32_t& n,
+                                             uint32_t slot, uint32_t frame, uint32_t lane) {
+    kptr<StageDev> stages = as_k(a.stages);
+    for (uint32_t s = 1; s < a.n_stages && n != 0u; ++s) {
+        if (COUNT && lane == 0) atomicAdd(a.stage_entered + s, (unsigned long long)n);
+        kptr<NodeRecDev> tab = table + stages[s].first_node;
+        const uint32_t n_nodes = stages[s].n_nodes, f64 = stages[s].cv_f64;
+        const double thr = (double)stages[s].threshold;
+        const bool near_end = s + 3u >= a.n_stages, last = s + 1u == a.n_stages;
+        uint32_t m = 0;
+        const bool upright = !TREES && a.tilted == nullptr;
+        if (upright && n <= a.tail_max && n_nodes >= 16u && n_nodes <= CV_TAIL_BLOCKS * 64u) {
+            const uint32_t* recs_g = reinterpret_cast<const uint32_t*>((uintptr_t)(table + stages[s].first_node));
+            unsigned long long* masks = reinterpret_cast<unsigned long long*>(q + CV_TAIL_MAX);
+            const double ssum = f64 != 0u ? cv_tail_stage_sum<true>(img, recs_g, tab, n_nodes, q, n, masks, lane)
+                                          : cv_tail_stage_sum<false>(img, recs_g, tab, n_nodes, q, n, masks, lane);
+            const bool have = lane < n, pass = have && ssum >= thr;
+            const unsigned long long pm = __ballot(pass);
+            const CvQEntry e = q[have ? lane : 0u];
+            if (near_end)
+                cv_roc_report(a, have && (!pass || last), e.xy & 0xffffu, e.xy >> 16, slot, frame, pass ? a.n_stages : s, ssum, lane);
+            __builtin_amdgcn_wave_barrier();
+            if (pass) q[mbcnt(pm)] = e;
+            n = (uint32_t)__popcll(pm);
+            __builtin_amdgcn_wave_barrier();
+            continue;
+        }
+        for (uint32_t base = 0; base < n; base += 64u) {
+            const uint32_t i = base + lane;
+            const bool act = i < n;
+            const CvQEntry e = q[act ? i : 0u];
+            double ssum = 0.0;
+            bool pass = false;
+            if (act) {
+                ssum = cv_stage_sum_mode<TREES>(img, timg, tab, n_nodes, e.off, e.vnf, f64, a.tree2);
+                pass = ssum >= thr;
+            }
+            if (near_end)
+                cv_roc_report(a, act && (!pass || last), e.xy & 0xffffu, e.xy >> 16, slot, frame, pass ? a.n_stages : s, ssum, lane);
+            const unsigned long long mask = __ballot(pass);
+            __builtin_amdgcn_wave_barrier();
+            if (pass) q[m + mbcnt(mask)] = e;
+            m += (uint32_t)__popcll(mask);
+            __builtin_amdgcn_wave_barrier();
+        }
+        n = m;
+    }
     n = 0;
 }
 

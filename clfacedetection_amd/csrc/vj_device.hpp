@@ -429,8 +429,19 @@ struct CvArgs {
 // launch_cv_profile_pass(..., prune): the CV_HAAR_DO_CANNY_PRUNING variants (tempcv.cpp:1147-1158)
 // exhaustive: CV_HAAR_SCALE_IMAGE's grid (tempcv.cpp:1079-1102) — every position is evaluated, a reject skips nothing, no border rule;
 // a scale is a pyramid level in the canvas (ystep 1 or 2, positions and detections in the level's own coordinates)
+// roc: cvHaarDetectObjectsForROC's outputRejectLevels (tempcv.cpp:1084-1095; exhaustive grid only) — CvArgs::det is
+// an array of CvRocDet and det_cap counts those: a window is reported with the stage it reached and that stage's sum
 int launch_cv_profile_pass(const CvArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream, bool prune = false,
-                           bool exhaustive = false);
+                           bool exhaustive = false, bool roc = false);
+
+// One reported window of a ROC call: a linear cascade reports who passes (level = the stage count, weight = the last stage's sum) and
+// who fails one of the last three stages (level = that stage, weight = its sum); a stage tree reports the accepted windows only.
+struct CvRocDet {
+    uint32_t x, y, slot, frame;   // as CvDet
+    uint32_t level, pad;
+    double weight;                // stage_sum of the last stage evaluated, the f64 the verdict compared
+};
+static_assert(sizeof(CvRocDet) == 32, "CvRocDet is 32 bytes");
 
 // CV_HAAR_FIND_BIGGEST_OBJECT (VJ_FLAG_CV_FIND_BIGGEST; vj_cv_biggest.hip): the scales run from the largest window
 // down, one round each, and every frame carries its own search state on the device — written by cv_biggest_update only, read by

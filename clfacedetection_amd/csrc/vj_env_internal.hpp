@@ -135,6 +135,7 @@ struct CvPlan {
     // slot = position in the walk, scale_idx = n_factors - 1 - slot; every scale on cv_biggest_pass (no tiles, no pruning, no pyramid)
     bool find_biggest = false;
     bool scale_image = false;
+    bool roc = false;                 // vj_detect_opencv_roc: a scale-image plan whose levels all stay on the row kernel
     std::vector<double> level_factor;   // per scale slot: what a position of the level is multiplied by
     uint32_t canvas_w = 0, canvas_h = 0, canvas_pitch = 0, n_pyr_levels = 0, n_pyr_units = 0;
     DevBuf d_pyr_levels, d_pyr_taps;
@@ -348,8 +349,9 @@ struct vj_env : vj::Tunables {
     typedef std::tuple<PlanKey, int> BalanceKey;    // the plan key with the cascade's content hash and split = 0, batch-size class
     std::map<BalanceKey, Balance> balance;
     uint64_t balance_tick = 0;
-    typedef std::tuple<uint64_t, int, int, int, int, uint64_t, int> CvPlanKey;   // cascade uid, W, H, min size, bits of the scale factor,
+    typedef std::tuple<uint64_t, int, int, int, int, uint64_t, int, int> CvPlanKey;   // cascade uid, W, H, min size, bits of the scale factor,
                                                                                   // call of <= 4 frames (bit 0) | canny pruning (bit 1) | scale image (bit 2) | find biggest (bit 3)
+                                                                                  // | reject levels (bit 4), the level at which a ROC call's maxSize ends the level loop (-1: none)
     std::map<CvPlanKey, std::unique_ptr<vj::CvPlan>> cv_plans;
     typedef std::tuple<uint64_t, int, uint64_t> CvRoiPlanKey;   // cascade uid, frame width (the tables' stride), bits of the scale factor
     std::map<CvRoiPlanKey, std::unique_ptr<vj::CvRoiPlan>> cv_roi_plans;

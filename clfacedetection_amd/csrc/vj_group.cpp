@@ -11,6 +11,7 @@
 #include "vj_internal.hpp"
 
 #include <algorithm>
+#include <cfloat>
 #include <climits>
 #include <cstdlib>
 
@@ -50,9 +51,15 @@ static int label_components(const std::vector<IRect>& v, double eps, std::vector
     return ncls;
 }
 
-// AgroupRectangles(rectList, groupThreshold, eps, weights, 0) (tempcv.cpp:145-243).
-void group_rectangles(std::vector<IRect>* rects, int group_threshold, double eps, std::vector<int>* weights) {
-    weights->clear();
+// AgroupRectangles(rectList, groupThreshold, eps, weights, levelWeights) (tempcv.cpp:145-243).  level_weights == nullptr: the
+// plain overloads (:245-253), `weights` is an output, the classes' member counts.  Else the ROC overload (:255-258): `weights`
+// comes in as the rectangles' reject levels and `level_weights` as their stage sums; a class is judged by its greatest level,
+// and both go out per kept class — the quirks of the original stay (a threshold <= 0 overwrites the levels with 1 and leaves
+// the stage sums; the nested-rectangle filter weighs the OTHER class by its member count; the greatest sum starts from DBL_MIN,
+// the smallest POSITIVE double, which only a class without a member of a level above 0 keeps).
+void group_rectangles(std::vector<IRect>* rects, int group_threshold, double eps, std::vector<int>* weights,
+                      std::vector<double>* level_weights = nullptr) {
+    const std::vector<int> in_levels = level_weights ? *weights : std::vector<int>();
     if (group_threshold <= 0 || rects->empty()) {
         weights->assign(rects->size(), 1);
         return;
@@ -72,15 +79,30 @@ void group_rectangles(std::vector<IRect>* rects, int group_threshold, double eps
         rr[c].h = acc(rr[c].h, (*rects)[i].h);
         rw[c]++;
     }
+    std::vector<int> rl(ncls, 0);              // rejectLevels
+    std::vector<double> rlw(ncls, DBL_MIN);    // rejectWeights
+    if (level_weights && !in_levels.empty() && !level_weights->empty()) {   // (:176-189)
+        for (size_t i = 0; i < labels.size(); ++i) {
+            const int c = labels[i];
+            if (in_levels[i] > rl[c]) {
+                rl[c] = in_levels[i];
+                rlw[c] = (*level_weights)[i];
+            } else if (in_levels[i] == rl[c] && (*level_weights)[i] > rlw[c]) {
+                rlw[c] = (*level_weights)[i];
+            }
+        }
+    }
     auto sat = [](float v) { return v > (float)INT_MAX ? INT_MAX : (int)v; };
     for (int i = 0; i < ncls; ++i) {
         const float s = 1.f / rw[i];
         rr[i] = IRect{sat(rr[i].x * s), sat(rr[i].y * s), sat(rr[i].w * s), sat(rr[i].h * s)};
     }
     std::vector<IRect> out;
+    weights->clear();
+    if (level_weights) level_weights->clear();
     for (int i = 0; i < ncls; ++i) {
         const IRect r1 = rr[i];
-        const int n1 = rw[i];
+        const int n1 = level_weights ? rl[i] : rw[i];
         if (n1 <= group_threshold) continue;
         int j;
         for (j = 0; j < ncls; ++j) {  // filter out small rectangles inside large rectangles
@@ -97,6 +119,7 @@ void group_rectangles(std::vector<IRect>* rects, int group_threshold, double eps
         if (j == ncls) {
             out.push_back(r1);
             weights->push_back(n1);
+            if (level_weights) level_weights->push_back(rlw[i]);
         }
     }
     rects->swap(out);
@@ -132,4 +155,38 @@ extern "C" int vj_group_rectangles(vj_rect* rects, uint32_t* count, int group_th
     for (size_t k = 0; k < out.size(); ++k) rects[k] = out[k];
     *count = (uint32_t)out.size();
     return VJ_OK;
+}
+
+extern "C" int vj_group_rectangles_levels(vj_rect* rects, int32_t* levels, double* weights, int n, int group_threshold, double eps) {
+    if (n < 0 || (n > 0 && (!rects || !levels || !weights)) || !(eps >= 0.0)) return -VJ_ERR_ARG;
+    for (int k = 0; k < n; ++k) {   // image coordinates, as vj_group_rectangles asks
+        const vj_rect& r = rects[k];
+        const int lim = 1 << 20;
+        if (r.x < -lim || r.x > lim || r.y < -lim || r.y > lim || r.w < 0 || r.w > lim || r.h < 0 || r.h > lim) {
+            vj::set_error("rectangle %d is not an image rectangle", k);
+            return -VJ_ERR_ARG;
+        }
+    }
+    if (group_threshold <= 0) {   // (:147-156: nothing is grouped and the "weights", here the levels, are set to 1)
+        for (int k = 0; k < n; ++k) levels[k] = 1;
+        return n;
+    }
+    int m = 0;   // results written so far (never ahead of the frame being read)
+    for (int i = 0; i < n;) {
+        int j = i;
+        while (j < n && rects[j].frame == rects[i].frame) ++j;
+        const int32_t frame = rects[i].frame;
+        std::vector<vj::IRect> v;
+        std::vector<int> lv(levels + i, levels + j);
+        std::vector<double> lw(weights + i, weights + j);
+        for (int k = i; k < j; ++k) v.push_back(vj::IRect{rects[k].x, rects[k].y, rects[k].w, rects[k].h});
+        vj::group_rectangles(&v, group_threshold, eps, &lv, &lw);
+        for (size_t k = 0; k < v.size(); ++k, ++m) {
+            rects[m] = vj_rect{v[k].x, v[k].y, v[k].w, v[k].h, 0.0f, frame, -1};
+            levels[m] = lv[k];
+            weights[m] = lw[k];
+        }
+        i = j;
+    }
+    return m;
 }

@@ -387,6 +387,39 @@ typedef struct vj_cv_params {
 void vj_cv_params_default(vj_cv_params* p);
 int  vj_detect_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
                       const vj_cv_params* p, vj_result* out);
+/* cvHaarDetectObjectsForROC(image, cascade, storage, rejectLevels, levelWeights, scale_factor, min_neighbors, flags, min_size,
+ * max_size, outputRejectLevels = true) (tempcv.hpp:282-286, :389-395; tempcv.cpp:1188-1503) — the function cvHaarDetectObjects wraps
+ * (:1505-1516), with the two things only it has:
+ *   reject levels  In the CV_HAAR_SCALE_IMAGE branch every grid window that passes the cascade of n stages, or fails one of its last
+ *                  three stages n-3, n-2, n-1, is reported (:1084-1095) with the stage it reached (n for a pass) and stage_sum of the
+ *                  last stage evaluated — the f64 sum the verdict compared, bit for bit.  Stage trees return 0 on every reject
+ *                  (:834-861): only accepted windows are reported, with level n and the sum of the stage whose pass ended the walk.
+ *   max_w, max_h   maxSize: the level loop ends at the first window larger than it (:1285); a zero member means the frame (:1230).
+ * min_neighbors != 0 groups each frame with groupRectangles' level overload (vj_group_rectangles_levels, threshold min_neighbors —
+ * not max(min_neighbors, 1)).  flags: VJ_FLAG_CV_SCALE_IMAGE must be set; VJ_FLAG_COUNTERS fills the counters vj_detect_opencv fills
+ * for the same frames; VJ_FLAG_CV_CANNY_PRUNING and VJ_FLAG_CV_ROUGH_SEARCH are ignored, as the branch ignores them.  Refused with
+ * VJ_ERR_UNSUPPORTED, `out` left empty, each because the reference's answer is not a meaningful result:
+ *   without VJ_FLAG_CV_SCALE_IMAGE    the scale-cascade invoker (:1116-1185) never pushes a level: empty lists, or, once grouped
+ *                                     against them, nothing at all;
+ *   with VJ_FLAG_CV_FIND_BIGGEST      it clears scale-image (:1227) and then indexes an empty rweights (:1486);
+ *   a cascade of fewer than 4 stages  n + result < 4 holds for rejects at stage 0: the result is every grid position.
+ * Batches, sub-batches, BGR / BGRA and device-resident frames as in vj_detect_opencv.  The buffer of reported windows starts at
+ * the configured "det_cap" and grows on overflow.                                                                              */
+typedef struct vj_cv_roc_params {
+    int32_t  min_w, min_h, max_w, max_h;   /* 0 = none / frame size */
+    double   scale_factor;
+    uint32_t min_neighbors;
+    uint32_t flags;                        /* must hold VJ_FLAG_CV_SCALE_IMAGE; VJ_FLAG_COUNTERS optional */
+} vj_cv_roc_params;
+typedef struct vj_roc_result {
+    vj_result r;              /* rects sorted by (frame, scale_idx, y, x); raw: weight 0; grouped: scale_idx -1, weight 0 */
+    int32_t*  reject_levels;  /* r.count entries, parallel to r.rects */
+    double*   level_weights;  /* r.count entries */
+} vj_roc_result;
+void vj_cv_roc_params_default(vj_cv_roc_params* p);   /* scale_factor 1.1, flags VJ_FLAG_CV_SCALE_IMAGE, the rest 0 */
+int  vj_detect_opencv_roc(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
+                          const vj_cv_roc_params* p, vj_roc_result* out);
+void vj_roc_result_free(vj_roc_result* r);
 /* What vj_detect_opencv's plan for (c, width x height, p, a batch of n_frames) holds, with the environment's
  * current settings: the LDS-tile scales and, for stage trees on tiles, the survivors' tree queue.  The
  * queue's shift and split belong to the plan: they record what earlier calls with that plan did.        */
@@ -483,6 +516,13 @@ void vj_stream_destroy(vj_stream* s);
  * group_threshold members, weight = members, scale_idx = -1.  vj_detect applies it with
  * MAX(min_neighbors, 1) and eps 0.2 (clod.cpp:11, 1326) when min_neighbors != 0.            */
 int vj_group_rectangles(vj_rect* rects, uint32_t* count, int group_threshold, double eps);
+/* groupRectangles(rectList, rejectLevels, levelWeights, groupThreshold, eps) (tempcv.cpp:255-258 -> :145-243), host code, in place,
+ * per frame (`rects` sorted by frame); returns the new count, or -VJ_ERR_ARG.  Per class: the greatest level of its members and,
+ * among the members at that level, the greatest weight (starting from DBL_MIN); a class is kept iff its greatest LEVEL is >
+ * group_threshold; the nested-rectangle filter compares that level with the OTHER class's member count (n2 = rweights[j]).  Out:
+ * the averaged rectangle (weight 0, scale_idx -1), the class's level and weight.  group_threshold <= 0, literally (:147-156):
+ * nothing is grouped, every level becomes 1 and the weights stay.                                                          */
+int vj_group_rectangles_levels(vj_rect* rects, int32_t* levels, double* weights, int n, int group_threshold, double eps);
 
 /* ---------------------------------------------------------------- multi-GPU */
 /* One environment per device (clodInitEnvironment(device_index), clod.cpp:72-100), one rank per environment — threads of
