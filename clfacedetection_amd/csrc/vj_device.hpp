@@ -49,8 +49,15 @@ struct ScaleDev {
     uint32_t grp_te_lt;
     uint32_t grp_te_dh;
     int32_t  grp_te_dw;
+    // Block-transposed records of the wave-independent tail (TILE_TAIL_BLOCK_RECS NodeRec slots per block of
+    // CascadeArgs::sp_blocks, see tile_wave_tail), in NodeRec units like the tables they restate: of tile_table_first (the ROI
+    // pass) and of grp_table_first (the tile list).  Only filled when the plan has the tail.
+    uint32_t tile_tail_first;
+    uint32_t grp_tail_first;
+    uint32_t sq32;         // != 0: win_w * win_h <= SQ32_MAX_AREA — the squared sum of any window of this scale is below 2^32, so
+                           // the tile passes combine the LOW dwords of its four sqsum corners (mod 2^32: exact)
 };
-static_assert(sizeof(ScaleDev) == 140, "ScaleDev is 140 bytes");
+static_assert(sizeof(ScaleDev) == 152, "ScaleDev is 152 bytes");
 
 // One cascade stage with its resolved successors (tempcv.cpp:834-861 flattened).
 struct StageDev {
@@ -143,6 +150,13 @@ constexpr int TILE_WS_MAX_WINDOWS = 512;  // wave-split finish: 8 chunks of pack
 constexpr int TILE_SEG_MAX_WINDOWS = 256;  // stage-tree chains inside a tile: population + reject list (256 entries each) around the scratch
 constexpr int TILE_SP_MAX_BLOCKS = 4;     // blocks of 64 stumps per stage at most (stages of <= 256 nodes)
 constexpr int TILE_SP_BLOCK = 64;         // stumps evaluated per round and window (= lanes of a wave)
+// The tail's copy of a block: four sub-arrays back to back — dwords 0..3 of the block's 64 records, dwords 4..7, dwords 8..11
+// (16 bytes per record each, 1 KiB) and dwords 12..13 (8 bytes per record, 512 bytes) — so that a wave's load of one piece
+// covers consecutive bytes; partial blocks are padded with zero records.  3584 bytes = 56 NodeRec slots.
+constexpr int TILE_TAIL_BLOCK_RECS = (3 * 16 + 8) * TILE_SP_BLOCK / 64;
+// 255^2 * 66051 < 2^32 <= 255^2 * 66052: the largest window area whose squared sum always fits a dword
+constexpr uint32_t SQ32_MAX_AREA = 66051;
+static_assert(65025ull * SQ32_MAX_AREA < (1ull << 32) && 65025ull * (SQ32_MAX_AREA + 1ull) >= (1ull << 32), "SQ32_MAX_AREA");
 
 struct CascadeArgs {
     const uint32_t* sum;        // batch sum images, frame f at f * frame_elems

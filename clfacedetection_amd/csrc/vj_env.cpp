@@ -182,6 +182,7 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
         sd.scale_f = si.scale;
         sd.win_w = (uint32_t)si.win_w;
         sd.win_h = (uint32_t)si.win_h;
+        sd.sq32 = e->sq32 && (uint64_t)sd.win_w * sd.win_h <= SQ32_MAX_AREA ? 1u : 0u;
         table.resize(table.size() + n_nodes);
         int rc = build_node_table(c, W, si, table.data() + sd.table_first);
         if (rc) return rc;
@@ -373,6 +374,30 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
         }
     }
     pl->n_sp_blocks = (uint32_t)sp_blocks.size();
+    // The tail's own copy of the tile tables (TILE_TAIL_BLOCK_RECS): per table and block, the 14 dwords of the block's records
+    // transposed into four lane-contiguous pieces.  The fields are the table's; only their place differs.  (The gather chain's
+    // stump-parallel tail reads frame-stride tables in blocks of its own: it keeps the record form.)
+    if (pl->wave_tail && !sp_blocks.empty()) {
+        auto emit_tail = [&](uint32_t table_first) {
+            const uint32_t tail_first = (uint32_t)table.size();
+            table.resize(table.size() + sp_blocks.size() * (size_t)TILE_TAIL_BLOCK_RECS);   // (zeroed: the padding records)
+            for (size_t x = 0; x < sp_blocks.size(); ++x) {
+                uint32_t* blk = reinterpret_cast<uint32_t*>(table.data() + tail_first + x * (size_t)TILE_TAIL_BLOCK_RECS);
+                const uint32_t jn = sp_blocks[x].desc & 0xffu;
+                for (uint32_t j = 0; j < jn; ++j) {
+                    const uint32_t* rec = reinterpret_cast<const uint32_t*>(&table[table_first + sp_blocks[x].first_node + j]);
+                    for (uint32_t d = 0; d < 12u; ++d) blk[(d / 4u) * 4u * TILE_SP_BLOCK + j * 4u + d % 4u] = rec[d];
+                    for (uint32_t d = 12u; d < 14u; ++d) blk[12u * TILE_SP_BLOCK + j * 2u + (d - 12u)] = rec[d];
+                }
+            }
+            return tail_first;
+        };
+        for (ScaleDev& sd : pl->scales) {
+            if (!sd.tile_rw) continue;
+            sd.tile_tail_first = emit_tail(sd.tile_table_first);
+            sd.grp_tail_first = sd.grp_table_first == sd.tile_table_first ? sd.tile_tail_first : emit_tail(sd.grp_table_first);
+        }
+    }
     // Balance between the two chains: tile_split scales' worth of tile work (counted from the largest tile
     // scale down, fractions by window rows) moves to the global-gather chain, which overlaps the tile chain.
     {
@@ -1957,6 +1982,7 @@ int vj_env_create(int device_index, vj_env** out) {
     }
     e->n_cu = prop.multiProcessorCount;
     if (const char* g = getenv("VJ_TILE_GROUP")) e->tile_group = std::max(1, std::min(atoi(g), (int)MAX_SCALES));
+    if (const char* g = getenv("VJ_SQ32")) e->sq32 = atoi(g) != 0;
     if (const int hrc = prepare_tile_kernels()) {
         set_error("raising the dynamic LDS limit on device %d failed: %s", device_index, hipGetErrorString((hipError_t)hrc));
         return VJ_ERR_HIP;

@@ -1777,7 +1777,9 @@ int launch_roi_chain(const RoiArgs& r, const CascadeArgs& a, bool from_dets, boo
 // windows.  They are dealt to the waves — wave w takes windows w, w + 8, ..., at most 32, lane k holding its k-th — and
 // from there on a wave runs its own windows to the end of the cascade without a workgroup barrier.  Per stage, in the
 // host's blocks of <= 64 consecutive stumps (CascadeArgs::sp_blocks): lane j holds stump j's record, which the wave loads
-// itself (coalesced, the next block in flight while this one is evaluated); per window of the wave's list a block gives
+// itself from the block-transposed copy of the table (TILE_TAIL_BLOCK_RECS: every piece of the 64 records is one run of
+// consecutive bytes, 8 cache lines per 16-byte load instead of one per lane or two; the next block in flight while this
+// one is evaluated); per window of the wave's list a block gives
 // 64 verdict bits — which stumps answered alpha[1], one __ballot — and the block's leaf sum (a DPP butterfly).  After the
 // stage's last block lane k adds window k's block sums: when that clears the stage threshold by more than sp_delta (the
 // host's bound on the difference between any two summation orders) the stage is decided; otherwise the lane walks the
@@ -1787,6 +1789,7 @@ int launch_roi_chain(const RoiArgs& r, const CascadeArgs& a, bool from_dets, boo
 template <bool COUNT, typename Img>
 __device__ __forceinline__ uint32_t tile_wave_tail(const CascadeArgs& a, const Img& img_by_window,
                                                    const uint32_t* table /* the scale's tile table, global */,
+                                                   const uint32_t* tail /* ... its block-transposed copy */,
                                                    const QEntry* lds_q, QEntry* out, unsigned long long* masks, uint32_t T,
                                                    uint32_t st_begin, uint32_t n_stages, uint32_t lane, uint32_t wib) {
     const auto img = img_by_window.by_stump();
@@ -1804,14 +1807,21 @@ __device__ __forceinline__ uint32_t tile_wave_tail(const CascadeArgs& a, const I
     if (nw == 0u) return 0u;
     const uint32_t g_end = a.n_sp_blocks;
     uint32_t g = stages[st_begin].sp_first;   // running block number over all stages
-    // the record of stump `lane` of block x (lanes past the block's end take its first stump: gathers stay in the tile)
+    // the record of stump `lane` of block x (lanes past the block's end take a zero record: they gather the window's own
+    // origin, inside the tile)
+    // (the block's address is scalar and the lane adds a 32-bit offset, made opaque so that it is recomputed per block:
+    // hoisted out of the stage loop it stays live through the whole tail, and the region kernel loses a wave of occupancy)
+    constexpr uint32_t BLOCK_BYTES = TILE_TAIL_BLOCK_RECS * 64u, PIECE = TILE_SP_BLOCK * 16u;
     auto fetch = [&](uint32_t x, uint4& r0, uint4& r1, uint4& r2, uint2& r3) {
-        const uint32_t jn = blocks[2u * x + 1u] & 0xffu;
-        const uint32_t* src = table + ((size_t)blocks[2u * x] + (lane < jn ? lane : 0u)) * 16u;
-        r0 = reinterpret_cast<const uint4*>(src)[0];
-        r1 = reinterpret_cast<const uint4*>(src)[1];
-        r2 = reinterpret_cast<const uint4*>(src)[2];
-        r3 = reinterpret_cast<const uint2*>(src)[6];
+        const char* src = reinterpret_cast<const char*>(tail) + (size_t)x * BLOCK_BYTES;
+        uint32_t o = lane * 8u;
+        asm volatile("" : "+v"(o));
+        r3 = *reinterpret_cast<const uint2*>(src + 3u * PIECE + o);
+        o *= 2u;
+        asm volatile("" : "+v"(o));
+        r0 = *reinterpret_cast<const uint4*>(src + o);
+        r1 = *reinterpret_cast<const uint4*>(src + PIECE + o);
+        r2 = *reinterpret_cast<const uint4*>(src + 2u * PIECE + o);
     };
     uint4 c0, c1, c2;
     uint2 c3;
@@ -2336,7 +2346,8 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
             const uint32_t pos_base = scales[slot].pos_base;
             // while the tile is in flight: this wave's share of the tile's tw*th windows (a run of consecutive
             // tile-local indices, at least one full wave per wave), their positions, and the four squared-sum
-            // corners of each (HBM, 8 bytes per lane) — all issued before the barrier that drains the staging
+            // corners of each (HBM; the low dwords alone where the scale's window area keeps the sum below 2^32,
+            // ScaleDev::sq32) — all issued before the barrier that drains the staging
             q = lds_q + wib * TILE_WAVE_CAP;   // (re-packing below moves the wave's queue base)
             const uint32_t n_tile = tw * th;
             const uint32_t per_wave = max(64u, (n_tile + TILE_WAVES - 1u) / TILE_WAVES);   // <= TILE_WAVE_CAP (host)
@@ -2348,8 +2359,11 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
             const uint32_t e_lt = scales[slot].e_lt, e_dh = scales[slot].e_dh;
             const float area = scales[slot].area;
             constexpr int NCH = TILE_WAVE_CAP / 64;
+            const bool sq32 = scales[slot].sq32 != 0u;   // (uniform)
             uint32_t w_lo4[NCH];
-            uint64_t w_q[NCH];
+            float w_q[NCH];   // the squared sum, already converted as the variance fill below wants it (the same f32 from
+                              // either width): one dword per window stays live across the barrier, which waits for
+                              // these loads anyhow
             bool w_valid[NCH];
 #pragma unroll
             for (int k = 0; k < NCH; ++k) {
@@ -2360,7 +2374,7 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                 if (!ROI && a.skip_bits != nullptr && w_valid[k])   // uniform test
                     w_valid[k] = window_visited(a, frame, scales[slot].skip_base, scales[slot].skip_wpr, nx, ix, iy);
                 w_lo4[k] = 0u;
-                w_q[k] = 0ull;
+                w_q[k] = 0.0f;
                 if (w_valid[k]) {
                     const uint32_t x = ox + window_pos(a, pos_base, ix, step);
                     const uint32_t y = oy + window_pos(a, pos_base, iy, step);
@@ -2368,8 +2382,12 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                     const uint32_t e = y * a.stride + x;
                     w_lo4[k] = ((y - y0) * pitch + (half ? (x - x0) >> 1 : x - x0)) * 4u;
                     const uint32_t c0 = e_lt, c1 = e_lt + e_dw, c2 = e_lt + e_dh, c3 = e_lt + e_dh + e_dw;
-                    w_q[k] = ld_u64(sq_f, e * 8u, c0 * 8u) - ld_u64(sq_f, e * 8u, c1 * 8u) - ld_u64(sq_f, e * 8u, c2 * 8u) +
-                             ld_u64(sq_f, e * 8u, c3 * 8u);
+                    if (sq32)   // mod 2^32 the corners' low dwords give the sum itself
+                        w_q[k] = (float)(uint32_t)(ld_u32(sq_f, e * 8u, c0 * 8u) - ld_u32(sq_f, e * 8u, c1 * 8u) -
+                                                   ld_u32(sq_f, e * 8u, c2 * 8u) + ld_u32(sq_f, e * 8u, c3 * 8u));
+                    else
+                        w_q[k] = (float)(uint64_t)(ld_u64(sq_f, e * 8u, c0 * 8u) - ld_u64(sq_f, e * 8u, c1 * 8u) -
+                                                   ld_u64(sq_f, e * 8u, c2 * 8u) + ld_u64(sq_f, e * 8u, c3 * 8u));
                 }
             }
             __syncthreads();
@@ -2386,7 +2404,7 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                     const uint32_t s4 = img.ld(lo4, te_lt) - img.ld(lo4, te_lt + te_dw) - img.ld(lo4, te_lt + te_dh) +
                                         img.ld(lo4, te_lt + te_dh + te_dw);
                     const float mean = (a.signed_mean ? (float)(int32_t)s4 : (float)s4) / area;
-                    float variance = (float)w_q[k];
+                    float variance = w_q[k];
                     variance = (variance / area) - (mean * mean);
                     en.var = variance >= 0.0f ? sqrtf(variance) : 1.0f;
                     en.off = lo4;
@@ -2513,7 +2531,8 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                             // (32 windows x TILE_SP_MAX_BLOCKS each) — all inside the queue area
                             q = lds_q + TILE_SP_MAX_WINDOWS + wib * 32u;
                             n = tile_wave_tail<COUNT>(
-                                a, img, a.table + (size_t)table_first * 16u, lds_q, q,
+                                a, img, a.table + (size_t)table_first * 16u,
+                                a.table + (size_t)(ROI ? scales[slot].tile_tail_first : scales[slot].grp_tail_first) * 16u, lds_q, q,
                                 reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS + TILE_WAVES * 32) +
                                     wib * 32u * TILE_SP_MAX_BLOCKS,
                                 left, s_next, n_stages_total, lane, wib);
