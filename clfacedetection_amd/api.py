@@ -81,6 +81,24 @@ class ScaleInfo(C.Structure):
                 ("area", C.c_uint32), ("nx", C.c_int32), ("ny", C.c_int32), ("accepted", C.c_int32)]
 
 
+class TileInfo(C.Structure):
+    """vj_tile_info: one accepted scale of a plan and, where it runs on LDS tiles, its tile shape."""
+    _fields_ = [("scale_idx", C.c_int32), ("scale", C.c_float), ("step", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("lds_class", C.c_int32), ("tile_w", C.c_int32), ("tile_h", C.c_int32), ("pitch", C.c_int32), ("rows", C.c_int32),
+                ("reach_x", C.c_int32), ("reach_y", C.c_int32), ("lead_scale_idx", C.c_int32), ("tile_row_end", C.c_int32)]
+
+
+class TilePlanInfo(C.Structure):
+    """vj_tile_plan_info: the LDS blocks of a plan's tile launches."""
+    _fields_ = [("header_bytes", C.c_uint32), ("gather_reserve_bytes", C.c_uint32), ("max_tile_windows", C.c_uint32),
+                ("n_classes", C.c_uint32), ("class_lds", C.c_uint32 * 4), ("class_per_cu", C.c_int32 * 4),
+                ("class_tiles", C.c_uint32 * 4)]
+
+
+VJ_PLAN_TILES_FORMER_SHAPES = 1
+VJ_PLAN_TILES_NO_GROUPS = 2
+
+
 class _Image(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32),
                 ("on_device", C.c_int32), ("channels", C.c_int32)]
@@ -166,6 +184,8 @@ _SIGNATURES = {
     "vj_plan_scales": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(ScaleInfo), C.c_int,
                                  C.POINTER(C.c_int)]),
     "vj_plan_feature_table": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ScaleInfo), C.c_void_p, C.c_void_p]),
+    "vj_plan_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_uint32, C.POINTER(TilePlanInfo),
+                                C.POINTER(TileInfo), C.c_int, C.POINTER(C.c_int)]),
     "vj_env_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "vj_env_destroy": (None, [C.c_void_p]),
     "vj_env_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -331,6 +351,19 @@ class Cascade:
         _check(load_library().vj_plan_feature_table(self._h, width, C.byref(scale), off.ctypes.data,
                                                     wts.ctypes.data), "vj_plan_feature_table")
         return off, wts
+
+    def plan_tiles(self, width: int, height: int, n_frames: int = 64, params: Params | None = None,
+                   flags: int = 0) -> tuple[TilePlanInfo, list[TileInfo]]:
+        """vj_plan_tiles: the tile shapes of the plan a fresh environment builds for n_frames frames (host only)."""
+        p = params or default_params()
+        n = C.c_int(0)
+        info = TilePlanInfo()
+        lib = load_library()
+        _check(lib.vj_plan_tiles(self._h, width, height, C.byref(p), n_frames, flags, None, None, 0, C.byref(n)), "vj_plan_tiles")
+        arr = (TileInfo * max(n.value, 1))()
+        _check(lib.vj_plan_tiles(self._h, width, height, C.byref(p), n_frames, flags, C.byref(info), arr, n.value, C.byref(n)),
+               "vj_plan_tiles")
+        return info, list(arr)[:n.value]
 
     def shard_scales(self, width: int, height: int, rank: int, world: int, params: Params | None = None) -> list[int]:
         """vj_shard_scales: the scale indices of `rank` when one frame is split over `world` ranks by scale."""

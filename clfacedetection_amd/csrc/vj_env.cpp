@@ -78,8 +78,17 @@ struct TileThresholds {
     int min_windows, accept_windows, max_dwords_per_window;
 };
 
-static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_params& p, Plan* pl, float tile_split,
-                      const TileThresholds& thresholds, bool one_pass = false) {
+// What the host-only plan query (vj_plan_tiles) asks of build_plan: no device copies, the shape search as it was before
+// round 11 (the budget of the former stump-parallel finish, the coarser candidate lists, the widest shape on a tie), and
+// the feature reach of every scale of the plan.
+struct PlanBuildOptions {
+    bool upload = true;
+    bool former_shapes = false;
+    std::vector<std::pair<uint32_t, uint32_t>>* tile_reach = nullptr;
+};
+
+static int build_plan(const vj_env* e, const vj_cascade& c, int W, int H, const vj_params& p, Plan* pl, float tile_split,
+                      const TileThresholds& thresholds, bool one_pass = false, const PlanBuildOptions& opt = PlanBuildOptions()) {
     pl->tile_split = tile_split;
     if ((int)c.stages.size() > VJ_MAX_STAGES) {
         set_error("cascade has %zu stages; at most %d are supported", c.stages.size(), VJ_MAX_STAGES);
@@ -142,19 +151,20 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
     const size_t n_nodes = c.nodes.size();
 
     // wave-independent tail of a tile (tile_wave_tail): stages of more than TILE_SP_MAX_BLOCKS * 64 nodes rule it out.
-    // It needs no LDS beyond the header.  The tile shapes are still chosen as if the header also held what the former
-    // stump-parallel finish kept there (two blocks of 14-dword records at a pitch of 65, the leaf values of the largest
-    // stage): that LDS is no longer allocated, and growing the tiles into it is a change of its own.
-    uint32_t shape_header_bytes = TILE_LDS_HEADER;
+    // It needs no LDS beyond the header (its survivor and verdict areas lie in the queue area), so the shape search below
+    // budgets exactly what a launch allocates in front of the image tile: TILE_LDS_HEADER.  (Until round 11 it also
+    // subtracted the tables of the former stump-parallel finish — 8 992 bytes for frontalface_alt — which no launch
+    // allocated any more; opt.former_shapes restates that search for the plan dump, tools/plan_dump.py.)
+    const uint32_t tile_header_bytes = TILE_LDS_HEADER;
+    uint32_t shape_header_bytes = tile_header_bytes;
     if (!pl->trees && !pl->general && e->tile_sp_begin < (int)c.stages.size()) {
         uint32_t mx = 0;
         for (size_t s = 0; s < c.stages.size(); ++s) mx = std::max(mx, pl->prog.n_nodes[s]);
         if (mx <= (uint32_t)TILE_SP_MAX_BLOCKS * TILE_SP_BLOCK) {
             pl->wave_tail = true;
-            shape_header_bytes += ((2u * 14u * (TILE_SP_BLOCK + 1u) + 2u * mx + 3u) & ~3u) * 4u;
+            if (opt.former_shapes) shape_header_bytes += ((2u * 14u * (TILE_SP_BLOCK + 1u) + 2u * mx + 3u) & ~3u) * 4u;
         }
     }
-    const uint32_t tile_header_bytes = TILE_LDS_HEADER;
     std::vector<NodeRec> table;
     std::vector<uint32_t> pos_tab;
     std::vector<std::pair<uint32_t, uint32_t>> tile_reach;   // per scale: how far right / down of a window origin its features read
@@ -226,7 +236,9 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
         }
         if ((!pl->general || pl->general_prefix) && si.ny < 65536 && si.nx < 65536) {
             // candidate tile shapes; per class the shape with the most windows that fits wins
-            static const uint32_t kTw[] = {64, 48, 32, 24, 16, 12, 8}, kTh[] = {32, 24, 16, 12, 8, 6, 4};
+            // (the kernel maps a tile-local index to (t / tw, t % tw): any width does)
+            static const uint32_t kTw[] = {64, 56, 48, 40, 32, 24, 16, 12, 8}, kTh[] = {32, 28, 24, 20, 16, 12, 8, 6, 4};
+            auto former = [&](uint32_t v) { return opt.former_shapes && (v == 56u || v == 40u || v == 28u || v == 20u); };
             uint32_t best_cls = TILE_CLASSES, best_n = 0, b_tw = 0, b_th = 0, b_pitch = 0, b_rows = 0;
             for (uint32_t cls = 0; cls < TILE_CLASSES && best_n < (uint32_t)thresholds.min_windows; ++cls) {
                 const int kb = e->tile_class_kb[cls];
@@ -238,7 +250,8 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
                 for (uint32_t tw : kTw)
                     for (uint32_t th : kTh) {
                         const uint32_t nwt = tw * th;
-                        if (nwt > TILE_WAVES * TILE_WAVE_CAP || nwt < 64 || nwt <= best_n) continue;
+                        if (nwt > TILE_WAVES * TILE_WAVE_CAP || nwt < 64 || nwt < best_n || (nwt == best_n && best_cls != cls)) continue;
+                        if (former(tw) || former(th)) continue;
                         // rows staged 16 bytes per lane (not the de-interleaved step-2 tiles, whose sources are 8 bytes
                         // apart): pitch a multiple of 4 dwords, not of 32 (rows would share banks); step 2: an odd pitch
                         uint32_t pitch = (uint32_t)std::ceil((double)(tw - 1) * (double)si.step) + 3u + reach_x;
@@ -252,6 +265,8 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
                         if ((uint64_t)pitch * rows * 4u > budget) continue;
                         // staging a tile must stay far cheaper than gathering its windows from L2
                         if ((uint64_t)pitch * rows > (uint64_t)thresholds.max_dwords_per_window * nwt) continue;
+                        // as many windows as the best so far: the shape that stages fewer dwords (else the wider one stays)
+                        if (nwt == best_n && (opt.former_shapes || pitch * rows >= b_pitch * b_rows)) continue;
                         best_cls = cls; best_n = nwt; b_tw = tw; b_th = th; b_pitch = pitch; b_rows = rows;
                     }
             }
@@ -555,6 +570,11 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
                     pl->tile_units.push_back(UnitDev{slot, ix0 | (iy0 << 16), lead > slot ? lead - slot + 1u : 0u, 0});
             pl->class_lds[cls] = std::max(pl->class_lds[cls], L.tile_pitch * L.tile_rows * 4u);
         }
+        // the region pass lays a scale's tile out in the scale's OWN shape and launches with this class's block: a group
+        // member's own shape may be larger than the shape of the lead it follows on the frame's tile list
+        for (const ScaleDev& sd : pl->scales)
+            if (sd.tile_rw && sd.tile_class == cls && pl->class_lds[cls])
+                pl->class_lds[cls] = std::max(pl->class_lds[cls], sd.tile_pitch * sd.tile_rows * 4u);
         if (pl->class_lds[cls]) pl->class_lds[cls] += tile_header_bytes;
     }
     pl->class_first[TILE_CLASSES] = (uint32_t)pl->tile_units.size();
@@ -609,6 +629,8 @@ static int build_plan(vj_env* e, const vj_cascade& c, int W, int H, const vj_par
         pl->n_skip_segs = (uint32_t)skip_segs.size();
     }
 
+    if (opt.tile_reach) *opt.tile_reach = tile_reach;
+    if (!opt.upload) return VJ_OK;   // (the host-only plan query)
     int rc;
     if (!skip_units.empty()) {
         if ((rc = pl->d_skip_units.ensure(skip_units.size() * sizeof(UnitDev)))) return rc;
@@ -879,6 +901,15 @@ static int balance_import(vj_env* e, const char* path) {
     return VJ_OK;
 }
 
+// The tile thresholds of a plan: the environment's, those of small_frame_class (1, 2), or the feedback's lower ones (3).
+static TileThresholds thresholds_for(const vj_env* e, int small) {
+    TileThresholds th{e->tile_min_windows, e->tile_accept_windows, e->tile_max_dwords_per_window};
+    if (small == 2) th = TileThresholds{64, 64, 8000};
+    else if (small == 1) th = TileThresholds{256, 256, 2000};
+    else if (small == 3) th = TileThresholds{std::min(384, th.min_windows), std::min(384, th.accept_windows), th.max_dwords_per_window};
+    return th;
+}
+
 static int get_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_params& p, Plan** out, int n_frames = 1 << 20) {
     const vj_env::Balance* bal = balance_of(e, c, W, H, p, n_frames, false);
     const BalanceChoice choice = bal ? balance_choice(bal, n_frames) : BalanceChoice{e->split_for(n_frames, p), 0, false};
@@ -908,11 +939,7 @@ static int get_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_param
         }
     }
     auto pl = std::make_unique<Plan>();
-    TileThresholds th{e->tile_min_windows, e->tile_accept_windows, e->tile_max_dwords_per_window};
-    if (small == 2) th = TileThresholds{64, 64, 8000};
-    else if (small == 1) th = TileThresholds{256, 256, 2000};
-    else if (small == 3) th = TileThresholds{std::min(384, th.min_windows), std::min(384, th.accept_windows), th.max_dwords_per_window};
-    int rc = build_plan(e, *c, W, H, p, pl.get(), split, th, one_pass);
+    int rc = build_plan(e, *c, W, H, p, pl.get(), split, thresholds_for(e, small), one_pass);
     if (rc) {
         pl->release_device();
         return rc;
@@ -3024,6 +3051,65 @@ void vj_result_free(vj_result* r) {
     free(r->rects);
     r->rects = nullptr;
     r->count = 0;
+}
+
+// The tile side of the plan a fresh environment builds for a call of n_frames frames, on the host alone: an environment
+// object that never opens a device carries the shipped settings, and build_plan leaves out the device copies.
+int vj_plan_tiles(const vj_cascade* c, int width, int height, const vj_params* p, int n_frames, uint32_t flags,
+                  vj_tile_plan_info* info, vj_tile_info* out, int cap, int* n) {
+    if (!c || !p || !n || width <= 0 || height <= 0 || n_frames <= 0 || (cap > 0 && !out) ||
+        (flags & ~(uint32_t)(VJ_PLAN_TILES_FORMER_SHAPES | VJ_PLAN_TILES_NO_GROUPS)))
+        return VJ_ERR_ARG;
+    int rc = check_params(*p);
+    if (rc) return rc;
+    auto e = std::make_unique<vj_env>();
+    if (flags & VJ_PLAN_TILES_NO_GROUPS) e->tile_group = 1;
+    Plan pl;
+    PlanBuildOptions opt;
+    std::vector<std::pair<uint32_t, uint32_t>> reach;
+    opt.upload = false;
+    opt.former_shapes = (flags & VJ_PLAN_TILES_FORMER_SHAPES) != 0u;
+    opt.tile_reach = &reach;
+    const bool one_pass = n_frames <= e->one_pass_max_frames && (uint64_t)width * (uint64_t)height >= 800000ull;
+    rc = build_plan(e.get(), *c, width, height, *p, &pl, e->split_for(n_frames, *p),
+                    thresholds_for(e.get(), small_frame_class(e.get(), width, height, n_frames)), one_pass, opt);
+    if (rc) return rc;
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->header_bytes = TILE_LDS_HEADER;
+        info->gather_reserve_bytes = (uint32_t)e->tile_lds_reserve_kb * 1024u;
+        info->max_tile_windows = TILE_WAVES * TILE_WAVE_CAP;
+        info->n_classes = TILE_CLASSES;
+        for (uint32_t cls = 0; cls < TILE_CLASSES; ++cls) {
+            info->class_lds[cls] = pl.class_lds[cls];
+            info->class_per_cu[cls] = e->tile_class_kb[cls] < 0 ? -e->tile_class_kb[cls] : 0;
+            info->class_tiles[cls] = pl.class_first[cls + 1] - pl.class_first[cls];
+        }
+    }
+    *n = (int)pl.scales.size();
+    for (int k = 0; k < *n && k < cap; ++k) {
+        const ScaleDev& sd = pl.scales[(size_t)k];
+        vj_tile_info& t = out[k];
+        memset(&t, 0, sizeof(t));
+        t.scale_idx = (int32_t)sd.scale_idx;
+        t.scale = sd.scale_f;
+        t.step = sd.step;
+        t.nx = (int32_t)sd.nx;
+        t.ny = (int32_t)sd.ny;
+        t.reach_x = (int32_t)reach[(size_t)k].first;
+        t.reach_y = (int32_t)reach[(size_t)k].second;
+        t.lds_class = -1;
+        t.lead_scale_idx = t.scale_idx;
+        if (!sd.tile_rw) continue;
+        t.lds_class = (int32_t)sd.tile_class;
+        t.tile_w = (int32_t)sd.tile_tw;
+        t.tile_h = (int32_t)sd.tile_th;
+        t.pitch = (int32_t)sd.tile_pitch;
+        t.rows = (int32_t)sd.tile_rows;
+        t.lead_scale_idx = (int32_t)pl.scales[pl.tile_lead[(size_t)k]].scale_idx;
+        t.tile_row_end = (int32_t)sd.tile_row_end;
+    }
+    return VJ_OK;
 }
 
 }  // extern "C"

@@ -214,6 +214,39 @@ int vj_plan_scales(const vj_cascade* c, int width, int height, const vj_params* 
 int vj_plan_feature_table(const vj_cascade* c, int width, const vj_scale_info* s,
                           uint32_t* offsets, float* weights);
 
+/* The LDS-tile side of the plan that a fresh environment (shipped settings) builds for a call of n_frames
+ * frames: which scales run on image tiles, in which shapes.  Host only, read only, no device needed.
+ * One entry per accepted scale with windows, in scale order.                                           */
+typedef struct vj_tile_info {
+    int32_t  scale_idx;
+    float    scale, step;
+    int32_t  nx, ny;
+    int32_t  lds_class;        /* LDS class of the scale's own tile shape; -1: the scale stays on the
+                                  global-gather chain (the fields below are then 0)                   */
+    int32_t  tile_w, tile_h;   /* windows per tile row / window rows per tile                         */
+    int32_t  pitch, rows;      /* the staged image tile: dwords per row, rows                         */
+    int32_t  reach_x, reach_y; /* how far right / below a window's origin its features read           */
+    int32_t  lead_scale_idx;   /* scale group: the member whose tile the frame's tile list stages for
+                                  all of them (its class, shape and class block); itself: not grouped.
+                                  The region pass stages every scale in its own shape.                */
+    int32_t  tile_row_end;     /* window rows [0, tile_row_end) run on tiles; the chain balance gave the
+                                  rest to the global-gather chain                                     */
+} vj_tile_info;
+typedef struct vj_tile_plan_info {
+    uint32_t header_bytes;          /* LDS a tile workgroup holds in front of its image tile           */
+    uint32_t gather_reserve_bytes;  /* LDS per CU left to the global-gather chain's workgroup          */
+    uint32_t max_tile_windows;      /* most windows a tile may hold (a tile holds at least 64)         */
+    uint32_t n_classes;
+    uint32_t class_lds[4];          /* dynamic LDS of each class launch (0: the class has no tiles)    */
+    int32_t  class_per_cu[4];       /* workgroups of the class that share a CU (0: a fixed budget)     */
+    uint32_t class_tiles[4];        /* tiles per frame of each class launch                            */
+} vj_tile_plan_info;
+#define VJ_PLAN_TILES_FORMER_SHAPES 1u  /* shapes as chosen before the tiles grew into the LDS of the former
+                                           stump-parallel finish (a diagnostic: tools/plan_dump.py)   */
+#define VJ_PLAN_TILES_NO_GROUPS     2u  /* one tile per scale (what VJ_TILE_GROUP=1 gives)              */
+int vj_plan_tiles(const vj_cascade* c, int width, int height, const vj_params* p, int n_frames,
+                  uint32_t flags, vj_tile_plan_info* info, vj_tile_info* out, int cap, int* n);
+
 /* ------------------------------------------------------------- environment */
 /* clodInitEnvironment/clodReleaseEnvironment (clod.h:61-65, clod.cpp:72-100,
  * 173-180) — one env per device; not thread-safe (neither is the reference).   */

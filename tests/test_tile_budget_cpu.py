@@ -1,0 +1,118 @@
+"""The LDS budget of the tile planner (build_plan's shape search) against what a tile launch really allocates, on the host
+alone through vj_plan_tiles: every shipped cascade that takes the tile path, four frame sizes (the last one smaller than
+a single full tile), a single frame and a batch.
+
+The kernel's dynamic LDS is header + image tile, header = TILE_LDS_HEADER (the packed-window queues and the per-wave
+counts; the wave-independent tail's survivor and verdict areas lie inside the queue area).  Until round 11 the planner
+also subtracted the tables of the former stump-parallel finish, which no launch allocated any more: the last test fails
+if those phantom bytes come back."""
+import glob
+import math
+import os
+
+import pytest
+
+from clfacedetection_amd import VJ_FLAG_TILTED_AS_UPRIGHT, Cascade, default_params
+from clfacedetection_amd.api import DATA_DIR, VJ_PLAN_TILES_FORMER_SHAPES, VJ_PLAN_TILES_NO_GROUPS
+
+CU_LDS = 160 * 1024
+ROUNDING_RESERVE = 2048            # kept free so that the nested class blocks can be rounded up to whole granules
+NAMES = sorted(os.path.basename(p)[len("haarcascade_"):-len(".vjc")] for p in glob.glob(os.path.join(DATA_DIR, "haarcascade_*.vjc")))
+SIZES = [(1920, 1080), (1280, 720), (640, 480), (100, 80)]
+BATCHES = [1, 64]
+_PLANS = {}
+
+
+def plan(name, W, H, n_frames, flags=0):
+    key = (name, W, H, n_frames, flags)
+    if key not in _PLANS:
+        c = Cascade.load(name)
+        _PLANS[key] = c.plan_tiles(W, H, n_frames, default_params(flags=VJ_FLAG_TILTED_AS_UPRIGHT), flags)
+    return _PLANS[key]
+
+
+def budget(info, cls, extra_header=0):
+    """what the shape search may spend on the image tile of class `cls` (-k classes: k workgroups share a CU)"""
+    k = info.class_per_cu[cls]
+    assert k > 0, "the shipped classes are all of the shared-CU kind"
+    return ((CU_LDS - info.gather_reserve_bytes - ROUNDING_RESERVE) // k - info.header_bytes - extra_header) & ~63
+
+
+def tile_scales(tiles):
+    return [t for t in tiles if t.lds_class >= 0]
+
+
+def test_some_cascade_takes_the_tile_path_at_every_size():
+    for W, H in SIZES:
+        for nf in BATCHES:
+            assert any(tile_scales(plan(n, W, H, nf)[1]) for n in NAMES), (W, H, nf)
+    assert tile_scales(plan("frontalface_alt", 100, 80, 1)[1]), "the size below one full tile still runs tiles"
+    t = tile_scales(plan("frontalface_alt", 100, 80, 1)[1])[0]
+    assert t.nx < t.tile_w or t.ny < t.tile_h, "100 x 80 was chosen to hold less than one full tile"
+
+
+@pytest.mark.parametrize("flags", [0, VJ_PLAN_TILES_NO_GROUPS])
+@pytest.mark.parametrize("nf", BATCHES)
+@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("name", NAMES)
+def test_budget_invariants(name, W, H, nf, flags):
+    info, tiles = plan(name, W, H, nf, flags)
+    by_idx = {t.scale_idx: t for t in tiles}
+    ts = tile_scales(tiles)
+    if not ts:
+        assert not any(info.class_lds[k] for k in range(info.n_classes))
+        return
+    hdr = info.header_bytes
+    assert hdr == (8 * 256 * 2 + 32) * 4          # TILE_LDS_HEADER: the queues of TILE_WAVES x TILE_WAVE_CAP entries + 32 counts
+    for t in ts:
+        L = by_idx[t.lead_scale_idx]
+        nwt = t.tile_w * t.tile_h
+        # 5. windows per tile
+        assert 64 <= nwt <= info.max_tile_windows == 2048, (t.scale_idx, nwt)
+        # 1. the scale's own shape (the region pass stages it) fits the search budget and its class block; the group's shape
+        # (the frame's tile list stages it) fits the block of the launch that runs it
+        need = t.pitch * t.rows * 4
+        assert need <= budget(info, t.lds_class), (t.scale_idx, need)
+        if info.class_lds[t.lds_class]:
+            assert need + hdr <= info.class_lds[t.lds_class], (t.scale_idx, need, list(info.class_lds))
+        if t.tile_row_end > 0:
+            assert L.lds_class >= 0 and info.class_lds[L.lds_class] >= L.pitch * L.rows * 4 + hdr, (t.scale_idx, L.scale_idx)
+        # 4. the staged shape covers the reach of every window of the tile: the last window's origin, one pixel for the
+        # rounding of its position, its features' reach (inclusive)
+        for shape, who in ((t, "own"), (L, "group")):
+            span_x = math.ceil((shape.tile_w - 1) * t.step) + 1 + t.reach_x + 1
+            span_y = math.ceil((shape.tile_h - 1) * t.step) + 1 + t.reach_y + 1
+            if who == "group" and L is not t:
+                assert t.step == 2.0 and L.step == 2.0, "groups hold step-2 scales only"
+                span_x -= 1      # (step exactly 2: positions are exact)
+                span_y -= 1
+            assert span_x <= shape.pitch and span_y <= shape.rows, (t.scale_idx, who, span_x, shape.pitch, span_y, shape.rows)
+    # 2. nested blocks: class 1 is twice class 0, both whole allocation granules (the hardware's are 512 bytes)
+    b0, b1 = info.class_lds[0], info.class_lds[1]
+    if b0 and b1:
+        assert b1 == 2 * b0 and b0 % 512 == 0, (b0, b1)
+    # 3. the gather chain's workgroup plus two class-0 blocks (or one class-1 block) fit a CU
+    assert info.gather_reserve_bytes == 16 * 1024
+    assert info.gather_reserve_bytes + 2 * b0 <= CU_LDS and info.gather_reserve_bytes + b1 <= CU_LDS, (b0, b1)
+
+
+def test_bench_workload_uses_lds_the_former_budget_refused():
+    """64 x 1080p frontalface_alt: some tile scale stages more than the former budget (header + the stump-parallel finish's
+    two record blocks and leaf values: 8 992 bytes for this cascade) allowed — in its own shape and in a staged group shape."""
+    c = Cascade.load("frontalface_alt")
+    mx = int(max(c.stages["n_trees"]))
+    assert mx == 213
+    phantom = ((2 * 14 * 65 + 2 * mx + 3) & ~3) * 4
+    assert phantom == 8992
+    info, tiles = plan("frontalface_alt", 1920, 1080, 64)
+    by_idx = {t.scale_idx: t for t in tiles}
+    ts = tile_scales(tiles)
+    own = [t.scale_idx for t in ts if t.pitch * t.rows * 4 > budget(info, t.lds_class, phantom)]
+    leads = {t.lead_scale_idx for t in ts if t.tile_row_end > 0}
+    staged = [k for k in sorted(leads) if by_idx[k].pitch * by_idx[k].rows * 4 > budget(info, by_idx[k].lds_class, phantom)]
+    print("own shapes beyond the former budget:", own, "staged group shapes:", staged)
+    assert own and staged
+    # and the former search (kept for tools/plan_dump.py) really stayed inside it
+    _, former = plan("frontalface_alt", 1920, 1080, 64, VJ_PLAN_TILES_FORMER_SHAPES)
+    assert all(t.pitch * t.rows * 4 <= budget(info, t.lds_class, phantom) for t in tile_scales(former))
+    assert [(t.lds_class, t.tile_w, t.tile_h) for t in former] != [(t.lds_class, t.tile_w, t.tile_h) for t in tiles]
