@@ -95,6 +95,12 @@ class TilePlanInfo(C.Structure):
                 ("class_tiles", C.c_uint32 * 4)]
 
 
+class TileCutInfo(C.Structure):
+    """vj_tile_cut_info: how a plan divides a frame's windows between the tile chain and the global-gather chain."""
+    _fields_ = [("tile_split", C.c_float), ("gather_units", C.c_uint32), ("gather_windows", C.c_uint64),
+                ("plan_windows", C.c_uint64)]
+
+
 VJ_PLAN_TILES_FORMER_SHAPES = 1
 VJ_PLAN_TILES_NO_GROUPS = 2
 
@@ -186,6 +192,9 @@ _SIGNATURES = {
     "vj_plan_feature_table": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ScaleInfo), C.c_void_p, C.c_void_p]),
     "vj_plan_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_uint32, C.POINTER(TilePlanInfo),
                                 C.POINTER(TileInfo), C.c_int, C.POINTER(C.c_int)]),
+    "vj_plan_tiles_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_uint32, C.c_float,
+                                      C.POINTER(TilePlanInfo), C.POINTER(TileCutInfo), C.POINTER(TileInfo), C.POINTER(C.c_uint64),
+                                      C.c_int, C.POINTER(C.c_int)]),
     "vj_env_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "vj_env_destroy": (None, [C.c_void_p]),
     "vj_env_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -353,17 +362,30 @@ class Cascade:
         return off, wts
 
     def plan_tiles(self, width: int, height: int, n_frames: int = 64, params: Params | None = None,
-                   flags: int = 0) -> tuple[TilePlanInfo, list[TileInfo]]:
-        """vj_plan_tiles: the tile shapes of the plan a fresh environment builds for n_frames frames (host only)."""
+                   flags: int = 0, tile_split: float | None = None) -> tuple[TilePlanInfo, list[TileInfo]]:
+        """vj_plan_tiles: the tile shapes of the plan a fresh environment builds for n_frames frames (host only).
+        tile_split (vj_plan_tiles_split): the plan at that chain balance, negative = the shipped one; info.cut is then the
+        vj_tile_cut_info and every entry carries gather_windows, its windows on the gather chain's first-pass units."""
         p = params or default_params()
         n = C.c_int(0)
         info = TilePlanInfo()
         lib = load_library()
-        _check(lib.vj_plan_tiles(self._h, width, height, C.byref(p), n_frames, flags, None, None, 0, C.byref(n)), "vj_plan_tiles")
+        # (room for every enumerated scale: the plan holds the accepted ones; asking vj_plan_tiles for the count builds the plan twice)
+        _check(lib.vj_plan_scales(self._h, width, height, C.byref(p), None, 0, C.byref(n)), "vj_plan_scales")
         arr = (TileInfo * max(n.value, 1))()
-        _check(lib.vj_plan_tiles(self._h, width, height, C.byref(p), n_frames, flags, C.byref(info), arr, n.value, C.byref(n)),
-               "vj_plan_tiles")
-        return info, list(arr)[:n.value]
+        if tile_split is None:
+            _check(lib.vj_plan_tiles(self._h, width, height, C.byref(p), n_frames, flags, C.byref(info), arr, n.value, C.byref(n)),
+                   "vj_plan_tiles")
+            return info, list(arr)[:n.value]
+        cut = TileCutInfo()
+        gw = (C.c_uint64 * max(n.value, 1))()
+        _check(lib.vj_plan_tiles_split(self._h, width, height, C.byref(p), n_frames, flags, float(tile_split), C.byref(info),
+                                       C.byref(cut), arr, gw, n.value, C.byref(n)), "vj_plan_tiles_split")
+        info.cut = cut
+        tiles = list(arr)[:n.value]
+        for t, w in zip(tiles, gw):
+            t.gather_windows = int(w)
+        return info, tiles
 
     def shard_scales(self, width: int, height: int, rank: int, world: int, params: Params | None = None) -> list[int]:
         """vj_shard_scales: the scale indices of `rank` when one frame is split over `world` ranks by scale."""

@@ -290,7 +290,8 @@ static int build_plan(const vj_env* e, const vj_cascade& c, int W, int H, const 
                 fprintf(stderr, "vj plan: scale %d s=%.3f step=%.2f nx=%u ny=%u class %u tile %ux%u = %u windows, pitch %u rows %u (%u B)%s\n",
                         si.scale_idx, si.scale, si.step, sd.nx, sd.ny, sd.tile_class, sd.tile_tw, sd.tile_th, sd.tile_tw * sd.tile_th,
                         sd.tile_pitch, sd.tile_rows, sd.tile_pitch * sd.tile_rows * 4u, sd.tile_half ? " deinterleaved" : " x4");
-            rc = build_node_table_stride(c, sd.tile_pitch, si, table.data() + sd.tile_table_first, sd.tile_half);
+            // (the tile-stride tables only feed the device copy: the host-only query leaves their records zeroed)
+            rc = opt.upload ? build_node_table_stride(c, sd.tile_pitch, si, table.data() + sd.tile_table_first, sd.tile_half) : VJ_OK;
             if (rc) return rc;
             auto col = [&](uint32_t cx) { return sd.tile_half ? (cx & 1u) * sd.tile_half + (cx >> 1) : cx; };
             sd.te_lt = (uint32_t)si.equ_y * sd.tile_pitch + col((uint32_t)si.equ_x);
@@ -335,7 +336,7 @@ static int build_plan(const vj_env* e, const vj_cascade& c, int W, int H, const 
             const vj_scale_info& si = pl->scales_info[k];
             sd.grp_table_first = (uint32_t)table.size();
             table.resize(table.size() + n_nodes);
-            int rc = build_node_table_stride(c, L.tile_pitch, si, table.data() + sd.grp_table_first, L.tile_half);
+            int rc = opt.upload ? build_node_table_stride(c, L.tile_pitch, si, table.data() + sd.grp_table_first, L.tile_half) : VJ_OK;
             if (rc) return rc;
             auto col = [&](uint32_t cx) { return (cx & 1u) * L.tile_half + (cx >> 1); };
             sd.grp_te_lt = (uint32_t)si.equ_y * L.tile_pitch + col((uint32_t)si.equ_x);
@@ -392,7 +393,7 @@ static int build_plan(const vj_env* e, const vj_cascade& c, int W, int H, const 
     // The tail's own copy of the tile tables (TILE_TAIL_BLOCK_RECS): per table and block, the 14 dwords of the block's records
     // transposed into four lane-contiguous pieces.  The fields are the table's; only their place differs.  (The gather chain's
     // stump-parallel tail reads frame-stride tables in blocks of its own: it keeps the record form.)
-    if (pl->wave_tail && !sp_blocks.empty()) {
+    if (pl->wave_tail && !sp_blocks.empty() && opt.upload) {
         auto emit_tail = [&](uint32_t table_first) {
             const uint32_t tail_first = (uint32_t)table.size();
             table.resize(table.size() + sp_blocks.size() * (size_t)TILE_TAIL_BLOCK_RECS);   // (zeroed: the padding records)
@@ -3055,14 +3056,17 @@ void vj_result_free(vj_result* r) {
 
 // The tile side of the plan a fresh environment builds for a call of n_frames frames, on the host alone: an environment
 // object that never opens a device carries the shipped settings, and build_plan leaves out the device copies.
-int vj_plan_tiles(const vj_cascade* c, int width, int height, const vj_params* p, int n_frames, uint32_t flags,
-                  vj_tile_plan_info* info, vj_tile_info* out, int cap, int* n) {
-    if (!c || !p || !n || width <= 0 || height <= 0 || n_frames <= 0 || (cap > 0 && !out) ||
+// tile_split < 0: the shipped chain balance of that batch size (vj_env::split_for), else the given one — what a call runs
+// after vj_env_configure("tile_split", ...) or where the balance feedback has walked to.
+static int plan_tiles_query(const vj_cascade* c, int width, int height, const vj_params* p, int n_frames, uint32_t flags, float tile_split,
+                            vj_tile_plan_info* info, vj_tile_cut_info* cut, vj_tile_info* out, uint64_t* gather_windows, int cap, int* n) {
+    if (!c || !p || !n || width <= 0 || height <= 0 || n_frames <= 0 || (cap > 0 && !out) || tile_split != tile_split ||
         (flags & ~(uint32_t)(VJ_PLAN_TILES_FORMER_SHAPES | VJ_PLAN_TILES_NO_GROUPS)))
         return VJ_ERR_ARG;
     int rc = check_params(*p);
     if (rc) return rc;
     auto e = std::make_unique<vj_env>();
+    if (const char* g = getenv("VJ_TILE_GROUP")) e->tile_group = std::max(1, std::min(atoi(g), (int)MAX_SCALES));   // (as vj_env_create reads it)
     if (flags & VJ_PLAN_TILES_NO_GROUPS) e->tile_group = 1;
     Plan pl;
     PlanBuildOptions opt;
@@ -3071,9 +3075,28 @@ int vj_plan_tiles(const vj_cascade* c, int width, int height, const vj_params* p
     opt.former_shapes = (flags & VJ_PLAN_TILES_FORMER_SHAPES) != 0u;
     opt.tile_reach = &reach;
     const bool one_pass = n_frames <= e->one_pass_max_frames && (uint64_t)width * (uint64_t)height >= 800000ull;
-    rc = build_plan(e.get(), *c, width, height, *p, &pl, e->split_for(n_frames, *p),
+    rc = build_plan(e.get(), *c, width, height, *p, &pl, tile_split < 0.0f ? e->split_for(n_frames, *p) : tile_split,
                     thresholds_for(e.get(), small_frame_class(e.get(), width, height, n_frames)), one_pass, opt);
     if (rc) return rc;
+    // the windows every first-pass unit of the gather chain covers, clipped to its scale's grid as the grid pass clips them
+    std::vector<uint64_t> unit_windows(pl.scales.size(), 0);
+    for (const UnitDev& u : pl.units) {
+        const ScaleDev& sd = pl.scales[u.scale];
+        if (u.bw != 0u) {
+            const uint32_t ix0 = u.first & 0xffffu, iy0 = u.first >> 16, bh = u.count / u.bw;
+            if (ix0 < sd.nx && iy0 < sd.ny)
+                unit_windows[u.scale] += (uint64_t)std::min(u.bw, sd.nx - ix0) * std::min(bh, sd.ny - iy0);
+        } else if (u.first < sd.nwin) {
+            unit_windows[u.scale] += std::min(u.count, sd.nwin - u.first);
+        }
+    }
+    if (cut) {
+        memset(cut, 0, sizeof(*cut));
+        cut->tile_split = pl.tile_split;
+        cut->gather_units = (uint32_t)pl.units.size();
+        for (uint64_t w : unit_windows) cut->gather_windows += w;
+        cut->plan_windows = pl.windows_per_frame;
+    }
     if (info) {
         memset(info, 0, sizeof(*info));
         info->header_bytes = TILE_LDS_HEADER;
@@ -3098,6 +3121,7 @@ int vj_plan_tiles(const vj_cascade* c, int width, int height, const vj_params* p
         t.ny = (int32_t)sd.ny;
         t.reach_x = (int32_t)reach[(size_t)k].first;
         t.reach_y = (int32_t)reach[(size_t)k].second;
+        if (gather_windows) gather_windows[k] = unit_windows[(size_t)k];
         t.lds_class = -1;
         t.lead_scale_idx = t.scale_idx;
         if (!sd.tile_rw) continue;
@@ -3110,6 +3134,16 @@ int vj_plan_tiles(const vj_cascade* c, int width, int height, const vj_params* p
         t.tile_row_end = (int32_t)sd.tile_row_end;
     }
     return VJ_OK;
+}
+
+int vj_plan_tiles(const vj_cascade* c, int width, int height, const vj_params* p, int n_frames, uint32_t flags,
+                  vj_tile_plan_info* info, vj_tile_info* out, int cap, int* n) {
+    return plan_tiles_query(c, width, height, p, n_frames, flags, -1.0f, info, nullptr, out, nullptr, cap, n);
+}
+
+int vj_plan_tiles_split(const vj_cascade* c, int width, int height, const vj_params* p, int n_frames, uint32_t flags, float tile_split,
+                        vj_tile_plan_info* info, vj_tile_cut_info* cut, vj_tile_info* out, uint64_t* gather_windows, int cap, int* n) {
+    return plan_tiles_query(c, width, height, p, n_frames, flags, tile_split, info, cut, out, gather_windows, cap, n);
 }
 
 }  // extern "C"

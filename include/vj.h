@@ -246,6 +246,21 @@ typedef struct vj_tile_plan_info {
 #define VJ_PLAN_TILES_NO_GROUPS     2u  /* one tile per scale (what VJ_TILE_GROUP=1 gives)              */
 int vj_plan_tiles(const vj_cascade* c, int width, int height, const vj_params* p, int n_frames,
                   uint32_t flags, vj_tile_plan_info* info, vj_tile_info* out, int cap, int* n);
+/* vj_plan_tiles at a chain balance of the caller's choice: what a call runs after
+ * vj_env_configure("tile_split", ...) or where the balance feedback has walked to.  tile_split < 0: the shipped value
+ * of that batch size (exactly what vj_plan_tiles gives).  `cut` (may be NULL) says how the plan divides a frame's
+ * windows between the two chains: tile windows are the sum of nx * tile_row_end over the tile scales, the rest must
+ * be covered by the first-pass units of the global-gather chain.  `gather_windows` (may be NULL; cap entries, one per
+ * entry of `out`) receives the windows of each scale those units cover.  Host only, read only, like vj_plan_tiles. */
+typedef struct vj_tile_cut_info {
+    float    tile_split;            /* the chain balance the plan was built with                       */
+    uint32_t gather_units;          /* first-pass units of the global-gather chain, per frame          */
+    uint64_t gather_windows;        /* windows those units cover (each clipped to its scale's grid)    */
+    uint64_t plan_windows;          /* windows per frame of the whole plan (vj_count_windows)          */
+} vj_tile_cut_info;
+int vj_plan_tiles_split(const vj_cascade* c, int width, int height, const vj_params* p, int n_frames,
+                        uint32_t flags, float tile_split, vj_tile_plan_info* info, vj_tile_cut_info* cut,
+                        vj_tile_info* out, uint64_t* gather_windows, int cap, int* n);
 
 /* ------------------------------------------------------------- environment */
 /* clodInitEnvironment/clodReleaseEnvironment (clod.h:61-65, clod.cpp:72-100,
