@@ -12,5 +12,5 @@ from .api import (  # noqa: F401
     FrameStream, Params, VjError,
     clifIntegral, clodDetectObjects, clodInitBuffers, clodInitEnvironment, clodReleaseBuffers,
     clodReleaseEnvironment, cvHaarDetectObjects, cvHaarDetectObjectsForROC, default_params, group_rectangles,
-    group_rectangles_levels, load_library,
+    cvRunHaarClassifierCascade, group_rectangles_levels, load_library, run_windows_opencv,
 )

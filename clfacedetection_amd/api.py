@@ -160,6 +160,8 @@ class _RocResult(C.Structure):
     _fields_ = [("r", _Result), ("reject_levels", C.c_void_p), ("level_weights", C.c_void_p)]
 
 
+WINDOW_DTYPE = np.dtype([("frame", "<i4"), ("x", "<i4"), ("y", "<i4"), ("scale", "<i4")])                 # vj_window
+WINDOW_RESULT_DTYPE = np.dtype([("result", "<i4"), ("reserved", "<i4"), ("stage_sum", "<f8")])           # vj_window_result
 RECT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("weight", "<f4"),
                        ("frame", "<i4"), ("scale_idx", "<i4")])
 STAGE_DTYPE = np.dtype([("first_tree", "<i4"), ("n_trees", "<i4"), ("threshold", "<f4"), ("parent", "<i4"),
@@ -229,6 +231,9 @@ _SIGNATURES = {
     "vj_detect_opencv_roc": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(CvRocParams),
                                        C.POINTER(_RocResult)]),
     "vj_roc_result_free": (None, [C.POINTER(_RocResult)]),
+    "vj_run_windows_opencv": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32,
+                                        C.c_int, C.c_void_p]),
+    "vj_run_windows_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vj_cv_plan_info_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CvParams), C.POINTER(CvPlanInfo)]),
     "vj_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params),
                             C.POINTER(_Result)]),
@@ -675,6 +680,16 @@ class Environment:
         out.reject_levels, out.level_weights = levels, weights
         return out
 
+    def run_windows_opencv(self, cascade: Cascade, frames, windows, scales, start_stage: int = 0, color: bool = False):
+        """vj_run_windows_opencv: see the module-level run_windows_opencv."""
+        return _run_windows(self._h, cascade, frames, windows, scales, start_stage, color)
+
+    def run_windows_timing(self) -> tuple[float, float]:
+        """vj_run_windows_timing: (integral_ms, pass_ms) of the last run_windows_opencv call, device times summed over its sub-batches."""
+        i, p = C.c_float(0), C.c_float(0)
+        _check(load_library().vj_run_windows_timing(self._h, C.byref(i), C.byref(p)), "vj_run_windows_timing")
+        return float(i.value), float(p.value)
+
     def cv_plan_info(self, cascade: Cascade, width: int, height: int, n_frames: int, min_size=(0, 0),
                      scale_factor: float = 1.1, min_neighbors: int = 0, flags: int = 0) -> CvPlanInfo:
         """vj_cv_plan_info_get: the plan detect_opencv uses for a batch of n_frames width x height frames."""
@@ -898,3 +913,44 @@ def cvHaarDetectObjectsForROC(image, cascade: Cascade, env: Environment, scale_f
         if flags & cv_bit:
             vj_flags |= vj_bit
     return env.detect_opencv_roc(cascade, image, min_size, max_size, scale_factor, min_neighbors, vj_flags)
+
+def _run_windows(env_handle, cascade: Cascade, frames, windows, scales, start_stage, color):
+    w = np.asarray(windows)
+    if w.dtype != WINDOW_DTYPE:
+        if not np.issubdtype(w.dtype, np.integer) and w.size:
+            raise ValueError("windows must be integer rows of (frame, x, y, scale)")
+        if w.size and (w.ndim != 2 or w.shape[1] != 4):
+            raise ValueError("windows must be rows of (frame, x, y, scale)")
+        if w.size and (w.min() < -2**31 or w.max() >= 2**31):
+            raise ValueError("window members must fit an int32")
+        w = w.reshape(-1, 4).astype(np.int32)
+    w = np.ascontiguousarray(w)
+    n = int(w.shape[0])
+    sc = np.ascontiguousarray(np.atleast_1d(np.asarray(scales, np.float64)))
+    if sc.ndim != 1:
+        raise ValueError("scales must be a 1-D list of factors")
+    if start_stage != int(start_stage):
+        raise ValueError("start_stage must be an integer")
+    imgs, nf, keep = Environment._images(frames, color)
+    out = np.zeros(n, WINDOW_RESULT_DTYPE)
+    lib = load_library()
+    _check(lib.vj_run_windows_opencv(env_handle, cascade._h, imgs, nf, sc.ctypes.data, len(sc), w.ctypes.data, n, int(start_stage),
+                                     out.ctypes.data), "vj_run_windows_opencv")
+    return out["result"].copy(), out["stage_sum"].copy()
+
+
+def run_windows_opencv(frames, cascade: Cascade, env: Environment, windows, scales, start_stage: int = 0, color: bool = False):
+    """cvSetImagesForHaarClassifierCascade + cvRunHaarClassifierCascade on a list of windows, on the device (vj_run_windows_opencv).
+    windows: rows of (frame, x, y, scale) with `scale` an index into `scales` (any finite factors > 0).  Returns (results int32[n],
+    stage_sums float64[n]) in the order of `windows`: result -1 at the border, 1 on a pass, -i on a reject at stage i of a linear
+    cascade (0 at stage 0), 0 on every reject of a stage tree; stage_sum is the f64 sum of the stage whose verdict ended the run
+    (0.0 with result -1 and with start_stage >= the stage count).  frames: 2-D uint8 arrays of one size, (h, w, 3|4) BGR / BGRA
+    arrays with color=True, or DeviceFrames.  The arguments are checked before the environment is used."""
+    return _run_windows(env._h if env is not None else None, cascade, frames, windows, scales, start_stage, color)
+
+
+def cvRunHaarClassifierCascade(gray, cascade: Cascade, env: Environment, pt, scale: float = 1.0, start_stage: int = 0) -> int:
+    """cvRunHaarClassifierCascade(cascade, pt, start_stage) (tempcv.cpp:974-984) after cvSetImagesForHaarClassifierCascade(cascade,
+    sum, sqsum, tilted, scale) on `gray`'s integral images: one window through run_windows_opencv; pt = (x, y)."""
+    res, _ = run_windows_opencv(gray, cascade, env, [(0, int(pt[0]), int(pt[1]), 0)], [float(scale)], start_stage, color=np.ndim(gray) == 3)
+    return int(res[0])

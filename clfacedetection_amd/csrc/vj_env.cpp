@@ -2045,7 +2045,8 @@ void vj_env_destroy(vj_env* e) {
                       &e->d_skip_bits, &e->d_rois, &e->d_roi_units, &e->d_roi_det, &e->d_roi_tiles, &e->d_group, &e->d_cv_det, &e->d_cv_counts,
                       &e->d_cv_accept, &e->d_cv_tq, &e->d_cv_fail_rows, &e->d_cv_fail_walk, &e->d_run_table,
                       &e->d_canny_cls, &e->d_canny_label, &e->d_canny_flag, &e->d_edges, &e->d_edge_sum,
-                      &e->d_cv_prune_bits, &e->d_pyr, &e->d_pyr_tab, &e->d_cv_big, &e->d_cv_rois, &e->d_cv_roi_units})
+                      &e->d_cv_prune_bits, &e->d_pyr, &e->d_pyr_tab, &e->d_cv_big, &e->d_cv_rois, &e->d_cv_roi_units,
+                      &e->d_cv_points, &e->d_cv_point_units, &e->d_cv_point_scales, &e->d_cv_point_out})
         b->release();
     e->lane0.destroy();
     for (DevBuf& b : e->d_q) b.release();
@@ -2063,6 +2064,13 @@ int vj_env_device_name(const vj_env* e, char* buf, size_t cap) {
     return VJ_OK;
 }
 
+static void drop_cv_point_plans(vj_env* e) {
+    for (auto& kv : e->cv_point_cascades) kv.second->release_device();
+    e->cv_point_cascades.clear();
+    for (auto& kv : e->cv_point_plans) kv.second->release_device();
+    e->cv_point_plans.clear();
+}
+
 static void drop_plans(vj_env* e) {
     for (auto& kv : e->plans) kv.second->release_device();
     e->plans.clear();
@@ -2070,6 +2078,7 @@ static void drop_plans(vj_env* e) {
     e->cv_plans.clear();
     for (auto& kv : e->cv_roi_plans) kv.second->release_device();
     e->cv_roi_plans.clear();
+    drop_cv_point_plans(e);
 }
 
 // ----------------------------------------------------------------------------------------- tunables
@@ -2350,6 +2359,7 @@ int vj_env_configure(vj_env* e, const char* key, const char* value) {
         e->cv_plans.clear();
         for (auto& kv : e->cv_roi_plans) kv.second->release_device();
         e->cv_roi_plans.clear();
+        drop_cv_point_plans(e);
     }
     return VJ_OK;
 }

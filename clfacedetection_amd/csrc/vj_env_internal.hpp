@@ -4,6 +4,7 @@
 #include "vj_internal.hpp"
 #include "vj_device.hpp"
 #include "vj_cv_roi_host.hpp"
+#include "vj_cv_points_host.hpp"
 
 #include <hip/hip_runtime_api.h>
 
@@ -158,6 +159,24 @@ struct CvRoiPlan {
     void release_device() {
         for (DevBuf* b : {&d_table, &d_scales, &d_stages}) b->release();
     }
+};
+
+// What the window-list pass (vj_run_windows_opencv; vj_cv_points.hip) derives from the cascade alone — the stage
+// records — and from (cascade, frame stride, ONE scale): the scale's record and node table.  A call may name any number of scales;
+// each is a plan of its own, so that the scales of successive calls (a tracker's jitter set, a ROC's fixed ladder) are built once.
+struct CvPointCascade {
+    uint32_t n_stages = 0, n_order = 0;
+    bool trees = false, is_tree = false, has_tilted = false, tree2 = false;
+    DevBuf d_stages;
+    uint64_t last_used = 0;
+    void release_device() { d_stages.release(); }
+};
+struct CvPointPlan {
+    CvPointScaleDev rec = {};     // table = d_table.p once built; win_w / win_h / equRect whatever the frame's height
+    uint64_t max_reach = 0;       // furthest element a feature touches, from the window origin (valid once the table is built)
+    DevBuf d_table;               // built at the first call whose frame the window fits (no window of a larger one is evaluated)
+    uint64_t last_used = 0;
+    void release_device() { d_table.release(); }
 };
 
 }  // namespace vj
@@ -359,6 +378,13 @@ struct vj_env : vj::Tunables {
     typedef std::tuple<uint64_t, int, uint64_t> CvRoiPlanKey;   // cascade uid, frame width (the tables' stride), bits of the scale factor
     std::map<CvRoiPlanKey, std::unique_ptr<vj::CvRoiPlan>> cv_roi_plans;
     vj::DevBuf d_cv_rois, d_cv_roi_units;   // region pass of the OpenCV profile: a sub-batch's regions and work units
+    // vj_run_windows_opencv: per cascade uid; per (cascade uid, frame width, bits of the scale).  Both under plan_cache_max, least
+    // recently used first — except the plans of the call in progress, which may name more scales than that
+    std::map<uint64_t, std::unique_ptr<vj::CvPointCascade>> cv_point_cascades;
+    typedef std::tuple<uint64_t, int, uint64_t> CvPointPlanKey;
+    std::map<CvPointPlanKey, std::unique_ptr<vj::CvPointPlan>> cv_point_plans;
+    float cv_points_integral_ms = 0, cv_points_pass_ms = 0;   // ... device times of the last call, summed over its sub-batches (vj_run_windows_timing)
+    vj::DevBuf d_cv_points, d_cv_point_units, d_cv_point_scales, d_cv_point_out;   // ... a sub-batch's windows, units and verdicts; the call's scale records
     vj::DevBuf d_cv_det, d_cv_counts;   // vj_detect_opencv: detection list and counters
     vj::DevBuf d_cv_accept, d_cv_tq;    // ... stage trees on tiles: accept bitmap, the queue of the prefix's survivors
     vj::DevBuf d_cv_fail_rows, d_cv_fail_walk;   // ... per-wave fail lists of the chain sweeps (rows kernel / chain pass)

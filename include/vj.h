@@ -468,6 +468,32 @@ void vj_cv_roc_params_default(vj_cv_roc_params* p);   /* scale_factor 1.1, flags
 int  vj_detect_opencv_roc(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
                           const vj_cv_roc_params* p, vj_roc_result* out);
 void vj_roc_result_free(vj_roc_result* r);
+/* cvSetImagesForHaarClassifierCascade(cascade, sum, sqsum, tilted, scale) + cvRunHaarClassifierCascade(cascade, pt, start_stage)
+ * (tempcv.cpp:549-768, :974-984 -> cvRunHaarClassifierCascadeSum :795-972) on a caller's list of windows:
+ * out[i] is the verdict on windows[i] — the window at (x, y) of frame `frame`, the cascade set to scales[scale] — in the caller's
+ * order; nothing is sorted or deduplicated.
+ *   result      the function's return value: -1 when the border rule holds (:817-820: x < 0, y < 0, x + real_w >= W + 1 or
+ *               y + real_h >= H + 1, real = cvRound(orig * scale)); 1 on a pass; -i on a reject at stage i of a linear cascade (so
+ *               a reject at stage 0 is 0); 0 on every reject of a stage tree (:834-861).
+ *   stage_sum   the f64 the function leaves in stage_sum, bit for bit: the sum of the stage whose verdict ended the run (for a
+ *               pass the last stage evaluated); 0.0 where it is never written (result -1, or start_stage >= the stage count,
+ *               which returns 1).
+ * start_stage: linear cascades start there (:864, :952); a stage tree asserts 0 (:837): anything else is VJ_ERR_ARG, as is a
+ * negative value.  scales: any finite value > 0, not only members of a factor chain; any number of them per call (each has a node
+ * table of its own, cached per (cascade, frame width, bits of the scale) next to the other plans).  A scale whose window exceeds
+ * the frame gives -1 for every window; that is no error.  Frames: one size, gray / BGR / BGRA, host or device-resident; integrated
+ * once per call (per sub-batch when the call splits), the tilted integral only for cascades with tilted nodes.  n_windows == 0 is
+ * VJ_OK (whatever the other arguments, a null environment included; only the cascade and start_stage are checked first); a frame
+ * or scale index out of range is VJ_ERR_ARG with `out` untouched.  At most 2^27 windows per call, and a frame whose sqsum image
+ * fits one 4 GiB buffer descriptor (VJ_ERR_LIMIT). */
+typedef struct vj_window        { int32_t frame, x, y, scale; } vj_window;          /* scale: index into scales[] */
+typedef struct vj_window_result { int32_t result, reserved; double stage_sum; } vj_window_result;
+int  vj_run_windows_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
+                           const double* scales, int n_scales, const vj_window* windows, uint32_t n_windows,
+                           int start_stage, vj_window_result* out /* n_windows entries, caller's */);
+/* Device times of the environment's last vj_run_windows_opencv call that ran a pass, summed over its sub-batches: the integral
+ * images (with the tilted integral, where built) and the window-list kernel alone (hipEvents around the launch).  Either may be NULL. */
+int  vj_run_windows_timing(const vj_env* e, float* integral_ms, float* pass_ms);
 /* What vj_detect_opencv's plan for (c, width x height, p, a batch of n_frames) holds, with the environment's
  * current settings: the LDS-tile scales and, for stage trees on tiles, the survivors' tree queue.  The
  * queue's shift and split belong to the plan: they record what earlier calls with that plan did.        */
