@@ -1786,12 +1786,16 @@ int launch_roi_chain(const RoiArgs& r, const CascadeArgs& a, bool from_dets, boo
 // window's bits IN STUMP ORDER and adds the leaf values (stage_sum += alpha[rect_sum >= norm_threshold], clod.cl:81) —
 // exactly the sequence of f32 additions a single lane would have made.  The wave's survivors are compacted in registers.
 // Returns how many of the wave's windows survived the last stage (detections), written to out[0, n).
+// deal_barrier (workgroup-uniform): one workgroup barrier once every wave holds its windows in registers.  After it
+// nothing of the tail reads LDS outside `out` and `masks` (and the read-only image tile), so a caller that passes
+// scratch inside the wave's own queue region may let the wave run on into the next member without another barrier.
 template <bool COUNT, typename Img>
 __device__ __forceinline__ uint32_t tile_wave_tail(const CascadeArgs& a, const Img& img_by_window,
                                                    const uint32_t* table /* the scale's tile table, global */,
                                                    const uint32_t* tail /* ... its block-transposed copy */,
                                                    const QEntry* lds_q, QEntry* out, unsigned long long* masks, uint32_t T,
-                                                   uint32_t st_begin, uint32_t n_stages, uint32_t lane, uint32_t wib) {
+                                                   uint32_t st_begin, uint32_t n_stages, uint32_t lane, uint32_t wib,
+                                                   bool deal_barrier) {
     const auto img = img_by_window.by_stump();
     kptr<StageDev> stages = as_k(a.stages);
     kptr<uint32_t> blocks = as_k(reinterpret_cast<const uint32_t*>(a.sp_blocks));   // {first_node, desc} pairs
@@ -1799,11 +1803,14 @@ __device__ __forceinline__ uint32_t tile_wave_tail(const CascadeArgs& a, const I
     static_assert(TILE_SP_MAX_WINDOWS <= TILE_WAVES * 32, "a wave's list fits 32 lanes");
     static_assert((TILE_SP_MAX_WINDOWS + TILE_WAVES * 32) * sizeof(QEntry) + TILE_WAVES * 32 * MAXB * 8 <=
                       TILE_WAVES * TILE_WAVE_CAP * sizeof(QEntry), "windows, survivors and verdict words fit the queue area");
+    static_assert(32 * sizeof(QEntry) + 32 * MAXB * 8 <= TILE_WAVE_CAP * sizeof(QEntry),
+                  "a wave's survivors and verdict words fit its own queue region");
     uint32_t nw = T > wib ? (T - wib + TILE_WAVES - 1u) / TILE_WAVES : 0u;   // (uniform) windows of this wave, <= 32
     QEntry e{0u, 0.0f};
     if (lane < nw) e = lds_q[wib + lane * TILE_WAVES];
     uint32_t off = e.off;
     float var = e.var;
+    if (deal_barrier) lds_barrier();   // (before the per-wave return: every wave of the workgroup crosses it)
     if (nw == 0u) return 0u;
     const uint32_t g_end = a.n_sp_blocks;
     uint32_t g = stages[st_begin].sp_first;   // running block number over all stages
@@ -2336,6 +2343,31 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
         // The members of a group, smallest scale first, each the whole cascade on the staged tile (a lone scale: one
         // member).  A member skips a tile past its own grid edge or past its tile_row_end (rows the chain balance gave
         // to the global-gather chain).
+        //
+        // Barriers between the members of a group.  A member ends with a workgroup barrier (its queues are rewritten by
+        // the next one) and the next begins with one (the staging is drained).  Where a member that is not the group's
+        // last ends in the wave-independent tail, or ends in the wave-split finish with nothing or only wave 0's
+        // detections left, both are dropped: a wave that is done goes on to the next member's squared-sum loads, variance
+        // fill and first stages while the slower waves finish their tails, and the workgroup meets again at the next
+        // member's first re-pack.  What makes that safe — everything a wave (E) touches before that re-pack against
+        // everything a wave (L) still uses after the member's last barrier:
+        //   - E's queue: q = lds_q + wib * TILE_WAVE_CAP, the wave's own region, written by the fill and compacted in
+        //     place by sweep_stages (entries [0, n) of q only).  L in the tail uses `out` and `masks`, both inside L's own
+        //     region, and its flush reads `out`; the packed windows the tail deals from (wave 0's region) are in
+        //     registers before the tail's dealing barrier, which E cannot have passed without L.  L = wave 0 flushing
+        //     the wave-split finish's detections reads lds_q[0, left), left <= TILE_WAVE_CAP: its own region.
+        //   - lds_cnt[0..8) (E publishes its count before the re-pack barrier), lds_cnt[1..9) and [20..28) (wave-split
+        //     counts), the wave-split scratch lds_x: L reads them only before the last lds_barrier of tile_wave_split,
+        //     which waits for its LDS reads; the tail and the flush read none of them.
+        //   - the ticket slot lds_cnt[TILE_WAVES + 8]: written after the member loop, read after the barrier that
+        //     follows; no member touches it.  If every later member is skipped, that barrier is the next one E meets.
+        //   - the COUNT counters, the queues' counters and the detection list: global atomics, order-free.
+        //   - the image tile: read-only until the barrier at the top of the next tile.
+        //   - `q`, `n`, `skip_front` and the loop's own state: registers.
+        // Every condition that decides a barrier is workgroup-uniform (m, n_mem, the skip test, totals read from lds_cnt),
+        // so all waves run the same barrier sequence.  Lone scales, the ROI pass, tree cascades and the stage-tree
+        // segments never relax.
+        bool skip_front = false;   // the previous member of this tile ended without its barrier
         for (uint32_t m = 0; m < n_mem; ++m) {
             const uint32_t slot = slot0 + m;
             // (opaque per member: what the member's windows derive from the tile shape is recomputed, not kept live
@@ -2350,8 +2382,12 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
             // ScaleDev::sq32) — all issued before the barrier that drains the staging
             q = lds_q + wib * TILE_WAVE_CAP;   // (re-packing below moves the wave's queue base)
             const uint32_t n_tile = tw * th;
-            const uint32_t per_wave = max(64u, (n_tile + TILE_WAVES - 1u) / TILE_WAVES);   // <= TILE_WAVE_CAP (host)
-            const uint32_t t_begin = min(wib * per_wave, n_tile), t_end = min(t_begin + per_wave, n_tile);
+            // whole 64-window chunks, the first waves one more than the others (a partly filled chunk costs the sweep
+            // as much as a full one); n_tile <= TILE_WAVES * TILE_WAVE_CAP (host), so no wave exceeds TILE_WAVE_CAP
+            const uint32_t n_chunks = (n_tile + 63u) >> 6;
+            const uint32_t c_base = n_chunks / TILE_WAVES, c_extra = n_chunks % TILE_WAVES;
+            const uint32_t t_begin = min((wib * c_base + min(wib, c_extra)) * 64u, n_tile);
+            const uint32_t t_end = min(t_begin + (c_base + (wib < c_extra ? 1u : 0u)) * 64u, n_tile);
             // (the ROI pass lays a scale's tile out for that scale alone; the tile list's tiles in the group's layout)
             const uint32_t te_lt = (ROI ? scales[slot].te_lt : scales[slot].grp_te_lt) * 4u;
             const uint32_t te_dh = (ROI ? scales[slot].te_dh : scales[slot].grp_te_dh) * 4u, e_dw = scales[slot].e_dw;
@@ -2390,7 +2426,7 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                                                    ld_u64(sq_f, e * 8u, c2 * 8u) + ld_u64(sq_f, e * 8u, c3 * 8u));
                 }
             }
-            __syncthreads();
+            if (!skip_front) __syncthreads();   // (the staging is drained; after a relaxed member it already was)
             STAMP(1);
 
             // computeVariance (clod.cpp:418-446): pixel sum from the LDS tile, squared sum as loaded above
@@ -2461,6 +2497,8 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
             };
             uint32_t dest = a.n_pass;   // n_pass = ran the whole cascade: survivors are detections
             uint32_t next_p = 1;        // next pass boundary index
+            const bool may_relax = !ROI && !TREES && m + 1u < n_mem;   // (uniform) see the member loop's head
+            bool relaxed = false;
             const uint32_t n_stages_total = a.pass_begin[a.n_pass];
             for (uint32_t st = 0; st < n_stages_total; ++st) {
                 const bool at_boundary = next_p < a.n_pass && st == a.pass_begin[next_p];
@@ -2525,17 +2563,24 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                                                                             n_stages_total, lane, wib, t_last);
                         q = lds_q;
                         n = wib == 0u ? left : 0u;
+                        // (nothing left, or detections that wave 0 flushes from its own region: no wave reads another's
+                        // region after the finish's last barrier)
+                        relaxed = may_relax && left <= (uint32_t)TILE_WAVE_CAP;
                         if (!TREES && left != 0u && s_next < n_stages_total) {
-                            // below tile_ws_min windows: every wave finishes its share alone.  Behind the packed windows
-                            // [0, TILE_SP_MAX_WINDOWS): the waves' survivors (32 entries each), then their verdict words
-                            // (32 windows x TILE_SP_MAX_BLOCKS each) — all inside the queue area
-                            q = lds_q + TILE_SP_MAX_WINDOWS + wib * 32u;
+                            // below tile_ws_min windows: every wave finishes its share alone, with scratch for its
+                            // survivors (32 entries) and its verdict words (32 windows x TILE_SP_MAX_BLOCKS).  Behind the
+                            // packed windows [0, TILE_SP_MAX_WINDOWS): all waves' survivors, then all waves' verdict words
+                            // — or, where the member's end barrier is dropped, both at the head of the wave's own queue
+                            // region, behind a barrier that keeps wave 0's scratch off the windows being dealt.
+                            relaxed = may_relax;
+                            q = relaxed ? lds_q + wib * TILE_WAVE_CAP : lds_q + TILE_SP_MAX_WINDOWS + wib * 32u;
                             n = tile_wave_tail<COUNT>(
                                 a, img, a.table + (size_t)table_first * 16u,
                                 a.table + (size_t)(ROI ? scales[slot].tile_tail_first : scales[slot].grp_tail_first) * 16u, lds_q, q,
-                                reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS + TILE_WAVES * 32) +
-                                    wib * 32u * TILE_SP_MAX_BLOCKS,
-                                left, s_next, n_stages_total, lane, wib);
+                                relaxed ? reinterpret_cast<unsigned long long*>(q + 32)
+                                        : reinterpret_cast<unsigned long long*>(lds_q + TILE_SP_MAX_WINDOWS + TILE_WAVES * 32) +
+                                              wib * 32u * TILE_SP_MAX_BLOCKS,
+                                left, s_next, n_stages_total, lane, wib, relaxed);
                         }
                         dest = a.n_pass;
                         STAMP(12);
@@ -2553,7 +2598,9 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
             }
             if (n != 0u) flush_wave(q, n, dest);
             STAMP(13);
-            __syncthreads();   // the member is finished: its queue may be rewritten, lds_cnt may carry the next ticket
+            // the member is finished: its queue may be rewritten, lds_cnt may carry the next ticket
+            if (!relaxed) __syncthreads();
+            skip_front = relaxed;
             STAMP(19);         // (waiting here for the workgroup's slowest wave: a tail ends per wave)
         }
         if (threadIdx.x == 0) lds_cnt[TILE_WAVES + 8] = next_u;
