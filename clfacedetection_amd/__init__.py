@@ -13,4 +13,5 @@ from .api import (  # noqa: F401
     clifIntegral, clodDetectObjects, clodInitBuffers, clodInitEnvironment, clodReleaseBuffers,
     clodReleaseEnvironment, cvHaarDetectObjects, cvHaarDetectObjectsForROC, default_params, group_rectangles,
     cvRunHaarClassifierCascade, group_rectangles_levels, load_library, run_windows_opencv,
+    CLOD_WINDOW_RESULT_DTYPE, VJ_WINDOW_OUTSIDE, runCascade, run_windows,
 )

@@ -162,6 +162,8 @@ class _RocResult(C.Structure):
 
 WINDOW_DTYPE = np.dtype([("frame", "<i4"), ("x", "<i4"), ("y", "<i4"), ("scale", "<i4")])                 # vj_window
 WINDOW_RESULT_DTYPE = np.dtype([("result", "<i4"), ("reserved", "<i4"), ("stage_sum", "<f8")])           # vj_window_result
+CLOD_WINDOW_RESULT_DTYPE = np.dtype([("result", "<i4"), ("variance", "<f4"), ("stage_sum", "<f4"), ("reserved", "<i4")])   # vj_clod_window_result
+VJ_WINDOW_OUTSIDE = -2**31   # vj_clod_window_result.result of a window that does not lie inside its frame
 RECT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("weight", "<f4"),
                        ("frame", "<i4"), ("scale_idx", "<i4")])
 STAGE_DTYPE = np.dtype([("first_tree", "<i4"), ("n_trees", "<i4"), ("threshold", "<f4"), ("parent", "<i4"),
@@ -233,6 +235,8 @@ _SIGNATURES = {
     "vj_roc_result_free": (None, [C.POINTER(_RocResult)]),
     "vj_run_windows_opencv": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32,
                                         C.c_int, C.c_void_p]),
+    "vj_run_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32,
+                                 C.c_int, C.c_uint32, C.c_void_p]),
     "vj_run_windows_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vj_cv_plan_info_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CvParams), C.POINTER(CvPlanInfo)]),
     "vj_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params),
@@ -684,8 +688,13 @@ class Environment:
         """vj_run_windows_opencv: see the module-level run_windows_opencv."""
         return _run_windows(self._h, cascade, frames, windows, scales, start_stage, color)
 
+    def run_windows(self, cascade: Cascade, frames, windows, scales, start_stage: int = 0, flags: int = 0, color: bool = False):
+        """vj_run_windows: see the module-level run_windows."""
+        return _run_windows_clod(self._h, cascade, frames, windows, scales, start_stage, flags, color)
+
     def run_windows_timing(self) -> tuple[float, float]:
-        """vj_run_windows_timing: (integral_ms, pass_ms) of the last run_windows_opencv call, device times summed over its sub-batches."""
+        """vj_run_windows_timing: (integral_ms, pass_ms) of the last run_windows_opencv or run_windows call, device times summed
+        over its sub-batches."""
         i, p = C.c_float(0), C.c_float(0)
         _check(load_library().vj_run_windows_timing(self._h, C.byref(i), C.byref(p)), "vj_run_windows_timing")
         return float(i.value), float(p.value)
@@ -914,7 +923,8 @@ def cvHaarDetectObjectsForROC(image, cascade: Cascade, env: Environment, scale_f
             vj_flags |= vj_bit
     return env.detect_opencv_roc(cascade, image, min_size, max_size, scale_factor, min_neighbors, vj_flags)
 
-def _run_windows(env_handle, cascade: Cascade, frames, windows, scales, start_stage, color):
+def _window_args(windows, scales, scale_dtype, start_stage):
+    """The window list as contiguous vj_window rows, the scales as a 1-D array of scale_dtype; ValueError for what is neither."""
     w = np.asarray(windows)
     if w.dtype != WINDOW_DTYPE:
         if not np.issubdtype(w.dtype, np.integer) and w.size:
@@ -925,12 +935,17 @@ def _run_windows(env_handle, cascade: Cascade, frames, windows, scales, start_st
             raise ValueError("window members must fit an int32")
         w = w.reshape(-1, 4).astype(np.int32)
     w = np.ascontiguousarray(w)
-    n = int(w.shape[0])
-    sc = np.ascontiguousarray(np.atleast_1d(np.asarray(scales, np.float64)))
+    sc = np.ascontiguousarray(np.atleast_1d(np.asarray(scales, scale_dtype)))
     if sc.ndim != 1:
         raise ValueError("scales must be a 1-D list of factors")
     if start_stage != int(start_stage):
         raise ValueError("start_stage must be an integer")
+    return w, sc
+
+
+def _run_windows(env_handle, cascade: Cascade, frames, windows, scales, start_stage, color):
+    w, sc = _window_args(windows, scales, np.float64, start_stage)
+    n = int(w.shape[0])
     imgs, nf, keep = Environment._images(frames, color)
     out = np.zeros(n, WINDOW_RESULT_DTYPE)
     lib = load_library()
@@ -953,4 +968,37 @@ def cvRunHaarClassifierCascade(gray, cascade: Cascade, env: Environment, pt, sca
     """cvRunHaarClassifierCascade(cascade, pt, start_stage) (tempcv.cpp:974-984) after cvSetImagesForHaarClassifierCascade(cascade,
     sum, sqsum, tilted, scale) on `gray`'s integral images: one window through run_windows_opencv; pt = (x, y)."""
     res, _ = run_windows_opencv(gray, cascade, env, [(0, int(pt[0]), int(pt[1]), 0)], [float(scale)], start_stage, color=np.ndim(gray) == 3)
+    return int(res[0])
+
+
+def _run_windows_clod(env_handle, cascade: Cascade, frames, windows, scales, start_stage, flags, color):
+    w, sc = _window_args(windows, scales, np.float32, start_stage)
+    if flags != int(flags) or not 0 <= int(flags) < 2**32:
+        raise ValueError("flags must be an unsigned 32-bit integer")
+    n = int(w.shape[0])
+    imgs, nf, keep = Environment._images(frames, color)
+    out = np.zeros(n, CLOD_WINDOW_RESULT_DTYPE)
+    lib = load_library()
+    _check(lib.vj_run_windows(env_handle, cascade._h, imgs, nf, sc.ctypes.data, len(sc), w.ctypes.data, n, int(start_stage), int(flags),
+                              out.ctypes.data), "vj_run_windows")
+    return out["result"].copy(), out["stage_sum"].copy(), out["variance"].copy()
+
+
+def run_windows(frames, cascade: Cascade, env: Environment, windows, scales, start_stage: int = 0, flags: int = 0, color: bool = False):
+    """runCascade (clod.cpp:736-787) with computeVariance (:418-446) on a list of windows, on the device (vj_run_windows): the clod
+    profile's arithmetic.  windows: rows of (frame, x, y, scale) with `scale` an index into `scales` (the reference's current_scale,
+    float32: any finite values > 0).  Returns (results int32[n], stage_sums float32[n], variances float32[n]) in the order of
+    `windows`: result VJ_WINDOW_OUTSIDE for a window that does not lie inside its frame (x >= 0, y >= 0, x + sw <= W, y + sh <= H),
+    1 on a pass, -i on a reject at stage i of a linear cascade (0 at stage 0), 0 on every reject of a stage tree; stage_sum is the
+    f32 sum of the stage whose verdict ended the run (0.0 outside and with start_stage >= the stage count); variance is the norm
+    factor of every inside window.  flags: VJ_FLAG_SIGNED_MEAN, VJ_FLAG_TILTED_AS_UPRIGHT.  frames: 2-D uint8 arrays of one size,
+    (h, w, 3|4) BGR / BGRA arrays with color=True, or DeviceFrames.  The arguments are checked before the environment is used."""
+    return _run_windows_clod(env._h if env is not None else None, cascade, frames, windows, scales, start_stage, flags, color)
+
+
+def runCascade(gray, cascade: Cascade, env: Environment, pt, scale: float = 1.0) -> int:
+    """runCascade (clod.cpp:736-787) for the window at pt = (x, y) of `gray` at current_scale `scale`: one window through
+    run_windows, tilted features read as upright rectangles as clodDetectObjects reads them; returns exit_stage."""
+    res, _, _ = run_windows(gray, cascade, env, [(0, int(pt[0]), int(pt[1]), 0)], [float(scale)], 0, VJ_FLAG_TILTED_AS_UPRIGHT,
+                            color=np.ndim(gray) == 3)
     return int(res[0])

@@ -1880,19 +1880,7 @@ int run_cv_roi_pass(vj_env* e, const vj_cascade* c, int W, int H, int nf, const 
 // ------------------------------------------------------------------------ a cascade on a caller's windows
 // (what needs no device — argument checks, grouping by scale slot, the unit list, the scatter of results — is vj_cv_points_host.cpp)
 
-// Room for one more entry in a cache of vj_run_windows_opencv: the least recently used go first, but never an entry of the call in
-// progress (last_used >= call_tick) — a call that names more scales than plan_cache_max keeps them all while it runs.
-template <typename Map>
-void cv_point_make_room(vj_env* e, Map& m, uint64_t call_tick) {
-    while ((int)m.size() >= std::max(1, e->plan_cache_max)) {
-        auto lru = m.end();
-        for (auto i = m.begin(); i != m.end(); ++i)
-            if (i->second->last_used < call_tick && (lru == m.end() || i->second->last_used < lru->second->last_used)) lru = i;
-        if (lru == m.end()) return;
-        lru->second->release_device();
-        m.erase(lru);
-    }
-}
+// (room in the two caches: cv_point_make_room, vj_env_internal.hpp)
 
 // The stage records of `c` (what vj_detect_opencv's plans hold, once per cascade)
 int get_cv_point_cascade(vj_env* e, const vj_cascade* c, uint64_t call_tick, CvPointCascade** out) {

@@ -2069,6 +2069,10 @@ static void drop_cv_point_plans(vj_env* e) {
     e->cv_point_cascades.clear();
     for (auto& kv : e->cv_point_plans) kv.second->release_device();
     e->cv_point_plans.clear();
+    for (auto& kv : e->clod_point_cascades) kv.second->release_device();
+    e->clod_point_cascades.clear();
+    for (auto& kv : e->clod_point_plans) kv.second->release_device();
+    e->clod_point_plans.clear();
 }
 
 static void drop_plans(vj_env* e) {

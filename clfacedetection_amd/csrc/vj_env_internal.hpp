@@ -5,6 +5,7 @@
 #include "vj_device.hpp"
 #include "vj_cv_roi_host.hpp"
 #include "vj_cv_points_host.hpp"
+#include "vj_points_host.hpp"
 
 #include <hip/hip_runtime_api.h>
 
@@ -174,6 +175,23 @@ struct CvPointCascade {
 struct CvPointPlan {
     CvPointScaleDev rec = {};     // table = d_table.p once built; win_w / win_h / equRect whatever the frame's height
     uint64_t max_reach = 0;       // furthest element a feature touches, from the window origin (valid once the table is built)
+    DevBuf d_table;               // built at the first call whose frame the window fits (no window of a larger one is evaluated)
+    uint64_t last_used = 0;
+    void release_device() { d_table.release(); }
+};
+
+// The same two for the clod profile's window-list pass (vj_run_windows; vj_points.hip): the stage records of a
+// cascade, and the record and node table (build_node_table, the code behind vj_plan_feature_table) of ONE scale on frames of one width.
+struct ClodPointCascade {
+    uint32_t n_stages = 0, n_order = 0;
+    bool trees = false, is_tree = false;
+    DevBuf d_stages;
+    uint64_t last_used = 0;
+    void release_device() { d_stages.release(); }
+};
+struct ClodPointPlan {
+    ClodPointScaleDev rec = {};   // table = d_table.p once built; win_w / win_h whatever the frame's height
+    uint64_t max_reach = 0;       // furthest element a feature or the variance rectangle touches, from the window origin (once built)
     DevBuf d_table;               // built at the first call whose frame the window fits (no window of a larger one is evaluated)
     uint64_t last_used = 0;
     void release_device() { d_table.release(); }
@@ -383,8 +401,13 @@ struct vj_env : vj::Tunables {
     std::map<uint64_t, std::unique_ptr<vj::CvPointCascade>> cv_point_cascades;
     typedef std::tuple<uint64_t, int, uint64_t> CvPointPlanKey;
     std::map<CvPointPlanKey, std::unique_ptr<vj::CvPointPlan>> cv_point_plans;
-    float cv_points_integral_ms = 0, cv_points_pass_ms = 0;   // ... device times of the last call, summed over its sub-batches (vj_run_windows_timing)
+    float cv_points_integral_ms = 0, cv_points_pass_ms = 0;   // ... device times of the last run-windows call of either profile, summed over its sub-batches (vj_run_windows_timing)
     vj::DevBuf d_cv_points, d_cv_point_units, d_cv_point_scales, d_cv_point_out;   // ... a sub-batch's windows, units and verdicts; the call's scale records
+    // vj_run_windows, the clod profile's twin: its caches, keyed and bounded the same way (the key's last member: tilted-as-upright);
+    // its calls use the four buffers and the two times above (one call runs at a time; the records have the same sizes)
+    std::map<uint64_t, std::unique_ptr<vj::ClodPointCascade>> clod_point_cascades;
+    typedef std::tuple<uint64_t, int, uint32_t, int> ClodPointPlanKey;
+    std::map<ClodPointPlanKey, std::unique_ptr<vj::ClodPointPlan>> clod_point_plans;
     vj::DevBuf d_cv_det, d_cv_counts;   // vj_detect_opencv: detection list and counters
     vj::DevBuf d_cv_accept, d_cv_tq;    // ... stage trees on tiles: accept bitmap, the queue of the prefix's survivors
     vj::DevBuf d_cv_fail_rows, d_cv_fail_walk;   // ... per-wave fail lists of the chain sweeps (rows kernel / chain pass)
@@ -410,4 +433,19 @@ int enqueue_integral(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int s
 int stage_frames(vj_env* e, const vj_image* frames, int n, int W, int H, const uint8_t** d_ptr, size_t* frame_bytes,
                  int* stride, Lane* lane = nullptr, hipStream_t copy_stream = nullptr);
 int enqueue_tilted(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int stride, int W, int H, int frames, int channels);
+
+// Room for one more entry in a cache of the run-windows calls (vj_run_windows_opencv, vj_run_windows): the least recently used go
+// first, but never an entry of the call in progress (last_used >= call_tick) — a call that names more scales than plan_cache_max
+// keeps them all while it runs.
+template <typename Map>
+void cv_point_make_room(vj_env* e, Map& m, uint64_t call_tick) {
+    while ((int)m.size() >= std::max(1, e->plan_cache_max)) {
+        auto lru = m.end();
+        for (auto i = m.begin(); i != m.end(); ++i)
+            if (i->second->last_used < call_tick && (lru == m.end() || i->second->last_used < lru->second->last_used)) lru = i;
+        if (lru == m.end()) return;
+        lru->second->release_device();
+        m.erase(lru);
+    }
+}
 }  // namespace vj

@@ -491,8 +491,44 @@ typedef struct vj_window_result { int32_t result, reserved; double stage_sum; } 
 int  vj_run_windows_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
                            const double* scales, int n_scales, const vj_window* windows, uint32_t n_windows,
                            int start_stage, vj_window_result* out /* n_windows entries, caller's */);
-/* Device times of the environment's last vj_run_windows_opencv call that ran a pass, summed over its sub-batches: the integral
- * images (with the tilted integral, where built) and the window-list kernel alone (hipEvents around the launch).  Either may be NULL. */
+/* The clod profile's twin: runCascade (clod.cpp:736-787) on what setupScale (:371-415), computeVariance (:418-446) and
+ * precomputeFeatures / precomputeKernelCascade (:448-492, :529-578) give, on a caller's list of windows: out[i] is
+ * the verdict on windows[i] — the window at (x, y) of frame `frame`, at scales[scale] — in the caller's order; nothing is sorted or
+ * deduplicated.  scales[k] is the reference's current_scale, a binary32: any finite value > 0, not only members of the 1.1f chain.
+ * From it, as setupScale writes them: sw = (uint)round(win_w * s) and sh likewise (int x f32 product, rounded half away from zero),
+ * equ = {round(s), round(s), round((win_w - 2) * s), round((win_h - 2) * s)}, area = equ.w * equ.h; sw and sh are clamped at 2^20.
+ * setupScale's step, grid ends and min / max / image-size rejections belong to the detector's loop and play no part.  A scale with
+ * sw, sh or area equal to 0 is VJ_ERR_ARG (the reference would divide by zero).
+ *   inside      in 64 bits on the caller's int32 coordinates: a window is evaluated iff x >= 0, y >= 0, x + sw <= W and y + sh <= H
+ *               (x = W - sw is evaluated, x = W - sw + 1 is not: there the reference reads outside the image and has no answer).
+ *               Any other window gets (VJ_WINDOW_OUTSIDE, 0.0f, 0.0f) and performs no image read; a scale whose window exceeds the
+ *               frame gives that for every window and builds no table: no error.
+ *   variance    computeVariance's value: mean = (float)S / (float)area, var = (float)Q / (float)area - mean * mean, variance =
+ *               var >= 0 ? sqrtf(var) : 1; S read unsigned, or through int* with VJ_FLAG_SIGNED_MEAN exactly as vj_detect does.
+ *               Written for every inside window, whatever start_stage.
+ *   result      runCascade's return value: 1 on a pass; -i on a reject at stage i of a linear cascade (stumps, or multi-node trees
+ *               walked as tempcv.cpp:771-792 in clod arithmetic, as vj_detect runs them), so a reject at stage 0 is 0; for a stage
+ *               tree — which the reference's clod path does not know — the walk of tempcv.cpp:834-861: 1 on a pass, 0 on every reject.
+ *   stage_sum   the f32 running sum (one accumulator, added in tree order, clod.cl:81) of the stage whose verdict ended the run, for
+ *               a pass the last stage evaluated; compared with the stage threshold WITHOUT OpenCV's bias.  0.0f where no stage runs:
+ *               outside windows, and start_stage >= the stage count, which returns 1.
+ * start_stage: linear cascades start there; a stage tree accepts only 0; anything else, or a negative value, is VJ_ERR_ARG.
+ * flags: VJ_FLAG_SIGNED_MEAN is honoured; VJ_FLAG_TILTED_AS_UPRIGHT works as in vj_detect (a cascade with tilted features is refused
+ * with VJ_ERR_UNSUPPORTED without it); any other bit is VJ_ERR_ARG — a window list has no skip mode, grid or counters.
+ * n_windows == 0 is VJ_OK (whatever the other arguments, a null environment included; only the cascade, start_stage and flags are
+ * checked first); a frame or scale index out of range is VJ_ERR_ARG with `out` untouched.  Frames: one size, gray / BGR / BGRA,
+ * host or device-resident, integrated once per call (per sub-batch when the call splits).  At most 2^27 windows per call; a frame
+ * whose sqsum image exceeds one 4 GiB buffer descriptor, or a scale whose features reach beyond the frame allocation (the check of
+ * the other clod paths, per scale slot), is VJ_ERR_LIMIT.  Node tables are cached per (cascade, frame width, bits of the scale,
+ * tilted-as-upright) next to the other plans. */
+#define VJ_WINDOW_OUTSIDE INT32_MIN
+typedef struct vj_clod_window_result { int32_t result; float variance; float stage_sum; int32_t reserved; } vj_clod_window_result;
+int  vj_run_windows(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
+                    const float* scales, int n_scales, const vj_window* windows, uint32_t n_windows,
+                    int start_stage, uint32_t flags, vj_clod_window_result* out /* n_windows entries, caller's */);
+/* Device times of the environment's last run-windows call of either profile (vj_run_windows_opencv or vj_run_windows) that ran a
+ * pass, summed over its sub-batches: the integral images (with the tilted integral, where built) and the window-list kernel alone
+ * (hipEvents around the launch).  Either may be NULL. */
 int  vj_run_windows_timing(const vj_env* e, float* integral_ms, float* pass_ms);
 /* What vj_detect_opencv's plan for (c, width x height, p, a batch of n_frames) holds, with the environment's
  * current settings: the LDS-tile scales and, for stage trees on tiles, the survivors' tree queue.  The
