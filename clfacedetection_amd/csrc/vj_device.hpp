@@ -180,7 +180,7 @@ struct CascadeArgs {
     uint32_t gather_waves;      // waves per workgroup of cascade_pass / cascade_roi_pass (3 or 4; stage trees: 3)
     const QEntry*   q_in;       // survivor queue read by this pass (passes > 0)
     const uint32_t* q_in_count; // entry counts of q_in, [scale][Q_PARTS]
-    uint32_t* q_ticket;         // Q_PARTS chunk-ticket counters of this queue pass (zeroed before the launch)
+    uint32_t* q_ticket;         // Q_PARTS ticket counters of this pass, zeroed before the launch: a queue pass's chunks, the grid pass's units (vj_grid_parts.hpp)
     uint32_t wide_tail;         // queue passes: the stump-parallel tail keeps several windows' gathers in flight (small batches)
     uint32_t min_chunk;         // queue passes: smallest chunk of windows a wave draws (1..64)
     uint32_t q_slices;          // queue passes: a part's chunks are handed out in this many slices of every scale's range (frame-major order)

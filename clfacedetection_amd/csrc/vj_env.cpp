@@ -22,6 +22,7 @@
 #include <tuple>
 
 #include "vj_env_internal.hpp"
+#include "vj_grid_parts.hpp"
 
 using namespace vj;
 
@@ -1199,7 +1200,17 @@ struct CountsLayout {
     static constexpr size_t roi_off_u32 = stage_off_u32 + (size_t)(1 + VJ_MAX_LAUNCHES) * VJ_MAX_STAGES * 2;
     static constexpr size_t q2_off_u32 = roi_off_u32 + 8 + (size_t)VJ_MAX_STAGES * 2;   // second set of queue counters (stage trees)
     static constexpr size_t bytes = (q2_off_u32 + MAX_PASSES * q_counts) * sizeof(uint32_t);
+    // Queue 0 does not exist, so its q_counts counters serve as tickets, zeroed with the block once per enqueue_cascade.  From
+    // the front: pass ps draws from [ps * Q_PARTS, (ps + 1) * Q_PARTS) — pass 0 is the grid pass, whose GRID_PARTS parts of the
+    // (frame, unit) list take the first range (one grid launch per zeroing); from the back: tile class c at
+    // q_counts - 8 (c + 1), the region pass's tiles at q_counts - 40.
+    static constexpr size_t pass_tickets_end = (size_t)MAX_PASSES * Q_PARTS;
+    static constexpr size_t tile_tickets_begin = q_counts - 8u * TILE_CLASSES;
+    static constexpr size_t roi_tickets_begin = q_counts - 40u;
 };
+static_assert(GRID_PARTS == Q_PARTS, "the grid pass's tickets are pass 0's range of queue 0's counters");
+static_assert(CountsLayout::pass_tickets_end <= CountsLayout::roi_tickets_begin, "pass tickets (the grid pass's among them) end before the region pass's");
+static_assert(CountsLayout::roi_tickets_begin + 8u <= CountsLayout::tile_tickets_begin, "the region pass's tile tickets end before the tile classes'");
 
 // Upload (or adopt) the frames of one batch and enqueue its integral images.  `copy_stream` != null: the upload runs
 // on that stream and the integral waits for it (vj_stream); else everything is ordered on the environment's stream.
@@ -1462,8 +1473,7 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
             const int b_blocks = two_streams ? std::max(1, e->n_cu * e->concurrent_blocks_per_cu) : n_blocks;
             auto chain_b = [&]() -> int {
             if (!hrc && ca.n_units > 0) {
-                CascadeArgs ga = queue_args(0);
-                ga.total_waves = (uint32_t)b_blocks * ga.gather_waves;
+                CascadeArgs ga = queue_args(0);   // (q_ticket: pass 0's range — the tickets of the unit list's parts)
                 if ((rc = begin_launch(VJ_LAUNCH_GRID, 0, ga.stage_begin, ga.stage_end, 0, sB))) return rc;
                 ga.stage_entered = launch_counters();
                 hrc = launch_cascade_pass(ga, true, pl->trees, n_pass == 1, count, general_kernel && n_pass == 1, b_blocks, sB);
@@ -1600,6 +1610,14 @@ static int finish_batch(vj_env* e, Lane* L, Plan* pl, int f0, int W, int H, cons
                             linfo[l].stage_begin, linfo[l].stage_end, se[(1 + l) * VJ_MAX_STAGES + 50], se[(1 + l) * VJ_MAX_STAGES + 48],
                             se[(1 + l) * VJ_MAX_STAGES + 49], se[(1 + l) * VJ_MAX_STAGES + 51], se[(1 + l) * VJ_MAX_STAGES + 52],
                             se[(1 + l) * VJ_MAX_STAGES + 53], se[(1 + l) * VJ_MAX_STAGES + 54]);
+            for (size_t l = 0; l < linfo.size(); ++l)   // grid pass: when the waves leave the unit loop (vj_kernels.hip, slots 40..45)
+                if (linfo[l].kind == VJ_LAUNCH_GRID) {
+                    const unsigned long long* g = se + (1 + l) * VJ_MAX_STAGES + 40;
+                    const double wgs = (double)std::max(1ull, g[5]), span = (double)(g[3] - ~g[4]);
+                    fprintf(stderr, "vj grid launch %zu: workgroups %llu span %.0f ticks | per workgroup last - mean wave end: mean %.0f (%.2f %%) max %llu (%.2f %%) | "
+                            "launch end - mean last wave end %.0f (%.2f %%)\n", l, g[5], span, (double)g[0] / wgs, 100.0 * (double)g[0] / wgs / span, g[1],
+                            100.0 * (double)g[1] / span, (double)g[3] - (double)g[2] / wgs, 100.0 * ((double)g[3] - (double)g[2] / wgs) / span);
+                }
             fprintf(stderr, "vj stamps:");
             for (int i = 40; i < 60; ++i) {
                 unsigned long long v = 0;

@@ -17,6 +17,7 @@
 #include <type_traits>
 #include "vj_device.hpp"
 #include "vj_devutil.hpp"
+#include "vj_grid_parts.hpp"
 
 #ifndef VJ_STAMPS
 #define VJ_STAMPS 0
@@ -1230,27 +1231,56 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t wpb = blockDim.x >> 6;     // the host's choice (CascadeArgs::gather_waves, clamped by the launcher)
     QEntry* q = lds_q + wib * UNIT_WINDOWS;
-    const uint32_t rank = blockIdx.x * wpb + wib;
     kptr<ScaleDev> scales = as_k(a.scales);
     // the whole batch of sum images behind one descriptor (host keeps it below 4 GiB)
     const rsrc_t img = make_rsrc(a.sum, a.sum_bytes);
 
     if (FROM_GRID) {
+        // (diagnostic build: s_memrealtime, the constant 100 MHz counter — these stamps are compared across CUs and XCDs, whose
+        // shader clocks, and so their s_memtime, differ)
+        const unsigned long long t_enter = VJ_STAMPS ? __builtin_amdgcn_s_memrealtime() : 0ull;
         kptr<UnitDev> units = as_k(a.units);
         const uint32_t total_units = a.n_units * a.n_frames;
         const uint32_t frame_bytes4 = a.frame_elems * 4u;
-        // Blocks are dealt round-robin over the 8 XCDs (observed placement; used for speed only): the waves that
-        // share an XCD — and its 4 MiB L2 — take one contiguous eighth of the (frame, unit) list, i.e. they work on
-        // the same frame's sum image at the same time instead of on every frame in flight.
-        uint32_t u_begin = 0, u_end = total_units, u_step = a.total_waves, u_first = rank;
-        if (gridDim.x >= 8u) {
-            const uint32_t xcd = blockIdx.x & 7u;
-            u_begin = (uint32_t)((unsigned long long)total_units * xcd / 8u);
-            u_end = (uint32_t)((unsigned long long)total_units * (xcd + 1u) / 8u);
-            u_step = ((gridDim.x - xcd + 7u) >> 3) * wpb;
-            u_first = u_begin + (blockIdx.x >> 3) * wpb + wib;
-        }
-        for (uint32_t u = u_first; u < u_end; u += u_step) {
+        // The (frame, unit) list is cut into GRID_PARTS contiguous parts with one ticket counter each (a.q_ticket: zeroed with
+        // the batch's counters).  Blocks are dealt round-robin over the 8 XCDs (observed placement; used for speed only), so the
+        // waves that share an XCD — and its 4 MiB L2 — start on the same part: they work on the same frame's sum image at the
+        // same time instead of on every frame in flight.  A wave draws one unit per ticket, in ascending order inside a
+        // part — survivors still reach the sub-queues roughly frame by frame, which q_slices and the band-major queue pass
+        // rely on — and steals from the next parts in turn once its own is used up, until all are: a wave that met heavy units, or a
+        // CU that the tile workgroups slowed down, simply draws fewer.  The ticket is the only interaction between waves, and
+        // the next one is drawn (lane 0's atomic is in flight) while the current unit is processed.
+        uint32_t part = grid_part_home(blockIdx.x);
+        uint32_t p_lo = grid_part_begin(total_units, part), p_n = grid_part_size(total_units, part);
+        auto issue = [&]() -> uint32_t {   // (per-lane value, not waited for: lane 0 holds the ticket)
+            uint32_t t = 0;
+            if (lane == 0) t = atomicAdd(a.q_ticket + part, 1u);
+            return t;
+        };
+        auto resolve = [&](uint32_t t_v) -> uint32_t {   // ticket -> unit; total_units once every part is used up
+            uint32_t t = __builtin_amdgcn_readfirstlane(t_v);
+            while (t >= p_n) {
+                // This part is used up (or empty): go on to the next one in turn that has units left.  One look at all
+                // the counters (lane x reads part x's) instead of a failing draw per part: a wave that finds nothing — most
+                // waves of a single small frame — leaves after one round trip, not after GRID_PARTS.  The counters only grow,
+                // so a part seen used up is used up; one seen with units left may be empty by the time the draw arrives,
+                // and then the loop looks again.
+                bool has = false;
+                if (lane < GRID_PARTS)
+                    has = __hip_atomic_load(a.q_ticket + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < grid_part_size(total_units, lane);
+                const uint32_t open = (uint32_t)__ballot(has) & ((1u << GRID_PARTS) - 1u);
+                if (open == 0u) return total_units;
+                const uint32_t turn = ((open >> part) | (open << (GRID_PARTS - part))) & ((1u << GRID_PARTS) - 1u);   // bit k: part + k
+                part = (part + (uint32_t)__builtin_ctz(turn)) & (GRID_PARTS - 1u);
+                p_lo = grid_part_begin(total_units, part);
+                p_n = grid_part_size(total_units, part);
+                t = __builtin_amdgcn_readfirstlane(issue());
+            }
+            return p_lo + t;
+        };
+        uint32_t u = resolve(p_n != 0u ? issue() : 0u);
+        while (u < total_units) {
+            const uint32_t t_next = issue();
             const uint32_t frame = u / a.n_units;
             const uint32_t r = u - frame * a.n_units;
             const uint32_t slot = units[r].scale;
@@ -1305,6 +1335,28 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
                                                       scales[slot].q_base, lane, a.stage_begin, frame_part(a, frame),
                                                       a.run_table != nullptr ? u : 0xffffffffu);
             __builtin_amdgcn_wave_barrier();
+            u = resolve(t_next);
+        }
+        if (VJ_STAMPS) {   // diagnostic build: when the waves of a workgroup leave the unit loop, and the launch's first start / last end
+            // (in the first entry of every wave's queue, which is free now: no LDS beyond what the shipped kernel takes)
+            static_assert(sizeof(QEntry) == sizeof(unsigned long long), "a stamp fits a queue entry");
+            unsigned long long* lds_end = reinterpret_cast<unsigned long long*>(lds_q);
+            if (lane == 0) lds_end[wib * UNIT_WINDOWS] = __builtin_amdgcn_s_memrealtime();
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                unsigned long long last = 0, sum = 0;
+                for (uint32_t w = 0; w < wpb; ++w) {
+                    last = max(last, lds_end[w * UNIT_WINDOWS]);
+                    sum += lds_end[w * UNIT_WINDOWS];
+                }
+                const unsigned long long tail = last - sum / wpb;
+                atomicAdd(a.stage_entered + 40, tail);      // sum over workgroups: last wave's end - mean wave end
+                atomicMax(a.stage_entered + 41, tail);
+                atomicAdd(a.stage_entered + 42, last);      // sum over workgroups of the last wave's end
+                atomicMax(a.stage_entered + 43, last);      // the launch's end
+                atomicMax(a.stage_entered + 44, ~t_enter);  // ... and (complemented) its first start
+                atomicAdd(a.stage_entered + 45, 1ull);      // workgroups
+            }
         }
     } else if (!GENERAL && a.q_groups != nullptr) {
         // Band-major queue pass (see CascadeArgs::run_table).  The (frame, group) list is cut by frame group — the parts of the
