@@ -686,11 +686,11 @@ class Environment:
 
     def run_windows_opencv(self, cascade: Cascade, frames, windows, scales, start_stage: int = 0, color: bool = False):
         """vj_run_windows_opencv: see the module-level run_windows_opencv."""
-        return _run_windows(self._h, cascade, frames, windows, scales, start_stage, color)
+        return _run_windows(*_CV_WINDOWS, self._h, cascade, frames, windows, scales, start_stage, color)
 
     def run_windows(self, cascade: Cascade, frames, windows, scales, start_stage: int = 0, flags: int = 0, color: bool = False):
         """vj_run_windows: see the module-level run_windows."""
-        return _run_windows_clod(self._h, cascade, frames, windows, scales, start_stage, flags, color)
+        return _run_windows(*_CLOD_WINDOWS, self._h, cascade, frames, windows, scales, start_stage, color, flags)
 
     def run_windows_timing(self) -> tuple[float, float]:
         """vj_run_windows_timing: (integral_ms, pass_ms) of the last run_windows_opencv or run_windows call, device times summed
@@ -943,15 +943,22 @@ def _window_args(windows, scales, scale_dtype, start_stage):
     return w, sc
 
 
-def _run_windows(env_handle, cascade: Cascade, frames, windows, scales, start_stage, color):
-    w, sc = _window_args(windows, scales, np.float64, start_stage)
+# C function, scale dtype, result dtype and the result fields returned, of the two window-list calls
+_CV_WINDOWS = ("vj_run_windows_opencv", np.float64, WINDOW_RESULT_DTYPE, ("result", "stage_sum"))
+_CLOD_WINDOWS = ("vj_run_windows", np.float32, CLOD_WINDOW_RESULT_DTYPE, ("result", "stage_sum", "variance"))
+
+
+def _run_windows(fn, scale_dtype, result_dtype, fields, env_handle, cascade: Cascade, frames, windows, scales, start_stage, color, flags=None):
+    """One window-list call (`flags`: for the C function that takes them); the result's `fields` as arrays of their own."""
+    w, sc = _window_args(windows, scales, scale_dtype, start_stage)
+    if flags is not None and (flags != int(flags) or not 0 <= int(flags) < 2**32):
+        raise ValueError("flags must be an unsigned 32-bit integer")
     n = int(w.shape[0])
     imgs, nf, keep = Environment._images(frames, color)
-    out = np.zeros(n, WINDOW_RESULT_DTYPE)
-    lib = load_library()
-    _check(lib.vj_run_windows_opencv(env_handle, cascade._h, imgs, nf, sc.ctypes.data, len(sc), w.ctypes.data, n, int(start_stage),
-                                     out.ctypes.data), "vj_run_windows_opencv")
-    return out["result"].copy(), out["stage_sum"].copy()
+    out = np.zeros(n, result_dtype)
+    _check(getattr(load_library(), fn)(env_handle, cascade._h, imgs, nf, sc.ctypes.data, len(sc), w.ctypes.data, n, int(start_stage),
+                                       *(() if flags is None else (int(flags),)), out.ctypes.data), fn)
+    return tuple(out[f].copy() for f in fields)
 
 
 def run_windows_opencv(frames, cascade: Cascade, env: Environment, windows, scales, start_stage: int = 0, color: bool = False):
@@ -961,7 +968,7 @@ def run_windows_opencv(frames, cascade: Cascade, env: Environment, windows, scal
     cascade (0 at stage 0), 0 on every reject of a stage tree; stage_sum is the f64 sum of the stage whose verdict ended the run
     (0.0 with result -1 and with start_stage >= the stage count).  frames: 2-D uint8 arrays of one size, (h, w, 3|4) BGR / BGRA
     arrays with color=True, or DeviceFrames.  The arguments are checked before the environment is used."""
-    return _run_windows(env._h if env is not None else None, cascade, frames, windows, scales, start_stage, color)
+    return _run_windows(*_CV_WINDOWS, env._h if env is not None else None, cascade, frames, windows, scales, start_stage, color)
 
 
 def cvRunHaarClassifierCascade(gray, cascade: Cascade, env: Environment, pt, scale: float = 1.0, start_stage: int = 0) -> int:
@@ -969,19 +976,6 @@ def cvRunHaarClassifierCascade(gray, cascade: Cascade, env: Environment, pt, sca
     sum, sqsum, tilted, scale) on `gray`'s integral images: one window through run_windows_opencv; pt = (x, y)."""
     res, _ = run_windows_opencv(gray, cascade, env, [(0, int(pt[0]), int(pt[1]), 0)], [float(scale)], start_stage, color=np.ndim(gray) == 3)
     return int(res[0])
-
-
-def _run_windows_clod(env_handle, cascade: Cascade, frames, windows, scales, start_stage, flags, color):
-    w, sc = _window_args(windows, scales, np.float32, start_stage)
-    if flags != int(flags) or not 0 <= int(flags) < 2**32:
-        raise ValueError("flags must be an unsigned 32-bit integer")
-    n = int(w.shape[0])
-    imgs, nf, keep = Environment._images(frames, color)
-    out = np.zeros(n, CLOD_WINDOW_RESULT_DTYPE)
-    lib = load_library()
-    _check(lib.vj_run_windows(env_handle, cascade._h, imgs, nf, sc.ctypes.data, len(sc), w.ctypes.data, n, int(start_stage), int(flags),
-                              out.ctypes.data), "vj_run_windows")
-    return out["result"].copy(), out["stage_sum"].copy(), out["variance"].copy()
 
 
 def run_windows(frames, cascade: Cascade, env: Environment, windows, scales, start_stage: int = 0, flags: int = 0, color: bool = False):
@@ -993,7 +987,7 @@ def run_windows(frames, cascade: Cascade, env: Environment, windows, scales, sta
     f32 sum of the stage whose verdict ended the run (0.0 outside and with start_stage >= the stage count); variance is the norm
     factor of every inside window.  flags: VJ_FLAG_SIGNED_MEAN, VJ_FLAG_TILTED_AS_UPRIGHT.  frames: 2-D uint8 arrays of one size,
     (h, w, 3|4) BGR / BGRA arrays with color=True, or DeviceFrames.  The arguments are checked before the environment is used."""
-    return _run_windows_clod(env._h if env is not None else None, cascade, frames, windows, scales, start_stage, flags, color)
+    return _run_windows(*_CLOD_WINDOWS, env._h if env is not None else None, cascade, frames, windows, scales, start_stage, color, flags)
 
 
 def runCascade(gray, cascade: Cascade, env: Environment, pt, scale: float = 1.0) -> int:

@@ -14,7 +14,7 @@
 // Stumps or multi-node trees, linear cascades or stage trees, upright or tilted features (tilted integral).
 // Second arithmetic profile.  OpenCV itself is not available here or on the GPU box, so
 // parity is against the oracle's restatement of the same lines (oc_detect_opencvlike): unpinned.
-#include "vj_env_internal.hpp"
+#include "vj_points_driver.hpp"
 #include "vj_cv_roi_host.hpp"
 
 #include <algorithm>
@@ -1878,93 +1878,66 @@ int run_cv_roi_pass(vj_env* e, const vj_cascade* c, int W, int H, int nf, const 
 }
 
 // ------------------------------------------------------------------------ a cascade on a caller's windows
-// (what needs no device — argument checks, grouping by scale slot, the unit list, the scatter of results — is vj_cv_points_host.cpp)
-
-// (room in the two caches: cv_point_make_room, vj_env_internal.hpp)
-
-// The stage records of `c` (what vj_detect_opencv's plans hold, once per cascade)
-int get_cv_point_cascade(vj_env* e, const vj_cascade* c, uint64_t call_tick, CvPointCascade** out) {
-    auto it = e->cv_point_cascades.find(c->uid);
-    if (it != e->cv_point_cascades.end()) {
-        it->second->last_used = call_tick;
-        *out = it->second.get();
+// vj_run_windows_opencv: what the shared driver (vj_points_driver.hpp) needs of this profile (device-free: vj_cv_points_host.cpp)
+struct CvPoints {
+    static constexpr const char* name = "vj_run_windows_opencv";
+    typedef CvPointScale Geom;
+    typedef CvPointScaleDev ScaleDev;
+    typedef CvPointResult Result;
+    typedef CvPointArgs Args;
+    static constexpr int waves = CV_WAVES_PER_BLOCK;
+    static constexpr auto scatter = cv_points_scatter;
+    static int check(const vj_cascade* c, const vj_image* frames, int n_frames, const double* scales, int n_scales, const vj_window* windows,
+                     uint32_t n_windows, int start_stage, uint32_t, const vj_window_result* out, int* W, int* H, int* CH) {
+        return cv_points_check(c, frames, n_frames, scales, n_scales, windows, n_windows, start_stage, out, W, H, CH);
+    }
+    static auto& cascades(vj_env* e) { return e->cv_point_cascades; }
+    static auto& plans(vj_env* e) { return e->cv_point_plans; }
+    static vj_env::CvPointPlanKey plan_key(const vj_cascade* c, int W, double scale, uint32_t) {
+        uint64_t bits;
+        memcpy(&bits, &scale, 8);
+        return vj_env::CvPointPlanKey(c->uid, W, bits);
+    }
+    // the stage records vj_detect_opencv's plans hold
+    static void build_stages(const vj_cascade* c, const StageProgram& prog, const std::vector<uint32_t>& order, PointCascade* pc,
+                             std::vector<StageDev>* stages) {
+        const CvShape shape = cv_shape_of(c);
+        pc->trees = shape.trees;
+        pc->is_tree = shape.is_tree;
+        pc->has_tilted = shape.has_tilted;
+        pc->tree2 = shape.tree2;
+        *stages = build_cv_stage_recs(c, prog, order, shape.two_rects, shape.trees, shape.is_tree);
+    }
+    static int geometry(const vj_cascade* c, double scale, int W, int H, CvPointScale* g) {
+        *g = cv_point_scale(c->win_w, c->win_h, scale, W, H);
         return VJ_OK;
     }
-    cv_point_make_room(e, e->cv_point_cascades, call_tick);
-    auto pc = std::make_unique<CvPointCascade>();
-    const StageProgram prog = build_stage_program(*c);
-    std::vector<uint32_t> order;
-    if (!stage_sweep_order(prog, &order)) {
-        set_error("stage links form a cycle");
-        return VJ_ERR_UNSUPPORTED;
-    }
-    const CvShape shape = cv_shape_of(c);
-    pc->trees = shape.trees;
-    pc->is_tree = shape.is_tree;
-    pc->has_tilted = shape.has_tilted;
-    pc->tree2 = shape.tree2;
-    pc->n_order = (uint32_t)order.size();
-    pc->n_stages = (uint32_t)c->stages.size();
-    const std::vector<StageDev> stages = build_cv_stage_recs(c, prog, order, shape.two_rects, shape.trees, shape.is_tree);
-    int rc = pc->d_stages.ensure(stages.size() * sizeof(StageDev));
-    if (!rc && hipMemcpy(pc->d_stages.p, stages.data(), stages.size() * sizeof(StageDev), hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("uploading the stage records failed");
-        rc = VJ_ERR_HIP;
-    }
-    if (rc) {
-        pc->release_device();
-        return rc;
-    }
-    pc->last_used = call_tick;
-    *out = pc.get();
-    e->cv_point_cascades[c->uid] = std::move(pc);
-    return VJ_OK;
-}
-
-// The record and node table of ONE scale on frames of width W (cvSetImagesForHaarClassifierCascade, tempcv.cpp:549-768, reads the
-// image only through its row step).  The table is built when the window fits the W x H frame: no window of a larger one is evaluated.
-int get_cv_point_plan(vj_env* e, const vj_cascade* c, int W, int H, double scale, uint64_t call_tick, CvPointPlan** out) {
-    uint64_t bits;
-    memcpy(&bits, &scale, 8);
-    const vj_env::CvPointPlanKey key(c->uid, W, bits);
-    auto it = e->cv_point_plans.find(key);
-    CvPointPlan* pl = it != e->cv_point_plans.end() ? it->second.get() : nullptr;
-    const uint32_t stride = (uint32_t)W + 1u;
-    const CvPointScale sc = cv_point_scale(c->win_w, c->win_h, scale, W, H);
-    if (!pl) {
-        cv_point_make_room(e, e->cv_point_plans, call_tick);
-        auto fresh = std::make_unique<CvPointPlan>();
-        pl = fresh.get();
-        pl->rec.win_w = (uint32_t)sc.win_w;
-        pl->rec.win_h = (uint32_t)sc.win_h;
-        e->cv_point_plans[key] = std::move(fresh);
-    }
-    pl->last_used = call_tick;
-    if (sc.fits && !pl->d_table.p) {
+    // cvSetImagesForHaarClassifierCascade (tempcv.cpp:549-768) reads the image only through its row step
+    static int build_scale(const vj_cascade* c, double scale, int W, const CvPointScale& sc, CvPointScaleDev* rec, CvNodeRec* table,
+                           uint64_t* max_reach) {
+        const uint32_t stride = (uint32_t)W + 1u;
         // equRect (tempcv.cpp:614-616): x = y = cvRound(scale), (orig - 2) * scale rounded
-        pl->rec.inv_area = sc.weight_scale;
-        pl->rec.q0 = (uint32_t)sc.ex * stride + (uint32_t)sc.ex;
-        pl->rec.q1 = pl->rec.q0 + (uint32_t)sc.ew;
-        pl->rec.q2 = (uint32_t)(sc.ex + sc.eh) * stride + (uint32_t)sc.ex;
-        pl->rec.q3 = pl->rec.q2 + (uint32_t)sc.ew;
-        std::vector<CvNodeRec> table(c->nodes.size());
-        pl->max_reach = std::max<uint64_t>(pl->rec.q3, 0);
-        int rc = build_cv_node_recs(c, scale, stride, sc.weight_scale, table.data(), &pl->max_reach);
-        if (!rc) rc = pl->d_table.ensure(std::max<size_t>(table.size(), 1) * sizeof(CvNodeRec));
-        if (!rc && !table.empty() && hipMemcpy(pl->d_table.p, table.data(), table.size() * sizeof(CvNodeRec), hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("uploading a node table failed");
-            rc = VJ_ERR_HIP;
-        }
-        if (rc) {
-            pl->release_device();
-            e->cv_point_plans.erase(key);
-            return rc;
-        }
-        pl->rec.table = (const CvNodeRec*)pl->d_table.p;
+        rec->inv_area = sc.weight_scale;
+        rec->q0 = (uint32_t)sc.ex * stride + (uint32_t)sc.ex;
+        rec->q1 = rec->q0 + (uint32_t)sc.ew;
+        rec->q2 = (uint32_t)(sc.ex + sc.eh) * stride + (uint32_t)sc.ex;
+        rec->q3 = rec->q2 + (uint32_t)sc.ew;
+        *max_reach = rec->q3;
+        return build_cv_node_recs(c, scale, stride, sc.weight_scale, table, max_reach);
     }
-    *out = pl;
-    return VJ_OK;
-}
+    static int extra_images(vj_env* e, const PointCascade& pc, const uint8_t* d_gray, size_t gray_frame_bytes, int gray_stride, int W, int H,
+                            int nf, int CH) {
+        return pc.has_tilted ? enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH) : VJ_OK;
+    }
+    static void fill_args(const vj_env* e, const PointCascade& pc, uint32_t, CvPointArgs* a) {
+        a->tilted = pc.has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
+        a->tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
+        a->tree2 = pc.tree2 && !pc.is_tree && !pc.has_tilted && e->cv_tree2 ? 1u : 0u;
+    }
+    static int launch(const CvPointArgs& a, const PointCascade& pc, int n_blocks, void* stream) {
+        return launch_cv_points_pass(a, pc.trees, pc.is_tree, n_blocks, stream);
+    }
+};
 
 const uint32_t CV_ROI_FAST_FLAGS = VJ_FLAG_COUNTERS;   // a flag word within these takes the region pass
 
@@ -2171,134 +2144,13 @@ int vj_detect_opencv_chain(vj_env* e, const vj_cascade* first, const vj_cascade*
 // cvSetImagesForHaarClassifierCascade + cvRunHaarClassifierCascade on a caller's windows (tempcv.cpp:549-768, :795-984)
 int vj_run_windows_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const double* scales, int n_scales,
                           const vj_window* windows, uint32_t n_windows, int start_stage, vj_window_result* out) {
-    int W = 0, H = 0, CH = 1;
-    int rc = cv_points_check(c, frames, n_frames, scales, n_scales, windows, n_windows, start_stage, out, &W, &H, &CH);
-    if (rc) return rc;
-    if (n_windows == 0) return VJ_OK;
-    if (!e) {
-        set_error("vj_run_windows_opencv: no environment");
-        return VJ_ERR_ARG;
-    }
-    if ((int)c->stages.size() > VJ_MAX_STAGES || c->stages.empty()) {
-        set_error("cascade has %zu stages; 1..%d are supported", c->stages.size(), VJ_MAX_STAGES);
-        return VJ_ERR_LIMIT;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));   // (plans may be released below)
-    const uint64_t call_tick = ++e->plan_tick;
-    CvPointCascade* pc;
-    if ((rc = get_cv_point_cascade(e, c, call_tick, &pc))) return rc;
-    const uint32_t stride = (uint32_t)W + 1u;
-    const uint32_t frame_elems = frame_elems_for(W, H);
-    // the slots some window names: their records; the others keep a window no frame holds (they are never read)
-    std::vector<uint8_t> used((size_t)n_scales, 0);
-    for (uint32_t i = 0; i < n_windows; ++i) used[(size_t)windows[i].scale] = 1;
-    std::vector<CvPointScaleDev> recs((size_t)n_scales);
-    for (int k = 0; k < n_scales; ++k) {
-        memset(&recs[(size_t)k], 0, sizeof(CvPointScaleDev));
-        recs[(size_t)k].win_w = recs[(size_t)k].win_h = CV_POINT_WIN_MAX;
-        if (!used[(size_t)k]) continue;
-        CvPointPlan* pl;
-        if ((rc = get_cv_point_plan(e, c, W, H, scales[k], call_tick, &pl))) return rc;
-        recs[(size_t)k] = pl->rec;
-        if ((int)pl->rec.win_w > W || (int)pl->rec.win_h > H) {   // -1 everywhere
-            recs[(size_t)k].table = nullptr;
-            continue;
-        }
-        // evaluated windows lie inside the frame (border rule); a feature may overshoot its window by one column / row (separate
-        // rounding): the frame allocation's zeroed slack rows, as for whole frames
-        const uint64_t origin_max = (uint64_t)(H - (int)pl->rec.win_h) * stride + (uint64_t)(W - (int)pl->rec.win_w);
-        if (origin_max + pl->max_reach >= (uint64_t)frame_elems) {
-            set_error("scale %d (%.17g): feature reach exceeds the frame allocation", k, scales[k]);
-            return VJ_ERR_LIMIT;
-        }
-    }
-    if ((rc = e->d_cv_point_scales.ensure(recs.size() * sizeof(CvPointScaleDev)))) return rc;
-    HIP_TRY(hipMemcpy(e->d_cv_point_scales.p, recs.data(), recs.size() * sizeof(CvPointScaleDev), hipMemcpyHostToDevice));
-    // a sub-batch: its sum images within 32-bit byte offsets, and its sqsum images too (one buffer descriptor for all of its frames)
-    const uint64_t frame_bytes = (uint64_t)frame_elems * 4u;
-    if (frame_bytes * 2u > 0xfffffff0ull) {   // (the kernel's 32-bit sqsum offsets would wrap)
-        set_error("vj_run_windows_opencv: a %d x %d frame's sqsum image exceeds one 4 GiB buffer descriptor", W, H);
-        return VJ_ERR_LIMIT;
-    }
-    int max_frames = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_frames, 0xfffffff0ull / (frame_bytes * 2u)));
-    if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
-    std::vector<uint32_t> order;
-    std::vector<size_t> sub_first;
-    cv_points_order(windows, n_windows, n_frames, max_frames, &order, &sub_first);
-    e->cv_points_integral_ms = e->cv_points_pass_ms = 0.0f;
-    std::vector<CvPointDev> points;
-    std::vector<CvPointUnit> units;
-    std::vector<CvPointResult> res;
-    for (size_t b = 0; b + 1 < sub_first.size(); ++b) {
-        const size_t m = sub_first[b + 1] - sub_first[b];
-        if (m == 0) continue;   // (a sub-batch no window looks at is not uploaded; within one, every frame is)
-        const int f0 = (int)b * max_frames, nf = std::min(max_frames, n_frames - f0);
-        const uint32_t* ord = order.data() + sub_first[b];
-        cv_points_build(windows, ord, m, f0, &points, &units);
-        if ((rc = ensure_image_buffers(e, W, H, nf, true, CH))) return rc;
-        const uint8_t* d_gray;
-        size_t gray_frame_bytes;
-        int gray_stride;
-        if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
-        HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
-        if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
-        if (pc->has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
-        HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
-        if ((rc = e->d_cv_points.ensure(points.size() * sizeof(CvPointDev)))) return rc;
-        if ((rc = e->d_cv_point_units.ensure(units.size() * sizeof(CvPointUnit)))) return rc;
-        if ((rc = e->d_cv_point_out.ensure(m * sizeof(CvPointResult)))) return rc;
-        HIP_TRY(hipMemcpyAsync(e->d_cv_points.p, points.data(), points.size() * sizeof(CvPointDev), hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->d_cv_point_units.p, units.data(), units.size() * sizeof(CvPointUnit), hipMemcpyHostToDevice, e->stream));
-        CvPointArgs a;
-        memset(&a, 0, sizeof(a));
-        a.sum = (const uint32_t*)e->d_sum.p;
-        a.sqsum = (const uint64_t*)e->d_sqsum.p;
-        a.tilted = pc->has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
-        a.scales = (const CvPointScaleDev*)e->d_cv_point_scales.p;
-        a.stages = (const StageDev*)pc->d_stages.p;
-        a.points = (const CvPointDev*)e->d_cv_points.p;
-        a.units = (const CvPointUnit*)e->d_cv_point_units.p;
-        a.out = (CvPointResult*)e->d_cv_point_out.p;
-        a.n_units = (uint32_t)units.size();
-        a.n_points = (uint32_t)m;
-        a.n_frames = (uint32_t)nf;
-        a.frame_elems = frame_elems;
-        a.stride = stride;
-        a.width = (uint32_t)W;
-        a.height = (uint32_t)H;
-        a.n_stages = pc->n_stages;
-        a.n_order = pc->n_order;
-        a.start_stage = (uint32_t)std::min<int>(start_stage, (int)pc->n_stages);
-        a.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
-        a.tree2 = pc->tree2 && !pc->is_tree && !pc->has_tilted && e->cv_tree2 ? 1u : 0u;
-        // one wave per unit, at most four workgroups (16 waves) per CU; the rest by stride
-        const int n_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((units.size() + CV_WAVES_PER_BLOCK - 1) / CV_WAVES_PER_BLOCK, (uint64_t)std::max(1, e->n_cu * 4)));
-        a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
-        HIP_TRY(hipEventRecord(e->lane0.ev[2], e->stream));
-        const int hrc = launch_cv_points_pass(a, pc->trees, pc->is_tree, n_blocks, e->stream);
-        if (hrc) {
-            set_error("window-list launch failed: %s", hipGetErrorString((hipError_t)hrc));
-            return VJ_ERR_HIP;
-        }
-        HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
-        res.resize(m);
-        HIP_TRY(hipMemcpyAsync(res.data(), e->d_cv_point_out.p, m * sizeof(CvPointResult), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        float ms_i = 0, ms_p = 0;
-        HIP_TRY(hipEventElapsedTime(&ms_i, e->lane0.ev[0], e->lane0.ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms_p, e->lane0.ev[2], e->lane0.ev[3]));
-        e->cv_points_integral_ms += ms_i;
-        e->cv_points_pass_ms += ms_p;
-        cv_points_scatter(res.data(), ord, m, out);
-    }
-    return VJ_OK;
+    return run_points<CvPoints>(e, c, frames, n_frames, scales, n_scales, windows, n_windows, start_stage, 0u, out);
 }
 
 int vj_run_windows_timing(const vj_env* e, float* integral_ms, float* pass_ms) {
     if (!e) return VJ_ERR_ARG;
-    if (integral_ms) *integral_ms = e->cv_points_integral_ms;
-    if (pass_ms) *pass_ms = e->cv_points_pass_ms;
+    if (integral_ms) *integral_ms = e->points_integral_ms;
+    if (pass_ms) *pass_ms = e->points_pass_ms;
     return VJ_OK;
 }
 

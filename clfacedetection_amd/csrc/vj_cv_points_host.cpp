@@ -1,4 +1,4 @@
-// Host side of vj_run_windows_opencv that needs no device: see vj_cv_points_host.hpp.
+// Host side of the window-list calls that needs no device: see vj_cv_points_host.hpp.
 #include "vj_cv_points_host.hpp"
 
 #include <algorithm>
@@ -11,52 +11,30 @@ namespace {
 int round_clamped(double v) { return v < (double)CV_POINT_WIN_MAX ? cv_round(v) : (int)CV_POINT_WIN_MAX; }
 }  // namespace
 
-int cv_points_check(const vj_cascade* c, const vj_image* frames, int n_frames, const double* scales, int n_scales,
-                    const vj_window* windows, uint32_t n_windows, int start_stage, const vj_window_result* out, int* W, int* H, int* CH) {
+int points_check_cascade(const char* fn, const vj_cascade* c, int start_stage) {
     if (!c) {
-        set_error("vj_run_windows_opencv: no cascade");
+        set_error("%s: no cascade", fn);
         return VJ_ERR_ARG;
     }
     if (start_stage < 0) {
-        set_error("vj_run_windows_opencv: start_stage %d is negative", start_stage);
+        set_error("%s: start_stage %d is negative", fn, start_stage);
         return VJ_ERR_ARG;
     }
     bool is_tree = false;
     for (const auto& st : c->stages) is_tree |= st.next != -1;
-    if (is_tree && start_stage != 0) {   // assert(start_stage == 0), tempcv.cpp:837
-        set_error("vj_run_windows_opencv: a stage tree starts at stage 0 only (start_stage %d)", start_stage);
+    if (is_tree && start_stage != 0) {   // the walk of tempcv.cpp:834-861 starts at the root (assert, :837)
+        set_error("%s: a stage tree starts at stage 0 only (start_stage %d)", fn, start_stage);
         return VJ_ERR_ARG;
-    }
-    if (n_windows == 0) return VJ_OK;
-    if (!windows || !out || !scales || !frames || n_frames <= 0 || n_scales <= 0) {
-        set_error("vj_run_windows_opencv: %u windows need frames, scales and a result array", n_windows);
-        return VJ_ERR_ARG;
-    }
-    if (n_windows > CV_POINTS_MAX) {
-        set_error("vj_run_windows_opencv: %u windows; at most %u per call", n_windows, CV_POINTS_MAX);
-        return VJ_ERR_LIMIT;
-    }
-    if (!cv_frames_uniform(frames, n_frames, W, H, CH)) {
-        set_error("vj_run_windows_opencv: the frames must be of one size and channel count (1, 3 or 4), with data");
-        return VJ_ERR_ARG;
-    }
-    for (int k = 0; k < n_scales; ++k)
-        if (!(std::isfinite(scales[k]) && scales[k] > 0.0)) {   // cvSetImagesForHaarClassifierCascade: scale <= 0 is refused (tempcv.cpp:568)
-            set_error("vj_run_windows_opencv: scale %d is %.17g; a scale is finite and > 0", k, scales[k]);
-            return VJ_ERR_ARG;
-        }
-    for (uint32_t i = 0; i < n_windows; ++i) {
-        const vj_window& w = windows[i];
-        if (w.frame < 0 || w.frame >= n_frames) {
-            set_error("vj_run_windows_opencv: window %u names frame %d of %d", i, w.frame, n_frames);
-            return VJ_ERR_ARG;
-        }
-        if (w.scale < 0 || w.scale >= n_scales) {
-            set_error("vj_run_windows_opencv: window %u names scale %d of %d", i, w.scale, n_scales);
-            return VJ_ERR_ARG;
-        }
     }
     return VJ_OK;
+}
+
+int cv_points_check(const vj_cascade* c, const vj_image* frames, int n_frames, const double* scales, int n_scales,
+                    const vj_window* windows, uint32_t n_windows, int start_stage, const vj_window_result* out, int* W, int* H, int* CH) {
+    const char* fn = "vj_run_windows_opencv";
+    const int rc = points_check_cascade(fn, c, start_stage);
+    if (rc) return rc;
+    return points_check_lists(fn, frames, n_frames, scales, n_scales, windows, n_windows, out, W, H, CH, [](int) { return VJ_OK; });
 }
 
 CvPointScale cv_point_scale(int orig_w, int orig_h, double scale, int W, int H) {

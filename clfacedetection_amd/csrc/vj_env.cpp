@@ -2064,7 +2064,7 @@ void vj_env_destroy(vj_env* e) {
                       &e->d_cv_accept, &e->d_cv_tq, &e->d_cv_fail_rows, &e->d_cv_fail_walk, &e->d_run_table,
                       &e->d_canny_cls, &e->d_canny_label, &e->d_canny_flag, &e->d_edges, &e->d_edge_sum,
                       &e->d_cv_prune_bits, &e->d_pyr, &e->d_pyr_tab, &e->d_cv_big, &e->d_cv_rois, &e->d_cv_roi_units,
-                      &e->d_cv_points, &e->d_cv_point_units, &e->d_cv_point_scales, &e->d_cv_point_out})
+                      &e->d_points, &e->d_point_units, &e->d_point_scales, &e->d_point_out})
         b->release();
     e->lane0.destroy();
     for (DevBuf& b : e->d_q) b.release();

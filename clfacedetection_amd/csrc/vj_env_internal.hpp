@@ -14,6 +14,7 @@
 #include <map>
 #include <memory>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 namespace vj {
@@ -162,35 +163,20 @@ struct CvRoiPlan {
     }
 };
 
-// What the window-list pass (vj_run_windows_opencv; vj_cv_points.hip) derives from the cascade alone — the stage
-// records — and from (cascade, frame stride, ONE scale): the scale's record and node table.  A call may name any number of scales;
-// each is a plan of its own, so that the scales of successive calls (a tracker's jitter set, a ROC's fixed ladder) are built once.
-struct CvPointCascade {
+// What a window-list pass (vj_cv_points.hip, vj_points.hip) derives from the cascade alone — the stage records — and
+// from (cascade, frame stride, ONE scale): the scale's record and node table.  A call may name any number of scales; each is a plan
+// of its own, so that the scales of successive calls (a tracker's jitter set, a ROC's fixed ladder) are built once.
+struct PointCascade {
     uint32_t n_stages = 0, n_order = 0;
-    bool trees = false, is_tree = false, has_tilted = false, tree2 = false;
+    bool trees = false, is_tree = false, has_tilted = false, tree2 = false;   // (the clod profile leaves the last two false)
     DevBuf d_stages;
     uint64_t last_used = 0;
     void release_device() { d_stages.release(); }
 };
-struct CvPointPlan {
-    CvPointScaleDev rec = {};     // table = d_table.p once built; win_w / win_h / equRect whatever the frame's height
-    uint64_t max_reach = 0;       // furthest element a feature touches, from the window origin (valid once the table is built)
-    DevBuf d_table;               // built at the first call whose frame the window fits (no window of a larger one is evaluated)
-    uint64_t last_used = 0;
-    void release_device() { d_table.release(); }
-};
-
-// The same two for the clod profile's window-list pass (vj_run_windows; vj_points.hip): the stage records of a
-// cascade, and the record and node table (build_node_table, the code behind vj_plan_feature_table) of ONE scale on frames of one width.
-struct ClodPointCascade {
-    uint32_t n_stages = 0, n_order = 0;
-    bool trees = false, is_tree = false;
-    DevBuf d_stages;
-    uint64_t last_used = 0;
-    void release_device() { d_stages.release(); }
-};
-struct ClodPointPlan {
-    ClodPointScaleDev rec = {};   // table = d_table.p once built; win_w / win_h whatever the frame's height
+template <class ScaleDev>   // CvPointScaleDev, ClodPointScaleDev
+struct PointPlan {
+    typedef std::remove_cv_t<std::remove_pointer_t<decltype(ScaleDev::table)>> Node;   // CvNodeRec, NodeRec
+    ScaleDev rec = {};            // table = d_table.p once built; win_w / win_h whatever the frame's height
     uint64_t max_reach = 0;       // furthest element a feature or the variance rectangle touches, from the window origin (once built)
     DevBuf d_table;               // built at the first call whose frame the window fits (no window of a larger one is evaluated)
     uint64_t last_used = 0;
@@ -396,18 +382,18 @@ struct vj_env : vj::Tunables {
     typedef std::tuple<uint64_t, int, uint64_t> CvRoiPlanKey;   // cascade uid, frame width (the tables' stride), bits of the scale factor
     std::map<CvRoiPlanKey, std::unique_ptr<vj::CvRoiPlan>> cv_roi_plans;
     vj::DevBuf d_cv_rois, d_cv_roi_units;   // region pass of the OpenCV profile: a sub-batch's regions and work units
-    // vj_run_windows_opencv: per cascade uid; per (cascade uid, frame width, bits of the scale).  Both under plan_cache_max, least
-    // recently used first — except the plans of the call in progress, which may name more scales than that
-    std::map<uint64_t, std::unique_ptr<vj::CvPointCascade>> cv_point_cascades;
+    // The window-list calls (vj_points_driver.hpp), per profile: stage records per cascade uid; plans per (cascade uid, frame width, bits of
+    // the scale[, tilted-as-upright]).  Under plan_cache_max, least recently used first — except the plans of the call in progress
+    typedef std::map<uint64_t, std::unique_ptr<vj::PointCascade>> PointCascades;
+    PointCascades cv_point_cascades, clod_point_cascades;
     typedef std::tuple<uint64_t, int, uint64_t> CvPointPlanKey;
-    std::map<CvPointPlanKey, std::unique_ptr<vj::CvPointPlan>> cv_point_plans;
-    float cv_points_integral_ms = 0, cv_points_pass_ms = 0;   // ... device times of the last run-windows call of either profile, summed over its sub-batches (vj_run_windows_timing)
-    vj::DevBuf d_cv_points, d_cv_point_units, d_cv_point_scales, d_cv_point_out;   // ... a sub-batch's windows, units and verdicts; the call's scale records
-    // vj_run_windows, the clod profile's twin: its caches, keyed and bounded the same way (the key's last member: tilted-as-upright);
-    // its calls use the four buffers and the two times above (one call runs at a time; the records have the same sizes)
-    std::map<uint64_t, std::unique_ptr<vj::ClodPointCascade>> clod_point_cascades;
+    std::map<CvPointPlanKey, std::unique_ptr<vj::PointPlan<vj::CvPointScaleDev>>> cv_point_plans;
     typedef std::tuple<uint64_t, int, uint32_t, int> ClodPointPlanKey;
-    std::map<ClodPointPlanKey, std::unique_ptr<vj::ClodPointPlan>> clod_point_plans;
+    std::map<ClodPointPlanKey, std::unique_ptr<vj::PointPlan<vj::ClodPointScaleDev>>> clod_point_plans;
+    // ... both profiles, one call at a time: the last call's device times, summed over its sub-batches (vj_run_windows_timing); a
+    // sub-batch's windows, units and verdicts and the call's scale records, each buffer sized in bytes per call
+    float points_integral_ms = 0, points_pass_ms = 0;
+    vj::DevBuf d_points, d_point_units, d_point_scales, d_point_out;
     vj::DevBuf d_cv_det, d_cv_counts;   // vj_detect_opencv: detection list and counters
     vj::DevBuf d_cv_accept, d_cv_tq;    // ... stage trees on tiles: accept bitmap, the queue of the prefix's survivors
     vj::DevBuf d_cv_fail_rows, d_cv_fail_walk;   // ... per-wave fail lists of the chain sweeps (rows kernel / chain pass)
@@ -438,7 +424,7 @@ int enqueue_tilted(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int str
 // first, but never an entry of the call in progress (last_used >= call_tick) — a call that names more scales than plan_cache_max
 // keeps them all while it runs.
 template <typename Map>
-void cv_point_make_room(vj_env* e, Map& m, uint64_t call_tick) {
+void point_make_room(vj_env* e, Map& m, uint64_t call_tick) {
     while ((int)m.size() >= std::max(1, e->plan_cache_max)) {
         auto lru = m.end();
         for (auto i = m.begin(); i != m.end(); ++i)

@@ -20,10 +20,9 @@ struct ClodPointScale {
 // VJ_ERR_ARG when win_w, win_h or the area is 0 (the reference would divide by zero)
 int clod_point_scale(int orig_w, int orig_h, float scale, int W, int H, ClodPointScale* out);
 
-// Everything of the call that can be refused without a device, in the order the header states it: the cascade, start_stage
-// (negative; non-zero on a stage tree), the flags (a bit other than VJ_FLAG_SIGNED_MEAN / VJ_FLAG_TILTED_AS_UPRIGHT: VJ_ERR_ARG;
-// tilted features without the latter: VJ_ERR_UNSUPPORTED), then — n_windows == 0 is VJ_OK before any of these — the pointers, the
-// window count, the frames (cv_frames_uniform), the scales (finite, > 0, clod_point_scale), the windows' frame and scale indices.
+// Everything of the call that can be refused without a device, in the order the header states it: points_check_cascade, the flags
+// (a bit other than VJ_FLAG_SIGNED_MEAN / VJ_FLAG_TILTED_AS_UPRIGHT: VJ_ERR_ARG; tilted features without the latter:
+// VJ_ERR_UNSUPPORTED), then points_check_lists, whose scales pass clod_point_scale too (vj_cv_points_host.hpp).
 // *W, *H, *CH: the frames' geometry (set when n_windows != 0).
 int clod_points_check(const vj_cascade* c, const vj_image* frames, int n_frames, const float* scales, int n_scales,
                       const vj_window* windows, uint32_t n_windows, int start_stage, uint32_t flags, const vj_clod_window_result* out,

@@ -6,8 +6,9 @@ import numpy as np
 import pytest
 
 import clod_window_oracle as cw
+import run_window_oracle as rw
 from clfacedetection_amd import (VJ_FLAG_COUNTERS, VJ_FLAG_SIGNED_MEAN, VJ_FLAG_TILTED_AS_UPRIGHT, VJ_WINDOW_OUTSIDE, DeviceFrames,
-                                 VjError, default_params, run_windows, runCascade)
+                                 VjError, default_params, run_windows, run_windows_opencv, runCascade)
 from clfacedetection_amd.api import CLOD_WINDOW_RESULT_DTYPE, WINDOW_DTYPE
 
 pytestmark = pytest.mark.gpu
@@ -312,3 +313,36 @@ def test_more_scales_than_the_plan_cache_holds(env, cascades):
     w = w[rng.permutation(len(w))]
     check(env, c, a, [frame(1)], w, scales)
     check(env, c, a, [frame(1)], w[::-1], scales)
+
+
+def test_profiles_share_one_environment(env, cascades):
+    """The two profiles' calls in turn on one environment, whose window, unit, verdict and scale-record buffers they share: OpenCV
+    with 129 windows over 2 scales (48-byte scale records), clod with one window, OpenCV with one window, then clod with 129 windows
+    over 3 scales — more scale records, of the other size (32 bytes), than any call before it.  Each call against its own oracle,
+    as the `check` helpers of the two files compare; the device times of each are reported."""
+    c, a = cascades("frontalface_alt")
+    f = [frame(1)]
+
+    def rows(grid_of, scales, n):
+        per = [n // len(scales) + (k < n % len(scales)) for k in range(len(scales))]
+        w = np.concatenate([np.column_stack([np.zeros(m, np.int64), grid_of(a, s)[50:50 + m], np.full(m, k)])
+                            for k, (s, m) in enumerate(zip(scales, per))])
+        assert len(w) == n
+        return w
+
+    def opencv(scales, n):
+        w = rows(rw.grid_of, scales, n)
+        res, sums = run_windows_opencv(f, c, env, w, scales)
+        want_res, want_sums = rw.run_windows(a, f, w, scales)
+        assert res.dtype == np.int32 and sums.dtype == np.float64 and len(res) == len(sums) == n
+        assert np.array_equal(res, want_res) and np.array_equal(sums.view(np.uint64), want_sums.view(np.uint64))
+        assert all(t > 0.0 for t in env.run_windows_timing())
+
+    def clod(scales, n):
+        check(env, c, a, f, rows(cw.grid_of, scales, n), scales)
+        assert all(t > 0.0 for t in env.run_windows_timing())
+
+    opencv(rw.case_scales()[:2], 129)
+    clod(cw.case_scales()[1:2], 1)
+    opencv(rw.case_scales()[2:3], 1)
+    clod(cw.case_scales()[:3], 129)
