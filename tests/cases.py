@@ -933,3 +933,311 @@ def near_flat_frames(size, n_off: int) -> np.ndarray:
 
 BRIGHT_MIN = 3000           # min_w / min_h of the bright-frame calls: the five largest scales (windows of 3125 .. 4575 pixels)
 BRIGHT_CASCADES = ("frontalface_alt", "frontalface_alt_tree")
+
+
+# ----------------------------------------------------------------------------- cascade topologies
+# Cascade SHAPES on each side of the planners' and kernels' fixed-size assumptions ("Fixed-size assumptions"):
+# stage counts around VJ_MAX_STAGES, stage widths around the two stump-parallel tails, node trees beyond {root, child}, stage
+# trees around CvChainDev::begin[4] / CascadeArgs::seg_end[4] and VJ_MAX_PASSES.  tests/test_topology_cases_cpu.py proves the
+# premises on the oracle alone and keeps the table on both sides of every limit; tests/test_gpu_topologies.py runs every case
+# through every entry point that takes a cascade.  These are structure tests, not rounding tests: every leaf is a multiple of
+# 2^-6 of magnitude <= 2 (as in tie_cascade), so every order of addition gives the same exact sum, and every stage threshold
+# lies halfway between two attained sums.
+TOPOLOGY_SIZE = (240, 320)
+# (stumps, how many must say yes): 1/2, 1/2, 5/16 and 11/16 of the windows on noise; the fifth form, 1/16, is for the cascades
+# too short to get below a tenth of the windows with the others (lin1, lin2)
+TOPOLOGY_SEL_FORMS = ((1, 1), (3, 2), (4, 3), (4, 2), (4, 4))
+TOPOLOGY_WIDE_STAGE = ORDER_PREFIX                      # index of the decisive stage of the w* cases
+_TOPOLOGY, _TOPOLOGY_CHAINS = {}, {}
+
+
+class _Spots:
+    """Hands every node a 3 x 3 spot of its own (_small_spot visits the 324 positions before it repeats)."""
+    def __init__(self, first: int = 0):
+        self.k = first
+
+    def take(self):
+        self.k += 1
+        return _small_spot(self.k - 1)
+
+
+def _stump(sp, lo=0.0, hi=1.0):
+    return ([_mean_node(sp.take(), 0, -1)], [lo, hi])
+
+
+def _all_stage(sp):
+    """Accepts every window: one stump with leaves 0 / 1 under a stage threshold of -1."""
+    return ([_stump(sp)], -1.0)
+
+
+def _sel_stage(sp, form: int = 0):
+    """`n` mean-vs-spot stumps with leaves 0 / 1, `need` of which must say yes: the threshold need - 0.5 lies halfway between
+    two attained sums."""
+    n, need = TOPOLOGY_SEL_FORMS[form]
+    return ([_stump(sp) for _ in range(n)], need - 0.5)
+
+
+def _sel_stage_tree2(sp):
+    """A selective stage of two {root, child at index 1} trees: a tree says yes when its root's spot is
+    dark and its child's is bright (1 in 4 on noise); one of the two is enough (7 in 16)."""
+    def tree():
+        return ([_mean_node(sp.take(), 1, 0), _mean_node(sp.take(), -1, -2)], [0.0, 0.0, 1.0])
+    return ([tree(), tree()], 0.5)
+
+
+# node trees: (left, right) per node, > 0 a node of the tree, <= 0 minus a leaf index; leaves are numbered in the order in
+# which a reader of the XML meets them (icvReadHaarClassifier), node by node, left before right
+def _shape_links(shape: str):
+    if shape == "stump":
+        return [(0, -1)]
+    if shape == "tree2":                       # the child hangs on the root's left branch
+        return [(1, 0), (-1, -2)]
+    if shape == "tree2r":                      # ... on its right branch
+        return [(0, 1), (-1, -2)]
+    if shape == "tree3y":                      # a root with two internal children
+        return [(1, 2), (0, -1), (-2, -3)]
+    if shape == "tree7":                       # the full binary tree of 7 nodes and 8 leaves
+        return [(1, 2), (3, 4), (5, 6), (0, -1), (-2, -3), (-4, -5), (-6, -7)]
+    if shape == "spine15":                     # each node's left branch is the next node
+        return [(k + 1, -k) for k in range(14)] + [(-14, -15)]
+    raise ValueError(shape)
+
+
+def _tree_values(links, leaves, bits):
+    """The leaf value every row of `bits` (rows x nodes; 1: the node's sum reaches its threshold, the walk goes right) ends on."""
+    left = np.array([l for l, _ in links])
+    right = np.array([r for _, r in links])
+    rows = np.arange(len(bits))
+    cur = np.zeros(len(bits), np.int64)
+    leaf = np.zeros(len(bits), np.int64)
+    active = np.ones(len(bits), bool)
+    for _ in links:
+        nxt = np.where(bits[rows, cur] != 0, right[cur], left[cur])
+        done = active & (nxt <= 0)
+        leaf[done] = -nxt[done]
+        active &= nxt > 0
+        cur = np.where(active, nxt, cur)
+    return np.asarray(leaves)[leaf]
+
+
+def _midpoint_threshold(sums) -> float:
+    """Halfway between the median attained sum and the attained sum below it."""
+    u = np.unique(sums)
+    m = int(np.searchsorted(u, np.sort(sums)[len(sums) // 2]))
+    m = max(m, 1)
+    return float(np.float32((u[m] + u[m - 1]) / 2.0))
+
+
+def _tree_stage(rng, sp, shapes):
+    """A stage of node trees of the given shapes, leaves seeded multiples of 2^-6 in [-1.5, 1.5]; the stage threshold is the
+    midpoint below the median sum under independent fair node bits (what the spots give on noise)."""
+    trees, total = [], np.zeros(4000)
+    for shape in shapes:
+        links = _shape_links(shape)
+        leaves = rng.permutation(np.arange(-96, 97))[:len(links) + 1] / 64.0      # distinct: every leaf can be told from the others
+        trees.append(([_mean_node(sp.take(), l, r) for l, r in links], [float(v) for v in leaves]))
+        total = total + _tree_values(links, leaves, rng.integers(0, 2, (4000, len(links))))
+    return trees, _midpoint_threshold(total)
+
+
+def _wide_stage(rng, sp, n: int):
+    """One decisive stage of n stumps with tie_cascade's leaves (no limit on n: the 324 spots repeat)."""
+    left = rng.integers(-96, 97, n) / 64.0
+    right = np.clip(left + rng.integers(1, 9, n) * rng.choice([-1, 1], n) / 64.0, -2.0, 2.0)
+    spots = [sp.take() for _ in range(n)]
+    first = {}
+    bits = rng.integers(0, 2, (4000, n))
+    for k, s in enumerate(spots):            # a repeated spot gives the same verdict
+        bits[:, k] = bits[:, first.setdefault(s, k)]
+    sums = np.where(bits != 0, right[None, :], left[None, :]).sum(1)
+    trees = [([_mean_node(spots[k], 0, -1)], [float(left[k]), float(right[k])]) for k in range(n)]
+    return trees, _midpoint_threshold(sums)
+
+
+def _link_stages(c, parent, nxt):
+    """Sets parent / next and the child links icvReadHaarClassifier would have set (a stage's first child by index)."""
+    n = c.n_stages
+    child = np.full(n, -1, np.int32)
+    for i in range(n):
+        if parent[i] != -1 and child[parent[i]] == -1:
+            child[parent[i]] = i
+    c.stage_parent, c.stage_next, c.stage_child = np.array(parent, np.int32), np.array(nxt, np.int32), child
+    return c
+
+
+def _stage_tree(name: str, n_prefix: int, chain_lens, stage=_sel_stage, forms=None):
+    """A prefix of n_prefix stages and chains of the given lengths, all children of the prefix's last stage (of nothing
+    without a prefix); each chain's first stage has the next chain's first stage as its `next`, so a reject anywhere in a
+    chain starts the next chain.  A chain's last stage has no child.  Returns (CascadeArrays, [(first, end) of every chain])."""
+    sp = _Spots()
+    n = n_prefix + sum(chain_lens)
+    if forms:                         # (None: a stage that accepts every window)
+        stages = [_all_stage(sp) if forms[i] is None else _sel_stage(sp, forms[i]) for i in range(n)]
+    else:
+        stages = [stage(sp, i % 4) if stage is _sel_stage else stage(sp) for i in range(n)]
+    c = _linear_cascade(name, stages)
+    parent, nxt = [-1] * n, [-1] * n
+    for i in range(1, n_prefix):
+        parent[i] = i - 1
+    chains, b = [], n_prefix
+    for ln in chain_lens:
+        chains.append((b, b + ln))
+        parent[b] = n_prefix - 1
+        for i in range(b + 1, b + ln):
+            parent[i] = i - 1
+        b += ln
+    for (b0, _), (b1, _) in zip(chains, chains[1:]):
+        nxt[b0] = b1
+    return _link_stages(c, parent, nxt), chains
+
+
+def _build_topology(case_id: str):
+    sp = _Spots()
+    rng = np.random.default_rng([9000, sum(case_id.encode())])
+    name = "topology_" + case_id
+    if case_id.startswith("lin"):
+        n = int(case_id[3:])
+        sel = {0: 0, 1: 1, n // 2 - 1: 2, n - 2: 3, n - 1: 0} if n >= 64 else dict(enumerate({1: [4], 2: [1, 4], 3: [0, 1, 2]}[n]))
+        return _linear_cascade(name, [_sel_stage(sp, sel[i]) if i in sel else _all_stage(sp) for i in range(n)]), []
+    if case_id.startswith("w"):
+        widths = [int(v) for v in case_id[1:].split("x")]
+        widths = widths[:1] * (widths[1] if len(widths) > 1 else 1)
+        sp.k = 20                         # (the thinning prefix has spots of its own, 300 and up)
+        return _linear_cascade(name, _thinning_prefix() + [_wide_stage(rng, sp, w) for w in widths]), []
+    node_trees = {"tree3y": [["tree3y"] * 3] * 5, "tree7": [["tree7"] * 3] * 5, "spine15": [["spine15"] * 3] * 5,
+                  "tree2r": [["tree2r"] * 4] * 5,
+                  "mixed": [["stump", "tree2", "tree7"], ["tree7", "stump", "stump", "tree2"], ["tree2", "tree7", "stump"],
+                            ["stump", "tree7", "tree2", "stump"], ["tree7", "tree2", "stump"]]}
+    if case_id in node_trees:
+        return _linear_cascade(name, [_tree_stage(rng, sp, shapes) for shapes in node_trees[case_id]]), []
+    stage_trees = {"st_root": (0, (3, 3)), "st_p1": (1, (3, 3)), "st_c3": (3, (2, 2, 2)), "st_c4": (3, (2, 2, 2, 2)),
+                   "st_c5": (3, (2, 2, 2, 2, 2)), "st_c3long": (3, (6, 6, 6)), "st_c4long": (3, (6, 6, 6, 6)),
+                   "st_c1": (3, (1, 6, 1))}
+    if case_id == "st_root":              # (5 in 16 a stage: two chains of three loose stages accept more than a tenth of the windows)
+        return _stage_tree(name, *stage_trees[case_id], forms=[2] * 6)
+    if case_id in stage_trees:
+        return _stage_tree(name, *stage_trees[case_id])
+    if case_id == "st_64":                # VJ_MAX_STAGES stages in a stage tree: the 64-bit "entered" masks of the OpenCV-profile kernels carry
+        # bits 32 .. 63 only there.  Prefix 0 1 2, chains 3 .. 32 and 33 .. 63; selective: the prefix, each chain's first and last two stages
+        forms = [0, 1, 2] + [0] + [None] * 27 + [1, 0] + [0] + [None] * 28 + [1, 0]
+        return _stage_tree(name, 3, (30, 31), forms=forms)
+    if case_id == "st_tree2":
+        return _stage_tree(name, *stage_trees["st_c4"], stage=_sel_stage_tree2)
+    if case_id == "st_dead":              # st_c3 and a tenth stage that nothing points to (a second root without a `next` leading to it)
+        c, chains = _stage_tree(name, *stage_trees["st_c3"])
+        d = _linear_cascade(name, [_sel_stage(sp, i % 4) for i in range(10)])   # (the first nine: st_c3's own stages)
+        return _link_stages(d, list(c.stage_parent) + [-1], list(c.stage_next) + [-1]), chains
+    if case_id == "st_cycle":             # st_c3 whose last chain's rejects go back to the first chain
+        c, chains = _stage_tree(name, *stage_trees["st_c3"])
+        c.stage_next[chains[-1][0]] = chains[0][0]
+        return c, chains
+    if case_id == "st_nested":
+        # prefix 0 1 2; the first chain 3 4 5; stage 4 has a sibling list of its own, 6 7 (children of 3): a reject at 4 or 5
+        # goes to 6, one at 3, 6 or 7 to the second chain 8 9 (a child of 2, the `next` of 3)
+        c = _linear_cascade(name, [_sel_stage(sp, i % 4) for i in range(10)])
+        parent = [-1, 0, 1, 2, 3, 4, 3, 6, 2, 8]
+        nxt = [-1, -1, -1, 8, 6, -1, -1, -1, -1, -1]
+        return _link_stages(c, parent, nxt), [(3, 6), (6, 8), (8, 10)]
+    raise KeyError(case_id)
+
+
+def topology_cascade(case_id: str):
+    """oracle CascadeArrays of one topology case (built once; callers copy before they change anything)."""
+    if case_id not in _TOPOLOGY:
+        _TOPOLOGY[case_id], _TOPOLOGY_CHAINS[case_id] = _build_topology(case_id)
+    return _TOPOLOGY[case_id]
+
+
+def topology_chains(case_id: str):
+    """[(first stage, end stage)] of a stage-tree case's chains ([] for the others)."""
+    topology_cascade(case_id)
+    return list(_TOPOLOGY_CHAINS[case_id])
+
+
+# (id, family, (h, w), first frame seed, runnable): frames are arith_frames(size, seed) — a batch of ARITH_FRAMES distinct
+# 240 x 320 noise frames, and its first frame alone.  Not runnable: lin65 (more than VJ_MAX_STAGES stages) and st_cycle are
+# refused by every entry point.  No case needed another frame set or size.
+TOPOLOGY_CELLS = [
+    ("lin1", "linear", TOPOLOGY_SIZE, 300, True), ("lin2", "linear", TOPOLOGY_SIZE, 301, True),
+    ("lin3", "linear", TOPOLOGY_SIZE, 302, True), ("lin64", "linear", TOPOLOGY_SIZE, 303, True),
+    ("lin65", "linear", TOPOLOGY_SIZE, 304, False),
+    ("w256", "wide", TOPOLOGY_SIZE, 310, True), ("w257", "wide", TOPOLOGY_SIZE, 311, True),
+    ("w512", "wide", TOPOLOGY_SIZE, 312, True), ("w513", "wide", TOPOLOGY_SIZE, 313, True),
+    ("w257x2", "wide", TOPOLOGY_SIZE, 314, True),
+    ("tree3y", "trees", TOPOLOGY_SIZE, 320, True), ("tree7", "trees", TOPOLOGY_SIZE, 321, True),
+    ("spine15", "trees", TOPOLOGY_SIZE, 322, True), ("mixed", "trees", TOPOLOGY_SIZE, 323, True),
+    ("tree2r", "trees", TOPOLOGY_SIZE, 324, True),
+    ("st_root", "stage_tree", TOPOLOGY_SIZE, 330, True), ("st_p1", "stage_tree", TOPOLOGY_SIZE, 331, True),
+    ("st_c3", "stage_tree", TOPOLOGY_SIZE, 332, True), ("st_c4", "stage_tree", TOPOLOGY_SIZE, 333, True),
+    ("st_c5", "stage_tree", TOPOLOGY_SIZE, 334, True), ("st_c3long", "stage_tree", TOPOLOGY_SIZE, 335, True),
+    ("st_c4long", "stage_tree", TOPOLOGY_SIZE, 336, True), ("st_c1", "stage_tree", TOPOLOGY_SIZE, 337, True),
+    ("st_nested", "stage_tree", TOPOLOGY_SIZE, 338, True), ("st_dead", "stage_tree", TOPOLOGY_SIZE, 339, True),
+    ("st_cycle", "stage_tree", TOPOLOGY_SIZE, 340, False), ("st_tree2", "stage_tree", TOPOLOGY_SIZE, 341, True),
+    ("st_64", "stage_tree", TOPOLOGY_SIZE, 342, True),
+]
+TOPOLOGY_RUNNABLE = [cell for cell in TOPOLOGY_CELLS if cell[4]]
+
+
+def topology_cell(case_id: str):
+    return next(cell for cell in TOPOLOGY_CELLS if cell[0] == case_id)
+
+
+def topology_frames(cell) -> np.ndarray:
+    return arith_frames(cell[2], cell[3])
+
+
+def stage_links(c):
+    """(on_pass, on_fail) of every stage as the walk of tempcv.cpp:834-861 gives them: a stage index, -1 accept, -2 reject."""
+    on_pass = [int(v) for v in c.stage_child]
+    on_fail = []
+    for s in range(c.n_stages):
+        ptr = s
+        while ptr != -1 and c.stage_next[ptr] == -1:
+            ptr = int(c.stage_parent[ptr])
+        on_fail.append(-2 if ptr == -1 else int(c.stage_next[ptr]))
+    return on_pass, on_fail
+
+
+def reachable_stages(c) -> set:
+    """Stages the pass / fail graph reaches from stage 0."""
+    on_pass, on_fail = stage_links(c)
+    seen, todo = set(), [0]
+    while todo:
+        s = todo.pop()
+        if s < 0 or s in seen:
+            continue
+        seen.add(s)
+        todo += [on_pass[s], on_fail[s]]
+    return seen
+
+
+def linked_linearly(c):
+    """A copy with the same stages in one chain."""
+    import copy
+    t = copy.deepcopy(c)
+    n = t.n_stages
+    t.stage_parent = np.arange(-1, n - 1, dtype=np.int32)
+    t.stage_next = np.full(n, -1, np.int32)
+    t.stage_child = np.array(list(range(1, n)) + [-1], np.int32)
+    return t
+
+
+def without_chain(c, chains, k: int):
+    """A copy without chain k: the `next` that leads to it is cut and joined to the chain after it (the prefix's child link
+    for the first chain), so the other chains stay as they are."""
+    import copy
+    t = copy.deepcopy(c)
+    head = chains[k][0]
+    after = int(t.stage_next[head])
+    for s in range(t.n_stages):
+        if t.stage_next[s] == head:
+            t.stage_next[s] = after
+        if t.stage_child[s] == head:
+            t.stage_child[s] = after
+    return t
+
+
+def topology_passes(n_prefix: int, chain_lens) -> int:
+    """The passes build_plan's segment plan needs with seg_cut2 at its default: one for the prefix, two per chain of more than
+    4 stages, else one."""
+    return 1 + sum(2 if ln > 4 else 1 for ln in chain_lens)
