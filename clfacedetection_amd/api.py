@@ -38,6 +38,7 @@ VJ_FLAG_CV_CANNY_PRUNING = 1 << 6    # OpenCV profile: CV_HAAR_DO_CANNY_PRUNING 
 VJ_FLAG_CV_SCALE_IMAGE = 1 << 7      # OpenCV profile: CV_HAAR_SCALE_IMAGE (the image is scaled, the cascade runs at base size on every grid position)
 VJ_FLAG_CV_FIND_BIGGEST = 1 << 8     # OpenCV profile: CV_HAAR_FIND_BIGGEST_OBJECT (largest window first, one grouped object per frame, then its surroundings only)
 VJ_FLAG_CV_ROUGH_SEARCH = 1 << 9     # OpenCV profile: CV_HAAR_DO_ROUGH_SEARCH (with find-biggest: the search stops at 0.6 of the object's size, not 0.4)
+VJ_FLAG_CV_CHAIN_DEVICE = 1 << 10    # detect_opencv_chain only (flags of the first cascade): regions and units are built on the device, one wait per sub-batch
 
 # cvHaarDetectObjects' flags (tempcv.hpp:127-130).  cvHaarDetectObjects below takes only CV_HAAR_DO_CANNY_PRUNING in its `flags`
 # argument and refuses the other three values there; their paths are reached through `vj_flags` (VJ_FLAG_CV_SCALE_IMAGE,
@@ -120,6 +121,14 @@ class CvPlanInfo(C.Structure):
     """vj_cv_plan_info: the LDS-tile scales and the stage-tree queue of an OpenCV-profile plan."""
     _fields_ = [("tile_windows", C.c_uint64), ("n_tile_scales", C.c_uint32), ("tree_prefix", C.c_uint32),
                 ("tree_queue", C.c_int32), ("tq_shift", C.c_int32), ("tq_split_frames", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CvChainInfo(C.Structure):
+    """vj_cv_chain_info: what the environment's last detect_opencv_chain call did.  handoff: 0 no call yet, 1 on the device, 2 through
+    the host, 3 the two public calls."""
+    _fields_ = [("handoff", C.c_int32), ("sub_batches", C.c_int32), ("sub_batches_device", C.c_int32), ("reruns", C.c_int32),
+                ("regions", C.c_uint64), ("units", C.c_uint64), ("windows", C.c_uint64), ("handoff_ms", C.c_float),
+                ("reserved", C.c_int32)]
 
 
 class _Counters(C.Structure):
@@ -238,6 +247,7 @@ _SIGNATURES = {
     "vj_run_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32,
                                  C.c_int, C.c_uint32, C.c_void_p]),
     "vj_run_windows_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "vj_cv_chain_info_get": (C.c_int, [C.c_void_p, C.POINTER(CvChainInfo)]),
     "vj_cv_plan_info_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CvParams), C.POINTER(CvPlanInfo)]),
     "vj_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params),
                             C.POINTER(_Result)]),
@@ -649,7 +659,9 @@ class Environment:
         """vj_detect_opencv_chain: `first` as detect_opencv runs it, then `second` inside everything it finds (its raw candidates
         when min_neighbors == 0, else its grouped objects) as detect_opencv_rois would; with flags within VJ_FLAG_COUNTERS the
         frames are uploaded and integrated once for both.  Returns (result_first, result_second); result_second.rects['frame']
-        indexes result_first.rects, x / y are relative to that region.  frames: numpy arrays or DeviceFrames."""
+        indexes result_first.rects, x / y are relative to that region.  frames: numpy arrays or DeviceFrames.
+        flags | VJ_FLAG_CV_CHAIN_DEVICE: the hand-off between the two happens on the device (same results; cv_chain_info() tells
+        which way the last call went)."""
         imgs, n, keep = self._images(frames, color)
         p1 = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
         p2 = CvParams(int(min_size_second[0]), int(min_size_second[1]), float(scale_factor_second), int(min_neighbors_second),
@@ -698,6 +710,13 @@ class Environment:
         i, p = C.c_float(0), C.c_float(0)
         _check(load_library().vj_run_windows_timing(self._h, C.byref(i), C.byref(p)), "vj_run_windows_timing")
         return float(i.value), float(p.value)
+
+    def cv_chain_info(self) -> CvChainInfo:
+        """vj_cv_chain_info_get: route, sub-batches, reruns, regions / units / windows and the hand-off kernels' device time of the
+        last detect_opencv_chain call."""
+        info = CvChainInfo()
+        _check(load_library().vj_cv_chain_info_get(self._h, C.byref(info)), "vj_cv_chain_info_get")
+        return info
 
     def cv_plan_info(self, cascade: Cascade, width: int, height: int, n_frames: int, min_size=(0, 0),
                      scale_factor: float = 1.1, min_neighbors: int = 0, flags: int = 0) -> CvPlanInfo:

@@ -1122,11 +1122,38 @@ namespace {
 // rect.frame counts from the call's first frame).
 typedef std::function<int(int f0, int nf, const vj_rect* raw, size_t n_raw)> CvSubBatchHook;
 
+// vj_detect_opencv_chain with VJ_FLAG_CV_CHAIN_DEVICE: what vj_detect_opencv's sub-batch loop calls so that the
+// second cascade is enqueued behind the first before the host waits.  Per attempt at a sub-batch: enqueue() behind the first
+// cascade's launches (hand-off kernels, vj_cv_chain.hip, then the region pass; the state block and the second cascade's counters
+// are copied back on the stream), check() after the synchronisation (a short buffer: grown, *again; a frame the device does not
+// group: the sub-batch goes through the host hook), finish() once the first cascade's result of the sub-batch stands.
+struct CvChainDevice {
+    vj_env* e = nullptr;
+    const vj_cascade* second = nullptr;
+    const vj_cv_params* p_second = nullptr;   // (flags: VJ_FLAG_COUNTERS at most)
+    bool grouped = false;                     // p_first->min_neighbors != 0
+    int32_t threshold = 1;                    // max(min_neighbors, 1)
+    int W = 0, H = 0;
+    CvRoiPlan* rp = nullptr;                  // the second cascade's tables; its factor table is on the device (begin())
+    const CvSubBatchHook* host_hook = nullptr;
+    vj_result* out_second = nullptr;
+    std::vector<vj_rect>* all2 = nullptr;     // the second cascade's candidates (rect.frame = index in out_first)
+    std::vector<vj_rect>* regions = nullptr;  // grouped: the regions of every sub-batch so far — out_first's rectangles
+    uint32_t unit_cap = 0, det2_cap = 0;
+    bool fallback = false;                    // this sub-batch is redone through the host hook
+    CvChainState h_state = {};
+    std::vector<unsigned long long> h_counts2;
+    int begin();
+    int enqueue(int nf, const CvPlan* pl, const CvArgs& a, uint32_t det_cap);
+    int check(bool* again);
+    int finish(int f0, int nf, const vj_rect* raw, size_t n_raw, size_t base);
+};
+
 // vj_detect_opencv.  need_tilted: compute the tilted integral even when `c` has no tilted feature (someone after it reads it).
 // roc: vj_detect_opencv_roc's scale-image call — the kernels report CvRocDet records; the rectangles come back raw (ungrouped),
 // sorted, with their levels and weights in roc's vectors.
 int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_params* p, vj_result* out,
-                       bool need_tilted, const CvSubBatchHook* hook, const CvRocCall* roc = nullptr) {
+                       bool need_tilted, const CvSubBatchHook* hook, const CvRocCall* roc = nullptr, CvChainDevice* dev = nullptr) {
     if (!e || !c || !p || !out || n_frames < 0 || (n_frames > 0 && !frames)) return VJ_ERR_ARG;
     memset(out, 0, sizeof(*out));
     if (n_frames == 0) return VJ_OK;
@@ -1182,7 +1209,8 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
     }
     if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
     // (a ROC call reports several times as many windows: its buffer starts at the configured "det_cap" and grows the same way)
-    uint32_t det_cap = roc ? std::max(1u, e->det_cap_init) : 1u << 16;
+    // (the chain's device hand-off too: its buffers all start at "det_cap", so that a small value drives every regrow path)
+    uint32_t det_cap = roc || dev ? std::max(1u, e->det_cap_init) : 1u << 16;
     const size_t det_bytes = roc ? sizeof(CvRocDet) : sizeof(CvDet);
     std::vector<vj_rect> all;
     std::vector<int32_t> all_levels;   // (ROC) parallel to `all`
@@ -1220,7 +1248,8 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
         bool rows_only = false, done = false, resplit = false;
         const size_t sub_first = all.size();
-        for (int attempt = 0; attempt < 2; ++attempt) {
+        // (the device hand-off may grow three buffers in turn — this cascade's detections, the units, the second cascade's detections)
+        for (int attempt = 0; attempt < (dev ? 5 : 2); ++attempt) {
             if ((rc = d_det.ensure((size_t)det_cap * det_bytes))) return rc;
             HIP_TRY(hipMemsetAsync(d_counts.p, 0, counts_bytes, e->stream));
             CvArgs a;
@@ -1557,6 +1586,7 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
                 return VJ_ERR_HIP;
             }
             HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
+            if (dev && (rc = dev->enqueue(nf, pl, a, det_cap))) return rc;   // (stream2 has joined: every branch above ends on e->stream)
             std::vector<unsigned long long> h((counts_bytes + 7) / 8);
             HIP_TRY(hipMemcpyAsync(h.data(), d_counts.p, counts_bytes, hipMemcpyDeviceToHost, e->stream));
             HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1580,7 +1610,13 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
             }
             if (n_det > det_cap) {   // overflow: grow and redo this sub-batch's cascade
                 det_cap = grown_cap(det_cap, n_det);
+                if (dev) e->cv_chain_info.reruns += 1;
                 continue;
+            }
+            if (dev) {
+                bool again = false;
+                if ((rc = dev->check(&again))) return rc;
+                if (again) continue;
             }
             float ms_i = 0, ms_c = 0, ms_t = 0;
             HIP_TRY(hipEventElapsedTime(&ms_i, e->lane0.ev[0], e->lane0.ev[1]));
@@ -1607,6 +1643,10 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
                 done = true;
                 break;
             }
+            if (dev && dev->grouped && !dev->fallback) {   // the grouped rectangles are read back instead (CvChainDevice::finish)
+                done = true;
+                break;
+            }
             std::vector<CvDet> raw(n_det);
             if (n_det) HIP_TRY(hipMemcpy(raw.data(), d_det.p, (size_t)n_det * sizeof(CvDet), hipMemcpyDeviceToHost));
             for (const CvDet& d : raw)
@@ -1628,8 +1668,13 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
             set_error("vj_detect_opencv: the detection buffer overflowed twice");
             return VJ_ERR_LIMIT;
         }
-        if (hook && (rc = (*hook)(f0, nf, all.data() + sub_first, all.size() - sub_first))) return rc;
+        if (dev) {
+            if ((rc = dev->finish(f0, nf, all.data() + sub_first, all.size() - sub_first, sub_first))) return rc;
+        } else if (hook && (rc = (*hook)(f0, nf, all.data() + sub_first, all.size() - sub_first))) return rc;
     }
+    // the device grouped every frame (or, where it could not, the host hook did): the regions of all sub-batches ARE the result
+    const bool pre_grouped = dev && dev->grouped;
+    if (pre_grouped) all = *dev->regions;
     if (roc) {   // the key is unique (one report per grid position of a level): levels and weights follow their rectangles
         std::vector<size_t> idx(all.size());
         for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
@@ -1645,7 +1690,7 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
             (*roc->weights)[i] = all_weights[idx[i]];
         }
         all.swap(sorted);
-    } else
+    } else if (!pre_grouped)
     std::sort(all.begin(), all.end(), [](const vj_rect& a, const vj_rect& b) {
         return std::tie(a.frame, a.scale_idx, a.y, a.x) < std::tie(b.frame, b.scale_idx, b.y, b.x);
     });
@@ -1655,7 +1700,7 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         if (!out->rects) return VJ_ERR_NOMEM;
         memcpy(out->rects, all.data(), all.size() * sizeof(vj_rect));
     }
-    if (!roc && p->min_neighbors != 0 && out->count) {   // groupRectangles(rectList, max(minNeighbors, 1), GROUP_EPS)
+    if (!roc && !pre_grouped && p->min_neighbors != 0 && out->count) {   // groupRectangles(rectList, max(minNeighbors, 1), GROUP_EPS)
         rc = vj_group_rectangles(out->rects, &out->count, (int)std::max<uint32_t>(p->min_neighbors, 1u), 0.2);
         if (rc) return rc;
     }
@@ -1737,10 +1782,12 @@ int get_cv_roi_plan(vj_env* e, const vj_cascade* c, int W, const vj_cv_params* p
     const uint32_t stride = (uint32_t)W + 1u;
     std::vector<CvScaleDev> scales((size_t)n_factors);
     std::vector<CvRoiFactor> factors((size_t)n_factors);
+    std::vector<double> factor_values((size_t)n_factors);
     std::vector<CvNodeRec> table((size_t)n_factors * n_nodes);
     double factor = 1;
     int rc = VJ_OK;
     for (int k = 0; k < n_factors && !rc; ++k, factor *= p->scale_factor) {
+        factor_values[(size_t)k] = factor;
         CvScaleDev& sd = scales[(size_t)k];
         memset(&sd, 0, sizeof(sd));
         CvRoiFactor& f = factors[(size_t)k];
@@ -1774,6 +1821,8 @@ int get_cv_roi_plan(vj_env* e, const vj_cascade* c, int W, const vj_cv_params* p
         return rc;
     }
     pl->factors = std::move(factors);
+    pl->factor_values = std::move(factor_values);
+    pl->chain_factors_n = 0;
     pl->last_used = ++e->plan_tick;
     if (fresh) e->cv_roi_plans[key] = std::move(fresh);
     *out = pl;
@@ -1784,7 +1833,7 @@ int get_cv_roi_plan(vj_env* e, const vj_cascade* c, int W, const vj_cv_params* p
 // has tilted nodes) are on the device: one launch of cv_roi_pass for all of them.  Appends the raw candidates (rect.frame = the
 // region's id, x / y relative to the region) to *all, adds counters and times to *out.  *plan_out: the tables used (prog, n_stages).
 int run_cv_roi_pass(vj_env* e, const vj_cascade* c, int W, int H, int nf, const std::vector<CvRoiHost>& regs, const vj_cv_params* p,
-                    std::vector<vj_rect>* all, vj_result* out, CvRoiPlan** plan_out) {
+                    std::vector<vj_rect>* all, vj_result* out, CvRoiPlan** plan_out, uint64_t* units_out = nullptr, uint64_t* windows_out = nullptr) {
     const int cap = (int)((1ull << 26) / std::max<size_t>(c->nodes.size(), 1));   // (what get_cv_roi_plan's tables may hold)
     // the tables are sized once for the frame's own last factor: no region inside it takes more, so a plan grows only when a
     // taller frame of the same width comes, never in the middle of a batch
@@ -1803,6 +1852,8 @@ int run_cv_roi_pass(vj_env* e, const vj_cascade* c, int W, int H, int nf, const 
     if ((rc = cv_roi_build_units(regs, c->win_w, c->win_h, p->scale_factor, pl->factors, stride, frame_elems, p->min_w, p->min_h, &rois, &units,
                                  &windows)))
         return rc;
+    if (units_out) *units_out = units.size();
+    if (windows_out) *windows_out = windows;
     if (units.empty()) return VJ_OK;
     if ((rc = e->d_cv_rois.ensure(rois.size() * sizeof(CvRoiDev)))) return rc;
     if ((rc = e->d_cv_roi_units.ensure(units.size() * sizeof(CvRoiUnit)))) return rc;
@@ -1875,6 +1926,180 @@ int run_cv_roi_pass(vj_env* e, const vj_cascade* c, int W, int H, int nf, const 
         if (n_det) HIP_TRY(hipMemcpy(raw.data(), d_det.p, (size_t)n_det * sizeof(CvDet), hipMemcpyDeviceToHost));
         return cv_roi_rects_of(raw.data(), raw.size(), pl->factors, regs, all);
     }
+}
+
+// ------------------------------------------------------------------------ the chain's device hand-off
+// (what needs no device — the route, the index remap, the info record, the state block's errors — is vj_cv_roi_host.cpp)
+
+// Before the first cascade runs: the second cascade's tables for the frame, and its factor slots as the device's unit builder reads
+// them.  rp stays null when the frame is too small for any scale of the second cascade (the caller takes the host route).
+int CvChainDevice::begin() {
+    const int cap = (int)((1ull << 26) / std::max<size_t>(second->nodes.size(), 1));
+    const int n_factors = cv_count_factors(second->win_w, second->win_h, W, H, p_second->scale_factor, cap);
+    if (n_factors == 0) return VJ_OK;
+    int rc = get_cv_roi_plan(e, second, W, p_second, n_factors, &rp);
+    if (rc) return rc;
+    if (rp->chain_factors_n != (uint32_t)rp->factors.size()) {
+        std::vector<CvChainFactor> t(rp->factors.size());
+        for (size_t k = 0; k < t.size(); ++k)
+            t[k] = CvChainFactor{rp->factor_values[k], rp->factors[k].ystep, rp->factors[k].win_w, rp->factors[k].win_h, rp->factors[k].max_reach};
+        if ((rc = rp->d_chain_factors.ensure(t.size() * sizeof(CvChainFactor)))) return rc;
+        HIP_TRY(hipMemcpy(rp->d_chain_factors.p, t.data(), t.size() * sizeof(CvChainFactor), hipMemcpyHostToDevice));
+        rp->chain_factors_n = (uint32_t)t.size();
+    }
+    unit_cap = (uint32_t)std::min<uint64_t>(4ull * std::max(1u, e->det_cap_init), 0x7fffffffull);
+    det2_cap = std::max(1u, e->det_cap_init);
+    return VJ_OK;
+}
+
+int CvChainDevice::enqueue(int nf, const CvPlan* pl, const CvArgs& a, uint32_t det_cap) {
+    int rc;
+    fallback = false;
+    const size_t counts2_bytes = 2 * VJ_MAX_STAGES * sizeof(uint64_t) + 16;   // stage_entered | visited ... | detection count
+    // frame_count | frame_cursor | grouped_count | frame_first [nf + 1] | the state block (8-byte aligned)
+    const size_t state_at = ((size_t)(4 * nf + 1) * sizeof(uint32_t) + 7u) & ~(size_t)7u;
+    const size_t small_bytes = state_at + sizeof(CvChainState);
+    if ((rc = e->d_cv_chain.ensure(small_bytes))) return rc;
+    if (grouped && (rc = e->d_cv_chain_keys.ensure((size_t)det_cap * sizeof(uint64_t)))) return rc;
+    if (grouped && (rc = e->d_cv_chain_staged.ensure((size_t)det_cap * sizeof(CvRoiDev)))) return rc;
+    if ((rc = e->d_cv_rois.ensure((size_t)det_cap * sizeof(CvRoiDev)))) return rc;
+    if ((rc = e->d_cv_roi_first.ensure((size_t)det_cap * 2u * sizeof(uint32_t)))) return rc;
+    if ((rc = e->d_cv_roi_units.ensure((size_t)unit_cap * sizeof(CvRoiUnit)))) return rc;
+    if ((rc = e->d_cv_det2.ensure((size_t)det2_cap * sizeof(CvDet)))) return rc;
+    if ((rc = e->d_cv_counts2.ensure(counts2_bytes))) return rc;
+    h_counts2.assign((counts2_bytes + 7) / 8, 0ull);
+    const uint32_t stride = (uint32_t)W + 1u;
+    const uint32_t frame_elems = frame_elems_for(W, H);
+    CvChainArgs g;
+    memset(&g, 0, sizeof(g));
+    g.det = a.det;
+    g.det_count = a.det_count;
+    g.det_cap = det_cap;
+    g.scales = (const CvScaleDev*)pl->d_scales.p;
+    g.n_scales = (uint32_t)pl->scales.size();
+    g.n_frames = (uint32_t)nf;
+    g.width = (uint32_t)W;
+    g.height = (uint32_t)H;
+    g.stride = stride;
+    g.frame_elems = frame_elems;
+    g.grouped = grouped ? 1u : 0u;
+    g.threshold = threshold;
+    g.group_max = (uint32_t)std::max(1, e->group_max);
+    g.eps = 0.2;
+    g.frame_count = (uint32_t*)e->d_cv_chain.p;
+    g.frame_cursor = g.frame_count + nf;
+    g.grouped_count = g.frame_cursor + nf;
+    g.frame_first = g.grouped_count + nf;
+    g.keys = (uint64_t*)e->d_cv_chain_keys.p;
+    g.staged = (CvRoiDev*)e->d_cv_chain_staged.p;
+    g.rois = (CvRoiDev*)e->d_cv_rois.p;
+    g.factors = (const CvChainFactor*)rp->d_chain_factors.p;
+    g.n_factors = rp->chain_factors_n;
+    g.scale_factor = p_second->scale_factor;
+    g.win_w = second->win_w;
+    g.win_h = second->win_h;
+    g.min_w = p_second->min_w;
+    g.min_h = p_second->min_h;
+    g.roi_units = (uint32_t*)e->d_cv_roi_first.p;
+    g.roi_first = g.roi_units + det_cap;
+    g.units = (CvRoiUnit*)e->d_cv_roi_units.p;
+    g.unit_cap = unit_cap;
+    g.state = (CvChainState*)((char*)e->d_cv_chain.p + state_at);
+    HIP_TRY(hipEventRecord(e->cv_chain_ev[0], e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_cv_chain.p, 0, small_bytes, e->stream));
+    int hrc = launch_cv_chain_handoff(g, e->n_cu, e->stream);
+    if (hrc) {
+        set_error("hand-off launch failed: %s", hipGetErrorString((hipError_t)hrc));
+        return VJ_ERR_HIP;
+    }
+    HIP_TRY(hipEventRecord(e->cv_chain_ev[1], e->stream));
+    // the region pass as run_cv_roi_pass launches it, on the units the kernels above left: their count comes from the state block
+    HIP_TRY(hipMemsetAsync(e->d_cv_counts2.p, 0, counts2_bytes, e->stream));
+    CvRoiArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    CvArgs& b = ra.cv;
+    b.sum = (const uint32_t*)e->d_sum.p;
+    b.sqsum = (const uint64_t*)e->d_sqsum.p;
+    b.tilted = rp->has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
+    b.n_order = rp->n_order;
+    b.table = (const uint32_t*)rp->d_table.p;
+    b.scales = (const CvScaleDev*)rp->d_scales.p;
+    b.stages = (const StageDev*)rp->d_stages.p;
+    b.n_frames = (uint32_t)nf;
+    b.n_stages = rp->n_stages;
+    b.frame_elems = frame_elems;
+    b.stride = stride;
+    b.sum_h = (uint32_t)H + 1u;
+    b.det = (CvDet*)e->d_cv_det2.p;
+    b.det_count = (uint32_t*)((unsigned long long*)e->d_cv_counts2.p + 2 * VJ_MAX_STAGES);
+    b.det_cap = det2_cap;
+    b.stage_entered = (unsigned long long*)e->d_cv_counts2.p;
+    b.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
+    b.tree2 = rp->tree2 && !rp->is_tree && !rp->has_tilted && e->cv_tree2 ? 1u : 0u;
+    ra.rois = (const CvRoiDev*)e->d_cv_rois.p;
+    ra.units = (const CvRoiUnit*)e->d_cv_roi_units.p;
+    ra.n_units_dev = &g.state->n_units_run;
+    // (the host does not know the unit count: the full four workgroups per CU; the units go round by stride)
+    const int n_blocks = std::max(1, e->n_cu * 4);
+    b.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
+    hrc = launch_cv_roi_pass(ra, rp->trees, (p_second->flags & VJ_FLAG_COUNTERS) != 0, rp->is_tree, n_blocks, e->stream);
+    if (hrc) {
+        set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
+        return VJ_ERR_HIP;
+    }
+    HIP_TRY(hipEventRecord(e->cv_chain_ev[2], e->stream));
+    HIP_TRY(hipMemcpyAsync(&h_state, g.state, sizeof(CvChainState), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(h_counts2.data(), e->d_cv_counts2.p, counts2_bytes, hipMemcpyDeviceToHost, e->stream));
+    return VJ_OK;
+}
+
+// After the synchronisation, when the first cascade's detections fitted
+int CvChainDevice::check(bool* again) {
+    *again = false;
+    if (h_state.overflow != 0u) {   // a frame with more candidates than the device groups: this sub-batch through the host
+        fallback = true;
+        return VJ_OK;
+    }
+    const int rc = cv_chain_state_error(h_state);
+    if (rc) return rc;
+    const uint32_t n_det2 = (uint32_t)(h_counts2[2 * VJ_MAX_STAGES] & 0xffffffffull);
+    if (h_state.n_units > (uint64_t)unit_cap) unit_cap = grown_cap(unit_cap, h_state.n_units);   // (the count pass's total is exact)
+    else if (n_det2 > det2_cap) det2_cap = grown_cap(det2_cap, n_det2);
+    else return VJ_OK;
+    e->cv_chain_info.reruns += 1;
+    *again = true;
+    return VJ_OK;
+}
+
+// The sub-batch stands.  raw: the first cascade's candidates of the sub-batch as the loop appended them (not there when the device
+// grouped them); base: their place in the call's list.
+int CvChainDevice::finish(int f0, int nf, const vj_rect* raw, size_t n_raw, size_t base) {
+    if (fallback) return (*host_hook)(f0, nf, raw, n_raw);
+    float ms_h = 0, ms_c = 0;
+    HIP_TRY(hipEventElapsedTime(&ms_h, e->cv_chain_ev[0], e->cv_chain_ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms_c, e->cv_chain_ev[1], e->cv_chain_ev[2]));
+    e->cv_chain_info.handoff_ms += ms_h;
+    if (h_state.n_units_run != 0u) {
+        out_second->timing.cascade_ms += ms_c;
+        out_second->timing.total_ms += ms_c;
+        out_second->timing.n_cascade_launches += 1;
+    }
+    if ((p_second->flags & VJ_FLAG_COUNTERS) != 0) {
+        for (size_t s = 0; s < rp->n_stages; ++s) out_second->counters.stage_entered[s] += h_counts2[s];
+        out_second->counters.windows += h_counts2[VJ_MAX_STAGES];
+    }
+    const uint32_t n_regions = h_state.n_regions, n_det2 = (uint32_t)(h_counts2[2 * VJ_MAX_STAGES] & 0xffffffffull);
+    std::vector<CvRoiDev> rois(n_regions);
+    if (n_regions) HIP_TRY(hipMemcpy(rois.data(), e->d_cv_rois.p, (size_t)n_regions * sizeof(CvRoiDev), hipMemcpyDeviceToHost));
+    std::vector<CvDet> det2(n_det2);
+    if (n_det2) HIP_TRY(hipMemcpy(det2.data(), e->d_cv_det2.p, (size_t)n_det2 * sizeof(CvDet), hipMemcpyDeviceToHost));
+    std::vector<int> ids;
+    int rc = grouped ? cv_chain_grouped_regions(rois.data(), rois.size(), f0, nf, regions, &ids)
+                     : cv_chain_region_ids(rois.data(), rois.size(), raw, n_raw, f0, base, &ids);
+    if (rc) return rc;
+    if ((rc = cv_chain_rects_of(det2.data(), det2.size(), rp->factors, ids, all2))) return rc;
+    cv_chain_info_add(&e->cv_chain_info, true, n_regions, h_state.n_units, h_state.windows);
+    return VJ_OK;
 }
 
 // ------------------------------------------------------------------------ a cascade on a caller's windows
@@ -2046,7 +2271,8 @@ int vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames
         }
     if (n_rois == 0) return VJ_OK;
     int W, H, CH;
-    if ((p->flags & ~CV_ROI_FAST_FLAGS) == 0u && cv_frames_uniform(frames, n_frames, &W, &H, &CH)) {
+    // (VJ_FLAG_CV_CHAIN_DEVICE belongs to vj_detect_opencv_chain: ignored here)
+    if ((p->flags & ~(CV_ROI_FAST_FLAGS | (uint32_t)VJ_FLAG_CV_CHAIN_DEVICE)) == 0u && cv_frames_uniform(frames, n_frames, &W, &H, &CH)) {
         // ---- every region in one pass per sub-batch, on the frames' own integral images
         HIP_TRY(hipSetDevice(e->device));
         const std::vector<int> by_frame = cv_rois_by_frame(rois, n_rois);
@@ -2106,6 +2332,15 @@ int vj_detect_opencv_chain(vj_env* e, const vj_cascade* first, const vj_cascade*
         set_error("scale_factor must be > 1");
         return VJ_ERR_ARG;
     }
+    // VJ_FLAG_CV_CHAIN_DEVICE is read here and nowhere else: from now on both parameter blocks are without it
+    const CvChainRoute route = cv_chain_route(p_first->flags, p_second->flags);
+    vj_cv_params q_first = *p_first, q_second = *p_second;
+    q_first.flags = route.flags_first;
+    q_second.flags = route.flags_second;
+    p_first = &q_first;
+    p_second = &q_second;
+    e->cv_chain_info = vj_cv_chain_info{};
+    e->cv_chain_info.handoff = route.handoff;
     if (((p_first->flags | p_second->flags) & ~CV_ROI_FAST_FLAGS) != 0u) {
         // the two public calls back to back: what `first` finds are the regions
         int rc = vj_detect_opencv(e, first, frames, n_frames, p_first, out_first);
@@ -2115,6 +2350,7 @@ int vj_detect_opencv_chain(vj_env* e, const vj_cascade* first, const vj_cascade*
             const vj_rect& r = out_first->rects[i];
             rois[i] = vj_roi{r.frame, r.x, r.y, r.w, r.h};
         }
+        e->cv_chain_info.regions = out_first->count;
         return vj_detect_opencv_rois(e, second, frames, n_frames, rois.data(), (int)rois.size(), p_second, out_second);
     }
     // ---- per sub-batch: the frames' integral images once (with the tilted integral when either cascade reads it), `first` on the
@@ -2126,11 +2362,39 @@ int vj_detect_opencv_chain(vj_env* e, const vj_cascade* first, const vj_cascade*
     std::vector<CvRoiHost> regs;
     CvRoiPlan* pl = nullptr;
     const CvSubBatchHook hook = [&](int f0, int nf, const vj_rect* raw, size_t n_raw) -> int {
-        const int hrc = cv_chain_regions(raw, n_raw, p_first->min_neighbors, W, H, f0, nf, &regs, &regions);
+        int hrc = cv_chain_regions(raw, n_raw, p_first->min_neighbors, W, H, f0, nf, &regs, &regions);
         if (hrc) return hrc;
-        if (regs.empty()) return VJ_OK;
-        return run_cv_roi_pass(e, second, W, H, nf, regs, p_second, &all, out_second, &pl);
+        uint64_t n_units = 0, n_windows = 0;
+        if (!regs.empty() && (hrc = run_cv_roi_pass(e, second, W, H, nf, regs, p_second, &all, out_second, &pl, &n_units, &n_windows))) return hrc;
+        cv_chain_info_add(&e->cv_chain_info, false, regs.size(), n_units, n_windows);
+        return VJ_OK;
     };
+    int uW, uH, uCH;   // (frames the profile does not take as a batch: the host route reports them as it always did)
+    if (route.handoff == 1 && cv_frames_uniform(frames, n_frames, &uW, &uH, &uCH)) {
+        // ---- the hand-off on the device: both cascades are enqueued before the host waits, once per sub-batch
+        HIP_TRY(hipSetDevice(e->device));
+        CvChainDevice dev;
+        dev.e = e;
+        dev.second = second;
+        dev.p_second = p_second;
+        dev.grouped = p_first->min_neighbors != 0;
+        dev.threshold = (int32_t)std::min<uint32_t>(std::max<uint32_t>(p_first->min_neighbors, 1u), 0x7fffffffu);
+        dev.W = W;
+        dev.H = H;
+        dev.host_hook = &hook;
+        dev.out_second = out_second;
+        dev.all2 = &all;
+        dev.regions = &regions;
+        int rc = dev.begin();
+        if (rc) return rc;
+        if (dev.rp) {
+            pl = dev.rp;
+            if ((rc = detect_opencv_impl(e, first, frames, n_frames, p_first, out_first, second_tilted, &hook, nullptr, &dev))) return rc;
+            return finish_cv_roi_result(all, &pl->prog, p_second, out_second);
+        }
+        // (a frame too small for any scale of the second cascade: nothing to hand off)
+    }
+    if (route.handoff == 1) e->cv_chain_info.handoff = 2;
     int rc = detect_opencv_impl(e, first, frames, n_frames, p_first, out_first, second_tilted, &hook);
     if (rc) return rc;
     // (grouping is per frame and the sub-batches are runs of frames: the regions are out_first's rectangles, in order)
@@ -2145,6 +2409,12 @@ int vj_detect_opencv_chain(vj_env* e, const vj_cascade* first, const vj_cascade*
 int vj_run_windows_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const double* scales, int n_scales,
                           const vj_window* windows, uint32_t n_windows, int start_stage, vj_window_result* out) {
     return run_points<CvPoints>(e, c, frames, n_frames, scales, n_scales, windows, n_windows, start_stage, 0u, out);
+}
+
+int vj_cv_chain_info_get(const vj_env* e, vj_cv_chain_info* out) {
+    if (!e || !out) return VJ_ERR_ARG;
+    *out = e->cv_chain_info;
+    return VJ_OK;
 }
 
 int vj_run_windows_timing(const vj_env* e, float* integral_ms, float* pass_ms) {

@@ -37,14 +37,16 @@ __global__ __launch_bounds__(CV_WAVES_PER_BLOCK * 64) void cv_roi_pass(CvRoiArgs
     const rsrc_t img = make_rsrc(a.sum, a.n_frames * frame_bytes4);
     const rsrc_t timg = make_rsrc(a.tilted != nullptr ? a.tilted : a.sum, a.n_frames * frame_bytes4);
     const double thr0 = (double)stages[0].threshold;
+    // (a unit list built on the device, vj_cv_chain.hip, brings its count with it: one scalar load, uniform for the launch)
+    const uint32_t n_units = r.n_units_dev != nullptr ? *r.n_units_dev : r.n_units;
 
     // the waves of an XCD walk one contiguous eighth of the unit list (units are ordered by frame, region, factor, row): what they
     // gather from at one time is one neighbourhood of one frame's images (as cv_profile_pass deals its rows)
-    uint32_t u_first = rank, u_end = r.n_units, u_step = a.total_waves;
+    uint32_t u_first = rank, u_end = n_units, u_step = a.total_waves;
     if (gridDim.x >= 8u) {
         const uint32_t xcd = blockIdx.x & 7u;
-        const uint32_t u_begin = (uint32_t)((unsigned long long)r.n_units * xcd / 8u);
-        u_end = (uint32_t)((unsigned long long)r.n_units * (xcd + 1u) / 8u);
+        const uint32_t u_begin = (uint32_t)((unsigned long long)n_units * xcd / 8u);
+        u_end = (uint32_t)((unsigned long long)n_units * (xcd + 1u) / 8u);
         u_step = ((gridDim.x - xcd + 7u) >> 3) * CV_WAVES_PER_BLOCK;
         u_first = u_begin + (blockIdx.x >> 3) * CV_WAVES_PER_BLOCK + wib;
     }

@@ -222,4 +222,107 @@ bool cv_chain_regions_match(const std::vector<vj_rect>& regions, const vj_result
     return true;
 }
 
+CvChainRoute cv_chain_route(uint32_t flags_first, uint32_t flags_second) {
+    const bool asked = (flags_first & VJ_FLAG_CV_CHAIN_DEVICE) != 0u;
+    CvChainRoute r{flags_first & ~(uint32_t)VJ_FLAG_CV_CHAIN_DEVICE, flags_second & ~(uint32_t)VJ_FLAG_CV_CHAIN_DEVICE, 0};
+    const bool fast = ((r.flags_first | r.flags_second) & ~(uint32_t)VJ_FLAG_COUNTERS) == 0u;
+    r.handoff = !fast ? 3 : asked ? 1 : 2;
+    return r;
+}
+
+std::vector<uint32_t> cv_chain_rank(const vj_rect* raw, size_t n) {
+    std::vector<uint32_t> idx(n), rank(n);
+    for (size_t i = 0; i < n; ++i) idx[i] = (uint32_t)i;
+    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t i, uint32_t j) {
+        return std::tie(raw[i].frame, raw[i].scale_idx, raw[i].y, raw[i].x) < std::tie(raw[j].frame, raw[j].scale_idx, raw[j].y, raw[j].x);
+    });
+    for (size_t k = 0; k < n; ++k) rank[idx[k]] = (uint32_t)k;
+    return rank;
+}
+
+int cv_chain_region_ids(const CvRoiDev* rois, size_t n_regions, const vj_rect* raw, size_t n_raw, int f0, size_t base, std::vector<int>* ids) {
+    ids->clear();
+    if (n_regions != n_raw) {
+        set_error("the device made %zu regions of %zu candidates", n_regions, n_raw);
+        return VJ_ERR_HIP;
+    }
+    const std::vector<uint32_t> rank = cv_chain_rank(raw, n_raw);
+    std::vector<bool> seen(n_raw, false);
+    ids->reserve(n_regions);
+    for (size_t r = 0; r < n_regions; ++r) {
+        const CvRoiDev& d = rois[r];
+        const size_t src = d.pad[0];
+        if (src >= n_raw || seen[src]) {
+            set_error("region %zu names candidate %zu of %zu%s", r, src, n_raw, src < n_raw ? " a second time" : "");
+            return VJ_ERR_HIP;
+        }
+        seen[src] = true;
+        const vj_rect& q = raw[src];
+        if ((int64_t)d.frame + f0 != q.frame || (int64_t)d.x != q.x || (int64_t)d.y != q.y || (int64_t)d.w != q.w || (int64_t)d.h != q.h) {
+            set_error("region %zu is not candidate %zu's rectangle", r, src);
+            return VJ_ERR_HIP;
+        }
+        ids->push_back((int)(base + rank[src]));
+    }
+    return VJ_OK;
+}
+
+int cv_chain_grouped_regions(const CvRoiDev* rois, size_t n_regions, int f0, int nf, std::vector<vj_rect>* regions, std::vector<int>* ids) {
+    ids->clear();
+    ids->reserve(n_regions);
+    uint32_t last = 0;
+    for (size_t r = 0; r < n_regions; ++r) {
+        const CvRoiDev& d = rois[r];
+        if (d.frame >= (uint32_t)std::max(nf, 0) || d.frame < last) {
+            set_error("grouped region %zu names frame %u of %d out of order", r, d.frame, nf);
+            return VJ_ERR_HIP;
+        }
+        last = d.frame;
+        ids->push_back((int)regions->size());
+        regions->push_back(vj_rect{(int32_t)d.x, (int32_t)d.y, (int32_t)d.w, (int32_t)d.h, (float)(int)d.pad[0], f0 + (int32_t)d.frame, -1});
+    }
+    return VJ_OK;
+}
+
+int cv_chain_rects_of(const CvDet* raw, size_t n_raw, const std::vector<CvRoiFactor>& factors, const std::vector<int>& ids, std::vector<vj_rect>* all) {
+    for (size_t i = 0; i < n_raw; ++i) {
+        const CvDet& d = raw[i];
+        if (d.slot >= factors.size() || d.frame >= ids.size()) {
+            set_error("the region pass returned a detection outside its regions");
+            return VJ_ERR_HIP;
+        }
+        const CvRoiFactor& f = factors[d.slot];
+        all->push_back(vj_rect{(int32_t)d.x, (int32_t)d.y, f.win_w, f.win_h, 0.0f, ids[d.frame], (int32_t)d.slot});
+    }
+    return VJ_OK;
+}
+
+void cv_chain_info_add(vj_cv_chain_info* info, bool on_device, uint64_t regions, uint64_t units, uint64_t windows) {
+    info->sub_batches += 1;
+    if (on_device) info->sub_batches_device += 1;
+    info->regions += regions;
+    info->units += units;
+    info->windows += windows;
+}
+
+int cv_chain_state_error(const CvChainState& s) {
+    if (s.err_outside != 0u) {
+        set_error("%u regions lie outside their frames", s.err_outside);
+        return VJ_ERR_ARG;
+    }
+    if (s.err_factors != 0u) {
+        set_error("%u regions take more factors than the tables hold", s.err_factors);
+        return VJ_ERR_LIMIT;
+    }
+    if (s.err_reach != 0u) {
+        set_error("feature reach exceeds the frame allocation");
+        return VJ_ERR_LIMIT;
+    }
+    if (s.windows > 0xffffffffull || s.n_units > 0x7fffffffull) {
+        set_error("the regions hold more windows than a 32-bit detection count holds");
+        return VJ_ERR_LIMIT;
+    }
+    return VJ_OK;
+}
+
 }  // namespace vj

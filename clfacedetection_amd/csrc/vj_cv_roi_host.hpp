@@ -64,4 +64,29 @@ int cv_chain_regions(const vj_rect* raw, size_t n_raw, uint32_t min_neighbors, i
                      std::vector<CvRoiHost>* regs, std::vector<vj_rect>* regions);
 bool cv_chain_regions_match(const std::vector<vj_rect>& regions, const vj_result& first);
 
+// ---- the chain's device hand-off (VJ_FLAG_CV_CHAIN_DEVICE; vj_cv_chain.hip): what the host does around it
+// Which way a vj_detect_opencv_chain call goes (vj_cv_chain_info::handoff: 1 device, 2 host, 3 the two public calls), and the two
+// flag words with VJ_FLAG_CV_CHAIN_DEVICE taken out: nothing keyed on flags ever sees the bit.  Only flags_first is read for it.
+struct CvChainRoute { uint32_t flags_first, flags_second; int handoff; };
+CvChainRoute cv_chain_route(uint32_t flags_first, uint32_t flags_second);
+
+// rank[i]: the place of raw[i] among raw[0..n) in the order of the result, (frame, scale_idx, y, x); equal keys keep their order
+std::vector<uint32_t> cv_chain_rank(const vj_rect* raw, size_t n);
+
+// Raw candidates as regions: device region r comes from record rois[r].pad[0] of the sub-batch's `raw` (rect.frame counts from the
+// call's first frame, the sub-batch's from f0) and is out_first's rectangle base + rank of that record.  Refused (VJ_ERR_HIP): a
+// source index out of range or used twice, a count that is not the records', a region that is not its record's rectangle.
+int cv_chain_region_ids(const CvRoiDev* rois, size_t n_regions, const vj_rect* raw, size_t n_raw, int f0, size_t base, std::vector<int>* ids);
+
+// Grouped regions, as read back: appended to *regions as vj_group_rectangles writes them (weight = members, scale_idx -1, frames
+// counted from the call's first), ids continuing.  Refused (VJ_ERR_HIP): frames out of [0, nf) or not in order.
+int cv_chain_grouped_regions(const CvRoiDev* rois, size_t n_regions, int f0, int nf, std::vector<vj_rect>* regions, std::vector<int>* ids);
+
+// The second cascade's detections as rectangles: rect.frame = ids[the device's region index]
+int cv_chain_rects_of(const CvDet* raw, size_t n_raw, const std::vector<CvRoiFactor>& factors, const std::vector<int>& ids, std::vector<vj_rect>* all);
+
+// One sub-batch into the call's record; what the device's state block makes the call return (VJ_OK: nothing refused)
+void cv_chain_info_add(vj_cv_chain_info* info, bool on_device, uint64_t regions, uint64_t units, uint64_t windows);
+int cv_chain_state_error(const CvChainState& s);
+
 }  // namespace vj

@@ -501,8 +501,46 @@ struct CvRoiArgs {
     const CvRoiDev* rois;
     const CvRoiUnit* units;  // ordered by (frame, region, factor, row)
     uint32_t n_units;
+    const uint32_t* n_units_dev;   // not null: the unit count is read from here (the list was built on the device: vj_cv_chain.hip)
 };
 int launch_cv_roi_pass(const CvRoiArgs& a, bool trees, bool count, bool stage_tree, int n_blocks, void* stream);
+
+// vj_detect_opencv_chain's device hand-off (VJ_FLAG_CV_CHAIN_DEVICE; vj_cv_chain.hip): the first cascade's CvDet
+// records become the regions (CvRoiDev) and units (CvRoiUnit) of the region pass without leaving the device.
+struct CvChainArgs {
+    const CvDet* det;            // the first cascade's detections: {x, y, scale slot, frame of the sub-batch}
+    const uint32_t* det_count;   // ... their count (may exceed det_cap: the sub-batch is enqueued again with more room)
+    uint32_t det_cap;
+    const CvScaleDev* scales;    // the FIRST plan's scale records (win_w / win_h of a slot)
+    uint32_t n_scales;
+    uint32_t n_frames, width, height;
+    uint32_t stride;             // W + 1
+    uint32_t frame_elems;
+    uint32_t grouped;            // 0: every record is a region; 1: grouped per frame (groupRectangles)
+    int32_t  threshold;          // max(min_neighbors, 1)
+    uint32_t group_max;          // a frame with more candidates raises CvChainState::overflow
+    double   eps;                // GROUP_EPS = 0.2
+    uint32_t* frame_count;       // [n_frames] } one zeroed block: frame_count | frame_cursor | grouped_count
+    uint32_t* frame_cursor;      // [n_frames] }
+    uint32_t* grouped_count;     // [n_frames] }
+    uint32_t* frame_first;       // [n_frames + 1]
+    uint64_t* keys;              // [det_cap] grouped: slot << 32 | y * stride + x, a frame's together
+    CvRoiDev* staged;            // [det_cap] grouped: a frame's rectangles at frame_first[frame]
+    CvRoiDev* rois;              // [det_cap] the regions, a frame's together, frames in order
+    const CvChainFactor* factors;   // the SECOND cascade's factor slots (the region plan's)
+    uint32_t n_factors;          // >= 1
+    double   scale_factor;       // the second call's (the factor after the table's last: refused, as on the host)
+    int32_t  win_w, win_h;       // the second cascade's window
+    int32_t  min_w, min_h;       // its minimum object size
+    uint32_t* roi_units;         // [det_cap] units of each region
+    uint32_t* roi_first;         // [det_cap] where a region's units start
+    CvRoiUnit* units;            // [unit_cap] ordered by (region, factor, row)
+    uint32_t unit_cap;
+    CvChainState* state;         // zeroed before the launches
+};
+// regions (count / offsets / scatter, or scatter / group / collect), then units (count / offsets / fill); all on `stream`, in order
+int launch_cv_chain_handoff(const CvChainArgs& a, int n_cu, void* stream);
+int prepare_cv_chain_kernels();   // per device: the dynamic-LDS cap of the grouping kernel
 
 // The profile's LDS-tile kernel (vj_cv_tile.hip): small scales of stump cascades with linear stages and upright features.
 constexpr int CVT_WAVES = 8;            // waves per workgroup

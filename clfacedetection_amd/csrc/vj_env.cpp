@@ -2041,6 +2041,10 @@ int vj_env_create(int device_index, vj_env** out) {
         set_error("raising the dynamic LDS limit on device %d failed: %s", device_index, hipGetErrorString((hipError_t)hrc));
         return VJ_ERR_HIP;
     }
+    if (const int hrc = prepare_cv_chain_kernels()) {
+        set_error("raising the dynamic LDS limit on device %d failed: %s", device_index, hipGetErrorString((hipError_t)hrc));
+        return VJ_ERR_HIP;
+    }
     if (const int hrc = prepare_cv_biggest_kernels()) {
         set_error("raising the dynamic LDS limit on device %d failed: %s", device_index, hipGetErrorString((hipError_t)hrc));
         return VJ_ERR_HIP;
@@ -2049,6 +2053,7 @@ int vj_env_create(int device_index, vj_env** out) {
     { const int lrc = e->lane0.create(); if (lrc) return lrc; }
     HIP_TRY(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&e->join_ev, hipEventDisableTiming));
+    for (hipEvent_t& ev : e->cv_chain_ev) HIP_TRY(hipEventCreate(&ev));
     HIP_TRY(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
     *out = e.release();
     return VJ_OK;
@@ -2064,11 +2069,14 @@ void vj_env_destroy(vj_env* e) {
                       &e->d_cv_accept, &e->d_cv_tq, &e->d_cv_fail_rows, &e->d_cv_fail_walk, &e->d_run_table,
                       &e->d_canny_cls, &e->d_canny_label, &e->d_canny_flag, &e->d_edges, &e->d_edge_sum,
                       &e->d_cv_prune_bits, &e->d_pyr, &e->d_pyr_tab, &e->d_cv_big, &e->d_cv_rois, &e->d_cv_roi_units,
+                      &e->d_cv_chain, &e->d_cv_chain_keys, &e->d_cv_chain_staged, &e->d_cv_roi_first, &e->d_cv_det2, &e->d_cv_counts2,
                       &e->d_points, &e->d_point_units, &e->d_point_scales, &e->d_point_out})
         b->release();
     e->lane0.destroy();
     for (DevBuf& b : e->d_q) b.release();
     for (DevBuf& b : e->d_q2) b.release();
+    for (hipEvent_t& ev : e->cv_chain_ev)
+        if (ev) (void)hipEventDestroy(ev);
     if (e->fork_ev) (void)hipEventDestroy(e->fork_ev);
     if (e->join_ev) (void)hipEventDestroy(e->join_ev);
     if (e->stream2) (void)hipStreamDestroy(e->stream2);

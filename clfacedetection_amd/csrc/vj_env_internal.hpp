@@ -157,9 +157,15 @@ struct CvRoiPlan {
     uint32_t n_stages = 0, n_order = 0;
     bool trees = false, is_tree = false, has_tilted = false, tree2 = false;
     DevBuf d_table, d_scales, d_stages;
+    // the chain's device hand-off (vj_cv_chain.hip): the enumeration's own factor of every slot, and the table the device's unit
+    // builder reads (uploaded when a flagged call first needs it: chain_factors_n slots, 0 after the plan grew)
+    std::vector<double> factor_values;
+    DevBuf d_chain_factors;
+    uint32_t chain_factors_n = 0;
     uint64_t last_used = 0;
     void release_device() {
-        for (DevBuf* b : {&d_table, &d_scales, &d_stages}) b->release();
+        for (DevBuf* b : {&d_table, &d_scales, &d_stages, &d_chain_factors}) b->release();
+        chain_factors_n = 0;
     }
 };
 
@@ -382,6 +388,12 @@ struct vj_env : vj::Tunables {
     typedef std::tuple<uint64_t, int, uint64_t> CvRoiPlanKey;   // cascade uid, frame width (the tables' stride), bits of the scale factor
     std::map<CvRoiPlanKey, std::unique_ptr<vj::CvRoiPlan>> cv_roi_plans;
     vj::DevBuf d_cv_rois, d_cv_roi_units;   // region pass of the OpenCV profile: a sub-batch's regions and work units
+    // vj_detect_opencv_chain's device hand-off (VJ_FLAG_CV_CHAIN_DEVICE; vj_cv_chain.hip): per-frame counts, offsets and the state block;
+    // the grouping's keys and per-frame rectangles; units per region and their offsets; the SECOND cascade's detections and counters
+    // (the first one's stay in d_cv_det / d_cv_counts until the sub-batch's one synchronisation); events around the hand-off and the pass
+    vj::DevBuf d_cv_chain, d_cv_chain_keys, d_cv_chain_staged, d_cv_roi_first, d_cv_det2, d_cv_counts2;
+    hipEvent_t cv_chain_ev[3] = {};
+    vj_cv_chain_info cv_chain_info = {};    // the last vj_detect_opencv_chain call (vj_cv_chain_info_get)
     // The window-list calls (vj_points_driver.hpp), per profile: stage records per cascade uid; plans per (cascade uid, frame width, bits of
     // the scale[, tilted-as-upright]).  Under plan_cache_max, least recently used first — except the plans of the call in progress
     typedef std::map<uint64_t, std::unique_ptr<vj::PointCascade>> PointCascades;

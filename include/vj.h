@@ -175,6 +175,13 @@ enum {
                                        (tempcv.hpp:130), read only by the find-biggest search (:1450): minSize after the first
                                        grouped object is cvRound(0.6 w), cvRound(0.6 h) instead of 0.4.  Without
                                        VJ_FLAG_CV_FIND_BIGGEST it changes nothing.  The clod-profile entry points ignore it.    */
+    VJ_FLAG_CV_CHAIN_DEVICE = 1u << 10, /* vj_detect_opencv_chain only, and only in p_first->flags: the first cascade's rectangles
+                                       become the second one's regions and work units ON THE DEVICE, and the host
+                                       waits once per sub-batch, after both cascades.  Taken when both flag words are otherwise
+                                       within VJ_FLAG_COUNTERS; next to a flag that sends the chain through the two public calls
+                                       it is ignored.  The results — rectangles, order, counters — are those of the call without
+                                       it.  Not the default yet: what it gains is measured and recorded in DESIGN.md 4.10.
+                                       Every other entry point ignores the bit; no plan is keyed on it.                         */
 };
 
 typedef struct vj_params {
@@ -603,9 +610,30 @@ int  vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frame
  * vj_detect_opencv_rois(second, those regions, p_second) returns, rect.frame indexing out_first->rects.  Both flag words within
  * VJ_FLAG_COUNTERS: the frames are uploaded and integrated once for both cascades (per sub-batch when the batch is split; with the
  * tilted integral when either cascade has tilted nodes), and `second` runs in the region pass before the sub-batch's images are
- * replaced; the rectangle list travels through the host in between.  Any other flag: the two public calls back to back.          */
+ * replaced; the rectangle list travels through the host in between.  Any other flag: the two public calls back to back.
+ * With VJ_FLAG_CV_CHAIN_DEVICE in p_first->flags (and both words otherwise within VJ_FLAG_COUNTERS) the list stays on the device:
+ * kernels turn the first cascade's records into regions — bucketed by frame, or grouped per frame by the device's groupRectangles
+ * when p_first->min_neighbors != 0 — and into the region pass's units, the region pass runs behind them, and the host waits once
+ * per sub-batch.  The buffers of that route start at the configured "det_cap" (first-cascade detections and so regions,
+ * second-cascade detections, 4 x det_cap units) and grow to what the device counted, the sub-batch being enqueued again; a frame
+ * with more candidates to group than "group_max" sends its sub-batch through the host as above.  Same results either way.        */
 int  vj_detect_opencv_chain(vj_env* e, const vj_cascade* first, const vj_cascade* second, const vj_image* frames, int n_frames,
                             const vj_cv_params* p_first, const vj_cv_params* p_second, vj_result* out_first, vj_result* out_second);
+/* What the environment's last vj_detect_opencv_chain call did, whichever route it took (zeroed when a call begins). */
+typedef struct vj_cv_chain_info {
+    int32_t  handoff;             /* 0 no call yet; 1 on the device (VJ_FLAG_CV_CHAIN_DEVICE); 2 through the host; 3 the two
+                                     public calls back to back (units / windows stay 0: they run no common region pass)          */
+    int32_t  sub_batches;         /* sub-batches of the call ...                                                                  */
+    int32_t  sub_batches_device;  /* ... and how many of them handed off on the device (the others: more candidates in a frame
+                                     than "group_max", redone through the host)                                                   */
+    int32_t  reruns;              /* times a sub-batch's chain was enqueued again because a buffer was short                      */
+    uint64_t regions;             /* regions handed to the second cascade                                                         */
+    uint64_t units;               /* window rows of the region pass: one per (region, factor, row)                                */
+    uint64_t windows;             /* grid positions of those rows                                                                 */
+    float    handoff_ms;          /* device time of the hand-off kernels (events), summed over sub-batches; 0 on the host routes  */
+    int32_t  reserved;
+} vj_cv_chain_info;
+int  vj_cv_chain_info_get(const vj_env* e, vj_cv_chain_info* out);   /* a null argument: VJ_ERR_ARG */
 
 /* ------------------------------------------------------------ frame streams */
 /* Video-style use (the demo's per-frame loop, main.cpp:104-125): batches of host frames are uploaded into
