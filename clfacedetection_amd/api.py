@@ -131,6 +131,15 @@ class CvChainInfo(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class CvRoisInfo(C.Structure):
+    """vj_cv_rois_info: what the environment's last detect_opencv_rois call did.  route: 0 no call yet, 1 one pass on the frames'
+    integral images, 2 one pass on level canvases (VJ_FLAG_CV_SCALE_IMAGE), 3 one detect_opencv call per region size, 4 route 2 with
+    some regions sent through route 3."""
+    _fields_ = [("route", C.c_int32), ("canvases", C.c_int32), ("canvas_w", C.c_uint32), ("canvas_h", C.c_uint32),
+                ("regions", C.c_uint64), ("level_images", C.c_uint64), ("windows", C.c_uint64), ("pyramid_ms", C.c_float),
+                ("reserved", C.c_int32)]
+
+
 class _Counters(C.Structure):
     _fields_ = [("windows", C.c_uint64), ("stump_evals", C.c_uint64), ("gather_bytes", C.c_uint64),
                 ("stage_entered", C.c_uint64 * VJ_MAX_STAGES)]
@@ -248,6 +257,7 @@ _SIGNATURES = {
                                  C.c_int, C.c_uint32, C.c_void_p]),
     "vj_run_windows_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vj_cv_chain_info_get": (C.c_int, [C.c_void_p, C.POINTER(CvChainInfo)]),
+    "vj_cv_rois_info_get": (C.c_int, [C.c_void_p, C.POINTER(CvRoisInfo)]),
     "vj_cv_plan_info_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CvParams), C.POINTER(CvPlanInfo)]),
     "vj_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params),
                             C.POINTER(_Result)]),
@@ -642,8 +652,10 @@ class Environment:
         """vj_detect_opencv_rois: `cascade` in the OpenCV profile inside `rois` = rows of (frame, x, y, w, h); the result equals
         detect_opencv on every region as a sub-image (what cvSetImageROI gives an OpenCV caller): rects['frame'] is the region's
         row, x / y are relative to its origin, regions are grouped one by one.  flags 0 / VJ_FLAG_COUNTERS and frames of one size:
-        the frames are integrated once and all regions run in one pass on those integral images; other flags or mixed frame
-        sizes: one detect_opencv call per region size.  Same result either way."""
+        the frames are integrated once and all regions run in one pass on those integral images; VJ_FLAG_CV_SCALE_IMAGE (with
+        VJ_FLAG_COUNTERS, canny pruning or rough search at most) and frames of one size: every region's level images are resized
+        into one canvas by one launch and walked by one pass per canvas (unless the call has more than 32 regions per distinct
+        region size, which the next route runs faster); other flags or mixed frame sizes: one detect_opencv call per region size.  Same result either way; cv_rois_info() tells which way the last call went."""
         imgs, n, keep = self._images(frames, color)
         r = np.ascontiguousarray(np.asarray(rois, np.int32).reshape(-1, 5))
         p = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
@@ -716,6 +728,13 @@ class Environment:
         last detect_opencv_chain call."""
         info = CvChainInfo()
         _check(load_library().vj_cv_chain_info_get(self._h, C.byref(info)), "vj_cv_chain_info_get")
+        return info
+
+    def cv_rois_info(self) -> CvRoisInfo:
+        """vj_cv_rois_info_get: route, regions, level images, canvases (count and the largest one's size), windows and the pyramid
+        launches' device time of the last detect_opencv_rois call."""
+        info = CvRoisInfo()
+        _check(load_library().vj_cv_rois_info_get(self._h, C.byref(info)), "vj_cv_rois_info_get")
         return info
 
     def cv_plan_info(self, cascade: Cascade, width: int, height: int, n_frames: int, min_size=(0, 0),

@@ -16,6 +16,7 @@
 // parity is against the oracle's restatement of the same lines (oc_detect_opencvlike): unpinned.
 #include "vj_points_driver.hpp"
 #include "vj_cv_roi_host.hpp"
+#include "vj_cv_roi_levels_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -35,37 +36,7 @@ struct CvScaleHost {
     int lw = 0, lh = 0, ox = 0, oy = 0, step = 0;
 };
 
-// cvResize(CV_INTER_LINEAR), 8-bit: source indices and 11-bit weights of the `dst` columns (rows = false) or rows
-// of a `src` -> `dst` resize.  Columns past the last source column take it alone (fx = 0); rows keep their fraction and clamp the
-// two indices instead.  area: the 2 x 2 mean's taps.
-void build_taps(int src, int dst, bool rows, bool area, PyrTap* out) {
-    const double scale = 1. / ((double)dst / src);
-    for (int d = 0; d < dst; ++d) {
-        PyrTap& t = out[d];
-        if (area) {
-            t.i0 = (uint16_t)std::min(2 * d, src - 1);
-            t.i1 = (uint16_t)std::min(2 * d + 1, src - 1);
-            t.c0 = t.c1 = 0;
-            continue;
-        }
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int i = (int)std::floor(f);
-        f -= (float)i;
-        if (!rows) {
-            if (i < 0) { i = 0; f = 0.f; }
-            if (i >= src - 1) { i = src - 1; f = 0.f; }
-        }
-        t.i0 = (uint16_t)std::min(std::max(i, 0), src - 1);
-        t.i1 = (uint16_t)std::min(std::max(i + 1, 0), src - 1);
-        auto coef = [](float v) { return (int16_t)std::min(32767, std::max(-32768, cv_round((double)(v * 2048.f)))); };
-        t.c0 = coef(1.f - f);
-        t.c1 = coef(f);
-    }
-}
-bool resize_is_area(int sw, int sh, int dw, int dh) {
-    const double sx = 1. / ((double)dw / sw), sy = 1. / ((double)dh / sh);
-    return std::fabs(sx - 2.) < 2.220446049250313e-16 && std::fabs(sy - 2.) < 2.220446049250313e-16;
-}
+// (the level loop of CV_HAAR_SCALE_IMAGE, build_taps and resize_is_area: vj_cv_roi_levels_host.cpp — the regions' level canvases share them)
 
 // icvCreateHidHaarClassifierCascade's flags (tempcv.cpp:410-470) and the tree shape the kernels have a fast form for
 struct CvShape {
@@ -254,27 +225,20 @@ static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_
     if (si) {
         // ---- the level loop (tempcv.cpp:1268-1288; maxSize is the image unless a ROC call brings one)
         const int max_w = roc ? roc->max_w : W, max_h = roc ? roc->max_h : H;
-        double factor = 1;
-        for (int k = 0;; ++k, factor *= p->scale_factor) {
-            if (k > 65536) {
-                set_error("scale_factor %.17g gives more than 65536 pyramid levels", p->scale_factor);
-                return VJ_ERR_LIMIT;
-            }
+        std::vector<CvLevelHost> lv;
+        const int lrc = cv_scale_image_levels(c->win_w, c->win_h, W, H, p->scale_factor, p->min_w, p->min_h, max_w, max_h, &lv);
+        if (lrc) return lrc;
+        for (const CvLevelHost& l : lv) {
             CvScaleHost s;
-            s.factor = factor;
-            s.idx = k;
-            s.win_w = cv_round(c->win_w * factor);
-            s.win_h = cv_round(c->win_h * factor);
-            s.lw = cv_round(W / factor);
-            s.lh = cv_round(H / factor);
-            if (s.lw - c->win_w + 1 <= 0 || s.lh - c->win_h + 1 <= 0) break;
-            if (s.win_w > max_w || s.win_h > max_h) break;
-            if (s.win_w < p->min_w || s.win_h < p->min_h) continue;
-            // x, y = 0, ystep, ... < size - window (:1015-1020, :1079-1080)
-            s.step = factor > 2 ? 1 : 2;
-            s.end_x = (s.lw - c->win_w + s.step - 1) / s.step;
-            s.end_y = (s.lh - c->win_h + s.step - 1) / s.step;
-            if (s.end_x <= 0 || s.end_y <= 0) continue;   // (a level exactly one window wide or high: no position)
+            s.factor = l.factor;
+            s.idx = l.idx;
+            s.win_w = l.win_w;
+            s.win_h = l.win_h;
+            s.lw = l.lw;
+            s.lh = l.lh;
+            s.step = l.step;
+            s.end_x = l.end_x;
+            s.end_y = l.end_y;
             hs.push_back(s);
         }
         // One canvas per frame holds every level (levels come in decreasing size): shelves of the canvas's width, a level goes to the
@@ -2166,6 +2130,257 @@ struct CvPoints {
 
 const uint32_t CV_ROI_FAST_FLAGS = VJ_FLAG_COUNTERS;   // a flag word within these takes the region pass
 
+// ------------------------------------------------------------------------ CV_HAAR_SCALE_IMAGE inside regions
+// A flag word with VJ_FLAG_CV_SCALE_IMAGE and within these takes the level canvases (canny pruning and rough search are not read
+// by the scale-image branch; VJ_FLAG_CV_FIND_BIGGEST clears scale-image and is not among them)
+const uint32_t CV_ROI_LEVEL_FLAGS = VJ_FLAG_COUNTERS | VJ_FLAG_CV_SCALE_IMAGE | VJ_FLAG_CV_CANNY_PRUNING | VJ_FLAG_CV_ROUGH_SEARCH | VJ_FLAG_CV_CHAIN_DEVICE;
+// Pixels of a canvas of level images: 64 MiB of sum image, 128 MiB of square sums (and 64 MiB of tilted integral); far below the
+// (w + 1) * (h + 3) < 2^30 of a frame's 32-bit offsets
+const uint64_t CV_ROI_CANVAS_PX = 1ull << 24;
+
+// vj_detect_opencv_rois with VJ_FLAG_CV_SCALE_IMAGE on uniform frames: per canvas ONE pyramid launch for every level image of its
+// regions (pyramid_regions), the integral kernels on the canvas as on a frame, and the exhaustive-grid row kernel with one scale
+// record per level image and the node table at factor 1 in the canvas's pitch.  ONE loop: an iteration either moves on to the next
+// sub-batch of frames or runs the next canvas of the current one (a sub-batch's host frames are uploaded once, before its first
+// canvas).  Appends the raw candidates (rect.frame = the region's index) to *all; *oversized: regions no canvas holds.
+int run_cv_rois_levels(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_roi* rois, int n_rois, int W, int H, int CH,
+                       const vj_cv_params* p, uint64_t budget_px, std::vector<vj_rect>* all, vj_result* out, StageProgram* prog_out,
+                       std::vector<int>* oversized) {
+    if ((int)c->stages.size() > VJ_MAX_STAGES || c->stages.empty()) {
+        set_error("cascade has %zu stages; 1..%d are supported", c->stages.size(), VJ_MAX_STAGES);
+        return VJ_ERR_LIMIT;
+    }
+    *prog_out = build_stage_program(*c);
+    const StageProgram& prog = *prog_out;
+    std::vector<uint32_t> order;
+    if (!stage_sweep_order(prog, &order)) {
+        set_error("stage links form a cycle");
+        return VJ_ERR_UNSUPPORTED;
+    }
+    const CvShape shape = cv_shape_of(c);
+    const std::vector<StageDev> stages = build_cv_stage_recs(c, prog, order, shape.two_rects, shape.trees, shape.is_tree);
+    const bool count = (p->flags & VJ_FLAG_COUNTERS) != 0;
+    const size_t n_nodes = c->nodes.size();
+    int rc;
+    if ((rc = e->d_cv_rl_stages.ensure(stages.size() * sizeof(StageDev)))) return rc;
+    HIP_TRY(hipMemcpy(e->d_cv_rl_stages.p, stages.data(), stages.size() * sizeof(StageDev), hipMemcpyHostToDevice));
+    DevBuf& d_det = e->d_cv_det;
+    DevBuf& d_counts = e->d_cv_counts;
+    const size_t counts_bytes = 2 * VJ_MAX_STAGES * sizeof(uint64_t) + 16;   // stage_entered | visited ... | detection count
+    if ((rc = d_counts.ensure(counts_bytes))) return rc;
+    const uint64_t frame_bytes = (uint64_t)frame_elems_for(W, H) * 4u;
+    int max_frames = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_frames, 0xfffffff0ull / frame_bytes));
+    if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
+    const std::vector<int> by_frame = cv_rois_by_frame(rois, n_rois);
+    std::vector<CvRoiHost> regs;
+    CvTapCache taps;
+    size_t taps_uploaded = 0;
+    CvRegionCanvas cv;
+    std::vector<CvNodeRec> table(n_nodes);
+    uint32_t table_stride = 0;
+    uint64_t max_reach = 0;
+    std::vector<CvScaleDev> scales;
+    std::vector<UnitDev> rows;
+    uint32_t det_cap = 1u << 16;
+    const uint8_t* d_gray = nullptr;
+    size_t gray_frame_bytes = 0;
+    int gray_stride = 0;
+    bool staged = false;
+    size_t next = 0, pos = 0;
+    int f0 = 0, nf = 0;
+    vj_cv_rois_info& info = e->cv_rois_info;
+    for (;;) {
+        if (pos == regs.size()) {   // ---- the next sub-batch of frames
+            f0 += nf;
+            if (f0 >= n_frames || next >= by_frame.size()) break;
+            nf = std::min(max_frames, n_frames - f0);
+            cv_rois_of_subbatch(rois, by_frame, &next, f0, nf, &regs);
+            pos = 0;
+            staged = false;
+            continue;
+        }
+        // ---- the next canvas of this sub-batch
+        if ((rc = cv_roi_plan_canvas(regs, pos, c->win_w, c->win_h, p->scale_factor, p->min_w, p->min_h, budget_px, &taps, &cv))) return rc;
+        if (cv.oversized) oversized->push_back(regs[pos].id);
+        pos += cv.n_regions;
+        info.level_images += cv.n_empty_levels;
+        if (cv.oversized || cv.levels.empty()) continue;   // (regions too small for any level leave nothing to run)
+        if (!staged) {   // (a sub-batch no level image comes from is not uploaded)
+            if ((rc = ensure_gray_staging(e, W, H, nf, CH))) return rc;
+            if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
+            staged = true;
+        }
+        const int IW = (int)cv.w, IH = (int)cv.h;
+        const uint32_t stride = cv.w + 1u;
+        const uint32_t frame_elems = frame_elems_for(IW, IH);
+        if ((rc = ensure_image_buffers(e, IW, IH, 1, false))) return rc;
+        if ((rc = e->d_pyr.ensure((size_t)cv.pitch * (size_t)cv.h))) return rc;
+        // the cascade at factor 1 (cvSetImagesForHaarClassifierCascade(.., 1.), tempcv.cpp:1321) in this canvas's pitch
+        const int ex = cv_round(1.), ew = cv_round((c->win_w - 2) * 1.), eh = cv_round((c->win_h - 2) * 1.);
+        const double weight_scale = 1. / (ew * eh);
+        if (table_stride != stride) {
+            max_reach = 0;
+            if ((rc = build_cv_node_recs(c, 1., stride, weight_scale, table.data(), &max_reach))) return rc;
+            if ((rc = e->d_cv_rl_table.ensure(std::max<size_t>(table.size(), 1) * sizeof(CvNodeRec)))) return rc;
+            HIP_TRY(hipStreamSynchronize(e->stream));   // (the last canvas's pass is done: every iteration ends in a synchronise)
+            if (!table.empty()) HIP_TRY(hipMemcpy(e->d_cv_rl_table.p, table.data(), table.size() * sizeof(CvNodeRec), hipMemcpyHostToDevice));
+            table_stride = stride;
+        }
+        scales.assign(cv.levels.size(), CvScaleDev{});
+        rows.clear();
+        rows.reserve(cv.n_rows);
+        for (size_t k = 0; k < cv.levels.size(); ++k) {
+            const CvLevelHost& l = cv.levels[k].lv;
+            const PyrRegionLevelDev& d = cv.dev[k];
+            CvScaleDev& sd = scales[k];
+            memset(&sd, 0, sizeof(sd));
+            sd.ystep = (double)l.step;
+            sd.inv_area = weight_scale;
+            sd.win_w = (uint32_t)l.win_w;
+            sd.win_h = (uint32_t)l.win_h;
+            sd.end_x = (uint32_t)l.end_x;
+            sd.end_y = (uint32_t)l.end_y;
+            sd.q0 = (uint32_t)ex * stride + (uint32_t)ex;
+            sd.q1 = sd.q0 + (uint32_t)ew;
+            sd.q2 = (uint32_t)(ex + eh) * stride + (uint32_t)ex;
+            sd.q3 = sd.q2 + (uint32_t)ew;
+            sd.table_first = 0u;
+            sd.scale_idx = (uint32_t)l.idx;
+            // a level image's windows lie inside it, and it inside the canvas
+            const uint64_t origin_max = (uint64_t)(d.oy + d.h - (uint32_t)c->win_h) * stride + (uint64_t)(d.ox + d.w - (uint32_t)c->win_w);
+            if (d.ox + d.w > cv.w || d.oy + d.h > cv.h || origin_max + std::max<uint64_t>(max_reach, sd.q3) >= (uint64_t)frame_elems) {
+                set_error("feature reach exceeds the canvas allocation");
+                return VJ_ERR_LIMIT;
+            }
+            for (uint32_t iy = 0; iy < sd.end_y; ++iy) rows.push_back(UnitDev{(uint32_t)k, iy, d.oy * stride + d.ox, 0});
+        }
+        if ((rc = e->d_cv_rl_levels.ensure(cv.dev.size() * sizeof(PyrRegionLevelDev)))) return rc;
+        if ((rc = e->d_cv_rl_scales.ensure(scales.size() * sizeof(CvScaleDev)))) return rc;
+        if ((rc = e->d_cv_rl_rows.ensure(rows.size() * sizeof(UnitDev)))) return rc;
+        HIP_TRY(hipMemcpy(e->d_cv_rl_levels.p, cv.dev.data(), cv.dev.size() * sizeof(PyrRegionLevelDev), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->d_cv_rl_scales.p, scales.data(), scales.size() * sizeof(CvScaleDev), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->d_cv_rl_rows.p, rows.data(), rows.size() * sizeof(UnitDev), hipMemcpyHostToDevice));
+        if (taps_uploaded != taps.taps.size()) {   // (the call's taps grow by the pairs this canvas saw first)
+            if ((rc = e->d_cv_rl_taps.ensure(taps.taps.size() * sizeof(PyrTap)))) return rc;
+            HIP_TRY(hipMemcpy(e->d_cv_rl_taps.p, taps.taps.data(), taps.taps.size() * sizeof(PyrTap), hipMemcpyHostToDevice));
+            taps_uploaded = taps.taps.size();
+        }
+        PyrRegionArgs pa;
+        memset(&pa, 0, sizeof(pa));
+        pa.gray = d_gray;
+        pa.gray_frame_bytes = gray_frame_bytes;
+        pa.gray_stride = (uint32_t)gray_stride;
+        pa.channels = (uint32_t)CH;
+        pa.width = (uint32_t)W;
+        pa.height = (uint32_t)H;
+        pa.n_frames = (uint32_t)nf;
+        pa.levels = (const PyrRegionLevelDev*)e->d_cv_rl_levels.p;
+        pa.n_levels = (uint32_t)cv.dev.size();
+        pa.n_units = cv.n_pyr_units;
+        pa.taps = (const PyrTap*)e->d_cv_rl_taps.p;
+        pa.canvas = (uint8_t*)e->d_pyr.p;
+        pa.canvas_pitch = cv.pitch;
+        pa.canvas_w = cv.w;
+        pa.canvas_h = cv.h;
+        HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
+        int hrc = launch_pyramid_regions(pa, e->stream);
+        if (hrc) {
+            set_error("pyramid launch failed: %s", hipGetErrorString((hipError_t)hrc));
+            return VJ_ERR_HIP;
+        }
+        HIP_TRY(hipEventRecord(e->cv_rois_ev[0], e->stream));
+        // from here on the "frame" is the gray canvas
+        const uint8_t* d_canvas = (const uint8_t*)e->d_pyr.p;
+        const size_t canvas_bytes = (size_t)cv.pitch * (size_t)cv.h;
+        if ((rc = enqueue_integral(e, d_canvas, canvas_bytes, (int)cv.pitch, IW, IH, 1, 1))) return rc;
+        if (shape.has_tilted && (rc = enqueue_tilted(e, d_canvas, canvas_bytes, (int)cv.pitch, IW, IH, 1, 1))) return rc;
+        HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
+        for (int attempt = 0;; ++attempt) {
+            if (attempt == 2) {   // (cannot happen: the count of a repeated pass is the count that sized its buffer)
+                set_error("vj_detect_opencv_rois: the detection buffer overflowed twice");
+                return VJ_ERR_LIMIT;
+            }
+            if ((rc = d_det.ensure((size_t)det_cap * sizeof(CvDet)))) return rc;
+            HIP_TRY(hipMemsetAsync(d_counts.p, 0, counts_bytes, e->stream));
+            CvArgs a;
+            memset(&a, 0, sizeof(a));
+            a.sum = (const uint32_t*)e->d_sum.p;
+            a.sqsum = (const uint64_t*)e->d_sqsum.p;
+            a.tilted = shape.has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
+            a.n_order = (uint32_t)order.size();
+            a.table = (const uint32_t*)e->d_cv_rl_table.p;
+            a.scales = (const CvScaleDev*)e->d_cv_rl_scales.p;
+            a.stages = (const StageDev*)e->d_cv_rl_stages.p;
+            a.rows = (const UnitDev*)e->d_cv_rl_rows.p;
+            a.n_rows = (uint32_t)rows.size();
+            a.n_frames = 1u;
+            a.n_stages = (uint32_t)c->stages.size();
+            a.frame_elems = frame_elems;
+            a.stride = stride;
+            a.sum_h = (uint32_t)IH + 1u;
+            a.det = (CvDet*)d_det.p;
+            a.det_count = (uint32_t*)((unsigned long long*)d_counts.p + 2 * VJ_MAX_STAGES);
+            a.det_cap = det_cap;
+            a.stage_entered = (unsigned long long*)d_counts.p;
+            a.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
+            a.tree2 = shape.tree2 && !shape.is_tree && !shape.has_tilted && e->cv_tree2 ? 1u : 0u;
+            // one wave per row unit, at most four workgroups (16 waves) per CU; the rest by stride
+            // (a stage tree walks every position to the end of the tree: a.chains stays empty, the per-lane target-stage sweep)
+            const int n_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((rows.size() + CV_WAVES_PER_BLOCK - 1) / CV_WAVES_PER_BLOCK, (uint64_t)std::max(1, e->n_cu * 4)));
+            a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
+            HIP_TRY(hipEventRecord(e->lane0.ev[2], e->stream));
+            hrc = launch_cv_profile_pass(a, shape.trees, count, shape.is_tree, n_blocks, e->stream, false, true);
+            if (hrc) {
+                set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
+                return VJ_ERR_HIP;
+            }
+            HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
+            std::vector<unsigned long long> h((counts_bytes + 7) / 8);
+            HIP_TRY(hipMemcpyAsync(h.data(), d_counts.p, counts_bytes, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            const uint32_t n_det = (uint32_t)(h[2 * VJ_MAX_STAGES] & 0xffffffffull);
+            if (n_det > det_cap) {   // overflow: grow and run the pass again
+                det_cap = grown_cap(det_cap, n_det);
+                continue;
+            }
+            float ms_p = 0, ms_i = 0, ms_c = 0;
+            HIP_TRY(hipEventElapsedTime(&ms_p, e->lane0.ev[0], e->cv_rois_ev[0]));
+            HIP_TRY(hipEventElapsedTime(&ms_i, e->lane0.ev[0], e->lane0.ev[1]));
+            HIP_TRY(hipEventElapsedTime(&ms_c, e->lane0.ev[2], e->lane0.ev[3]));
+            out->timing.integral_ms += ms_i;
+            out->timing.cascade_ms += ms_c;
+            out->timing.total_ms += ms_i + ms_c;
+            out->timing.n_cascade_launches += 1;
+            info.pyramid_ms += ms_p;
+            if (count) {
+                for (size_t s = 0; s < c->stages.size(); ++s) out->counters.stage_entered[s] += h[s];
+                out->counters.windows += h[VJ_MAX_STAGES];
+            }
+            std::vector<CvDet> raw(n_det);
+            if (n_det) HIP_TRY(hipMemcpy(raw.data(), d_det.p, (size_t)n_det * sizeof(CvDet), hipMemcpyDeviceToHost));
+            for (const CvDet& d : raw) {
+                if (d.slot >= cv.levels.size()) {
+                    set_error("the level pass returned a detection outside its level images");
+                    return VJ_ERR_HIP;
+                }
+                // Rect(cvRound(x * factor), cvRound(y * factor), winSize) (tempcv.cpp:1099-1100), relative to the region
+                const CvRegionLevel& L = cv.levels[d.slot];
+                all->push_back(vj_rect{cv_round((double)d.x * L.lv.factor), cv_round((double)d.y * L.lv.factor), L.lv.win_w, L.lv.win_h, 0.0f,
+                                       regs[(size_t)L.region].id, L.lv.idx});
+            }
+            break;
+        }
+        info.canvases += 1;
+        info.level_images += cv.levels.size();
+        info.windows += cv.windows;
+        if ((uint64_t)cv.w * cv.h > (uint64_t)info.canvas_w * info.canvas_h) {
+            info.canvas_w = cv.w;
+            info.canvas_h = cv.h;
+        }
+    }
+    return VJ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2269,11 +2484,47 @@ int vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames
             set_error("roi %d lies outside its frame", i);
             return VJ_ERR_ARG;
         }
+    e->cv_rois_info = vj_cv_rois_info{};
+    e->cv_rois_info.regions = (uint64_t)n_rois;
     if (n_rois == 0) return VJ_OK;
     int W, H, CH;
+    // (many regions of few sizes stay on the per-size route, which is faster for them: cv_rois_levels_pay)
+    if ((p->flags & VJ_FLAG_CV_SCALE_IMAGE) != 0u && (p->flags & ~CV_ROI_LEVEL_FLAGS) == 0u && cv_frames_uniform(frames, n_frames, &W, &H, &CH) &&
+        cv_rois_levels_pay(rois, n_rois)) {
+        // ---- CV_HAAR_SCALE_IMAGE: every region's level images on canvases, one pass per canvas
+        HIP_TRY(hipSetDevice(e->device));
+        e->cv_rois_info.route = 2;
+        std::vector<vj_rect> all;
+        std::vector<int> oversized;
+        StageProgram prog;
+        int rc = run_cv_rois_levels(e, c, frames, n_frames, rois, n_rois, W, H, CH, p, CV_ROI_CANVAS_PX, &all, out, &prog, &oversized);
+        if (rc) return rc;
+        if (oversized.empty()) return finish_cv_roi_result(all, &prog, p, out);
+        // regions too large for a canvas: the per-size route below for them, merged region by region (each part is in its final
+        // order and a region's rectangles all come from one part)
+        e->cv_rois_info.route = 4;
+        if ((rc = finish_cv_roi_result(all, &prog, p, out))) return rc;
+        all.assign(out->rects, out->rects + out->count);
+        free(out->rects);
+        out->rects = nullptr;
+        out->count = 0;
+        std::vector<vj_roi> big(oversized.size());
+        for (size_t i = 0; i < big.size(); ++i) big[i] = rois[oversized[i]];
+        for (const CvRoiSizeGroup& g : cv_roi_size_groups(frames, big.data(), (int)big.size())) {
+            std::vector<int> idx(g.idx.size());
+            for (size_t i = 0; i < idx.size(); ++i) idx[i] = oversized[(size_t)g.idx[i]];
+            vj_result part;
+            rc = vj_detect_opencv(e, c, g.views.data(), (int)g.views.size(), p, &part);
+            if (!rc) rc = cv_roi_take_part(part, idx, &all, out);
+            vj_result_free(&part);
+            if (rc) return rc;
+        }
+        return cv_roi_emit_parts(all, out);
+    }
     // (VJ_FLAG_CV_CHAIN_DEVICE belongs to vj_detect_opencv_chain: ignored here)
     if ((p->flags & ~(CV_ROI_FAST_FLAGS | (uint32_t)VJ_FLAG_CV_CHAIN_DEVICE)) == 0u && cv_frames_uniform(frames, n_frames, &W, &H, &CH)) {
-        // ---- every region in one pass per sub-batch, on the frames' own integral images
+        e->cv_rois_info.route = 1;
+    // ---- every region in one pass per sub-batch, on the frames' own integral images
         HIP_TRY(hipSetDevice(e->device));
         const std::vector<int> by_frame = cv_rois_by_frame(rois, n_rois);
         bool has_tilted = false;
@@ -2299,7 +2550,9 @@ int vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames
             if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
             if (has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
             HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
-            if ((rc = run_cv_roi_pass(e, c, W, H, nf, regs, p, &all, out, &pl))) return rc;   // (ends in a stream synchronise)
+            uint64_t n_windows = 0;
+            if ((rc = run_cv_roi_pass(e, c, W, H, nf, regs, p, &all, out, &pl, nullptr, &n_windows))) return rc;   // (ends in a stream synchronise)
+            e->cv_rois_info.windows += n_windows;
             HIP_TRY(hipEventSynchronize(e->lane0.ev[1]));   // (so this returns at once, also when the pass had nothing to launch)
             float ms_i = 0;
             HIP_TRY(hipEventElapsedTime(&ms_i, e->lane0.ev[0], e->lane0.ev[1]));
@@ -2309,7 +2562,9 @@ int vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames
         return finish_cv_roi_result(all, pl ? &pl->prog : nullptr, p, out);
     }
     // ---- frames of differing sizes, or a flag whose result on a crop is not a crop of its result on the frame (the edge map, the
-    // resized image, the find-biggest search): one vj_detect_opencv call per region size (and channel count) on the sub-images
+    // find-biggest search; the resized image when the frames differ in size): one vj_detect_opencv call per region size (and channel
+    // count) on the sub-images
+    e->cv_rois_info.route = 3;
     std::vector<vj_rect> all;
     for (const CvRoiSizeGroup& g : cv_roi_size_groups(frames, rois, n_rois)) {
         vj_result part;
@@ -2409,6 +2664,12 @@ int vj_detect_opencv_chain(vj_env* e, const vj_cascade* first, const vj_cascade*
 int vj_run_windows_opencv(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const double* scales, int n_scales,
                           const vj_window* windows, uint32_t n_windows, int start_stage, vj_window_result* out) {
     return run_points<CvPoints>(e, c, frames, n_frames, scales, n_scales, windows, n_windows, start_stage, 0u, out);
+}
+
+int vj_cv_rois_info_get(const vj_env* e, vj_cv_rois_info* out) {
+    if (!e || !out) return VJ_ERR_ARG;
+    *out = e->cv_rois_info;
+    return VJ_OK;
 }
 
 int vj_cv_chain_info_get(const vj_env* e, vj_cv_chain_info* out) {

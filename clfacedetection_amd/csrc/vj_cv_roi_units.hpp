@@ -71,4 +71,24 @@ struct CvChainState {
 };
 static_assert(sizeof(CvChainState) == 40, "CvChainState is 40 bytes");
 
+// ---- CV_HAAR_SCALE_IMAGE inside regions (vj_detect_opencv_rois, route 2): the level images of a canvas (vj_cv_roi_levels_host.cpp
+// plans them, pyramid_regions in vj_pyramid.hip writes them)
+struct alignas(8) PyrTap {  // one destination column or row of a level
+    uint16_t i0, i1;       // the two source columns / rows (clamped to the source)
+    int16_t  c0, c1;       // their 11-bit weights (2048 = 1.0); area levels do not read them
+};
+// One level image: cvResize of the crop [cx, cx + cw) x [cy, cy + ch) of frame `frame` to w x h at (ox, oy) of the canvas.  The taps
+// index the CROP.  ox is a multiple of 4 (the kernel stores four pixels as one dword).
+struct PyrRegionLevelDev {
+    uint32_t frame;        // in the sub-batch on the device
+    uint32_t cx, cy, cw, ch;
+    uint32_t ox, oy, w, h;
+    uint32_t xtab, ytab;   // first PyrTap of its columns / rows
+    uint32_t unit_first;   // first work unit (a PYR_REGION_TW x PYR_REGION_TH block of destination pixels) of this level image
+    uint32_t area;         // != 0: the crop is exactly 2 w x 2 h: dst = (2 x 2 sum + 2) >> 2
+    uint32_t pad[3];
+};
+static_assert(sizeof(PyrRegionLevelDev) == 64, "PyrRegionLevelDev is 64 bytes");
+constexpr uint32_t PYR_REGION_TW = 64, PYR_REGION_TH = 16;   // destination pixels per workgroup: 16 x 16 threads of four pixels each
+
 }  // namespace vj

@@ -675,10 +675,7 @@ int launch_cv_prune_visited(const CvPruneArgs& a, int n_blocks, void* stream);
 // CV_HAAR_SCALE_IMAGE (VJ_FLAG_CV_SCALE_IMAGE; vj_pyramid.hip): every level of every frame's pyramid in ONE launch, written into
 // one canvas per frame that holds all levels (shelf-packed; the integral kernels then run on the canvas as on a frame).
 // cvResize(CV_INTER_LINEAR) of 8-bit gray, DESIGN.md §4.8: coefficient tables built on the host per plan.
-struct alignas(8) PyrTap {  // one destination column or row of a level
-    uint16_t i0, i1;       // the two source columns / rows (clamped to the source)
-    int16_t  c0, c1;       // their 11-bit weights (2048 = 1.0); area levels do not read them
-};
+// (PyrTap: vj_cv_roi_units.hpp, shared with the host planner of the regions' level canvases)
 struct PyrLevelDev {
     uint32_t ox, oy;       // the level's origin in the canvas
     uint32_t w, h;         // its size
@@ -704,5 +701,25 @@ struct PyrArgs {
     uint64_t canvas_frame_bytes;
 };
 int launch_pyramid(const PyrArgs& a, void* stream);
+
+// CV_HAAR_SCALE_IMAGE inside regions (vj_detect_opencv_rois, route 2; pyramid_regions in vj_pyramid.hip): every level
+// image of every region of a canvas in ONE launch.  The levels name their source frame and crop (PyrRegionLevelDev); one canvas, not
+// one per frame.
+struct PyrRegionArgs {
+    const uint8_t* gray;        // the sub-batch's frames (1 / 3 / 4 channels)
+    uint64_t gray_frame_bytes;
+    uint32_t gray_stride;
+    uint32_t channels;
+    uint32_t width, height;     // of a frame
+    uint32_t n_frames;
+    const PyrRegionLevelDev* levels;
+    uint32_t n_levels;
+    uint32_t n_units;
+    const PyrTap* taps;
+    uint8_t* canvas;            // rows of canvas_pitch bytes (a multiple of 4)
+    uint32_t canvas_pitch;
+    uint32_t canvas_w, canvas_h;
+};
+int launch_pyramid_regions(const PyrRegionArgs& a, void* stream);
 
 }  // namespace vj

@@ -394,6 +394,12 @@ struct vj_env : vj::Tunables {
     vj::DevBuf d_cv_chain, d_cv_chain_keys, d_cv_chain_staged, d_cv_roi_first, d_cv_det2, d_cv_counts2;
     hipEvent_t cv_chain_ev[3] = {};
     vj_cv_chain_info cv_chain_info = {};    // the last vj_detect_opencv_chain call (vj_cv_chain_info_get)
+    // vj_detect_opencv_rois with VJ_FLAG_CV_SCALE_IMAGE (route 2): a canvas's level records, the call's taps, one scale
+    // record per level image, the row units, the node table at factor 1 in the canvas's pitch, the stage records; events around the
+    // pyramid launch
+    vj::DevBuf d_cv_rl_levels, d_cv_rl_taps, d_cv_rl_scales, d_cv_rl_rows, d_cv_rl_table, d_cv_rl_stages;
+    hipEvent_t cv_rois_ev[2] = {};
+    vj_cv_rois_info cv_rois_info = {};      // the last vj_detect_opencv_rois call (vj_cv_rois_info_get)
     // The window-list calls (vj_points_driver.hpp), per profile: stage records per cascade uid; plans per (cascade uid, frame width, bits of
     // the scale[, tilted-as-upright]).  Under plan_cache_max, least recently used first — except the plans of the call in progress
     typedef std::map<uint64_t, std::unique_ptr<vj::PointCascade>> PointCascades;

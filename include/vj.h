@@ -598,13 +598,37 @@ int  vj_detect_chain(vj_env* e, const vj_cascade* first, const vj_cascade* secon
  *                               integral images (a rectangle sum does not depend on where the integral image starts; a tilted
  *                               rectangle's four corners give the sum over the same pixels in the frame's tilted integral as in the
  *                               crop's).  Frames of differing sizes: the route below.
+ *   VJ_FLAG_CV_SCALE_IMAGE      (with or without VJ_FLAG_COUNTERS; VJ_FLAG_CV_CANNY_PRUNING and VJ_FLAG_CV_ROUGH_SEARCH beside it are not
+ *                               read, as in vj_detect_opencv) frames of one size: a resized crop is not a crop of the resized frame,
+ *                               so every region gets level images of its own — cvResize of the crop for every level the region's
+ *                               w x h takes — but all of them, for all regions of a sub-batch, are written by ONE launch into one
+ *                               canvas, integrated once, and walked by one exhaustive-grid pass (a canvas holds a fixed number of
+ *                               pixels; regions beyond it start another one; a region too large for an empty canvas takes the
+ *                               route below).  Frames of differing sizes, and calls with more than 32 regions per distinct
+ *                               region size on average (measured faster there): the route below.
  *   VJ_FLAG_CV_CANNY_PRUNING    } one vj_detect_opencv call per region size on the sub-images: the Canny map of a crop is not the
- *   VJ_FLAG_CV_SCALE_IMAGE      } crop of the Canny map (replicated borders, hysteresis connectivity), a resized crop is not a crop
- *   VJ_FLAG_CV_FIND_BIGGEST     } of the resized frame, and the find-biggest search keeps its state per image.
+ *   VJ_FLAG_CV_FIND_BIGGEST     } crop of the Canny map (replicated borders, hysteresis connectivity), and the find-biggest search
+ *                               } keeps its state per image (it clears VJ_FLAG_CV_SCALE_IMAGE).
  *   any other bit               the same route (vj_detect_opencv ignores what it does not know).
  * The result is the same either way, by definition.                                                                              */
 int  vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_roi* rois, int n_rois,
                            const vj_cv_params* p, vj_result* out);
+/* What the environment's last vj_detect_opencv_rois call did (zeroed when a call begins; a chain call that runs "the two public
+ * calls" makes one). */
+typedef struct vj_cv_rois_info {
+    int32_t  route;               /* 0 no call yet; 1 one pass on the frames' integral images; 2 one pass on level canvases
+                                     (VJ_FLAG_CV_SCALE_IMAGE); 3 one vj_detect_opencv call per region size; 4 route 2 with some
+                                     regions, too large for a canvas, sent through route 3                                       */
+    int32_t  canvases;            /* route 2 / 4: canvases of level images the call made                                          */
+    uint32_t canvas_w, canvas_h;  /* ... the size of the largest (by pixels)                                                      */
+    uint64_t regions;             /* regions of the call                                                                          */
+    uint64_t level_images;        /* route 2 / 4: (region, level) pairs the level loop evaluates (the few without a grid
+                                     position included: they have no level image)                                               */
+    uint64_t windows;             /* grid positions of the pass (routes 1, 2, 4: of what ran there); 0 on route 3                 */
+    float    pyramid_ms;          /* device time of the pyramid launches (events), summed over canvases                          */
+    int32_t  reserved;
+} vj_cv_rois_info;
+int  vj_cv_rois_info_get(const vj_env* e, vj_cv_rois_info* out);   /* a null argument: VJ_ERR_ARG */
 /* vj_detect_opencv_chain mirrors vj_detect_chain: out_first is what vj_detect_opencv(first, p_first) returns, and its rectangles are
  * the regions — the raw candidates when p_first->min_neighbors == 0, the grouped objects otherwise; out_second is what
  * vj_detect_opencv_rois(second, those regions, p_second) returns, rect.frame indexing out_first->rects.  Both flag words within

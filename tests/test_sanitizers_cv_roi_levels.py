@@ -1,0 +1,30 @@
+"""AddressSanitizer + UBSan run on the CPU of the host planner of CV_HAAR_SCALE_IMAGE inside regions
+(csrc/vj_cv_roi_levels_host.cpp: the level loop, the resize taps, the canvases of level images) behind
+tests/cv_roi_levels_asan_driver.cpp, a stand-alone program: the REGIONS geometry of tests/cv_rois_cases.py with the library's canvas
+budget and with budgets so small that the canvases split and regions fit none."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "clfacedetection_amd", "csrc")
+
+
+def _asan_runtime():
+    p = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
+    return p if os.path.isabs(p) and os.path.exists(p) else None
+
+
+@pytest.mark.skipif(_asan_runtime() is None, reason="no libasan in this toolchain")
+def test_cv_roi_level_planner_under_asan_ubsan(tmp_path):
+    exe = str(tmp_path / "cv_roi_levels_asan")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
+           "-DVJ_BUILDING", os.path.join(ROOT, "tests", "cv_roi_levels_asan_driver.cpp")] + \
+          [os.path.join(CSRC, f) for f in ("vj_cv_roi_levels_host.cpp", "vj_cv_roi_host.cpp", "vj_cascade.cpp", "vj_group.cpp")] + ["-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    r = subprocess.run([exe], capture_output=True, text=True,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "cv_roi_levels_asan_driver: OK" in r.stdout
