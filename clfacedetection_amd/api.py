@@ -140,6 +140,19 @@ class CvRoisInfo(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class MixedOpts(C.Structure):
+    """vj_mixed_opts: speed only.  atlas_px: pixel budget of one atlas (0: default); own_call_px: a group of equal frames with at
+    least this many pixels in total gets a batched call of its own (0: default, 2**64 - 1: never)."""
+    _fields_ = [("atlas_px", C.c_uint64), ("own_call_px", C.c_uint64)]
+
+
+class MixedInfo(C.Structure):
+    """vj_mixed_info: what the environment's last detect_mixed / detect_opencv_mixed call did."""
+    _fields_ = [("atlases", C.c_int32), ("own_calls", C.c_int32), ("atlas_w", C.c_uint32), ("atlas_h", C.c_uint32),
+                ("frames", C.c_uint64), ("frames_atlas", C.c_uint64), ("frames_own_calls", C.c_uint64),
+                ("frames_oversized", C.c_uint64), ("windows", C.c_uint64), ("pack_ms", C.c_float), ("reserved", C.c_int32)]
+
+
 class _Counters(C.Structure):
     _fields_ = [("windows", C.c_uint64), ("stump_evals", C.c_uint64), ("gather_bytes", C.c_uint64),
                 ("stage_entered", C.c_uint64 * VJ_MAX_STAGES)]
@@ -261,6 +274,13 @@ _SIGNATURES = {
     "vj_cv_plan_info_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CvParams), C.POINTER(CvPlanInfo)]),
     "vj_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params),
                             C.POINTER(_Result)]),
+    "vj_detect_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Params), C.POINTER(MixedOpts),
+                                  C.POINTER(_Result)]),
+    "vj_detect_opencv_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(CvParams), C.POINTER(MixedOpts),
+                                         C.POINTER(_Result)]),
+    "vj_pack_frames": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                 C.POINTER(C.c_int), C.c_void_p]),
+    "vj_mixed_info_get": (C.c_int, [C.c_void_p, C.POINTER(MixedInfo)]),
     "vj_result_free": (None, [C.POINTER(_Result)]),
     "vj_group_rectangles": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_double]),
     "vj_group_rectangles_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double]),
@@ -744,6 +764,77 @@ class Environment:
         info = CvPlanInfo()
         _check(load_library().vj_cv_plan_info_get(self._h, cascade._h, width, height, n_frames, C.byref(p), C.byref(info)),
                "vj_cv_plan_info_get")
+        return info
+
+    @staticmethod
+    def _mixed_images(frames):
+        """Frames of any sizes -> (ctypes array of vj_image, n, arrays to keep alive).  Items: 2-D uint8 arrays (gray), (h, w, 3 | 4)
+        uint8 arrays (BGR / BGRA; rows may be strided views) and DeviceFrames, each of which contributes its frames."""
+        keep, imgs = [], []
+        if isinstance(frames, (np.ndarray, DeviceFrames)):
+            frames = [frames]
+        for f in frames:
+            if isinstance(f, DeviceFrames):
+                imgs += [_Image(f.ptr + i * f.stride * f.height, f.width, f.height, f.stride, 1, f.channels) for i in range(f.n)]
+                continue
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim not in (2, 3) or (f.ndim == 3 and f.shape[2] not in (3, 4)):
+                raise ValueError("a frame must be a 2-D uint8 array, a (h, w, 3|4) uint8 array (BGR / BGRA) or DeviceFrames")
+            g = _pixel_contiguous(f) if f.ndim == 3 else (f if f.strides[1] == 1 else np.ascontiguousarray(f))
+            keep.append(g)
+            imgs.append(_Image(g.ctypes.data, g.shape[1], g.shape[0], g.strides[0], 0, g.shape[2] if g.ndim == 3 else 1))
+        arr = (_Image * max(len(imgs), 1))(*imgs)
+        return arr, len(imgs), keep
+
+    @staticmethod
+    def _mixed_opts(atlas_px, own_call_px):
+        return MixedOpts(int(atlas_px), min(int(own_call_px), 2**64 - 1))
+
+    def detect_mixed(self, cascade: Cascade, frames, params: Params | None = None, atlas_px: int = 0, own_call_px: int = 0) -> DetectResult:
+        """vj_detect_mixed: detect() on a list of frames of ANY sizes, strides and channel counts (see _mixed_images), host and
+        device-resident ones mixed, in one call: the result is the concatenation over i of what detect() returns for frames[i]
+        alone (rects['frame'] = i, every frame grouped on its own, counters summed).  Groups of equal frames with at least
+        own_call_px pixels take a batched call of their own; the others are packed into atlases on the device, integrated once and
+        run as regions.  atlas_px / own_call_px change speed only; mixed_info() tells what the last call did."""
+        p = params or default_params()
+        imgs, n, keep = self._mixed_images(frames)
+        o = self._mixed_opts(atlas_px, own_call_px)
+        res = _Result()
+        lib = load_library()
+        _check(lib.vj_detect_mixed(self._h, cascade._h, imgs, n, C.byref(p), C.byref(o), C.byref(res)), "vj_detect_mixed")
+        return self._result(lib, res, cascade)
+
+    def detect_opencv_mixed(self, cascade: Cascade, frames, min_size=(0, 0), scale_factor: float = 1.1, min_neighbors: int = 0,
+                            flags: int = 0, atlas_px: int = 0, own_call_px: int = 0) -> DetectResult:
+        """vj_detect_opencv_mixed: the same for detect_opencv (every flag of it; those whose result needs the image alone — canny
+        pruning without scale-image, find-biggest — run per group of equal frames, without an atlas)."""
+        imgs, n, keep = self._mixed_images(frames)
+        p = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
+        o = self._mixed_opts(atlas_px, own_call_px)
+        res = _Result()
+        lib = load_library()
+        _check(lib.vj_detect_opencv_mixed(self._h, cascade._h, imgs, n, C.byref(p), C.byref(o), C.byref(res)), "vj_detect_opencv_mixed")
+        return self._result(lib, res, cascade)
+
+    def pack_frames(self, frames, atlas_px: int = 0):
+        """vj_pack_frames: the first atlas a mixed call would make of `frames` -> (atlas as a (h, w) uint8 array, origins as an
+        (n, 2) int32 array of (x, y), -1 -1 for a frame that is not in it).  A frame's gray image lies at its origin; what no frame
+        covers is 0."""
+        imgs, n, keep = self._mixed_images(frames)
+        lib = load_library()
+        w, h = C.c_int(0), C.c_int(0)
+        origins = np.full((n, 2), -1, np.int32)
+        _check(lib.vj_pack_frames(self._h, imgs, n, int(atlas_px), None, 0, C.byref(w), C.byref(h), origins.ctypes.data), "vj_pack_frames")
+        atlas = np.zeros((h.value, w.value), np.uint8)
+        if atlas.size:
+            _check(lib.vj_pack_frames(self._h, imgs, n, int(atlas_px), atlas.ctypes.data, atlas.strides[0], C.byref(w), C.byref(h),
+                                      origins.ctypes.data), "vj_pack_frames")
+        return atlas, origins
+
+    def mixed_info(self) -> MixedInfo:
+        """vj_mixed_info_get: atlases (count and the largest one's size), batched calls on original frames, frames by route, grid
+        positions of the atlas passes and the pack launches' device time of the last detect_mixed / detect_opencv_mixed call."""
+        info = MixedInfo()
+        _check(load_library().vj_mixed_info_get(self._h, C.byref(info)), "vj_mixed_info_get")
         return info
 
     def detect(self, cascade: Cascade, frames, params: Params | None = None, color: bool = False) -> DetectResult:

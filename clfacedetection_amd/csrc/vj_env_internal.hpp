@@ -422,6 +422,11 @@ struct vj_env : vj::Tunables {
     vj::DevBuf d_cv_big;              // CV_HAAR_FIND_BIGGEST_OBJECT: a sub-batch's search states (CvBigState), then its frames' candidate counts
     int edge_slack_w = 0, edge_slack_h = 0, edge_slack_frames = 0;   // layout whose slack rows of d_edge_sum are known to be zero
     void* edge_slack_sum = nullptr;
+    // vj_detect_mixed / vj_detect_opencv_mixed / vj_pack_frames (vj_mixed.cpp): the 8-bit atlas (grows, reused), the
+    // block one copy brings per atlas — its frame records, then its host frames at a 4-byte pitch —, events around the pack launch
+    vj::DevBuf d_atlas, d_atlas_src;
+    hipEvent_t atlas_ev[2] = {};
+    vj_mixed_info mixed_info = {};          // the last mixed call (vj_mixed_info_get)
     uint64_t plan_tick = 0;
     int cv_tq_shift = 4;              // ... stage trees: the survivors' queue holds 1 / 2^shift of the tile windows (grows on overflow)
 };

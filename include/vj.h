@@ -411,7 +411,8 @@ typedef struct vj_result {
 } vj_result;
 
 /* clodDetectObjects(image, cascade, data, min, max, min_neighbors, flags, CL_TRUE)
- * (clod.h:72-81, clod.cpp:1176-1336), batched over n_frames frames of equal size. */
+ * (clod.h:72-81, clod.cpp:1176-1336), batched over n_frames frames of equal size (frames of differing
+ * sizes: vj_detect_mixed, vj_detect_opencv_mixed below). */
 int  vj_detect(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames,
                const vj_params* p, vj_result* out);
 void vj_result_free(vj_result* r);
@@ -658,6 +659,60 @@ typedef struct vj_cv_chain_info {
     int32_t  reserved;
 } vj_cv_chain_info;
 int  vj_cv_chain_info_get(const vj_env* e, vj_cv_chain_info* out);   /* a null argument: VJ_ERR_ARG */
+
+/* ------------------------------------------------- batches of frames of differing sizes */
+/* vj_detect and vj_detect_opencv take frames of ONE size.  These two take frames of any sizes — a folder of photographs, thumbnails,
+ * crops from another detector — in one call.  The result is, by definition, the concatenation over i of what
+ * vj_detect / vj_detect_opencv returns for frames[i] ALONE with the same parameters: rect.frame = i, x / y in the frame, scale_idx the
+ * index in that frame's own enumeration, min_neighbors != 0 groups every frame on its own, counters and timings are sums, the list is
+ * sorted by (frame, scale_idx, y, x).  Frames may differ in width, height, stride and channels (1, 3 or 4); host and device-resident
+ * frames may be mixed.  A frame too small for any scale contributes nothing; n_frames == 0 is VJ_OK; a frame with null data, w <= 0,
+ * h <= 0, another channel count or stride < w * channels is VJ_ERR_ARG, and vj_last_error names the frame.
+ * How a call runs: frames are grouped by (w, h, channels).  A group with at least own_call_px pixels in total goes through ONE batched
+ * vj_detect / vj_detect_opencv call on the original frames (large or many equal frames run best there).  The gray images of all
+ * other frames are written by ONE launch (atlas_pack, vj_atlas.hip) into an atlas — shelf-packed, no gaps but the rounding of slot
+ * widths to 4 columns, dimensions from a short ladder so that plans repeat —, the atlas is integrated ONCE as one frame (with the
+ * tilted integral when the cascade has tilted nodes) and every frame runs as a region of it in one region pass (what
+ * vj_detect_opencv_rois / vj_detect_rois do for one device-resident frame: a rectangle sum does not depend on where the integral
+ * image starts).  Frames beyond the atlas's pixel budget, or beyond the configured "max_subbatch" frames, start the next atlas; a
+ * frame whose slot exceeds an empty atlas takes a call of its own.  An atlas stays inside the 32-bit offsets of a frame's sum image.
+ * Flags whose result needs the image alone send EVERY group through its own batched call, and no atlas is made: VJ_FLAG_SKIP_ROW /
+ * VJ_FLAG_SKIP_LIST (clod profile); VJ_FLAG_CV_CANNY_PRUNING without VJ_FLAG_CV_SCALE_IMAGE, VJ_FLAG_CV_FIND_BIGGEST, and bits
+ * vj_detect_opencv does not know (OpenCV profile).  VJ_FLAG_CV_SCALE_IMAGE runs from the atlas on level canvases
+ * (vj_detect_opencv_rois' route 2, the atlas as its one device-resident gray frame).  Same result either way.
+ * The options are a call argument, not vj_env_configure keys; like those they change speed only, never a result.               */
+typedef struct vj_mixed_opts {     /* NULL = defaults */
+    uint64_t atlas_px;             /* pixel budget of one atlas: the frame slots it holds, in total (0 = default: 2^24)          */
+    uint64_t own_call_px;          /* a group of frames of one (w, h, channels) with at least this many pixels in total gets a
+                                      batched call of its own; 0 = default: 2^19 (measured), UINT64_MAX = never */
+} vj_mixed_opts;
+int  vj_detect_mixed(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_params* p,
+                     const vj_mixed_opts* opts, vj_result* out);
+int  vj_detect_opencv_mixed(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_params* p,
+                            const vj_mixed_opts* opts, vj_result* out);
+/* The packing alone, next to vj_grayscale: the first atlas a mixed call with this budget would make of `frames` if none of them took
+ * a call of its own (frames in order while the budget and "max_subbatch" hold; frames too large for an empty atlas are passed over),
+ * written to the HOST buffer `atlas` (atlas_stride bytes per row).  *atlas_w, *atlas_h: its size; origins_xy[2 i], [2 i + 1]: where
+ * frame i's gray image lies, -1 -1 when it is not in this atlas.  A frame's slot is its width rounded up to 4 columns; those pad
+ * columns and whatever no slot covers are 0 here (the detect calls never clear them).  atlas == NULL: nothing is packed, only the
+ * size and the origins are written — what a caller needs to allocate `atlas`; otherwise atlas_stride >= *atlas_w, or VJ_ERR_ARG.
+ * n_frames == 0, or no frame that fits: VJ_OK with a 0 x 0 atlas.                                                               */
+int  vj_pack_frames(vj_env* e, const vj_image* frames, int n_frames, uint64_t atlas_px, uint8_t* atlas, int atlas_stride,
+                    int* atlas_w, int* atlas_h, int32_t* origins_xy);
+/* What the environment's last vj_detect_mixed / vj_detect_opencv_mixed call did (zeroed when a call begins). */
+typedef struct vj_mixed_info {
+    int32_t  atlases;             /* atlases made ...                                                                              */
+    int32_t  own_calls;           /* ... and batched calls on original frames (one per group sent there)                           */
+    uint32_t atlas_w, atlas_h;    /* the size of the largest atlas (by pixels)                                                     */
+    uint64_t frames;              /* frames of the call                                                                            */
+    uint64_t frames_atlas;        /* ... that ran on atlases                                                                       */
+    uint64_t frames_own_calls;    /* ... that the own_call_px rule, or a flag, sent through calls of their own                     */
+    uint64_t frames_oversized;    /* ... too large for an empty atlas (they take calls of their own too)                          */
+    uint64_t windows;             /* grid positions of the atlas passes                                                            */
+    float    pack_ms;             /* device time of the pack launches (events), summed over atlases                               */
+    int32_t  reserved;
+} vj_mixed_info;
+int  vj_mixed_info_get(const vj_env* e, vj_mixed_info* out);   /* a null argument: VJ_ERR_ARG */
 
 /* ------------------------------------------------------------ frame streams */
 /* Video-style use (the demo's per-frame loop, main.cpp:104-125): batches of host frames are uploaded into
