@@ -39,6 +39,7 @@ VJ_FLAG_CV_SCALE_IMAGE = 1 << 7      # OpenCV profile: CV_HAAR_SCALE_IMAGE (the 
 VJ_FLAG_CV_FIND_BIGGEST = 1 << 8     # OpenCV profile: CV_HAAR_FIND_BIGGEST_OBJECT (largest window first, one grouped object per frame, then its surroundings only)
 VJ_FLAG_CV_ROUGH_SEARCH = 1 << 9     # OpenCV profile: CV_HAAR_DO_ROUGH_SEARCH (with find-biggest: the search stops at 0.6 of the object's size, not 0.4)
 VJ_FLAG_CV_CHAIN_DEVICE = 1 << 10    # detect_opencv_chain only (flags of the first cascade): regions and units are built on the device, one wait per sub-batch
+VJ_FLAG_EQUALIZE_HIST = 1 << 11      # cv::equalizeHist on every frame, on the device, in front of detect / detect_opencv / detect_opencv_roc / the mixed calls; refused elsewhere
 
 # cvHaarDetectObjects' flags (tempcv.hpp:127-130).  cvHaarDetectObjects below takes only CV_HAAR_DO_CANNY_PRUNING in its `flags`
 # argument and refuses the other three values there; their paths are reached through `vj_flags` (VJ_FLAG_CV_SCALE_IMAGE,
@@ -241,6 +242,7 @@ _SIGNATURES = {
     "vj_integral_tilted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "vj_grayscale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vj_canny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "vj_equalize_hist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vj_resize_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "vj_host_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "vj_host_free": (None, [C.c_void_p, C.c_void_p]),
@@ -563,6 +565,16 @@ class Environment:
         e = np.empty((imgs[0].height, imgs[0].width), np.uint8)
         _check(load_library().vj_canny(self._h, C.byref(imgs[0]), e.ctypes.data, e.strides[0]), "vj_canny")
         return e
+
+    def equalize_hist(self, img, color: bool = False) -> np.ndarray:
+        """vj_equalize_hist: cv::equalizeHist of the 8-bit gray image on the device, the image VJ_FLAG_EQUALIZE_HIST puts in front
+        of a detect call; returns a (h, w) uint8 array.  img as for canny."""
+        imgs, n, keep = self._images(img, color)
+        if n != 1:
+            raise ValueError("equalize_hist takes one image")
+        d = np.empty((imgs[0].height, imgs[0].width), np.uint8)
+        _check(load_library().vj_equalize_hist(self._h, C.byref(imgs[0]), d.ctypes.data, d.strides[0]), "vj_equalize_hist")
+        return d
 
     def resize_linear(self, img, dst_w: int, dst_h: int, color: bool = False) -> np.ndarray:
         """vj_resize_linear: cvResize(gray, dst, CV_INTER_LINEAR) of the 8-bit gray image on the device, one level of the

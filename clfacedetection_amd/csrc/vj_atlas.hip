@@ -13,13 +13,19 @@
 //   stores  always one aligned dword: slot origins, the atlas pitch and a thread's column are multiples of 4, and a slot is
 //           align4(w) wide, so a row's last dword — its pixels beyond w are written as 0 — stays inside the slot.
 // No LDS, no scratch; bound by the byte traffic.
+//
+// EQ (VJ_FLAG_EQUALIZE_HIST): the second instantiation sends the four pixels through the frame's look-up table
+// (equalize_lut, vj_equalize.hip) before the store — the table staged in LDS, one byte per thread, one barrier that every thread
+// reaches before the first return.  atlas_pack<false> is the kernel as it was, instruction for instruction.
 #include <hip/hip_runtime.h>
 #include "vj_atlas_units.hpp"
 #include "vj_devutil.hpp"
 
 namespace vj {
 
+template <bool EQ>
 __global__ __launch_bounds__(256) void atlas_pack(AtlasPackArgs a) {
+    __shared__ uint8_t lut[256];   // (EQ only: never touched, and not allocated, otherwise)
     kptr<AtlasFrameDev> frames = as_k(a.frames);
     const uint32_t unit = blockIdx.x;
     uint32_t lo = 0, hi = a.n_frames;   // the last frame whose first unit is <= unit
@@ -27,6 +33,10 @@ __global__ __launch_bounds__(256) void atlas_pack(AtlasPackArgs a) {
         const uint32_t mid = (lo + hi) >> 1;
         if (frames[mid].unit_first <= unit) lo = mid;
         else hi = mid;
+    }
+    if constexpr (EQ) {
+        lut[threadIdx.x] = a.lut[(size_t)lo * 256u + threadIdx.x];
+        __syncthreads();
     }
     const uint32_t w = frames[lo].w, h = frames[lo].h, ox = frames[lo].ox, oy = frames[lo].oy;
     const uint32_t blocks_per_row = (w + ATLAS_BLOCK_W - 1u) / ATLAS_BLOCK_W;
@@ -37,14 +47,16 @@ __global__ __launch_bounds__(256) void atlas_pack(AtlasPackArgs a) {
     if (dy >= h || dx >= w || ((ox | a.atlas_pitch) & 3u) != 0u) return;
     if (ox + dx + 4u > a.atlas_pitch || ox + dx >= a.atlas_w || oy + dy >= a.atlas_h) return;
     const uint8_t* row = frames[lo].src + (size_t)dy * frames[lo].stride;
-    const uint32_t v = load_gray4(row, dx, w, frames[lo].channels);
+    uint32_t v = load_gray4(row, dx, w, frames[lo].channels);
+    if constexpr (EQ) v = lut_gray4(lut, v);
     *reinterpret_cast<uint32_t*>(a.atlas + (size_t)(oy + dy) * a.atlas_pitch + ox + dx) = v;
 }
 
 int launch_atlas_pack(const AtlasPackArgs& a, void* stream_) {
     if (a.n_units == 0u || a.n_frames == 0u) return 0;
     dim3 g(a.n_units), b(256);
-    hipLaunchKernelGGL(atlas_pack, g, b, 0, (hipStream_t)stream_, a);
+    if (a.lut) hipLaunchKernelGGL(atlas_pack<true>, g, b, 0, (hipStream_t)stream_, a);
+    else hipLaunchKernelGGL(atlas_pack<false>, g, b, 0, (hipStream_t)stream_, a);
     return (int)hipGetLastError();
 }
 

@@ -815,7 +815,7 @@ static CvPruneArgs prune_args(vj_env* e, const CvPlan* pl, const CvArgs& a, int 
 // step 5 on the host: a frame's candidates in the walk's order, maxRect behind the scale that found it, groupRectangles, the
 // first group of strictly greatest area.
 static int detect_biggest(vj_env* e, const vj_cascade* c, CvPlan* pl, const vj_image* frames, int n_frames, int W, int H, int CH,
-                          const vj_cv_params* p, vj_result* out) {
+                          const vj_cv_params* p, bool equalize, vj_result* out) {
     const std::vector<CvScaleDev>& scales = pl->scales;
     const StageProgram& prog = pl->prog;
     const uint32_t stride = (uint32_t)W + 1u;
@@ -847,8 +847,10 @@ static int detect_biggest(vj_env* e, const vj_cascade* c, CvPlan* pl, const vj_i
         int gray_stride;
         if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
         HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
-        if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
-        if (pl->has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
+        int gray_ch = CH;
+        if (equalize && (rc = enqueue_equalize(e, nullptr, &d_gray, &gray_frame_bytes, &gray_stride, &gray_ch, W, H, nf))) return rc;
+        if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, gray_ch))) return rc;
+        if (pl->has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, gray_ch))) return rc;
         HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
         const size_t state_bytes = (size_t)nf * sizeof(CvBigState), big_bytes = state_bytes + (size_t)nf * sizeof(uint32_t);
         if ((rc = e->d_cv_big.ensure(big_bytes))) return rc;
@@ -1125,6 +1127,11 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         set_error("scale_factor must be > 1");
         return VJ_ERR_ARG;
     }
+    // VJ_FLAG_EQUALIZE_HIST is read here and nowhere else: the plan, its key and the kernels see the parameters without it
+    const bool equalize = (p->flags & VJ_FLAG_EQUALIZE_HIST) != 0u;
+    vj_cv_params p_plain = *p;
+    p_plain.flags &= ~(uint32_t)VJ_FLAG_EQUALIZE_HIST;
+    p = &p_plain;
     const int W = frames[0].width, H = frames[0].height;
     if (W <= 0 || H <= 0 || W >= 65535 || H >= 65535) return VJ_ERR_ARG;
     if ((uint64_t)(W + 1) * (uint64_t)(H + 3) >= (1ull << 30)) {   // the limit of vj_detect (check_frames): 32-bit byte offsets
@@ -1142,7 +1149,7 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
     CvPlan* pl;
     int rc = get_cv_plan(e, c, W, H, p, n_frames, &pl, roc);
     if (rc) return rc;
-    if (pl->find_biggest) return detect_biggest(e, c, pl, frames, n_frames, W, H, CH, p, out);
+    if (pl->find_biggest) return detect_biggest(e, c, pl, frames, n_frames, W, H, CH, p, equalize, out);
     const std::vector<CvScaleDev>& scales = pl->scales;
     const StageProgram& prog = pl->prog;
     const bool trees = pl->trees, is_tree = pl->is_tree, has_tilted = pl->has_tilted;
@@ -1193,8 +1200,10 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         int gray_ch = CH;
         if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
         HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
+        // VJ_FLAG_EQUALIZE_HIST: from here on the frames are the lane's equalized gray batch
+        if (equalize && (rc = enqueue_equalize(e, nullptr, &d_gray, &gray_frame_bytes, &gray_stride, &gray_ch, W, H, nf))) return rc;
         if (si) {   // every level of every frame; from here on the "frames" are the gray canvases
-            if ((rc = enqueue_pyramid(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH, pl->d_pyr_levels.p, pl->d_pyr_taps.p,
+            if ((rc = enqueue_pyramid(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, gray_ch, pl->d_pyr_levels.p, pl->d_pyr_taps.p,
                                       pl->n_pyr_levels, pl->n_pyr_units, pl->canvas_w, pl->canvas_h, pl->canvas_pitch)))
                 return rc;
             d_gray = (const uint8_t*)e->d_pyr.p;
@@ -1204,7 +1213,7 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         }
         if (pl->prune) {   // the edge maps and their integral
             uint32_t pitch = 0;
-            if ((rc = enqueue_canny(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH, &pitch))) return rc;
+            if ((rc = enqueue_canny(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, gray_ch, &pitch))) return rc;
             if ((rc = enqueue_edge_integral(e, pitch, W, H, nf))) return rc;
         }
         if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, IW, IH, nf, gray_ch))) return rc;
@@ -2436,7 +2445,7 @@ int vj_detect_opencv_roc(vj_env* e, const vj_cascade* c, const vj_image* frames,
     q.min_h = p->min_h;
     q.scale_factor = p->scale_factor;
     q.min_neighbors = p->min_neighbors;
-    q.flags = p->flags & (VJ_FLAG_COUNTERS | VJ_FLAG_CV_SCALE_IMAGE);   // (canny pruning and rough search: not read by this branch)
+    q.flags = p->flags & (VJ_FLAG_COUNTERS | VJ_FLAG_CV_SCALE_IMAGE | VJ_FLAG_EQUALIZE_HIST);   // (canny pruning and rough search: not read by this branch)
     std::vector<int32_t> levels;
     std::vector<double> weights;
     const bool whole = p->max_w == 0 || p->max_h == 0;   // maxSize with a zero member is the frame (:1230-1234)
@@ -2475,6 +2484,7 @@ int vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames
                           const vj_cv_params* p, vj_result* out) {
     if (!e || !c || !p || !out || n_frames < 0 || n_rois < 0 || (n_rois > 0 && (!frames || !rois))) return VJ_ERR_ARG;
     memset(out, 0, sizeof(*out));
+    if (refuse_equalize(p->flags, "vj_detect_opencv_rois")) return VJ_ERR_UNSUPPORTED;
     if (!(p->scale_factor > 1.0)) {
         set_error("scale_factor must be > 1");
         return VJ_ERR_ARG;
@@ -2582,6 +2592,7 @@ int vj_detect_opencv_chain(vj_env* e, const vj_cascade* first, const vj_cascade*
         return VJ_ERR_ARG;
     memset(out_first, 0, sizeof(*out_first));
     memset(out_second, 0, sizeof(*out_second));
+    if (refuse_equalize(p_first->flags | p_second->flags, "vj_detect_opencv_chain")) return VJ_ERR_UNSUPPORTED;
     if (n_frames == 0) return VJ_OK;
     if (!(p_first->scale_factor > 1.0) || !(p_second->scale_factor > 1.0)) {
         set_error("scale_factor must be > 1");

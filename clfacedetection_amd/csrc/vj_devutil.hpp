@@ -80,6 +80,12 @@ __device__ __forceinline__ uint32_t load_gray4(const uint8_t* row, uint32_t x, u
     return v;
 }
 
+// VJ_FLAG_EQUALIZE_HIST: four packed pixels through a frame's look-up table in LDS (vj_equalize.hip, vj_atlas.hip).  Pixels beyond
+// the row come as 0 from load_gray4 and stay 0: lut[0] is 0 in every table equalize_lut writes.
+__device__ __forceinline__ uint32_t lut_gray4(const uint8_t* lut, uint32_t v) {
+    return (uint32_t)lut[v & 0xffu] | (uint32_t)lut[(v >> 8) & 0xffu] << 8 | (uint32_t)lut[(v >> 16) & 0xffu] << 16 | (uint32_t)lut[v >> 24] << 24;
+}
+
 // CV_HAAR_DO_CANNY_PRUNING's test (tempcv.cpp:1147-1158): the edge map's sum s and the frame's own sum sq (pq points at `sum`)
 // over the pruning rectangle, four-corner differences in int; pruned iff s < 100 || sq < 20
 __device__ __forceinline__ bool cv_pruned(rsrc_t eimg, rsrc_t img, uint32_t off, uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3) {

@@ -23,6 +23,7 @@
 
 #include "vj_env_internal.hpp"
 #include "vj_grid_parts.hpp"
+#include "vj_atlas_units.hpp"
 
 using namespace vj;
 
@@ -965,7 +966,7 @@ int Lane::create() {
 }
 
 void Lane::destroy() {
-    for (DevBuf* b : {&d_gray, &d_counts, &d_det}) b->release();
+    for (DevBuf* b : {&d_gray, &d_counts, &d_det, &d_eq_frames, &d_eq_hist, &d_eq_lut, &d_eq_gray}) b->release();
     if (h_pinned) (void)hipHostFree(h_pinned);
     if (h_stage) (void)hipHostFree(h_stage);
     h_pinned = h_stage = nullptr;
@@ -1185,6 +1186,75 @@ int stage_frames(vj_env* e, const vj_image* frames, int n, int W, int H, const u
     return VJ_OK;
 }
 
+int refuse_equalize(uint32_t flags, const char* entry_point) {
+    if ((flags & VJ_FLAG_EQUALIZE_HIST) == 0u) return VJ_OK;
+    set_error("%s does not take VJ_FLAG_EQUALIZE_HIST: equalize the frames with vj_equalize_hist first", entry_point);
+    return VJ_ERR_UNSUPPORTED;
+}
+
+int enqueue_equalize_tables(vj_env* e, Lane* lane, const void* d_frame_recs, uint32_t n_frames, uint32_t n_hist_units, const uint8_t** lut) {
+    int rc;
+    if ((rc = lane->d_eq_hist.ensure((size_t)n_frames * 256u * sizeof(uint32_t)))) return rc;
+    if ((rc = lane->d_eq_lut.ensure((size_t)n_frames * 256u))) return rc;
+    HIP_TRY(hipMemsetAsync(lane->d_eq_hist.p, 0, (size_t)n_frames * 256u * sizeof(uint32_t), e->stream));
+    EqualizeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.frames = (const AtlasFrameDev*)d_frame_recs;
+    a.n_frames = n_frames;
+    a.n_hist_units = n_hist_units;
+    a.hist = (uint32_t*)lane->d_eq_hist.p;
+    a.lut = (uint8_t*)lane->d_eq_lut.p;
+    int hrc = launch_equalize_hist(a, e->stream);
+    if (!hrc) hrc = launch_equalize_lut(a, e->stream);
+    if (hrc) {
+        set_error("equalization launch failed: %s", hipGetErrorString((hipError_t)hrc));
+        return VJ_ERR_HIP;
+    }
+    *lut = (const uint8_t*)lane->d_eq_lut.p;
+    return VJ_OK;
+}
+
+int enqueue_equalize(vj_env* e, Lane* lane, const uint8_t** d_gray, size_t* frame_bytes, int* stride, int* channels, int W, int H, int frames) {
+    if (!lane) lane = &e->lane0;
+    int rc;
+    const uint32_t pitch = ((uint32_t)W + 3u) & ~3u;
+    const uint64_t units_per_frame = (uint64_t)(((uint32_t)W + ATLAS_BLOCK_W - 1u) / ATLAS_BLOCK_W) * (((uint32_t)H + ATLAS_BLOCK_H - 1u) / ATLAS_BLOCK_H);
+    if (units_per_frame * (uint64_t)frames > 0x7fffffffull) {
+        set_error("VJ_FLAG_EQUALIZE_HIST: a sub-batch of %d frames holds more work units than a 32-bit index holds", frames);
+        return VJ_ERR_LIMIT;
+    }
+    std::vector<AtlasFrameDev> recs((size_t)frames);
+    for (int i = 0; i < frames; ++i)
+        recs[(size_t)i] = AtlasFrameDev{*d_gray + (size_t)i * *frame_bytes, (uint32_t)*stride, (uint32_t)*channels, (uint32_t)W, (uint32_t)H, 0u, 0u,
+                                        (uint32_t)(units_per_frame * (uint64_t)i), eq_hist_units((uint32_t)H) * (uint32_t)i};
+    if ((rc = lane->d_eq_frames.ensure(recs.size() * sizeof(AtlasFrameDev)))) return rc;
+    if ((rc = lane->d_eq_gray.ensure((size_t)pitch * (size_t)H * (size_t)frames))) return rc;
+    // (pageable memory: the runtime has taken the records when the call returns)
+    HIP_TRY(hipMemcpyAsync(lane->d_eq_frames.p, recs.data(), recs.size() * sizeof(AtlasFrameDev), hipMemcpyHostToDevice, e->stream));
+    const uint8_t* lut;
+    if ((rc = enqueue_equalize_tables(e, lane, lane->d_eq_frames.p, (uint32_t)frames, eq_hist_units((uint32_t)H) * (uint32_t)frames, &lut))) return rc;
+    EqualizeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.frames = (const AtlasFrameDev*)lane->d_eq_frames.p;
+    a.n_frames = (uint32_t)frames;
+    a.n_units = (uint32_t)(units_per_frame * (uint64_t)frames);
+    a.lut = (uint8_t*)lane->d_eq_lut.p;
+    a.dst = (uint8_t*)lane->d_eq_gray.p;
+    a.dst_pitch = pitch;
+    a.dst_h = (uint32_t)H;
+    a.dst_frame_bytes = (uint64_t)pitch * (uint64_t)H;
+    const int hrc = launch_equalize_apply(a, e->stream);
+    if (hrc) {
+        set_error("equalization launch failed: %s", hipGetErrorString((hipError_t)hrc));
+        return VJ_ERR_HIP;
+    }
+    *d_gray = (const uint8_t*)lane->d_eq_gray.p;
+    *frame_bytes = (size_t)pitch * (size_t)H;
+    *stride = (int)pitch;
+    *channels = 1;
+    return VJ_OK;
+}
+
 struct RawDet {
     int frame;
     uint32_t slot, x, y;
@@ -1215,9 +1285,9 @@ static_assert(CountsLayout::roi_tickets_begin + 8u <= CountsLayout::tile_tickets
 // Upload (or adopt) the frames of one batch and enqueue its integral images.  `copy_stream` != null: the upload runs
 // on that stream and the integral waits for it (vj_stream); else everything is ordered on the environment's stream.
 static int enqueue_prepare(vj_env* e, Lane* L, Plan* pl, const vj_image* frames, int nf, int W, int H, bool fixed_queue_layout,
-                           hipStream_t copy_stream) {
+                           hipStream_t copy_stream, bool equalize = false) {
     int rc;
-    const int channels = image_channels(frames[0]);
+    int channels = image_channels(frames[0]);
     if ((rc = ensure_image_buffers(e, W, H, nf, true, channels, L))) return rc;
     uint64_t q_entries = 0;
     if (!fixed_queue_layout) {
@@ -1239,11 +1309,13 @@ static int enqueue_prepare(vj_env* e, Lane* L, Plan* pl, const vj_image* frames,
         HIP_TRY(hipEventRecord(L->upload_done, copy_stream));
         HIP_TRY(hipStreamWaitEvent(e->stream, L->upload_done, 0));
     }
+    HIP_TRY(hipEventRecord(L->ev[0], e->stream));
+    // VJ_FLAG_EQUALIZE_HIST: from here on the batch is the lane's equalized gray frames (a redo integrates those again)
+    if (equalize && (rc = enqueue_equalize(e, L, &d_gray, &gray_frame_bytes, &gray_stride, &channels, W, H, nf))) return rc;
     L->src_gray = d_gray;
     L->src_frame_bytes = gray_frame_bytes;
     L->src_stride = gray_stride;
     L->src_channels = channels;
-    HIP_TRY(hipEventRecord(L->ev[0], e->stream));
     if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, channels))) return rc;
     HIP_TRY(hipEventRecord(L->ev[1], e->stream));
     HIP_TRY(hipEventRecord(L->integral_done, e->stream));   // the lane's frame buffer may be overwritten from here on
@@ -1657,10 +1729,10 @@ static int finish_batch(vj_env* e, Lane* L, Plan* pl, int f0, int W, int H, cons
 
 // One sub-batch: frames [f0, f0+nf).  Appends decoded detections to `dets`.
 static int detect_subbatch(vj_env* e, Plan* pl, const vj_image* frames, int f0, int nf, int W, int H,
-                           const vj_params& p, std::vector<RawDet>* dets, vj_counters* ctr, vj_timing* tm) {
+                           const vj_params& p, bool equalize, std::vector<RawDet>* dets, vj_counters* ctr, vj_timing* tm) {
     int rc;
     Lane* L = &e->lane0;
-    if ((rc = enqueue_prepare(e, L, pl, frames + f0, nf, W, H, false, nullptr))) return rc;
+    if ((rc = enqueue_prepare(e, L, pl, frames + f0, nf, W, H, false, nullptr, equalize))) return rc;
     if ((rc = enqueue_cascade(e, L, pl, W, H, p))) return rc;
     return finish_batch(e, L, pl, f0, W, H, p, dets, ctr, tm);
 }
@@ -2516,6 +2588,34 @@ int vj_grayscale(vj_env* e, const vj_image* image, uint8_t* gray, int gray_strid
     return VJ_OK;
 }
 
+int vj_equalize_hist(vj_env* e, const vj_image* image, uint8_t* dst, int dst_stride) {
+    if (!e || !image || !image->data || !dst || dst_stride < image->width) return VJ_ERR_ARG;
+    int ch, rc;
+    if ((rc = check_single_image(image, &ch))) return rc;
+    const int w = image->width, h = image->height;
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = ensure_image_buffers(e, w, h, 1, true, ch))) return rc;
+    const uint8_t* d_src;
+    size_t fb;
+    int gs;
+    if ((rc = stage_frames(e, image, 1, w, h, &d_src, &fb, &gs))) return rc;
+    Lane* L = &e->lane0;
+    if ((rc = enqueue_equalize(e, L, &d_src, &fb, &gs, &ch, w, h, 1))) return rc;
+    // one block into page-locked memory, the rows from there (as vj_grayscale returns a strided image)
+    const size_t pitch = (size_t)gs, need = pitch * (size_t)h;
+    if (L->h_stage_bytes < need) {
+        if (L->h_stage) (void)hipHostFree(L->h_stage);
+        L->h_stage = nullptr;
+        L->h_stage_bytes = 0;
+        HIP_TRY(hipHostMalloc(&L->h_stage, need, hipHostMallocDefault));
+        L->h_stage_bytes = need;
+    }
+    HIP_TRY(hipMemcpyAsync(L->h_stage, d_src, need, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int y = 0; y < h; ++y) memcpy(dst + (size_t)y * (size_t)dst_stride, (const uint8_t*)L->h_stage + (size_t)y * pitch, (size_t)w);
+    return VJ_OK;
+}
+
 int vj_host_alloc(vj_env* e, size_t bytes, void** out) {
     if (!e || !out || bytes == 0) return VJ_ERR_ARG;
     *out = nullptr;
@@ -2546,6 +2646,11 @@ int vj_detect(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_fram
     if (!e || !c || !p || !out || n_frames < 0 || (n_frames > 0 && !frames)) return VJ_ERR_ARG;
     memset(out, 0, sizeof(*out));
     if (n_frames == 0) return VJ_OK;
+    // VJ_FLAG_EQUALIZE_HIST is read here and nowhere else: plans, balance entries and kernels see the parameters without it
+    const bool equalize = (p->flags & VJ_FLAG_EQUALIZE_HIST) != 0u;
+    vj_params q = *p;
+    q.flags &= ~(uint32_t)VJ_FLAG_EQUALIZE_HIST;
+    p = &q;
     int rc = check_params(*p);
     if (rc) return rc;
     int W, H, CH;
@@ -2565,7 +2670,7 @@ int vj_detect(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_fram
     std::vector<RawDet> dets;
     for (int f0 = 0; f0 < n_frames; f0 += (int)max_frames) {
         const int nf = (int)std::min<uint64_t>(max_frames, (uint64_t)(n_frames - f0));
-        rc = detect_subbatch(e, pl, frames, f0, nf, W, H, *p, &dets, &out->counters, &out->timing);
+        rc = detect_subbatch(e, pl, frames, f0, nf, W, H, *p, equalize, &dets, &out->counters, &out->timing);
         if (rc) return rc;
     }
     // feedback for the chain balance: only the timed (uncounted) kernel variants.  A plan none of whose scales can run on tiles
@@ -2594,6 +2699,7 @@ int vj_detect_rois(vj_env* e, const vj_cascade* c, const vj_image* frames, int n
                    const vj_params* p, vj_result* out) {
     if (!e || !c || !p || !out || n_frames < 0 || n_rois < 0 || (n_rois > 0 && (!frames || !rois))) return VJ_ERR_ARG;
     memset(out, 0, sizeof(*out));
+    if (refuse_equalize(p->flags, "vj_detect_rois")) return VJ_ERR_UNSUPPORTED;
     {
         const int prc = check_params(*p);
         if (prc) return prc;
@@ -2676,6 +2782,7 @@ int vj_detect_chain(vj_env* e, const vj_cascade* first, const vj_cascade* second
         return VJ_ERR_ARG;
     memset(out_first, 0, sizeof(*out_first));
     memset(out_second, 0, sizeof(*out_second));
+    if (refuse_equalize(p_first->flags | p_second->flags, "vj_detect_chain")) return VJ_ERR_UNSUPPORTED;
     if (n_frames == 0) return VJ_OK;
     for (const vj_params* pp : {p_first, p_second}) {
         const int prc = check_params(*pp);
@@ -2982,6 +3089,7 @@ int vj_stream_create(vj_env* e, const vj_cascade* c, int width, int height, int 
     if (!e || !c || !p || width <= 0 || height <= 0 || max_batch <= 0) return VJ_ERR_ARG;
     const int CH = channels <= 1 ? 1 : channels;
     if (CH != 1 && CH != 3 && CH != 4) return VJ_ERR_ARG;
+    if (refuse_equalize(p->flags, "vj_stream_create")) return VJ_ERR_UNSUPPORTED;
     if (check_params(*p)) return VJ_ERR_ARG;
     if ((uint64_t)(width + 1) * (uint64_t)(height + 3) >= (1ull << 30)) {
         set_error("image too large");

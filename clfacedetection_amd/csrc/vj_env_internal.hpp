@@ -200,6 +200,9 @@ namespace vj {
 
 struct Lane {
     DevBuf d_gray, d_counts, d_det;
+    // VJ_FLAG_EQUALIZE_HIST (vj_equalize.hip): the sub-batch's frame records, histograms and look-up tables, and
+    // its equalized gray frames at the device's pitch (each grows and is reused)
+    DevBuf d_eq_frames, d_eq_hist, d_eq_lut, d_eq_gray;
     uint32_t det_cap = 0;
     void* h_pinned = nullptr;        // counters block + the first detections, read back asynchronously
     size_t h_pinned_bytes = 0;
@@ -442,6 +445,15 @@ int enqueue_integral(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int s
 int stage_frames(vj_env* e, const vj_image* frames, int n, int W, int H, const uint8_t** d_ptr, size_t* frame_bytes,
                  int* stride, Lane* lane = nullptr, hipStream_t copy_stream = nullptr);
 int enqueue_tilted(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int stride, int W, int H, int frames, int channels);
+// VJ_FLAG_EQUALIZE_HIST, right after stage_frames: the `frames` staged frames (what stage_frames returned) equalized into the lane's
+// gray batch — one memset and three launches on the environment's stream, nothing waited for — and *d_gray, *frame_bytes, *stride,
+// *channels (1 from here on) name that batch.
+int enqueue_equalize(vj_env* e, Lane* lane, const uint8_t** d_gray, size_t* frame_bytes, int* stride, int* channels, int W, int H, int frames);
+// ... the histograms and tables alone, for frame records already on the device (hist_first filled in): what an atlas needs before
+// atlas_pack<true>.  *lut: the tables, 256 bytes per frame.
+int enqueue_equalize_tables(vj_env* e, Lane* lane, const void* d_frame_recs, uint32_t n_frames, uint32_t n_hist_units, const uint8_t** lut);
+// What an entry point that does not equalize answers to the flag: VJ_ERR_UNSUPPORTED, vj_last_error names both; else VJ_OK.
+int refuse_equalize(uint32_t flags, const char* entry_point);
 
 // Room for one more entry in a cache of the run-windows calls (vj_run_windows_opencv, vj_run_windows): the least recently used go
 // first, but never an entry of the call in progress (last_used >= call_tick) — a call that names more scales than plan_cache_max

@@ -15,7 +15,9 @@ namespace {
 // Packs the atlas `pl` of `frames` into e->d_atlas: one copy brings the frame records and the atlas's host frames (gathered at a
 // 4-byte pitch in the lane's page-locked staging buffer, as stage_frames gathers small frames), device-resident frames are read
 // where they lie; one launch.  Events e->atlas_ev[0], [1] lie around the launch.  Nothing is waited for.
-int enqueue_atlas_pack(vj_env* e, const vj_image* frames, const AtlasPlan& pl, bool clear) {
+// equalize (VJ_FLAG_EQUALIZE_HIST): the frames' histograms and look-up tables first, from the same records, and the
+// pack applies each frame's table before its store — no second gray copy; the events lie around all of it.
+int enqueue_atlas_pack(vj_env* e, const vj_image* frames, const AtlasPlan& pl, bool clear, bool equalize = false) {
     int rc;
     const size_t n = pl.slots.size();
     const size_t atlas_bytes = (size_t)pl.pitch * (size_t)pl.h;
@@ -38,6 +40,7 @@ int enqueue_atlas_pack(vj_env* e, const vj_image* frames, const AtlasPlan& pl, b
     if ((rc = e->d_atlas_src.ensure(bytes))) return rc;
     AtlasFrameDev* recs = (AtlasFrameDev*)L->h_stage;
     size_t at = rec_bytes;
+    uint32_t hist_units = 0;
     for (size_t i = 0; i < n; ++i) {
         const AtlasSlot& s = pl.slots[i];
         const vj_image& f = frames[s.frame];
@@ -48,7 +51,8 @@ int enqueue_atlas_pack(vj_env* e, const vj_image* frames, const AtlasPlan& pl, b
             return VJ_ERR_HIP;
         }
         AtlasFrameDev& d = recs[i];
-        d = AtlasFrameDev{f.data, (uint32_t)f.stride, ch, s.w, s.h, s.ox, s.oy, s.unit_first, 0u};
+        d = AtlasFrameDev{f.data, (uint32_t)f.stride, ch, s.w, s.h, s.ox, s.oy, s.unit_first, equalize ? hist_units : 0u};
+        hist_units += eq_hist_units(s.h);   // (an atlas is lower than 65535 rows)
         if (!f.on_device) {
             const size_t row_bytes = (size_t)s.w * ch, pitch = (row_bytes + 3u) & ~(size_t)3;
             uint8_t* st = (uint8_t*)L->h_stage + at;
@@ -59,8 +63,9 @@ int enqueue_atlas_pack(vj_env* e, const vj_image* frames, const AtlasPlan& pl, b
         }
     }
     HIP_TRY(hipMemcpyAsync(e->d_atlas_src.p, L->h_stage, bytes, hipMemcpyHostToDevice, e->stream));
-    AtlasPackArgs a{(const AtlasFrameDev*)e->d_atlas_src.p, (uint32_t)n, pl.n_units, (uint8_t*)e->d_atlas.p, pl.pitch, pl.w, pl.h};
+    AtlasPackArgs a{(const AtlasFrameDev*)e->d_atlas_src.p, (uint32_t)n, pl.n_units, (uint8_t*)e->d_atlas.p, pl.pitch, pl.w, pl.h, nullptr};
     HIP_TRY(hipEventRecord(e->atlas_ev[0], e->stream));
+    if (equalize && (rc = enqueue_equalize_tables(e, L, e->d_atlas_src.p, (uint32_t)n, hist_units, &a.lut))) return rc;
     const int hrc = launch_atlas_pack(a, e->stream);
     if (hrc) {
         set_error("atlas pack launch failed: %s", hipGetErrorString((hipError_t)hrc));
@@ -77,7 +82,8 @@ struct MixedRun {
     std::function<int(const vj_image*, const vj_roi*, int, vj_result*, uint64_t*)> rois;
 };
 
-int detect_mixed(vj_env* e, const vj_image* frames, int n_frames, const vj_mixed_opts* opts, bool all_own, const MixedRun& run, vj_result* out) {
+int detect_mixed(vj_env* e, const vj_image* frames, int n_frames, const vj_mixed_opts* opts, bool all_own, bool equalize, const MixedRun& run,
+                 vj_result* out) {
     e->mixed_info = vj_mixed_info{};
     vj_mixed_info& info = e->mixed_info;
     std::vector<AtlasSize> sizes;
@@ -102,7 +108,7 @@ int detect_mixed(vj_env* e, const vj_image* frames, int n_frames, const vj_mixed
             big.push_back(route.packed[pos]);
             continue;
         }
-        if ((rc = enqueue_atlas_pack(e, frames, pl, false))) return rc;
+        if ((rc = enqueue_atlas_pack(e, frames, pl, false, equalize))) return rc;
         rois.clear();
         idx.clear();
         for (const AtlasSlot& s : pl.slots) {
@@ -170,9 +176,10 @@ int vj_detect_opencv_mixed(vj_env* e, const vj_cascade* c, const vj_image* frame
     // Flags whose result needs the image alone (the edge map of a crop is not the crop of the edge map; the find-biggest search keeps
     // its state per image), and bits vj_detect_opencv does not know: every group on its original frames.  What the atlas route
     // passes on is the flag word as the region call's fast routes know it: rough search means nothing without find-biggest, canny
-    // pruning nothing under scale-image, the chain's bit nothing here.
+    // pruning nothing under scale-image, the chain's bit nothing here.  VJ_FLAG_EQUALIZE_HIST: an atlas is packed through its frames'
+    // look-up tables and the region call runs without the bit; a batched call of its own takes it as it is.
     const uint32_t known = VJ_FLAG_COUNTERS | VJ_FLAG_CV_CANNY_PRUNING | VJ_FLAG_CV_SCALE_IMAGE | VJ_FLAG_CV_FIND_BIGGEST | VJ_FLAG_CV_ROUGH_SEARCH |
-                           VJ_FLAG_CV_CHAIN_DEVICE;
+                           VJ_FLAG_CV_CHAIN_DEVICE | VJ_FLAG_EQUALIZE_HIST;
     const bool all_own = (p->flags & VJ_FLAG_CV_FIND_BIGGEST) != 0u || (p->flags & ~known) != 0u ||
                          ((p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u && (p->flags & VJ_FLAG_CV_SCALE_IMAGE) == 0u);
     vj_cv_params pr = *p;
@@ -184,7 +191,7 @@ int vj_detect_opencv_mixed(vj_env* e, const vj_cascade* c, const vj_image* frame
         *windows = e->cv_rois_info.windows;
         return rc;
     };
-    return detect_mixed(e, frames, n_frames, opts, all_own, run, out);
+    return detect_mixed(e, frames, n_frames, opts, all_own, (p->flags & VJ_FLAG_EQUALIZE_HIST) != 0u, run, out);
 }
 
 int vj_detect_mixed(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_params* p, const vj_mixed_opts* opts,
@@ -198,17 +205,20 @@ int vj_detect_mixed(vj_env* e, const vj_cascade* c, const vj_image* frames, int 
     // the skip modes walk the image's own window list: every group on its original frames (so does a call with the region pass
     // configured off, "rois_on_device" 0: vj_detect_rois would run one call per size on views of the atlas)
     const bool all_own = (p->flags & (VJ_FLAG_SKIP_LIST | VJ_FLAG_SKIP_ROW)) != 0u || !e->rois_on_device;
+    // VJ_FLAG_EQUALIZE_HIST: an atlas is packed through its frames' look-up tables and the region call runs without the bit
+    vj_params pr = *p;
+    pr.flags &= ~(uint32_t)VJ_FLAG_EQUALIZE_HIST;
     MixedRun run;
     run.batch = [&](const vj_image* f, int n, vj_result* part) { return vj_detect(e, c, f, n, p, part); };
     run.rois = [&](const vj_image* atlas, const vj_roi* rois, int n, vj_result* part, uint64_t* windows) {
         *windows = 0;
         for (int i = 0; i < n; ++i) {
             uint64_t w = 0;
-            if (vj_count_windows(c, rois[i].w, rois[i].h, p, &w) == VJ_OK) *windows += w;
+            if (vj_count_windows(c, rois[i].w, rois[i].h, &pr, &w) == VJ_OK) *windows += w;
         }
-        return vj_detect_rois(e, c, atlas, 1, rois, n, p, part);
+        return vj_detect_rois(e, c, atlas, 1, rois, n, &pr, part);
     };
-    return detect_mixed(e, frames, n_frames, opts, all_own, run, out);
+    return detect_mixed(e, frames, n_frames, opts, all_own, (p->flags & VJ_FLAG_EQUALIZE_HIST) != 0u, run, out);
 }
 
 int vj_pack_frames(vj_env* e, const vj_image* frames, int n_frames, uint64_t atlas_px, uint8_t* atlas, int atlas_stride, int* atlas_w,

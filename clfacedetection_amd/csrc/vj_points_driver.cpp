@@ -88,6 +88,7 @@ extern "C" {
 // runCascade + computeVariance on a caller's windows (clod.cpp:736-787, :418-446)
 int vj_run_windows(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const float* scales, int n_scales,
                    const vj_window* windows, uint32_t n_windows, int start_stage, uint32_t flags, vj_clod_window_result* out) {
+    if (refuse_equalize(flags, "vj_run_windows")) return VJ_ERR_UNSUPPORTED;
     return run_points<ClodPoints>(e, c, frames, n_frames, scales, n_scales, windows, n_windows, start_stage, flags, out);
 }
 

@@ -182,6 +182,19 @@ enum {
                                        it is ignored.  The results — rectangles, order, counters — are those of the call without
                                        it.  Not the default yet: what it gains is measured and recorded in DESIGN.md 4.10.
                                        Every other entry point ignores the bit; no plan is keyed on it.                         */
+    VJ_FLAG_EQUALIZE_HIST = 1u << 11,   /* cvtColor -> equalizeHist -> detect on the device: every frame is equalized
+                                       on its own — cv::equalizeHist on the gray image vj_grayscale returns, the image
+                                       vj_equalize_hist returns — right after it is staged, and the call goes on with the equalized
+                                       gray frames.  The result — rectangles, order, counters, reject levels — is that of the same
+                                       call without the flag on the images vj_equalize_hist returns for its frames.  Valid in
+                                       vj_params.flags, vj_cv_params.flags and vj_cv_roc_params.flags; honoured by vj_detect (skip
+                                       modes and grouping included), vj_detect_opencv (with every other flag of its profile),
+                                       vj_detect_opencv_roc, vj_detect_mixed and vj_detect_opencv_mixed (an atlas is packed through
+                                       its frames' look-up tables).  Every other entry point that takes frames and flags — the
+                                       region and chain calls of both profiles, vj_run_windows, vj_stream_create — returns
+                                       VJ_ERR_UNSUPPORTED and vj_last_error names the flag: none ignores it, an un-equalized result
+                                       would look plausible.  No plan or cache is keyed on it; vj_timing.integral_ms includes
+                                       the stage.                                                                               */
 };
 
 typedef struct vj_params {
@@ -344,6 +357,13 @@ int  vj_canny(vj_env* e, const struct vj_image* image, uint8_t* edges, int edges
  * exactly twice the destination in both directions; the definition is DESIGN.md §4.8.  dst_w x dst_h bytes, written to the HOST
  * buffer `dst` (dst_stride bytes per row).  Host or device input, 1 / 3 / 4 channels, any row stride.                            */
 int  vj_resize_linear(vj_env* e, const struct vj_image* image, int dst_w, int dst_h, uint8_t* dst, int dst_stride);
+/* cv::equalizeHist for 8-bit single-channel images (OpenCV imgproc/histogram.cpp, 2.4.4 .. 4.x) on the gray image vj_grayscale
+ * returns; what VJ_FLAG_EQUALIZE_HIST puts in front of a detect call.  hist[v] = pixels of value v; i = the lowest v with
+ * hist[v] != 0; an image of one value is returned unchanged; else scale = 255.f / (float)(w * h - hist[i]), lut[i] = 0 and, for
+ * k > i, lut[k] = saturate_cast<uchar>((float)(hist[i + 1] + .. + hist[k]) * scale) in binary32 with round-half-to-even;
+ * dst = lut[gray] (the definition is DESIGN.md §4.15).  w x h bytes, written to the HOST buffer `dst` (dst_stride bytes per row).
+ * Host or device input, 1 / 3 / 4 channels, any row stride.  Null arguments or dst_stride < width: VJ_ERR_ARG.                   */
+int  vj_equalize_hist(vj_env* e, const struct vj_image* image, uint8_t* dst, int dst_stride);
 typedef struct vj_image {
     const uint8_t* data;       /* 8-bit, interleaved channels                   */
     int32_t width, height;

@@ -1,8 +1,9 @@
 """Are the kernels of one .hip file the same instruction streams in two builds?  Takes two device assembly files of the same source
 at two commits (hipcc <build.py's FLAGS> --cuda-device-only -S file.hip -o x.s), demangles the kernel names, drops labels, directives
 and comments, and compares kernel by kernel.  A template that gained trailing defaulted parameters is matched by --strip-args N:
-that many trailing template arguments equal to `false` are dropped from the names of the second file.  Needs no GPU.
-    python tools/isa_compare.py before.s after.s [--strip-args 1]"""
+that many trailing template arguments equal to `false` are dropped from the names of the second file; a function that became a
+template is matched by --map 'NAME IN THE SECOND FILE=NAME IN THE FIRST' (demangled, as this tool prints them).  Needs no GPU.
+    python tools/isa_compare.py before.s after.s [--strip-args 1] [--map 'void vj::atlas_pack<false>(vj::AtlasPackArgs)=vj::atlas_pack(vj::AtlasPackArgs)']"""
 import argparse
 import re
 import subprocess
@@ -31,10 +32,14 @@ def main():
     ap.add_argument("before")
     ap.add_argument("after")
     ap.add_argument("--strip-args", type=int, default=0)
+    ap.add_argument("--map", action="append", default=[], metavar="AFTER=BEFORE")
     args = ap.parse_args()
     b, a = kernels(args.before), kernels(args.after)
     for _ in range(args.strip_args):
         a = {re.sub(r", false>\(", ">(", k): v for k, v in a.items()}
+    for m in args.map:
+        after, before = m.split("=", 1)
+        a[before] = a.pop(after)
     same = [k for k in b if a.get(k) == b[k]]
     for k in b:
         if k not in a:
