@@ -239,6 +239,7 @@ _SIGNATURES = {
     "vj_env_query": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t]),
     "vj_integral": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vj_integral_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vj_integral_batch_sq32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vj_integral_tilted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "vj_grayscale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "vj_canny": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
@@ -533,6 +534,17 @@ class Environment:
         h, w = g.shape
         _check(load_library().vj_integral(self._h, g.ctypes.data, w, h, g.strides[0], s.ctypes.data, q.ctypes.data),
                "vj_integral")
+        return s, q
+
+    def integral_sq32(self, frames, color: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """The integral images of a batch of equal-sized frames as detect() and FrameStream keep them on the device
+        (vj_integral_batch_sq32): sum and the squared sum mod 2^32, both uint32 (n, h + 1, w + 1).  frames as detect()."""
+        imgs, n, keep = self._images(frames, color)
+        if n == 0:
+            raise ValueError("integral_sq32 expects at least one frame")
+        s = np.empty((n, imgs[0].height + 1, imgs[0].width + 1), np.uint32)
+        q = np.empty_like(s)
+        _check(load_library().vj_integral_batch_sq32(self._h, imgs, n, s.ctypes.data, q.ctypes.data), "vj_integral_batch_sq32")
         return s, q
 
     def _one_image(self, img: np.ndarray):

@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 #include "vj_cv_roi_units.hpp"
+#include "vj_sq_strips.hpp"
 
 namespace vj {
 
@@ -56,8 +57,10 @@ struct ScaleDev {
     uint32_t grp_tail_first;
     uint32_t sq32;         // != 0: win_w * win_h <= SQ32_MAX_AREA — the squared sum of any window of this scale is below 2^32, so
                            // the tile passes combine the LOW dwords of its four sqsum corners (mod 2^32: exact)
+    uint32_t sq_strip;     // u32 layout of the squared integral (CascadeArgs::sq_u32), scales without sq32: the variance window in
+                           // strips of this many elements (sq_strip_rows(e_dw) * stride, vj_sq_strips.hpp); 0 with sq32
 };
-static_assert(sizeof(ScaleDev) == 152, "ScaleDev is 152 bytes");
+static_assert(sizeof(ScaleDev) == 156, "ScaleDev is 156 bytes");
 
 // One cascade stage with its resolved successors (tempcv.cpp:834-861 flattened).
 struct StageDev {
@@ -154,13 +157,11 @@ constexpr int TILE_SP_BLOCK = 64;         // stumps evaluated per round and wind
 // (16 bytes per record each, 1 KiB) and dwords 12..13 (8 bytes per record, 512 bytes) — so that a wave's load of one piece
 // covers consecutive bytes; partial blocks are padded with zero records.  3584 bytes = 56 NodeRec slots.
 constexpr int TILE_TAIL_BLOCK_RECS = (3 * 16 + 8) * TILE_SP_BLOCK / 64;
-// 255^2 * 66051 < 2^32 <= 255^2 * 66052: the largest window area whose squared sum always fits a dword
-constexpr uint32_t SQ32_MAX_AREA = 66051;
-static_assert(65025ull * SQ32_MAX_AREA < (1ull << 32) && 65025ull * (SQ32_MAX_AREA + 1ull) >= (1ull << 32), "SQ32_MAX_AREA");
+// SQ32_MAX_AREA, the largest window area whose squared sum always fits a dword: vj_sq_strips.hpp
 
 struct CascadeArgs {
     const uint32_t* sum;        // batch sum images, frame f at f * frame_elems
-    const uint64_t* sqsum;      // batch squared-sum images, same geometry
+    const uint64_t* sqsum;      // batch squared-sum images, same geometry (sq_u32: u32 elements mod 2^32 in the buffer's first half)
     const uint32_t* table;      // NodeRec[] viewed as dwords (16 per node)
     const ScaleDev* scales;
     const StageDev* stages;
@@ -239,6 +240,8 @@ struct CascadeArgs {
     uint32_t  n_skip_units;
     const UnitDev* skip_segs;           // one per recurrence domain (a window row, or a scale's whole list): {scale, first word, words, -}
     uint32_t  n_skip_segs;
+    uint32_t  sq_u32;                   // != 0: sqsum holds u32 elements, the values mod 2^32 (IntegralArgs::sq_u32); scales without
+                                        // ScaleDev::sq32 walk their variance window in strips (ScaleDev::sq_strip).  0: u64 elements
 };
 
 struct IntegralArgs {
@@ -257,6 +260,8 @@ struct IntegralArgs {
     uint64_t* sqsum;
     uint32_t frame_elems;
     uint32_t rows_mode;         // band_rows: 0 one wave walks a band's chunks; 1 the chunks side by side (band_rows_par); 2 side by side unless the call is a batch
+    uint32_t sq_u32;            // != 0: the squares stay in 32 bits end to end — sqsum and band_sq_prefix are written as u32 arrays of
+                                // the same element counts (the first halves of the buffers), values mod 2^32; 0: u64, the exact values
 };
 constexpr int BAND_ROWS = 8;
 

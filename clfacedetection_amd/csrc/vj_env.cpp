@@ -195,6 +195,8 @@ static int build_plan(const vj_env* e, const vj_cascade& c, int W, int H, const 
         sd.win_w = (uint32_t)si.win_w;
         sd.win_h = (uint32_t)si.win_h;
         sd.sq32 = e->sq32 && (uint64_t)sd.win_w * sd.win_h <= SQ32_MAX_AREA ? 1u : 0u;
+        // (the u32 layout of the squared integral: a larger window's variance rectangle in strips whose squared sums fit a dword)
+        sd.sq_strip = sd.sq32 ? 0u : sq_strip_rows(sd.e_dw) * stride;
         table.resize(table.size() + n_nodes);
         int rc = build_node_table(c, W, si, table.data() + sd.table_first);
         if (rc) return rc;
@@ -1000,7 +1002,7 @@ int ensure_image_buffers(vj_env* e, int W, int H, int frames, bool need_gray, in
 
 // Enqueue the three integral kernels for `frames` frames already on the device.
 int enqueue_integral(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int stride, int W, int H, int frames,
-                     int channels) {
+                     int channels, bool sq_u32) {
     IntegralArgs ia;
     memset(&ia, 0, sizeof(ia));
     ia.channels = (uint32_t)channels;
@@ -1019,16 +1021,18 @@ int enqueue_integral(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int s
     ia.sqsum = (uint64_t*)e->d_sqsum.p;
     ia.frame_elems = frame_elems_for(W, H);
     ia.rows_mode = (uint32_t)e->integral_rows_mode;
+    ia.sq_u32 = sq_u32 ? 1u : 0u;   // (u32 elements: frame f at element f * frame_elems of the same buffer, its first half)
     // the slack rows after row H (and the alignment tail) must read as zero
     // (the kernels never write there, so once per buffer layout is enough)
     const size_t used = (size_t)(W + 1) * (size_t)(H + 1);
     const bool zeroed = e->slack_w == W && e->slack_h == H && e->slack_frames >= frames && e->slack_sum == e->d_sum.p &&
-                        e->slack_sq == e->d_sqsum.p;
+                        e->slack_sq == e->d_sqsum.p && e->slack_sq_u32 == sq_u32;
+    const size_t sq_elem = sq_u32 ? 4 : 8;
     for (int f = 0; f < frames && !zeroed; ++f) {
         HIP_TRY(hipMemsetAsync((uint32_t*)e->d_sum.p + (size_t)f * ia.frame_elems + used, 0,
                                (ia.frame_elems - used) * 4, e->stream));
-        HIP_TRY(hipMemsetAsync((uint64_t*)e->d_sqsum.p + (size_t)f * ia.frame_elems + used, 0,
-                               (ia.frame_elems - used) * 8, e->stream));
+        HIP_TRY(hipMemsetAsync((char*)e->d_sqsum.p + ((size_t)f * ia.frame_elems + used) * sq_elem, 0,
+                               (ia.frame_elems - used) * sq_elem, e->stream));
     }
     if (!zeroed) {
         e->slack_w = W;
@@ -1036,6 +1040,7 @@ int enqueue_integral(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int s
         e->slack_frames = frames;
         e->slack_sum = e->d_sum.p;
         e->slack_sq = e->d_sqsum.p;
+        e->slack_sq_u32 = sq_u32;
     }
     int hrc = launch_integral(ia, e->stream);
     if (hrc) {
@@ -1285,7 +1290,7 @@ static_assert(CountsLayout::roi_tickets_begin + 8u <= CountsLayout::tile_tickets
 // Upload (or adopt) the frames of one batch and enqueue its integral images.  `copy_stream` != null: the upload runs
 // on that stream and the integral waits for it (vj_stream); else everything is ordered on the environment's stream.
 static int enqueue_prepare(vj_env* e, Lane* L, Plan* pl, const vj_image* frames, int nf, int W, int H, bool fixed_queue_layout,
-                           hipStream_t copy_stream, bool equalize = false) {
+                           hipStream_t copy_stream, bool equalize = false, bool sq_u32 = false) {
     int rc;
     int channels = image_channels(frames[0]);
     if ((rc = ensure_image_buffers(e, W, H, nf, true, channels, L))) return rc;
@@ -1316,7 +1321,9 @@ static int enqueue_prepare(vj_env* e, Lane* L, Plan* pl, const vj_image* frames,
     L->src_frame_bytes = gray_frame_bytes;
     L->src_stride = gray_stride;
     L->src_channels = channels;
-    if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, channels))) return rc;
+    // (a variance rectangle wider than SQ32_MAX_AREA pixels has no strip height: such frames keep the u64 layout)
+    L->sq_u32 = sq_u32 && e->sq32 && e->sq_u32 && (uint32_t)W <= SQ32_MAX_AREA;
+    if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, channels, L->sq_u32))) return rc;
     HIP_TRY(hipEventRecord(L->ev[1], e->stream));
     HIP_TRY(hipEventRecord(L->integral_done, e->stream));   // the lane's frame buffer may be overwritten from here on
     L->nf = nf;
@@ -1346,6 +1353,7 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
         memset(&ca, 0, sizeof(ca));
         ca.sum = (const uint32_t*)e->d_sum.p;
         ca.sqsum = (const uint64_t*)e->d_sqsum.p;
+        ca.sq_u32 = L->sq_u32 ? 1u : 0u;
         ca.table = (const uint32_t*)pl->d_table.p;
         ca.scales = (const ScaleDev*)pl->d_scales.p;
         ca.stages = (const StageDev*)pl->d_stages.p;
@@ -1638,7 +1646,7 @@ static int finish_batch(vj_env* e, Lane* L, Plan* pl, int f0, int W, int H, cons
             L->det_cap = want;
             if (L->shared_integrals) {
                 HIP_TRY(hipEventRecord(L->ev[0], e->stream));
-                if ((rc = enqueue_integral(e, L->src_gray, L->src_frame_bytes, L->src_stride, W, H, L->nf, L->src_channels))) return rc;
+                if ((rc = enqueue_integral(e, L->src_gray, L->src_frame_bytes, L->src_stride, W, H, L->nf, L->src_channels, L->sq_u32))) return rc;
                 HIP_TRY(hipEventRecord(L->ev[1], e->stream));
             }
             if ((rc = enqueue_cascade(e, L, pl, W, H, p))) return rc;
@@ -1732,7 +1740,7 @@ static int detect_subbatch(vj_env* e, Plan* pl, const vj_image* frames, int f0, 
                            const vj_params& p, bool equalize, std::vector<RawDet>* dets, vj_counters* ctr, vj_timing* tm) {
     int rc;
     Lane* L = &e->lane0;
-    if ((rc = enqueue_prepare(e, L, pl, frames + f0, nf, W, H, false, nullptr, equalize))) return rc;
+    if ((rc = enqueue_prepare(e, L, pl, frames + f0, nf, W, H, false, nullptr, equalize, true))) return rc;
     if ((rc = enqueue_cascade(e, L, pl, W, H, p))) return rc;
     return finish_batch(e, L, pl, f0, W, H, p, dets, ctr, tm);
 }
@@ -2101,6 +2109,7 @@ int vj_env_create(int device_index, vj_env** out) {
     e->n_cu = prop.multiProcessorCount;
     if (const char* g = getenv("VJ_TILE_GROUP")) e->tile_group = std::max(1, std::min(atoi(g), (int)MAX_SCALES));
     if (const char* g = getenv("VJ_SQ32")) e->sq32 = atoi(g) != 0;
+    if (const char* g = getenv("VJ_SQ_U32")) e->sq_u32 = atoi(g) != 0;
     if (const int hrc = prepare_tile_kernels()) {
         set_error("raising the dynamic LDS limit on device %d failed: %s", device_index, hipGetErrorString((hipError_t)hrc));
         return VJ_ERR_HIP;
@@ -2498,6 +2507,30 @@ int vj_integral_image(vj_env* e, const vj_image* image, uint32_t* sum, uint64_t*
     const size_t n = (size_t)(w + 1) * (size_t)(h + 1);
     HIP_TRY(hipMemcpyAsync(sum, e->d_sum.p, n * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(sqsum, e->d_sqsum.p, n * 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return VJ_OK;
+}
+
+int vj_integral_batch_sq32(vj_env* e, const vj_image* frames, int n_frames, uint32_t* sum, uint32_t* sqsum32) {
+    if (!e || !frames || n_frames <= 0 || !sum || !sqsum32) return VJ_ERR_ARG;
+    int W, H, CH, rc;
+    if ((rc = check_frames(frames, n_frames, &W, &H, &CH))) return rc;
+    const size_t fe = frame_elems_for(W, H);
+    if (fe * 8u * (size_t)n_frames > 0xfffffff0ull) {
+        set_error("vj_integral_batch_sq32: %d frames of %d x %d exceed one batch", n_frames, W, H);
+        return VJ_ERR_LIMIT;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = ensure_image_buffers(e, W, H, n_frames, true, CH))) return rc;
+    const uint8_t* d_gray;
+    size_t fb;
+    int gs;
+    if ((rc = stage_frames(e, frames, n_frames, W, H, &d_gray, &fb, &gs))) return rc;
+    if ((rc = enqueue_integral(e, d_gray, fb, gs, W, H, n_frames, CH, true))) return rc;
+    // frame f of either image starts at element f * frame_elems on the device; the caller's arrays are dense
+    const size_t row = (size_t)(W + 1) * (size_t)(H + 1) * 4;
+    HIP_TRY(hipMemcpy2DAsync(sum, row, e->d_sum.p, fe * 4, row, (size_t)n_frames, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpy2DAsync(sqsum32, row, e->d_sqsum.p, fe * 4, row, (size_t)n_frames, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return VJ_OK;
 }
@@ -3161,7 +3194,7 @@ int vj_stream_submit(vj_stream* s, const vj_image* frames, int n_frames) {
     Lane* L = &s->lanes[lane];
     // the lane's frame buffer is free once the integral kernels of its previous batch have read it
     HIP_TRY(hipEventSynchronize(L->integral_done));
-    if ((rc = enqueue_prepare(e, L, s->plan.get(), frames, n_frames, W, H, true, s->copy))) return rc;
+    if ((rc = enqueue_prepare(e, L, s->plan.get(), frames, n_frames, W, H, true, s->copy, false, true))) return rc;
     if ((rc = enqueue_cascade(e, L, s->plan.get(), W, H, s->p))) return rc;
     s->fifo[s->n_pending] = lane;
     s->n_frames_of[lane] = n_frames;

@@ -221,6 +221,7 @@ struct Lane {
     const uint8_t* src_gray = nullptr;
     size_t src_frame_bytes = 0;
     int src_stride = 0, src_channels = 1;
+    bool sq_u32 = false;             // this batch's squared integral is in the u32 layout (IntegralArgs::sq_u32); a redo keeps it
     bool shared_integrals = false;
     size_t n_pass = 0;
     int launches = 0;
@@ -337,6 +338,10 @@ struct vj_env : vj::Tunables {
     // The tile passes read the squared-sum corners of a scale as dwords where its window area allows (ScaleDev::sq32).  Not a
     // configure key: VJ_SQ32=0, read once by vj_env_create, keeps every scale on the 64-bit form (a diagnostic).
     bool sq32 = true;
+    // vj_detect and vj_stream keep the squared integral of a batch as u32, mod 2^32 (IntegralArgs::sq_u32): scales
+    // with sq32 read its dwords, the others walk their variance window in strips.  Not a configure key: VJ_SQ_U32=0, read once by
+    // vj_env_create, keeps those calls on the u64 layout, and so does VJ_SQ32=0.  Every other entry point uses the u64 layout.
+    bool sq_u32 = true;
     hipStream_t stream = nullptr;
     vj::Lane lane0;                  // the batch of a plain vj_detect call
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
@@ -350,6 +355,7 @@ struct vj_env : vj::Tunables {
     vj::DevBuf d_out;               // scratch for device -> host results (vj_grayscale)
     int slack_w = 0, slack_h = 0, slack_frames = 0;   // layout whose slack rows are known to be zero
     void *slack_sum = nullptr, *slack_sq = nullptr;
+    bool slack_sq_u32 = false;      // ... of the squared integral in this layout
     // survivor queues + counters + detections
     vj::DevBuf d_q[vj::MAX_PASSES];   // d_q[p]: windows waiting to enter pass p (p >= 1)
     vj::DevBuf d_q2[vj::MAX_PASSES];  // stage trees: the tiles' own queue set (enqueue_cascade: split_sets)
@@ -440,8 +446,9 @@ int image_channels(const vj_image& im);
 int check_single_image(const vj_image* image, int* ch_out);   // VJ_ERR_ARG / VJ_ERR_LIMIT, else the channel count
 uint32_t frame_elems_for(int W, int H);
 int ensure_image_buffers(vj_env* e, int W, int H, int frames, bool need_gray, int channels = 1, Lane* lane = nullptr);
+// (sq_u32: the squared integral in the u32 layout, for readers that are told so — CascadeArgs::sq_u32; default: u64)
 int enqueue_integral(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int stride, int W, int H, int frames,
-                     int channels = 1);
+                     int channels = 1, bool sq_u32 = false);
 int stage_frames(vj_env* e, const vj_image* frames, int n, int W, int H, const uint8_t** d_ptr, size_t* frame_bytes,
                  int* stride, Lane* lane = nullptr, hipStream_t copy_stream = nullptr);
 int enqueue_tilted(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int stride, int W, int H, int frames, int channels);

@@ -77,7 +77,8 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 //   2. band_scan   : per column, exclusive prefix of those over the bands
 //   3. band_rows   : one wave per band; top edge = prefix along x of the column totals above, then
 //                    per row a wave prefix scan along x (DPP) + carry of the chunks to the left.
-// All integers, so the result is exact: sum wraps mod 2^32 like CV_32S, sqsum is u64.
+// All integers, so the result is exact: sum wraps mod 2^32 like CV_32S, sqsum is u64 — or, for the detect path's u32 layout
+// (IntegralArgs::sq_u32), wraps mod 2^32 too: its readers rebuild the exact window sums (vj_sq_strips.hpp).
 
 // load_px4 / bgr2gray / load_gray4: vj_devutil.hpp (shared with the Canny kernels, vj_canny.hip)
 
@@ -110,12 +111,15 @@ __device__ __forceinline__ void band_colsum_body(const IntegralArgs& a) {
 __global__ __launch_bounds__(256) void band_colsum(IntegralArgs a) { band_colsum_body<true>(a); }
 __global__ __launch_bounds__(256) void band_colsum_sum(IntegralArgs a) { band_colsum_body<false>(a); }
 
+// P: the element of band_sq_prefix — uint64_t, or uint32_t (IntegralArgs::sq_u32: the prefix mod 2^32, in the array's first half)
+template <typename P>
 __global__ __launch_bounds__(256) void band_scan(IntegralArgs a) {
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
     const uint32_t frame = blockIdx.y;
     if (x >= a.band_pitch) return;
+    P* const sq_prefix = reinterpret_cast<P*>(a.band_sq_prefix);
     uint32_t s = 0;
-    uint64_t q = 0;
+    P q = 0;
     size_t o = (size_t)frame * a.n_bands * a.band_pitch + x;
     // eight bands per step: the loads of a step are independent of its stores (the prefix is written in place)
     for (uint32_t b0 = 0; b0 < a.n_bands; b0 += 8u) {
@@ -130,7 +134,7 @@ __global__ __launch_bounds__(256) void band_scan(IntegralArgs a) {
         for (uint32_t k = 0; k < 8u; ++k) {
             if (b0 + k < a.n_bands) {
                 a.band_sum[o + (size_t)k * a.band_pitch] = s;         // exclusive prefix, in place
-                a.band_sq_prefix[o + (size_t)k * a.band_pitch] = q;
+                sq_prefix[o + (size_t)k * a.band_pitch] = q;
             }
             s += ts[k];
             q += tq[k];
@@ -161,10 +165,11 @@ __global__ __launch_bounds__(256) void band_scan_sum(IntegralArgs a) {
 // every lane loads its column's BPG band totals at once (one memory round trip instead of n_bands / 8 dependent ones: the
 // single-frame integral is latency-bound, 135 bands at 1080p), scans them in registers, and adds the totals of the groups
 // above from LDS.  Same arithmetic (integer adds), same outputs as band_scan.
-template <int BPG>
+template <int BPG, typename P>
 __global__ __launch_bounds__(1024) void band_scan2(IntegralArgs a) {
     __shared__ uint32_t tot_s[16][64];
-    __shared__ uint64_t tot_q[16][64];
+    __shared__ P tot_q[16][64];
+    P* const sq_prefix = reinterpret_cast<P*>(a.band_sq_prefix);
     const uint32_t lane = threadIdx.x & 63u, g = threadIdx.x >> 6;
     const uint32_t x = blockIdx.x * 64u + lane, frame = blockIdx.y;
     const bool in = x < a.band_pitch;
@@ -178,7 +183,7 @@ __global__ __launch_bounds__(1024) void band_scan2(IntegralArgs a) {
         tq[k] = have ? a.band_sq[o + (size_t)k * a.band_pitch] : 0u;
     }
     uint32_t s = 0;
-    uint64_t q = 0;
+    P q = 0;
 #pragma unroll
     for (int k = 0; k < BPG; ++k) {
         s += ts[k];
@@ -197,7 +202,7 @@ __global__ __launch_bounds__(1024) void band_scan2(IntegralArgs a) {
     for (int k = 0; k < BPG; ++k) {
         if (in && b0 + (uint32_t)k < a.n_bands) {
             a.band_sum[o + (size_t)k * a.band_pitch] = s;         // exclusive prefix, in place
-            a.band_sq_prefix[o + (size_t)k * a.band_pitch] = q;
+            sq_prefix[o + (size_t)k * a.band_pitch] = q;
         }
         s += ts[k];
         q += tq[k];
@@ -256,15 +261,39 @@ __device__ __forceinline__ void out_store(V* p, V v) {
 // plus the prefixes along x of the band's rows down to y.  A row's prefix of squares stays below 2^32 for rows of up
 // to 66051 pixels (Q = uint32_t: one 32-bit DPP scan per row and image); wider images scan in 64 bits.  All integer
 // arithmetic: the sum wraps mod 2^32 like CV_32S whatever the order of the additions, the squared sum is exact.
-template <typename Q, bool NT = false, bool SQ = true>
+// S: the element of the squared integral and of band_sq_prefix.  uint64_t holds the exact value; uint32_t (IntegralArgs::sq_u32,
+// Q = uint32_t whatever the width) keeps the squares in 32 bits end to end, wrapping mod 2^32 like the sum: a second 32-bit DPP
+// scan for the top edge, one 16-byte load of the prefix and one 16-byte store per lane and row, into the buffers' first halves.
+template <typename S>
+__device__ __forceinline__ void load_sq_prefix4(const IntegralArgs& a, size_t i, S (&aq)[4]) {
+    if constexpr (sizeof(S) == 8) {
+        const ulonglong2 u0 = *reinterpret_cast<const ulonglong2*>(a.band_sq_prefix + i);
+        const ulonglong2 u1 = *reinterpret_cast<const ulonglong2*>(a.band_sq_prefix + i + 2);
+        aq[0] = u0.x; aq[1] = aq[0] + u0.y; aq[2] = aq[1] + u1.x; aq[3] = aq[2] + u1.y;
+    } else {
+        const uint4 t = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint32_t*>(a.band_sq_prefix) + i);
+        aq[0] = t.x; aq[1] = aq[0] + t.y; aq[2] = aq[1] + t.z; aq[3] = aq[2] + t.w;
+    }
+}
+template <bool NT, typename S>
+__device__ __forceinline__ void store_sq4(S* p, const S (&aq)[4]) {
+    if constexpr (sizeof(S) == 8) {
+        out_store<NT>(reinterpret_cast<u64x2_unaligned*>(p), u64x2_unaligned{aq[0], aq[1]});
+        out_store<NT>(reinterpret_cast<u64x2_unaligned*>(p + 2), u64x2_unaligned{aq[2], aq[3]});
+    } else {
+        out_store<NT>(reinterpret_cast<u32x4_unaligned*>(p), u32x4_unaligned{aq[0], aq[1], aq[2], aq[3]});
+    }
+}
+template <typename Q, bool NT = false, bool SQ = true, typename S = uint64_t>
 __device__ __forceinline__ void band_rows_body(const IntegralArgs& a) {
+    static_assert(sizeof(S) == 8 || sizeof(Q) == 4, "a 32-bit squared integral scans its rows in 32 bits");
     const uint32_t lane = lane_id();
     const uint32_t band = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t frame = blockIdx.y;
     if (band >= a.n_bands) return;  // whole wave exits together
     const uint8_t* img = a.gray + (size_t)frame * a.gray_frame_bytes;
     uint32_t* sum = a.sum + (size_t)frame * a.frame_elems;
-    uint64_t* sqs = a.sqsum + (size_t)frame * a.frame_elems;
+    S* sqs = reinterpret_cast<S*>(a.sqsum) + (size_t)frame * a.frame_elems;
     const uint32_t ow = a.width + 1u;   // output row length
     const uint32_t y0 = band * BAND_ROWS;
     const size_t bo = ((size_t)frame * a.n_bands + band) * a.band_pitch;
@@ -272,7 +301,7 @@ __device__ __forceinline__ void band_rows_body(const IntegralArgs& a) {
     if (band == 0) {  // row 0 of both outputs is zero
         for (uint32_t x = lane; x < ow; x += 64u) {
             sum[x] = 0u;
-            if (SQ) sqs[x] = 0ull;
+            if (SQ) sqs[x] = 0;
         }
     }
     uint32_t rs[BAND_ROWS];  // per row: total of the row left of the current chunk
@@ -283,7 +312,7 @@ __device__ __forceinline__ void band_rows_body(const IntegralArgs& a) {
         rq[r] = 0;
     }
     uint32_t top_s = 0;      // integral at the band's top edge, left of the current chunk
-    uint64_t top_q = 0;
+    S top_q = 0;
     for (uint32_t x0 = 0; x0 < a.width; x0 += 256u) {
         const uint32_t x = x0 + lane * 4u;
         const bool in = x < a.width;
@@ -292,21 +321,17 @@ __device__ __forceinline__ void band_rows_body(const IntegralArgs& a) {
         for (int r = 0; r < BAND_ROWS; ++r)   // every row of the chunk is in flight before the first scan
             v[r] = in && y0 + r < a.height ? load_gray4(img + (size_t)(y0 + r) * a.gray_stride, x, a.width, a.channels) : 0u;
         uint32_t as[4] = {0, 0, 0, 0};   // running integral of the lane's four columns
-        uint64_t aq[4] = {0, 0, 0, 0};
+        S aq[4] = {0, 0, 0, 0};
         if (in) {  // column totals above the band
             const uint4 t = *reinterpret_cast<const uint4*>(a.band_sum + bo + x);
             as[0] = t.x; as[1] = as[0] + t.y; as[2] = as[1] + t.z; as[3] = as[2] + t.w;
         }
-        if (in && SQ) {
-            const ulonglong2 u0 = *reinterpret_cast<const ulonglong2*>(a.band_sq_prefix + bo + x);
-            const ulonglong2 u1 = *reinterpret_cast<const ulonglong2*>(a.band_sq_prefix + bo + x + 2);
-            aq[0] = u0.x; aq[1] = aq[0] + u0.y; aq[2] = aq[1] + u1.x; aq[3] = aq[2] + u1.y;
-        }
+        if (in && SQ) load_sq_prefix4(a, bo + x, aq);
         {
             const uint32_t is = wave_incl_scan(as[3]);
-            const uint64_t iq = wave_incl_scan(aq[3]);
+            const S iq = wave_incl_scan(aq[3]);
             const uint32_t base_s = top_s + (is - as[3]);
-            const uint64_t base_q = top_q + (iq - aq[3]);
+            const S base_q = top_q + (iq - aq[3]);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 as[c] += base_s;
@@ -334,21 +359,18 @@ __device__ __forceinline__ void band_rows_body(const IntegralArgs& a) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     as[c] += base_s + ls[c];
-                    aq[c] += (uint64_t)(Q)(base_q + lq[c]);
+                    aq[c] += (S)(Q)(base_q + lq[c]);
                 }
                 const size_t ro = (size_t)(y + 1u) * ow;
                 if (x0 == 0 && lane == 0) {  // column 0 is zero
                     sum[ro] = 0u;
-                    if (SQ) sqs[ro] = 0ull;
+                    if (SQ) sqs[ro] = 0;
                 }
                 if (x + 4u <= a.width) {
                     // 16 (sum) and 32 (squared sum) contiguous bytes per lane: the wave writes
                     // contiguous 1 KiB / 2 KiB runs; rows are only 4-byte aligned (odd stride)
                     out_store<NT>(reinterpret_cast<u32x4_unaligned*>(sum + ro + x + 1u), u32x4_unaligned{as[0], as[1], as[2], as[3]});
-                    if (SQ) {
-                        out_store<NT>(reinterpret_cast<u64x2_unaligned*>(sqs + ro + x + 1u), u64x2_unaligned{aq[0], aq[1]});
-                        out_store<NT>(reinterpret_cast<u64x2_unaligned*>(sqs + ro + x + 3u), u64x2_unaligned{aq[2], aq[3]});
-                    }
+                    if (SQ) store_sq4<NT>(sqs + ro + x + 1u, aq);
                 } else {
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
@@ -369,10 +391,10 @@ __device__ __forceinline__ void band_rows_body(const IntegralArgs& a) {
 // which are bound by stores in flight — 64 x 1080p 0.721 -> 0.664 ms, 256 x 720p 1.325 -> 1.199; four waves per SIMD spill 200-250 bytes
 // and lose it again: profiles/r04_notes.md #6).  The batch variant also stores non-temporally (64 x 1080p -7 %, 256 x 720p -6 %; a single
 // 4096 x 4096 frame or 8 x 1080p, whose outputs the caches still hold when the cascade starts, +20-30 % with such stores: they keep the ordinary ones).
-template <typename Q>
-__global__ __launch_bounds__(256) void band_rows(IntegralArgs a) { band_rows_body<Q>(a); }
-template <typename Q>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void band_rows_w3(IntegralArgs a) { band_rows_body<Q, true>(a); }
+template <typename Q, typename S = uint64_t>
+__global__ __launch_bounds__(256) void band_rows(IntegralArgs a) { band_rows_body<Q, false, true, S>(a); }
+template <typename Q, typename S = uint64_t>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void band_rows_w3(IntegralArgs a) { band_rows_body<Q, true, true, S>(a); }
 __global__ __launch_bounds__(256) void band_rows_sum(IntegralArgs a) { band_rows_body<uint32_t, false, false>(a); }
 
 // The same rows with the CHUNKS of a band side by side instead of one after the other: a workgroup of up to eight waves takes one
@@ -382,31 +404,32 @@ __global__ __launch_bounds__(256) void band_rows_sum(IntegralArgs a) { band_rows
 // chain of 8 dependent chunks, were the whole launch), and a wave carries no per-row state from chunk to chunk (fewer registers:
 // more bands' stores in flight on a batch).  Images wider than 2048 pixels loop with a carry.  Same integer arithmetic, same
 // outputs as band_rows_body.
-template <typename Q>
+template <typename Q, typename S = uint64_t>
 __global__ __launch_bounds__(512) void band_rows_par(IntegralArgs a) {
+    static_assert(sizeof(S) == 8 || sizeof(Q) == 4, "a 32-bit squared integral scans its rows in 32 bits");
     __shared__ uint32_t tot_s[2][BAND_ROWS + 1][8];
-    __shared__ uint64_t tot_q[2][BAND_ROWS + 1][8];
+    __shared__ S tot_q[2][BAND_ROWS + 1][8];
     const uint32_t lane = lane_id();
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
     const uint32_t band = blockIdx.x, frame = blockIdx.y;
     const uint8_t* img = a.gray + (size_t)frame * a.gray_frame_bytes;
     uint32_t* sum = a.sum + (size_t)frame * a.frame_elems;
-    uint64_t* sqs = a.sqsum + (size_t)frame * a.frame_elems;
+    S* sqs = reinterpret_cast<S*>(a.sqsum) + (size_t)frame * a.frame_elems;
     const uint32_t ow = a.width + 1u;
     const uint32_t y0 = band * BAND_ROWS;
     const size_t bo = ((size_t)frame * a.n_bands + band) * a.band_pitch;
     if (band == 0) {  // row 0 of both outputs is zero
         for (uint32_t x = threadIdx.x; x < ow; x += blockDim.x) {
             sum[x] = 0u;
-            sqs[x] = 0ull;
+            sqs[x] = 0;
         }
     }
     uint32_t carry_s[BAND_ROWS + 1];   // [0]: the band's top edge, [1 + r]: row r — totals left of the current group of chunks (uniform)
-    uint64_t carry_q[BAND_ROWS + 1];
+    S carry_q[BAND_ROWS + 1];
 #pragma unroll
     for (int r = 0; r <= BAND_ROWS; ++r) {
         carry_s[r] = 0u;
-        carry_q[r] = 0ull;
+        carry_q[r] = 0;
     }
     uint32_t buf = 0;
     for (uint32_t x0 = 0; x0 < a.width; x0 += 256u * nw, buf ^= 1u) {
@@ -417,21 +440,19 @@ __global__ __launch_bounds__(512) void band_rows_par(IntegralArgs a) {
         for (int r = 0; r < BAND_ROWS; ++r)
             v[r] = in && y0 + r < a.height ? load_gray4(img + (size_t)(y0 + r) * a.gray_stride, x, a.width, a.channels) : 0u;
         uint32_t as[4] = {0, 0, 0, 0};
-        uint64_t aq[4] = {0, 0, 0, 0};
+        S aq[4] = {0, 0, 0, 0};
         if (in) {  // column totals above the band
             const uint4 t = *reinterpret_cast<const uint4*>(a.band_sum + bo + x);
             as[0] = t.x; as[1] = as[0] + t.y; as[2] = as[1] + t.z; as[3] = as[2] + t.w;
-            const ulonglong2 u0 = *reinterpret_cast<const ulonglong2*>(a.band_sq_prefix + bo + x);
-            const ulonglong2 u1 = *reinterpret_cast<const ulonglong2*>(a.band_sq_prefix + bo + x + 2);
-            aq[0] = u0.x; aq[1] = aq[0] + u0.y; aq[2] = aq[1] + u1.x; aq[3] = aq[2] + u1.y;
+            load_sq_prefix4(a, bo + x, aq);
         }
         // this chunk's own scans: exclusive prefixes per lane, totals to LDS
         uint32_t ex_s[BAND_ROWS + 1], t_s[BAND_ROWS + 1];
-        uint64_t ex_top_q, t_q[BAND_ROWS + 1];
+        S ex_top_q, t_q[BAND_ROWS + 1];
         Q ex_q[BAND_ROWS];
         {
             const uint32_t is = wave_incl_scan(as[3]);
-            const uint64_t iq = wave_incl_scan(aq[3]);
+            const S iq = wave_incl_scan(aq[3]);
             ex_s[0] = is - as[3];
             ex_top_q = iq - aq[3];
             t_s[0] = wave_last(is);
@@ -452,7 +473,7 @@ __global__ __launch_bounds__(512) void band_rows_par(IntegralArgs a) {
             ex_s[1 + r] = is - ls;
             ex_q[r] = iq - lq;
             t_s[1 + r] = wave_last(is);
-            t_q[1 + r] = (uint64_t)wave_last(iq);
+            t_q[1 + r] = (S)wave_last(iq);
         }
         if (lane == 0) {
 #pragma unroll
@@ -464,11 +485,11 @@ __global__ __launch_bounds__(512) void band_rows_par(IntegralArgs a) {
         __syncthreads();   // (one barrier per group: the totals are double-buffered)
         // lane r adds up row r's totals: of the chunks to the left of this wave's, and of the whole group
         uint32_t pre_s = 0, all_s = 0;
-        uint64_t pre_q = 0, all_q = 0;
+        S pre_q = 0, all_q = 0;
         if (lane <= (uint32_t)BAND_ROWS) {
             for (uint32_t k = 0; k < nw; ++k) {
                 const uint32_t ts = tot_s[buf][lane][k];
-                const uint64_t tq = tot_q[buf][lane][k];
+                const S tq = tot_q[buf][lane][k];
                 if (k < w) {
                     pre_s += ts;
                     pre_q += tq;
@@ -478,24 +499,27 @@ __global__ __launch_bounds__(512) void band_rows_par(IntegralArgs a) {
             }
         }
         auto lane_u32 = [&](uint32_t val, int r) { return (uint32_t)__builtin_amdgcn_readlane((int)val, r); };
-        auto lane_u64 = [&](uint64_t val, int r) { return (uint64_t)lane_u32((uint32_t)val, r) | (uint64_t)lane_u32((uint32_t)(val >> 32), r) << 32; };
+        auto lane_q = [&](S val, int r) -> S {
+            if constexpr (sizeof(S) == 8) return (uint64_t)lane_u32((uint32_t)val, r) | (uint64_t)lane_u32((uint32_t)((uint64_t)val >> 32), r) << 32;
+            else return lane_u32(val, r);
+        };
         {
             const uint32_t base_s = carry_s[0] + lane_u32(pre_s, 0) + ex_s[0];
-            const uint64_t base_q = carry_q[0] + lane_u64(pre_q, 0) + ex_top_q;
+            const S base_q = carry_q[0] + lane_q(pre_q, 0) + ex_top_q;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 as[c] += base_s;
                 aq[c] += base_q;
             }
             carry_s[0] += lane_u32(all_s, 0);
-            carry_q[0] += lane_u64(all_q, 0);
+            carry_q[0] += lane_q(all_q, 0);
         }
 #pragma unroll
         for (int r = 0; r < BAND_ROWS; ++r) {
             const uint32_t y = y0 + r;
             if (y < a.height) {  // uniform
                 const uint32_t base_s = carry_s[1 + r] + lane_u32(pre_s, 1 + r) + ex_s[1 + r];
-                const Q base_q = (Q)(carry_q[1 + r] + lane_u64(pre_q, 1 + r)) + ex_q[r];
+                const Q base_q = (Q)(carry_q[1 + r] + lane_q(pre_q, 1 + r)) + ex_q[r];
                 uint32_t ls = 0;
                 Q lq = 0;
 #pragma unroll
@@ -504,17 +528,16 @@ __global__ __launch_bounds__(512) void band_rows_par(IntegralArgs a) {
                     ls += p;
                     lq += (Q)(p * p);
                     as[c] += base_s + ls;
-                    aq[c] += (uint64_t)(Q)(base_q + lq);
+                    aq[c] += (S)(Q)(base_q + lq);
                 }
                 const size_t ro = (size_t)(y + 1u) * ow;
                 if (x == 0u) {  // column 0 is zero
                     sum[ro] = 0u;
-                    sqs[ro] = 0ull;
+                    sqs[ro] = 0;
                 }
                 if (x + 4u <= a.width) {
                     out_store<false>(reinterpret_cast<u32x4_unaligned*>(sum + ro + x + 1u), u32x4_unaligned{as[0], as[1], as[2], as[3]});
-                    out_store<false>(reinterpret_cast<u64x2_unaligned*>(sqs + ro + x + 1u), u64x2_unaligned{aq[0], aq[1]});
-                    out_store<false>(reinterpret_cast<u64x2_unaligned*>(sqs + ro + x + 3u), u64x2_unaligned{aq[2], aq[3]});
+                    store_sq4<false>(sqs + ro + x + 1u, aq);
                 } else {
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
@@ -524,7 +547,7 @@ __global__ __launch_bounds__(512) void band_rows_par(IntegralArgs a) {
                         }
                 }
                 carry_s[1 + r] += lane_u32(all_s, 1 + r);
-                carry_q[1 + r] += lane_u64(all_q, 1 + r);
+                carry_q[1 + r] += lane_q(all_q, 1 + r);
             }
         }
     }
@@ -546,26 +569,38 @@ int launch_integral(const IntegralArgs& a, void* stream_) {
     hipLaunchKernelGGL(band_colsum, g1, dim3(256), 0, stream, a);
     // prefix over the bands: two levels (16 groups per workgroup) while a group stays <= 32 bands (images up to 4096 rows)
     const dim3 g2b((a.band_pitch + 63u) / 64u, a.n_frames, 1);
-    if (a.n_bands <= 16u * 8u) hipLaunchKernelGGL(band_scan2<8>, g2b, dim3(1024), 0, stream, a);
-    else if (a.n_bands <= 16u * 16u) hipLaunchKernelGGL(band_scan2<16>, g2b, dim3(1024), 0, stream, a);
-    else if (a.n_bands <= 16u * 32u) hipLaunchKernelGGL(band_scan2<32>, g2b, dim3(1024), 0, stream, a);
-    else {
+    const bool q32 = a.sq_u32 != 0u;   // the squares in 32 bits end to end (mod 2^32), whatever the width
+    if (a.n_bands <= 16u * 8u) {
+        if (q32) hipLaunchKernelGGL((band_scan2<8, uint32_t>), g2b, dim3(1024), 0, stream, a);
+        else hipLaunchKernelGGL((band_scan2<8, uint64_t>), g2b, dim3(1024), 0, stream, a);
+    } else if (a.n_bands <= 16u * 16u) {
+        if (q32) hipLaunchKernelGGL((band_scan2<16, uint32_t>), g2b, dim3(1024), 0, stream, a);
+        else hipLaunchKernelGGL((band_scan2<16, uint64_t>), g2b, dim3(1024), 0, stream, a);
+    } else if (a.n_bands <= 16u * 32u) {
+        if (q32) hipLaunchKernelGGL((band_scan2<32, uint32_t>), g2b, dim3(1024), 0, stream, a);
+        else hipLaunchKernelGGL((band_scan2<32, uint64_t>), g2b, dim3(1024), 0, stream, a);
+    } else {
         dim3 g2((a.band_pitch + 255u) / 256u, a.n_frames, 1);
-        hipLaunchKernelGGL(band_scan, g2, dim3(256), 0, stream, a);
+        if (q32) hipLaunchKernelGGL(band_scan<uint32_t>, g2, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(band_scan<uint64_t>, g2, dim3(256), 0, stream, a);
     }
     if (a.rows_mode != 0u) {   // chunks of a band side by side (band_rows_par): 1 always, 2 for calls that are not batches
         const bool batch_p = (uint64_t)a.n_frames * a.n_bands >= 2048u;
         if (a.rows_mode == 1u || !batch_p) {
             const uint32_t nw = min(8u, (a.width + 255u) / 256u);
             dim3 gp(a.n_bands, a.n_frames, 1);
-            if ((uint64_t)a.width * 65025ull < (1ull << 32)) hipLaunchKernelGGL(band_rows_par<uint32_t>, gp, dim3(64u * nw), 0, stream, a);
+            if (q32) hipLaunchKernelGGL((band_rows_par<uint32_t, uint32_t>), gp, dim3(64u * nw), 0, stream, a);
+            else if ((uint64_t)a.width * 65025ull < (1ull << 32)) hipLaunchKernelGGL(band_rows_par<uint32_t>, gp, dim3(64u * nw), 0, stream, a);
             else hipLaunchKernelGGL(band_rows_par<uint64_t>, gp, dim3(64u * nw), 0, stream, a);
             return (int)hipGetLastError();
         }
     }
     dim3 g3((a.n_bands + 3u) / 4u, a.n_frames, 1);
     const bool batch = (uint64_t)a.n_frames * a.n_bands >= 2048u;   // enough bands in flight to fill the chip several times
-    if ((uint64_t)a.width * 65025ull < (1ull << 32)) {
+    if (q32) {
+        if (batch) hipLaunchKernelGGL((band_rows_w3<uint32_t, uint32_t>), g3, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((band_rows<uint32_t, uint32_t>), g3, dim3(256), 0, stream, a);
+    } else if ((uint64_t)a.width * 65025ull < (1ull << 32)) {
         if (batch) hipLaunchKernelGGL(band_rows_w3<uint32_t>, g3, dim3(256), 0, stream, a);
         else hipLaunchKernelGGL(band_rows<uint32_t>, g3, dim3(256), 0, stream, a);
     } else {
@@ -605,18 +640,38 @@ __device__ __forceinline__ bool window_visited(const CascadeArgs& a, uint32_t fr
     return ((a.skip_bits[(size_t)frame * a.skip_frame_words + word] >> bit) & 1ull) != 0ull;
 }
 
+// One frame of the squared integral behind a buffer descriptor: u64 elements, or u32 elements mod 2^32 in the first half of
+// the same buffer (CascadeArgs::sq_u32, wave-uniform).
+__device__ __forceinline__ rsrc_t sq_frame_rsrc(const CascadeArgs& a, uint32_t frame, bool sq_u32) {
+    const uint32_t frame_bytes = a.frame_elems * (sq_u32 ? 4u : 8u);
+    return make_rsrc(reinterpret_cast<const char*>(a.sqsum) + (size_t)frame * frame_bytes, frame_bytes);
+}
+
+// The squared sum of a window as the f32 computeVariance converts it to ((float)(uint64_t)q of the exact value, round to
+// nearest even), from either layout.  `sq_u32` and `strip` are wave-uniform: u64 elements; u32 elements whose four corners
+// give the value itself mod 2^32 (strip == 0: ScaleDev::sq32); or u32 elements walked in strips (ScaleDev::sq_strip,
+// vj_sq_strips.hpp) whose exact sums add up in 64 bits.
+__device__ __forceinline__ float window_sq_f32(rsrc_t sq_f, uint32_t e, uint32_t c0, uint32_t e_dw, uint32_t e_dh, bool sq_u32,
+                                               uint32_t strip) {
+    if (!sq_u32)
+        return (float)(uint64_t)(ld_u64(sq_f, e * 8u, c0 * 8u) - ld_u64(sq_f, e * 8u, (c0 + e_dw) * 8u) -
+                                 ld_u64(sq_f, e * 8u, (c0 + e_dh) * 8u) + ld_u64(sq_f, e * 8u, (c0 + e_dh + e_dw) * 8u));
+    if (strip == 0u)
+        return (float)(uint32_t)(ld_u32(sq_f, e * 4u, c0 * 4u) - ld_u32(sq_f, e * 4u, (c0 + e_dw) * 4u) -
+                                 ld_u32(sq_f, e * 4u, (c0 + e_dh) * 4u) + ld_u32(sq_f, e * 4u, (c0 + e_dh + e_dw) * 4u));
+    return (float)sq_window_strips([&](uint32_t i) { return ld_u32(sq_f, e * 4u, i * 4u); }, c0, e_dw, e_dh, strip);
+}
+
 // computeVariance (clod.cpp:418-446) for the window whose origin is element `e` of the
 // frame described by (sum_f, sq_f).
 __device__ __forceinline__ float window_variance(rsrc_t sum_f, rsrc_t sq_f, uint32_t e, uint32_t e_lt, uint32_t e_dw,
-                                                 uint32_t e_dh, float area, bool signed_mean) {
+                                                 uint32_t e_dh, float area, bool signed_mean, bool sq_u32, uint32_t sq_strip) {
     // corner offsets are uniform (scalar adds); the lane contributes e
     const uint32_t c0 = e_lt, c1 = e_lt + e_dw, c2 = e_lt + e_dh, c3 = e_lt + e_dh + e_dw;
     const uint32_t s = ld_u32(sum_f, e * 4u, c0 * 4u) - ld_u32(sum_f, e * 4u, c1 * 4u) - ld_u32(sum_f, e * 4u, c2 * 4u) +
                        ld_u32(sum_f, e * 4u, c3 * 4u);
-    const uint64_t q = ld_u64(sq_f, e * 8u, c0 * 8u) - ld_u64(sq_f, e * 8u, c1 * 8u) - ld_u64(sq_f, e * 8u, c2 * 8u) +
-                       ld_u64(sq_f, e * 8u, c3 * 8u);
     const float mean = (signed_mean ? (float)(int32_t)s : (float)s) / area;
-    float variance = (float)q;                       // u64 -> f32, round to nearest even
+    float variance = window_sq_f32(sq_f, e, c0, e_dw, e_dh, sq_u32, sq_strip);   // u64 -> f32, round to nearest even
     variance = (variance / area) - (mean * mean);    // separate divide, multiply, subtract
     return variance >= 0.0f ? sqrtf(variance) : 1.0f;
 }
@@ -1293,7 +1348,9 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
             const float area = scales[slot].area;
             const size_t frame_off = (size_t)frame * a.frame_elems;
             const rsrc_t sum_f = make_rsrc(a.sum + frame_off, frame_bytes4);
-            const rsrc_t sq_f = make_rsrc(a.sqsum + frame_off, frame_bytes4 * 2u);
+            const bool sq_u32 = a.sq_u32 != 0u;
+            const uint32_t sq_strip = scales[slot].sq_strip;
+            const rsrc_t sq_f = sq_frame_rsrc(a, frame, sq_u32);
             const uint32_t frame_bytes = frame * frame_bytes4;  // < 2^32, checked on the host
             // precomputeWindows (clod.cpp:495-527): x = lrint(ix * step); a unit is either a row-major run of
             // windows or a 2-D block of them (compact footprint in the sum image: the L2 traffic of the
@@ -1319,7 +1376,7 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
                     const uint32_t x = window_pos(a, pos_base, ix, step);
                     const uint32_t y = window_pos(a, pos_base, iy, step);
                     const uint32_t e = y * a.stride + x;
-                    en.var = window_variance(sum_f, sq_f, e, e_lt, e_dw, e_dh, area, a.signed_mean != 0u);
+                    en.var = window_variance(sum_f, sq_f, e, e_lt, e_dw, e_dh, area, a.signed_mean != 0u, sq_u32, sq_strip);
                     en.off = frame_bytes + e * 4u;
                 }
                 const unsigned long long mask = __ballot(valid);
@@ -1562,11 +1619,11 @@ __global__ __launch_bounds__(256) void skip_fail_bits(CascadeArgs a) {
         if (lane < count) {
             const size_t frame_off = (size_t)frame * a.frame_elems;
             const rsrc_t sum_f = make_rsrc(a.sum + frame_off, frame_bytes4);
-            const rsrc_t sq_f = make_rsrc(a.sqsum + frame_off, frame_bytes4 * 2u);
+            const rsrc_t sq_f = sq_frame_rsrc(a, frame, a.sq_u32 != 0u);
             const uint32_t x = window_pos(a, pos_base, ix, step), y = window_pos(a, pos_base, iy, step);
             const uint32_t e = y * a.stride + x;
             const float var = window_variance(sum_f, sq_f, e, scales[slot].e_lt, scales[slot].e_dw, scales[slot].e_dh, scales[slot].area,
-                                              a.signed_mean != 0u);
+                                              a.signed_mean != 0u, a.sq_u32 != 0u, scales[slot].sq_strip);
             kptr<NodeRecDev> tab = as_k(reinterpret_cast<const NodeRecDev*>(a.table)) + scales[slot].table_first + stages[0].first_node;
             fail = !(stage_sum_of<TREES>(GlobalImg{img}, tab, stages[0].n_nodes, frame * frame_bytes4 + e * 4u, var) >= stages[0].threshold);
         }
@@ -1731,7 +1788,7 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_roi_pass(RoiArg
                 const uint32_t x = x0 + (uint32_t)__float2int_rn((float)ix * step);
                 const uint32_t y = y0 + (uint32_t)__float2int_rn((float)iy * step);
                 const uint32_t e = y * a.stride + x;
-                en.var = window_variance(sum_f, sq_f, e, e_lt, e_dw, e_dh, area, a.signed_mean != 0u);
+                en.var = window_variance(sum_f, sq_f, e, e_lt, e_dw, e_dh, area, a.signed_mean != 0u, false, 0u);   // (regions: the u64 layout)
                 en.off = frame_bytes + e * 4u;
             }
             const unsigned long long mask = __ballot(valid);
@@ -2352,7 +2409,8 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
         const uint32_t frame_bytes = frame * frame_bytes4;   // < 2^32, checked on the host
         const size_t frame_off = (size_t)frame * a.frame_elems;
         const rsrc_t sum_f = make_rsrc(a.sum + frame_off, frame_bytes4);
-        const rsrc_t sq_f = make_rsrc(a.sqsum + frame_off, frame_bytes4 * 2u);
+        const bool sq_u32 = !ROI && a.sq_u32 != 0u;   // (uniform; the region pass reads the u64 layout)
+        const rsrc_t sq_f = sq_frame_rsrc(a, frame, sq_u32);
         // tile origin in the image: the first window's origin (same expression as below; every member of a group
         // places index i at 2 i)
         const uint32_t x0 = ox + __builtin_amdgcn_readfirstlane(window_pos(a, scales[slot0].pos_base, ix0, step));
@@ -2470,7 +2528,13 @@ __device__ __forceinline__ void tile_pass_body(const CascadeArgs& a, const RoiAr
                     const uint32_t e = y * a.stride + x;
                     w_lo4[k] = ((y - y0) * pitch + (half ? (x - x0) >> 1 : x - x0)) * 4u;
                     const uint32_t c0 = e_lt, c1 = e_lt + e_dw, c2 = e_lt + e_dh, c3 = e_lt + e_dh + e_dw;
-                    if (sq32)   // mod 2^32 the corners' low dwords give the sum itself
+                    if (sq_u32) {   // dword elements, the values mod 2^32
+                        if (sq32)   // the four corners give the sum itself
+                            w_q[k] = (float)(uint32_t)(ld_u32(sq_f, e * 4u, c0 * 4u) - ld_u32(sq_f, e * 4u, c1 * 4u) -
+                                                       ld_u32(sq_f, e * 4u, c2 * 4u) + ld_u32(sq_f, e * 4u, c3 * 4u));
+                        else        // (no tile scale of a shipped cascade: the variance window in strips, vj_sq_strips.hpp)
+                            w_q[k] = window_sq_f32(sq_f, e, c0, e_dw, e_dh, true, scales[slot].sq_strip);
+                    } else if (sq32)   // mod 2^32 the corners' low dwords give the sum itself
                         w_q[k] = (float)(uint32_t)(ld_u32(sq_f, e * 8u, c0 * 8u) - ld_u32(sq_f, e * 8u, c1 * 8u) -
                                                    ld_u32(sq_f, e * 8u, c2 * 8u) + ld_u32(sq_f, e * 8u, c3 * 8u));
                     else

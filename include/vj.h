@@ -339,6 +339,10 @@ struct vj_image;
 /* clifGrayscaleIntegral (clif.h:67-70, clif.cpp:326-335): gray conversion + both integrals of one image
  * (host or device pointer, 1 / 3 / 4 channels); outputs as vj_integral.                       */
 int  vj_integral_image(vj_env* e, const struct vj_image* image, uint32_t* sum, uint64_t* sqsum);
+/* The integral images as vj_detect and vj_stream keep them on the device for a batch of equal-sized frames: sum as above and
+ * the squared sum as u32, the values mod 2^32 (what the detect path's readers rebuild exact window sums from).  HOST outputs,
+ * dense: n_frames x (h+1) x (w+1) each.                                                                        */
+int  vj_integral_batch_sq32(vj_env* e, const struct vj_image* frames, int n_frames, uint32_t* sum, uint32_t* sqsum32);
 /* clifGrayscale (clif.h:55-58, clif.cpp:226-271 -> cvCvtColor BGR2GRAY): the 8-bit gray image the integral
  * kernels see, written to the HOST buffer `gray` (gray_stride bytes per row).  1-channel input is copied. */
 int  vj_grayscale(vj_env* e, const struct vj_image* image, uint8_t* gray, int gray_stride);
