@@ -39,6 +39,7 @@ VJ_FLAG_CV_SCALE_IMAGE = 1 << 7      # OpenCV profile: CV_HAAR_SCALE_IMAGE (the 
 VJ_FLAG_CV_FIND_BIGGEST = 1 << 8     # OpenCV profile: CV_HAAR_FIND_BIGGEST_OBJECT (largest window first, one grouped object per frame, then its surroundings only)
 VJ_FLAG_CV_ROUGH_SEARCH = 1 << 9     # OpenCV profile: CV_HAAR_DO_ROUGH_SEARCH (with find-biggest: the search stops at 0.6 of the object's size, not 0.4)
 VJ_FLAG_CV_CHAIN_DEVICE = 1 << 10    # detect_opencv_chain only (flags of the first cascade): regions and units are built on the device, one wait per sub-batch
+VJ_PREP_EQUALIZE = 1 << 0            # vj_prep.flags: cv::equalizeHist of the resized image (Environment.preprocess(equalize=True))
 VJ_FLAG_EQUALIZE_HIST = 1 << 11      # cv::equalizeHist on every frame, on the device, in front of detect / detect_opencv / detect_opencv_roc / the mixed calls; refused elsewhere
 
 # cvHaarDetectObjects' flags (tempcv.hpp:127-130).  cvHaarDetectObjects below takes only CV_HAAR_DO_CANNY_PRUNING in its `flags`
@@ -145,6 +146,11 @@ class MixedOpts(C.Structure):
     """vj_mixed_opts: speed only.  atlas_px: pixel budget of one atlas (0: default); own_call_px: a group of equal frames with at
     least this many pixels in total gets a batched call of its own (0: default, 2**64 - 1: never)."""
     _fields_ = [("atlas_px", C.c_uint64), ("own_call_px", C.c_uint64)]
+
+
+class Prep(C.Structure):
+    """vj_prep"""
+    _fields_ = [("dst_w", C.c_int32), ("dst_h", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class MixedInfo(C.Structure):
@@ -284,6 +290,10 @@ _SIGNATURES = {
     "vj_pack_frames": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                  C.POINTER(C.c_int), C.c_void_p]),
     "vj_mixed_info_get": (C.c_int, [C.c_void_p, C.POINTER(MixedInfo)]),
+    "vj_prep_default": (None, [C.POINTER(Prep)]),
+    "vj_preprocess_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.POINTER(Prep), C.POINTER(_Image), C.POINTER(C.c_uint64)]),
+    "vj_preprocess": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Prep), C.c_void_p, C.c_uint64, C.POINTER(_Image)]),
+    "vj_preprocess_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vj_result_free": (None, [C.POINTER(_Result)]),
     "vj_group_rectangles": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_double]),
     "vj_group_rectangles_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double]),
@@ -639,8 +649,7 @@ class Environment:
             n = frames.n
             imgs = (_Image * max(n, 1))()
             for i in range(n):
-                imgs[i] = _Image(frames.ptr + i * frames.stride * frames.height, frames.width, frames.height,
-                                 frames.stride, 1, frames.channels)
+                imgs[i] = _Image(frames.frame_ptr(i), frames.width, frames.height, frames.stride, 1, frames.channels)
             return imgs, n, keep
         if isinstance(frames, np.ndarray) and frames.ndim == (3 if color else 2):
             frames = [frames]
@@ -799,7 +808,7 @@ class Environment:
             frames = [frames]
         for f in frames:
             if isinstance(f, DeviceFrames):
-                imgs += [_Image(f.ptr + i * f.stride * f.height, f.width, f.height, f.stride, 1, f.channels) for i in range(f.n)]
+                imgs += [_Image(f.frame_ptr(i), f.width, f.height, f.stride, 1, f.channels) for i in range(f.n)]
                 continue
             if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim not in (2, 3) or (f.ndim == 3 and f.shape[2] not in (3, 4)):
                 raise ValueError("a frame must be a 2-D uint8 array, a (h, w, 3|4) uint8 array (BGR / BGRA) or DeviceFrames")
@@ -853,6 +862,67 @@ class Environment:
             _check(lib.vj_pack_frames(self._h, imgs, n, int(atlas_px), atlas.ctypes.data, atlas.strides[0], C.byref(w), C.byref(h),
                                       origins.ctypes.data), "vj_pack_frames")
         return atlas, origins
+
+    @staticmethod
+    def _prep_args(frames, size, fx, fy, equalize, color):
+        """-> (ctypes array of vj_image, n, arrays to keep alive, vj_prep).  frames: as detect() (one array, a batch, DeviceFrames; color=True
+        for BGR / BGRA arrays) or, as a list without color=True, as detect_mixed(): gray and BGR / BGRA arrays and DeviceFrames of any sizes."""
+        if (fx is None) != (fy is None):
+            raise ValueError("fx and fy go together")
+        if size is not None and fx is not None:
+            raise ValueError("size or fx / fy, not both")
+        if color or isinstance(frames, (np.ndarray, DeviceFrames)):
+            imgs, n, keep = Environment._images(frames, color)
+        else:
+            imgs, n, keep = Environment._mixed_images(frames)
+        p = Prep()
+        load_library().vj_prep_default(C.byref(p))
+        if size is not None:
+            p.dst_w, p.dst_h = int(size[0]), int(size[1])
+        if fx is not None:
+            p.fx, p.fy = float(fx), float(fy)
+        p.flags = VJ_PREP_EQUALIZE if equalize else 0
+        return imgs, n, keep, p
+
+    @staticmethod
+    def preprocess_layout(frames, size=None, fx=None, fy=None, equalize: bool = False, color: bool = False):
+        """vj_preprocess_layout (host only): where preprocess() puts every output image -> ([(offset, width, height, stride)], bytes)."""
+        imgs, n, keep, p = Environment._prep_args(frames, size, fx, fy, equalize, color)
+        out = (_Image * max(n, 1))()
+        nbytes = C.c_uint64(0)
+        _check(load_library().vj_preprocess_layout(imgs, n, C.byref(p), out, C.byref(nbytes)), "vj_preprocess_layout")
+        return [(int(out[i].data or 0), out[i].width, out[i].height, out[i].stride) for i in range(n)], int(nbytes.value)
+
+    def preprocess(self, frames, size=None, fx=None, fy=None, equalize: bool = False, color: bool = False, out=None) -> list:
+        """vj_preprocess: the front end of an OpenCV caller's detect call on the device — BGR2GRAY, resize(INTER_LINEAR)
+        to size = (w, h) or by the factors fx, fy (neither: no resize), then with equalize=True equalizeHist of the resized image — for
+        all frames in one call, device in, device out.  frames: see _prep_args.  Returns a list of DeviceFrames (gray, in device
+        memory): ONE entry of n frames when all outputs share a size — it goes straight into detect(), detect_opencv_chain() and the
+        rest —, else one entry per frame, which detect_mixed() takes as they are.  out: a torch.uint8 tensor on this device of at
+        least preprocess_layout()'s bytes; None: one is allocated.  The returned objects keep it alive."""
+        import torch
+        imgs, n, keep, p = self._prep_args(frames, size, fx, fy, equalize, color)
+        lib = load_library()
+        res = (_Image * max(n, 1))()
+        nbytes = C.c_uint64(0)
+        _check(lib.vj_preprocess_layout(imgs, n, C.byref(p), res, C.byref(nbytes)), "vj_preprocess_layout")
+        if out is None:
+            out = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device="cuda")
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
+            raise ValueError("out must be a contiguous torch.uint8 tensor in device memory")
+        _check(lib.vj_preprocess(self._h, imgs, n, C.byref(p), C.c_void_p(out.data_ptr()), out.numel(), res), "vj_preprocess")
+        if n == 0:
+            return []
+        r = [DeviceFrames(int(res[i].data), 1, res[i].height, res[i].width, res[i].stride, 1, 0, out) for i in range(n)]
+        if all((f.width, f.height) == (r[0].width, r[0].height) for f in r):
+            return [DeviceFrames(r[0].ptr, n, r[0].height, r[0].width, r[0].stride, 1, (r[1].ptr - r[0].ptr) if n > 1 else 0, out)]
+        return r
+
+    def preprocess_timing(self) -> float:
+        """vj_preprocess_timing: device time of the last preprocess() call (events around its copies and launches), ms."""
+        ms = C.c_float(0)
+        _check(load_library().vj_preprocess_timing(self._h, C.byref(ms)), "vj_preprocess_timing")
+        return float(ms.value)
 
     def mixed_info(self) -> MixedInfo:
         """vj_mixed_info_get: atlases (count and the largest one's size), batched calls on original frames, frames by route, grid
@@ -949,13 +1019,19 @@ class FrameStream:
 class DeviceFrames:
     """A batch of equal-size 8-bit frames already resident in device memory
     (e.g. a torch.uint8 CUDA tensor's data_ptr()); rows `stride` bytes apart,
-    frames `stride * height` bytes apart; channels = 1 (gray), 3 (BGR) or 4 (BGRA), interleaved."""
+    frames `frame_bytes` bytes apart (0: stride * height); channels = 1 (gray), 3 (BGR) or 4 (BGRA), interleaved.
+    owner: whatever keeps the memory alive (Environment.preprocess puts its tensor there)."""
     ptr: int
     n: int
     height: int
     width: int
     stride: int
     channels: int = 1
+    frame_bytes: int = 0
+    owner: object = None
+
+    def frame_ptr(self, i: int) -> int:
+        return self.ptr + i * (self.frame_bytes or self.stride * self.height)
 
     @classmethod
     def from_torch(cls, t) -> "DeviceFrames":
@@ -967,6 +1043,12 @@ class DeviceFrames:
             return cls(t.data_ptr(), n, h, w, w * ch, ch)
         n, h, w = t.shape
         return cls(t.data_ptr(), n, h, w, w)
+
+
+def preprocess_layout(frames, size=None, fx=None, fy=None, equalize: bool = False, color: bool = False):
+    """vj_preprocess_layout: the host-only twin of Environment.preprocess (no environment, no device) ->
+    ([(offset, width, height, stride) per frame], bytes of the destination buffer)."""
+    return Environment.preprocess_layout(frames, size, fx, fy, equalize, color)
 
 
 def _pixel_contiguous(img: np.ndarray) -> np.ndarray:

@@ -436,6 +436,12 @@ struct vj_env : vj::Tunables {
     vj::DevBuf d_atlas, d_atlas_src;
     hipEvent_t atlas_ev[2] = {};
     vj_mixed_info mixed_info = {};          // the last mixed call (vj_mixed_info_get)
+    // vj_preprocess (vj_preprocess.cpp): the block one copy brings per slice — frame records, the records equalize_lut reads,
+    // taps, then the slice's host frames at a 4-byte pitch (grows, reused; histograms and tables: lane0's d_eq_hist / d_eq_lut) —,
+    // events around a call's copies and launches and their time (vj_preprocess_timing)
+    vj::DevBuf d_prep;
+    hipEvent_t prep_ev[2] = {};
+    float prep_ms = 0;
     uint64_t plan_tick = 0;
     int cv_tq_shift = 4;              // ... stage trees: the survivors' queue holds 1 / 2^shift of the tile windows (grows on overflow)
 };

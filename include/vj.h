@@ -738,6 +738,43 @@ typedef struct vj_mixed_info {
 } vj_mixed_info;
 int  vj_mixed_info_get(const vj_env* e, vj_mixed_info* out);   /* a null argument: VJ_ERR_ARG */
 
+/* ------------------------------------------------- the front end of a detect call, on the device */
+/* What every OpenCV caller of a Haar cascade runs first — cvtColor(BGR2GRAY), resize(INTER_LINEAR) to the detection size,
+ * equalizeHist — as ONE batched call, device in, device out.  It adds no arithmetic: out[i] holds, byte for byte,
+ * vj_grayscale(frames[i]), then vj_resize_linear to the destination size (the identity when that is the source's size), then, with
+ * VJ_PREP_EQUALIZE, vj_equalize_hist — of the RESIZED image: its histogram is the destination's own, total = its width * height.
+ * Every frame is processed on its own.  Third-party arithmetic throughout, parity unpinned, like its parts.
+ * The records it returns have on_device = 1, so every entry point takes them as they are — also the ones that refuse
+ * VJ_FLAG_EQUALIZE_HIST (vj_detect_rois, vj_detect_chain, vj_detect_opencv_rois, vj_detect_opencv_chain, vj_run_windows) and
+ * vj_run_windows_opencv, which has no flags; outputs of differing sizes go to vj_detect_mixed / vj_detect_opencv_mixed.  Rectangles
+ * come back in the resized frame's coordinates: the caller scales them, as OpenCV's facedetect sample does.
+ * Layout of the destination buffer: image i has a row stride of its width rounded up to 4 and starts at a multiple of 256 bytes;
+ * the pad columns are written as 0 (and never counted in a histogram).                                                        */
+enum { VJ_PREP_EQUALIZE = 1u << 0 };
+typedef struct vj_prep {
+    int32_t  dst_w, dst_h;   /* both > 0: every frame is resized to this size                                                   */
+    double   fx, fy;         /* else both > 0: frame i goes to cvRound(w_i * fx) x cvRound(h_i * fy) (round half to even of the
+                                f64 product), at least 1 x 1; else (all four 0): no resize                                      */
+    uint32_t flags;          /* VJ_PREP_EQUALIZE                                                                                */
+    uint32_t reserved;       /* must be 0                                                                                       */
+} vj_prep;
+void vj_prep_default(vj_prep* p);                       /* all 0 */
+/* Host only, no environment: where each output image lies and how many bytes the buffer needs.  out[i] is what vj_preprocess will
+ * return for frame i, with data = (const uint8_t*)offset in the buffer; *bytes is the end of the last image.  Errors as below.  */
+int  vj_preprocess_layout(const vj_image* frames, int n_frames, const vj_prep* p, vj_image* out, uint64_t* bytes);
+/* frames: host or device-resident, 1 / 3 / 4 channels, any strides, sizes may differ.  d_dst: device memory of at least the layout's
+ * `bytes` (dst_bytes says how many there are).  out[i]: gray, on_device = 1, data inside d_dst.  Returns after the work is complete.
+ * All checks come before the device is used.  VJ_ERR_ARG, with vj_last_error naming the frame or the field: null arguments; a frame
+ * with null data, w <= 0, h <= 0, another channel count or stride < w * channels; one of dst_w / dst_h, or of fx / fy, set without
+ * the other; negative sizes, negative or non-finite factors; unknown flag bits, reserved != 0; dst_bytes below the layout's bytes;
+ * d_dst not a multiple of 4 (device allocations are); a device-resident source that overlaps [d_dst, d_dst + bytes).  VJ_ERR_LIMIT: a source or destination side above 65535 (the taps'
+ * 16-bit indices), or more work units than a 32-bit index holds.  n_frames == 0 is VJ_OK.  Calls of more frames than the configured
+ * "max_subbatch" run in slices.                                                                                                 */
+int  vj_preprocess(vj_env* e, const vj_image* frames, int n_frames, const vj_prep* p, uint8_t* d_dst, uint64_t dst_bytes,
+                   vj_image* out);
+/* Device time of the environment's last vj_preprocess call: events around its copies and launches, in ms.  A null argument: VJ_ERR_ARG. */
+int  vj_preprocess_timing(const vj_env* e, float* ms);
+
 /* ------------------------------------------------------------ frame streams */
 /* Video-style use (the demo's per-frame loop, main.cpp:104-125): batches of host frames are uploaded into
  * one of two device buffers by DMA on a copy stream while the kernels of the previous batch run, and the
