@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "vj_cv_roi_units.hpp"
 #include "vj_sq_strips.hpp"
+#include "vj_gather_queue.hpp"
 
 namespace vj {
 
@@ -134,12 +135,18 @@ struct SpBlock {
     uint32_t desc;         // jn | jb << 8 | b << 16 | nb << 20 | stage << 24
 };
 
-constexpr int UNIT_WINDOWS = 512;   // windows per wave-unit == per-wave LDS queue capacity
+constexpr int UNIT_WINDOWS = 512;   // windows per wave-unit == per-wave LDS queue capacity (the linear cascade_pass above 4 waves: CascadeArgs::q_cap)
 constexpr int WAVES_PER_BLOCK = 3;    // waves per workgroup of the global-gather kernels: with one workgroup per CU next to the tile
-                                      // chain, 2 starve the gather chain (+12 ms); batches run 4 (GATHER_WAVES_MAX: the gather chain is
-                                      // 11 % faster, the tiles 1 % slower, and the balance moves three quarters of a scale further:
-                                      // profiles/r03_notes.md #6g), single frames and stage trees 3 (CascadeArgs::gather_waves)
-constexpr int GATHER_WAVES_MAX = 4;   // (the workgroup's queues: 4 KiB of LDS per wave, 16 KiB = what the tile classes leave free)
+                                      // chain, 2 starve the gather chain (+12 ms); 4 made the gather chain 11 % faster and the tiles 1 %
+                                      // slower (profiles/r03_notes.md #6g); single frames and stage trees run 3 (CascadeArgs::gather_waves)
+constexpr int GATHER_WAVES_FULL = 4;  // the most waves with full queues: 4 KiB of LDS per wave, 16 KiB = what the tile classes leave free.  Stage
+                                      // trees (a second array) stay at WAVES_PER_BLOCK; cascade_roi_pass takes up to this many
+constexpr int GATHER_WAVES_MAX = 8;   // the linear cascade_pass divides the SAME 16 KiB among up to 8 waves (vj_gather_queue.hpp: 384 entries
+                                      // per wave at 5, 320 at 6, 256 at 7 and 8), and the plan cuts its first-pass units to match.  Batches of
+                                      // 8 frames and more run 8: the chain is 21 % faster at the same balance, the tiles 3 % slower, and the
+                                      // balance moves one and a half scales further (profiles/r15_notes.md)
+static_assert(GATHER_WAVES_MAX == (int)GATHER_WAVES_LIMIT && UNIT_WINDOWS == (int)GATHER_QUEUE_CAP_MAX &&
+              GATHER_WAVES_FULL * UNIT_WINDOWS == (int)GATHER_LDS_ENTRIES, "vj_gather_queue.hpp describes these queues");
 constexpr int MAX_SCALES = 128;
 constexpr int MAX_PASSES = 8;         // == VJ_MAX_PASSES
 constexpr uint32_t Q_PARTS = 8;       // parts of a scale's survivor-queue segment, by frame group (one per XCD to drain)
@@ -178,7 +185,8 @@ struct CascadeArgs {
     uint32_t stride;            // elements per image row (W + 1)
     uint32_t stage_begin, stage_end;  // stages [begin, end) evaluated by this pass
     uint32_t total_waves;       // gridDim.x * gather_waves
-    uint32_t gather_waves;      // waves per workgroup of cascade_pass / cascade_roi_pass (3 or 4; stage trees: 3)
+    uint32_t gather_waves;      // waves per workgroup of cascade_pass / cascade_roi_pass (linear cascade_pass: 1 ... 8; cascade_roi_pass: <= 4; stage trees: 3)
+    uint32_t q_cap;             // entries of a wave's LDS queue: gather_queue_cap(gather_waves) in the linear cascade_pass, else UNIT_WINDOWS
     const QEntry*   q_in;       // survivor queue read by this pass (passes > 0)
     const uint32_t* q_in_count; // entry counts of q_in, [scale][Q_PARTS]
     uint32_t* q_ticket;         // Q_PARTS ticket counters of this pass, zeroed before the launch: a queue pass's chunks, the grid pass's units (vj_grid_parts.hpp)
@@ -231,7 +239,7 @@ struct CascadeArgs {
     // null = every grid window (the OpenCL kernel's contract)
     unsigned long long* skip_bits;      // [n_frames][skip_frame_words]
     uint32_t  skip_frame_words;
-    uint32_t  sp_tail_max;              // global-gather sweeps: at most this many windows left in a wave -> stump-parallel tail (0: off; <= 48)
+    uint32_t  sp_tail_max;              // global-gather sweeps: at most this many windows left in a wave -> stump-parallel tail (0: off; <= gather_tail_max(q_cap))
     uint32_t  max_stage_nodes;          // nodes of the cascade's largest stage
     uint32_t  gather_pairs;             // global-gather sweeps evaluate two stumps per step: 0 never, 1 when the wave holds one chunk, 2 always
     uint32_t  pos_mode;                 // window_pos(): bit 0 = round half away from zero (clod.cpp:1416) instead of lrint (:514); bit 1: the block variant's f64 grid (ScaleDev::pos_base tables)

@@ -89,8 +89,9 @@ struct PlanBuildOptions {
     std::vector<std::pair<uint32_t, uint32_t>>* tile_reach = nullptr;
 };
 
+// n_frames: the size of the calls the plan is for — it decides the gather chain's wave count and with it the size of the first-pass units.
 static int build_plan(const vj_env* e, const vj_cascade& c, int W, int H, const vj_params& p, Plan* pl, float tile_split,
-                      const TileThresholds& thresholds, bool one_pass = false, const PlanBuildOptions& opt = PlanBuildOptions()) {
+                      const TileThresholds& thresholds, int n_frames, bool one_pass = false, const PlanBuildOptions& opt = PlanBuildOptions()) {
     pl->tile_split = tile_split;
     if ((int)c.stages.size() > VJ_MAX_STAGES) {
         set_error("cascade has %zu stages; at most %d are supported", c.stages.size(), VJ_MAX_STAGES);
@@ -433,23 +434,21 @@ static int build_plan(const vj_env* e, const vj_cascade& c, int W, int H, const 
         }
     }
     // first-pass units of the global-gather path: whole scales, and the rows of split scales the tiles leave
+    pl->unit_cap = e->unit_cap_for(n_frames, pl->general, pl->trees);
     for (uint32_t slot = 0; slot < pl->scales.size(); ++slot) {
         const ScaleDev& sd = pl->scales[slot];
         const uint32_t row0 = sd.tile_row_end;
         if (row0 >= sd.ny) continue;
-        if (e->grid_block_w > 0 && sd.nx < 65536 && sd.ny < 65536) {
-            // 2-D blocks of <= UNIT_WINDOWS windows: a compact footprint in the sum image per wave (a row run
-            // of 512 windows drags a full-width band of 20 s rows through the L2)
-            const uint32_t bw = std::min<uint32_t>((uint32_t)e->grid_block_w, sd.nx);
-            const uint32_t bh = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)UNIT_WINDOWS / bw, sd.ny));
-            for (uint32_t iy0 = row0; iy0 < sd.ny; iy0 += bh)
-                for (uint32_t ix0 = 0; ix0 < sd.nx; ix0 += bw)
-                    pl->units.push_back(UnitDev{slot, ix0 | (iy0 << 16), bw * bh, bw});
-        } else {
-            for (uint32_t f = row0 * sd.nx; f < sd.nwin; f += UNIT_WINDOWS)
-                pl->units.push_back(UnitDev{slot, f, std::min<uint32_t>(UNIT_WINDOWS, sd.nwin - f), 0});
-        }
+        // 2-D blocks of <= unit_cap windows (what a wave's queue holds at this plan's wave count): a compact footprint in the
+        // sum image per wave (a row run of 512 windows drags a full-width band of 20 s rows through the L2)
+        gather_cut_units(sd.nx, sd.ny, row0, (uint32_t)std::max(0, e->grid_block_w), pl->unit_cap,
+                         [&](uint32_t first, uint32_t count, uint32_t bw) { pl->units.push_back(UnitDev{slot, first, count, bw}); });
     }
+    for (const UnitDev& u : pl->units)
+        if (u.count > pl->unit_cap) {
+            set_error("internal error: a first-pass unit of %u windows for queues of %u", u.count, pl->unit_cap);
+            return VJ_ERR_LIMIT;
+        }
     // Band-major order: the units of a frame sorted by the image band their top row lies in, then by scale — the waves of an
     // XCD (which take a contiguous run of the (frame, unit) list) then gather from ONE band of the sum image across all scales
     // instead of sweeping the frame once per scale — and, for the queue pass, groups of consecutive units of one (band, scale).
@@ -465,7 +464,8 @@ static int build_plan(const vj_env* e, const vj_cascade& c, int W, int H, const 
         std::stable_sort(keyed.begin(), keyed.end(), [](const auto& a, const auto& b) {
             return std::make_tuple(a.first, a.second.scale) < std::make_tuple(b.first, b.second.scale);   // (stable: blocks stay row-major inside)
         });
-        const uint32_t G = (uint32_t)std::max(1, e->q_group_units);
+        // (q_group_units counts units of UNIT_WINDOWS windows: a plan with shorter units groups as many windows)
+        const uint32_t G = std::max<uint32_t>(1u, (uint32_t)std::max(1, e->q_group_units) * pl->unit_cap / (uint32_t)UNIT_WINDOWS);
         for (size_t i = 0; i < keyed.size(); ++i) {
             pl->units[i] = keyed[i].second;
             if (pl->unit_groups.empty() || pl->unit_groups.back().bw != keyed[i].first || pl->unit_groups.back().scale != keyed[i].second.scale ||
@@ -704,6 +704,22 @@ static int small_frame_class(const vj_env* e, int W, int H, int n_frames) {
     return px <= 115200 ? 2 : px <= 460800 ? 1 : 0;
 }
 
+// A linear cascade of stumps: the cascades whose batches run eight gather waves and the balance that goes with them
+// (Tunables::gather_waves_for, split_for).
+static bool has_trees(const vj_cascade& c) {
+    for (const auto& t : c.trees)
+        if (t.n_nodes != 1) return true;
+    return false;
+}
+static bool linear_stumps(const vj_cascade& c) {
+    if (has_trees(c)) return false;
+    const StageProgram prog = build_stage_program(c);
+    for (size_t s = 0; s < c.stages.size(); ++s)
+        if (!(prog.on_fail[s] == STAGE_REJECT && (prog.on_pass[s] == (int)s + 1 || (prog.on_pass[s] == STAGE_ACCEPT && s + 1 == c.stages.size()))))
+            return false;
+    return true;
+}
+
 // The workload whose chain balance is being found (or was found) by feedback: batches of >= 8 frames through vj_detect.
 static vj_env::BalanceKey balance_key(const vj_env* e, const vj_cascade* c, int W, int H, const vj_params& p, int n_frames) {
     return vj_env::BalanceKey(vj_env::PlanKey(c->content_hash, W, H, p.min_w, p.min_h, p.max_w, p.max_h, f2u(p.scale_factor), p.scale_mask[0],
@@ -730,7 +746,7 @@ static vj_env::Balance* balance_of(vj_env* e, const vj_cascade* c, int W, int H,
         e->balance.erase(lru);
     }
     vj_env::Balance b;
-    b.cur = b.best = e->split_for(n_frames, p);
+    b.cur = b.best = e->split_for(n_frames, p, linear_stumps(*c));
     b.n_ref = n_frames;
     b.last_used = ++e->balance_tick;
     return &(e->balance[key] = b);
@@ -917,14 +933,15 @@ static TileThresholds thresholds_for(const vj_env* e, int small) {
 
 static int get_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_params& p, Plan** out, int n_frames = 1 << 20) {
     const vj_env::Balance* bal = balance_of(e, c, W, H, p, n_frames, false);
-    const BalanceChoice choice = bal ? balance_choice(bal, n_frames) : BalanceChoice{e->split_for(n_frames, p), 0, false};
+    const BalanceChoice choice = bal ? balance_choice(bal, n_frames) : BalanceChoice{e->split_for(n_frames, p, linear_stumps(*c)), 0, false};
     const float split = choice.split;
     int small = small_frame_class(e, W, H, n_frames);
     if (small == 0 && choice.thr == 1 && !e->tile_thresholds_set) small = 3;   // the feedback's lower thresholds
     // (frames of 720p and more: below that the queue pass costs nothing — 640 x 480 0.473 / 0.476 ms with / without it, 320 x 240 the same)
     const bool one_pass = n_frames <= e->one_pass_max_frames && (uint64_t)W * (uint64_t)H >= 800000ull;
     vj_env::PlanKey key(c->uid, W, H, p.min_w, p.min_h, p.max_w, p.max_h, f2u(p.scale_factor), p.scale_mask[0],
-                        p.scale_mask[1], (p.flags & (VJ_FLAG_SKIP_LIST | VJ_FLAG_SKIP_ROW | VJ_FLAG_GRID_F64 | VJ_FLAG_TILTED_AS_UPRIGHT)) | ((uint32_t)small << 8) | ((uint32_t)one_pass << 12), f2u(split));
+                        p.scale_mask[1], (p.flags & (VJ_FLAG_SKIP_LIST | VJ_FLAG_SKIP_ROW | VJ_FLAG_GRID_F64 | VJ_FLAG_TILTED_AS_UPRIGHT)) | ((uint32_t)small << 8) | ((uint32_t)one_pass << 12) |
+                            ((e->unit_cap_for(n_frames, false, has_trees(*c)) / 64u) << 16), f2u(split));   // (bits 16-19: the first-pass units' size, which follows the wave count)
     auto it = e->plans.find(key);
     if (it != e->plans.end()) {
         it->second->last_used = ++e->plan_tick;
@@ -944,7 +961,7 @@ static int get_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_param
         }
     }
     auto pl = std::make_unique<Plan>();
-    int rc = build_plan(e, *c, W, H, p, pl.get(), split, thresholds_for(e, small), one_pass);
+    int rc = build_plan(e, *c, W, H, p, pl.get(), split, thresholds_for(e, small), n_frames, one_pass);
     if (rc) {
         pl->release_device();
         return rc;
@@ -1367,8 +1384,11 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
         ca.sum_bytes = (uint32_t)((uint64_t)pl->frame_elems * 4u * (uint64_t)nf);
         ca.stride = (uint32_t)W + 1u;
         // waves per workgroup of the gather chain: four for batches, three for single frames and for stage trees (their
-        // workgroups carry a second LDS array); the launchers clamp, the kernels read blockDim
-        ca.gather_waves = (uint32_t)e->gather_waves_for(nf, pl->general);
+        // workgroups carry a second LDS array); the launchers clamp, the kernels read blockDim.  The waves of a linear launch
+        // divide one 16 KiB array (vj_gather_queue.hpp), and the plan's units must fit a wave's share: a plan cut for fewer
+        // waves than this call would run (a stream's plan, a sub-batch) keeps the call at the waves it was cut for
+        ca.gather_waves = gather_waves_fitting((uint32_t)e->gather_waves_for(nf, pl->general, pl->trees), pl->unit_cap);
+        ca.q_cap = pl->general ? (uint32_t)UNIT_WINDOWS : gather_queue_cap(ca.gather_waves);
         ca.total_waves = (uint32_t)n_blocks * ca.gather_waves;
         ca.det = (DetEntry*)L->d_det.p;
         ca.det_count = d_det_count;
@@ -1400,7 +1420,7 @@ static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const
         ca.pos_mode = pl->pos_mode;
         ca.pos_tab = (const uint32_t*)pl->d_pos_tab.p;
         ca.gather_pairs = e->pairs_for(nf);
-        ca.sp_tail_max = (uint32_t)std::max(0, std::min(e->sp_tail_max, 48));
+        ca.sp_tail_max = (uint32_t)std::max(0, std::min(e->sp_tail_max, (int)gather_tail_max(ca.q_cap)));
         ca.max_stage_nodes = pl->max_stage_nodes;
         if (pl->skip_mode && pl->n_skip_units) {
             // the windows the reference's sequential CPU loop visits, as a bitmap: stage-0 verdict of every grid window,
@@ -1893,7 +1913,8 @@ static void fill_region_args(vj_env* e, Lane* L, Plan* pl2, const vj_cascade* se
     ca.frame_elems = pl2->frame_elems;
     ca.sum_bytes = (uint32_t)((uint64_t)pl2->frame_elems * 4u * (uint64_t)nf);
     ca.stride = stride;
-    ca.gather_waves = (uint32_t)e->gather_waves_for(nf, pl2->general);
+    ca.gather_waves = (uint32_t)std::min(e->gather_waves_for(nf, pl2->general, pl2->trees), (int)GATHER_WAVES_FULL);   // the region pass keeps full queues
+    ca.q_cap = (uint32_t)UNIT_WINDOWS;
     ca.stage_begin = 0;
     ca.stage_end = pl2->general ? pl2->pass_bounds.back() : (uint32_t)pl2->stages.size();   // stage trees: positions in the sweep order
     ca.identity_order = pl2->general ? 0u : 1u;
@@ -1902,7 +1923,7 @@ static void fill_region_args(vj_env* e, Lane* L, Plan* pl2, const vj_cascade* se
     ca.pos_mode = pl2->pos_mode;   // (0 on this path: check_params sends the f64 grids through the per-size plans; bound all the same)
     ca.pos_tab = (const uint32_t*)pl2->d_pos_tab.p;
     ca.gather_pairs = 2u;   // regions are small: thin waves, latency-bound
-    ca.sp_tail_max = (uint32_t)std::max(0, std::min(e->sp_tail_max, 48));
+    ca.sp_tail_max = (uint32_t)std::max(0, std::min(e->sp_tail_max, (int)gather_tail_max(ca.q_cap)));
     ca.max_stage_nodes = pl2->max_stage_nodes;
     ca.stage_entered = (unsigned long long*)(roi_counts + 8);
     ca.tree_ctr = (unsigned long long*)((uint32_t*)L->d_counts.p + CountsLayout::stage_off_u32) + 2;   // the spare array's [2], [3]: the region pass's
@@ -2363,7 +2384,7 @@ const Key KEYS[] = {
     special("balance_import", [](vj_env* e, const char* path) { return balance_import(e, path); }, nullptr),
     // global-gather chain
     clamped("grid_block_w", &Tunables::grid_block_w, 0, UNIT_WINDOWS, DROP_PLANS),
-    clamped("gather_waves", &Tunables::gather_waves, INT_MIN, MAX),   // 3, 4, or -1 = 4 for calls of >= 8 frames
+    clamped("gather_waves", &Tunables::gather_waves, INT_MIN, MAX, DROP_PLANS),   // 1 ... 8, or -1 = 4 for calls of >= 8 frames; the first-pass units follow it
     with_auto("gather_pairs", &Tunables::gather_pairs, 0, 2),
     clamped("sp_tail_max", &Tunables::sp_tail_max, 0, 48),
     with_auto("wide_tail", &Tunables::wide_tail, 0, 1),
@@ -3148,7 +3169,7 @@ int vj_stream_create(vj_env* e, const vj_cascade* c, int width, int height, int 
     const vj_env::Balance* bal = balance_of(e, c, width, height, *p, max_batch, false);
     TileThresholds sth{e->tile_min_windows, e->tile_accept_windows, e->tile_max_dwords_per_window};
     if (bal && balance_choice(bal, -1).thr == 1 && !e->tile_thresholds_set) sth = TileThresholds{std::min(384, sth.min_windows), std::min(384, sth.accept_windows), sth.max_dwords_per_window};
-    int rc = build_plan(e, *c, width, height, *p, s->plan.get(), bal ? bal->best : e->split_for(max_batch, *p), sth);
+    int rc = build_plan(e, *c, width, height, *p, s->plan.get(), bal ? bal->best : e->split_for(max_batch, *p, linear_stumps(*c)), sth, max_batch);
     if (rc) {
         s->plan->release_device();
         return rc;
@@ -3266,8 +3287,8 @@ static int plan_tiles_query(const vj_cascade* c, int width, int height, const vj
     opt.former_shapes = (flags & VJ_PLAN_TILES_FORMER_SHAPES) != 0u;
     opt.tile_reach = &reach;
     const bool one_pass = n_frames <= e->one_pass_max_frames && (uint64_t)width * (uint64_t)height >= 800000ull;
-    rc = build_plan(e.get(), *c, width, height, *p, &pl, tile_split < 0.0f ? e->split_for(n_frames, *p) : tile_split,
-                    thresholds_for(e.get(), small_frame_class(e.get(), width, height, n_frames)), one_pass, opt);
+    rc = build_plan(e.get(), *c, width, height, *p, &pl, tile_split < 0.0f ? e->split_for(n_frames, *p, linear_stumps(*c)) : tile_split,
+                    thresholds_for(e.get(), small_frame_class(e.get(), width, height, n_frames)), n_frames, one_pass, opt);
     if (rc) return rc;
     // the windows every first-pass unit of the gather chain covers, clipped to its scale's grid as the grid pass clips them
     std::vector<uint64_t> unit_windows(pl.scales.size(), 0);

@@ -940,8 +940,9 @@ struct FailSink {
 // bits, and afterwards lane w adds window w's leaf values IN STUMP ORDER from the bits — the reference's sequence of f32
 // additions (clod.cl:81; the leaf values come through the scalar cache).  Scratch: the unused part of the wave's LDS
 // queue (the verdict words).  Per stage the cost is windows x blocks instead of stumps, so it pays below ~64 windows.
-constexpr uint32_t SP_TAIL_MAX = 48;          // windows at most: 48 entries (384 B) + 48 x 9 verdict words (3456 B) fit the wave's 4 KiB queue
-constexpr uint32_t SP_TAIL_MAX_BLOCKS = 9;    // blocks of 64 stumps per stage at most (stages of <= 576 nodes)
+// windows at most: gather_tail_max(a.q_cap) — 48 entries (384 B) + 48 x 9 verdict words (3456 B) fit a 4 KiB queue of 512 entries, 32 + 32 x 9
+// one of 320, 24 + 24 x 9 one of 256 (vj_gather_queue.hpp states the fit for every capacity); the words start behind that many entries
+constexpr uint32_t SP_TAIL_MAX_BLOCKS = GATHER_TAIL_BLOCKS;    // blocks of 64 stumps per stage at most (stages of <= 576 nodes)
 constexpr uint32_t SP_TAIL_MAX_NODES = SP_TAIL_MAX_BLOCKS * 64u;
 #ifndef VJ_TAIL_NW
 #define VJ_TAIL_NW 2
@@ -953,7 +954,7 @@ __device__ __forceinline__ uint32_t sweep_tail_stump_parallel(const CascadeArgs&
                                                               uint32_t lane, uint32_t begin, uint32_t end, FailSink fail) {
     kptr<StageDev> stages = as_k(a.stages);
     const GlobalImgByStump img{img_r};
-    unsigned long long* masks = reinterpret_cast<unsigned long long*>(q + SP_TAIL_MAX);          // [window][block]
+    unsigned long long* masks = reinterpret_cast<unsigned long long*>(q + gather_tail_max(a.q_cap));   // [window][block]; n <= a.sp_tail_max <= that
     for (uint32_t pos = begin; pos < end && n != 0u; ++pos) {
         const uint32_t s = a.identity_order != 0u ? pos : stages[pos].order;
         const uint32_t first_node = stages[s].first_node, n_nodes = stages[s].n_nodes;
@@ -1280,12 +1281,15 @@ __device__ __forceinline__ void run_stages_general(const CascadeArgs& a, rsrc_t 
 template <bool FROM_GRID, bool TREES, bool LAST, bool COUNT, bool GENERAL, int NW = 1>
 __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArgs a) {
     // (stage trees are launched with WAVES_PER_BLOCK waves: their second array would not fit next to the tiles otherwise)
-    __shared__ QEntry lds_q[(GENERAL ? WAVES_PER_BLOCK : GATHER_WAVES_MAX) * UNIT_WINDOWS];
+    // Linear cascades: 16 KiB whatever the wave count; the launch's waves divide it (a.q_cap entries each: vj_gather_queue.hpp)
+    __shared__ QEntry lds_q[GENERAL ? WAVES_PER_BLOCK * UNIT_WINDOWS : (int)GATHER_LDS_ENTRIES];
     __shared__ int32_t lds_tgt[GENERAL ? WAVES_PER_BLOCK * UNIT_WINDOWS : 1];
+    static_assert(GATHER_LDS_ENTRIES * sizeof(QEntry) == 16384, "the gather workgroup's LDS stays 16 KiB");
     const uint32_t lane = lane_id();
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t wpb = blockDim.x >> 6;     // the host's choice (CascadeArgs::gather_waves, clamped by the launcher)
-    QEntry* q = lds_q + wib * UNIT_WINDOWS;
+    const uint32_t cap = GENERAL ? (uint32_t)UNIT_WINDOWS : a.q_cap;   // entries of this wave's queue (the launcher: wpb * cap fits the array)
+    QEntry* q = lds_q + wib * cap;
     kptr<ScaleDev> scales = as_k(a.scales);
     // the whole batch of sum images behind one descriptor (host keeps it below 4 GiB)
     const rsrc_t img = make_rsrc(a.sum, a.sum_bytes);
@@ -1398,13 +1402,13 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
             // (in the first entry of every wave's queue, which is free now: no LDS beyond what the shipped kernel takes)
             static_assert(sizeof(QEntry) == sizeof(unsigned long long), "a stamp fits a queue entry");
             unsigned long long* lds_end = reinterpret_cast<unsigned long long*>(lds_q);
-            if (lane == 0) lds_end[wib * UNIT_WINDOWS] = __builtin_amdgcn_s_memrealtime();
+            if (lane == 0) lds_end[wib * cap] = __builtin_amdgcn_s_memrealtime();
             __syncthreads();
             if (threadIdx.x == 0) {
                 unsigned long long last = 0, sum = 0;
                 for (uint32_t w = 0; w < wpb; ++w) {
-                    last = max(last, lds_end[w * UNIT_WINDOWS]);
-                    sum += lds_end[w * UNIT_WINDOWS];
+                    last = max(last, lds_end[w * cap]);
+                    sum += lds_end[w * cap];
                 }
                 const unsigned long long tail = last - sum / wpb;
                 atomicAdd(a.stage_entered + 40, tail);      // sum over workgroups: last wave's end - mean wave end
@@ -1448,7 +1452,7 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
                 const size_t ri = ((size_t)frame * a.n_units + u0 + k) * 2u;
                 const uint32_t g = runs[ri], n = runs[ri + 1u];
                 if (n == 0u) continue;
-                if (n_q + n > (uint32_t)UNIT_WINDOWS) {   // the wave's queue is full: sweep what it holds first
+                if (n_q + n > cap) {   // the wave's queue is full: sweep what it holds first (n <= cap: a unit's windows)
                     __builtin_amdgcn_wave_barrier();
                     run_stages_linear<TREES, LAST, COUNT, NW>(a, img, q, n_q, slot, scales[slot].table_first, q_base, lane, a.stage_begin, part);
                     __builtin_amdgcn_wave_barrier();
@@ -1492,7 +1496,7 @@ __global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_pass(CascadeArg
         // then spreads over two waves instead of sitting in one (16 and 8 make the populous passes of a stage tree slower).
         const uint32_t min_chunk = max(1u, min(a.min_chunk, 64u));
         const uint32_t per_wave = total / a.total_waves;
-        const uint32_t chunk = per_wave >= 64u ? min((uint32_t)UNIT_WINDOWS, ((per_wave + 63u) / 64u) * 64u)
+        const uint32_t chunk = per_wave >= 64u ? min(cap, ((per_wave + 63u) / 64u) * 64u)
                                                : max(min_chunk, ((per_wave + min_chunk - 1u) / min_chunk) * min_chunk);
         // Fewer chunks than waves (a late pass, a single frame): whichever waves draw the tickets first get the
         // chunks, and with 24 resident waves per CU some CUs end up with twice the average — the pass then waits for
@@ -1748,8 +1752,8 @@ __global__ __launch_bounds__(256) void roi_plan_units(RoiArgs r, CascadeArgs a) 
 }
 
 template <bool TREES, bool COUNT, bool GENERAL>
-__global__ __launch_bounds__(GATHER_WAVES_MAX * 64) void cascade_roi_pass(RoiArgs r, CascadeArgs a) {
-    __shared__ QEntry lds_q[(GENERAL ? WAVES_PER_BLOCK : GATHER_WAVES_MAX) * UNIT_WINDOWS];
+__global__ __launch_bounds__(GATHER_WAVES_FULL * 64) void cascade_roi_pass(RoiArgs r, CascadeArgs a) {
+    __shared__ QEntry lds_q[(GENERAL ? WAVES_PER_BLOCK : GATHER_WAVES_FULL) * UNIT_WINDOWS];   // (full queues: a.q_cap == UNIT_WINDOWS)
     __shared__ int32_t lds_tgt[GENERAL ? WAVES_PER_BLOCK * UNIT_WINDOWS : 1];   // stage trees: the stage every queued window visits next
     const uint32_t lane = lane_id();
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1838,15 +1842,25 @@ static void launch_roi_pass(const RoiArgs& r, const CascadeArgs& a, bool trees, 
 }
 
 // Threads per workgroup of the global-gather kernels: the host's choice (CascadeArgs::gather_waves), within what the kernels' LDS
-// arrays hold; the kernels read the same field.
-static uint32_t gather_block_threads(const CascadeArgs& a, bool general) {
-    const uint32_t most = general ? (uint32_t)WAVES_PER_BLOCK : (uint32_t)GATHER_WAVES_MAX;
+// arrays hold; the kernels read the same field.  Only the linear cascade_pass divides its array by the wave count (`divided`:
+// the host passes a.q_cap = gather_queue_cap(waves)); stage trees and the region pass keep queues of UNIT_WINDOWS entries and
+// clamp the waves.
+static uint32_t gather_block_threads(const CascadeArgs& a, bool general, bool divided = false) {
+    const uint32_t most = general ? (uint32_t)WAVES_PER_BLOCK : (divided ? (uint32_t)GATHER_WAVES_MAX : (uint32_t)GATHER_WAVES_FULL);
     return 64u * std::min(std::max(a.gather_waves, 1u), most);
+}
+// What the host owes a gather launch: the waves' queues fit the kernel's LDS array, and the stump-parallel tail's scratch a queue.
+static bool gather_queues_fit(const CascadeArgs& a, bool general, bool divided) {
+    const uint32_t waves = gather_block_threads(a, general, divided) / 64u;
+    const uint32_t entries = general ? (uint32_t)(WAVES_PER_BLOCK * UNIT_WINDOWS) : (divided ? GATHER_LDS_ENTRIES : (uint32_t)(GATHER_WAVES_FULL * UNIT_WINDOWS));
+    const bool cap_ok = divided && !general ? a.q_cap >= 64u && a.q_cap % 64u == 0u && a.q_cap <= (uint32_t)UNIT_WINDOWS : a.q_cap == (uint32_t)UNIT_WINDOWS;
+    return cap_ok && waves * a.q_cap <= entries && a.sp_tail_max <= gather_tail_max(a.q_cap);
 }
 
 int launch_roi_chain(const RoiArgs& r, const CascadeArgs& a, bool from_dets, bool trees, bool count, bool general, int n_blocks,
                      void* stream_, void* stream2_, void* fork_ev_, void* join_ev_) {
     hipStream_t stream = (hipStream_t)stream_, stream2 = (hipStream_t)stream2_;
+    if (!gather_queues_fit(a, general, false)) return (int)hipErrorInvalidValue;
     if (from_dets) hipLaunchKernelGGL(dets_to_rois, dim3(256), dim3(256), 0, stream, r);
     hipLaunchKernelGGL(roi_plan_units, dim3(512), dim3(256), 0, stream, r, a);
     dim3 g(n_blocks), b(gather_block_threads(a, general));
@@ -2770,7 +2784,7 @@ int launch_cascade_tile_pass(const CascadeArgs& a, bool trees, bool count, int n
 
 template <bool FROM_GRID, bool TREES>
 static void launch_variant(const CascadeArgs& a, bool last, bool count, int n_blocks, hipStream_t stream) {
-    dim3 g(n_blocks), b(gather_block_threads(a, false));
+    dim3 g(n_blocks), b(gather_block_threads(a, false, true));
     if constexpr (!FROM_GRID && !TREES) {
         if (a.wide_tail != 0u) {   // queue passes of a small batch: TAIL_NW windows per step of the stump-parallel tail
             if (last) {
@@ -2802,6 +2816,7 @@ static void launch_general(const CascadeArgs& a, bool count, int n_blocks, hipSt
 int launch_cascade_pass(const CascadeArgs& a, bool from_grid, bool trees, bool last, bool count, bool general,
                         int n_blocks, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    if (!gather_queues_fit(a, general, true)) return (int)hipErrorInvalidValue;
     if (general) {  // stage-tree cascade: everything (from the grid) or everything after the linear prefix (from its queue)
         if (!last) return (int)hipErrorInvalidValue;
         if (from_grid) {
