@@ -156,7 +156,7 @@ static std::vector<StageDev> build_cv_stage_recs(const vj_cascade* c, const Stag
         // an f64 product per rectangle only on cvRunHaarClassifierCascadeSum's stump path (:863-888)
         stages[s].cv_f64 = (two_rects[s] && !trees && !is_tree) ? 1u : 0u;
         // wave-split finish of the tile kernel: bound on the difference between any two summation orders of the stage's
-        // leaf values (the f32 form of the clod profile's bound, build_plan; the kernel scales it to f64's unit roundoff)
+        // leaf values (the f32 form of the clod profile's bound, stage_records in vj_clod_plan.cpp; the kernel scales it to f64's unit roundoff)
         double amax = 0.0;
         for (int t = 0; t < c->stages[s].n_trees; ++t) {
             const vj_tree_desc& td = c->trees[c->stages[s].first_tree + t];

@@ -379,10 +379,10 @@ static_assert(sizeof(CvScaleDev) == 88, "CvScaleDev is 88 bytes");
 // (vj_detect_opencv), so that every sub-queue lies inside the buffer
 constexpr uint64_t CV_TQ_MAX = 1ull << 28;
 // one sub-queue: 1 / 2^shift of the scale's grid windows in the batch, at least 4096 entries
-__host__ __device__ inline uint64_t cv_tq_cap(uint32_t end_x, uint32_t end_y, uint32_t n_frames, uint32_t shift) {
+VJ_HD inline uint64_t cv_tq_cap(uint32_t end_x, uint32_t end_y, uint32_t n_frames, uint32_t shift) {
     return (((uint64_t)end_x * end_y * n_frames) >> shift) + 4096u;
 }
-__host__ __device__ inline uint64_t cv_tq_first(uint32_t tq_win_first, uint32_t tq_slot, uint32_t n_frames, uint32_t shift) {
+VJ_HD inline uint64_t cv_tq_first(uint32_t tq_win_first, uint32_t tq_slot, uint32_t n_frames, uint32_t shift) {
     return (((uint64_t)tq_win_first * n_frames) >> shift) + (uint64_t)tq_slot * 4096u;
 }
 

@@ -63,5 +63,8 @@ enum { NODE_LEFT_IS_NODE = 1, NODE_RIGHT_IS_NODE = 2, NODE_TREE_LAST = 4 };
 int build_node_table(const vj_cascade& c, int width, const vj_scale_info& s, NodeRec* recs);
 int build_node_table_stride(const vj_cascade& c, uint32_t stride, const vj_scale_info& s, NodeRec* recs,
                             uint32_t deint_half);
+// Where column cx of an image row sits in a row of that layout: de-interleaved rows (deint_half != 0) keep the even columns
+// first and the odd columns from element deint_half on.
+inline uint32_t deint_col(uint32_t cx, uint32_t deint_half) { return deint_half ? (cx & 1u) * deint_half + (cx >> 1) : cx; }
 
 }  // namespace vj

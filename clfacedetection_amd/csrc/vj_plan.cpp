@@ -77,7 +77,7 @@ int build_node_table(const vj_cascade& c, int width, const vj_scale_info& s, Nod
 // (dw is a signed 16-bit field).
 int build_node_table_stride(const vj_cascade& c, uint32_t stride, const vj_scale_info& s, NodeRec* recs,
                             uint32_t deint_half) {
-    auto col = [deint_half](uint32_t cx) { return deint_half ? (cx & 1u) * deint_half + (cx >> 1) : cx; };
+    auto col = [deint_half](uint32_t cx) { return deint_col(cx, deint_half); };
     const float cs = s.scale;
     const float area = (float)s.area;
     for (size_t t = 0; t < c.trees.size(); ++t) {
@@ -86,7 +86,7 @@ int build_node_table_stride(const vj_cascade& c, uint32_t stride, const vj_scale
             const vj_node_desc& nd = c.nodes[td.first_node + k];
             NodeRec& r = recs[td.first_node + k];
             memset(&r, 0, sizeof(r));
-            // (nd.tilted is not read: precomputeFeatures takes the rectangles as they are, clod.cpp:448-492; build_plan refuses such
+            // (nd.tilted is not read: precomputeFeatures takes the rectangles as they are, clod.cpp:448-492; plan_clod refuses such
             // a cascade unless the caller asks for the reference's reading with VJ_FLAG_TILTED_AS_UPRIGHT)
             if (nd.rect[0].weight == 0.0f || nd.rect[1].weight == 0.0f) {
                 set_error("node %d: rect 0 and rect 1 must both be weighted (clod.cl:60-68 reads both)",

@@ -613,7 +613,7 @@ TUNABLE_SWEEPS = {
     # ---- stage trees
     "general_prefix": [Sweep(("0",), "tree")],
     "tile_segments": [Sweep(("0",), "tree")],
-    # asserted: r.passes are build_plan's rule — every chain longer than value + 4 stages gets a boundary at its start + value
+    # asserted: r.passes are the planner's rule — every chain longer than value + 4 stages gets a boundary at its start + value
     # (8, 4); 3 (not > 3) and 40 (no chain that long) leave the passes alone.  tile_segments and tree_split_queues choose who
     # feeds the new pass
     "seg_cut2": [Sweep(("8", "4", "3", "40"), "tree"), Sweep(("8",), "tree", also=(("tile_segments", "0"),)),
@@ -1238,6 +1238,6 @@ def without_chain(c, chains, k: int):
 
 
 def topology_passes(n_prefix: int, chain_lens) -> int:
-    """The passes build_plan's segment plan needs with seg_cut2 at its default: one for the prefix, two per chain of more than
+    """The passes the planner's segment plan (segment_stage_tree) needs with seg_cut2 at its default: one for the prefix, two per chain of more than
     4 stages, else one."""
     return 1 + sum(2 if ln > 4 else 1 for ln in chain_lens)

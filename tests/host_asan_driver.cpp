@@ -1,7 +1,7 @@
-// Sanitizer driver of the library's host-side sources (cascade parser / loader, scale and feature-table planning,
-// sharding helpers, rectangle grouping): built by tests/test_sanitizers.py with
+// Sanitizer driver of the library's host-side sources (cascade parser / loader, scale and feature-table planning, the clod
+// profile's plan builder, sharding helpers, rectangle grouping): built by tests/test_sanitizers.py with
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off -DVJ_BUILDING
-//       tests/host_asan_driver.cpp csrc/vj_cascade.cpp csrc/vj_plan.cpp csrc/vj_group.cpp
+//       tests/host_asan_driver.cpp csrc/vj_cascade.cpp csrc/vj_plan.cpp csrc/vj_clod_plan.cpp csrc/vj_group.cpp
 // (no HIP involved — GPU AddressSanitizer is not available on the pool).  Malformed and truncated inputs must come back
 // as error codes; every memory error or undefined behaviour aborts the process.
 #include <cstdio>
@@ -32,6 +32,28 @@ static void spit(const std::string& path, const std::string& s) {
     fclose(f);
 }
 
+// The whole clod plan (vj_clod_plan.cpp) of a frame size through the host-only query, with VJ_FLAG_TILTED_AS_UPRIGHT so that
+// a tilted feature does not end the query before any table is built (main asks once without it).  The chain balance, the batch
+// size and the query flag rotate from call to call with periods 4, 8 and 3: every 24 calls meet each combination of the three
+// once.  Error codes are fine, the sanitizers watch the index arithmetic; main prints how many queries gave a plan.
+static int plans_ok = 0, plans_refused = 0;
+static void plan(const vj_cascade* c, int W, int H, const vj_params* params) {
+    static unsigned turn = 0;
+    vj_params upright = *params;
+    upright.flags |= VJ_FLAG_TILTED_AS_UPRIGHT;
+    const vj_params* p = &upright;
+    const float splits[] = {-1.0f, 0.0f, 0.5f, 3.3f};
+    const uint32_t flags[] = {0u, VJ_PLAN_TILES_NO_GROUPS, VJ_PLAN_TILES_FORMER_SHAPES};
+    std::vector<vj_tile_info> tiles(256);
+    std::vector<uint64_t> gather(256);
+    vj_tile_plan_info info;
+    vj_tile_cut_info cut;
+    int n = 0;
+    const int rc = vj_plan_tiles_split(c, W, H, p, (turn / 4u) % 2u ? 64 : 1, flags[turn % 3u], splits[turn % 4u], &info, &cut, tiles.data(), gather.data(), 256, &n);
+    ++(rc == VJ_OK ? plans_ok : plans_refused);
+    ++turn;
+}
+
 // everything the host does with a cascade once it is loaded
 static void exercise(const vj_cascade* c) {
     vj_cascade_info info;
@@ -51,6 +73,7 @@ static void exercise(const vj_cascade* c) {
         std::vector<float> wts((size_t)info.n_nodes * 3);
         for (int i = 0; i < n && i < 256; i += 7)
             if (sc[(size_t)i].accepted) (void)vj_plan_feature_table(c, W, &sc[(size_t)i], off.data(), wts.data());
+        plan(c, W, H, &p);
     }
 }
 
@@ -83,6 +106,10 @@ int main(int argc, char** argv) {
         vj_cascade* c = nullptr;
         if (vj_cascade_load(path.c_str(), &c) != VJ_OK) { fprintf(stderr, "cannot load %s: %s\n", path.c_str(), vj_last_error()); return 1; }
         exercise(c);
+        vj_params tp;
+        vj_params_default(&tp);
+        plan(c, 1920, 1080, &tp);
+        plan(c, 100, 80, &tp);
         const std::string rt = tmp + "/asan_rt.vjc";
         if (vj_cascade_save(c, rt.c_str()) != VJ_OK || slurp(rt) != slurp(path)) { fprintf(stderr, "round trip of %s differs\n", n); return 1; }
         // the in-memory constructor takes the same arrays
@@ -132,6 +159,12 @@ int main(int argc, char** argv) {
         vj_cascade_get_info(c, &info);
         if (info.n_stages != 2 || info.n_trees != 3 || info.n_nodes != 4 || info.n_tilted != 1 || info.max_nodes_per_tree != 2) return 1;
         exercise(c);
+        {   // its tilted node: planned as upright only on request
+            vj_params p;
+            vj_params_default(&p);
+            int n = 0;
+            if (vj_plan_tiles(c, 320, 240, &p, 1, 0, nullptr, nullptr, 0, &n) != VJ_ERR_UNSUPPORTED || !strstr(vj_last_error(), "tilted")) return 1;
+        }
         vj_cascade_free(c);
     }
     {   // the same cascade with a tilted rectangle whose corner (x - h, y + h) lies left of the window: refused at load
@@ -219,6 +252,8 @@ int main(int argc, char** argv) {
         uint32_t n = 1;
         if (vj_group_rectangles(&r, &n, 1, 0.2) != VJ_ERR_ARG) return 1;
     }
-    printf("host_asan_driver: OK (%d cascades accepted, %d inputs refused)\n", loaded, refused);
+    if (plans_ok == 0) { fprintf(stderr, "no plan query gave a plan\n"); return 1; }
+    printf("host_asan_driver: OK (%d cascades accepted, %d inputs refused; %d plan queries gave a plan, %d an error code)\n", loaded, refused,
+           plans_ok, plans_refused);
     return 0;
 }

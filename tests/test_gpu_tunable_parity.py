@@ -221,7 +221,7 @@ def stage_nodes(c):
 
 
 def cut_rule(c, cuts):
-    """default_pass_bounds (vj_env.cpp) for a linear cascade: a boundary after the stage at which the cumulative node count
+    """default_pass_bounds (vj_clod_plan.cpp) for a linear cascade: a boundary after the stage at which the cumulative node count
     reaches each value of pass_cut_nodes (compared as unsigned: -1 is never reached)."""
     nodes, n = stage_nodes(c), c.info.n_stages
     cuts = [v % (1 << 32) for v in cuts]
@@ -239,7 +239,7 @@ def cut_rule(c, cuts):
 
 
 def seg_cut2_rule(base, v, max_passes=8):
-    """build_plan's passes of a stage tree whose part after the prefix is chains of more than four stages (each cut after its
+    """plan_clod's passes of a stage tree whose part after the prefix is chains of more than four stages (each cut after its
     third stage): a chain longer than v + 4 stages gets one more boundary at its start + v when v > 3 and launches are left."""
     assert len(base) >= 3 and len(base) % 2 == 1 and all(base[i][1] - base[i][0] == 3 for i in range(1, len(base), 2)), base
     chains = [(base[i][0], base[i + 1][1]) for i in range(1, len(base), 2)]
@@ -372,7 +372,7 @@ def test_the_workloads_match_the_oracle_at_the_defaults(env, oracle, cascades, w
     run_cell(env, oracle, cascades, (), None, None, (), wl, casc, size, n, None)
 
 
-# one_pass_max_frames is refused by build_plan for cascades of multi-node trees, for stage trees and under a pass_split, and
+# one_pass_max_frames is refused by plan_clod for cascades of multi-node trees, for stage trees and under a pass_split, and
 # by get_plan below 800000 pixels: the passes are the ones without it, and the result is the oracle's all the same
 ONE_PASS_REFUSALS = [  # (id, cascade, workload whose frames are used, size, other settings)
     ("two_node_trees", "frontalface_alt2", "lin_few", (720, 1280), ()),

@@ -1,4 +1,4 @@
-"""The LDS budget of the tile planner (build_plan's shape search) against what a tile launch really allocates, on the host
+"""The LDS budget of the tile planner (search_tile_shape, vj_clod_plan.cpp) against what a tile launch really allocates, on the host
 alone through vj_plan_tiles: every shipped cascade that takes the tile path, four frame sizes (the last one smaller than
 a single full tile), a single frame and a batch.
 

@@ -1,7 +1,7 @@
 """Where the chain balance cuts the tile work, read from the host-only plan query (Cascade.plan_tiles(tile_split=...)), and
 the cells of tests/test_gpu_tile_cut.py: each names a regime of the cut ("the lead of a group is cut while its members keep
 every row"), a split that lands in it is searched through the query, and tests/test_tile_cut_cpu.py asserts that every cell
-still finds one — nothing here restates build_plan's rounding rule.
+still finds one — nothing here restates the planner's rounding rule.
 
 A call of 5 .. 7 frames caps its split at 0.5 (vj_env::split_for), so the cells that need a deeper cut run 8 frames."""
 import math
