@@ -9,7 +9,7 @@ from .api import (  # noqa: F401
     CLOD_BLOCK_IMPLEMENTATION, CLOD_PER_STAGE_ITERATIONS, CLOD_PRECOMPUTE_FEATURES,
     CV_HAAR_DO_CANNY_PRUNING, CV_HAAR_DO_ROUGH_SEARCH, CV_HAAR_FIND_BIGGEST_OBJECT, CV_HAAR_SCALE_IMAGE, VJ_FLAG_CV_CANNY_PRUNING, VJ_FLAG_CV_SCALE_IMAGE, VJ_FLAG_CV_FIND_BIGGEST, VJ_FLAG_CV_ROUGH_SEARCH, VJ_FLAG_CV_CHAIN_DEVICE, VJ_FLAG_EQUALIZE_HIST,
     VJ_FLAG_COUNTERS, VJ_FLAG_SIGNED_MEAN, VJ_FLAG_GRID_F64, VJ_FLAG_TILTED_AS_UPRIGHT, VJ_FLAG_SKIP_LIST, VJ_FLAG_SKIP_ROW, Cascade, DetectResult, DeviceFrames, Environment,
-    FrameStream, MixedInfo, MixedOpts, Params, Prep, VJ_PREP_EQUALIZE, VjError, preprocess_layout,
+    ExtractParams, FrameStream, MixedInfo, MixedOpts, Params, Prep, VJ_EXTRACT_GRAY, VJ_EXTRACT_PLANAR, VJ_PREP_EQUALIZE, VjError, extract_layout, preprocess_layout,
     clifIntegral, clodDetectObjects, clodInitBuffers, clodInitEnvironment, clodReleaseBuffers,
     clodReleaseEnvironment, cvHaarDetectObjects, cvHaarDetectObjectsForROC, default_params, group_rectangles,
     cvRunHaarClassifierCascade, group_rectangles_levels, load_library, run_windows_opencv,

@@ -40,6 +40,8 @@ VJ_FLAG_CV_FIND_BIGGEST = 1 << 8     # OpenCV profile: CV_HAAR_FIND_BIGGEST_OBJE
 VJ_FLAG_CV_ROUGH_SEARCH = 1 << 9     # OpenCV profile: CV_HAAR_DO_ROUGH_SEARCH (with find-biggest: the search stops at 0.6 of the object's size, not 0.4)
 VJ_FLAG_CV_CHAIN_DEVICE = 1 << 10    # detect_opencv_chain only (flags of the first cascade): regions and units are built on the device, one wait per sub-batch
 VJ_PREP_EQUALIZE = 1 << 0            # vj_prep.flags: cv::equalizeHist of the resized image (Environment.preprocess(equalize=True))
+VJ_EXTRACT_GRAY = 1 << 0             # vj_extract_params.flags: C = 1, colour sources through BGR2GRAY (Environment.extract(gray=True))
+VJ_EXTRACT_PLANAR = 1 << 1           # vj_extract_params.flags: n x C x h x w instead of n x h x w x C (Environment.extract(planar=True))
 VJ_FLAG_EQUALIZE_HIST = 1 << 11      # cv::equalizeHist on every frame, on the device, in front of detect / detect_opencv / detect_opencv_roc / the mixed calls; refused elsewhere
 
 # cvHaarDetectObjects' flags (tempcv.hpp:127-130).  cvHaarDetectObjects below takes only CV_HAAR_DO_CANNY_PRUNING in its `flags`
@@ -151,6 +153,12 @@ class MixedOpts(C.Structure):
 class Prep(C.Structure):
     """vj_prep"""
     _fields_ = [("dst_w", C.c_int32), ("dst_h", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ExtractParams(C.Structure):
+    """vj_extract_params"""
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("sx", C.c_double), ("sy", C.c_double), ("margin", C.c_double),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class MixedInfo(C.Structure):
@@ -294,6 +302,11 @@ _SIGNATURES = {
     "vj_preprocess_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.POINTER(Prep), C.POINTER(_Image), C.POINTER(C.c_uint64)]),
     "vj_preprocess": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(Prep), C.c_void_p, C.c_uint64, C.POINTER(_Image)]),
     "vj_preprocess_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "vj_extract_default": (None, [C.POINTER(ExtractParams)]),
+    "vj_extract_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(ExtractParams), C.c_void_p,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "vj_extract": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(ExtractParams), C.c_void_p, C.c_uint64]),
+    "vj_extract_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vj_result_free": (None, [C.POINTER(_Result)]),
     "vj_group_rectangles": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_double]),
     "vj_group_rectangles_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double]),
@@ -924,6 +937,73 @@ class Environment:
         _check(load_library().vj_preprocess_timing(self._h, C.byref(ms)), "vj_preprocess_timing")
         return float(ms.value)
 
+    @staticmethod
+    def _extract_args(frames, rects, size, scale, margin, gray, planar, color):
+        """-> (ctypes array of vj_image, n, arrays to keep alive, (n, 5) int32 regions, vj_extract_params).  frames: as preprocess().
+        rects: a RECT_DTYPE array (its frame, x, y, w, h fields) or rows of (frame, x, y, w, h)."""
+        if color or isinstance(frames, (np.ndarray, DeviceFrames)):
+            imgs, n, keep = Environment._images(frames, color)
+        else:
+            imgs, n, keep = Environment._mixed_images(frames)
+        if isinstance(rects, np.ndarray) and rects.dtype.names is not None:
+            r = np.stack([np.asarray(rects[k], np.int32).reshape(-1) for k in ("frame", "x", "y", "w", "h")], axis=1)
+        else:
+            r = np.asarray(rects)
+            if r.size and not np.issubdtype(r.dtype, np.integer):
+                raise ValueError("rects must be a RECT_DTYPE array or integer rows of (frame, x, y, w, h)")
+            r = r.astype(np.int32).reshape(-1, 5)
+        r = np.ascontiguousarray(r, np.int32)
+        p = ExtractParams()
+        load_library().vj_extract_default(C.byref(p))
+        p.out_w, p.out_h = int(size[0]), int(size[1])
+        p.sx, p.sy = float(scale[0]), float(scale[1])
+        p.margin = float(margin)
+        p.flags = (VJ_EXTRACT_GRAY if gray else 0) | (VJ_EXTRACT_PLANAR if planar else 0)
+        return imgs, n, keep, r, p
+
+    @staticmethod
+    def extract_layout(frames, rects, size, scale=(1.0, 1.0), margin: float = 0.0, gray: bool = False, planar: bool = False,
+                       color: bool = False):
+        """vj_extract_layout (host only): what extract() will cut -> ((n, 5) int32 rows of the mapped source regions (frame, x, y, w, h),
+        which may lie outside their frames; channels of the output; bytes of the output)."""
+        imgs, n, keep, r, p = Environment._extract_args(frames, rects, size, scale, margin, gray, planar, color)
+        src = np.zeros((len(r), 5), np.int32)
+        ch, nbytes = C.c_int(0), C.c_uint64(0)
+        _check(load_library().vj_extract_layout(imgs, n, r.ctypes.data, len(r), C.byref(p), src.ctypes.data, C.byref(ch), C.byref(nbytes)),
+               "vj_extract_layout")
+        return src, int(ch.value), int(nbytes.value)
+
+    def extract(self, frames, rects, size, scale=(1.0, 1.0), margin: float = 0.0, gray: bool = False, planar: bool = False,
+                color: bool = False, out=None):
+        """vj_extract: the pixels inside rectangles, at one fixed size, on the device.  Region (frame, x, y, w, h) is
+        mapped to source pixels as OpenCV's facedetect sample maps its boxes (cvRound of the coordinates times scale = (sx, sy)), grown
+        by cvRound(side * margin) on every side, cut out with the frame's border replicated (never clipped) and resized to
+        size = (w, h) with vj_resize_linear's arithmetic per channel; gray=True: one channel through BGR2GRAY.  frames: as preprocess()
+        — the full-resolution frames, e.g. the DeviceFrames preprocess() was given.  Returns a torch.uint8 device tensor of shape
+        (n, h, w, C), or (n, C, h, w) with planar=True.  out: a contiguous torch.uint8 tensor on this device with that many elements;
+        None: one is allocated."""
+        import torch
+        imgs, n, keep, r, p = self._extract_args(frames, rects, size, scale, margin, gray, planar, color)
+        lib = load_library()
+        src = np.zeros((len(r), 5), np.int32)
+        ch, nbytes = C.c_int(0), C.c_uint64(0)
+        _check(lib.vj_extract_layout(imgs, n, r.ctypes.data, len(r), C.byref(p), src.ctypes.data, C.byref(ch), C.byref(nbytes)), "vj_extract_layout")
+        shape = (len(r), ch.value, p.out_h, p.out_w) if planar else (len(r), p.out_h, p.out_w, ch.value)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device="cuda")
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
+            raise ValueError("out must be a contiguous torch.uint8 tensor in device memory")
+        if out.numel() != int(nbytes.value):
+            raise ValueError(f"out must hold {int(nbytes.value)} bytes, the shape {shape}; it holds {out.numel()}")
+        _check(lib.vj_extract(self._h, imgs, n, r.ctypes.data, len(r), C.byref(p), C.c_void_p(out.data_ptr()), out.numel()), "vj_extract")
+        return out.view(shape)
+
+    def extract_timing(self) -> float:
+        """vj_extract_timing: device time of the last extract() call (events around its copies and launches), ms."""
+        ms = C.c_float(0)
+        _check(load_library().vj_extract_timing(self._h, C.byref(ms)), "vj_extract_timing")
+        return float(ms.value)
+
     def mixed_info(self) -> MixedInfo:
         """vj_mixed_info_get: atlases (count and the largest one's size), batched calls on original frames, frames by route, grid
         positions of the atlas passes and the pack launches' device time of the last detect_mixed / detect_opencv_mixed call."""
@@ -1049,6 +1129,12 @@ def preprocess_layout(frames, size=None, fx=None, fy=None, equalize: bool = Fals
     """vj_preprocess_layout: the host-only twin of Environment.preprocess (no environment, no device) ->
     ([(offset, width, height, stride) per frame], bytes of the destination buffer)."""
     return Environment.preprocess_layout(frames, size, fx, fy, equalize, color)
+
+
+def extract_layout(frames, rects, size, scale=(1.0, 1.0), margin: float = 0.0, gray: bool = False, planar: bool = False, color: bool = False):
+    """vj_extract_layout: the host-only twin of Environment.extract (no environment, no device) ->
+    (mapped source regions as (n, 5) int32 rows, channels, bytes)."""
+    return Environment.extract_layout(frames, rects, size, scale, margin, gray, planar, color)
 
 
 def _pixel_contiguous(img: np.ndarray) -> np.ndarray:

@@ -312,6 +312,11 @@ struct vj_env : vj::Tunables {
     vj::DevBuf d_prep;
     hipEvent_t prep_ev[2] = {};
     float prep_ms = 0;
+    // vj_extract (vj_extract.cpp): the block one copy brings per slice — region records, taps, then the slice's host
+    // frames at a 4-byte pitch (grows, reused) —, events around a call's copies and launches and their time (vj_extract_timing)
+    vj::DevBuf d_extract;
+    hipEvent_t extract_ev[2] = {};
+    float extract_ms = 0;
     uint64_t plan_tick = 0;
     int cv_tq_shift = 4;              // ... stage trees: the survivors' queue holds 1 / 2^shift of the tile windows (grows on overflow)
 };

@@ -775,6 +775,48 @@ int  vj_preprocess(vj_env* e, const vj_image* frames, int n_frames, const vj_pre
 /* Device time of the environment's last vj_preprocess call: events around its copies and launches, in ms.  A null argument: VJ_ERR_ARG. */
 int  vj_preprocess_timing(const vj_env* e, float* ms);
 
+/* ------------------------------------------------- rectangles back into pixels, on the device */
+/* What every consumer of a detector does next — cut the boxes out of the frames and bring them to one fixed size — as ONE batched
+ * call, device in, device out.  It adds no arithmetic: the resize is vj_resize_linear's, per channel (the 2 x 2
+ * mean where the crop is exactly twice the output on both axes, the identity where the sizes are equal); parity unpinned at the
+ * OpenCV boundary, like vj_preprocess.  For region k = (frame, x, y, w, h):
+ *   1. the sample's mapping to source pixels: x0 = cvRound(x * sx), y0 = cvRound(y * sy), w0 = max(cvRound(w * sx), 1),
+ *      h0 = max(cvRound(h * sy), 1) (round half to even of the f64 product), then mx = cvRound(w0 * margin), my = cvRound(h0 * margin)
+ *      and the source region (x0 - mx, y0 - my, w0 + 2 mx, h0 + 2 my);
+ *   2. a virtual crop with replicated border: crop[i][j] = frame[clamp(y0 - my + i, 0, H - 1)][clamp(x0 - mx + j, 0, W - 1)], so a
+ *      region is never clipped (a box keeps its aspect) and one partly or wholly outside its frame is defined;
+ *   3. out[k] = cv::resize(crop, (out_w, out_h), INTER_LINEAR) per channel: the taps clamp at the CROP's edges, not the frame's.
+ * Channels: without flags all frames the regions name share a channel count, which is C (BGRA's alpha is resized like any
+ * channel); VJ_EXTRACT_GRAY gives C = 1, colour sources going through the ingest BGR2GRAY tap by tap and then the resize — the
+ * order of vj_preprocess, so a whole-frame region with this flag and no margin is vj_preprocess without equalization, byte for
+ * byte.  Layout of the destination: n_regions x out_h x out_w x C bytes, interleaved like a cv::Mat; VJ_EXTRACT_PLANAR gives
+ * n_regions x C x out_h x out_w (an NCHW batch).        No padding anywhere.                                                      */
+enum { VJ_EXTRACT_GRAY = 1u << 0, VJ_EXTRACT_PLANAR = 1u << 1 };
+typedef struct vj_extract_params {
+    int32_t  out_w, out_h;   /* both > 0: the size of every output                                                              */
+    double   sx, sy;         /* the regions' coordinates times these are source pixels; 0 means 1                               */
+    double   margin;         /* the mapped region grows by cvRound(side * margin) on each of its four sides                     */
+    uint32_t flags;          /* VJ_EXTRACT_GRAY, VJ_EXTRACT_PLANAR                                                              */
+    uint32_t reserved;       /* must be 0                                                                                       */
+} vj_extract_params;
+void vj_extract_default(vj_extract_params* p);          /* sx = sy = 1, margin = 0, sizes 0: the caller must set them */
+/* Host only, no environment: src_regions[k] is the mapped source region of region k (it may lie outside its frame), *channels is
+ * C and *bytes the size of the output.  Errors as below.                                                                        */
+int  vj_extract_layout(const vj_image* frames, int n_frames, const vj_roi* regions, int n_regions, const vj_extract_params* p,
+                       vj_roi* src_regions, int* channels, uint64_t* bytes);
+/* frames: host or device-resident, 1 / 3 / 4 channels, any strides, sizes may differ.  d_dst: device memory of at least the
+ * layout's `bytes` (dst_bytes says how many there are), at any address.  Returns after the work is complete.  All checks come
+ * before the device is used.  VJ_ERR_ARG, with vj_last_error naming the row or the field: null arguments; a frame that breaks
+ * vj_detect_mixed's rules; a region's frame index out of range, w <= 0 or h <= 0; out_w or out_h <= 0; negative or non-finite sx, sy
+ * or margin; unknown flag bits, reserved != 0; frames of differing channel counts without VJ_EXTRACT_GRAY; dst_bytes below the
+ * layout's bytes; a device-resident source that overlaps [d_dst, d_dst + bytes).  VJ_ERR_LIMIT: an output side or a mapped region
+ * side above 65535 (the taps' 16-bit indices), a mapped coordinate beyond +-2^24, or more work units than a 32-bit index holds.
+ * n_regions == 0 is VJ_OK.  With "max_subbatch" configured a call runs in slices of regions that name at most that many frames.  */
+int  vj_extract(vj_env* e, const vj_image* frames, int n_frames, const vj_roi* regions, int n_regions,
+                const vj_extract_params* p, uint8_t* d_dst, uint64_t dst_bytes);
+/* Device time of the environment's last vj_extract call: events around its copies and launches, in ms.  A null argument: VJ_ERR_ARG. */
+int  vj_extract_timing(const vj_env* e, float* ms);
+
 /* ------------------------------------------------------------ frame streams */
 /* Video-style use (the demo's per-frame loop, main.cpp:104-125): batches of host frames are uploaded into
  * one of two device buffers by DMA on a copy stream while the kernels of the previous batch run, and the
