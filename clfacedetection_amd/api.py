@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 from dataclasses import dataclass
 
 import numpy as np
@@ -341,6 +342,16 @@ def _check(rc: int, what: str):
         raise VjError(rc, f"{what} failed ({lib.vj_strerror(rc).decode()})", lib.vj_last_error().decode())
 
 
+def _order_after_torch(device: int):
+    """The library's streams are non-blocking: they wait for no stream of torch's.  A call that hands the C ABI device memory which
+    torch may still be writing (DeviceFrames) or using (an out= tensor, a block its allocator recycled) therefore first waits for
+    torch's current stream on the environment's device.  Every such call returns only after its own work is complete, so the host
+    waits for that stream either way.  Without torch in the process there is nothing to order, and it is not imported for this."""
+    torch = sys.modules.get("torch")
+    if torch is not None and torch.cuda.is_initialized():
+        torch.cuda.current_stream(device).synchronize()
+
+
 def default_params(**kw) -> Params:
     p = Params()
     load_library().vj_params_default(C.byref(p))
@@ -519,6 +530,7 @@ class Environment:
         h = C.c_void_p()
         _check(load_library().vj_env_create(device_index, C.byref(h)), "vj_env_create")
         self._h = h
+        self._device = int(device_index)
 
     @property
     def device_name(self) -> str:
@@ -562,7 +574,7 @@ class Environment:
     def integral_sq32(self, frames, color: bool = False) -> tuple[np.ndarray, np.ndarray]:
         """The integral images of a batch of equal-sized frames as detect() and FrameStream keep them on the device
         (vj_integral_batch_sq32): sum and the squared sum mod 2^32, both uint32 (n, h + 1, w + 1).  frames as detect()."""
-        imgs, n, keep = self._images(frames, color)
+        imgs, n, keep = self._images(frames, color, self._device)
         if n == 0:
             raise ValueError("integral_sq32 expects at least one frame")
         s = np.empty((n, imgs[0].height + 1, imgs[0].width + 1), np.uint32)
@@ -594,7 +606,7 @@ class Environment:
         """vj_canny: cvCanny(gray, edges, 0, 50, 3) on the device, the edge map CV_HAAR_DO_CANNY_PRUNING computes per frame
         (uint8, 255 on edges, 0 elsewhere).  img: a 2-D uint8 image, a (h, w, 3|4) BGR / BGRA image (color=True), or a
         one-frame DeviceFrames."""
-        imgs, n, keep = self._images(img, color)
+        imgs, n, keep = self._images(img, color, self._device)
         if n != 1:
             raise ValueError("canny takes one image")
         e = np.empty((imgs[0].height, imgs[0].width), np.uint8)
@@ -604,7 +616,7 @@ class Environment:
     def equalize_hist(self, img, color: bool = False) -> np.ndarray:
         """vj_equalize_hist: cv::equalizeHist of the 8-bit gray image on the device, the image VJ_FLAG_EQUALIZE_HIST puts in front
         of a detect call; returns a (h, w) uint8 array.  img as for canny."""
-        imgs, n, keep = self._images(img, color)
+        imgs, n, keep = self._images(img, color, self._device)
         if n != 1:
             raise ValueError("equalize_hist takes one image")
         d = np.empty((imgs[0].height, imgs[0].width), np.uint8)
@@ -614,7 +626,7 @@ class Environment:
     def resize_linear(self, img, dst_w: int, dst_h: int, color: bool = False) -> np.ndarray:
         """vj_resize_linear: cvResize(gray, dst, CV_INTER_LINEAR) of the 8-bit gray image on the device, one level of the
         pyramid VJ_FLAG_CV_SCALE_IMAGE builds; returns a (dst_h, dst_w) uint8 array.  img as for canny."""
-        imgs, n, keep = self._images(img, color)
+        imgs, n, keep = self._images(img, color, self._device)
         if n != 1:
             raise ValueError("resize_linear takes one image")
         d = np.empty((int(dst_h), int(dst_w)), np.uint8)
@@ -643,7 +655,7 @@ class Environment:
         result_second); result_second.rects['frame'] indexes result_first.rects, x / y are relative to that region."""
         p1 = params_first or default_params()
         p2 = params_second or default_params()
-        imgs, n, keep = self._images(frames, color)
+        imgs, n, keep = self._images(frames, color, self._device)
         r1, r2 = _Result(), _Result()
         lib = load_library()
         _check(lib.vj_detect_chain(self._h, first._h, second._h, imgs, n, C.byref(p1), C.byref(p2), C.byref(r1), C.byref(r2)),
@@ -655,10 +667,13 @@ class Environment:
         return FrameStream(self, cascade, width, height, max_batch, params or default_params(), channels)
 
     @staticmethod
-    def _images(frames, color: bool):
-        """-> (ctypes array of vj_image, n, arrays to keep alive)"""
+    def _images(frames, color: bool, device: int | None = None):
+        """-> (ctypes array of vj_image, n, arrays to keep alive).  device: the environment's, for a call that will run on it — device
+        frames are then ordered after torch's current stream there (_order_after_torch); None for the host-only layout calls."""
         keep = []
         if isinstance(frames, DeviceFrames):
+            if device is not None:
+                _order_after_torch(device)
             n = frames.n
             imgs = (_Image * max(n, 1))()
             for i in range(n):
@@ -689,7 +704,7 @@ class Environment:
         cascade: one pass for all of them on the frames' integral images; else one batched pass per region size).  In the
         result rects['frame'] is the ROI's row and x / y are relative to the ROI's origin."""
         p = params or default_params()
-        imgs, n, keep = self._images(frames, color)
+        imgs, n, keep = self._images(frames, color, self._device)
         r = np.ascontiguousarray(np.asarray(rois, np.int32).reshape(-1, 5))
         res = _Result()
         lib = load_library()
@@ -706,7 +721,7 @@ class Environment:
         VJ_FLAG_CV_FIND_BIGGEST for CV_HAAR_FIND_BIGGEST_OBJECT (the scales from the largest window down, searched on the device; at
         most one rectangle per frame with weight = neighbors and scale_idx = -1; min_neighbors 0 counts as 1; the canny and
         scale-image flags are ignored), with VJ_FLAG_CV_ROUGH_SEARCH for CV_HAAR_DO_ROUGH_SEARCH next to it."""
-        imgs, n, keep = self._images(frames, color)
+        imgs, n, keep = self._images(frames, color, self._device)
         p = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
         res = _Result()
         lib = load_library()
@@ -722,7 +737,7 @@ class Environment:
         VJ_FLAG_COUNTERS, canny pruning or rough search at most) and frames of one size: every region's level images are resized
         into one canvas by one launch and walked by one pass per canvas (unless the call has more than 32 regions per distinct
         region size, which the next route runs faster); other flags or mixed frame sizes: one detect_opencv call per region size.  Same result either way; cv_rois_info() tells which way the last call went."""
-        imgs, n, keep = self._images(frames, color)
+        imgs, n, keep = self._images(frames, color, self._device)
         r = np.ascontiguousarray(np.asarray(rois, np.int32).reshape(-1, 5))
         p = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
         res = _Result()
@@ -740,7 +755,7 @@ class Environment:
         indexes result_first.rects, x / y are relative to that region.  frames: numpy arrays or DeviceFrames.
         flags | VJ_FLAG_CV_CHAIN_DEVICE: the hand-off between the two happens on the device (same results; cv_chain_info() tells
         which way the last call went)."""
-        imgs, n, keep = self._images(frames, color)
+        imgs, n, keep = self._images(frames, color, self._device)
         p1 = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
         p2 = CvParams(int(min_size_second[0]), int(min_size_second[1]), float(scale_factor_second), int(min_neighbors_second),
                       int(flags_second))
@@ -758,7 +773,7 @@ class Environment:
         max_size: the level loop ends at the first window larger than it ((0, 0), or a zero member: the frame).  min_neighbors != 0
         groups with groupRectangles' level overload (group_rectangles_levels).  flags must hold VJ_FLAG_CV_SCALE_IMAGE;
         VJ_FLAG_CV_FIND_BIGGEST and cascades of fewer than 4 stages are refused (VJ_ERR_UNSUPPORTED)."""
-        imgs, n, keep = self._images(frames, color)
+        imgs, n, keep = self._images(frames, color, self._device)
         p = CvRocParams(int(min_size[0]), int(min_size[1]), int(max_size[0]), int(max_size[1]), float(scale_factor),
                         int(min_neighbors), int(flags))
         res = _RocResult()
@@ -776,11 +791,11 @@ class Environment:
 
     def run_windows_opencv(self, cascade: Cascade, frames, windows, scales, start_stage: int = 0, color: bool = False):
         """vj_run_windows_opencv: see the module-level run_windows_opencv."""
-        return _run_windows(*_CV_WINDOWS, self._h, cascade, frames, windows, scales, start_stage, color)
+        return _run_windows(*_CV_WINDOWS, self, cascade, frames, windows, scales, start_stage, color)
 
     def run_windows(self, cascade: Cascade, frames, windows, scales, start_stage: int = 0, flags: int = 0, color: bool = False):
         """vj_run_windows: see the module-level run_windows."""
-        return _run_windows(*_CLOD_WINDOWS, self._h, cascade, frames, windows, scales, start_stage, color, flags)
+        return _run_windows(*_CLOD_WINDOWS, self, cascade, frames, windows, scales, start_stage, color, flags)
 
     def run_windows_timing(self) -> tuple[float, float]:
         """vj_run_windows_timing: (integral_ms, pass_ms) of the last run_windows_opencv or run_windows call, device times summed
@@ -813,12 +828,16 @@ class Environment:
         return info
 
     @staticmethod
-    def _mixed_images(frames):
+    def _mixed_images(frames, device: int | None = None):
         """Frames of any sizes -> (ctypes array of vj_image, n, arrays to keep alive).  Items: 2-D uint8 arrays (gray), (h, w, 3 | 4)
-        uint8 arrays (BGR / BGRA; rows may be strided views) and DeviceFrames, each of which contributes its frames."""
+        uint8 arrays (BGR / BGRA; rows may be strided views) and DeviceFrames, each of which contributes its frames.  device: as for
+        _images."""
         keep, imgs = [], []
         if isinstance(frames, (np.ndarray, DeviceFrames)):
             frames = [frames]
+        frames = list(frames)
+        if device is not None and any(isinstance(f, DeviceFrames) for f in frames):
+            _order_after_torch(device)
         for f in frames:
             if isinstance(f, DeviceFrames):
                 imgs += [_Image(f.frame_ptr(i), f.width, f.height, f.stride, 1, f.channels) for i in range(f.n)]
@@ -842,7 +861,7 @@ class Environment:
         own_call_px pixels take a batched call of their own; the others are packed into atlases on the device, integrated once and
         run as regions.  atlas_px / own_call_px change speed only; mixed_info() tells what the last call did."""
         p = params or default_params()
-        imgs, n, keep = self._mixed_images(frames)
+        imgs, n, keep = self._mixed_images(frames, self._device)
         o = self._mixed_opts(atlas_px, own_call_px)
         res = _Result()
         lib = load_library()
@@ -853,7 +872,7 @@ class Environment:
                             flags: int = 0, atlas_px: int = 0, own_call_px: int = 0) -> DetectResult:
         """vj_detect_opencv_mixed: the same for detect_opencv (every flag of it; those whose result needs the image alone — canny
         pruning without scale-image, find-biggest — run per group of equal frames, without an atlas)."""
-        imgs, n, keep = self._mixed_images(frames)
+        imgs, n, keep = self._mixed_images(frames, self._device)
         p = CvParams(int(min_size[0]), int(min_size[1]), float(scale_factor), int(min_neighbors), int(flags))
         o = self._mixed_opts(atlas_px, own_call_px)
         res = _Result()
@@ -865,7 +884,7 @@ class Environment:
         """vj_pack_frames: the first atlas a mixed call would make of `frames` -> (atlas as a (h, w) uint8 array, origins as an
         (n, 2) int32 array of (x, y), -1 -1 for a frame that is not in it).  A frame's gray image lies at its origin; what no frame
         covers is 0."""
-        imgs, n, keep = self._mixed_images(frames)
+        imgs, n, keep = self._mixed_images(frames, self._device)
         lib = load_library()
         w, h = C.c_int(0), C.c_int(0)
         origins = np.full((n, 2), -1, np.int32)
@@ -920,9 +939,10 @@ class Environment:
         nbytes = C.c_uint64(0)
         _check(lib.vj_preprocess_layout(imgs, n, C.byref(p), res, C.byref(nbytes)), "vj_preprocess_layout")
         if out is None:
-            out = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device="cuda")
+            out = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=torch.device("cuda", self._device))
         if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
             raise ValueError("out must be a contiguous torch.uint8 tensor in device memory")
+        _order_after_torch(self._device)       # after the allocation: device frames, a caller's `out`, and a block the allocator recycled
         _check(lib.vj_preprocess(self._h, imgs, n, C.byref(p), C.c_void_p(out.data_ptr()), out.numel(), res), "vj_preprocess")
         if n == 0:
             return []
@@ -990,11 +1010,12 @@ class Environment:
         _check(lib.vj_extract_layout(imgs, n, r.ctypes.data, len(r), C.byref(p), src.ctypes.data, C.byref(ch), C.byref(nbytes)), "vj_extract_layout")
         shape = (len(r), ch.value, p.out_h, p.out_w) if planar else (len(r), p.out_h, p.out_w, ch.value)
         if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device="cuda")
+            out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", self._device))
         if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
             raise ValueError("out must be a contiguous torch.uint8 tensor in device memory")
         if out.numel() != int(nbytes.value):
             raise ValueError(f"out must hold {int(nbytes.value)} bytes, the shape {shape}; it holds {out.numel()}")
+        _order_after_torch(self._device)       # after the allocation, as in preprocess()
         _check(lib.vj_extract(self._h, imgs, n, r.ctypes.data, len(r), C.byref(p), C.c_void_p(out.data_ptr()), out.numel()), "vj_extract")
         return out.view(shape)
 
@@ -1016,7 +1037,7 @@ class Environment:
         DeviceFrames (frames already resident in HBM).  color=True: every frame is (h, w, 3 | 4) BGR / BGRA
         (one 3-D array, a 4-D batch or a list) and is converted to gray on the device."""
         p = params or default_params()
-        imgs, n, keep = self._images(frames, color)
+        imgs, n, keep = self._images(frames, color, self._device)
         res = _Result()
         lib = load_library()
         _check(lib.vj_detect(self._h, cascade._h, imgs, n, C.byref(p), C.byref(res)), "vj_detect")
@@ -1071,7 +1092,7 @@ class FrameStream:
         self._keep = []
 
     def submit(self, frames, color: bool = False):
-        imgs, n, keep = Environment._images(frames, color)
+        imgs, n, keep = Environment._images(frames, color, self._env._device)
         _check(load_library().vj_stream_submit(self._h, imgs, n), "vj_stream_submit")
         self._keep.append((imgs, keep))
 
@@ -1100,7 +1121,9 @@ class DeviceFrames:
     """A batch of equal-size 8-bit frames already resident in device memory
     (e.g. a torch.uint8 CUDA tensor's data_ptr()); rows `stride` bytes apart,
     frames `frame_bytes` bytes apart (0: stride * height); channels = 1 (gray), 3 (BGR) or 4 (BGRA), interleaved.
-    owner: whatever keeps the memory alive (Environment.preprocess puts its tensor there)."""
+    owner: whatever keeps the memory alive (Environment.preprocess puts its tensor there).
+    Every call that is given one first waits for torch's current stream on the environment's device (_order_after_torch), so work
+    queued there — a copy_, a decoder's kernels — has written the frames; producers on other streams are the caller's to wait for."""
     ptr: int
     n: int
     height: int
@@ -1269,15 +1292,15 @@ _CV_WINDOWS = ("vj_run_windows_opencv", np.float64, WINDOW_RESULT_DTYPE, ("resul
 _CLOD_WINDOWS = ("vj_run_windows", np.float32, CLOD_WINDOW_RESULT_DTYPE, ("result", "stage_sum", "variance"))
 
 
-def _run_windows(fn, scale_dtype, result_dtype, fields, env_handle, cascade: Cascade, frames, windows, scales, start_stage, color, flags=None):
+def _run_windows(fn, scale_dtype, result_dtype, fields, env, cascade: Cascade, frames, windows, scales, start_stage, color, flags=None):
     """One window-list call (`flags`: for the C function that takes them); the result's `fields` as arrays of their own."""
     w, sc = _window_args(windows, scales, scale_dtype, start_stage)
     if flags is not None and (flags != int(flags) or not 0 <= int(flags) < 2**32):
         raise ValueError("flags must be an unsigned 32-bit integer")
     n = int(w.shape[0])
-    imgs, nf, keep = Environment._images(frames, color)
+    imgs, nf, keep = Environment._images(frames, color, env._device if env is not None else None)
     out = np.zeros(n, result_dtype)
-    _check(getattr(load_library(), fn)(env_handle, cascade._h, imgs, nf, sc.ctypes.data, len(sc), w.ctypes.data, n, int(start_stage),
+    _check(getattr(load_library(), fn)(env._h if env is not None else None, cascade._h, imgs, nf, sc.ctypes.data, len(sc), w.ctypes.data, n, int(start_stage),
                                        *(() if flags is None else (int(flags),)), out.ctypes.data), fn)
     return tuple(out[f].copy() for f in fields)
 
@@ -1289,7 +1312,7 @@ def run_windows_opencv(frames, cascade: Cascade, env: Environment, windows, scal
     cascade (0 at stage 0), 0 on every reject of a stage tree; stage_sum is the f64 sum of the stage whose verdict ended the run
     (0.0 with result -1 and with start_stage >= the stage count).  frames: 2-D uint8 arrays of one size, (h, w, 3|4) BGR / BGRA
     arrays with color=True, or DeviceFrames.  The arguments are checked before the environment is used."""
-    return _run_windows(*_CV_WINDOWS, env._h if env is not None else None, cascade, frames, windows, scales, start_stage, color)
+    return _run_windows(*_CV_WINDOWS, env, cascade, frames, windows, scales, start_stage, color)
 
 
 def cvRunHaarClassifierCascade(gray, cascade: Cascade, env: Environment, pt, scale: float = 1.0, start_stage: int = 0) -> int:
@@ -1308,7 +1331,7 @@ def run_windows(frames, cascade: Cascade, env: Environment, windows, scales, sta
     f32 sum of the stage whose verdict ended the run (0.0 outside and with start_stage >= the stage count); variance is the norm
     factor of every inside window.  flags: VJ_FLAG_SIGNED_MEAN, VJ_FLAG_TILTED_AS_UPRIGHT.  frames: 2-D uint8 arrays of one size,
     (h, w, 3|4) BGR / BGRA arrays with color=True, or DeviceFrames.  The arguments are checked before the environment is used."""
-    return _run_windows(*_CLOD_WINDOWS, env._h if env is not None else None, cascade, frames, windows, scales, start_stage, color, flags)
+    return _run_windows(*_CLOD_WINDOWS, env, cascade, frames, windows, scales, start_stage, color, flags)
 
 
 def runCascade(gray, cascade: Cascade, env: Environment, pt, scale: float = 1.0) -> int:

@@ -372,7 +372,13 @@ typedef struct vj_image {
     const uint8_t* data;       /* 8-bit, interleaved channels                   */
     int32_t width, height;
     int32_t stride;            /* bytes per row                                 */
-    int32_t on_device;         /* 0: host pointer; 1: device pointer on env's GPU */
+    int32_t on_device;         /* 0: host pointer; 1: device pointer on env's GPU.  The library's streams are created with
+                                  hipStreamNonBlocking: they wait for no other stream, the null stream included.  All work
+                                  that writes a device-resident frame must be COMPLETE before the call that is given it (an
+                                  event or stream synchronize of the caller's; queued is not enough), and nothing may write it
+                                  until that call has returned (vj_stream_submit: until the batch is collected).  Every call
+                                  returns after its own work is complete, so its results are ready for any stream.  What the
+                                  Python wrapper does on top of this for its callers: INTEGRATION.md                       */
     int32_t channels;          /* 0 or 1: gray (the configs' contract); 3: BGR, 4: BGRA — converted on the
                                   fly with OpenCV's 8-bit BGR2GRAY, as setupImage does (clif.cpp:326-335) */
 } vj_image;
@@ -763,7 +769,9 @@ void vj_prep_default(vj_prep* p);                       /* all 0 */
  * return for frame i, with data = (const uint8_t*)offset in the buffer; *bytes is the end of the last image.  Errors as below.  */
 int  vj_preprocess_layout(const vj_image* frames, int n_frames, const vj_prep* p, vj_image* out, uint64_t* bytes);
 /* frames: host or device-resident, 1 / 3 / 4 channels, any strides, sizes may differ.  d_dst: device memory of at least the layout's
- * `bytes` (dst_bytes says how many there are).  out[i]: gray, on_device = 1, data inside d_dst.  Returns after the work is complete.
+ * `bytes` (dst_bytes says how many there are); all work of the caller's that reads or writes it must be complete before the call
+ * (the library's streams are non-blocking, see vj_image.on_device).  out[i]: gray, on_device = 1, data inside d_dst.  Returns after
+ * the work is complete.
  * All checks come before the device is used.  VJ_ERR_ARG, with vj_last_error naming the frame or the field: null arguments; a frame
  * with null data, w <= 0, h <= 0, another channel count or stride < w * channels; one of dst_w / dst_h, or of fx / fy, set without
  * the other; negative sizes, negative or non-finite factors; unknown flag bits, reserved != 0; dst_bytes below the layout's bytes;
@@ -805,7 +813,8 @@ void vj_extract_default(vj_extract_params* p);          /* sx = sy = 1, margin =
 int  vj_extract_layout(const vj_image* frames, int n_frames, const vj_roi* regions, int n_regions, const vj_extract_params* p,
                        vj_roi* src_regions, int* channels, uint64_t* bytes);
 /* frames: host or device-resident, 1 / 3 / 4 channels, any strides, sizes may differ.  d_dst: device memory of at least the
- * layout's `bytes` (dst_bytes says how many there are), at any address.  Returns after the work is complete.  All checks come
+ * layout's `bytes` (dst_bytes says how many there are), at any address; all work of the caller's that reads or writes it must be
+ * complete before the call (the library's streams are non-blocking, see vj_image.on_device).  Returns after the work is complete.  All checks come
  * before the device is used.  VJ_ERR_ARG, with vj_last_error naming the row or the field: null arguments; a frame that breaks
  * vj_detect_mixed's rules; a region's frame index out of range, w <= 0 or h <= 0; out_w or out_h <= 0; negative or non-finite sx, sy
  * or margin; unknown flag bits, reserved != 0; frames of differing channel counts without VJ_EXTRACT_GRAY; dst_bytes below the
