@@ -28,609 +28,36 @@ using namespace vj;
 
 namespace {
 
-struct CvScaleHost {
-    double factor;
-    int idx;
-    int win_w, win_h, end_x, end_y;
-    // CV_HAAR_SCALE_IMAGE: a level of the pyramid — its size, its place in the canvas and its grid step
-    int lw = 0, lh = 0, ox = 0, oy = 0, step = 0;
-};
+// (the planner — scales, canvas, node tables, tile shapes, work lists, the pyramid's taps — needs no device: vj_cv_plan.cpp)
 
-// (the level loop of CV_HAAR_SCALE_IMAGE, build_taps and resize_is_area: vj_cv_roi_levels_host.cpp — the regions' level canvases share them)
-
-// icvCreateHidHaarClassifierCascade's flags (tempcv.cpp:410-470) and the tree shape the kernels have a fast form for
-struct CvShape {
-    bool trees = false, is_tree = false, has_tilted = false, tree2 = false;
-    std::vector<uint8_t> two_rects;   // per stage: no node has a third rectangle (:452-457)
-};
-static CvShape cv_shape_of(const vj_cascade* c) {
-    CvShape sh;
-    for (const auto& st : c->stages) sh.is_tree |= st.next != -1;
-    for (const auto& t : c->trees)
-        if (t.n_nodes != 1) sh.trees = true;
-    for (const auto& nd : c->nodes) sh.has_tilted |= nd.tilted != 0;
-    // two-node trees (frontalface_alt2): root + one node child — the shape the tile kernel's tree path knows
-    sh.tree2 = sh.trees;
-    for (const auto& t : c->trees) {
-        if (!sh.tree2) break;
-        if (t.n_nodes != 2) { sh.tree2 = false; break; }
-        const vj_node_desc& n0 = c->nodes[t.first_node];
-        const vj_node_desc& n1 = c->nodes[t.first_node + 1];
-        const int kids = (n0.left > 0) + (n0.right > 0);
-        if (kids != 1 || (n0.left > 0 ? n0.left : n0.right) != 1 || n1.left > 0 || n1.right > 0) sh.tree2 = false;
-    }
-    sh.two_rects.assign(c->stages.size(), 1);
-    for (size_t s2 = 0; s2 < c->stages.size(); ++s2)
-        for (int t = 0; t < c->stages[s2].n_trees; ++t) {
-            const vj_tree_desc& td = c->trees[c->stages[s2].first_tree + t];
-            for (int l = 0; l < td.n_nodes; ++l) {
-                const vj_rect_desc& r2 = c->nodes[td.first_node + l].rect[2];
-                // :452-457: the third rectangle counts unless |weight| < DBL_EPSILON or it is empty
-                if (!(std::fabs((double)r2.weight) < 2.220446049250313e-16 || r2.w == 0 || r2.h == 0)) sh.two_rects[s2] = 0;
-            }
-        }
-    return sh;
-}
-
-// cvSetImagesForHaarClassifierCascade's node records for one factor (tempcv.cpp:632-768): cvRound-ed rectangles as byte offsets from the
-// window origin in a `stride`-wide integral image, f32 weights with rect 0's derived from the others (:752-767; CV_ADJUST_WEIGHTS = 0).
-// Nothing here depends on the image beyond its row step.  *max_reach: furthest element a feature touches, from the window origin.
-static int build_cv_node_recs(const vj_cascade* c, double scale, uint32_t stride, double weight_scale, CvNodeRec* recs, uint64_t* max_reach) {
-    for (size_t t = 0; t < c->trees.size(); ++t) {
-        const vj_tree_desc& td = c->trees[t];
-        for (int j = 0; j < td.n_nodes; ++j) {
-            const vj_node_desc& nd = c->nodes[td.first_node + j];
-            CvNodeRec& r = recs[td.first_node + j];
-            memset(&r, 0, sizeof(r));
-            if (nd.rect[0].weight == 0.0f || nd.rect[1].weight == 0.0f) {
-                set_error("node %d: rect 0 and rect 1 must both be weighted", td.first_node + j);
-                return VJ_ERR_UNSUPPORTED;
-            }
-            double sum0 = 0, area0 = 0;
-            const double correction_ratio = weight_scale * (!nd.tilted ? 1 : 0.5);   // :731
-            for (int q = 0; q < 3; ++q) {
-                // hidfeature->rect[k].p0 == 0 ends the list (tempcv.cpp:663): only a third rectangle can be absent (:452-455)
-                if (q == 2 && (std::fabs((double)nd.rect[2].weight) < 2.220446049250313e-16 || nd.rect[2].w == 0 || nd.rect[2].h == 0))
-                    break;
-                const int tx = cv_round(nd.rect[q].x * scale), ty = cv_round(nd.rect[q].y * scale);
-                const int tw = cv_round(nd.rect[q].w * scale), th = cv_round(nd.rect[q].h * scale);
-                // corners p0, p1 = p0 + da, p2 = p0 + db, p3 = p0 + da + db (element offsets)
-                const int64_t p0 = (int64_t)ty * stride + tx;
-                int64_t da, db;
-                if (!nd.tilted) {         // :735-741
-                    da = tw;
-                    db = (int64_t)th * stride;
-                } else {                  // :743-750: p1 = (y + h, x - h), p2 = (y + w, x + w), p3 = (y + w + h, x + w - h)
-                    da = (int64_t)th * stride - th;
-                    db = (int64_t)tw * stride + tw;
-                }
-                if (p0 < 0 || da < 0 || db < 0 || (p0 + da + db) * 4 > 0x7fffffffll) {
-                    set_error("feature offsets exceed the device record range");
-                    return VJ_ERR_LIMIT;
-                }
-                r.lt[q] = (uint32_t)(p0 * 4);
-                r.da[q] = (uint32_t)(da * 4);
-                r.db[q] = (uint32_t)(db * 4);
-                r.w[q] = (float)(nd.rect[q].weight * correction_ratio);
-                if (q == 0)
-                    area0 = tw * th;
-                else
-                    sum0 += r.w[q] * tw * th;                          // float * int * int, added to a double (:756)
-                *max_reach = std::max<uint64_t>(*max_reach, (uint64_t)(p0 + da + db));
-                *max_reach = std::max<uint64_t>(*max_reach, (uint64_t)(p0 + db));
-            }
-            r.w[0] = (float)(-sum0 / area0);
-            r.thr = nd.threshold;
-            uint32_t flags = nd.tilted ? CV_NODE_TILTED : 0u;
-            auto leaf_or_node = [&](int v, uint32_t flag, uint32_t* dst) {
-                if (v > 0) {
-                    flags |= flag;
-                    *dst = (uint32_t)v;
-                } else {
-                    const float a = c->alpha[td.first_alpha - v];
-                    memcpy(dst, &a, 4);
-                }
-            };
-            leaf_or_node(nd.left, NODE_LEFT_IS_NODE, &r.left);
-            leaf_or_node(nd.right, NODE_RIGHT_IS_NODE, &r.right);
-            if (j == td.n_nodes - 1) flags |= NODE_TREE_LAST;
-            r.flags = flags;
-        }
-    }
-    return VJ_OK;
-}
-
-// The stage records of the profile: threshold - 0.0001f, resolved successors, sweep order, the arithmetic mode of a node sum
-static std::vector<StageDev> build_cv_stage_recs(const vj_cascade* c, const StageProgram& prog, const std::vector<uint32_t>& order,
-                                                 const std::vector<uint8_t>& two_rects, bool trees, bool is_tree) {
-    std::vector<StageDev> stages(c->stages.size());
-    for (size_t s = 0; s < c->stages.size(); ++s) {
-        memset(&stages[s], 0, sizeof(StageDev));
-        stages[s].first_node = prog.first_node[s];
-        stages[s].n_nodes = prog.n_nodes[s];
-        stages[s].threshold = c->stages[s].threshold - 0.0001f;   // icv_stage_threshold_bias, in f32
-        stages[s].n_trees = (uint32_t)c->stages[s].n_trees;
-        stages[s].on_pass = prog.on_pass[s];
-        stages[s].on_fail = prog.on_fail[s];
-        stages[s].order = s < order.size() ? order[s] : 0u;
-        // an f64 product per rectangle only on cvRunHaarClassifierCascadeSum's stump path (:863-888)
-        stages[s].cv_f64 = (two_rects[s] && !trees && !is_tree) ? 1u : 0u;
-        // wave-split finish of the tile kernel: bound on the difference between any two summation orders of the stage's
-        // leaf values (the f32 form of the clod profile's bound, stage_records in vj_clod_plan.cpp; the kernel scales it to f64's unit roundoff)
-        double amax = 0.0;
-        for (int t = 0; t < c->stages[s].n_trees; ++t) {
-            const vj_tree_desc& td = c->trees[c->stages[s].first_tree + t];
-            double m = 0.0;
-            for (int k = 0; k <= td.n_nodes; ++k) m = std::max(m, (double)std::fabs(c->alpha[td.first_alpha + k]));
-            amax += m;
-        }
-        stages[s].sp_delta = (float)(4.0 * (double)prog.n_nodes[s] * std::ldexp(1.0, -24) * amax * 1.001 + 1e-30);
-    }
-    return stages;
-}
-
-// What vj_detect_opencv_roc adds to a scale-image call: maxSize, already resolved (a zero member means the frame,
-// tempcv.cpp:1230-1234), and where the levels and weights of the reported windows go, parallel to the call's rectangles.
-struct CvRocCall {
-    int max_w, max_h;
+// What vj_detect_opencv_roc adds to a scale-image call: maxSize, and where the levels and weights of the reported
+// windows go, parallel to the call's rectangles.
+struct CvRocCall : CvMaxSize {
     std::vector<int32_t>* levels;
     std::vector<double>* weights;
 };
 
-// The level k at which `winSize > maxSize` ends the scale-image level loop (tempcv.cpp:1268-1286), -1 when the loop ends on the
-// level's size first: what a plan's key records of maxSize.
-static int cv_max_level_end(const vj_cascade* c, int W, int H, double scale_factor, int max_w, int max_h) {
-    double factor = 1;
-    for (int k = 0; k <= 65536; ++k, factor *= scale_factor) {
-        if (cv_round(W / factor) - c->win_w + 1 <= 0 || cv_round(H / factor) - c->win_h + 1 <= 0) return -1;
-        if (cv_round(c->win_w * factor) > max_w || cv_round(c->win_h * factor) > max_h) return k;
-    }
-    return -1;
-}
-
-// Everything that depends on (cascade, frame size, parameters) only: scales, feature tables, stage records, row list.
-static int build_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv_params* p, bool small_batch, CvPlan* pl,
-                         const CvRocCall* roc = nullptr) {
-    if ((int)c->stages.size() > VJ_MAX_STAGES || c->stages.empty()) {
-        set_error("cascade has %zu stages; 1..%d are supported", c->stages.size(), VJ_MAX_STAGES);
-        return VJ_ERR_LIMIT;
-    }
-    pl->prog = build_stage_program(*c);
-    const StageProgram& prog = pl->prog;
-    std::vector<uint32_t> order;
-    if (!stage_sweep_order(prog, &order)) {
-        set_error("stage links form a cycle");
-        return VJ_ERR_UNSUPPORTED;
-    }
-    const CvShape shape = cv_shape_of(c);
-    const bool trees = shape.trees, is_tree = shape.is_tree, has_tilted = shape.has_tilted, tree2 = shape.tree2;
-    const std::vector<uint8_t>& two_rects = shape.two_rects;
-    pl->tree2 = tree2;
-    // CV_HAAR_SCALE_IMAGE never reads doCannyPruning (tempcv.cpp:1257-1329)
-    // CV_HAAR_FIND_BIGGEST_OBJECT clears both (tempcv.cpp:1227, :1254)
-    const bool fb = (p->flags & VJ_FLAG_CV_FIND_BIGGEST) != 0u;
-    const bool si = !fb && (p->flags & VJ_FLAG_CV_SCALE_IMAGE) != 0u;
-    pl->find_biggest = fb;
-    pl->scale_image = si;
-    pl->roc = roc != nullptr;
-    pl->prune = !fb && !si && (p->flags & VJ_FLAG_CV_CANNY_PRUNING) != 0u;
-    pl->trees = trees;
-    pl->is_tree = is_tree;
-    pl->has_tilted = has_tilted;
-    pl->n_order = (uint32_t)order.size();
-    pl->n_stages = (uint32_t)c->stages.size();
-    // ---- the scale loop (tempcv.cpp:1344-1377)
-    std::vector<CvScaleHost> hs;
-    int IW = W, IH = H;   // what the integral images are computed of: the frame, or the canvas of the pyramid's levels
-    if (si) {
-        // ---- the level loop (tempcv.cpp:1268-1288; maxSize is the image unless a ROC call brings one)
-        const int max_w = roc ? roc->max_w : W, max_h = roc ? roc->max_h : H;
-        std::vector<CvLevelHost> lv;
-        const int lrc = cv_scale_image_levels(c->win_w, c->win_h, W, H, p->scale_factor, p->min_w, p->min_h, max_w, max_h, &lv);
-        if (lrc) return lrc;
-        for (const CvLevelHost& l : lv) {
-            CvScaleHost s;
-            s.factor = l.factor;
-            s.idx = l.idx;
-            s.win_w = l.win_w;
-            s.win_h = l.win_h;
-            s.lw = l.lw;
-            s.lh = l.lh;
-            s.step = l.step;
-            s.end_x = l.end_x;
-            s.end_y = l.end_y;
-            hs.push_back(s);
-        }
-        // One canvas per frame holds every level (levels come in decreasing size): shelves of the canvas's width, a level goes to the
-        // first shelf that has room beside what it holds, else it opens a new one below.  A rectangle sum does not depend on where the
-        // integral image starts (u32 wrap-around cancels, the u64 square sums are exact), and the four corners of a tilted rectangle
-        // give the sum of the pixels INSIDE it whatever lies beside it: neighbours need no gap.
-        struct Shelf { int y, h, used; };
-        std::vector<Shelf> shelves;
-        IW = hs.empty() ? 1 : hs[0].lw;
-        IH = 0;
-        for (CvScaleHost& s : hs) {
-            Shelf* fit = nullptr;
-            for (Shelf& sh : shelves)
-                if (sh.used + s.lw <= IW && s.lh <= sh.h) { fit = &sh; break; }
-            if (!fit) {
-                shelves.push_back(Shelf{IH, s.lh, 0});
-                IH += s.lh;
-                fit = &shelves.back();
-            }
-            s.ox = fit->used;
-            s.oy = fit->y;
-            fit->used += s.lw;
-        }
-        IH = std::max(IH, 1);
-        if (IH >= 65535 || (uint64_t)(IW + 1) * (uint64_t)(IH + 3) >= (1ull << 30)) {
-            set_error("the image pyramid (%d x %d for %zu levels) does not fit 32-bit offsets", IW, IH, hs.size());
-            return VJ_ERR_LIMIT;
-        }
-        pl->canvas_w = (uint32_t)IW;
-        pl->canvas_h = (uint32_t)IH;
-        pl->canvas_pitch = ((uint32_t)IW + 3u) & ~3u;
-    }
-    const uint32_t stride = (uint32_t)IW + 1u;
-    if (fb) {
-        // find-biggest (tempcv.cpp:1344-1380): the factors are counted upwards, then walked DOWN from the last one by repeated
-        // multiplication with the reciprocal — other doubles than the ascending ones in general.  The loop BREAKS at the first window
-        // below minSize, but minSize is the frame's own from its first grouped object on (:1450-1452, possibly smaller than the
-        // call's): every scale is planned, and the waves of cv_biggest_pass apply the break per frame (windows only shrink, so a
-        // frame that broke stays out).  Slot k is the k-th scale of the walk; scale_idx = n_factors - 1 - k.
-        int n_factors = 0;
-        double factor = 1;
-        for (; factor * c->win_w < W - 10 && factor * c->win_h < H - 10; n_factors++, factor *= p->scale_factor) {}
-        const double down = 1. / p->scale_factor;
-        factor *= down;
-        for (int k = 0; k < n_factors; ++k, factor *= down) {
-            const double ystep = std::max(2., factor);
-            CvScaleHost s;
-            s.factor = factor;
-            s.idx = n_factors - 1 - k;
-            s.win_w = cv_round(c->win_w * factor);
-            s.win_h = cv_round(c->win_h * factor);
-            s.end_x = cv_round((W - s.win_w) / ystep);
-            s.end_y = cv_round((H - s.win_h) / ystep);
-            if (s.end_x <= 0 || s.end_y <= 0) continue;   // (no position: nothing to walk, and no new candidate to group)
-            hs.push_back(s);
-        }
-    } else if (!si) {
-        int n_factors = 0;
-        double factor = 1;
-        for (; factor * c->win_w < W - 10 && factor * c->win_h < H - 10; n_factors++, factor *= p->scale_factor) {}
-        factor = 1;
-        for (int k = 0; k < n_factors; ++k, factor *= p->scale_factor) {
-            const double ystep = std::max(2., factor);
-            CvScaleHost s;
-            s.factor = factor;
-            s.idx = k;
-            s.win_w = cv_round(c->win_w * factor);
-            s.win_h = cv_round(c->win_h * factor);
-            s.end_x = cv_round((W - s.win_w) / ystep);
-            s.end_y = cv_round((H - s.win_h) / ystep);
-            if (s.win_w < p->min_w || s.win_h < p->min_h) continue;
-            if (s.end_x <= 0 || s.end_y <= 0) continue;
-            hs.push_back(s);
-        }
-    }
-    // stage trees: the tiles run the tree's linear prefix — leading stages of the sweep order that reject outright and pass
-    // on to the next one (cv_profile_pass finds the same prefix) — when the prefix is stages 0, 1, 2, ... themselves
-    uint32_t tree_prefix = 0;
-    if (is_tree) {
-        while (tree_prefix + 1u < order.size() && order[tree_prefix] == tree_prefix && prog.on_fail[tree_prefix] == STAGE_REJECT &&
-               prog.on_pass[tree_prefix] == (int)order[tree_prefix + 1u])
-            ++tree_prefix;
-    }
-    pl->tree_prefix = tree_prefix;
-    // Is the rest of the tree a sequence of chains (CvChainDev)?  A chain is a run of sweep positions whose pass edges follow
-    // the order and end in an accept, whose rejects all go to ONE place: nowhere (final) or the first stage of the NEXT chain.
-    if (!fb && is_tree && tree_prefix != 0u && prog.on_pass[order[tree_prefix - 1u]] == (int)order[tree_prefix]) {   // (find-biggest: no chain sweep)
-        CvChainDev ch;
-        memset(&ch, 0, sizeof(ch));
-        bool ok = true;
-        uint32_t b = tree_prefix;
-        while (b < order.size() && ok) {
-            if (ch.n == 4u) { ok = false; break; }
-            const int f = prog.on_fail[order[b]];
-            uint32_t e2 = b;
-            while (true) {
-                const uint32_t sid = order[e2];
-                if (prog.on_fail[sid] != f) { ok = false; break; }
-                const int np = prog.on_pass[sid];
-                ++e2;
-                if (np == STAGE_ACCEPT) break;
-                if (e2 >= order.size() || np != (int)order[e2]) { ok = false; break; }
-            }
-            if (!ok) break;
-            ch.begin[ch.n] = b;
-            ch.end[ch.n] = e2;
-            if (f != STAGE_REJECT) {
-                if (e2 < order.size() && f == (int)order[e2]) ch.chained |= 1u << ch.n;   // rejects start the next chain
-                else ok = false;
-            }
-            ++ch.n;
-            b = e2;
-        }
-        ch.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
-        if (ok && ch.n != 0u && !((ch.chained >> (ch.n - 1u)) & 1u)) pl->chains = ch;
-    }
-    // (a stage tree's row kernel evaluates the whole tree at every grid position and is far slower per window than the tiles'
-    // prefix: trees send every scale they can to tiles and leave the row kernel two workgroups per CU)
-    // (linear cascades, profiles/r04_notes.md #5b: stumps 2 workgroups x tiles of >= 2048 windows — 64 x 1080p frontalface_alt 66.6 ms against 80.5
-    // at 3 x 1536, frontalface_default 51.4 / 57.1, 256 x 720p 112.7 / 136.9 —, multi-node trees the other way round: frontalface_alt2 99.3 / 77.5;
-    // two-node trees with both nodes fetched at once (CvArgs::tree2, #5d): 2 x 1536 69.9 ms against 80.9 at 3 x 1536)
-    const bool rows_tree2 = pl->tree2 && !is_tree && !has_tilted && e->cv_tree2;
-    // (cascades with tilted features, #12: a tile holds two images, so the shapes that fit are smaller — and the row kernel they relieve is 2-3x
-    // the tiles' cost per window: two workgroups x tiles of >= 512 windows, `fullbody` 16 x 1080p 28-29 ms against 40.8 with every tile of
-    // >= 2048 windows refused, `upperbody` 50.7 / 96.6, `mcs_righteye`'s kernels 30.9 / 72.4)
-    const bool tilt_tiles = has_tilted && e->cv_tiles_tilted && !is_tree;
-    const int lin_blocks = e->cv_row_blocks > 0 ? e->cv_row_blocks : tilt_tiles ? 2 : trees && !rows_tree2 ? 3 : 2;
-    const int lin_min_windows = e->cv_tile_min_windows > 0 ? e->cv_tile_min_windows : tilt_tiles ? 512 : trees ? 1536 : 2048;
-    pl->row_blocks = is_tree ? e->cv_row_blocks_tree : lin_blocks;
-    // a call of <= 4 frames is bound by latency, not by the balance of two saturated chains: one row-kernel workgroup per CU
-    // and every scale that has a tile of 512 windows on tiles (one 1080p frame: 2.4 -> 2.0 ms)
-    int min_windows = is_tree ? e->cv_tile_min_windows_tree : lin_min_windows, min_windows0 = tilt_tiles ? std::min(e->cv_tile_min_windows0, 512) : e->cv_tile_min_windows0;
-    if (small_batch && !is_tree) {
-        pl->row_blocks = 1;
-        min_windows = std::min(min_windows, 512);
-        min_windows0 = std::min(min_windows0, 1024);
-    }
-    const size_t n_nodes = c->nodes.size();
-    std::vector<CvScaleDev>& scales = pl->scales;
-    scales.assign(hs.size(), CvScaleDev{});
-    std::vector<CvNodeRec> table((si ? std::min<size_t>(hs.size(), 1) : hs.size()) * n_nodes);   // (the levels share the table of factor 1)
-    table.reserve(2 * hs.size() * n_nodes);   // tile copies of the small scales' records are appended: no reallocation, `recs` stays valid
-    std::vector<UnitDev> rows;
-    std::vector<int> tile_class(hs.size(), -1);
-    std::vector<CvPruneDev> prune(pl->prune ? hs.size() : 0);
-    bool reach_ok = true;
-    const uint32_t frame_elems = frame_elems_for(IW, IH);
-    uint64_t max_reach = 0;   // furthest element a feature of this scale touches, from the window origin
-    pl->level_factor.clear();
-    for (size_t k = 0; k < hs.size(); ++k) {
-        if (!si || k == 0) max_reach = 0;
-        const double scale = si ? 1. : hs[k].factor;   // cvSetImagesForHaarClassifierCascade(.., 1.) for every level (:1321)
-        pl->level_factor.push_back(hs[k].factor);
-        CvScaleDev& sd = scales[k];
-        memset(&sd, 0, sizeof(sd));
-        sd.ystep = si ? (double)hs[k].step : std::max(2., scale);
-        // equRect (tempcv.cpp:607-611): x = y = cvRound(scale), (orig - 2) * scale rounded
-        const int ex = cv_round(scale), ew = cv_round((c->win_w - 2) * scale), eh = cv_round((c->win_h - 2) * scale);
-        const double weight_scale = 1. / (ew * eh);
-        sd.inv_area = weight_scale;
-        sd.win_w = (uint32_t)hs[k].win_w;
-        sd.win_h = (uint32_t)hs[k].win_h;
-        sd.end_x = (uint32_t)hs[k].end_x;
-        sd.end_y = (uint32_t)hs[k].end_y;
-        sd.q0 = (uint32_t)ex * stride + (uint32_t)ex;
-        sd.q1 = sd.q0 + (uint32_t)ew;
-        sd.q2 = (uint32_t)(ex + eh) * stride + (uint32_t)ex;
-        sd.q3 = sd.q2 + (uint32_t)ew;
-        sd.table_first = si ? 0u : (uint32_t)(k * n_nodes);
-        sd.scale_idx = (uint32_t)hs[k].idx;
-        CvNodeRec* recs = table.data() + sd.table_first;
-        if (!(si && k != 0)) {
-            const int nrc = build_cv_node_recs(c, scale, stride, weight_scale, recs, &max_reach);
-            if (nrc) return nrc;
-        }
-        // evaluated windows satisfy x + win_w <= W and y + win_h <= H (border rule); a feature may overshoot its
-        // window by one column / row (separate rounding): the frame allocation has two zeroed slack rows for that
-        // (a level: its windows lie inside it, and it inside the canvas)
-        const uint64_t origin_max = si ? (uint64_t)(hs[k].oy + hs[k].lh - c->win_h) * stride + (uint64_t)(hs[k].ox + hs[k].lw - c->win_w)
-                                       : (uint64_t)(H - hs[k].win_h) * stride + (uint64_t)(W - hs[k].win_w);
-        if (origin_max + max_reach >= (uint64_t)frame_elems) reach_ok = false;
-        if (pl->prune) {
-            // CV_HAAR_DO_CANNY_PRUNING (tempcv.cpp:1147-1158): the rectangle [x + ex, + ew) x [y + ey, + eh) of the scaled window, tested at
-            // every visited position BEFORE the border rule — so its furthest corner, from the last grid position, must stay in the frame's
-            // allocation (rows past H read the zeroed slack rows, as OpenCV's pointers read whatever follows)
-            const int px = cv_round(hs[k].win_w * 0.15), py = cv_round(hs[k].win_h * 0.15);
-            const int pw = cv_round(hs[k].win_w * 0.7), ph = cv_round(hs[k].win_h * 0.7);
-            CvPruneDev& pr = prune[k];
-            pr.p0 = (uint32_t)py * stride + (uint32_t)px;
-            pr.p1 = pr.p0 + (uint32_t)pw;
-            pr.p2 = (uint32_t)(py + ph) * stride + (uint32_t)px;
-            pr.p3 = pr.p2 + (uint32_t)pw;
-            const uint64_t last = (uint64_t)cv_round((double)(sd.end_y - 1u) * sd.ystep) * stride + (uint64_t)cv_round((double)(sd.end_x - 1u) * sd.ystep);
-            if (last + pr.p3 >= (uint64_t)frame_elems) reach_ok = false;
-        }
-        for (uint32_t iy = 0; iy < sd.end_y && !fb; ++iy)   // (find-biggest: cv_biggest_pass lays out a scale's rows itself)
-            rows.push_back(UnitDev{(uint32_t)k, iy, si ? (uint32_t)hs[k].oy * stride + (uint32_t)hs[k].ox : 0u, 0});
-
-        // ---- LDS-tile path (vj_cv_tile.hip): stump cascades with linear stages and upright features.  A tile is tw x th
-        // windows (tw divides 64, so a tile row never straddles a word of the reject / visited bitmap); its footprint is
-        // the span of its window origins plus the furthest corner any feature or the equRect reaches.  Two LDS classes
-        // like the clod profile's tiles: two workgroups per CU or one, next to one workgroup of cv_profile_pass.
-        // Tilted features (round 4): the tile's footprint of the TILTED integral is staged right behind the sum's (same origin, pitch and
-        // rows: a tilted rectangle's corners (y, x), (y + h, x - h), (y + w, x + w), (y + w + h, x + w - h) lie inside the window's box), a
-        // tilted node's record carries that distance in its corner offsets, and the kernel's node code does not change.
-        const bool tiles_tilted = has_tilted && e->cv_tiles_tilted && !is_tree;
-        // CV_HAAR_SCALE_IMAGE: the levels of linear cascades whose grid fills a tile run cv_tile_pass<3> (the exhaustive grid; step 1 or 2);
-        // stage trees stay on the exhaustive-grid row kernel (their tile path is built around the tree queue and the accept bitmap)
-        // (a ROC call keeps every level on the rows: the tile kernel has no form that reports reject levels)
-        if (!fb && !(si && is_tree) && !roc && e->cv_tiles && (!trees || (tree2 && !is_tree)) && (!is_tree || tree_prefix != 0u) && (!has_tilted || tiles_tilted) && sd.end_x < 65536u &&
-            sd.end_y < 65536u) {
-            uint32_t reach_x = (uint32_t)(ex + ew), reach_y = (uint32_t)(ex + eh);
-            for (size_t n = 0; n < n_nodes; ++n) {
-                const CvNodeRec& r = recs[n];
-                for (int q = 0; q < 3; ++q)
-                    if (q < 2 || r.w[2] != 0.0f) {
-                        const uint32_t p0 = r.lt[q] / 4u;
-                        if (r.flags & CV_NODE_TILTED) {   // da = h * (stride - 1), db = w * (stride + 1): rightmost corner x + w, lowest y + w + h
-                            const uint32_t hh = (r.da[q] / 4u) / (stride - 1u), ww = (r.db[q] / 4u) / (stride + 1u);
-                            reach_x = std::max(reach_x, p0 % stride + ww);
-                            reach_y = std::max(reach_y, p0 / stride + ww + hh);
-                        } else {
-                            reach_x = std::max(reach_x, p0 % stride + r.da[q] / 4u);
-                            reach_y = std::max(reach_y, p0 / stride + (r.db[q] / 4u) / stride);
-                        }
-                    }
-            }
-            const uint32_t images = has_tilted ? 2u : 1u;   // LDS images per tile
-            static const uint32_t kTw[] = {64, 32, 16}, kTh[] = {32, 24, 16, 12, 8, 4};
-            // LDS budget of a CU: the row kernel's workgroups (20 KiB each) stay resident next to two tile workgroups
-            // of class 0 or one of class 1; a tile workgroup also owns CVT_LDS_HEADER bytes of queues
-            const uint32_t avail = 160u * 1024u - (uint32_t)pl->row_blocks * 20u * 1024u - 1024u;
-            const uint32_t class_bytes[2] = {avail / 2u - (uint32_t)CVT_LDS_HEADER, avail - (uint32_t)CVT_LDS_HEADER};
-            uint32_t best_n = 0, b_tw = 0, b_th = 0, b_pitch = 0, b_rows = 0;
-            int b_cls = -1;
-            for (int cls = 0; cls < 2 && b_cls < 0; ++cls) {
-                for (uint32_t tw : kTw)
-                    for (uint32_t th : kTh) {
-                        const uint32_t pitch = (((uint32_t)std::ceil((double)(tw - 1) * sd.ystep) + 3u + reach_x) + 3u) & ~3u;
-                        const uint32_t trows = (uint32_t)std::ceil((double)(th - 1) * sd.ystep) + 3u + reach_y;
-                        if ((uint64_t)pitch * trows * 4u * images > class_bytes[cls]) continue;
-                        const uint32_t nwin = std::min(tw, sd.end_x) * std::min(th, sd.end_y);
-                        if (nwin > best_n) { best_n = nwin; b_tw = tw; b_th = th; b_pitch = pitch; b_rows = trows; }
-                    }
-                // a class-0 tile must be worth two workgroups per CU; else try the larger class
-                if (best_n >= (uint32_t)(cls == 0 ? min_windows0 : min_windows))
-                    b_cls = cls;
-                else
-                    best_n = 0;
-            }
-            if (b_cls >= 0) {
-                sd.tile_tw = b_tw;
-                sd.tile_th = b_th;
-                sd.tile_pitch = b_pitch;
-                sd.tile_rows = b_rows;
-                tile_class[k] = b_cls;
-                if (si) {   // levels whose tiles have one shape share one table in that pitch: every level is the cascade at factor 1
-                    bool shared = false;
-                    for (size_t j = 0; j < k && !shared; ++j)
-                        if (scales[j].tile_th != 0u && scales[j].tile_pitch == b_pitch && scales[j].tile_rows == b_rows) {
-                            sd.tile_table_first = scales[j].tile_table_first;
-                            shared = true;
-                        }
-                    if (shared) continue;
-                }
-                sd.tile_table_first = (uint32_t)table.size();
-                table.resize(table.size() + n_nodes);   // (within the reserved capacity)
-                CvNodeRec* trec = table.data() + sd.tile_table_first;
-                for (size_t n = 0; n < n_nodes; ++n) {
-                    trec[n] = recs[n];
-                    for (int q = 0; q < 3; ++q)
-                        if (q < 2 || recs[n].w[2] != 0.0f) {
-                            const uint32_t p0 = recs[n].lt[q] / 4u;
-                            if (recs[n].flags & CV_NODE_TILTED) {   // in the tilted image behind the sum image, corner steps in the tile's pitch
-                                const uint32_t hh = (recs[n].da[q] / 4u) / (stride - 1u), ww = (recs[n].db[q] / 4u) / (stride + 1u);
-                                trec[n].lt[q] = (b_pitch * b_rows + (p0 / stride) * b_pitch + p0 % stride) * 4u;
-                                trec[n].da[q] = (hh * b_pitch - hh) * 4u;
-                                trec[n].db[q] = (ww * b_pitch + ww) * 4u;
-                            } else {
-                                const uint32_t hh = (recs[n].db[q] / 4u) / stride;
-                                trec[n].lt[q] = ((p0 / stride) * b_pitch + p0 % stride) * 4u;
-                                trec[n].db[q] = hh * b_pitch * 4u;
-                            }
-                        }
-                }
-            }
-        }
-    }
-    // tiles of one frame by LDS class; rows of the scales that stay on cv_profile_pass; one recurrence domain per window
-    // row of a tile scale in the per-frame bitmap
-    std::vector<UnitDev> tiles, rows_rest, bit_segs;
-    pl->n_tile_scales = 0;
-    {
-        uint32_t word = 0;
-        for (size_t k = 0; k < hs.size(); ++k) {
-            CvScaleDev& sd = scales[k];
-            if (sd.tile_th == 0u) continue;
-            sd.tq_slot = pl->n_tile_scales;
-            sd.tq_win_first = (uint32_t)std::min<uint64_t>(pl->tile_windows, 0xffffffffull);
-            ++pl->n_tile_scales;
-            pl->tile_windows += (uint64_t)sd.end_x * sd.end_y;
-            sd.bits_base = word;
-            const uint32_t wpr = (sd.end_x + 63u) / 64u;
-            for (uint32_t iy = 0; iy < sd.end_y; ++iy) bit_segs.push_back(UnitDev{(uint32_t)k, word + iy * wpr, wpr, 0});
-            word += wpr * sd.end_y;
-        }
-        pl->bits_frame_words = word;
-        for (int cls = 0; cls < 2; ++cls) {
-            pl->class_first[cls] = (uint32_t)tiles.size();
-            uint32_t lds = 0;
-            for (size_t k = 0; k < hs.size(); ++k) {
-                const CvScaleDev& sd = scales[k];
-                if (sd.tile_th == 0u || tile_class[k] != cls) continue;
-                lds = std::max(lds, (uint32_t)CVT_LDS_HEADER + sd.tile_pitch * sd.tile_rows * 4u * (has_tilted ? 2u : 1u));
-                for (uint32_t iy0 = 0; iy0 < sd.end_y; iy0 += sd.tile_th)
-                    for (uint32_t ix0 = 0; ix0 < sd.end_x; ix0 += sd.tile_tw)
-                        tiles.push_back(UnitDev{(uint32_t)k, ix0 | (iy0 << 16), si ? (uint32_t)hs[k].oy * stride + (uint32_t)hs[k].ox : 0u, 0});
-            }
-            pl->class_lds[cls] = lds;
-        }
-        pl->class_first[2] = (uint32_t)tiles.size();
-        // Band-major row order (cv_row_band_px != 0): the rows of ALL scales whose top lies in one band of the image, band after
-        // band.  The waves of an XCD walk one contiguous piece of the (frame, row) list together (cv_profile_pass), so what they
-        // gather from at one time is a band of one frame's integral image — within the XCD's 4 MB of L2 — instead of a whole
-        // scale's rows, i.e. the whole 8.3 MB image (rows are independent: the skip rule runs along a row).
-        if (e->cv_row_band_px > 0) {
-            const double band = (double)e->cv_row_band_px;
-            std::stable_sort(rows.begin(), rows.end(), [&](const UnitDev& x, const UnitDev& y) {
-                // (levels: bands of the canvas)
-                const uint32_t bx = (uint32_t)(((double)x.first * scales[x.scale].ystep + hs[x.scale].oy) / band),
-                               by = (uint32_t)(((double)y.first * scales[y.scale].ystep + hs[y.scale].oy) / band);
-                return bx != by ? bx < by : x.scale != y.scale ? x.scale < y.scale : x.first < y.first;
-            });
-        }
-        for (const UnitDev& r : rows)
-            if (scales[r.scale].tile_th == 0u) rows_rest.push_back(r);
-    }
-    const std::vector<StageDev> stages = build_cv_stage_recs(c, prog, order, two_rects, trees, is_tree);
-    if (!reach_ok) {
-        set_error("feature reach exceeds the frame allocation");
-        return VJ_ERR_LIMIT;
-    }
-
-    int rc;
-    if ((rc = pl->d_table.ensure(std::max<size_t>(table.size(), 1) * sizeof(CvNodeRec)))) return rc;
-    if ((rc = pl->d_scales.ensure(std::max<size_t>(scales.size(), 1) * sizeof(CvScaleDev)))) return rc;
-    if ((rc = pl->d_stages.ensure(stages.size() * sizeof(StageDev)))) return rc;
-    if ((rc = pl->d_rows.ensure(std::max<size_t>(rows.size(), 1) * sizeof(UnitDev)))) return rc;
-    if ((rc = pl->d_tiles.ensure(std::max<size_t>(tiles.size(), 1) * sizeof(UnitDev)))) return rc;
-    if ((rc = pl->d_rows_rest.ensure(std::max<size_t>(rows_rest.size(), 1) * sizeof(UnitDev)))) return rc;
-    if ((rc = pl->d_bit_segs.ensure(std::max<size_t>(bit_segs.size(), 1) * sizeof(UnitDev)))) return rc;
-    if (!prune.empty()) {
-        if ((rc = pl->d_prune.ensure(prune.size() * sizeof(CvPruneDev)))) return rc;
-        HIP_TRY(hipMemcpy(pl->d_prune.p, prune.data(), prune.size() * sizeof(CvPruneDev), hipMemcpyHostToDevice));
-    }
-    if (!tiles.empty()) HIP_TRY(hipMemcpy(pl->d_tiles.p, tiles.data(), tiles.size() * sizeof(UnitDev), hipMemcpyHostToDevice));
-    if (!rows_rest.empty()) HIP_TRY(hipMemcpy(pl->d_rows_rest.p, rows_rest.data(), rows_rest.size() * sizeof(UnitDev), hipMemcpyHostToDevice));
-    if (!bit_segs.empty()) HIP_TRY(hipMemcpy(pl->d_bit_segs.p, bit_segs.data(), bit_segs.size() * sizeof(UnitDev), hipMemcpyHostToDevice));
-    pl->n_rows_rest = (uint32_t)rows_rest.size();
-    pl->n_bit_segs = (uint32_t)bit_segs.size();
-    if (!table.empty()) HIP_TRY(hipMemcpy(pl->d_table.p, table.data(), table.size() * sizeof(CvNodeRec), hipMemcpyHostToDevice));
-    if (!scales.empty()) HIP_TRY(hipMemcpy(pl->d_scales.p, scales.data(), scales.size() * sizeof(CvScaleDev), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pl->d_stages.p, stages.data(), stages.size() * sizeof(StageDev), hipMemcpyHostToDevice));
-    if (!rows.empty()) HIP_TRY(hipMemcpy(pl->d_rows.p, rows.data(), rows.size() * sizeof(UnitDev), hipMemcpyHostToDevice));
-    pl->n_rows = (uint32_t)rows.size();
-    if (si && !hs.empty()) {
-        // the pyramid launch's level table and taps (vj_pyramid.hip): per level its columns' taps, then its rows'
-        std::vector<PyrLevelDev> lv(hs.size());
-        size_t n_taps = 0;
-        for (const CvScaleHost& s : hs) n_taps += (size_t)s.lw + (size_t)s.lh;
-        std::vector<PyrTap> taps(n_taps);
-        uint32_t tap = 0, unit = 0;
-        for (size_t k = 0; k < hs.size(); ++k) {
-            const CvScaleHost& s = hs[k];
-            const bool area = resize_is_area(W, H, s.lw, s.lh);
-            lv[k] = PyrLevelDev{(uint32_t)s.ox, (uint32_t)s.oy, (uint32_t)s.lw, (uint32_t)s.lh, tap, tap + (uint32_t)s.lw, unit, area ? 1u : 0u};
-            build_taps(W, s.lw, false, area, taps.data() + tap);
-            build_taps(H, s.lh, true, area, taps.data() + tap + s.lw);
-            tap += (uint32_t)(s.lw + s.lh);
-            const uint64_t units = (uint64_t)((s.lw + PYR_UNIT_PX - 1) / PYR_UNIT_PX) * (uint64_t)s.lh;
-            if (unit + units > 0x7fffffffull) {
-                set_error("the image pyramid has too many work units");
-                return VJ_ERR_LIMIT;
-            }
-            unit += (uint32_t)units;
-        }
-        if ((rc = pl->d_pyr_levels.ensure(lv.size() * sizeof(PyrLevelDev)))) return rc;
-        if ((rc = pl->d_pyr_taps.ensure(taps.size() * sizeof(PyrTap)))) return rc;
-        HIP_TRY(hipMemcpy(pl->d_pyr_levels.p, lv.data(), lv.size() * sizeof(PyrLevelDev), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(pl->d_pyr_taps.p, taps.data(), taps.size() * sizeof(PyrTap), hipMemcpyHostToDevice));
-        pl->n_pyr_levels = (uint32_t)lv.size();
-        pl->n_pyr_units = unit;
+// The device copies of a plan: every table at the size its kernels index, at least one element where a launch binds the pointer
+// of an empty list.
+static int upload_cv_plan(CvPlan* pl, const CvPlanTables& tab) {
+    struct Row { DevBuf* buf; const void* src; size_t bytes, min_bytes; };
+    const Row rows[] = {
+        {&pl->d_table, tab.table.data(), tab.table.size() * sizeof(CvNodeRec), sizeof(CvNodeRec)},
+        {&pl->d_scales, pl->scales.data(), pl->scales.size() * sizeof(CvScaleDev), sizeof(CvScaleDev)},
+        {&pl->d_stages, tab.stages.data(), tab.stages.size() * sizeof(StageDev), 0},
+        {&pl->d_rows, tab.rows.data(), tab.rows.size() * sizeof(UnitDev), sizeof(UnitDev)},
+        {&pl->d_tiles, tab.tiles.data(), tab.tiles.size() * sizeof(UnitDev), sizeof(UnitDev)},
+        {&pl->d_rows_rest, tab.rows_rest.data(), tab.rows_rest.size() * sizeof(UnitDev), sizeof(UnitDev)},
+        {&pl->d_bit_segs, tab.bit_segs.data(), tab.bit_segs.size() * sizeof(UnitDev), sizeof(UnitDev)},
+        {&pl->d_prune, tab.prune.data(), tab.prune.size() * sizeof(CvPruneDev), 0},
+        {&pl->d_pyr_levels, tab.pyr_levels.data(), tab.pyr_levels.size() * sizeof(PyrLevelDev), 0},
+        {&pl->d_pyr_taps, tab.pyr_taps.data(), tab.pyr_taps.size() * sizeof(PyrTap), 0},
+    };
+    for (const Row& r : rows) {
+        const size_t want = std::max(r.bytes, r.min_bytes);
+        if (!want) continue;   // (an empty list nothing binds)
+        if (const int rc = r.buf->ensure(want)) return rc;
+        if (r.bytes) HIP_TRY(hipMemcpy(r.buf->p, r.src, r.bytes, hipMemcpyHostToDevice));
     }
     return VJ_OK;
 }
@@ -655,16 +82,12 @@ static int get_cv_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_cv
     }
     if ((int)e->cv_plans.size() >= std::max(1, e->plan_cache_max)) {   // bounded: the least recently used plans go first
         HIP_TRY(hipStreamSynchronize(e->stream));
-        while ((int)e->cv_plans.size() >= std::max(1, e->plan_cache_max)) {
-            auto lru = e->cv_plans.begin();
-            for (auto i = e->cv_plans.begin(); i != e->cv_plans.end(); ++i)
-                if (i->second->last_used < lru->second->last_used) lru = i;
-            lru->second->release_device();
-            e->cv_plans.erase(lru);
-        }
+        cache_make_room(e, e->cv_plans);
     }
     auto pl = std::make_unique<CvPlan>();
-    const int rc = build_cv_plan(e, c, W, H, p, small_batch, pl.get(), roc);
+    CvPlanTables tab;
+    int rc = plan_cv(*e, c, W, H, *p, small_batch, roc, pl.get(), &tab);
+    if (!rc) rc = upload_cv_plan(pl.get(), tab);
     if (rc) {
         pl->release_device();
         return rc;
@@ -1706,10 +1129,9 @@ int get_cv_roi_plan(vj_env* e, const vj_cascade* c, int W, const vj_cv_params* p
         *out = pl;
         return VJ_OK;
     }
-    if ((int)c->stages.size() > VJ_MAX_STAGES || c->stages.empty()) {
-        set_error("cascade has %zu stages; 1..%d are supported", c->stages.size(), VJ_MAX_STAGES);
-        return VJ_ERR_LIMIT;
-    }
+    CvCascadeHost ch;   // (a plan that only grows was built from this cascade before)
+    if (!pl)
+        if (const int crc = cv_cascade_host(c, &ch)) return crc;
     const size_t n_nodes = c->nodes.size();
     if ((uint64_t)n_factors * n_nodes > (1ull << 26)) {
         set_error("scale_factor %.17g gives %d factors: the node tables would exceed 4 GiB", p->scale_factor, n_factors);
@@ -1718,31 +1140,18 @@ int get_cv_roi_plan(vj_env* e, const vj_cascade* c, int W, const vj_cv_params* p
     HIP_TRY(hipStreamSynchronize(e->stream));   // (tables are released below)
     std::unique_ptr<CvRoiPlan> fresh;
     if (!pl) {
-        while (!e->cv_roi_plans.empty() && (int)e->cv_roi_plans.size() >= std::max(1, e->plan_cache_max)) {   // least recently used first
-            auto lru = e->cv_roi_plans.begin();
-            for (auto i = e->cv_roi_plans.begin(); i != e->cv_roi_plans.end(); ++i)
-                if (i->second->last_used < lru->second->last_used) lru = i;
-            lru->second->release_device();
-            e->cv_roi_plans.erase(lru);
-        }
+        cache_make_room(e, e->cv_roi_plans);
         fresh = std::make_unique<CvRoiPlan>();
         pl = fresh.get();
-        pl->prog = build_stage_program(*c);
-        std::vector<uint32_t> order;
-        if (!stage_sweep_order(pl->prog, &order)) {
-            set_error("stage links form a cycle");
-            return VJ_ERR_UNSUPPORTED;
-        }
-        const CvShape shape = cv_shape_of(c);
-        pl->trees = shape.trees;
-        pl->is_tree = shape.is_tree;
-        pl->has_tilted = shape.has_tilted;
-        pl->tree2 = shape.tree2;
-        pl->n_order = (uint32_t)order.size();
+        pl->prog = ch.prog;
+        pl->trees = ch.shape.trees;
+        pl->is_tree = ch.shape.is_tree;
+        pl->has_tilted = ch.shape.has_tilted;
+        pl->tree2 = ch.shape.tree2;
+        pl->n_order = (uint32_t)ch.order.size();
         pl->n_stages = (uint32_t)c->stages.size();
-        const std::vector<StageDev> stages = build_cv_stage_recs(c, pl->prog, order, shape.two_rects, shape.trees, shape.is_tree);
-        int rc = pl->d_stages.ensure(stages.size() * sizeof(StageDev));
-        if (!rc && hipMemcpy(pl->d_stages.p, stages.data(), stages.size() * sizeof(StageDev), hipMemcpyHostToDevice) != hipSuccess) {
+        int rc = pl->d_stages.ensure(ch.stages.size() * sizeof(StageDev));
+        if (!rc && hipMemcpy(pl->d_stages.p, ch.stages.data(), ch.stages.size() * sizeof(StageDev), hipMemcpyHostToDevice) != hipSuccess) {
             set_error("uploading the stage records failed");
             rc = VJ_ERR_HIP;
         }
@@ -1766,19 +1175,13 @@ int get_cv_roi_plan(vj_env* e, const vj_cascade* c, int W, const vj_cv_params* p
         CvRoiFactor& f = factors[(size_t)k];
         f = cv_roi_factor(c->win_w, c->win_h, factor);
         sd.ystep = f.ystep;
-        // equRect (tempcv.cpp:607-611): x = y = cvRound(scale), (orig - 2) * scale rounded
-        const int ex = cv_round(factor), ew = cv_round((c->win_w - 2) * factor), eh = cv_round((c->win_h - 2) * factor);
-        const double weight_scale = 1. / (ew * eh);
-        sd.inv_area = weight_scale;
+        const CvEquRect q = cv_equ_rect(c->win_w, c->win_h, factor);
+        cv_set_equ_rect(&sd, q, stride);
         sd.win_w = (uint32_t)f.win_w;
         sd.win_h = (uint32_t)f.win_h;
-        sd.q0 = (uint32_t)ex * stride + (uint32_t)ex;
-        sd.q1 = sd.q0 + (uint32_t)ew;
-        sd.q2 = (uint32_t)(ex + eh) * stride + (uint32_t)ex;
-        sd.q3 = sd.q2 + (uint32_t)ew;
         sd.table_first = (uint32_t)((size_t)k * n_nodes);
         sd.scale_idx = (uint32_t)k;
-        rc = build_cv_node_recs(c, factor, stride, weight_scale, table.data() + sd.table_first, &f.max_reach);
+        rc = build_cv_node_recs(c, factor, stride, q.inv_area, table.data() + sd.table_first, &f.max_reach);
     }
     if (!rc) rc = pl->d_table.ensure(std::max<size_t>(table.size(), 1) * sizeof(CvNodeRec));
     if (!rc) rc = pl->d_scales.ensure(std::max<size_t>(scales.size(), 1) * sizeof(CvScaleDev));
@@ -2114,12 +1517,7 @@ struct CvPoints {
     static int build_scale(const vj_cascade* c, double scale, int W, const CvPointScale& sc, CvPointScaleDev* rec, CvNodeRec* table,
                            uint64_t* max_reach) {
         const uint32_t stride = (uint32_t)W + 1u;
-        // equRect (tempcv.cpp:614-616): x = y = cvRound(scale), (orig - 2) * scale rounded
-        rec->inv_area = sc.weight_scale;
-        rec->q0 = (uint32_t)sc.ex * stride + (uint32_t)sc.ex;
-        rec->q1 = rec->q0 + (uint32_t)sc.ew;
-        rec->q2 = (uint32_t)(sc.ex + sc.eh) * stride + (uint32_t)sc.ex;
-        rec->q3 = rec->q2 + (uint32_t)sc.ew;
+        cv_set_equ_rect(rec, CvEquRect{sc.ex, sc.ew, sc.eh, sc.weight_scale}, stride);   // (cv_point_scale's equRect: clamped so that no scale overflows an int)
         *max_reach = rec->q3;
         return build_cv_node_recs(c, scale, stride, sc.weight_scale, table, max_reach);
     }
@@ -2155,22 +1553,16 @@ const uint64_t CV_ROI_CANVAS_PX = 1ull << 24;
 int run_cv_rois_levels(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_roi* rois, int n_rois, int W, int H, int CH,
                        const vj_cv_params* p, uint64_t budget_px, std::vector<vj_rect>* all, vj_result* out, StageProgram* prog_out,
                        std::vector<int>* oversized) {
-    if ((int)c->stages.size() > VJ_MAX_STAGES || c->stages.empty()) {
-        set_error("cascade has %zu stages; 1..%d are supported", c->stages.size(), VJ_MAX_STAGES);
-        return VJ_ERR_LIMIT;
-    }
-    *prog_out = build_stage_program(*c);
+    CvCascadeHost ch;
+    int rc = cv_cascade_host(c, &ch);
+    if (rc) return rc;
+    *prog_out = ch.prog;
     const StageProgram& prog = *prog_out;
-    std::vector<uint32_t> order;
-    if (!stage_sweep_order(prog, &order)) {
-        set_error("stage links form a cycle");
-        return VJ_ERR_UNSUPPORTED;
-    }
-    const CvShape shape = cv_shape_of(c);
-    const std::vector<StageDev> stages = build_cv_stage_recs(c, prog, order, shape.two_rects, shape.trees, shape.is_tree);
+    const std::vector<uint32_t>& order = ch.order;
+    const CvShape& shape = ch.shape;
+    const std::vector<StageDev>& stages = ch.stages;
     const bool count = (p->flags & VJ_FLAG_COUNTERS) != 0;
     const size_t n_nodes = c->nodes.size();
-    int rc;
     if ((rc = e->d_cv_rl_stages.ensure(stages.size() * sizeof(StageDev)))) return rc;
     HIP_TRY(hipMemcpy(e->d_cv_rl_stages.p, stages.data(), stages.size() * sizeof(StageDev), hipMemcpyHostToDevice));
     DevBuf& d_det = e->d_cv_det;
@@ -2225,11 +1617,10 @@ int run_cv_rois_levels(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         if ((rc = ensure_image_buffers(e, IW, IH, 1, false))) return rc;
         if ((rc = e->d_pyr.ensure((size_t)cv.pitch * (size_t)cv.h))) return rc;
         // the cascade at factor 1 (cvSetImagesForHaarClassifierCascade(.., 1.), tempcv.cpp:1321) in this canvas's pitch
-        const int ex = cv_round(1.), ew = cv_round((c->win_w - 2) * 1.), eh = cv_round((c->win_h - 2) * 1.);
-        const double weight_scale = 1. / (ew * eh);
+        const CvEquRect q = cv_equ_rect(c->win_w, c->win_h, 1.);
         if (table_stride != stride) {
             max_reach = 0;
-            if ((rc = build_cv_node_recs(c, 1., stride, weight_scale, table.data(), &max_reach))) return rc;
+            if ((rc = build_cv_node_recs(c, 1., stride, q.inv_area, table.data(), &max_reach))) return rc;
             if ((rc = e->d_cv_rl_table.ensure(std::max<size_t>(table.size(), 1) * sizeof(CvNodeRec)))) return rc;
             HIP_TRY(hipStreamSynchronize(e->stream));   // (the last canvas's pass is done: every iteration ends in a synchronise)
             if (!table.empty()) HIP_TRY(hipMemcpy(e->d_cv_rl_table.p, table.data(), table.size() * sizeof(CvNodeRec), hipMemcpyHostToDevice));
@@ -2244,15 +1635,11 @@ int run_cv_rois_levels(vj_env* e, const vj_cascade* c, const vj_image* frames, i
             CvScaleDev& sd = scales[k];
             memset(&sd, 0, sizeof(sd));
             sd.ystep = (double)l.step;
-            sd.inv_area = weight_scale;
+            cv_set_equ_rect(&sd, q, stride);
             sd.win_w = (uint32_t)l.win_w;
             sd.win_h = (uint32_t)l.win_h;
             sd.end_x = (uint32_t)l.end_x;
             sd.end_y = (uint32_t)l.end_y;
-            sd.q0 = (uint32_t)ex * stride + (uint32_t)ex;
-            sd.q1 = sd.q0 + (uint32_t)ew;
-            sd.q2 = (uint32_t)(ex + eh) * stride + (uint32_t)ex;
-            sd.q3 = sd.q2 + (uint32_t)ew;
             sd.table_first = 0u;
             sd.scale_idx = (uint32_t)l.idx;
             // a level image's windows lie inside it, and it inside the canvas
@@ -2449,7 +1836,7 @@ int vj_detect_opencv_roc(vj_env* e, const vj_cascade* c, const vj_image* frames,
     std::vector<int32_t> levels;
     std::vector<double> weights;
     const bool whole = p->max_w == 0 || p->max_h == 0;   // maxSize with a zero member is the frame (:1230-1234)
-    const CvRocCall roc{whole ? frames[0].width : p->max_w, whole ? frames[0].height : p->max_h, &levels, &weights};
+    const CvRocCall roc{{whole ? frames[0].width : p->max_w, whole ? frames[0].height : p->max_h}, &levels, &weights};
     int rc = detect_opencv_impl(e, c, frames, n_frames, &q, &out->r, false, nullptr, &roc);
     if (rc) {
         vj_roc_result_free(out);

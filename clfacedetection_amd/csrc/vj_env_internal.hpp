@@ -5,6 +5,7 @@
 #include "vj_device.hpp"
 #include "vj_tunables.hpp"
 #include "vj_clod_plan.hpp"
+#include "vj_cv_plan.hpp"
 #include "vj_cv_roi_host.hpp"
 #include "vj_cv_points_host.hpp"
 #include "vj_points_host.hpp"
@@ -76,38 +77,17 @@ struct Plan : PlanHost {
     }
 };
 
-// What vj_detect_opencv derives from (cascade, frame size, parameters): kept per environment like the clod plans, so that a
-// caller that hands over one frame per call (main.cpp:145) does not rebuild and upload 42 feature tables every time.
-struct CvPlan {
-    std::vector<CvScaleDev> scales;   // host copy (window sizes and scale indices of the result)
-    StageProgram prog;
-    uint32_t n_stages = 0, n_order = 0, n_rows = 0;
-    bool trees = false, is_tree = false, has_tilted = false, tree2 = false;
+// A plan of the OpenCV profile: what the planner computed from (cascade, frame size, parameters) (CvPlanHost, vj_cv_plan.hpp) and its
+// device copies (upload_cv_plan, vj_cv.cpp).  Kept per environment like the clod plans, so that a caller that hands over one frame
+// per call (main.cpp:145) does not rebuild and upload 42 feature tables every time.
+struct CvPlan : CvPlanHost {
     DevBuf d_table, d_scales, d_stages, d_rows;
-    // LDS-tile path (vj_cv_tile.hip): tiles of one frame per LDS class, the rows of the scales that stay on
-    // cv_profile_pass, and the per-frame reject / visited bitmap with one recurrence domain per window row
-    uint32_t n_tile_scales = 0, n_rows_rest = 0, bits_frame_words = 0, n_bit_segs = 0;
-    int row_blocks = 1;               // workgroups per CU of cv_profile_pass next to the tiles
-    uint32_t tree_prefix = 0;         // stage trees: stages of the linear prefix the tiles run (0: the cascade is linear)
-    CvChainDev chains = {};           // stage trees: the part after the prefix as chains (n = 0: not of that shape)
-    bool prune = false;               // CV_HAAR_DO_CANNY_PRUNING: every scale on cv_profile_pass<..., PRUNE>; d_prune per scale slot
-    DevBuf d_prune;
+    DevBuf d_tiles, d_rows_rest, d_bit_segs;   // LDS-tile path (vj_cv_tile.hip)
+    DevBuf d_prune;                   // CV_HAAR_DO_CANNY_PRUNING: per scale slot
+    DevBuf d_pyr_levels, d_pyr_taps;  // CV_HAAR_SCALE_IMAGE: the pyramid launch's level records and taps
     int tq_shift = -1;                // stage trees on tiles: the prefix survivors' sub-queues hold 1 / 2^shift of the tile windows
                                       // (-1: the environment's start value; lowered for THIS plan when a sub-queue overflows)
-    uint64_t tile_windows = 0;        // grid windows of the tile scales, per frame
     int tq_split_frames = 0;          // frames per sub-batch the tree queue last split a batch to (CV_TQ_MAX; 0: never)
-    uint32_t class_first[3] = {0, 0, 0}, class_lds[2] = {0, 0};
-    DevBuf d_tiles, d_rows_rest, d_bit_segs;
-    // CV_HAAR_SCALE_IMAGE (VJ_FLAG_CV_SCALE_IMAGE): `scales` are the evaluated LEVELS of the image pyramid, which share ONE node
-    // table at factor 1 in the canvas's pitch; every level's place in the canvas, its taps (vj_pyramid.hip) and output factor
-    // CV_HAAR_FIND_BIGGEST_OBJECT (VJ_FLAG_CV_FIND_BIGGEST): `scales` are the DESCENDING factors (repeated multiplication by the reciprocal),
-    // slot = position in the walk, scale_idx = n_factors - 1 - slot; every scale on cv_biggest_pass (no tiles, no pruning, no pyramid)
-    bool find_biggest = false;
-    bool scale_image = false;
-    bool roc = false;                 // vj_detect_opencv_roc: a scale-image plan whose levels all stay on the row kernel
-    std::vector<double> level_factor;   // per scale slot: what a position of the level is multiplied by
-    uint32_t canvas_w = 0, canvas_h = 0, canvas_pitch = 0, n_pyr_levels = 0, n_pyr_units = 0;
-    DevBuf d_pyr_levels, d_pyr_taps;
     uint64_t last_used = 0;
     void release_device() {
         for (DevBuf* b : {&d_table, &d_scales, &d_stages, &d_rows, &d_tiles, &d_rows_rest, &d_bit_segs, &d_prune, &d_pyr_levels, &d_pyr_taps}) b->release();
@@ -342,15 +322,16 @@ int enqueue_equalize_tables(vj_env* e, Lane* lane, const void* d_frame_recs, uin
 // What an entry point that does not equalize answers to the flag: VJ_ERR_UNSUPPORTED, vj_last_error names both; else VJ_OK.
 int refuse_equalize(uint32_t flags, const char* entry_point);
 
-// Room for one more entry in a cache of the run-windows calls (vj_run_windows_opencv, vj_run_windows): the least recently used go
-// first, but never an entry of the call in progress (last_used >= call_tick) — a call that names more scales than plan_cache_max
+// Room for one more entry in a plan cache bounded by plan_cache_max: the least recently used go first and release their tables (the
+// caller has synchronised the stream that may still read them).  An entry with last_used >= keep_tick stays: the run-windows calls
+// (vj_run_windows_opencv, vj_run_windows) pass the tick of the call in progress — a call that names more scales than plan_cache_max
 // keeps them all while it runs.
 template <typename Map>
-void point_make_room(vj_env* e, Map& m, uint64_t call_tick) {
+void cache_make_room(vj_env* e, Map& m, uint64_t keep_tick = ~0ull) {
     while ((int)m.size() >= std::max(1, e->plan_cache_max)) {
         auto lru = m.end();
         for (auto i = m.begin(); i != m.end(); ++i)
-            if (i->second->last_used < call_tick && (lru == m.end() || i->second->last_used < lru->second->last_used)) lru = i;
+            if (i->second->last_used < keep_tick && (lru == m.end() || i->second->last_used < lru->second->last_used)) lru = i;
         if (lru == m.end()) return;
         lru->second->release_device();
         m.erase(lru);

@@ -25,7 +25,7 @@ int get_point_cascade(vj_env* e, vj_env::PointCascades& m, const vj_cascade* c, 
         *out = it->second.get();
         return VJ_OK;
     }
-    point_make_room(e, m, call_tick);
+    cache_make_room(e, m, call_tick);
     auto pc = std::make_unique<PointCascade>();
     const StageProgram prog = build_stage_program(*c);
     std::vector<uint32_t> order;
@@ -60,7 +60,7 @@ int get_point_plan(vj_env* e, Map& m, const typename Map::key_type& key, uint32_
     auto it = m.find(key);
     Plan* pl = it != m.end() ? it->second.get() : nullptr;
     if (!pl) {
-        point_make_room(e, m, call_tick);
+        cache_make_room(e, m, call_tick);
         auto fresh = std::make_unique<Plan>();
         pl = fresh.get();
         pl->rec.win_w = win_w;

@@ -354,7 +354,7 @@ def refused_calls(env, lib, c, good, frames):
 
 @pytest.mark.parametrize("cid,code", [("lin65", VJ_ERR_LIMIT), ("st_cycle", VJ_ERR_UNSUPPORTED)])
 def test_refusals_leave_the_result_empty_and_the_environment_usable(env, lib, oracle, cid, code):
-    """More than VJ_MAX_STAGES stages: VJ_ERR_LIMIT from plan_clod, build_cv_plan, get_cv_roi_plan and run_points; a cycle of the
+    """More than VJ_MAX_STAGES stages: VJ_ERR_LIMIT from plan_clod, plan_cv, get_cv_roi_plan and run_points; a cycle of the
     pass / fail graph: VJ_ERR_UNSUPPORTED wherever stage_sweep_order is asked.  After every refusal a valid call on the same
     environment gives the oracle's result."""
     c = cascade_to_product(topology_cascade(cid))

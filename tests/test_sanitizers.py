@@ -24,7 +24,8 @@ def test_host_sources_under_asan_ubsan_legal_windows(tmp_path):
     exe = str(tmp_path / "host_asan")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
            "-DVJ_BUILDING", os.path.join(ROOT, "tests", "host_asan_driver.cpp")] + \
-          [os.path.join(CSRC, f) for f in ("vj_cascade.cpp", "vj_plan.cpp", "vj_clod_plan.cpp", "vj_group.cpp")] + ["-o", exe]
+          [os.path.join(CSRC, f) for f in ("vj_cascade.cpp", "vj_plan.cpp", "vj_clod_plan.cpp", "vj_group.cpp", "vj_cv_plan.cpp", "vj_cv_roi_host.cpp",
+                                          "vj_cv_roi_levels_host.cpp")] + ["-o", exe]
     subprocess.run(cmd, check=True, capture_output=True)
     r = subprocess.run([exe, os.path.join(ROOT, "clfacedetection_amd", "data"), str(tmp_path)], capture_output=True, text=True,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
