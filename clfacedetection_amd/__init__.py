@@ -14,4 +14,5 @@ from .api import (  # noqa: F401
     clodReleaseEnvironment, cvHaarDetectObjects, cvHaarDetectObjectsForROC, default_params, group_rectangles,
     cvRunHaarClassifierCascade, group_rectangles_levels, load_library, run_windows_opencv,
     CLOD_WINDOW_RESULT_DTYPE, VJ_WINDOW_OUTSIDE, runCascade, run_windows,
+    AFFINE_DTYPE, AffineParams, affine_from_eyes, affine_from_rect, align_transforms, extract_affine_layout,
 )

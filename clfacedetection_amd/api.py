@@ -162,6 +162,11 @@ class ExtractParams(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class AffineParams(C.Structure):
+    """vj_affine_params"""
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class MixedInfo(C.Structure):
     """vj_mixed_info: what the environment's last detect_mixed / detect_opencv_mixed call did."""
     _fields_ = [("atlases", C.c_int32), ("own_calls", C.c_int32), ("atlas_w", C.c_uint32), ("atlas_h", C.c_uint32),
@@ -213,6 +218,7 @@ CLOD_WINDOW_RESULT_DTYPE = np.dtype([("result", "<i4"), ("variance", "<f4"), ("s
 VJ_WINDOW_OUTSIDE = -2**31   # vj_clod_window_result.result of a window that does not lie inside its frame
 RECT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("weight", "<f4"),
                        ("frame", "<i4"), ("scale_idx", "<i4")])
+AFFINE_DTYPE = np.dtype([("frame", "<i4"), ("reserved", "<i4"), ("m", "<f8", (6,))])                      # vj_affine
 STAGE_DTYPE = np.dtype([("first_tree", "<i4"), ("n_trees", "<i4"), ("threshold", "<f4"), ("parent", "<i4"),
                         ("next", "<i4"), ("child", "<i4")])
 TREE_DTYPE = np.dtype([("first_node", "<i4"), ("n_nodes", "<i4"), ("first_alpha", "<i4")])
@@ -308,6 +314,14 @@ _SIGNATURES = {
                                     C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "vj_extract": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(ExtractParams), C.c_void_p, C.c_uint64]),
     "vj_extract_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "vj_affine_default": (None, [C.POINTER(AffineParams)]),
+    "vj_extract_affine_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(AffineParams), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_uint64)]),
+    "vj_extract_affine": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(AffineParams), C.c_void_p, C.c_uint64]),
+    "vj_extract_affine_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "vj_affine_from_rect": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "vj_affine_from_eyes": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                      C.POINTER(C.c_double)]),
     "vj_result_free": (None, [C.POINTER(_Result)]),
     "vj_group_rectangles": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_double]),
     "vj_group_rectangles_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double]),
@@ -1025,6 +1039,70 @@ class Environment:
         _check(load_library().vj_extract_timing(self._h, C.byref(ms)), "vj_extract_timing")
         return float(ms.value)
 
+    @staticmethod
+    def _affine_args(frames, affines, size, gray, planar, color):
+        """-> (ctypes array of vj_image, n, arrays to keep alive, AFFINE_DTYPE array, vj_affine_params).  frames: as preprocess().
+        affines: an AFFINE_DTYPE array or (n, 7) float64 rows of (frame, m0 .. m5)."""
+        if color or isinstance(frames, (np.ndarray, DeviceFrames)):
+            imgs, n, keep = Environment._images(frames, color)
+        else:
+            imgs, n, keep = Environment._mixed_images(frames)
+        if isinstance(affines, np.ndarray) and affines.dtype.names is not None:
+            a = np.ascontiguousarray(affines, AFFINE_DTYPE).reshape(-1)
+        else:
+            rows = np.asarray(affines, np.float64).reshape(-1, 7)
+            if rows.size and not (np.isfinite(rows[:, 0]).all() and (rows[:, 0] == np.floor(rows[:, 0])).all() and (np.abs(rows[:, 0]) < 2**31).all()):
+                raise ValueError("the first column of affines is the frame index: an integer")
+            a = np.zeros(len(rows), AFFINE_DTYPE)
+            a["frame"] = rows[:, 0].astype(np.int32)
+            a["m"] = rows[:, 1:]
+        p = AffineParams()
+        load_library().vj_affine_default(C.byref(p))
+        p.out_w, p.out_h = int(size[0]), int(size[1])
+        p.flags = (VJ_EXTRACT_GRAY if gray else 0) | (VJ_EXTRACT_PLANAR if planar else 0)
+        return imgs, n, keep, a, p
+
+    @staticmethod
+    def extract_affine_layout(frames, affines, size, gray: bool = False, planar: bool = False, color: bool = False):
+        """vj_extract_affine_layout (host only): what extract_affine() will write -> (channels of the output, bytes of the output)."""
+        imgs, n, keep, a, p = Environment._affine_args(frames, affines, size, gray, planar, color)
+        ch, nbytes = C.c_int(0), C.c_uint64(0)
+        _check(load_library().vj_extract_affine_layout(imgs, n, a.ctypes.data, len(a), C.byref(p), C.byref(ch), C.byref(nbytes)),
+               "vj_extract_affine_layout")
+        return int(ch.value), int(nbytes.value)
+
+    def extract_affine(self, frames, affines, size, gray: bool = False, planar: bool = False, color: bool = False, out=None):
+        """vj_extract_affine: one affine warp per region, all to one fixed size, on the device — aligned crops for a
+        recognition network (align_transforms), or whole frames rotated (one affine per frame, size = the frame's).  Row
+        (frame, m0 .. m5) maps OUTPUT pixel (x, y) to the source pixel (m0 x + m1 y + m2, m3 x + m4 y + m5) of that frame, pixel
+        coordinates used directly (no half-pixel offset: a scaling matrix is not extract()'s resize; affine_from_rect adds the offset
+        that aligns pixel centres); the four neighbours are blended with 1/32-pixel weights, the frame's border replicated (never
+        clipped).  gray=True: one channel, the taps through BGR2GRAY first.  frames: as extract().  affines: (n, 7) float64 rows or
+        an AFFINE_DTYPE array.  Returns a torch.uint8 device tensor of shape (n, h, w, C), or (n, C, h, w) with planar=True.  out: a
+        contiguous torch.uint8 tensor on this device with that many elements; None: one is allocated."""
+        import torch
+        imgs, n, keep, a, p = self._affine_args(frames, affines, size, gray, planar, color)
+        lib = load_library()
+        ch, nbytes = C.c_int(0), C.c_uint64(0)
+        _check(lib.vj_extract_affine_layout(imgs, n, a.ctypes.data, len(a), C.byref(p), C.byref(ch), C.byref(nbytes)), "vj_extract_affine_layout")
+        shape = (len(a), ch.value, p.out_h, p.out_w) if planar else (len(a), p.out_h, p.out_w, ch.value)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", self._device))
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
+            raise ValueError("out must be a contiguous torch.uint8 tensor in device memory")
+        if out.numel() != int(nbytes.value):
+            raise ValueError(f"out must hold {int(nbytes.value)} bytes, the shape {shape}; it holds {out.numel()}")
+        _order_after_torch(self._device)       # after the allocation, as in preprocess()
+        _check(lib.vj_extract_affine(self._h, imgs, n, a.ctypes.data, len(a), C.byref(p), C.c_void_p(out.data_ptr()), out.numel()),
+               "vj_extract_affine")
+        return out.view(shape)
+
+    def extract_affine_timing(self) -> float:
+        """vj_extract_affine_timing: device time of the last extract_affine() call (events around its copies and launches), ms."""
+        ms = C.c_float(0)
+        _check(load_library().vj_extract_affine_timing(self._h, C.byref(ms)), "vj_extract_affine_timing")
+        return float(ms.value)
+
     def mixed_info(self) -> MixedInfo:
         """vj_mixed_info_get: atlases (count and the largest one's size), batched calls on original frames, frames by route, grid
         positions of the atlas passes and the pack launches' device time of the last detect_mixed / detect_opencv_mixed call."""
@@ -1158,6 +1236,64 @@ def extract_layout(frames, rects, size, scale=(1.0, 1.0), margin: float = 0.0, g
     """vj_extract_layout: the host-only twin of Environment.extract (no environment, no device) ->
     (mapped source regions as (n, 5) int32 rows, channels, bytes)."""
     return Environment.extract_layout(frames, rects, size, scale, margin, gray, planar, color)
+
+
+def extract_affine_layout(frames, affines, size, gray: bool = False, planar: bool = False, color: bool = False):
+    """vj_extract_affine_layout: the host-only twin of Environment.extract_affine (no environment, no device) -> (channels, bytes)."""
+    return Environment.extract_affine_layout(frames, affines, size, gray, planar, color)
+
+
+def affine_from_rect(x: float, y: float, w: float, h: float, size) -> np.ndarray:
+    """vj_affine_from_rect (host only): the matrix (6 float64) that scales the box (x, y, w, h) to size = (out_w, out_h) with pixel
+    centres aligned: {w / out_w, 0, x + 0.5 w / out_w - 0.5, 0, h / out_h, y + 0.5 h / out_h - 0.5}."""
+    m = (C.c_double * 6)()
+    _check(load_library().vj_affine_from_rect(float(x), float(y), float(w), float(h), int(size[0]), int(size[1]), m), "vj_affine_from_rect")
+    return np.array(m[:], np.float64)
+
+
+def affine_from_eyes(lx: float, ly: float, rx: float, ry: float, size, eye_pos=(0.3, 0.7, 0.35)) -> np.ndarray:
+    """vj_affine_from_eyes (host only): the similarity (6 float64) that puts the left eye (lx, ly) at output pixel
+    (ex_l out_w, ey out_h) and the right eye (rx, ry) at (ex_r out_w, ey out_h); eye_pos = (ex_l, ex_r, ey)."""
+    m = (C.c_double * 6)()
+    _check(load_library().vj_affine_from_eyes(float(lx), float(ly), float(rx), float(ry), int(size[0]), int(size[1]), float(eye_pos[0]),
+                                              float(eye_pos[1]), float(eye_pos[2]), m), "vj_affine_from_eyes")
+    return np.array(m[:], np.float64)
+
+
+def align_transforms(faces, eyes, size, eye_pos=(0.3, 0.7, 0.35), scale=(1.0, 1.0)):
+    """The matrices that cut every face of a two-cascade call aligned by its eyes -> (affines, paired): an AFFINE_DTYPE array with
+    one row per face, for Environment.extract_affine, and a bool array.  faces, eyes: the two results of detect_opencv_chain or
+    detect_chain (or their RECT_DTYPE arrays): eyes' `frame` indexes faces' rectangles and its x, y are relative to that region.
+    scale = (sx, sy) takes detector coordinates to the pixels of the frames the crops are cut from.
+
+    The pairing rule, for face k = (x, y, w, h): the candidates are the second-cascade rectangles with frame == k whose centre
+    (e.x + e.w / 2, e.y + e.h / 2) has its y below h / 2 (the upper half of the face).  The left eye is the candidate with centre x
+    below w / 2 and the greatest weight, the right eye likewise among those with centre x at or above w / 2; ties go to the lowest
+    index.  An eye's centre in the frame is (x + e.x + e.w / 2) * sx, (y + e.y + e.h / 2) * sy in f64, not rounded.  A face with both
+    eyes gets affine_from_eyes(left, right, size, eye_pos) and paired[k] = True; any other face gets affine_from_rect of its box times
+    scale and paired[k] = False — so every face has a crop."""
+    fr = np.asarray(getattr(faces, "rects", faces))
+    er = np.asarray(getattr(eyes, "rects", eyes))
+    sx, sy = float(scale[0]), float(scale[1])
+    out = np.zeros(len(fr), AFFINE_DTYPE)
+    paired = np.zeros(len(fr), bool)
+    for k, f in enumerate(fr):
+        x, y, w, h = (float(f[n]) for n in ("x", "y", "w", "h"))
+        best = [None, None]                                            # (weight, centre x, centre y) of the left and the right eye
+        for e in er[er["frame"] == k] if len(er) else ():
+            cx, cy = float(e["x"]) + float(e["w"]) / 2, float(e["y"]) + float(e["h"]) / 2
+            if not cy < h / 2:
+                continue
+            side = 0 if cx < w / 2 else 1
+            if best[side] is None or float(e["weight"]) > best[side][0]:
+                best[side] = (float(e["weight"]), cx, cy)
+        out["frame"][k] = int(f["frame"])
+        if best[0] is not None and best[1] is not None:
+            out["m"][k] = affine_from_eyes((x + best[0][1]) * sx, (y + best[0][2]) * sy, (x + best[1][1]) * sx, (y + best[1][2]) * sy, size, eye_pos)
+            paired[k] = True
+        else:
+            out["m"][k] = affine_from_rect(x * sx, y * sy, w * sx, h * sy, size)
+    return out, paired
 
 
 def _pixel_contiguous(img: np.ndarray) -> np.ndarray:

@@ -297,6 +297,9 @@ struct vj_env : vj::Tunables {
     vj::DevBuf d_extract;
     hipEvent_t extract_ev[2] = {};
     float extract_ms = 0;
+    // vj_extract_affine (vj_extract_affine.cpp) brings its slices in d_extract too; its own events and time
+    hipEvent_t affine_ev[2] = {};
+    float affine_ms = 0;
     uint64_t plan_tick = 0;
     int cv_tq_shift = 4;              // ... stage trees: the survivors' queue holds 1 / 2^shift of the tile windows (grows on overflow)
 };

@@ -826,6 +826,56 @@ int  vj_extract(vj_env* e, const vj_image* frames, int n_frames, const vj_roi* r
 /* Device time of the environment's last vj_extract call: events around its copies and launches, in ms.  A null argument: VJ_ERR_ARG. */
 int  vj_extract_timing(const vj_env* e, float* ms);
 
+/* ------------------------------------------------- aligned crops: one affine warp per region, on the device */
+/* What a recognition or landmark network is fed: regions rotated and scaled so the eyes sit at fixed places — or, with one affine
+ * per frame and the frame's size as the output, whole frames rotated — as ONE batched call, device in, device out.
+ * The arithmetic is laid out after the 8-bit INTER_LINEAR path of cv::warpAffine(..., WARP_INVERSE_MAP, BORDER_REPLICATE); parity
+ * is unpinned at the OpenCV boundary, the definition here and in DESIGN.md 4.19 is authoritative.  For affine k = (frame, m[6]) the
+ * matrix maps OUTPUT pixel (x, y) to a source pixel, in f64, pixel coordinates used directly (no half-pixel offset: a scaling
+ * matrix is NOT vj_extract's resize — vj_affine_from_rect adds the offset that aligns the pixel centres):
+ *   src_x = m0 x + m1 y + m2,   src_y = m3 x + m4 y + m5
+ * With rne(v) = cvRound(v), round half to even of an f64 to int32, and no contraction anywhere:
+ *   ax[x] = rne((m0 * x) * 1024.0)               bx[x] = rne((m3 * x) * 1024.0)
+ *   X0[y] = rne((m1 * y + m2) * 1024.0) + 16     Y0[y] = rne((m4 * y + m5) * 1024.0) + 16
+ *   X = (X0[y] + ax[x]) >> 5, Y = (Y0[y] + bx[x]) >> 5 (arithmetic shifts of int32);  sx = X >> 5, fx = X & 31, sy = Y >> 5, fy = Y & 31
+ *   w00 = (32 - fx)(32 - fy) 32, w01 = fx (32 - fy) 32, w10 = (32 - fx) fy 32, w11 = fx fy 32        (they sum to 32768)
+ *   p_ij = frame[clamp(sy + i, 0, H - 1)][clamp(sx + j, 0, W - 1)] per channel: the border is replicated, nothing is clipped, a
+ *   region wholly outside its frame is defined;   out = (p00 w00 + p01 w01 + p10 w10 + p11 w11 + 16384) >> 15
+ * Channels and layout are vj_extract's: all named frames share a channel count C; VJ_EXTRACT_GRAY takes the four taps through the
+ * ingest BGR2GRAY first, then blends them, C = 1; the output is dense n x out_h x out_w x C, VJ_EXTRACT_PLANAR n x C x out_h x out_w. */
+typedef struct vj_affine { int32_t frame; int32_t reserved; double m[6]; } vj_affine;   /* reserved must be 0 */
+typedef struct vj_affine_params {
+    int32_t  out_w, out_h;   /* both > 0: the size of every output                                                              */
+    uint32_t flags;          /* VJ_EXTRACT_GRAY, VJ_EXTRACT_PLANAR                                                              */
+    uint32_t reserved;       /* must be 0                                                                                       */
+} vj_affine_params;
+void vj_affine_default(vj_affine_params* p);            /* all 0: the caller must set the sizes */
+/* Host only, no environment: *channels is C and *bytes the size of the output.  Errors as vj_extract_affine's.                  */
+int  vj_extract_affine_layout(const vj_image* frames, int n_frames, const vj_affine* affines, int n, const vj_affine_params* p,
+                              int* channels, uint64_t* bytes);
+/* frames and d_dst: as vj_extract.  Returns after the work is complete.  All checks come before the device is used.  VJ_ERR_ARG,
+ * with vj_last_error naming the row and the field: null arguments; a frame that breaks vj_detect_mixed's rules; an affine's frame
+ * index out of range, reserved != 0 or a non-finite matrix entry; out_w or out_h <= 0; unknown flag bits, reserved != 0; frames of
+ * differing channel counts without VJ_EXTRACT_GRAY; dst_bytes below the layout's bytes; a device-resident source that overlaps
+ * [d_dst, d_dst + bytes).  VJ_ERR_LIMIT: an output side above 65535; more work units than a 32-bit index holds; any of
+ * |m0| (out_w - 1), |m3| (out_w - 1), |m1 y + m2|, |m4 y + m5| at y in {0, out_h - 1} above 2^19 (under that bound no rne saturates
+ * and X0 + ax stays inside int32).  n == 0 is VJ_OK.  With "max_subbatch" configured a call runs in slices like vj_extract's.     */
+int  vj_extract_affine(vj_env* e, const vj_image* frames, int n_frames, const vj_affine* affines, int n, const vj_affine_params* p,
+                       uint8_t* d_dst, uint64_t dst_bytes);
+/* Device time of the environment's last vj_extract_affine call: events around its copies and launches, in ms.  A null argument: VJ_ERR_ARG. */
+int  vj_extract_affine_timing(const vj_env* e, float* ms);
+/* Host only.  The box (x, y, w, h) scaled to the output with pixel centres aligned:
+ *   m = {w / out_w, 0, x + 0.5 * w / out_w - 0.5, 0, h / out_h, y + 0.5 * h / out_h - 0.5}
+ * VJ_ERR_ARG: null m, non-finite input, w <= 0, h <= 0, out_w <= 0 or out_h <= 0.                                                */
+int  vj_affine_from_rect(double x, double y, double w, double h, int out_w, int out_h, double m[6]);
+/* Host only.  The similarity that puts the left eye (lx, ly) at output pixel (ex_l * out_w, ey * out_h) and the right eye (rx, ry)
+ * at (ex_r * out_w, ey * out_h).  With d = (ex_r - ex_l) * out_w, a = (rx - lx) / d, b = (ry - ly) / d, cxl = ex_l * out_w,
+ * cy = ey * out_h, in exactly this order of f64 operations:
+ *   m = {a, -b, lx - a * cxl + b * cy, b, a, ly - b * cxl - a * cy}
+ * VJ_ERR_ARG: null m, non-finite input, out_w <= 0 or out_h <= 0, ex_r <= ex_l, or coincident eyes.                              */
+int  vj_affine_from_eyes(double lx, double ly, double rx, double ry, int out_w, int out_h, double ex_l, double ex_r, double ey,
+                         double m[6]);
+
 /* ------------------------------------------------------------ frame streams */
 /* Video-style use (the demo's per-frame loop, main.cpp:104-125): batches of host frames are uploaded into
  * one of two device buffers by DMA on a copy stream while the kernels of the previous batch run, and the
