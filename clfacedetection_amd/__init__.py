@@ -15,4 +15,5 @@ from .api import (  # noqa: F401
     cvRunHaarClassifierCascade, group_rectangles_levels, load_library, run_windows_opencv,
     CLOD_WINDOW_RESULT_DTYPE, VJ_WINDOW_OUTSIDE, runCascade, run_windows,
     AFFINE_DTYPE, AffineParams, affine_from_eyes, affine_from_rect, align_transforms, extract_affine_layout,
+    PaintParams, VJ_PAINT_FILL, VJ_PAINT_OUTLINE, VJ_PAINT_PIXELATE, VJ_PAINT_BLUR, VJ_PAINT_ELLIPSE, paint_layout,
 )

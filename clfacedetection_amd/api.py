@@ -42,6 +42,9 @@ VJ_FLAG_CV_ROUGH_SEARCH = 1 << 9     # OpenCV profile: CV_HAAR_DO_ROUGH_SEARCH (
 VJ_FLAG_CV_CHAIN_DEVICE = 1 << 10    # detect_opencv_chain only (flags of the first cascade): regions and units are built on the device, one wait per sub-batch
 VJ_PREP_EQUALIZE = 1 << 0            # vj_prep.flags: cv::equalizeHist of the resized image (Environment.preprocess(equalize=True))
 VJ_EXTRACT_GRAY = 1 << 0             # vj_extract_params.flags: C = 1, colour sources through BGR2GRAY (Environment.extract(gray=True))
+VJ_PAINT_FILL, VJ_PAINT_OUTLINE, VJ_PAINT_PIXELATE, VJ_PAINT_BLUR = 0, 1, 2, 3   # vj_paint_params.mode (Environment.paint(mode=...))
+VJ_PAINT_ELLIPSE = 1 << 0            # vj_paint_params.flags: the ellipse inscribed in the mapped rectangle (Environment.paint(ellipse=True))
+PAINT_MODES = {"fill": VJ_PAINT_FILL, "outline": VJ_PAINT_OUTLINE, "pixelate": VJ_PAINT_PIXELATE, "blur": VJ_PAINT_BLUR}
 VJ_EXTRACT_PLANAR = 1 << 1           # vj_extract_params.flags: n x C x h x w instead of n x h x w x C (Environment.extract(planar=True))
 VJ_FLAG_EQUALIZE_HIST = 1 << 11      # cv::equalizeHist on every frame, on the device, in front of detect / detect_opencv / detect_opencv_roc / the mixed calls; refused elsewhere
 
@@ -160,6 +163,12 @@ class ExtractParams(C.Structure):
     """vj_extract_params"""
     _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("sx", C.c_double), ("sy", C.c_double), ("margin", C.c_double),
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PaintParams(C.Structure):
+    """vj_paint_params"""
+    _fields_ = [("mode", C.c_int32), ("flags", C.c_uint32), ("sx", C.c_double), ("sy", C.c_double), ("margin", C.c_double),
+                ("size", C.c_int32), ("rel", C.c_double), ("color", C.c_uint8 * 4), ("reserved", C.c_uint32)]
 
 
 class AffineParams(C.Structure):
@@ -315,6 +324,11 @@ _SIGNATURES = {
     "vj_extract": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(ExtractParams), C.c_void_p, C.c_uint64]),
     "vj_extract_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vj_affine_default": (None, [C.POINTER(AffineParams)]),
+    "vj_paint_default": (None, [C.POINTER(PaintParams)]),
+    "vj_paint_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(PaintParams), C.c_void_p, C.c_void_p,
+                                  C.POINTER(C.c_uint64)]),
+    "vj_paint": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(PaintParams)]),
+    "vj_paint_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vj_extract_affine_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(AffineParams), C.POINTER(C.c_int),
                                            C.POINTER(C.c_uint64)]),
     "vj_extract_affine": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(AffineParams), C.c_void_p, C.c_uint64]),
@@ -1040,6 +1054,117 @@ class Environment:
         return float(ms.value)
 
     @staticmethod
+    def _paint_images(frames, color):
+        """-> (ctypes array of vj_image, n, objects to keep alive, True if a device frame is among them).  frames: a DeviceFrames, a
+        uint8 CUDA tensor (DeviceFrames.from_torch), a writeable uint8 numpy array — one frame or a batch, as detect() reads its
+        shape, color=True for BGR / BGRA — or a list of these, each array then one frame (2-D gray, 3-D BGR / BGRA).  The frames are
+        painted IN PLACE: an array the call would have to copy (read-only, another dtype, pixels not contiguous) is a ValueError."""
+        def is_tensor(f):
+            return not isinstance(f, (np.ndarray, DeviceFrames)) and hasattr(f, "data_ptr") and hasattr(f, "is_cuda")
+
+        def one(f, ndim):
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8:
+                raise ValueError("paint() writes into its frames: a host frame must be a uint8 numpy array (no copy is made)")
+            if f.ndim != ndim or (ndim == 3 and f.shape[2] not in (3, 4)):
+                raise ValueError("a host frame must be a 2-D uint8 array or a (h, w, 3|4) uint8 array (BGR / BGRA)")
+            if not f.flags.writeable:
+                raise ValueError("paint() writes into its frames: a read-only array cannot be painted (no copy is made)")
+            if f.shape[0] == 0 or f.shape[1] == 0:
+                raise ValueError("a frame must not be empty")
+            if (ndim == 3 and (f.strides[2] != 1 or f.strides[1] != f.shape[2])) or (ndim == 2 and f.strides[1] != 1) or f.strides[0] <= 0:
+                raise ValueError("paint() writes into its frames: the pixels of a row must be contiguous (no copy is made)")
+            return _Image(f.ctypes.data, f.shape[1], f.shape[0], f.strides[0], 0, f.shape[2] if ndim == 3 else 1)
+
+        items = frames if isinstance(frames, (list, tuple)) else [frames]
+        batch_ok = not isinstance(frames, (list, tuple))
+        imgs, keep, dev = [], [], False
+        for f in items:
+            if is_tensor(f):
+                if not f.is_cuda or f.dtype.itemsize != 1:
+                    raise ValueError("a tensor frame must be a uint8 CUDA tensor")
+                keep.append(f)
+                f = DeviceFrames.from_torch(f)
+            if isinstance(f, DeviceFrames):
+                dev = True
+                keep.append(f)
+                imgs += [_Image(f.frame_ptr(i), f.width, f.height, f.stride, 1, f.channels) for i in range(f.n)]
+                continue
+            if not isinstance(f, np.ndarray):
+                raise ValueError("frames must be DeviceFrames, uint8 CUDA tensors, writeable uint8 numpy arrays or a list of these")
+            keep.append(f)
+            nd = 3 if (color or (not batch_ok and f.ndim == 3)) else 2
+            if batch_ok and f.ndim == nd + 1:
+                imgs += [one(f[i], nd) for i in range(f.shape[0])]
+            else:
+                imgs.append(one(f, nd))
+        arr = (_Image * max(len(imgs), 1))(*imgs)
+        return arr, len(imgs), keep, dev
+
+    @staticmethod
+    def _paint_args(frames, rects, mode, size, rel, scale, margin, ellipse, fill, color):
+        imgs, n, keep, dev = Environment._paint_images(frames, color)
+        if isinstance(rects, np.ndarray) and rects.dtype.names is not None:
+            r = np.stack([np.asarray(rects[k], np.int32).reshape(-1) for k in ("frame", "x", "y", "w", "h")], axis=1)
+        else:
+            r = np.asarray(rects)
+            if r.size and not np.issubdtype(r.dtype, np.integer):
+                raise ValueError("rects must be a RECT_DTYPE array or integer rows of (frame, x, y, w, h)")
+            r = r.astype(np.int32).reshape(-1, 5)
+        r = np.ascontiguousarray(r, np.int32)
+        p = PaintParams()
+        load_library().vj_paint_default(C.byref(p))
+        if isinstance(mode, str):
+            if mode not in PAINT_MODES:
+                raise ValueError(f"mode must be one of {sorted(PAINT_MODES)} or a VJ_PAINT_* value")
+            mode = PAINT_MODES[mode]
+        p.mode = int(mode)
+        p.flags = VJ_PAINT_ELLIPSE if ellipse else 0
+        p.sx, p.sy = float(scale[0]), float(scale[1])
+        p.margin = float(margin)
+        p.size = int(size)
+        p.rel = float(rel)
+        fill = tuple(int(v) for v in (fill if np.ndim(fill) else (fill,) * 4))
+        if len(fill) > 4 or any(not 0 <= v <= 255 for v in fill):
+            raise ValueError("fill: up to four values of 0 .. 255, one per channel")
+        for c, v in enumerate(fill + (0,) * (4 - len(fill))):
+            p.color[c] = v
+        return imgs, n, keep, dev, r, p
+
+    @staticmethod
+    def paint_layout(frames, rects, mode="blur", size: int = 0, rel: float = 0.25, scale=(1.0, 1.0), margin: float = 0.0,
+                     ellipse: bool = False, color: bool = False):
+        """vj_paint_layout (host only): what paint() will touch -> ((n, 5) int32 rows of the clipped rectangles (frame, x, y, w, h),
+        w = h = 0 where nothing is painted; (n,) int32 sizes — the thickness, the cell side or the blur's kernel side, 0 for "fill";
+        the scratch bytes of the call run as one slice)."""
+        imgs, n, keep, dev, r, p = Environment._paint_args(frames, rects, mode, size, rel, scale, margin, ellipse, 0, color)
+        clipped = np.zeros((len(r), 5), np.int32)
+        sizes = np.zeros(len(r), np.int32)
+        nbytes = C.c_uint64(0)
+        _check(load_library().vj_paint_layout(imgs, n, r.ctypes.data, len(r), C.byref(p), clipped.ctypes.data, sizes.ctypes.data,
+                                              C.byref(nbytes)), "vj_paint_layout")
+        return clipped, sizes, int(nbytes.value)
+
+    def paint(self, frames, rects, mode="blur", size: int = 0, rel: float = 0.25, scale=(1.0, 1.0), margin: float = 0.0,
+              ellipse: bool = False, fill=(0, 0, 0, 0), color: bool = False):
+        """vj_paint: the pixels inside, or around, rectangles changed IN PLACE, on the device.  mode: "blur" (a box
+        blur of the region, its border replicated), "pixelate" (cells replaced by their mean), "fill" (the colour `fill`, one value
+        per channel) or "outline" (a frame of that colour along the rectangle, cvRectangle's use).  size: the blur's kernel side, the
+        cell side or the line's thickness in pixels; 0: rel times the mapped region's shorter side.  scale, margin, rects: as
+        extract().  ellipse=True: the ellipse inscribed in the rectangle instead of the rectangle.  Where regions overlap the
+        later one wins, every value computed from the frames as they were before the call.  frames: see _paint_images — device
+        frames are painted where they lie, host arrays through a staged copy of the touched rows.  Returns `frames`."""
+        imgs, n, keep, dev, r, p = self._paint_args(frames, rects, mode, size, rel, scale, margin, ellipse, fill, color)
+        _order_after_torch(self._device)       # work queued on the frames (a decoder, a copy_) has written them before they are painted
+        _check(load_library().vj_paint(self._h, imgs, n, r.ctypes.data, len(r), C.byref(p)), "vj_paint")
+        return frames
+
+    def paint_timing(self) -> float:
+        """vj_paint_timing: device time of the last paint() call (events around its copies and launches), ms."""
+        ms = C.c_float(0)
+        _check(load_library().vj_paint_timing(self._h, C.byref(ms)), "vj_paint_timing")
+        return float(ms.value)
+
+    @staticmethod
     def _affine_args(frames, affines, size, gray, planar, color):
         """-> (ctypes array of vj_image, n, arrays to keep alive, AFFINE_DTYPE array, vj_affine_params).  frames: as preprocess().
         affines: an AFFINE_DTYPE array or (n, 7) float64 rows of (frame, m0 .. m5)."""
@@ -1236,6 +1361,13 @@ def extract_layout(frames, rects, size, scale=(1.0, 1.0), margin: float = 0.0, g
     """vj_extract_layout: the host-only twin of Environment.extract (no environment, no device) ->
     (mapped source regions as (n, 5) int32 rows, channels, bytes)."""
     return Environment.extract_layout(frames, rects, size, scale, margin, gray, planar, color)
+
+
+def paint_layout(frames, rects, mode="blur", size: int = 0, rel: float = 0.25, scale=(1.0, 1.0), margin: float = 0.0,
+                 ellipse: bool = False, color: bool = False):
+    """vj_paint_layout: the host-only twin of Environment.paint (no environment, no device) ->
+    (clipped rectangles as (n, 5) int32 rows, sizes as (n,) int32, scratch bytes)."""
+    return Environment.paint_layout(frames, rects, mode, size, rel, scale, margin, ellipse, color)
 
 
 def extract_affine_layout(frames, affines, size, gray: bool = False, planar: bool = False, color: bool = False):

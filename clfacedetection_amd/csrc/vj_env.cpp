@@ -1504,6 +1504,7 @@ int vj_env_create(int device_index, vj_env** out) {
     for (hipEvent_t& ev : e->prep_ev) HIP_TRY(hipEventCreate(&ev));
     for (hipEvent_t& ev : e->extract_ev) HIP_TRY(hipEventCreate(&ev));
     for (hipEvent_t& ev : e->affine_ev) HIP_TRY(hipEventCreate(&ev));
+    for (hipEvent_t& ev : e->paint_ev) HIP_TRY(hipEventCreate(&ev));
     HIP_TRY(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
     *out = e.release();
     return VJ_OK;
@@ -1537,6 +1538,8 @@ void vj_env_destroy(vj_env* e) {
     for (hipEvent_t& ev : e->extract_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t& ev : e->affine_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t& ev : e->paint_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (e->fork_ev) (void)hipEventDestroy(e->fork_ev);
     if (e->join_ev) (void)hipEventDestroy(e->join_ev);

@@ -300,6 +300,9 @@ struct vj_env : vj::Tunables {
     // vj_extract_affine (vj_extract_affine.cpp) brings its slices in d_extract too; its own events and time
     hipEvent_t affine_ev[2] = {};
     float affine_ms = 0;
+    // vj_paint (vj_paint.cpp) brings its slices in d_extract too, with its scratch behind them; its own events and time
+    hipEvent_t paint_ev[2] = {};
+    float paint_ms = 0;
     uint64_t plan_tick = 0;
     int cv_tq_shift = 4;              // ... stage trees: the survivors' queue holds 1 / 2^shift of the tile windows (grows on overflow)
 };

@@ -42,6 +42,10 @@ int map_axis(int r, const char* axis, int o, int len, double f, double margin, i
 }
 }  // namespace
 
+int extract_map_axis(int r, const char* axis, int o, int len, double f, double margin, int32_t* c0, int32_t* clen) {
+    return map_axis(r, axis, o, len, f, margin, c0, clen);
+}
+
 int extract_layout(const vj_image* frames, int n_frames, const vj_roi* regions, int n_regions, const vj_extract_params* p, ExtractLayout* out) {
     *out = ExtractLayout{};
     if (!p || n_regions < 0 || (n_regions > 0 && !regions)) {

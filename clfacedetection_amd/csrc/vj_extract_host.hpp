@@ -22,6 +22,10 @@ struct ExtractLayout {
 // naming the row or the field.
 int extract_layout(const vj_image* frames, int n_frames, const vj_roi* regions, int n_regions, const vj_extract_params* p, ExtractLayout* out);
 
+// One axis of step 1 of the mapping (origin o and length len times factor f, cvRound, then the margin) with its limits; `r` and
+// `axis` go into the message.  vj_paint maps its regions with it too.
+int extract_map_axis(int r, const char* axis, int o, int len, double f, double margin, int32_t* c0, int32_t* clen);
+
 // The end of the slice that begins at region `first`: regions are taken in order while they name at most `max_frames` distinct
 // frames (0: no bound); at least one region.
 size_t extract_slice_end(const vj_roi* regions, size_t n_regions, size_t first, size_t max_frames);

@@ -369,7 +369,8 @@ int  vj_resize_linear(vj_env* e, const struct vj_image* image, int dst_w, int ds
  * Host or device input, 1 / 3 / 4 channels, any row stride.  Null arguments or dst_stride < width: VJ_ERR_ARG.                   */
 int  vj_equalize_hist(vj_env* e, const struct vj_image* image, uint8_t* dst, int dst_stride);
 typedef struct vj_image {
-    const uint8_t* data;       /* 8-bit, interleaved channels                   */
+    const uint8_t* data;       /* 8-bit, interleaved channels.  Read only by every entry point but vj_paint, which WRITES the
+                                  painted pixels through this pointer (the memory must be writable)            */
     int32_t width, height;
     int32_t stride;            /* bytes per row                                 */
     int32_t on_device;         /* 0: host pointer; 1: device pointer on env's GPU.  The library's streams are created with
@@ -875,6 +876,63 @@ int  vj_affine_from_rect(double x, double y, double w, double h, int out_w, int 
  * VJ_ERR_ARG: null m, non-finite input, out_w <= 0 or out_h <= 0, ex_r <= ex_l, or coincident eyes.                              */
 int  vj_affine_from_eyes(double lx, double ly, double rx, double ry, int out_w, int out_h, double ex_l, double ex_r, double ey,
                          double m[6]);
+
+/* ------------------------------------------------- rectangles painted into the frames, on the device */
+/* The other consumers of a detector's rectangles write into the frames themselves: redaction (every face blurred or pixelated
+ * before a video is stored or shown) and the reference sample's own last step, cvRectangle around every result (main.cpp:155,
+ * :181) — as ONE batched call that changes the pixels inside, or around, the rectangles IN PLACE.  This is the
+ * only entry point that writes through vj_image.data.  All arithmetic is on integers; parity is unpinned at the OpenCV boundary,
+ * the definition here and in DESIGN.md 4.20 is authoritative.  For region k = (frame, x, y, w, h):
+ *   1. M = (X0, Y0, Wm, Hm): step 1 of vj_extract (cvRound of the coordinates times sx, sy, then the margin), the same limits.
+ *      K = M ∩ frame = [cx0, cx1) x [cy0, cy1).  A region whose K is empty paints nothing and is no error.
+ *   2. s = size when size > 0, else max(cvRound(min(Wm, Hm) * rel), 1).  OUTLINE: the thickness t = s.  PIXELATE: the cell side s.
+ *      BLUR: the kernel side kk = max(s | 1, 3), r = kk >> 1.  FILL ignores it.
+ *   3. The shape: M; with VJ_PAINT_ELLIPSE the ellipse inscribed in M: pixel (px, py) of M is in it iff
+ *      (2 (px - X0) + 1 - Wm)^2 Hm^2 + (2 (py - Y0) + 1 - Hm)^2 Wm^2 <= Wm^2 Hm^2, in 64-bit integers.
+ *   4. The painted set P_k.  FILL, PIXELATE, BLUR: shape ∩ K.  OUTLINE: the shape of M minus the shape of M shrunk by t on each
+ *      of its four sides, ∩ K; a shrunk rectangle with a side <= 0: the whole shape.  The outline follows M, not K: a box that
+ *      leaves the frame draws no line along the frame's edge.
+ *   5. The value, per channel c (alpha like any other); F is the frame AS IT WAS BEFORE THE CALL.  FILL, OUTLINE: color[c].
+ *      PIXELATE: cells anchored at (cx0, cy0), cell (i, j) = [cx0 + i s, min(cx0 + (i + 1) s, cx1)) x [cy0 + j s, min(cy0 + (j + 1) s, cy1));
+ *      every pixel of a cell takes (sum of F over the cell + n / 2) / n, n the cell's pixel count, the divisions flooring.
+ *      BLUR: (sum over dy, dx in -r .. r of F[clamp(py + dy, cy0, cy1 - 1)][clamp(px + dx, cx0, cx1 - 1)][c] + kk^2 / 2) / kk^2,
+ *      flooring: the border is replicated at the edge of K, as cv::blur on the ROI does, so a region reads only its own pixels.
+ *   6. A pixel in several painted sets of one frame takes the value of the HIGHEST-INDEX region among them — as if the regions
+ *      were painted in order, but every value comes from the original frame, never from another region's output.  Bytes in no
+ *      painted set are never written; there is no gray conversion.                                                              */
+enum { VJ_PAINT_FILL = 0, VJ_PAINT_OUTLINE = 1, VJ_PAINT_PIXELATE = 2, VJ_PAINT_BLUR = 3 };   /* vj_paint_params.mode  */
+enum { VJ_PAINT_ELLIPSE = 1u << 0 };                                                           /* vj_paint_params.flags */
+typedef struct vj_paint_params {
+    int32_t  mode;
+    uint32_t flags;
+    double   sx, sy, margin;   /* the mapping of vj_extract_params: 0 means 1 for sx, sy                                        */
+    int32_t  size;             /* pixels; 0: take it from rel                                                                    */
+    double   rel;              /* fraction of the mapped region's shorter side                                                   */
+    uint8_t  color[4];         /* FILL, OUTLINE: channel c of a frame takes color[c]; gray frames: color[0]                      */
+    uint32_t reserved;         /* must be 0                                                                                      */
+} vj_paint_params;
+void vj_paint_default(vj_paint_params* p);   /* mode BLUR, sx = sy = 1, margin 0, size 0, rel 0.25, color 0 */
+/* Host only, no environment: clipped[k] is K of region k (w = h = 0 when it is empty), sizes[k] its t, s or kk (0 for FILL) and
+ * *scratch_bytes what the phase between reading and writing the frames keeps of the call run as one slice (its largest): per
+ * region with a K, rounded up to 16 bytes — BLUR: 2 bytes per byte of K; PIXELATE: one byte per cell and channel.  Errors as
+ * vj_paint's.                                                                                                                   */
+int  vj_paint_layout(const vj_image* frames, int n_frames, const vj_roi* regions, int n_regions, const vj_paint_params* p,
+                     vj_roi* clipped, int32_t* sizes, uint64_t* scratch_bytes);
+/* frames: vj_detect_mixed's rules — host or device-resident, 1 / 3 / 4 channels, any strides, sizes may differ — and the call
+ * WRITES through vj_image.data: nothing else may read or write the frames until it returns, and all work of the caller's on
+ * device-resident frames must be complete before it (see vj_image.on_device).  Device frames: only the bytes of painted pixels are
+ * stored.  Host frames: the painted pixels change; other bytes of K's span of a touched row may be rewritten with their own
+ * values; a row's padding and rows outside K are never written.  Returns after the work is complete.
+ * All checks come before the device is used.  VJ_ERR_ARG, with vj_last_error naming the row or the field: the null, frame and
+ * region errors of vj_extract; an unknown mode, unknown flag bits, reserved != 0, size < 0; negative or non-finite sx, sy, margin;
+ * size == 0 with a rel that is not finite or <= 0; two frames of the call whose memory overlaps (ownership is decided per frame).
+ * VJ_ERR_LIMIT: vj_extract's mapping limits; a mapped side above 32767 (the ellipse's products stay below 2^60); BLUR with
+ * kk > 255 (a column sum fits 16 bits); PIXELATE with s > 4096 (a cell sum fits 32 bits); more work units than a 32-bit index
+ * holds.  VJ_ERR_NOMEM names the bytes.  n_regions == 0 is VJ_OK.  With "max_subbatch" configured a call runs in slices of whole
+ * frames, at most that many each.                                                                                               */
+int  vj_paint(vj_env* e, const vj_image* frames, int n_frames, const vj_roi* regions, int n_regions, const vj_paint_params* p);
+/* Device time of the environment's last vj_paint call: events around its copies and launches, in ms.  A null argument: VJ_ERR_ARG. */
+int  vj_paint_timing(const vj_env* e, float* ms);
 
 /* ------------------------------------------------------------ frame streams */
 /* Video-style use (the demo's per-frame loop, main.cpp:104-125): batches of host frames are uploaded into
