@@ -1082,7 +1082,7 @@ static int finish_batch(vj_env* e, Lane* L, Plan* pl, int f0, int W, int H, cons
                             100.0 * (double)g[1] / span, (double)g[3] - (double)g[2] / wgs, 100.0 * ((double)g[3] - (double)g[2] / wgs) / span);
                 }
             fprintf(stderr, "vj stamps:");
-            for (int i = 40; i < 60; ++i) {
+            for (int i = 40; i < 63; ++i) {   // (60 .. 62: the dense sweep's groups, its lone chunks, how many lone chunks)
                 unsigned long long v = 0;
                 for (int l = 1; l <= VJ_MAX_LAUNCHES; ++l) v += se[l * VJ_MAX_STAGES + i];
                 fprintf(stderr, " %llu", v);

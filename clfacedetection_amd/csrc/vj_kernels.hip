@@ -1104,8 +1104,13 @@ __device__ __forceinline__ uint32_t sweep_stages(const CascadeArgs& a, const Img
                 base += 128u;
             }
         }
+        const unsigned long long t_grp = VJ_STAMPS && MULTI ? __builtin_amdgcn_s_memtime() : 0ull;
         if (!TREES && MULTI) {
-            // groups of 4, then 2 full-or-partial chunks; a last single chunk falls through to the loop below
+            // groups of 4 while more than 3 chunks are left, then ONE group of 3 or of 2 full-or-partial chunks; a last single
+            // chunk falls through to the loop below.  A tile deals whole chunks and a re-pack whole-chunk shares, so 3 chunks
+            // (129..192 entries) is a common population: as a group of 2 plus a lone chunk it paid the stage's record fetches
+            // twice and walked the lone chunk with one stump's reads in flight.  Exactly 256 / 192 / 128 / 64 entries take
+            // one group of 4 / one of 3 / one of 2 / the lone form.
             auto group = [&](auto nc_tag) {
                 constexpr int NC = decltype(nc_tag)::value;
                 QEntry e[NC];
@@ -1131,8 +1136,19 @@ __device__ __forceinline__ uint32_t sweep_stages(const CascadeArgs& a, const Img
                 base += (uint32_t)NC * 64u;
             };
             while (base + 192u < n) group(std::integral_constant<int, 4>{});
-            if (base + 64u < n) group(std::integral_constant<int, 2>{});
+            if (base + 128u < n) group(std::integral_constant<int, 3>{});
+            else if (base + 64u < n) group(std::integral_constant<int, 2>{});
         }
+        if (VJ_STAMPS && MULTI && threadIdx.x == 0) {   // diagnostic build: thread 0's wave, the groups of this stage
+            const unsigned long long t_ = __builtin_amdgcn_s_memtime();
+            atomicAdd(a.stage_entered + 60, t_ - t_grp);
+            atomicAdd(a.stage_entered + 62, (unsigned long long)(base < n ? 1u : 0u));
+        }
+        const unsigned long long t_lone = VJ_STAMPS && MULTI ? __builtin_amdgcn_s_memtime() : 0ull;
+        // a lone chunk on the staged tile always walks the stage two stumps per step (16-24 LDS reads in flight, one wait per
+        // pair): the flag was tuned for the global-gather sweeps, whose gathers contend for the texture-address unit, and LDS
+        // reads do not.  Compile-time on the image type: the global-gather instantiations keep the flag.
+        constexpr bool lone_pairs_always = std::is_same<Img, LdsImg>::value;
         for (; base < n; base += 64u) {
             const uint32_t i = base + lane;
             const bool act = i < n;
@@ -1147,7 +1163,9 @@ __device__ __forceinline__ uint32_t sweep_stages(const CascadeArgs& a, const Img
                     stage_sum_tree2_multi<1, COUNT>(img, tab, n_nodes >> 1, off1, var1, sum1, cnt1);
                     pass = sum1[0] >= threshold;
                 } else {
-                    pass = stage_sum_of<TREES, COUNT>(img, tab, n_nodes, e.off, e.var, a.gather_pairs == 2u || (a.gather_pairs == 1u && n <= 64u), cnt1[0]) >= threshold;
+                    bool pairs = true;
+                    if constexpr (!lone_pairs_always) pairs = a.gather_pairs == 2u || (a.gather_pairs == 1u && n <= 64u);
+                    pass = stage_sum_of<TREES, COUNT>(img, tab, n_nodes, e.off, e.var, pairs, cnt1[0]) >= threshold;
                 }
             }
             if (TREES && COUNT) tree_count_flush(a, cnt1[0][0], cnt1[0][1], lane);
@@ -1166,6 +1184,7 @@ __device__ __forceinline__ uint32_t sweep_stages(const CascadeArgs& a, const Img
             m += (uint32_t)__popcll(mask);
             __builtin_amdgcn_wave_barrier();
         }
+        if (VJ_STAMPS && MULTI && threadIdx.x == 0) atomicAdd(a.stage_entered + 61, __builtin_amdgcn_s_memtime() - t_lone);   // the lone chunk
         n = m;
     }
     return n;

@@ -33,7 +33,7 @@ struct Tunables {
     // frame is bound by the latency of the gather chain's thin queue pass (measured, 1080p / frontalface_alt: 1 frame
     // 1.20 / 1.46 / 1.46 ms at split 0 / 0.5 / 1.25; 4 frames 3.50 / 3.61 / 3.96; 16 frames 12.51 / 12.25 / 12.36;
     // 64 frames — / 48.0 / 54.0), so small batches keep everything they can on the tiles
-    float tile_split = 2.75f;           // batches of >= 32 frames (round 15, eight gather waves with queues of 256 entries, q_group_units 2: 64 x 1080p 34.18 / 33.93 / 33.66 / 34.42 ms for 2.25 / 2.5 / 2.75 / 3, 32: 17.20 / 17.06 / 16.95 for 2.25 / 2.5 / 2.75, repeats within 0.1 ms; four waves at 1.25: 34.33 and 17.30; profiles/r15_notes.md; round 13, four gather waves, the grid pass hands its units out by ticket and is 2.9 ms shorter: 64 x 1080p 35.96 / 35.53 / 35.05 / 35.74 / 36.91 ms for 0.75 / 1 / 1.25 / 1.5 / 1.75, repeats within 0.04 ms but for 1.5; 32: 18.14 / 17.88 / 17.88 / 18.18 / 18.71 — 1.25 beats 1 by 0.48 ms at 64 and is level with it at 32; round 12, first sweep on the round-11 tile shapes, members of a group without their end barrier: 64 x 1080p 36.68 / 36.23 / 35.97 / 37.72 / 38.07 ms for 0.5 / 0.75 / 1 / 1.25 / 1.5, 32: 18.34 / 18.16 / 18.21 / 18.95 / 19.15 — 1 beats 1.25 by 1.7 ms at 64 and 0.7 ms at 32, repeats within 0.05 ms but for one value at 32; 0.75 is level with 1 at 32 and 0.25 ms behind at 64; round 10, after the tail's transposed records: 64 x 1080p 38.58 / 38.24 / 38.86 / 40.04 ms for 1 / 1.25 / 1.5 / 1.75, 32: 19.33 / 19.38 / 19.46 / 20.23 — 1.25 beats 1.5 at both sizes by more than the 0.03 ms between repeats, 1 wins only at 32; round 8, wave-independent tile tail: 64 x 1080p 38.94 / 40.14 / 41.00 / 42.35 / 43.60 ms for 1.5 / 1.75 / 2 / 2.25 / 2.5, 32: 19.50 / 20.19 / 20.68 / 21.14 / 21.84; round 4, band-major queue pass: 64 x 1080p 43.6 / 43.0 / 42.5 / 43.4 / 44.5 ms for 1.5 / 1.75 / 2 / 2.25 / 2.5; round 3: (four gather waves; 64 x 1080p: 46.70 / 46.24 / 45.57 / 45.16 / 45.55 / 46.72 ms for 0.75 / 1 / 1.25 / 1.5 / 1.75 / 2; 32: 23.39 / 23.16 / 22.80 / 22.62 / 22.78 / 23.38)
+    float tile_split = 2.5f;            // batches of >= 32 frames (round 16, the tile sweep's groups of three chunks and paired lone chunks: 64 x 1080p 33.35 / 33.08 / 33.41 / 34.45 / 35.95 ms for 2.25 / 2.5 / 2.75 / 3 / 3.25, 32: 16.77 / 16.67 / 16.91 / 17.40 / 18.06, repeats within 0.05 ms; round 15's kernels in the same job: 34.25 / 33.97 / 33.72 / 34.52 / 35.96 and 17.24 / 17.12 / 17.00 / 17.42 / 18.09 — 2.5 beats 2.75 by 0.33 ms at 64 and 0.24 ms at 32 on the new kernels and loses 0.25 / 0.12 ms on the old ones; profiles/r16_notes.md; round 15, eight gather waves with queues of 256 entries, q_group_units 2: 64 x 1080p 34.18 / 33.93 / 33.66 / 34.42 ms for 2.25 / 2.5 / 2.75 / 3, 32: 17.20 / 17.06 / 16.95 for 2.25 / 2.5 / 2.75, repeats within 0.1 ms; four waves at 1.25: 34.33 and 17.30; profiles/r15_notes.md; round 13, four gather waves, the grid pass hands its units out by ticket and is 2.9 ms shorter: 64 x 1080p 35.96 / 35.53 / 35.05 / 35.74 / 36.91 ms for 0.75 / 1 / 1.25 / 1.5 / 1.75, repeats within 0.04 ms but for 1.5; 32: 18.14 / 17.88 / 17.88 / 18.18 / 18.71 — 1.25 beats 1 by 0.48 ms at 64 and is level with it at 32; round 12, first sweep on the round-11 tile shapes, members of a group without their end barrier: 64 x 1080p 36.68 / 36.23 / 35.97 / 37.72 / 38.07 ms for 0.5 / 0.75 / 1 / 1.25 / 1.5, 32: 18.34 / 18.16 / 18.21 / 18.95 / 19.15 — 1 beats 1.25 by 1.7 ms at 64 and 0.7 ms at 32, repeats within 0.05 ms but for one value at 32; 0.75 is level with 1 at 32 and 0.25 ms behind at 64; round 10, after the tail's transposed records: 64 x 1080p 38.58 / 38.24 / 38.86 / 40.04 ms for 1 / 1.25 / 1.5 / 1.75, 32: 19.33 / 19.38 / 19.46 / 20.23 — 1.25 beats 1.5 at both sizes by more than the 0.03 ms between repeats, 1 wins only at 32; round 8, wave-independent tile tail: 64 x 1080p 38.94 / 40.14 / 41.00 / 42.35 / 43.60 ms for 1.5 / 1.75 / 2 / 2.25 / 2.5, 32: 19.50 / 20.19 / 20.68 / 21.14 / 21.84; round 4, band-major queue pass: 64 x 1080p 43.6 / 43.0 / 42.5 / 43.4 / 44.5 ms for 1.5 / 1.75 / 2 / 2.25 / 2.5; round 3: (four gather waves; 64 x 1080p: 46.70 / 46.24 / 45.57 / 45.16 / 45.55 / 46.72 ms for 0.75 / 1 / 1.25 / 1.5 / 1.75 / 2; 32: 23.39 / 23.16 / 22.80 / 22.62 / 22.78 / 23.38)
     float tile_split_mid = 2.75f;       // 8 .. 31 frames (round 15, eight gather waves: 16 x 1080p 8.86 / 8.70 / 8.70 / 9.25 ms for 1.75 / 2.25 / 2.75 / 3.25, 8: 4.57 / 4.48 / 4.48 / 4.75; four waves: 9.35 and 4.90 at 1.75, 8.93 and 4.72 at 1.25; round 4, band-major queue pass: 16 x 1080p 11.53 / 11.36 / 11.13 / 11.01 / 10.89 / 10.90 ms for 0.75 ... 2.0; round 3: (16 x 1080p: 11.81 / 11.67 / 11.47 / 11.52 / 11.86 for 0.75 ... 1.75; 8: 6.03 / 5.95 / 5.97 / 6.24); 5 .. 7 frames (three gather waves): at most 0.5
     float tile_split_small = 0.0f;      // <= 4 frames
     int one_pass_max_frames = 0;        // calls of at most this many frames (of 720p and more, stump cascades) run the gather chain in ONE pass; 0: never.

@@ -1,8 +1,9 @@
 """Diagnostic build only (VJ_STAMPS=1 at build time, VJ_DEBUG_STAMPS=1 at run time): per-phase s_memtime sums of
-the tile kernel (thread 0 of each workgroup); the library prints slots 40..59 to stderr after every detect.
+the tile kernel (thread 0 of each workgroup); the library prints slots 40..62 to stderr after every detect.
   40 wait at loop top | 41 staging + sqsum loads + barrier | 42 variance fill | 43+min(st,8) stage st-1 + re-pack
   52 wave-independent tail (thread 0's wave) | 53 spill | 54..58 inside the wave-split finish: sweep, barrier, decision,
-  barrier, compaction | 59 end of a member: waiting for the slowest wave
+  barrier, compaction | 59 end of a member: waiting for the slowest wave | 60 thread 0's wave inside the chunk groups of the
+  dense sweep | 61 ... inside its lone-chunk loop | 62 lone chunks it swept
 Usage on the GPU box:  VJ_STAMPS=1 python -c "from clfacedetection_amd.build import build_lib; build_lib(force=True)"
                        VJ_DEBUG_STAMPS=1 B=64 python tools/stamps.py
 """
