@@ -44,6 +44,9 @@ VJ_PREP_EQUALIZE = 1 << 0            # vj_prep.flags: cv::equalizeHist of the re
 VJ_EXTRACT_GRAY = 1 << 0             # vj_extract_params.flags: C = 1, colour sources through BGR2GRAY (Environment.extract(gray=True))
 VJ_PAINT_FILL, VJ_PAINT_OUTLINE, VJ_PAINT_PIXELATE, VJ_PAINT_BLUR = 0, 1, 2, 3   # vj_paint_params.mode (Environment.paint(mode=...))
 VJ_PAINT_ELLIPSE = 1 << 0            # vj_paint_params.flags: the ellipse inscribed in the mapped rectangle (Environment.paint(ellipse=True))
+VJ_YUV_NV12, VJ_YUV_NV21, VJ_YUV_I420 = 0, 1, 2   # vj_yuv_image.layout (YuvFrames.layout, Environment.bgr_to_yuv(layout=...))
+VJ_YUV_RGB_ORDER = 1 << 0            # vj_yuv_params.flags: the BGR side is RGB / RGBA (Environment.yuv_to_bgr(rgb=True))
+YUV_LAYOUTS = {"nv12": VJ_YUV_NV12, "nv21": VJ_YUV_NV21, "i420": VJ_YUV_I420}
 PAINT_MODES = {"fill": VJ_PAINT_FILL, "outline": VJ_PAINT_OUTLINE, "pixelate": VJ_PAINT_PIXELATE, "blur": VJ_PAINT_BLUR}
 VJ_EXTRACT_PLANAR = 1 << 1           # vj_extract_params.flags: n x C x h x w instead of n x h x w x C (Environment.extract(planar=True))
 VJ_FLAG_EQUALIZE_HIST = 1 << 11      # cv::equalizeHist on every frame, on the device, in front of detect / detect_opencv / detect_opencv_roc / the mixed calls; refused elsewhere
@@ -169,6 +172,17 @@ class PaintParams(C.Structure):
     """vj_paint_params"""
     _fields_ = [("mode", C.c_int32), ("flags", C.c_uint32), ("sx", C.c_double), ("sy", C.c_double), ("margin", C.c_double),
                 ("size", C.c_int32), ("rel", C.c_double), ("color", C.c_uint8 * 4), ("reserved", C.c_uint32)]
+
+
+class _YuvImage(C.Structure):
+    """vj_yuv_image"""
+    _fields_ = [("y", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("y_stride", C.c_int32), ("c_stride", C.c_int32), ("layout", C.c_int32), ("on_device", C.c_int32)]
+
+
+class YuvParams(C.Structure):
+    """vj_yuv_params"""
+    _fields_ = [("channels", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class AffineParams(C.Structure):
@@ -329,6 +343,14 @@ _SIGNATURES = {
                                   C.POINTER(C.c_uint64)]),
     "vj_paint": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(PaintParams)]),
     "vj_paint_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "vj_yuv_default": (None, [C.POINTER(YuvParams)]),
+    "vj_yuv_to_bgr_layout": (C.c_int, [C.POINTER(_YuvImage), C.c_int, C.POINTER(YuvParams), C.POINTER(_Image), C.POINTER(C.c_uint64)]),
+    "vj_yuv_to_bgr": (C.c_int, [C.c_void_p, C.POINTER(_YuvImage), C.c_int, C.POINTER(YuvParams), C.c_void_p, C.c_uint64, C.POINTER(_Image)]),
+    "vj_bgr_to_yuv_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.POINTER(YuvParams), C.c_int, C.POINTER(_YuvImage), C.POINTER(C.c_uint64)]),
+    "vj_bgr_to_yuv": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.POINTER(YuvParams), C.c_int, C.c_void_p, C.c_uint64,
+                                C.POINTER(_YuvImage)]),
+    "vj_yuv_luma": (C.c_int, [C.POINTER(_YuvImage), C.POINTER(_Image)]),
+    "vj_yuv_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vj_extract_affine_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(AffineParams), C.POINTER(C.c_int),
                                            C.POINTER(C.c_uint64)]),
     "vj_extract_affine": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(AffineParams), C.c_void_p, C.c_uint64]),
@@ -1165,6 +1187,162 @@ class Environment:
         return float(ms.value)
 
     @staticmethod
+    def _yuv_layout_id(layout) -> int:
+        if isinstance(layout, str):
+            if layout.lower() not in YUV_LAYOUTS:
+                raise ValueError('layout must be "nv12", "nv21" or "i420"')
+            return YUV_LAYOUTS[layout.lower()]
+        return int(layout)
+
+    @staticmethod
+    def _yuv_images(frames, layout):
+        """4:2:0 frames -> (ctypes array of vj_yuv_image, n, arrays to keep alive).  frames: YuvFrames;
+        a numpy (n, h * 3 // 2, w) uint8 array of stacked frames (what OpenCV and the decoders hand out: the Y plane, the chroma
+        below it), or one (h * 3 // 2, w) frame; a tuple of a frame's planes (y, uv) or (y, u, v), 2-D uint8 arrays whose rows may be
+        strided views; or a list of any of these, of differing sizes.  layout: of the host frames (a YuvFrames carries its own)."""
+        lay = Environment._yuv_layout_id(layout)
+        keep, imgs = [], []
+
+        def plane(a):
+            if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or a.ndim != 2:
+                raise ValueError("a plane must be a 2-D uint8 array")
+            g = a if a.strides[1] == 1 else np.ascontiguousarray(a)
+            keep.append(g)
+            return g
+
+        def stacked(a):
+            if a.dtype != np.uint8 or a.ndim != 2 or a.shape[0] % 3 != 0 or a.shape[0] < 3:
+                raise ValueError("a stacked 4:2:0 frame is a (h * 3 // 2, w) uint8 array")
+            h, w = a.shape[0] * 2 // 3, a.shape[1]
+            if lay == VJ_YUV_I420:   # the U and V planes are runs of w / 2 * h / 2 bytes: the rows must follow each other
+                g = plane(np.ascontiguousarray(a))
+                base = g.ctypes.data + w * h
+                imgs.append(_YuvImage(g.ctypes.data, base, base + (w // 2) * (h // 2), w, h, w, w // 2, lay, 0))
+            else:
+                g = plane(a)
+                imgs.append(_YuvImage(g.ctypes.data, g.ctypes.data + h * g.strides[0], None, w, h, g.strides[0], g.strides[0], lay, 0))
+
+        if isinstance(frames, (YuvFrames, tuple)) or (isinstance(frames, np.ndarray) and frames.ndim == 2):
+            frames = [frames]
+        for f in list(frames):
+            if isinstance(f, YuvFrames):
+                imgs += [_YuvImage(f.ptr_y + i * f.frame_bytes, f.ptr_c0 + i * f.frame_bytes, (f.ptr_c1 + i * f.frame_bytes) if f.ptr_c1 else None,
+                                   f.width, f.height, f.y_stride, f.c_stride, f.layout, 1) for i in range(f.n)]
+            elif isinstance(f, tuple):
+                if len(f) != (3 if lay == VJ_YUV_I420 else 2):
+                    raise ValueError("planes: (y, uv) for nv12 / nv21, (y, u, v) for i420")
+                p = [plane(a) for a in f]
+                if any(q.strides[0] != p[1].strides[0] for q in p[1:]):
+                    raise ValueError("the u and v planes share one row stride")
+                imgs.append(_YuvImage(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data if len(p) > 2 else None, p[0].shape[1], p[0].shape[0],
+                                      p[0].strides[0], p[1].strides[0], lay, 0))
+            elif isinstance(f, np.ndarray) and f.ndim == 3:
+                for a in f:
+                    stacked(a)
+            elif isinstance(f, np.ndarray):
+                stacked(f)
+            else:
+                raise ValueError("a frame must be YuvFrames, a stacked (h * 3 // 2, w) uint8 array or a tuple of planes")
+        arr = (_YuvImage * max(len(imgs), 1))(*imgs)
+        return arr, len(imgs), keep
+
+    @staticmethod
+    def _yuv_params(channels: int, rgb: bool) -> "YuvParams":
+        p = YuvParams()
+        load_library().vj_yuv_default(C.byref(p))
+        p.channels = int(channels)
+        p.flags = VJ_YUV_RGB_ORDER if rgb else 0
+        return p
+
+    @staticmethod
+    def _out_tensor(out, nbytes: int, device: int):
+        import torch
+        if out is None:
+            out = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=torch.device("cuda", device))
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
+            raise ValueError("out must be a contiguous torch.uint8 tensor in device memory")
+        return out
+
+    @staticmethod
+    def yuv_to_bgr_layout(frames, alpha: bool = False, rgb: bool = False, layout="nv12"):
+        """vj_yuv_to_bgr_layout (host only): where yuv_to_bgr() puts every image -> ([(offset, width, height, stride)], bytes)."""
+        imgs, n, keep = Environment._yuv_images(frames, layout)
+        p = Environment._yuv_params(4 if alpha else 3, rgb)
+        out = (_Image * max(n, 1))()
+        nbytes = C.c_uint64(0)
+        _check(load_library().vj_yuv_to_bgr_layout(imgs, n, C.byref(p), out, C.byref(nbytes)), "vj_yuv_to_bgr_layout")
+        return [(int(out[i].data or 0), out[i].width, out[i].height, out[i].stride) for i in range(n)], int(nbytes.value)
+
+    def yuv_to_bgr(self, frames, alpha: bool = False, rgb: bool = False, out=None, layout="nv12") -> list:
+        """vj_yuv_to_bgr: a decoder's NV12 / NV21 / I420 frames to interleaved BGR (alpha=True: BGRA with alpha 255; rgb=True: RGB /
+        RGBA) on the device, OpenCV's 8-bit BT.601 limited-range arithmetic with nearest chroma.  frames: see
+        _yuv_images; layout names the layout of host arrays.  Returns what preprocess() returns: ONE DeviceFrames of n frames
+        when the sizes agree — extract(), extract_affine() and paint() take it as it is —, else one per frame.  out: as preprocess()."""
+        imgs, n, keep = self._yuv_images(frames, layout)
+        p = self._yuv_params(4 if alpha else 3, rgb)
+        lib = load_library()
+        res = (_Image * max(n, 1))()
+        nbytes = C.c_uint64(0)
+        _check(lib.vj_yuv_to_bgr_layout(imgs, n, C.byref(p), res, C.byref(nbytes)), "vj_yuv_to_bgr_layout")
+        out = self._out_tensor(out, nbytes.value, self._device)
+        _order_after_torch(self._device)       # after the allocation, as in preprocess()
+        _check(lib.vj_yuv_to_bgr(self._h, imgs, n, C.byref(p), C.c_void_p(out.data_ptr()), out.numel(), res), "vj_yuv_to_bgr")
+        if n == 0:
+            return []
+        ch = p.channels
+        r = [DeviceFrames(int(res[i].data), 1, res[i].height, res[i].width, res[i].stride, ch, 0, out) for i in range(n)]
+        if all((f.width, f.height) == (r[0].width, r[0].height) for f in r):
+            return [DeviceFrames(r[0].ptr, n, r[0].height, r[0].width, r[0].stride, ch, (r[1].ptr - r[0].ptr) if n > 1 else 0, out)]
+        return r
+
+    @staticmethod
+    def _bgr_images(frames):
+        if isinstance(frames, (np.ndarray, DeviceFrames)):
+            return Environment._images(frames, True)
+        return Environment._mixed_images(frames)
+
+    @staticmethod
+    def bgr_to_yuv_layout(frames, layout="nv12", rgb: bool = False):
+        """vj_bgr_to_yuv_layout (host only): where bgr_to_yuv() puts every frame ->
+        ([(y offset, c0 offset, c1 offset, width, height, y_stride, c_stride)], bytes)."""
+        imgs, n, keep = Environment._bgr_images(frames)
+        p = Environment._yuv_params(3, rgb)
+        out = (_YuvImage * max(n, 1))()
+        nbytes = C.c_uint64(0)
+        _check(load_library().vj_bgr_to_yuv_layout(imgs, n, C.byref(p), Environment._yuv_layout_id(layout), out, C.byref(nbytes)), "vj_bgr_to_yuv_layout")
+        return [(int(o.y or 0), int(o.c0 or 0), int(o.c1 or 0), o.width, o.height, o.y_stride, o.c_stride) for o in out[:n]], int(nbytes.value)
+
+    def bgr_to_yuv(self, frames, layout="nv12", rgb: bool = False, out=None):
+        """vj_bgr_to_yuv: BGR / BGRA frames (rgb=True: RGB / RGBA; alpha is ignored) to NV12 / NV21 / I420 on the device — what an
+        encoder takes —, OpenCV's 8-bit BT.601 limited-range arithmetic, chroma from the top-left pixel of each 2 x 2 block
+        (DESIGN.md §4.21).  frames: DeviceFrames, e.g. what yuv_to_bgr() returned and paint() changed; an (n, h, w, 3 | 4) array; or a
+        list as detect_mixed() takes it.  Every output frame is stacked: the Y plane at a pitch of the width rounded up to 4, the
+        chroma below it.  Returns ONE YuvFrames of n frames when the sizes agree, else a list of one per frame.  out: as preprocess()."""
+        lay = self._yuv_layout_id(layout)
+        imgs, n, keep = self._bgr_images(frames)
+        p = self._yuv_params(3, rgb)
+        lib = load_library()
+        res = (_YuvImage * max(n, 1))()
+        nbytes = C.c_uint64(0)
+        _check(lib.vj_bgr_to_yuv_layout(imgs, n, C.byref(p), lay, res, C.byref(nbytes)), "vj_bgr_to_yuv_layout")
+        out = self._out_tensor(out, nbytes.value, self._device)
+        _order_after_torch(self._device)       # after the allocation, as in preprocess()
+        _check(lib.vj_bgr_to_yuv(self._h, imgs, n, C.byref(p), lay, C.c_void_p(out.data_ptr()), out.numel(), res), "vj_bgr_to_yuv")
+        if n == 0:
+            return []
+        r = [YuvFrames(int(o.y), int(o.c0), int(o.c1 or 0), 1, o.height, o.width, o.y_stride, o.c_stride, lay, 0, out) for o in res[:n]]
+        if all((f.width, f.height) == (r[0].width, r[0].height) for f in r):
+            return YuvFrames(r[0].ptr_y, r[0].ptr_c0, r[0].ptr_c1, n, r[0].height, r[0].width, r[0].y_stride, r[0].c_stride, lay,
+                             (r[1].ptr_y - r[0].ptr_y) if n > 1 else 0, out)
+        return r
+
+    def yuv_timing(self) -> float:
+        """vj_yuv_timing: device time of the last yuv_to_bgr() or bgr_to_yuv() call (events around its copies and launches), ms."""
+        ms = C.c_float(0)
+        _check(load_library().vj_yuv_timing(self._h, C.byref(ms)), "vj_yuv_timing")
+        return float(ms.value)
+
+    @staticmethod
     def _affine_args(frames, affines, size, gray, planar, color):
         """-> (ctypes array of vj_image, n, arrays to keep alive, AFFINE_DTYPE array, vj_affine_params).  frames: as preprocess().
         affines: an AFFINE_DTYPE array or (n, 7) float64 rows of (frame, m0 .. m5)."""
@@ -1349,6 +1527,59 @@ class DeviceFrames:
             return cls(t.data_ptr(), n, h, w, w * ch, ch)
         n, h, w = t.shape
         return cls(t.data_ptr(), n, h, w, w)
+
+
+@dataclass
+class YuvFrames:
+    """A batch of equal-size 4:2:0 frames resident in device memory, as a hardware decoder writes them and an encoder reads them.
+    layout: VJ_YUV_NV12 / VJ_YUV_NV21 (ptr_c0: the plane of U, V / V, U byte pairs; ptr_c1 = 0) or VJ_YUV_I420 (ptr_c0, ptr_c1: the
+    U and V planes).  Rows of the Y plane are y_stride bytes apart, rows of the chroma planes c_stride; frame i's planes lie
+    i * frame_bytes behind frame 0's (planes that are allocated apart have no default for it: with n > 1 it must be given).  owner:
+    whatever keeps the memory alive.  Ordered after torch's current stream like DeviceFrames."""
+    ptr_y: int
+    ptr_c0: int
+    ptr_c1: int
+    n: int
+    height: int
+    width: int
+    y_stride: int
+    c_stride: int
+    layout: int = VJ_YUV_NV12
+    frame_bytes: int = 0
+    owner: object = None
+
+    def __post_init__(self):
+        if self.n > 1 and not self.frame_bytes:
+            raise ValueError("YuvFrames of more than one frame need frame_bytes")
+
+    @classmethod
+    def from_torch(cls, t, layout="nv12") -> "YuvFrames":
+        """(n, h * 3 // 2, w) uint8 CUDA tensor of stacked frames: the Y plane, the chroma below it (I420: the U plane, then the V
+        plane, w / 2 * h / 2 bytes each)."""
+        assert t.is_cuda and t.dtype.itemsize == 1 and t.dim() == 3 and t.is_contiguous() and t.shape[1] % 3 == 0
+        lay = Environment._yuv_layout_id(layout)
+        n, rows, w = t.shape
+        h = rows * 2 // 3
+        y = t.data_ptr()
+        if lay == VJ_YUV_I420:
+            return cls(y, y + w * h, y + w * h + (w // 2) * (h // 2), n, h, w, w, w // 2, lay, rows * w, t)
+        return cls(y, y + w * h, 0, n, h, w, w, w, lay, rows * w, t)
+
+    def luma(self) -> "DeviceFrames":
+        """vj_yuv_luma: the Y planes as gray frames (COLOR_YUV2GRAY_NV12) — what preprocess() and every detect call take."""
+        return DeviceFrames(self.ptr_y, self.n, self.height, self.width, self.y_stride, 1, self.frame_bytes, self.owner)
+
+
+def yuv_to_bgr_layout(frames, alpha: bool = False, rgb: bool = False, layout="nv12"):
+    """vj_yuv_to_bgr_layout: the host-only twin of Environment.yuv_to_bgr (no environment, no device) ->
+    ([(offset, width, height, stride) per frame], bytes of the destination buffer)."""
+    return Environment.yuv_to_bgr_layout(frames, alpha, rgb, layout)
+
+
+def bgr_to_yuv_layout(frames, layout="nv12", rgb: bool = False):
+    """vj_bgr_to_yuv_layout: the host-only twin of Environment.bgr_to_yuv ->
+    ([(y offset, c0 offset, c1 offset, width, height, y_stride, c_stride) per frame], bytes of the destination buffer)."""
+    return Environment.bgr_to_yuv_layout(frames, layout, rgb)
 
 
 def preprocess_layout(frames, size=None, fx=None, fy=None, equalize: bool = False, color: bool = False):

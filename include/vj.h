@@ -934,6 +934,75 @@ int  vj_paint(vj_env* e, const vj_image* frames, int n_frames, const vj_roi* reg
 /* Device time of the environment's last vj_paint call: events around its copies and launches, in ms.  A null argument: VJ_ERR_ARG. */
 int  vj_paint_timing(const vj_env* e, float* ms);
 
+/* ------------------------------------------------- decoder frames: NV12 / NV21 / I420 to BGR and back, on the device */
+/* Hardware decoders write 4:2:0 YCbCr and encoders read it; vj_extract and vj_paint work on interleaved BGR.  These two batched
+ * calls close the loop on the device:
+ *   decoder -> vj_yuv_luma -> vj_preprocess / detect -> vj_yuv_to_bgr -> vj_extract / vj_paint -> vj_bgr_to_yuv -> encoder.
+ * The arithmetic is OpenCV imgproc's 8-bit fixed-point BT.601 limited-range pair, cvtColor(COLOR_YUV2BGR_NV12 / _NV21 / _I420) and
+ * cvtColor(COLOR_BGR2YUV_I420); parity is unpinned at the OpenCV boundary, the definition here and in DESIGN.md 4.21 is
+ * authoritative.  All values are int32, >> is the arithmetic (flooring) shift, sat(t) = min(max(t, 0), 255), H = 1 << 19.
+ * Decode: pixel (x, y) takes Y = luma[y][x] and the chroma sample (x >> 1, y >> 1) — nearest, no interpolation:
+ *     yy = max(Y - 16, 0) * 1220542;  u = U - 128;  v = V - 128
+ *     B = sat((yy + H + 2116026 * u) >> 20)
+ *     G = sat((yy + H -  852492 * v - 409993 * u) >> 20)
+ *     R = sat((yy + H + 1673527 * v) >> 20)
+ *   and with four output channels alpha = 255.
+ * Encode (alpha, if present, is ignored): for every pixel
+ *     Y = (269484 R + 528482 G + 102760 B + H + (16 << 20)) >> 20
+ *   and from the TOP-LEFT pixel of each 2 x 2 block (even x, even y; no averaging)
+ *     U = (-155188 R - 305135 G + 460324 B + H + (128 << 20)) >> 20
+ *     V = ( 460324 R - 385875 G -  74448 B + H + (128 << 20)) >> 20
+ *   No clamp is needed: the outputs span 16 .. 240.
+ * Layouts: NV12 — a Y plane and one plane of interleaved U, V byte pairs at half resolution; NV21 — the same with pairs V, U;
+ * I420 — three planes Y, U, V, the chroma planes w/2 x h/2.  Every plane has its own pointer; width and height are even.      */
+enum { VJ_YUV_NV12 = 0, VJ_YUV_NV21 = 1, VJ_YUV_I420 = 2 };   /* vj_yuv_image.layout                                           */
+enum { VJ_YUV_RGB_ORDER = 1u << 0 };                          /* vj_yuv_params.flags: the BGR side is RGB / RGBA (R and B swapped) */
+typedef struct vj_yuv_image {
+    const uint8_t* y;          /* the Y plane: height rows of width bytes, y_stride bytes apart                                  */
+    const uint8_t* c0;         /* NV12 / NV21: the pair plane, height / 2 rows of width bytes; I420: the U plane, height / 2 rows
+                                  of width / 2 bytes.  Rows c_stride bytes apart                                                 */
+    const uint8_t* c1;         /* I420: the V plane (c_stride too); NV12 / NV21: ignored                                         */
+    int32_t width, height;     /* even, 2 .. 65534                                                                               */
+    int32_t y_stride, c_stride;
+    int32_t layout;            /* VJ_YUV_NV12 / _NV21 / _I420                                                                    */
+    int32_t on_device;         /* as vj_image.on_device, for all planes of the frame                                            */
+} vj_yuv_image;
+typedef struct vj_yuv_params {
+    int32_t  channels;         /* of the BGR side: 3, or 4 (BGRA)                                                               */
+    uint32_t flags;            /* VJ_YUV_RGB_ORDER                                                                               */
+    uint32_t reserved;         /* must be 0                                                                                      */
+} vj_yuv_params;
+void vj_yuv_default(vj_yuv_params* p);   /* channels 3, flags 0 */
+/* Host only, no environment: where each BGR image lies and how many bytes the buffer needs.  out[i] is what vj_yuv_to_bgr will
+ * return for frame i, with data = (const uint8_t*)offset in the buffer.  The layout is vj_preprocess's: a row pitch of
+ * width * channels rounded up to 4, every image at a multiple of 256 bytes; *bytes is the end of the last image.              */
+int  vj_yuv_to_bgr_layout(const vj_yuv_image* frames, int n_frames, const vj_yuv_params* p, vj_image* out, uint64_t* bytes);
+/* frames: host or device-resident, any strides, any addresses, sizes may differ.  d_dst: device memory of at least the layout's
+ * bytes, as vj_preprocess's.  out[i]: on_device = 1, channels = p->channels, data inside d_dst — every entry point, vj_paint
+ * included, takes them as they are.  The pad bytes inside the pitch are written as 0.  Returns after the work is complete.
+ * All checks come before the device is used.  VJ_ERR_ARG, with vj_last_error naming the frame or the field: null arguments; a null
+ * plane that the layout needs; odd or non-positive sizes; a stride below the plane's row bytes; an unknown layout; unknown flag
+ * bits, reserved != 0; channels not 3 or 4; dst_bytes below the layout's bytes; d_dst not a multiple of 4; a device-resident
+ * source plane that overlaps [d_dst, d_dst + bytes).  VJ_ERR_LIMIT: a side above 65534; more work units than a 32-bit index holds.
+ * n_frames == 0 is VJ_OK.  Calls of more frames than the configured "max_subbatch" run in slices.                               */
+int  vj_yuv_to_bgr(vj_env* e, const vj_yuv_image* frames, int n_frames, const vj_yuv_params* p, uint8_t* d_dst, uint64_t dst_bytes,
+                   vj_image* out);
+/* Host only: where each output frame lies.  A frame is STACKED: its Y plane at a pitch of width rounded up to 4, its chroma right
+ * below — NV12 / NV21: height / 2 rows of pairs at the same pitch; I420: the U plane, then the V plane, height / 2 rows each at a
+ * pitch of width / 2 rounded up to 4.  Every plane is 4-byte aligned, every frame starts at a multiple of 256 bytes, pad bytes
+ * are written as 0.  out[i]: y, c0, c1 = offsets in the buffer (c1 = 0 for NV12 / NV21), y_stride, c_stride = the pitches.    */
+int  vj_bgr_to_yuv_layout(const vj_image* frames, int n_frames, const vj_yuv_params* p, int layout, vj_yuv_image* out,
+                          uint64_t* bytes);
+/* frames: vj_detect_mixed's rules, with 3 or 4 channels (p->channels is not looked at: every frame says its own; a gray frame is
+ * VJ_ERR_ARG) and even sizes.  Otherwise as vj_yuv_to_bgr, errors included.  out[i]: on_device = 1, pointers inside d_dst.     */
+int  vj_bgr_to_yuv(vj_env* e, const vj_image* frames, int n_frames, const vj_yuv_params* p, int layout, uint8_t* d_dst,
+                   uint64_t dst_bytes, vj_yuv_image* out);
+/* Host only: the Y plane of a frame as a gray vj_image — what cvtColor(COLOR_YUV2GRAY_NV12) returns; vj_preprocess and every
+ * detect call take it.  VJ_ERR_ARG: null arguments, a null Y plane, non-positive sizes, y_stride < width.                       */
+int  vj_yuv_luma(const vj_yuv_image* frame, vj_image* out);
+/* Device time of the environment's last vj_yuv_to_bgr or vj_bgr_to_yuv call: events around its copies and launches, in ms.      */
+int  vj_yuv_timing(const vj_env* e, float* ms);
+
 /* ------------------------------------------------------------ frame streams */
 /* Video-style use (the demo's per-frame loop, main.cpp:104-125): batches of host frames are uploaded into
  * one of two device buffers by DMA on a copy stream while the kernels of the previous batch run, and the
