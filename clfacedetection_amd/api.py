@@ -185,6 +185,11 @@ class YuvParams(C.Structure):
     _fields_ = [("channels", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TrackParams(C.Structure):
+    """vj_track_params"""
+    _fields_ = [("tmpl", C.c_int32), ("radius", C.c_int32), ("sx", C.c_double), ("sy", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class AffineParams(C.Structure):
     """vj_affine_params"""
     _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
@@ -241,6 +246,8 @@ CLOD_WINDOW_RESULT_DTYPE = np.dtype([("result", "<i4"), ("variance", "<f4"), ("s
 VJ_WINDOW_OUTSIDE = -2**31   # vj_clod_window_result.result of a window that does not lie inside its frame
 RECT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("weight", "<f4"),
                        ("frame", "<i4"), ("scale_idx", "<i4")])
+TRACK_RESULT_DTYPE = np.dtype([("dx", "<i4"), ("dy", "<i4"), ("sad", "<u4"), ("sad0", "<u4"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"),
+                               ("h", "<i4")])                                                                 # vj_track_result
 AFFINE_DTYPE = np.dtype([("frame", "<i4"), ("reserved", "<i4"), ("m", "<f8", (6,))])                      # vj_affine
 STAGE_DTYPE = np.dtype([("first_tree", "<i4"), ("n_trees", "<i4"), ("threshold", "<f4"), ("parent", "<i4"),
                         ("next", "<i4"), ("child", "<i4")])
@@ -351,6 +358,11 @@ _SIGNATURES = {
                                 C.POINTER(_YuvImage)]),
     "vj_yuv_luma": (C.c_int, [C.POINTER(_YuvImage), C.POINTER(_Image)]),
     "vj_yuv_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "vj_track_default": (None, [C.POINTER(TrackParams)]),
+    "vj_track_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(TrackParams), C.c_void_p, C.c_void_p,
+                                  C.POINTER(C.c_uint64)]),
+    "vj_track": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(TrackParams), C.c_void_p]),
+    "vj_track_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vj_extract_affine_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(AffineParams), C.POINTER(C.c_int),
                                            C.POINTER(C.c_uint64)]),
     "vj_extract_affine": (C.c_int, [C.c_void_p, C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(AffineParams), C.c_void_p, C.c_uint64]),
@@ -1076,25 +1088,28 @@ class Environment:
         return float(ms.value)
 
     @staticmethod
-    def _paint_images(frames, color):
+    def _paint_images(frames, color, write: bool = True):
         """-> (ctypes array of vj_image, n, objects to keep alive, True if a device frame is among them).  frames: a DeviceFrames, a
         uint8 CUDA tensor (DeviceFrames.from_torch), a writeable uint8 numpy array — one frame or a batch, as detect() reads its
         shape, color=True for BGR / BGRA — or a list of these, each array then one frame (2-D gray, 3-D BGR / BGRA).  The frames are
-        painted IN PLACE: an array the call would have to copy (read-only, another dtype, pixels not contiguous) is a ValueError."""
+        painted IN PLACE: an array the call would have to copy (read-only, another dtype, pixels not contiguous) is a ValueError.
+        write=False (track(), which only reads them): a read-only array is taken too."""
         def is_tensor(f):
             return not isinstance(f, (np.ndarray, DeviceFrames)) and hasattr(f, "data_ptr") and hasattr(f, "is_cuda")
 
+        why = "paint() writes into its frames" if write else "track() reads its frames where they lie"
+
         def one(f, ndim):
             if not isinstance(f, np.ndarray) or f.dtype != np.uint8:
-                raise ValueError("paint() writes into its frames: a host frame must be a uint8 numpy array (no copy is made)")
+                raise ValueError(f"{why}: a host frame must be a uint8 numpy array (no copy is made)")
             if f.ndim != ndim or (ndim == 3 and f.shape[2] not in (3, 4)):
                 raise ValueError("a host frame must be a 2-D uint8 array or a (h, w, 3|4) uint8 array (BGR / BGRA)")
-            if not f.flags.writeable:
+            if write and not f.flags.writeable:
                 raise ValueError("paint() writes into its frames: a read-only array cannot be painted (no copy is made)")
             if f.shape[0] == 0 or f.shape[1] == 0:
                 raise ValueError("a frame must not be empty")
             if (ndim == 3 and (f.strides[2] != 1 or f.strides[1] != f.shape[2])) or (ndim == 2 and f.strides[1] != 1) or f.strides[0] <= 0:
-                raise ValueError("paint() writes into its frames: the pixels of a row must be contiguous (no copy is made)")
+                raise ValueError(f"{why}: the pixels of a row must be contiguous (no copy is made)")
             return _Image(f.ctypes.data, f.shape[1], f.shape[0], f.strides[0], 0, f.shape[2] if ndim == 3 else 1)
 
         items = frames if isinstance(frames, (list, tuple)) else [frames]
@@ -1185,6 +1200,53 @@ class Environment:
         ms = C.c_float(0)
         _check(load_library().vj_paint_timing(self._h, C.byref(ms)), "vj_paint_timing")
         return float(ms.value)
+
+    @staticmethod
+    def _track_args(frames, rows, tmpl, radius, scale, color):
+        """-> (ctypes array of vj_image, n, objects to keep alive, (n, 6) int32 rows, vj_track_params).  frames: as paint() takes them
+        (_paint_images), read-only arrays included; rows: integer rows of (src_frame, dst_frame, x, y, w, h)."""
+        imgs, n, keep, dev = Environment._paint_images(frames, color, write=False)
+        r = np.asarray(rows)
+        if r.size and not np.issubdtype(r.dtype, np.integer):
+            raise ValueError("rows must be integer rows of (src_frame, dst_frame, x, y, w, h)")
+        r = np.ascontiguousarray(r.astype(np.int32).reshape(-1, 6))
+        p = TrackParams()
+        load_library().vj_track_default(C.byref(p))
+        p.tmpl, p.radius = int(tmpl), int(radius)
+        p.sx, p.sy = float(scale[0]), float(scale[1])
+        return imgs, n, keep, r, p
+
+    @staticmethod
+    def track_layout(frames, rows, tmpl: int = 32, radius: int = 8, scale=(1.0, 1.0), color: bool = False):
+        """vj_track_layout (host only): what track() will match -> ((n, 5) int32 rows (src_frame, x0, y0, w0, h0) of the templates'
+        mapped source regions; (n, 5) int32 rows (dst_frame, X, Y, Wm, Hm) of the search patches'; the scratch bytes of the call run
+        as one slice).  The regions may lie outside their frames."""
+        imgs, n, keep, r, p = Environment._track_args(frames, rows, tmpl, radius, scale, color)
+        tr, sr = np.zeros((len(r), 5), np.int32), np.zeros((len(r), 5), np.int32)
+        nbytes = C.c_uint64(0)
+        _check(load_library().vj_track_layout(imgs, n, r.ctypes.data, len(r), C.byref(p), tr.ctypes.data, sr.ctypes.data, C.byref(nbytes)),
+               "vj_track_layout")
+        return tr, sr, int(nbytes.value)
+
+    def track(self, frames, rows, tmpl: int = 32, radius: int = 8, scale=(1.0, 1.0), color: bool = False) -> np.ndarray:
+        """vj_track: block matching on the device.  Row (src_frame, dst_frame, x, y, w, h): the box, mapped with
+        scale = (sx, sy) as extract() maps it, is cut from src_frame as a tmpl x tmpl gray patch and looked for in dst_frame at the
+        (2 radius + 1)^2 displacements of -radius .. radius patch pixels around its own position, by the sum of absolute differences;
+        on equal sums the shorter move wins.  frames: as paint() takes them, read-only arrays included; they are not written.
+        Returns a TRACK_RESULT_DTYPE array: dx, dy (patch pixels), sad, sad0 (the sum at (0, 0)) and the box x, y, w, h in dst_frame,
+        in SOURCE pixels (what paint() takes with scale = (1, 1))."""
+        imgs, n, keep, r, p = self._track_args(frames, rows, tmpl, radius, scale, color)
+        out = np.zeros(len(r), TRACK_RESULT_DTYPE)
+        _order_after_torch(self._device)       # work queued on the frames (a decoder, a copy_) has written them before they are read
+        _check(load_library().vj_track(self._h, imgs, n, r.ctypes.data, len(r), C.byref(p), out.ctypes.data), "vj_track")
+        return out
+
+    def track_timing(self):
+        """vj_track_timing: device time of the last track() call (events around its copies and launches) and of its match launches
+        alone -> (ms, match_ms)."""
+        ms, match = C.c_float(0), C.c_float(0)
+        _check(load_library().vj_track_timing(self._h, C.byref(ms), C.byref(match)), "vj_track_timing")
+        return float(ms.value), float(match.value)
 
     @staticmethod
     def _yuv_layout_id(layout) -> int:
@@ -1599,6 +1661,69 @@ def paint_layout(frames, rects, mode="blur", size: int = 0, rel: float = 0.25, s
     """vj_paint_layout: the host-only twin of Environment.paint (no environment, no device) ->
     (clipped rectangles as (n, 5) int32 rows, sizes as (n,) int32, scratch bytes)."""
     return Environment.paint_layout(frames, rects, mode, size, rel, scale, margin, ellipse, color)
+
+
+def track_layout(frames, rows, tmpl: int = 32, radius: int = 8, scale=(1.0, 1.0), color: bool = False):
+    """vj_track_layout: the host-only twin of Environment.track (no environment, no device) ->
+    (template regions as (n, 5) int32 rows, search regions as (n, 5) int32 rows, scratch bytes)."""
+    return Environment.track_layout(frames, rows, tmpl, radius, scale, color)
+
+
+def _box_iou(a, b) -> float:
+    """Intersection over union of two (x, y, w, h) boxes."""
+    iw = min(a[0] + a[2], b[0] + b[2]) - max(a[0], b[0])
+    ih = min(a[1] + a[3], b[1] + b[3]) - max(a[1], b[1])
+    if iw <= 0 or ih <= 0:
+        return 0.0
+    inter = float(iw) * float(ih)
+    return inter / (float(a[2]) * float(a[3]) + float(b[2]) * float(b[3]) - inter)
+
+
+def bridge_detections(env, frames, rects, max_age: int = 2, iou: float = 0.3, max_mad: float = 12.0, tmpl: int = 32, radius: int = 8,
+                      scale=(1.0, 1.0), color: bool = False, track=None):
+    """Fills the gaps a detector leaves in a video with Environment.track: host bookkeeping around at most 2 * max_age device calls.
+    frames: consecutive frames in index order, as track() takes them; rects: the detections of all frames, a RECT_DTYPE array or
+    integer rows of (frame, x, y, w, h), in the detector's coordinates — scale = (sx, sy) takes them to the frames' pixels, as in
+    extract() and paint().
+
+    Forward round a = 1 .. max_age: every box of age a - 1 (age 0: a detected box) in a frame f that is not the last, for which no box
+    of frame f + 1 — detected or carried — has an intersection over union of at least `iou`, becomes a row f -> f + 1; all rows of a
+    round are ONE track call.  A row is accepted when its sad <= max_mad * tmpl^2 (a mean absolute difference of max_mad gray
+    levels); its result box then joins frame f + 1 with age a.  The backward rounds do the same towards f - 1 with ages -1 ..
+    -max_age; they are seeded by detected boxes only, and the boxes of the forward pass count as present.  A round without rows ends
+    its pass.  max_mad is the caller's knob: its default of 12 gray levels is a guess that nobody has measured on real video.
+
+    Returns (rects, age): (n, 5) int32 rows of (frame, x, y, w, h) in the input's coordinates — the input's rows in their order, then
+    the carried boxes in the order they were found, each the result box divided by scale and rounded half to even (cvRound) — and
+    the (n,) int32 ages.  track: a callable with Environment.track's signature, default env.track."""
+    if isinstance(rects, np.ndarray) and rects.dtype.names is not None:
+        r = np.stack([np.asarray(rects[k], np.int32).reshape(-1) for k in ("frame", "x", "y", "w", "h")], axis=1)
+    else:
+        r = np.asarray(rects)
+        if r.size and not np.issubdtype(r.dtype, np.integer):
+            raise ValueError("rects must be a RECT_DTYPE array or integer rows of (frame, x, y, w, h)")
+        r = r.astype(np.int32).reshape(-1, 5)
+    if track is None:
+        track = env.track
+    n_frames = Environment._paint_images(frames, color, write=False)[1]       # as track() counts them: a DeviceFrames holds .n frames
+    sx, sy = (float(v) or 1.0 for v in scale)
+    boxes = [tuple(int(v) for v in row) for row in r]
+    ages = [0] * len(boxes)
+    limit = float(max_mad) * int(tmpl) * int(tmpl)
+    for step in (1, -1):
+        for a in range(1, int(max_age) + 1):
+            seeds = [b for b, g in zip(boxes, ages) if g == step * (a - 1) and 0 <= b[0] + step < n_frames]
+            rows = [(b[0], b[0] + step) + b[1:] for b in seeds
+                    if not any(o[0] == b[0] + step and _box_iou(b[1:], o[1:]) >= iou for o in boxes)]
+            if not rows:
+                break
+            res = track(frames, np.asarray(rows, np.int32).reshape(-1, 6), tmpl=tmpl, radius=radius, scale=scale, color=color)
+            for row, m in zip(rows, res):
+                if float(m["sad"]) <= limit:
+                    boxes.append((row[1], int(np.rint(float(m["x"]) / sx)), int(np.rint(float(m["y"]) / sy)),
+                                  max(int(np.rint(float(m["w"]) / sx)), 1), max(int(np.rint(float(m["h"]) / sy)), 1)))
+                    ages.append(step * a)
+    return np.asarray(boxes, np.int32).reshape(-1, 5), np.asarray(ages, np.int32)
 
 
 def extract_affine_layout(frames, affines, size, gray: bool = False, planar: bool = False, color: bool = False):

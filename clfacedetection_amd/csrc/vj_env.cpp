@@ -1506,6 +1506,7 @@ int vj_env_create(int device_index, vj_env** out) {
     for (hipEvent_t& ev : e->affine_ev) HIP_TRY(hipEventCreate(&ev));
     for (hipEvent_t& ev : e->paint_ev) HIP_TRY(hipEventCreate(&ev));
     for (hipEvent_t& ev : e->yuv_ev) HIP_TRY(hipEventCreate(&ev));
+    for (hipEvent_t& ev : e->track_ev) HIP_TRY(hipEventCreate(&ev));
     HIP_TRY(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
     *out = e.release();
     return VJ_OK;
@@ -1523,7 +1524,7 @@ void vj_env_destroy(vj_env* e) {
                       &e->d_cv_prune_bits, &e->d_pyr, &e->d_pyr_tab, &e->d_cv_big, &e->d_cv_rois, &e->d_cv_roi_units,
                       &e->d_cv_chain, &e->d_cv_chain_keys, &e->d_cv_chain_staged, &e->d_cv_roi_first, &e->d_cv_det2, &e->d_cv_counts2,
                       &e->d_cv_rl_levels, &e->d_cv_rl_taps, &e->d_cv_rl_scales, &e->d_cv_rl_rows, &e->d_cv_rl_table, &e->d_cv_rl_stages,
-                      &e->d_points, &e->d_point_units, &e->d_point_scales, &e->d_point_out, &e->d_atlas, &e->d_atlas_src, &e->d_prep, &e->d_extract, &e->d_yuv})
+                      &e->d_points, &e->d_point_units, &e->d_point_scales, &e->d_point_out, &e->d_atlas, &e->d_atlas_src, &e->d_prep, &e->d_extract, &e->d_yuv, &e->d_track})
         b->release();
     e->lane0.destroy();
     for (DevBuf& b : e->d_q) b.release();
@@ -1543,6 +1544,8 @@ void vj_env_destroy(vj_env* e) {
     for (hipEvent_t& ev : e->paint_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t& ev : e->yuv_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t& ev : e->track_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (e->fork_ev) (void)hipEventDestroy(e->fork_ev);
     if (e->join_ev) (void)hipEventDestroy(e->join_ev);

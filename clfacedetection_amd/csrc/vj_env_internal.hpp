@@ -308,6 +308,11 @@ struct vj_env : vj::Tunables {
     vj::DevBuf d_yuv;
     hipEvent_t yuv_ev[2] = {};
     float yuv_ms = 0;
+    // vj_track (vj_track.cpp): its scratch — the templates, the search patches, the match records (grows, reused);
+    // its slices come through d_extract like vj_extract's —, events around a call [0, 1] and around a match launch [2, 3], their times
+    vj::DevBuf d_track;
+    hipEvent_t track_ev[4] = {};
+    float track_ms = 0, track_match_ms = 0;
     uint64_t plan_tick = 0;
     int cv_tq_shift = 4;              // ... stage trees: the survivors' queue holds 1 / 2^shift of the tile windows (grows on overflow)
 };

@@ -13,6 +13,8 @@ namespace {
 
 inline size_t align16(size_t v) { return (v + 15u) & ~(size_t)15; }
 
+}  // namespace
+
 int enqueue_extract_slice(vj_env* e, const vj_image* frames, const vj_roi* regions, const ExtractLayout& lay, size_t first, size_t n,
                           uint8_t* d_dst, ExtractSlice* sl) {
     int rc;
@@ -72,8 +74,6 @@ int enqueue_extract_slice(vj_env* e, const vj_image* frames, const vj_roi* regio
     }
     return VJ_OK;
 }
-
-}  // namespace
 
 }  // namespace vj
 

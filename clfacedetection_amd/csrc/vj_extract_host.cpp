@@ -111,7 +111,8 @@ int extract_layout(const vj_image* frames, int n_frames, const vj_roi* regions, 
     out->rows = out->planar ? out->C * out->out_h : out->out_h;
     out->row_bytes = out->planar ? out->out_w : out->out_w * out->C;
     out->region_bytes = (uint64_t)out->rows * out->row_bytes;
-    out->bytes = out->region_bytes * (uint64_t)n_regions;
+    out->region_pitch = out->region_bytes;
+    out->bytes = out->region_pitch * (uint64_t)n_regions;
     if (extract_units(out->row_bytes, out->rows) * (uint64_t)n_regions > 0x7fffffffull) {
         set_error("vj_extract: the regions hold more work units than a 32-bit index holds");
         return VJ_ERR_LIMIT;
@@ -161,7 +162,7 @@ int extract_plan_slice(const vj_image* frames, const vj_roi* regions, const Extr
         ExtractRegionDev d;
         memset(&d, 0, sizeof(d));
         d.src = f.data;
-        d.dst_off = (uint64_t)(first + i) * lay.region_bytes;
+        d.dst_off = (uint64_t)(first + i) * lay.region_pitch;
         d.stride = (uint32_t)f.stride;
         d.channels = (uint32_t)(f.channels <= 1 ? 1 : f.channels);
         d.fw = f.width;

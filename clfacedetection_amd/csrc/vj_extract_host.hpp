@@ -16,7 +16,8 @@ struct ExtractLayout {
     bool gray = false, planar = false;
     uint32_t rows = 0, row_bytes = 0;   // of one region's output (vj_extract_units.hpp)
     uint64_t region_bytes = 0;     // rows * row_bytes
-    uint64_t bytes = 0;            // n_regions * region_bytes
+    uint64_t region_pitch = 0;     // bytes from one region's output to the next: region_bytes (vj_track pads it to a multiple of 16)
+    uint64_t bytes = 0;            // n_regions * region_pitch
 };
 // Checks `frames` (vj_detect_mixed's rules), `regions` and `p`, and maps every region.  VJ_ERR_ARG / VJ_ERR_LIMIT with vj_last_error
 // naming the row or the field.
@@ -40,5 +41,12 @@ struct ExtractSlice {
     uint32_t n_units = 0;
 };
 int extract_plan_slice(const vj_image* frames, const vj_roi* regions, const ExtractLayout& lay, size_t first, size_t n, ExtractSlice* out);
+
+// vj_extract.cpp (needs the device): regions [first, first + n) of a checked call as one copy into e->d_extract — records, taps and
+// the host frames they name, staged in the lane's page-locked buffer — and one launch that writes into d_dst, all on e->stream.
+// The caller waits for the stream before the next slice: that one reuses the staging buffer and the device block.  vj_track
+// brings its two patch sets with it.
+int enqueue_extract_slice(vj_env* e, const vj_image* frames, const vj_roi* regions, const ExtractLayout& lay, size_t first, size_t n,
+                          uint8_t* d_dst, ExtractSlice* sl);
 
 }  // namespace vj

@@ -1003,6 +1003,57 @@ int  vj_yuv_luma(const vj_yuv_image* frame, vj_image* out);
 /* Device time of the environment's last vj_yuv_to_bgr or vj_bgr_to_yuv call: events around its copies and launches, in ms.      */
 int  vj_yuv_timing(const vj_env* e, float* ms);
 
+/* ------------------------------------------------- boxes carried from frame to frame, on the device */
+/* A cascade drops a face for a frame or two; every video pipeline bridges that by looking for the box of frame f in frame f +- 1.
+ * vj_track is that search as ONE batched call: block matching of fixed-size gray patches, integer arithmetic only (DESIGN.md
+ * 4.22); parity unpinned, like the other stages around the detector.  For row k = (src_frame, dst_frame, x, y, w, h), with
+ * t = tmpl and r = radius:
+ *   1. T is what vj_extract writes for region (src_frame, x, y, w, h) with out_w = out_h = t, the call's sx, sy, margin = 0 and
+ *      VJ_EXTRACT_GRAY: a t x t gray patch;
+ *   2. S is what vj_extract writes for region (dst_frame, x, y, w, h) with out_w = out_h = t + 2 r, the same sx, sy,
+ *      margin = (double)r / t and VJ_EXTRACT_GRAY: the same box grown by the search radius, at (nearly) the same pixel size.
+ *      (X, Y, Wm, Hm) is its mapped source region, (x0, y0, w0, h0) the mapped region without margin.  The call adds no
+ *      resampling arithmetic of its own: the replicated border, the crop-edge taps and the BGR2GRAY order are vj_extract's;
+ *   3. for dy, dx in -r .. r: sad(dx, dy) = sum over i, j < t of |T[i][j] - S[i + r + dy][j + r + dx]|, integers of at most
+ *      64 * 64 * 255 = 1 044 480;
+ *   4. the best displacement has the smallest tuple (sad, dx * dx + dy * dy, dy, dx), compared lexicographically: on equal sums the
+ *      shorter move wins, then the smaller dy, then the smaller dx — a flat patch stays where it is.  sad0 = sad(0, 0);
+ *   5. the output box: x = x0 + cvRound(dx * (double)Wm / (t + 2 r)), y = y0 + cvRound(dy * (double)Hm / (t + 2 r)), w = w0,
+ *      h = h0 (cvRound: round half to even of the f64 value, as everywhere else).
+ * The two frames of a row may differ in size, stride, channel count and residency; a row may name the same frame twice.         */
+typedef struct vj_track_row { int32_t src_frame, dst_frame, x, y, w, h; } vj_track_row;
+typedef struct vj_track_params {
+    int32_t  tmpl;      /* t: side of the template in patch pixels; a multiple of 4 in 8 .. 64                                */
+    int32_t  radius;    /* r: displacements -r .. r on both axes, in patch pixels; 1 .. 16                                    */
+    double   sx, sy;    /* vj_extract_params' mapping; 0 means 1                                                               */
+    uint32_t flags;     /* none yet: must be 0                                                                                 */
+    uint32_t reserved;  /* must be 0                                                                                           */
+} vj_track_params;
+typedef struct vj_track_result {
+    int32_t  dx, dy;        /* the best displacement, patch pixels                                                             */
+    uint32_t sad, sad0;     /* its sum of absolute differences, and the one at (0, 0)                                          */
+    int32_t  x, y, w, h;    /* the box in dst_frame, in SOURCE pixels (what vj_paint takes with sx = sy = 1)                    */
+} vj_track_result;
+void vj_track_default(vj_track_params* p);                 /* tmpl 32, radius 8, the rest 0 */
+/* Host only, no environment: tmpl_regions[k] = (src_frame, x0, y0, w0, h0) and search_regions[k] = (dst_frame, X, Y, Wm, Hm), the
+ * mapped source regions of T and S (they may lie outside their frames); *scratch_bytes the device scratch of the call run as one
+ * slice: n_rows * t * t bytes of templates, then n_rows search patches of (t + 2 r)^2 bytes, each at a multiple of 16 bytes.
+ * Errors as below.                                                                                                            */
+int  vj_track_layout(const vj_image* frames, int n_frames, const vj_track_row* rows, int n_rows, const vj_track_params* p,
+                     vj_roi* tmpl_regions, vj_roi* search_regions, uint64_t* scratch_bytes);
+/* frames: as vj_extract (host or device-resident, 1 / 3 / 4 channels, any strides, sizes may differ; work of the caller's on
+ * device-resident frames must be complete).  out: n_rows records in HOST memory.  Returns after the work is complete.  All checks
+ * come before the device is used.  VJ_ERR_ARG, with vj_last_error naming the row or the field: the null, frame and region errors of
+ * vj_extract; src_frame or dst_frame out of range; tmpl not a multiple of 4 or outside 8 .. 64; radius outside 1 .. 16; flags or
+ * reserved not 0; negative or non-finite sx, sy.  VJ_ERR_LIMIT: vj_extract's mapping limits.  VJ_ERR_NOMEM names the bytes.
+ * n_rows == 0 is VJ_OK.  With "max_subbatch" configured a call runs in slices of rows that name at most that many frames (a
+ * row that names more by itself is a slice of its own); the results are the same.                                              */
+int  vj_track(vj_env* e, const vj_image* frames, int n_frames, const vj_track_row* rows, int n_rows,
+              const vj_track_params* p, vj_track_result* out);
+/* Device time of the environment's last vj_track call: events around its copies and launches (*ms), and around its match launches
+ * alone (*match_ms; their sum when the call ran in slices), in ms.  A null argument: VJ_ERR_ARG.                              */
+int  vj_track_timing(const vj_env* e, float* ms, float* match_ms);
+
 /* ------------------------------------------------------------ frame streams */
 /* Video-style use (the demo's per-frame loop, main.cpp:104-125): batches of host frames are uploaded into
  * one of two device buffers by DMA on a copy stream while the kernels of the previous batch run, and the
