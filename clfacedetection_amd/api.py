@@ -358,6 +358,10 @@ _SIGNATURES = {
                                 C.POINTER(_YuvImage)]),
     "vj_yuv_luma": (C.c_int, [C.POINTER(_YuvImage), C.POINTER(_Image)]),
     "vj_yuv_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "vj_paint_yuv_layout": (C.c_int, [C.POINTER(_YuvImage), C.c_int, C.c_void_p, C.c_int, C.POINTER(PaintParams), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "vj_paint_yuv": (C.c_int, [C.c_void_p, C.POINTER(_YuvImage), C.c_int, C.c_void_p, C.c_int, C.POINTER(PaintParams)]),
+    "vj_paint_yuv_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vj_track_default": (None, [C.POINTER(TrackParams)]),
     "vj_track_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(TrackParams), C.c_void_p, C.c_void_p,
                                   C.POINTER(C.c_uint64)]),
@@ -1202,6 +1206,81 @@ class Environment:
         return float(ms.value)
 
     @staticmethod
+    def _paint_yuv_args(frames, rects, mode, size, rel, scale, margin, ellipse, fill, layout):
+        """-> (ctypes array of vj_yuv_image, n, objects to keep alive, (n, 5) int32 rows, vj_paint_params).  frames: a YuvFrames; a
+        uint8 CUDA tensor of stacked (n, h * 3 // 2, w) frames (YuvFrames.from_torch with `layout`); a writeable uint8 numpy array of
+        stacked frames, (n, h * 3 // 2, w) or one (h * 3 // 2, w); a tuple of a frame's planes; or a list of these.  The frames are
+        painted IN PLACE: an array the call would have to copy (read-only, rows whose bytes are not contiguous, stacked i420 frames
+        whose rows do not follow each other) is a ValueError."""
+        def is_tensor(f):
+            return not isinstance(f, (np.ndarray, YuvFrames, tuple)) and hasattr(f, "data_ptr") and hasattr(f, "is_cuda")
+
+        lay = Environment._yuv_layout_id(layout)
+
+        def host(a, stacked):
+            if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+                raise ValueError("paint_yuv() writes into its frames: a host frame must be a uint8 numpy array (no copy is made)")
+            if not a.flags.writeable:
+                raise ValueError("paint_yuv() writes into its frames: a read-only array cannot be painted (no copy is made)")
+            if a.ndim < 2 or a.strides[-1] != 1 or a.strides[-2] <= 0 or (stacked and lay == VJ_YUV_I420 and a.strides[-2] != a.shape[-1]):
+                raise ValueError("paint_yuv() writes into its frames: the bytes of a row must be contiguous, and the rows of a stacked "
+                                 "i420 frame must follow each other (no copy is made)")
+            return a
+
+        flat = []
+        for f in (frames if isinstance(frames, list) else [frames]):
+            if is_tensor(f):
+                if not f.is_cuda or f.dtype.itemsize != 1:
+                    raise ValueError("a tensor frame must be a uint8 CUDA tensor")
+                f = YuvFrames.from_torch(f if f.dim() == 3 else f[None], lay)
+            elif isinstance(f, tuple):
+                f = tuple(host(a, False) for a in f)
+            elif not isinstance(f, YuvFrames):
+                f = host(f, True)
+            flat.append(f)
+        imgs, n, keep = Environment._yuv_images(flat, lay)
+        _, _, _, _, r, p = Environment._paint_args(np.zeros((2, 2), np.uint8), rects, mode, size, rel, scale, margin, ellipse, 0, False)
+        fill = tuple(int(v) for v in (fill if np.ndim(fill) else (fill,) * 3))
+        if len(fill) > 3 or any(not 0 <= v <= 255 for v in fill):
+            raise ValueError("fill: up to three values of 0 .. 255: B, G, R")
+        for c, v in enumerate(fill + (0,) * (3 - len(fill))):
+            p.color[c] = v
+        return imgs, n, keep + flat, r, p
+
+    @staticmethod
+    def paint_yuv_layout(frames, rects, mode="blur", size: int = 0, rel: float = 0.25, scale=(1.0, 1.0), margin: float = 0.0,
+                         ellipse: bool = False, layout="nv12"):
+        """vj_paint_yuv_layout (host only): what paint_yuv() will touch -> ((n, 5) int32 rows of K (frame, x, y, w, h) in luma pixels;
+        (n, 5) rows of Kc in chroma samples — w = h = 0 where nothing is painted; (n,) int32 luma sizes and (n,) chroma sizes — the
+        thickness, the cell side or the blur's kernel side, 0 for "fill"; the scratch bytes of the call run as one slice)."""
+        imgs, n, keep, r, p = Environment._paint_yuv_args(frames, rects, mode, size, rel, scale, margin, ellipse, 0, layout)
+        clipped, chroma = np.zeros((len(r), 5), np.int32), np.zeros((len(r), 5), np.int32)
+        sizes, csizes = np.zeros(len(r), np.int32), np.zeros(len(r), np.int32)
+        nbytes = C.c_uint64(0)
+        _check(load_library().vj_paint_yuv_layout(imgs, n, r.ctypes.data, len(r), C.byref(p), clipped.ctypes.data, chroma.ctypes.data,
+                                                  sizes.ctypes.data, csizes.ctypes.data, C.byref(nbytes)), "vj_paint_yuv_layout")
+        return clipped, chroma, sizes, csizes, int(nbytes.value)
+
+    def paint_yuv(self, frames, rects, mode="blur", size: int = 0, rel: float = 0.25, scale=(1.0, 1.0), margin: float = 0.0,
+                  ellipse: bool = False, fill=(0, 0, 0), layout="nv12"):
+        """vj_paint_yuv: rectangles painted into NV12 / NV21 / I420 frames IN PLACE, on the device, without the BGR copy (DESIGN.md
+        §4.23).  rects are in luma pixels; mode, size, rel, scale, margin, ellipse: as paint().  fill: B, G, R, converted once to
+        (Y, U, V).  The Y plane becomes what paint() makes of it as a gray frame; a chroma sample is painted when any of its four luma
+        pixels is, with halved sizes.  layout: of tensors and host arrays (a YuvFrames carries its own).  frames: see
+        _paint_yuv_args — device frames are painted where they lie, host arrays through a staged copy of the touched rows.
+        Returns `frames`."""
+        imgs, n, keep, r, p = self._paint_yuv_args(frames, rects, mode, size, rel, scale, margin, ellipse, fill, layout)
+        _order_after_torch(self._device)       # work queued on the frames (a decoder, a copy_) has written them before they are painted
+        _check(load_library().vj_paint_yuv(self._h, imgs, n, r.ctypes.data, len(r), C.byref(p)), "vj_paint_yuv")
+        return frames
+
+    def paint_yuv_timing(self) -> float:
+        """vj_paint_yuv_timing: device time of the last paint_yuv() call (events around its copies and launches), ms."""
+        ms = C.c_float(0)
+        _check(load_library().vj_paint_yuv_timing(self._h, C.byref(ms)), "vj_paint_yuv_timing")
+        return float(ms.value)
+
+    @staticmethod
     def _track_args(frames, rows, tmpl, radius, scale, color):
         """-> (ctypes array of vj_image, n, objects to keep alive, (n, 6) int32 rows, vj_track_params).  frames: as paint() takes them
         (_paint_images), read-only arrays included; rows: integer rows of (src_frame, dst_frame, x, y, w, h)."""
@@ -1661,6 +1740,13 @@ def paint_layout(frames, rects, mode="blur", size: int = 0, rel: float = 0.25, s
     """vj_paint_layout: the host-only twin of Environment.paint (no environment, no device) ->
     (clipped rectangles as (n, 5) int32 rows, sizes as (n,) int32, scratch bytes)."""
     return Environment.paint_layout(frames, rects, mode, size, rel, scale, margin, ellipse, color)
+
+
+def paint_yuv_layout(frames, rects, mode="blur", size: int = 0, rel: float = 0.25, scale=(1.0, 1.0), margin: float = 0.0,
+                     ellipse: bool = False, layout="nv12"):
+    """vj_paint_yuv_layout: the host-only twin of Environment.paint_yuv (no environment, no device) ->
+    (K rows, Kc rows, luma sizes, chroma sizes, scratch bytes)."""
+    return Environment.paint_yuv_layout(frames, rects, mode, size, rel, scale, margin, ellipse, layout)
 
 
 def track_layout(frames, rows, tmpl: int = 32, radius: int = 8, scale=(1.0, 1.0), color: bool = False):

@@ -303,6 +303,8 @@ struct vj_env : vj::Tunables {
     // vj_paint (vj_paint.cpp) brings its slices in d_extract too, with its scratch behind them; its own events and time
     hipEvent_t paint_ev[2] = {};
     float paint_ms = 0;
+    // vj_paint_yuv (vj_paint_yuv.cpp) shares the block and the events (calls on an environment do not overlap)
+    float paint_yuv_ms = 0;
     // vj_yuv_to_bgr / vj_bgr_to_yuv (vj_yuv.cpp): the block one copy brings per slice — frame records, then the planes
     // of the slice's host frames at a 4-byte pitch (grows, reused) —, events around a call's copies and launches (vj_yuv_timing)
     vj::DevBuf d_yuv;

@@ -958,7 +958,9 @@ int  vj_paint_timing(const vj_env* e, float* ms);
 enum { VJ_YUV_NV12 = 0, VJ_YUV_NV21 = 1, VJ_YUV_I420 = 2 };   /* vj_yuv_image.layout                                           */
 enum { VJ_YUV_RGB_ORDER = 1u << 0 };                          /* vj_yuv_params.flags: the BGR side is RGB / RGBA (R and B swapped) */
 typedef struct vj_yuv_image {
-    const uint8_t* y;          /* the Y plane: height rows of width bytes, y_stride bytes apart                                  */
+    const uint8_t* y;          /* the Y plane: height rows of width bytes, y_stride bytes apart.  The planes are read only by every
+                                  entry point but vj_paint_yuv, which WRITES the painted samples through all three pointers (the
+                                  memory must be writable)                                                                       */
     const uint8_t* c0;         /* NV12 / NV21: the pair plane, height / 2 rows of width bytes; I420: the U plane, height / 2 rows
                                   of width / 2 bytes.  Rows c_stride bytes apart                                                 */
     const uint8_t* c1;         /* I420: the V plane (c_stride too); NV12 / NV21: ignored                                         */
@@ -1002,6 +1004,52 @@ int  vj_bgr_to_yuv(vj_env* e, const vj_image* frames, int n_frames, const vj_yuv
 int  vj_yuv_luma(const vj_yuv_image* frame, vj_image* out);
 /* Device time of the environment's last vj_yuv_to_bgr or vj_bgr_to_yuv call: events around its copies and launches, in ms.      */
 int  vj_yuv_timing(const vj_env* e, float* ms);
+
+/* ------------------------------------------------- rectangles painted into 4:2:0 frames where they lie, on the device */
+/* Redaction between a decoder and an encoder: vj_paint on the BGR copy re-quantizes the whole picture on the way back
+ * (vj_bgr_to_yuv of vj_yuv_to_bgr is not the identity) and needs a copy twice the frames' size.  vj_paint_yuv paints the rectangles
+ * into NV12 / NV21 / I420 frames IN PLACE, as ONE batched call; parity is unpinned, the definition here and in
+ * DESIGN.md 4.23 is authoritative.  regions are in LUMA pixels; p is vj_paint's struct: the same modes, VJ_PAINT_ELLIPSE, sx, sy,
+ * margin, size, rel.
+ *   Colour.  FILL, OUTLINE: color[0..2] are B, G, R, color[3] is ignored; the host converts them once with the encode formulas
+ *     above to (Yc, Uc, Vc).
+ *   Luma.  The Y plane after the call is exactly what vj_paint (items 1 to 6 above) makes of it as a one-channel frame with
+ *     color[0] = Yc.  M, K = [cx0, cx1) x [cy0, cy1), s, the shape and the painted set P_k are that definition's.
+ *   Chroma.  The chroma image is W/2 x H/2 with two components, U and V — interleaved in either order (NV12 / NV21) or two planes
+ *     (I420); both are treated alike.  For region k with a non-empty K:
+ *     - Kc = [cx0 >> 1, (cx1 + 1) >> 1) x [cy0 >> 1, (cy1 + 1) >> 1): the chroma samples that K touches.
+ *     - The painted chroma set Pc_k: sample (u, v) of Kc is in it iff at least one of the four luma pixels (2u + a, 2v + b),
+ *       a, b in {0, 1}, is in P_k — "any of four", so that no painted luma pixel keeps its original chroma.  The price: a luma pixel
+ *       just outside K (or outside the ellipse, or inside the outline) may keep its Y and take new chroma.
+ *     - Sizes: PIXELATE sc = (s + 1) >> 1; BLUR kkc = max((kk >> 1) | 1, 3), rc = kkc >> 1.
+ *     - Values, from the chroma image AS IT WAS BEFORE THE CALL, per component: FILL, OUTLINE: Uc, Vc.  PIXELATE, BLUR: item 5 of
+ *       vj_paint with Kc for K, sc for s and kkc for kk: cells anchored at Kc's corner and clipped to Kc, taps clamped to Kc, the
+ *       same rounding and flooring.  A region reads only chroma samples of its own Kc.
+ *     - A chroma sample in several Pc_k of one frame takes the value of the HIGHEST-INDEX region among them.  Two regions whose K
+ *       are disjoint can share a chroma sample (x ranges [2, 7) and [7, 12) share sample 3): overlap is decided on Kc, not on K.
+ *   Bytes of chroma samples in no Pc_k, and luma bytes in no P_k, are never written on device frames.                             */
+/* Host only, no environment: clipped[k] is K of region k and chroma[k] its Kc, in chroma samples (w = h = 0 when K is empty);
+ * sizes[k] its t, s or kk (0 for FILL) and chroma_sizes[k] its t, sc or kkc; *scratch_bytes what the phase between reading and
+ * writing the planes keeps of the call run as one slice: per region with a K, vj_paint_layout's bytes of the Y plane (one channel,
+ * K, the luma size) plus twice those of one chroma component (one channel, Kc, the chroma size), each rounded up to 16.  Errors as
+ * vj_paint_yuv's.                                                                                                                */
+int  vj_paint_yuv_layout(const vj_yuv_image* frames, int n_frames, const vj_roi* regions, int n_regions, const vj_paint_params* p,
+                         vj_roi* clipped, vj_roi* chroma, int32_t* sizes, int32_t* chroma_sizes, uint64_t* scratch_bytes);
+/* frames: as vj_yuv_to_bgr takes them — host or device-resident, any strides, any addresses, sizes and layouts may differ — and
+ * the call WRITES through the planes' pointers: nothing else may read or write the frames until it returns, and all work of the
+ * caller's on device-resident frames must be complete before it.  Device frames: only the bytes of painted samples are stored.
+ * Host frames, per plane as vj_paint's host frames: the painted samples change; other bytes of the rectangle's span (K, Kc) of a
+ * touched row may be rewritten with their own values; a row's padding and rows outside the rectangle are never written.  Returns
+ * after the work is complete.
+ * All checks come before the device is used.  VJ_ERR_ARG, with vj_last_error naming the frame, the row or the field: null
+ * arguments; the frame errors of vj_yuv_to_bgr (a null plane that the layout needs, odd or non-positive sizes, a stride below the
+ * plane's row bytes, an unknown layout); the region and parameter errors of vj_paint; any two planes of the call whose byte
+ * extents overlap, planes of the same frame included.  VJ_ERR_LIMIT: vj_paint's limits; a side above 65534.  VJ_ERR_NOMEM names the
+ * bytes.  n_regions == 0 is VJ_OK; a region whose K is empty paints nothing.  With "max_subbatch" configured a call runs in slices
+ * of whole frames, at most that many each.                                                                                       */
+int  vj_paint_yuv(vj_env* e, const vj_yuv_image* frames, int n_frames, const vj_roi* regions, int n_regions, const vj_paint_params* p);
+/* Device time of the environment's last vj_paint_yuv call: events around its copies and launches, in ms.  A null argument: VJ_ERR_ARG. */
+int  vj_paint_yuv_timing(const vj_env* e, float* ms);
 
 /* ------------------------------------------------- boxes carried from frame to frame, on the device */
 /* A cascade drops a face for a frame or two; every video pipeline bridges that by looking for the box of frame f in frame f +- 1.
