@@ -21,7 +21,7 @@
 #include <string>
 #include <tuple>
 
-#include "vj_env_internal.hpp"
+#include "vj_slice.hpp"
 #include "vj_grid_parts.hpp"
 #include "vj_atlas_units.hpp"
 
@@ -370,7 +370,7 @@ int ensure_image_buffers(vj_env* e, int W, int H, int frames, bool need_gray, in
     if ((rc = e->d_sqsum.ensure(sq_bytes))) return rc;
     (void)grow;
     if (need_gray) {
-        const size_t gstride = ((size_t)W * (size_t)channels + 3) & ~(size_t)3;
+        const size_t gstride = align4((size_t)W * (size_t)channels);
         if ((rc = lane->d_gray.ensure(gstride * (size_t)H * (size_t)frames))) return rc;
     }
     const size_t band_elems = (size_t)frames * n_bands * band_pitch;
@@ -463,6 +463,16 @@ int enqueue_tilted(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int str
 // aligned pitch.  Returns the device pointer / pitch the integral kernels should use.
 int image_channels(const vj_image& im) { return im.channels <= 1 ? 1 : im.channels; }
 
+int stage_reserve(Lane* lane, size_t bytes) {
+    if (lane->h_stage_bytes >= bytes) return VJ_OK;
+    if (lane->h_stage) (void)hipHostFree(lane->h_stage);
+    lane->h_stage = nullptr;
+    lane->h_stage_bytes = 0;
+    HIP_TRY(hipHostMalloc(&lane->h_stage, bytes, hipHostMallocDefault));
+    lane->h_stage_bytes = bytes;
+    return VJ_OK;
+}
+
 int stage_frames(vj_env* e, const vj_image* frames, int n, int W, int H, const uint8_t** d_ptr, size_t* frame_bytes,
                  int* stride, Lane* lane, hipStream_t copy_stream) {
     if (!lane) lane = &e->lane0;
@@ -481,7 +491,7 @@ int stage_frames(vj_env* e, const vj_image* frames, int n, int W, int H, const u
         *frame_bytes = (size_t)frames[0].stride * (size_t)H;
         return VJ_OK;
     }
-    const size_t gstride = (row_bytes + 3) & ~(size_t)3;
+    const size_t gstride = align4(row_bytes);
     bool all_host = true;
     for (int i = 0; i < n; ++i) all_host = all_host && !frames[i].on_device;
     if (all_host && contiguous && (size_t)frames[0].stride == gstride && n > 1) {
@@ -494,13 +504,7 @@ int stage_frames(vj_env* e, const vj_image* frames, int n, int W, int H, const u
             const bool pinned = hipPointerGetAttributes(&at, src) == hipSuccess && at.type == hipMemoryTypeHost;
             if (!pinned) {
                 (void)hipGetLastError();
-                if (lane->h_stage_bytes < bytes) {
-                    if (lane->h_stage) (void)hipHostFree(lane->h_stage);
-                    lane->h_stage = nullptr;
-                    lane->h_stage_bytes = 0;
-                    HIP_TRY(hipHostMalloc(&lane->h_stage, bytes, hipHostMallocDefault));
-                    lane->h_stage_bytes = bytes;
-                }
+                if (const int err = stage_reserve(lane, bytes)) return err;
                 memcpy(lane->h_stage, src, bytes);
                 src = lane->h_stage;
             }
@@ -515,13 +519,7 @@ int stage_frames(vj_env* e, const vj_image* frames, int n, int W, int H, const u
         // many small frames in separate host buffers: gather them in the page-locked staging buffer (at the device's pitch)
         // and send one block — a copy call per frame costs more than copying a few KB twice
         const size_t fb = gstride * (size_t)H, bytes = fb * (size_t)n;
-        if (lane->h_stage_bytes < bytes) {
-            if (lane->h_stage) (void)hipHostFree(lane->h_stage);
-            lane->h_stage = nullptr;
-            lane->h_stage_bytes = 0;
-            HIP_TRY(hipHostMalloc(&lane->h_stage, bytes, hipHostMallocDefault));
-            lane->h_stage_bytes = bytes;
-        }
+        if (const int err = stage_reserve(lane, bytes)) return err;
         for (int i = 0; i < n; ++i) {
             uint8_t* st = (uint8_t*)lane->h_stage + (size_t)i * fb;
             if ((size_t)frames[i].stride == gstride) memcpy(st, frames[i].data, fb);
@@ -549,13 +547,7 @@ int stage_frames(vj_env* e, const vj_image* frames, int n, int W, int H, const u
             if (!pinned) {
                 (void)hipGetLastError();
                 const size_t need = gstride * (size_t)H * (size_t)n;
-                if (lane->h_stage_bytes < need) {
-                    if (lane->h_stage) (void)hipHostFree(lane->h_stage);
-                    lane->h_stage = nullptr;
-                    lane->h_stage_bytes = 0;
-                    HIP_TRY(hipHostMalloc(&lane->h_stage, need, hipHostMallocDefault));
-                    lane->h_stage_bytes = need;
-                }
+                if (const int err = stage_reserve(lane, need)) return err;
                 uint8_t* st = (uint8_t*)lane->h_stage + (size_t)i * gstride * (size_t)H;
                 for (int y = 0; y < H; ++y) memcpy(st + (size_t)y * gstride, src + (size_t)y * src_stride, row_bytes);
                 src = st;
@@ -1501,11 +1493,7 @@ int vj_env_create(int device_index, vj_env** out) {
     for (hipEvent_t& ev : e->cv_chain_ev) HIP_TRY(hipEventCreate(&ev));
     for (hipEvent_t& ev : e->cv_rois_ev) HIP_TRY(hipEventCreate(&ev));
     for (hipEvent_t& ev : e->atlas_ev) HIP_TRY(hipEventCreate(&ev));
-    for (hipEvent_t& ev : e->prep_ev) HIP_TRY(hipEventCreate(&ev));
-    for (hipEvent_t& ev : e->extract_ev) HIP_TRY(hipEventCreate(&ev));
-    for (hipEvent_t& ev : e->affine_ev) HIP_TRY(hipEventCreate(&ev));
-    for (hipEvent_t& ev : e->paint_ev) HIP_TRY(hipEventCreate(&ev));
-    for (hipEvent_t& ev : e->yuv_ev) HIP_TRY(hipEventCreate(&ev));
+    for (hipEvent_t& ev : e->call_ev) HIP_TRY(hipEventCreate(&ev));
     for (hipEvent_t& ev : e->track_ev) HIP_TRY(hipEventCreate(&ev));
     HIP_TRY(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
     *out = e.release();
@@ -1535,15 +1523,7 @@ void vj_env_destroy(vj_env* e) {
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t& ev : e->atlas_ev)
         if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t& ev : e->prep_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t& ev : e->extract_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t& ev : e->affine_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t& ev : e->paint_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t& ev : e->yuv_ev)
+    for (hipEvent_t& ev : e->call_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t& ev : e->track_ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -1963,7 +1943,7 @@ int vj_grayscale(vj_env* e, const vj_image* image, uint8_t* gray, int gray_strid
     size_t fb;
     int gs;
     if ((rc = stage_frames(e, image, 1, w, h, &d_src, &fb, &gs))) return rc;
-    const size_t pitch = ((size_t)w + 3) & ~(size_t)3;
+    const size_t pitch = align4((size_t)w);
     if ((rc = e->d_out.ensure(pitch * (size_t)h))) return rc;
     TiltedArgs ta;
     memset(&ta, 0, sizeof(ta));
@@ -1990,13 +1970,7 @@ int vj_grayscale(vj_env* e, const vj_image* image, uint8_t* gray, int gray_strid
     // memory goes row by row in the runtime)
     Lane* L = &e->lane0;
     const size_t need = pitch * (size_t)h;
-    if (L->h_stage_bytes < need) {
-        if (L->h_stage) (void)hipHostFree(L->h_stage);
-        L->h_stage = nullptr;
-        L->h_stage_bytes = 0;
-        HIP_TRY(hipHostMalloc(&L->h_stage, need, hipHostMallocDefault));
-        L->h_stage_bytes = need;
-    }
+    if (const int err = stage_reserve(L, need)) return err;
     HIP_TRY(hipMemcpyAsync(L->h_stage, e->d_out.p, need, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     for (int y = 0; y < h; ++y) memcpy(gray + (size_t)y * (size_t)gray_stride, (const uint8_t*)L->h_stage + (size_t)y * pitch, (size_t)w);
@@ -2018,13 +1992,7 @@ int vj_equalize_hist(vj_env* e, const vj_image* image, uint8_t* dst, int dst_str
     if ((rc = enqueue_equalize(e, L, &d_src, &fb, &gs, &ch, w, h, 1))) return rc;
     // one block into page-locked memory, the rows from there (as vj_grayscale returns a strided image)
     const size_t pitch = (size_t)gs, need = pitch * (size_t)h;
-    if (L->h_stage_bytes < need) {
-        if (L->h_stage) (void)hipHostFree(L->h_stage);
-        L->h_stage = nullptr;
-        L->h_stage_bytes = 0;
-        HIP_TRY(hipHostMalloc(&L->h_stage, need, hipHostMallocDefault));
-        L->h_stage_bytes = need;
-    }
+    if (const int err = stage_reserve(L, need)) return err;
     HIP_TRY(hipMemcpyAsync(L->h_stage, d_src, need, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     for (int y = 0; y < h; ++y) memcpy(dst + (size_t)y * (size_t)dst_stride, (const uint8_t*)L->h_stage + (size_t)y * pitch, (size_t)w);

@@ -286,30 +286,17 @@ struct vj_env : vj::Tunables {
     vj::DevBuf d_atlas, d_atlas_src;
     hipEvent_t atlas_ev[2] = {};
     vj_mixed_info mixed_info = {};          // the last mixed call (vj_mixed_info_get)
-    // vj_preprocess (vj_preprocess.cpp): the block one copy brings per slice — frame records, the records equalize_lut reads,
-    // taps, then the slice's host frames at a 4-byte pitch (grows, reused; histograms and tables: lane0's d_eq_hist / d_eq_lut) —,
-    // events around a call's copies and launches and their time (vj_preprocess_timing)
-    vj::DevBuf d_prep;
-    hipEvent_t prep_ev[2] = {};
-    float prep_ms = 0;
-    // vj_extract (vj_extract.cpp): the block one copy brings per slice — region records, taps, then the slice's host
-    // frames at a 4-byte pitch (grows, reused) —, events around a call's copies and launches and their time (vj_extract_timing)
-    vj::DevBuf d_extract;
-    hipEvent_t extract_ev[2] = {};
-    float extract_ms = 0;
-    // vj_extract_affine (vj_extract_affine.cpp) brings its slices in d_extract too; its own events and time
-    hipEvent_t affine_ev[2] = {};
-    float affine_ms = 0;
-    // vj_paint (vj_paint.cpp) brings its slices in d_extract too, with its scratch behind them; its own events and time
-    hipEvent_t paint_ev[2] = {};
-    float paint_ms = 0;
-    // vj_paint_yuv (vj_paint_yuv.cpp) shares the block and the events (calls on an environment do not overlap)
-    float paint_yuv_ms = 0;
-    // vj_yuv_to_bgr / vj_bgr_to_yuv (vj_yuv.cpp): the block one copy brings per slice — frame records, then the planes
-    // of the slice's host frames at a 4-byte pitch (grows, reused) —, events around a call's copies and launches (vj_yuv_timing)
-    vj::DevBuf d_yuv;
-    hipEvent_t yuv_ev[2] = {};
-    float yuv_ms = 0;
+    // The frame-processing calls (vj_slice.hpp): a call brings each of its slices in one block that grows and is reused —
+    // records, taps or lists, then the slice's host frames at a 4-byte pitch through lane0's h_stage —, and has finished with it when
+    // it returns.  Calls on an environment do not overlap, so ONE pair of events lies around the copies and launches of whichever
+    // call runs; every entry point keeps the time of its last call (vj_*_timing).
+    hipEvent_t call_ev[2] = {};
+    vj::DevBuf d_prep;      // vj_preprocess (§4.16): [frame records | the records equalize_lut reads | taps | frames]; histograms
+                            // and tables: lane0's d_eq_hist / d_eq_lut
+    vj::DevBuf d_extract;   // vj_extract (§4.17): [region records | taps | frames]; vj_extract_affine (§4.19): [region records | frames];
+                            // vj_paint (§4.20) and vj_paint_yuv (§4.23): [records | overlap lists | touched rows | scratch]
+    vj::DevBuf d_yuv;       // vj_yuv_to_bgr / vj_bgr_to_yuv (§4.21): [frame records | planes]
+    float prep_ms = 0, extract_ms = 0, affine_ms = 0, paint_ms = 0, paint_yuv_ms = 0, yuv_ms = 0;
     // vj_track (vj_track.cpp): its scratch — the templates, the search patches, the match records (grows, reused);
     // its slices come through d_extract like vj_extract's —, events around a call [0, 1] and around a match launch [2, 3], their times
     vj::DevBuf d_track;

@@ -3,7 +3,7 @@
 // an atlas is packed on the device by one launch (vj_atlas.hip) and handed, as ONE device-resident gray frame with one region per
 // frame, to the region entry point of the profile — vj_detect_opencv_rois / vj_detect_rois, whose contract ("what the batched call
 // returns for the region as a sub-image") is this call's definition.  Both profiles run through one driver.
-#include "vj_env_internal.hpp"
+#include "vj_slice.hpp"
 #include "vj_atlas_host.hpp"
 
 #include <functional>
@@ -23,23 +23,18 @@ int enqueue_atlas_pack(vj_env* e, const vj_image* frames, const AtlasPlan& pl, b
     const size_t atlas_bytes = (size_t)pl.pitch * (size_t)pl.h;
     if ((rc = e->d_atlas.ensure(atlas_bytes))) return rc;
     if (clear) HIP_TRY(hipMemsetAsync(e->d_atlas.p, 0, atlas_bytes, e->stream));
-    const size_t rec_bytes = (n * sizeof(AtlasFrameDev) + 15u) & ~(size_t)15;
-    size_t bytes = rec_bytes;
+    StageBlock head;
+    head.section(n * sizeof(AtlasFrameDev));
+    StageBlock b = head;
     for (const AtlasSlot& s : pl.slots) {
         const vj_image& f = frames[s.frame];
-        if (!f.on_device) bytes += (((size_t)s.w * (size_t)image_channels(f) + 3u) & ~(size_t)3) * (size_t)s.h;
+        if (!f.on_device) b.rows((size_t)s.w * (size_t)image_channels(f), (size_t)s.h);
     }
     Lane* L = &e->lane0;
-    if (L->h_stage_bytes < bytes) {
-        if (L->h_stage) (void)hipHostFree(L->h_stage);
-        L->h_stage = nullptr;
-        L->h_stage_bytes = 0;
-        HIP_TRY(hipHostMalloc(&L->h_stage, bytes, hipHostMallocDefault));
-        L->h_stage_bytes = bytes;
-    }
-    if ((rc = e->d_atlas_src.ensure(bytes))) return rc;
+    if ((rc = stage_reserve(L, b.bytes))) return rc;
+    if ((rc = e->d_atlas_src.ensure(b.bytes))) return rc;
     AtlasFrameDev* recs = (AtlasFrameDev*)L->h_stage;
-    size_t at = rec_bytes;
+    b = head;
     uint32_t hist_units = 0;
     for (size_t i = 0; i < n; ++i) {
         const AtlasSlot& s = pl.slots[i];
@@ -54,15 +49,12 @@ int enqueue_atlas_pack(vj_env* e, const vj_image* frames, const AtlasPlan& pl, b
         d = AtlasFrameDev{f.data, (uint32_t)f.stride, ch, s.w, s.h, s.ox, s.oy, s.unit_first, equalize ? hist_units : 0u};
         hist_units += eq_hist_units(s.h);   // (an atlas is lower than 65535 rows)
         if (!f.on_device) {
-            const size_t row_bytes = (size_t)s.w * ch, pitch = (row_bytes + 3u) & ~(size_t)3;
-            uint8_t* st = (uint8_t*)L->h_stage + at;
-            for (uint32_t y = 0; y < s.h; ++y) memcpy(st + (size_t)y * pitch, f.data + (size_t)y * (size_t)f.stride, row_bytes);
-            d.src = (const uint8_t*)e->d_atlas_src.p + at;
-            d.stride = (uint32_t)pitch;
-            at += pitch * (size_t)s.h;
+            const size_t row_bytes = (size_t)s.w * ch;
+            d.src = (const uint8_t*)e->d_atlas_src.p + stage_rows((uint8_t*)L->h_stage, &b, f.data, (size_t)f.stride, (size_t)s.h, row_bytes);
+            d.stride = (uint32_t)align4(row_bytes);
         }
     }
-    HIP_TRY(hipMemcpyAsync(e->d_atlas_src.p, L->h_stage, bytes, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_atlas_src.p, L->h_stage, b.bytes, hipMemcpyHostToDevice, e->stream));
     AtlasPackArgs a{(const AtlasFrameDev*)e->d_atlas_src.p, (uint32_t)n, pl.n_units, (uint8_t*)e->d_atlas.p, pl.pitch, pl.w, pl.h, nullptr};
     HIP_TRY(hipEventRecord(e->atlas_ev[0], e->stream));
     if (equalize && (rc = enqueue_equalize_tables(e, L, e->d_atlas_src.p, (uint32_t)n, hist_units, &a.lut))) return rc;

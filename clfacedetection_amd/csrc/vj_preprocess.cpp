@@ -1,57 +1,49 @@
 // vj_preprocess: gray, resized, equalized frames written into a device buffer of the caller's.  The planner
 // (vj_prep_host.cpp) checks the call and lays the images out; here a slice of the call — all of it unless "max_subbatch" is set —
 // is one copy (its frame records, the records equalize_lut reads, its taps and its host frames, gathered at a 4-byte pitch in the
-// lane's page-locked staging buffer as vj_detect_mixed stages its atlas sources), one memset of the histograms, and the launches.
-#include "vj_env_internal.hpp"
+// lane's page-locked staging buffer), one memset of the histograms, and the launches.  The call's skeleton is the shared one
+// (vj_slice.hpp, §4.24).
+#include "vj_slice.hpp"
 #include "vj_prep_host.hpp"
 
 namespace vj {
 
 namespace {
 
-inline size_t align16(size_t v) { return (v + 15u) & ~(size_t)15; }
-
 int enqueue_prep_slice(vj_env* e, const vj_image* frames, const PrepLayout& lay, size_t first, size_t n, uint8_t* d_dst, PrepSlice* sl) {
     int rc;
     if ((rc = prep_plan_slice(frames, lay, first, n, sl))) return rc;
-    const size_t rec_bytes = align16(n * sizeof(PrepFrameDev)), eq_bytes = align16(n * sizeof(AtlasFrameDev));
-    const size_t tap_bytes = align16(sl->taps.size() * sizeof(PyrTap));
-    size_t bytes = rec_bytes + eq_bytes + tap_bytes;
+    StageBlock head;
+    head.section(n * sizeof(PrepFrameDev));
+    const size_t eq_at = head.section(n * sizeof(AtlasFrameDev)), tap_at = head.section(sl->taps.size() * sizeof(PyrTap));
+    StageBlock b = head;
     for (size_t i = 0; i < n; ++i) {
         const vj_image& f = frames[first + i];
-        if (!f.on_device) bytes += (((size_t)f.width * (size_t)image_channels(f) + 3u) & ~(size_t)3) * (size_t)f.height;
+        if (!f.on_device) b.rows((size_t)f.width * (size_t)image_channels(f), (size_t)f.height);
     }
     Lane* L = &e->lane0;
-    if (L->h_stage_bytes < bytes) {
-        if (L->h_stage) (void)hipHostFree(L->h_stage);
-        L->h_stage = nullptr;
-        L->h_stage_bytes = 0;
-        HIP_TRY(hipHostMalloc(&L->h_stage, bytes, hipHostMallocDefault));
-        L->h_stage_bytes = bytes;
-    }
-    if ((rc = e->d_prep.ensure(bytes))) return rc;
+    if ((rc = stage_reserve(L, b.bytes))) return rc;
+    if ((rc = e->d_prep.ensure(b.bytes))) return rc;
     uint8_t* hs = (uint8_t*)L->h_stage;
     const uint8_t* dev = (const uint8_t*)e->d_prep.p;
-    size_t at = rec_bytes + eq_bytes + tap_bytes;
+    b = head;
     for (size_t i = 0; i < n; ++i) {
         const vj_image& f = frames[first + i];
         if (f.on_device) continue;
-        const size_t row_bytes = (size_t)f.width * (size_t)image_channels(f), pitch = (row_bytes + 3u) & ~(size_t)3;
-        for (int y = 0; y < f.height; ++y) memcpy(hs + at + (size_t)y * pitch, f.data + (size_t)y * (size_t)f.stride, row_bytes);
-        sl->recs[i].src = dev + at;
-        sl->recs[i].stride = (uint32_t)pitch;
-        at += pitch * (size_t)f.height;
+        const size_t row_bytes = (size_t)f.width * (size_t)image_channels(f);
+        sl->recs[i].src = dev + stage_rows(hs, &b, f.data, (size_t)f.stride, (size_t)f.height, row_bytes);
+        sl->recs[i].stride = (uint32_t)align4(row_bytes);
     }
     memcpy(hs, sl->recs.data(), n * sizeof(PrepFrameDev));
-    memcpy(hs + rec_bytes, sl->eq.data(), n * sizeof(AtlasFrameDev));
-    if (!sl->taps.empty()) memcpy(hs + rec_bytes + eq_bytes, sl->taps.data(), sl->taps.size() * sizeof(PyrTap));
-    HIP_TRY(hipMemcpyAsync(e->d_prep.p, hs, bytes, hipMemcpyHostToDevice, e->stream));
+    memcpy(hs + eq_at, sl->eq.data(), n * sizeof(AtlasFrameDev));
+    if (!sl->taps.empty()) memcpy(hs + tap_at, sl->taps.data(), sl->taps.size() * sizeof(PyrTap));
+    HIP_TRY(hipMemcpyAsync(e->d_prep.p, hs, b.bytes, hipMemcpyHostToDevice, e->stream));
     PrepArgs a;
     memset(&a, 0, sizeof(a));
     a.frames = (const PrepFrameDev*)dev;
     a.n_frames = (uint32_t)n;
     a.n_units = sl->n_units;
-    a.taps = (const PyrTap*)(dev + rec_bytes + eq_bytes);
+    a.taps = (const PyrTap*)(dev + tap_at);
     a.dst = d_dst;
     a.dst_bytes = lay.bytes;
     int hrc;
@@ -71,7 +63,7 @@ int enqueue_prep_slice(vj_env* e, const vj_image* frames, const PrepLayout& lay,
 #endif
         EqualizeArgs q;
         memset(&q, 0, sizeof(q));
-        q.frames = (const AtlasFrameDev*)(dev + rec_bytes);
+        q.frames = (const AtlasFrameDev*)(dev + eq_at);
         q.n_frames = (uint32_t)n;
         q.hist = (uint32_t*)L->d_eq_hist.p;
         q.lut = (uint8_t*)L->d_eq_lut.p;
@@ -102,33 +94,11 @@ int vj_preprocess(vj_env* e, const vj_image* frames, int n_frames, const vj_prep
     int rc = prep_layout(frames, n_frames, p, &lay);
     if (rc) return rc;
     if (n_frames == 0) return VJ_OK;
-    if (dst_bytes < lay.bytes) {
-        set_error("vj_preprocess: dst_bytes %llu is below the %llu bytes the layout needs", (unsigned long long)dst_bytes, (unsigned long long)lay.bytes);
-        return VJ_ERR_ARG;
-    }
-    if (((uintptr_t)d_dst & 3u) != 0u) {
-        set_error("vj_preprocess: d_dst must be a multiple of 4");
-        return VJ_ERR_ARG;
-    }
-    if ((rc = prep_check_overlap(frames, n_frames, d_dst, lay.bytes))) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t per_slice = e->max_subbatch > 0 ? (size_t)e->max_subbatch : (size_t)n_frames;
+    if ((rc = check_dst("vj_preprocess", frames, n_frames, d_dst, dst_bytes, lay.bytes, true, prep_check_overlap))) return rc;
     PrepSlice sl;
-    HIP_TRY(hipEventRecord(e->prep_ev[0], e->stream));
-    for (size_t first = 0; first < (size_t)n_frames; first += per_slice) {
-        const size_t n = std::min(per_slice, (size_t)n_frames - first);
-        // (a later slice reuses the staging buffer and the device block: the one before it has finished by then)
-        if (first != 0) HIP_TRY(hipStreamSynchronize(e->stream));
-        if ((rc = enqueue_prep_slice(e, frames, lay, first, n, d_dst, &sl))) {
-            (void)hipStreamSynchronize(e->stream);
-            return rc;
-        }
-    }
-    HIP_TRY(hipEventRecord(e->prep_ev[1], e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->prep_ev[0], e->prep_ev[1]));
-    e->prep_ms = ms;
+    rc = run_slices(e, e->call_ev, &e->prep_ms, (size_t)n_frames, slices_of(e, (size_t)n_frames),
+                    [&](size_t first, size_t end) { return enqueue_prep_slice(e, frames, lay, first, end - first, d_dst, &sl); });
+    if (rc) return rc;
     for (int i = 0; i < n_frames; ++i) {
         const PrepSlot& t = lay.slots[(size_t)i];
         out[i] = vj_image{d_dst + t.off, (int32_t)t.dw, (int32_t)t.dh, (int32_t)t.pitch, 1, 1};
