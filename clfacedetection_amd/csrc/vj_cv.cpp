@@ -17,6 +17,7 @@
 #include "vj_points_driver.hpp"
 #include "vj_cv_roi_host.hpp"
 #include "vj_cv_roi_levels_host.hpp"
+#include "vj_cv_tq_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -231,6 +232,144 @@ static CvPruneArgs prune_args(vj_env* e, const CvPlan* pl, const CvArgs& a, int 
     return pa;
 }
 
+// ------------------------------------------------------------------------ what the passes of this file share
+// A cascade's shape as the argument rules below read it: of a CvPlan, a CvRoiPlan, a PointCascade or a CvShape
+struct CvFacts { bool has_tilted, is_tree, tree2; };
+template <class P> static CvFacts facts_of(const P& p) { return CvFacts{p.has_tilted, p.is_tree, p.tree2}; }
+
+// The three fields every pass of the profile derives from the shape and the tunables (CvArgs and CvPointArgs)
+template <class A> static void fill_shape_args(const vj_env* e, const CvFacts& f, A* a) {
+    a->tilted = f.has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
+    a->tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
+    a->tree2 = f.tree2 && !f.is_tree && !f.has_tilted && e->cv_tree2 ? 1u : 0u;
+}
+
+struct CvTables { const void *table, *scales, *stages; uint32_t n_order, n_stages; };
+struct CvGeom { uint32_t frame_elems, stride, sum_h, n_frames; };
+
+// The CvArgs every pass starts from: the environment's integral images, a plan's tables, the geometry, and where detections and
+// counters go (counts: stage_entered [VJ_MAX_STAGES] | visited ... | the detection count).  rows / total_waves and whatever one
+// path adds are the caller's.
+static CvArgs cv_base_args(const vj_env* e, const CvFacts& f, const CvTables& t, const CvGeom& g, void* det, uint32_t det_cap, void* counts) {
+    CvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.sum = (const uint32_t*)e->d_sum.p;
+    a.sqsum = (const uint64_t*)e->d_sqsum.p;
+    a.n_order = t.n_order;
+    a.table = (const uint32_t*)t.table;
+    a.scales = (const CvScaleDev*)t.scales;
+    a.stages = (const StageDev*)t.stages;
+    a.n_frames = g.n_frames;
+    a.n_stages = t.n_stages;
+    a.frame_elems = g.frame_elems;
+    a.stride = g.stride;
+    a.sum_h = g.sum_h;
+    a.det = (CvDet*)det;
+    a.det_count = (uint32_t*)((unsigned long long*)counts + 2 * VJ_MAX_STAGES);
+    a.det_cap = det_cap;
+    a.stage_entered = (unsigned long long*)counts;
+    fill_shape_args(e, f, &a);
+    return a;
+}
+template <class Plan> static CvTables tables_of(const Plan* pl) {
+    return CvTables{pl->d_table.p, pl->d_scales.p, pl->d_stages.p, pl->n_order, pl->n_stages};
+}
+
+static int cascade_launched(int hrc) {
+    if (!hrc) return VJ_OK;
+    set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
+    return VJ_ERR_HIP;
+}
+
+// Frames per sub-batch: 32-bit byte offsets into the batch's sum images, and the configured "max_subbatch"
+static int cv_max_frames(const vj_env* e, int n_frames, uint32_t frame_elems) {
+    const int m = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_frames, 0xfffffff0ull / ((uint64_t)frame_elems * 4u)));
+    return e->max_subbatch > 0 ? std::min(m, e->max_subbatch) : m;
+}
+
+// A sub-batch's way onto the device, between lane0.ev[0] and ev[1]: the frames staged, VJ_FLAG_EQUALIZE_HIST, then — with a plan
+// that has them — the pyramid of CV_HAAR_SCALE_IMAGE (from there on the "frames" are the gray canvases, and the integral images
+// are theirs) or the edge maps and their integral, then the integrals.
+static int enqueue_cv_ingest(vj_env* e, const vj_image* frames, int nf, int W, int H, int CH, bool equalize, const CvPlan* pl, bool tilted) {
+    const bool si = pl && pl->scale_image;
+    const int IW = si ? (int)pl->canvas_w : W, IH = si ? (int)pl->canvas_h : H;
+    int rc;
+    if (si) {   // the frames' gray staging alone; the integral buffers are the canvases'
+        if ((rc = ensure_gray_staging(e, W, H, nf, CH))) return rc;
+        if ((rc = ensure_image_buffers(e, IW, IH, nf, false))) return rc;
+    } else if ((rc = ensure_image_buffers(e, W, H, nf, true, CH))) {
+        return rc;
+    }
+    const uint8_t* d_gray;
+    size_t gray_frame_bytes;
+    int gray_stride;
+    int gray_ch = CH;
+    if ((rc = stage_frames(e, frames, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
+    HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
+    // VJ_FLAG_EQUALIZE_HIST: from here on the frames are the lane's equalized gray batch
+    if (equalize && (rc = enqueue_equalize(e, nullptr, &d_gray, &gray_frame_bytes, &gray_stride, &gray_ch, W, H, nf))) return rc;
+    if (si) {   // every level of every frame
+        if ((rc = enqueue_pyramid(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, gray_ch, pl->d_pyr_levels.p, pl->d_pyr_taps.p,
+                                  pl->n_pyr_levels, pl->n_pyr_units, pl->canvas_w, pl->canvas_h, pl->canvas_pitch)))
+            return rc;
+        d_gray = (const uint8_t*)e->d_pyr.p;
+        gray_frame_bytes = (size_t)pl->canvas_pitch * (size_t)IH;
+        gray_stride = (int)pl->canvas_pitch;
+        gray_ch = 1;
+    }
+    if (pl && pl->prune) {   // the edge maps and their integral
+        uint32_t pitch = 0;
+        if ((rc = enqueue_canny(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, gray_ch, &pitch))) return rc;
+        if ((rc = enqueue_edge_integral(e, pitch, W, H, nf))) return rc;
+    }
+    if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, IW, IH, nf, gray_ch))) return rc;
+    if (tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, IW, IH, nf, gray_ch))) return rc;
+    HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
+    return VJ_OK;
+}
+
+// After a pass's launches: its counters on the host (e->d_cv_counts, `counts_bytes` of them) once the stream has drained, and the
+// number of detections it reported — which may be more than the buffer held.
+static int read_cv_counts(vj_env* e, size_t counts_bytes, std::vector<unsigned long long>* h, uint32_t* n_det) {
+    h->resize((counts_bytes + 7) / 8);
+    HIP_TRY(hipMemcpyAsync(h->data(), e->d_cv_counts.p, counts_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *n_det = (uint32_t)((*h)[2 * VJ_MAX_STAGES] & 0xffffffffull);
+    return VJ_OK;
+}
+
+// One pass until its detections fit.  Per attempt: e->d_cv_det for *det_cap records, the counters zeroed, enqueue(*det_cap) — the
+// launches — between lane0.ev[2] and ev[3], the counters read back; more detections than *det_cap: the capacity grown, once more.
+// `twice`: the error of the case that cannot happen (the count of a repeated pass is the count that sized its buffer).
+template <class Enqueue>
+static int run_cv_pass_until_fit(vj_env* e, size_t counts_bytes, uint32_t* det_cap, const char* twice, Enqueue&& enqueue,
+                                 std::vector<unsigned long long>* h, uint32_t* n_det) {
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        int rc;
+        if ((rc = e->d_cv_det.ensure((size_t)*det_cap * sizeof(CvDet)))) return rc;
+        HIP_TRY(hipMemsetAsync(e->d_cv_counts.p, 0, counts_bytes, e->stream));
+        HIP_TRY(hipEventRecord(e->lane0.ev[2], e->stream));
+        if ((rc = enqueue(*det_cap))) return rc;
+        HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
+        if ((rc = read_cv_counts(e, counts_bytes, h, n_det))) return rc;
+        if (*n_det <= *det_cap) return VJ_OK;
+        *det_cap = grown_cap(*det_cap, *n_det);   // overflow: grow and run the pass again
+    }
+    set_error("%s", twice);
+    return VJ_ERR_LIMIT;
+}
+
+static void add_cv_counters(const std::vector<unsigned long long>& h, size_t n_stages, vj_counters* k) {
+    for (size_t s = 0; s < n_stages; ++s) k->stage_entered[s] += h[s];
+    k->windows += h[VJ_MAX_STAGES];
+}
+
+template <class Det> static int read_cv_dets(vj_env* e, uint32_t n_det, std::vector<Det>* raw) {
+    raw->resize(n_det);
+    if (n_det) HIP_TRY(hipMemcpy(raw->data(), e->d_cv_det.p, (size_t)n_det * sizeof(Det), hipMemcpyDeviceToHost));
+    return VJ_OK;
+}
+
 
 // CV_HAAR_FIND_BIGGEST_OBJECT (VJ_FLAG_CV_FIND_BIGGEST; tempcv.cpp:1353-1490).  Per sub-batch: the integrals, then
 // one round per scale of the descending list — cv_biggest_pass and the grouping step cv_biggest_update — all enqueued up front;
@@ -240,7 +379,6 @@ static CvPruneArgs prune_args(vj_env* e, const CvPlan* pl, const CvArgs& a, int 
 static int detect_biggest(vj_env* e, const vj_cascade* c, CvPlan* pl, const vj_image* frames, int n_frames, int W, int H, int CH,
                           const vj_cv_params* p, bool equalize, vj_result* out) {
     const std::vector<CvScaleDev>& scales = pl->scales;
-    const StageProgram& prog = pl->prog;
     const uint32_t stride = (uint32_t)W + 1u;
     const uint32_t frame_elems = frame_elems_for(W, H);
     const bool count = (p->flags & VJ_FLAG_COUNTERS) != 0;
@@ -250,9 +388,7 @@ static int detect_biggest(vj_env* e, const vj_cascade* c, CvPlan* pl, const vj_i
     const size_t counts_bytes = 2 * VJ_MAX_STAGES * sizeof(uint64_t);   // stage_entered | visited
     int rc;
     if ((rc = d_counts.ensure(counts_bytes))) return rc;
-    const uint64_t frame_bytes = (uint64_t)frame_elems * 4u;
-    int max_frames = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_frames, 0xfffffff0ull / frame_bytes));
-    if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
+    const int max_frames = cv_max_frames(e, n_frames, frame_elems);
     // a frame's segment of the detection buffer: what a search may hold before its first grouped object (GROUP_MAX) and as much
     // again for the scanROI's candidates, or the configured start ("det_cap"); a fuller frame repeats the sub-batch with more room
     uint32_t frame_cap = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(e->det_cap_init, 2u * GROUP_MAX));
@@ -264,17 +400,7 @@ static int detect_biggest(vj_env* e, const vj_cascade* c, CvPlan* pl, const vj_i
     out->timing.n_cascade_launches = 0;
     for (int f0 = 0, nf = 0; f0 < n_frames && !scales.empty(); f0 += nf) {
         nf = std::min(max_frames, n_frames - f0);
-        if ((rc = ensure_image_buffers(e, W, H, nf, true, CH))) return rc;
-        const uint8_t* d_gray;
-        size_t gray_frame_bytes;
-        int gray_stride;
-        if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
-        HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
-        int gray_ch = CH;
-        if (equalize && (rc = enqueue_equalize(e, nullptr, &d_gray, &gray_frame_bytes, &gray_stride, &gray_ch, W, H, nf))) return rc;
-        if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, gray_ch))) return rc;
-        if (pl->has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, gray_ch))) return rc;
-        HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
+        if ((rc = enqueue_cv_ingest(e, frames + f0, nf, W, H, CH, equalize, pl, pl->has_tilted))) return rc;   // (a find-biggest plan: neither pyramid nor edge maps)
         const size_t state_bytes = (size_t)nf * sizeof(CvBigState), big_bytes = state_bytes + (size_t)nf * sizeof(uint32_t);
         if ((rc = e->d_cv_big.ensure(big_bytes))) return rc;
         st.resize((size_t)nf);
@@ -290,23 +416,8 @@ static int detect_biggest(vj_env* e, const vj_cascade* c, CvPlan* pl, const vj_i
             CvBigArgs b;
             memset(&b, 0, sizeof(b));
             CvArgs& a = b.cv;
-            a.sum = (const uint32_t*)e->d_sum.p;
-            a.sqsum = (const uint64_t*)e->d_sqsum.p;
-            a.tilted = pl->has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
-            a.n_order = pl->n_order;
-            a.table = (const uint32_t*)pl->d_table.p;
-            a.scales = (const CvScaleDev*)pl->d_scales.p;
-            a.stages = (const StageDev*)pl->d_stages.p;
-            a.n_frames = (uint32_t)nf;
-            a.n_stages = pl->n_stages;
-            a.frame_elems = frame_elems;
-            a.stride = stride;
-            a.sum_h = (uint32_t)H + 1u;
-            a.det = (CvDet*)d_det.p;
-            a.det_cap = frame_cap;
-            a.stage_entered = (unsigned long long*)d_counts.p;
-            a.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
-            a.tree2 = pl->tree2 && !pl->is_tree && !pl->has_tilted && e->cv_tree2 ? 1u : 0u;
+            a = cv_base_args(e, facts_of(*pl), tables_of(pl), CvGeom{frame_elems, stride, (uint32_t)H + 1u, (uint32_t)nf}, d_det.p, frame_cap, d_counts.p);
+            a.det_count = nullptr;   // (every frame's segment has a counter of its own: b.frame_count; the counters end with `visited`)
             b.state = (CvBigState*)e->d_cv_big.p;
             b.frame_count = (uint32_t*)((char*)e->d_cv_big.p + state_bytes);
             b.min_w = p->min_w;
@@ -326,11 +437,7 @@ static int detect_biggest(vj_env* e, const vj_cascade* c, CvPlan* pl, const vj_i
                 a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
                 // (the grouping step follows EVERY scale, the last one too, :1422-1454: a frame that first groups there still gets its
                 // maxRect pushed before step 5, which counts it among the neighbors)
-                const int hrc = launch_cv_biggest_round(b, pl->trees, count, pl->is_tree, n_blocks, true, e->stream);
-                if (hrc) {
-                    set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
-                    return VJ_ERR_HIP;
-                }
+                if ((rc = cascade_launched(launch_cv_biggest_round(b, pl->trees, count, pl->is_tree, n_blocks, true, e->stream)))) return rc;
                 launches += 2;
             }
             HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
@@ -359,10 +466,7 @@ static int detect_biggest(vj_env* e, const vj_cascade* c, CvPlan* pl, const vj_i
             out->timing.cascade_ms += ms_c;
             out->timing.total_ms += ms_t;
             out->timing.n_cascade_launches += launches;
-            if (count) {
-                for (size_t s = 0; s < pl->n_stages; ++s) out->counters.stage_entered[s] += h[s];
-                out->counters.windows += h[VJ_MAX_STAGES];
-            }
+            if (count) add_cv_counters(h, pl->n_stages, &out->counters);
             break;
         }
         // ---- step 5 (tempcv.cpp:1458-1490), frame by frame
@@ -400,22 +504,7 @@ static int detect_biggest(vj_env* e, const vj_cascade* c, CvPlan* pl, const vj_i
             if (best) all.push_back(*best);
         }
     }
-    out->count = (uint32_t)all.size();
-    if (!all.empty()) {
-        out->rects = (vj_rect*)malloc(all.size() * sizeof(vj_rect));
-        if (!out->rects) return VJ_ERR_NOMEM;
-        memcpy(out->rects, all.data(), all.size() * sizeof(vj_rect));
-    }
-    if (count) {
-        vj_counters& k = out->counters;
-        uint64_t rect_evals = 0;
-        for (size_t s = 0; s < pl->n_stages; ++s) {
-            k.stump_evals += k.stage_entered[s] * prog.n_nodes[s];
-            rect_evals += k.stage_entered[s] * prog.n_rects[s];
-        }
-        k.gather_bytes = 48ull * k.stage_entered[0] + 16ull * rect_evals;
-    }
-    return VJ_OK;
+    return cv_result_epilogue(all, count ? &pl->prog : nullptr, out);
 }
 
 }  // namespace
@@ -538,23 +627,44 @@ struct CvChainDevice {
     int finish(int f0, int nf, const vj_rect* raw, size_t n_raw, size_t base);
 };
 
-// vj_detect_opencv.  need_tilted: compute the tilted integral even when `c` has no tilted feature (someone after it reads it).
-// roc: vj_detect_opencv_roc's scale-image call — the kernels report CvRocDet records; the rectangles come back raw (ungrouped),
-// sorted, with their levels and weights in roc's vectors.
-int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_params* p, vj_result* out,
-                       bool need_tilted, const CvSubBatchHook* hook, const CvRocCall* roc = nullptr, CvChainDevice* dev = nullptr) {
-    if (!e || !c || !p || !out || n_frames < 0 || (n_frames > 0 && !frames)) return VJ_ERR_ARG;
-    memset(out, 0, sizeof(*out));
-    if (n_frames == 0) return VJ_OK;
+// ------------------------------------------------------------------------ vj_detect_opencv
+// What the functions of one call share
+struct CvCall {
+    vj_env* e;
+    const vj_image* frames;
+    const vj_cv_params* p;            // (without VJ_FLAG_EQUALIZE_HIST)
+    vj_result* out;
+    bool equalize, need_tilted, count;
+    const CvSubBatchHook* hook;
+    const CvRocCall* roc;
+    CvChainDevice* dev;
+    CvPlan* pl;
+    int W, H, CH;
+    int IH;                           // rows the integral images cover (CV_HAAR_SCALE_IMAGE: the canvas that holds the pyramid's levels)
+    uint32_t stride, frame_elems;
+    int max_frames;                   // frames per sub-batch (the tree queue may lower it: CvTqSizing::RESPLIT)
+    uint32_t det_cap;
+    std::vector<vj_rect> all;
+    std::vector<int32_t> all_levels;  // (ROC) parallel to `all`
+    std::vector<double> all_weights;
+};
+// counters: stage_entered[VJ_MAX_STAGES] | visited | ... | detection count | pad | 4 x 8 tile ticket counters
+// ... | 64 tree-queue counters (one per tile scale) | chain-pass ticket
+constexpr size_t CV_COUNTS_BYTES = 2 * VJ_MAX_STAGES * sizeof(uint64_t) + 16 + 4 * 8 * sizeof(uint32_t) + 64 * sizeof(uint32_t) + 16;
+
+// One attempt at a sub-batch as it was enqueued, or why it was not
+struct CvAttempt {
+    enum { LAUNCHED, ROWS_ONLY /* the same attempt again on the rows */, RESPLIT /* the same frames again, cc.max_frames at a time */ } outcome = LAUNCHED;
+    CvArgs a;
+    uint32_t tq_cap = 0;        // != 0: stage-tree tiles, with a survivor queue of this many entries ...
+    bool chain_pass = false;    // ... as one sub-queue per scale (cv_tree_chain_pass), else one flat queue (cv_tree_walk)
+};
+
+static int check_cv_call(const vj_image* frames, int n_frames, const vj_cv_params* p, int* W_out, int* H_out, int* CH_out) {
     if (!(p->scale_factor > 1.0)) {
         set_error("scale_factor must be > 1");
         return VJ_ERR_ARG;
     }
-    // VJ_FLAG_EQUALIZE_HIST is read here and nowhere else: the plan, its key and the kernels see the parameters without it
-    const bool equalize = (p->flags & VJ_FLAG_EQUALIZE_HIST) != 0u;
-    vj_cv_params p_plain = *p;
-    p_plain.flags &= ~(uint32_t)VJ_FLAG_EQUALIZE_HIST;
-    p = &p_plain;
     const int W = frames[0].width, H = frames[0].height;
     if (W <= 0 || H <= 0 || W >= 65535 || H >= 65535) return VJ_ERR_ARG;
     if ((uint64_t)(W + 1) * (uint64_t)(H + 3) >= (1ull << 30)) {   // the limit of vj_detect (check_frames): 32-bit byte offsets
@@ -568,548 +678,472 @@ int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, i
             set_error("frame %d: all frames of a batch must be non-null and of equal size and channel count", i);
             return VJ_ERR_ARG;
         }
-    HIP_TRY(hipSetDevice(e->device));
-    CvPlan* pl;
-    int rc = get_cv_plan(e, c, W, H, p, n_frames, &pl, roc);
-    if (rc) return rc;
-    if (pl->find_biggest) return detect_biggest(e, c, pl, frames, n_frames, W, H, CH, p, equalize, out);
-    const std::vector<CvScaleDev>& scales = pl->scales;
-    const StageProgram& prog = pl->prog;
-    const bool trees = pl->trees, is_tree = pl->is_tree, has_tilted = pl->has_tilted;
-    // CV_HAAR_SCALE_IMAGE: the integral images are those of the canvas that holds the pyramid's levels
-    const bool si = pl->scale_image;
-    const int IW = si ? (int)pl->canvas_w : W, IH = si ? (int)pl->canvas_h : H;
-    const uint32_t stride = (uint32_t)IW + 1u;
-    const uint32_t frame_elems = frame_elems_for(IW, IH);
-    DevBuf& d_det = e->d_cv_det;
-    DevBuf& d_counts = e->d_cv_counts;
-    // counters: stage_entered[VJ_MAX_STAGES] | visited | ... | detection count | pad | 4 x 8 tile ticket counters
-    // ... | 64 tree-queue counters (one per tile scale) | chain-pass ticket
-    const size_t counts_bytes = 2 * VJ_MAX_STAGES * sizeof(uint64_t) + 16 + 4 * 8 * sizeof(uint32_t) + 64 * sizeof(uint32_t) + 16;
-    if ((rc = d_counts.ensure(counts_bytes))) return rc;
+    *W_out = W;
+    *H_out = H;
+    *CH_out = CH;
+    return VJ_OK;
+}
 
-    const bool count = (p->flags & VJ_FLAG_COUNTERS) != 0;
-    const uint64_t frame_bytes = (uint64_t)frame_elems * 4u;
-    int max_frames = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_frames, 0xfffffff0ull / frame_bytes));
-    {   // the detection counter is 32-bit: a sub-batch holds fewer than 2^32 windows, so it cannot wrap
-        uint64_t frame_windows = 0;
-        for (const CvScaleDev& sd : scales) frame_windows += (uint64_t)sd.end_x * sd.end_y;
-        if (frame_windows > 0xffffffffull) {
-            set_error("vj_detect_opencv: %llu windows per frame, more than a 32-bit detection count holds",
-                      (unsigned long long)frame_windows);
-            return VJ_ERR_LIMIT;
-        }
-        if (frame_windows) max_frames = (int)std::min<uint64_t>((uint64_t)max_frames, 0xffffffffull / frame_windows);
+// ---- the launch paths of one attempt.  Each ends on e->stream.
+// Every scale on cv_profile_pass.  Four workgroups (16 waves) per CU: every wave walks its own window row, and the rows in flight on
+// an XCD should stay inside its 4 MiB L2 (64 x 1080p: 376 / 235 / 179 / 153 / 173 / 194 / 193 ms for 1 / 2 / 3 / 4 / 5 / 6 / 8)
+static int launch_cv_rows(const CvCall& cc, CvArgs& a) {
+    const vj_env* e = cc.e;
+    const CvPlan* pl = cc.pl;
+    const int n_blocks = std::max(1, e->n_cu * 4);
+    a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
+    return cascade_launched(launch_cv_profile_pass(a, pl->trees, cc.count, pl->is_tree, n_blocks, e->stream, pl->prune, pl->scale_image, cc.roc != nullptr));
+}
+
+// What the three tile paths share.  The small scales run on LDS tiles (vj_cv_tile.hip), the rest on cv_profile_pass, concurrently
+// on two streams: the row kernel is bound by the texture-address unit, the tile kernel by LDS and VALU.  The row kernel is launched
+// first, with one workgroup per CU, so that the tile workgroups find their LDS share next to it.
+// begin: stream2 forked off e->stream (behind whatever the path has enqueued there: its bitmaps' memsets) and the rest rows on it
+static int begin_cv_tiles(const CvCall& cc, const CvArgs& a, bool count, bool stage_tree, bool prune, bool exhaustive, bool* two) {
+    vj_env* e = cc.e;
+    const CvPlan* pl = cc.pl;
+    *two = e->concurrent && pl->n_rows_rest != 0;
+    if (*two) {
+        HIP_TRY(hipEventRecord(e->fork_ev, e->stream));
+        HIP_TRY(hipStreamWaitEvent(e->stream2, e->fork_ev, 0));
     }
-    if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
-    // (a ROC call reports several times as many windows: its buffer starts at the configured "det_cap" and grows the same way)
-    // (the chain's device hand-off too: its buffers all start at "det_cap", so that a small value drives every regrow path)
-    uint32_t det_cap = roc || dev ? std::max(1u, e->det_cap_init) : 1u << 16;
-    const size_t det_bytes = roc ? sizeof(CvRocDet) : sizeof(CvDet);
-    std::vector<vj_rect> all;
-    std::vector<int32_t> all_levels;   // (ROC) parallel to `all`
-    std::vector<double> all_weights;
-    for (int f0 = 0, nf = 0; f0 < n_frames && pl->n_rows != 0; f0 += nf) {
-        nf = std::min(max_frames, n_frames - f0);
-        if (si) {   // the frames' gray staging alone; the integral buffers are the canvases'
-            if ((rc = ensure_gray_staging(e, W, H, nf, CH))) return rc;
-            if ((rc = ensure_image_buffers(e, IW, IH, nf, false))) return rc;
-        } else if ((rc = ensure_image_buffers(e, W, H, nf, true, CH))) {
-            return rc;
+    if (pl->n_rows_rest == 0) return VJ_OK;
+    CvArgs b = a;
+    b.rows = (const UnitDev*)pl->d_rows_rest.p;
+    b.n_rows = pl->n_rows_rest;
+    const int nb = std::max(1, e->n_cu * (*two ? pl->row_blocks : 4));
+    b.total_waves = (uint32_t)nb * CV_WAVES_PER_BLOCK;
+    return cascade_launched(launch_cv_profile_pass(b, pl->trees, count, stage_tree, nb, *two ? e->stream2 : e->stream, prune, exhaustive));
+}
+// end: e->stream waits for the rest rows (also after a launch that failed)
+static int end_cv_tiles(const CvCall& cc, bool two, int rc) {
+    if (two) {
+        HIP_TRY(hipEventRecord(cc.e->join_ev, cc.e->stream2));
+        HIP_TRY(hipStreamWaitEvent(cc.e->stream, cc.e->join_ev, 0));
+    }
+    return rc;
+}
+
+// the tile kernel's arguments but for what differs between the paths: n_stages, the bitmap, the finish thresholds (ws_begin, ws_max),
+// stage_entered, the tree queue
+static CvTileArgs cv_tile_base_args(const CvArgs& a) {
+    CvTileArgs t;
+    memset(&t, 0, sizeof(t));
+    t.sum = a.sum;
+    t.tilted = a.tilted;
+    t.sqsum = a.sqsum;
+    t.table = a.table;
+    t.scales = a.scales;
+    t.stages = a.stages;
+    t.n_frames = a.n_frames;
+    t.frame_elems = a.frame_elems;
+    t.stride = a.stride;
+    t.sum_h = a.sum_h;
+    t.repack_mask = ~3ull;        // before every stage from 2 on (as the clod profile's tiles)
+    t.det = a.det;
+    t.det_count = a.det_count;
+    t.det_cap = a.det_cap;
+    return t;
+}
+
+// cv_tile_pass<mode>: one launch per LDS class that has tiles; the classes' ticket counters from `first_slot` on (8 dwords each)
+static int launch_cv_tile_classes(const CvCall& cc, const CvArgs& a, const CvTileArgs& t, int mode, bool count, bool tree2, int first_slot) {
+    const vj_env* e = cc.e;
+    const CvPlan* pl = cc.pl;
+    uint32_t* tickets = a.det_count + 4;
+    for (int cls = 0; cls < 2; ++cls) {
+        const uint32_t n_cls = pl->class_first[cls + 1] - pl->class_first[cls];
+        if (!n_cls) continue;
+        CvTileArgs ta = t;
+        ta.tiles = (const UnitDev*)pl->d_tiles.p + pl->class_first[cls];
+        ta.n_tiles = n_cls;
+        ta.lds_bytes = pl->class_lds[cls];
+        ta.ticket = tickets + 8 * (first_slot + cls);
+        const int per_cu = std::max(1, std::min(2, (int)((160u * 1024u - (uint32_t)pl->row_blocks * 20u * 1024u) / ta.lds_bytes)));
+        const int tb = (int)std::min<uint64_t>((uint64_t)n_cls * (uint64_t)a.n_frames, (uint64_t)e->n_cu * (uint64_t)per_cu);
+        if (const int rc = cascade_launched(launch_cv_tile_pass(ta, mode, count, tree2, std::max(1, tb), e->stream))) return rc;
+    }
+    return VJ_OK;
+}
+
+// reject bits -> visited bits, one recurrence domain per window row (skip_resolve)
+static int launch_cv_skip_resolve(const CvCall& cc, uint32_t nf) {
+    CascadeArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.skip_bits = (unsigned long long*)cc.e->d_skip_bits.p;
+    ra.skip_frame_words = cc.pl->bits_frame_words;
+    ra.skip_segs = (const UnitDev*)cc.pl->d_bit_segs.p;
+    ra.n_skip_segs = cc.pl->n_bit_segs;
+    ra.n_frames = nf;
+    return cascade_launched(launch_skip_resolve(ra, std::max(1, cc.e->n_cu * 2), cc.e->stream));
+}
+
+// Linear cascades: cv_tile_pass<0> (reject bits of stage 0), skip_resolve, cv_tile_pass<1> (the cascade on the visited windows)
+static int launch_cv_plain_tiles(const CvCall& cc, const CvArgs& a) {
+    vj_env* e = cc.e;
+    const CvPlan* pl = cc.pl;
+    const int nf = (int)a.n_frames;
+    const bool count = cc.count;
+    int rc;
+    if ((rc = e->d_skip_bits.ensure((size_t)pl->bits_frame_words * 8u * (size_t)nf))) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_skip_bits.p, 0, (size_t)pl->bits_frame_words * 8u * (size_t)nf, e->stream));
+    bool two;
+    rc = begin_cv_tiles(cc, a, count, pl->is_tree, pl->prune, false, &two);
+    CvTileArgs t = cv_tile_base_args(a);
+    t.n_stages = pl->n_stages;
+    t.bits = (unsigned long long*)e->d_skip_bits.p;
+    t.bits_frame_words = pl->bits_frame_words;
+    t.ws_begin = 3;
+    t.ws_max = (uint32_t)e->cv_tile_ws_max;
+    t.stage_entered = a.stage_entered;
+    if (!rc) rc = launch_cv_tile_classes(cc, a, t, 0, count, pl->tree2, 0);
+    if (!rc && pl->prune) {   // pruned windows are "zeros" of the walk (prune bitmap: cv_prune_mark)
+        // one wave per window row of a tile scale: the rows' words are latency-bound gathers, thousands of waves hide them
+        const CvPruneArgs pa = prune_args(e, pl, a, nf, nullptr);
+        rc = cascade_launched(launch_cv_prune_mark(pa, (int)std::max<uint32_t>(1u, (pa.n_segs * pa.n_frames + 3u) / 4u), e->stream));
+    }
+    if (!rc) rc = launch_cv_skip_resolve(cc, a.n_frames);
+    if (!rc && pl->prune) {   // ... visited but not evaluated: out of the visited bits, into counts.windows
+        const CvPruneArgs pa = prune_args(e, pl, a, nf, count ? a.stage_entered + VJ_MAX_STAGES : nullptr);
+        rc = cascade_launched(launch_cv_prune_visited(pa, std::max(1, e->n_cu * 2), e->stream));
+    }
+    if (!rc) rc = launch_cv_tile_classes(cc, a, t, 1, count, pl->tree2, 2);
+    return end_cv_tiles(cc, two, rc);
+}
+
+// CV_HAAR_SCALE_IMAGE: the levels whose grid fills a tile on cv_tile_pass<3> — every grid window, no bitmap passes —, the small
+// levels on the exhaustive-grid row kernel
+static int launch_cv_scale_image_tiles(const CvCall& cc, const CvArgs& a) {
+    const CvPlan* pl = cc.pl;
+    bool two;
+    int rc = begin_cv_tiles(cc, a, cc.count, false, false, true, &two);
+    CvTileArgs t = cv_tile_base_args(a);
+    t.n_stages = pl->n_stages;
+    t.ws_begin = 3;
+    t.ws_max = (uint32_t)cc.e->cv_tile_ws_max;
+    t.stage_entered = a.stage_entered;
+    if (!rc) rc = launch_cv_tile_classes(cc, a, t, 3, cc.count, pl->tree2, 0);
+    return end_cv_tiles(cc, two, rc);
+}
+
+// Stage tree (uncounted calls): the tiles run the linear prefix on every grid window (cv_tile_pass<2>), cv_tree_walk or
+// cv_tree_chain_pass the rest of the tree for the survivors, skip_resolve + cv_tree_emit the sequential walk.  cv_profile_pass keeps
+// the large scales.  The survivors' queue has room for 1 / 2^shift of the tile windows; an overflow takes two off the shift and runs
+// the attempt again, a forced capacity (tests) falls back to the rows instead (run_cv_subbatch).
+// (the shift belongs to the PLAN: one survivor-heavy workload does not make every later call allocate more)
+static int launch_cv_tree_tiles(CvCall& cc, CvAttempt* at) {
+    vj_env* e = cc.e;
+    CvPlan* pl = cc.pl;
+    const CvArgs& a = at->a;
+    const int nf = (int)a.n_frames;
+    int rc;
+    const size_t bits_bytes = (size_t)pl->bits_frame_words * 8u * (size_t)nf;
+    if ((rc = e->d_skip_bits.ensure(bits_bytes))) return rc;
+    if ((rc = e->d_cv_accept.ensure(bits_bytes))) return rc;
+    if (pl->tq_shift < 0) pl->tq_shift = e->cv_tq_shift;
+    const bool chain_pass = pl->chains.n != 0u && pl->n_tile_scales <= 64u && e->cv_tree_queue_cap <= 0 && e->cv_tree_chains;
+    const CvTqSizing sz = cv_tq_sizing(pl->tile_windows, pl->n_tile_scales, (uint32_t)nf, (uint32_t)pl->tq_shift, e->cv_tree_queue_cap, chain_pass, cc.max_frames);
+    if (sz.kind == CvTqSizing::ROWS_ONLY) {
+        at->outcome = CvAttempt::ROWS_ONLY;
+        return VJ_OK;
+    }
+    if (sz.kind == CvTqSizing::RESPLIT) {
+        cc.max_frames = (int)sz.n;
+        pl->tq_split_frames = cc.max_frames;
+        at->outcome = CvAttempt::RESPLIT;
+        return VJ_OK;
+    }
+    const uint32_t tq_cap = (uint32_t)sz.n;
+    {   // never more than a quarter of what the device has free: beyond that the rows take the call
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)tq_cap * sizeof(CvTreeEntry) > e->d_cv_tq.cap &&
+            (size_t)tq_cap * sizeof(CvTreeEntry) - e->d_cv_tq.cap > free_b / 4u) {
+            at->outcome = CvAttempt::ROWS_ONLY;
+            return VJ_OK;
         }
-        const uint8_t* d_gray;
-        size_t gray_frame_bytes;
-        int gray_stride;
-        int gray_ch = CH;
-        if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
-        HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
-        // VJ_FLAG_EQUALIZE_HIST: from here on the frames are the lane's equalized gray batch
-        if (equalize && (rc = enqueue_equalize(e, nullptr, &d_gray, &gray_frame_bytes, &gray_stride, &gray_ch, W, H, nf))) return rc;
-        if (si) {   // every level of every frame; from here on the "frames" are the gray canvases
-            if ((rc = enqueue_pyramid(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, gray_ch, pl->d_pyr_levels.p, pl->d_pyr_taps.p,
-                                      pl->n_pyr_levels, pl->n_pyr_units, pl->canvas_w, pl->canvas_h, pl->canvas_pitch)))
-                return rc;
-            d_gray = (const uint8_t*)e->d_pyr.p;
-            gray_frame_bytes = (size_t)pl->canvas_pitch * (size_t)IH;
-            gray_stride = (int)pl->canvas_pitch;
-            gray_ch = 1;
+    }
+    if ((rc = e->d_cv_tq.ensure((size_t)tq_cap * sizeof(CvTreeEntry)))) return rc;
+    at->tq_cap = tq_cap;
+    at->chain_pass = chain_pass;
+    HIP_TRY(hipMemsetAsync(e->d_skip_bits.p, 0, bits_bytes, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_cv_accept.p, 0, bits_bytes, e->stream));
+    bool two;
+    rc = begin_cv_tiles(cc, a, false, true, pl->prune, false, &two);
+    uint32_t* tq_count = a.det_count + 4 + 32;
+    CvTileArgs t = cv_tile_base_args(a);
+    t.tq_shift = chain_pass ? (uint32_t)pl->tq_shift : 0xffffffffu;   // one sub-queue per scale, or one flat queue (cv_tree_walk)
+    t.n_stages = pl->tree_prefix;        // the tiles stop after the prefix
+    t.bits = (unsigned long long*)e->d_skip_bits.p;
+    t.bits_frame_words = pl->bits_frame_words;
+    t.ws_begin = 0xffffffffu;            // no finish: whoever survives the prefix leaves the tile
+    t.ws_max = 0;
+    t.tq = (CvTreeEntry*)e->d_cv_tq.p;
+    t.tq_count = tq_count;
+    t.tq_cap = tq_cap;
+    if (!rc) rc = launch_cv_tile_classes(cc, a, t, 2, false, false, 0);
+    CvTreeArgs w;
+    memset(&w, 0, sizeof(w));
+    w.sum = a.sum;
+    w.table = a.table;
+    w.scales = a.scales;
+    w.stages = a.stages;
+    w.n_order = pl->n_order;
+    w.prefix = pl->tree_prefix;
+    w.sum_bytes = (uint32_t)((uint64_t)a.frame_elems * 4u * (uint64_t)nf);
+    w.tq = (const CvTreeEntry*)e->d_cv_tq.p;
+    w.tq_count = tq_count;
+    w.tq_cap = tq_cap;
+    w.reject = (unsigned long long*)e->d_skip_bits.p;
+    w.accept = (unsigned long long*)e->d_cv_accept.p;
+    w.bits_frame_words = pl->bits_frame_words;
+    w.n_frames = (uint32_t)nf;
+    w.segs = (const UnitDev*)pl->d_bit_segs.p;
+    w.n_segs = pl->n_bit_segs;
+    w.det = a.det;
+    w.det_count = a.det_count;
+    w.det_cap = a.det_cap;
+    if (chain_pass) {
+        // the tree is made of chains: chunks of one scale's survivors, swept like a linear cascade (cv_chain_sweep)
+        const int wb = std::max(1, e->n_cu * std::max(1, std::min(e->cv_tree_chain_blocks, 4)));
+        w.tq_shift = (uint32_t)pl->tq_shift;
+        w.n_scales = (uint32_t)pl->scales.size();
+        w.ticket = tq_count + 64;
+        w.chains = pl->chains;
+        w.total_waves = (uint32_t)wb * 4u;
+        w.chunk = (uint32_t)std::max(64, std::min(e->cv_tree_chunk, (int)CV_TQ_CHUNK));
+        int erc;
+        if ((erc = e->d_cv_fail_walk.ensure((size_t)w.total_waves * CV_TQ_CHUNK * sizeof(CvTreeEntry)))) return erc;
+        w.fail_scratch = e->d_cv_fail_walk.p;
+        if (!rc) rc = cascade_launched(launch_cv_tree_chain_pass(w, wb, e->stream));
+    } else if (!rc) {
+        rc = cascade_launched(launch_cv_tree_walk(w, std::max(1, e->n_cu * 4), e->stream));
+    }
+    if (!rc && pl->prune) {   // pruned windows: rejects of the walk, never accepted
+        CvPruneArgs pa = prune_args(e, pl, a, nf, nullptr);
+        pa.accept = (unsigned long long*)e->d_cv_accept.p;
+        rc = cascade_launched(launch_cv_prune_mark(pa, (int)std::max<uint32_t>(1u, (pa.n_segs * pa.n_frames + 3u) / 4u), e->stream));
+    }
+    if (!rc) rc = launch_cv_skip_resolve(cc, a.n_frames);
+    if (!rc) rc = cascade_launched(launch_cv_tree_emit(w, std::max(1, e->n_cu * 2), e->stream));
+    return end_cv_tiles(cc, two, rc);
+}
+
+// One attempt at the sub-batch of nf frames whose integral images are on the device: the arguments, then the launches of the path
+// the plan, the flags and `rows_only` choose, between lane0.ev[2] and ev[3], and the chain's hand-off behind them.
+static int enqueue_cv_attempt(CvCall& cc, int nf, bool rows_only, CvAttempt* at) {
+    vj_env* e = cc.e;
+    CvPlan* pl = cc.pl;
+    int rc;
+    if ((rc = e->d_cv_det.ensure((size_t)cc.det_cap * (cc.roc ? sizeof(CvRocDet) : sizeof(CvDet))))) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_cv_counts.p, 0, CV_COUNTS_BYTES, e->stream));
+    CvArgs& a = at->a;
+    a = cv_base_args(e, facts_of(*pl), tables_of(pl), CvGeom{cc.frame_elems, cc.stride, (uint32_t)cc.IH + 1u, (uint32_t)nf}, e->d_cv_det.p, cc.det_cap,
+                     e->d_cv_counts.p);
+    a.rows = (const UnitDev*)pl->d_rows.p;
+    a.n_rows = pl->n_rows;
+    if (pl->prune) {
+        a.edge_sum = (const uint32_t*)e->d_edge_sum.p;
+        a.prune = (const CvPruneDev*)pl->d_prune.p;
+    }
+    if (pl->is_tree && pl->chains.n != 0u && !cc.count && e->cv_tree_chains) {   // the rows kernel sweeps the chains too (cv_chain_sweep): a fail list per wave
+        a.chains = pl->chains;
+        const size_t waves = (size_t)std::max(1, e->n_cu * 4) * CV_WAVES_PER_BLOCK;
+        if ((rc = e->d_cv_fail_rows.ensure(waves * CV_QCAP * 16u))) return rc;
+        a.fail_scratch = e->d_cv_fail_rows.p;
+    }
+    HIP_TRY(hipEventRecord(e->lane0.ev[2], e->stream));
+    // (a stage tree's tile path leaves no per-stage counts of the visited windows: counted calls walk the rows)
+    const bool tiles = pl->n_tile_scales != 0 && pl->class_first[2] != 0 && !(pl->is_tree && (cc.count || rows_only));
+    if (tiles && pl->prune && (rc = e->d_cv_prune_bits.ensure((size_t)pl->bits_frame_words * 8u * (size_t)nf))) return rc;
+    if (!tiles) rc = launch_cv_rows(cc, a);
+    else if (pl->is_tree) rc = launch_cv_tree_tiles(cc, at);
+    else if (pl->scale_image) rc = launch_cv_scale_image_tiles(cc, a);
+    else rc = launch_cv_plain_tiles(cc, a);
+    if (rc || at->outcome != CvAttempt::LAUNCHED) return rc;
+    HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
+    if (cc.dev && (rc = cc.dev->enqueue(nf, pl, a, cc.det_cap))) return rc;   // (stream2 has joined: every path above ends on e->stream)
+    return VJ_OK;
+}
+
+// More prefix survivors than the tree queue (or one scale's sub-queue) holds?
+static bool cv_tq_overflowed(const CvCall& cc, const CvAttempt& at, const std::vector<unsigned long long>& h) {
+    if (at.tq_cap == 0u) return false;
+    const uint32_t* tqc = (const uint32_t*)(h.data() + 2 * VJ_MAX_STAGES) + 4 + 32;
+    if (!at.chain_pass) return tqc[0] > at.tq_cap;
+    for (const CvScaleDev& sd : cc.pl->scales)
+        if (sd.tile_th != 0u && (uint64_t)tqc[sd.tq_slot] > cv_tq_cap(sd.end_x, sd.end_y, at.a.n_frames, (uint32_t)cc.pl->tq_shift)) return true;
+    return false;
+}
+
+// A detection record as the call's rectangle.  CV_HAAR_SCALE_IMAGE (every ROC call is one): Rect(cvRound(x * factor),
+// cvRound(y * factor), winSize) (tempcv.cpp:1099-1100)
+template <class Det> static vj_rect cv_rect_of(const CvScaleDev* scales, const double* level_factor /* null: not scale-image */, const Det& d, int f0) {
+    const CvScaleDev& sd = scales[d.slot];
+    const int32_t x = level_factor ? cv_round((double)d.x * level_factor[d.slot]) : (int32_t)d.x;
+    const int32_t y = level_factor ? cv_round((double)d.y * level_factor[d.slot]) : (int32_t)d.y;
+    return vj_rect{x, y, (int32_t)sd.win_w, (int32_t)sd.win_h, 0.0f, f0 + (int32_t)d.frame, (int32_t)sd.scale_idx};
+}
+
+// The sub-batch [f0, f0 + nf): its integral images, then attempts until the detections, the tree queue and the hand-off's buffers
+// all held what came; its candidates appended to cc.all, raw.  *resplit: nothing ran — the same frames again, cc.max_frames at a time.
+static int run_cv_subbatch(CvCall& cc, int f0, int nf, bool* resplit) {
+    vj_env* e = cc.e;
+    CvPlan* pl = cc.pl;
+    CvChainDevice* dev = cc.dev;
+    vj_result* out = cc.out;
+    int rc;
+    *resplit = false;
+    if ((rc = enqueue_cv_ingest(e, cc.frames + f0, nf, cc.W, cc.H, cc.CH, cc.equalize, pl, pl->has_tilted || cc.need_tilted))) return rc;
+    bool rows_only = false, done = false;
+    const size_t sub_first = cc.all.size();
+    std::vector<unsigned long long> h;
+    // (the device hand-off may grow three buffers in turn — this cascade's detections, the units, the second cascade's detections)
+    for (int attempt = 0; attempt < (dev ? 5 : 2) && !done; ++attempt) {
+        CvAttempt at;
+        if ((rc = enqueue_cv_attempt(cc, nf, rows_only, &at))) return rc;
+        if (at.outcome == CvAttempt::RESPLIT) {
+            *resplit = true;
+            return VJ_OK;
         }
-        if (pl->prune) {   // the edge maps and their integral
-            uint32_t pitch = 0;
-            if ((rc = enqueue_canny(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, gray_ch, &pitch))) return rc;
-            if ((rc = enqueue_edge_integral(e, pitch, W, H, nf))) return rc;
-        }
-        if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, IW, IH, nf, gray_ch))) return rc;
-        if ((has_tilted || need_tilted) && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, IW, IH, nf, gray_ch))) return rc;
-        HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
-        bool rows_only = false, done = false, resplit = false;
-        const size_t sub_first = all.size();
-        // (the device hand-off may grow three buffers in turn — this cascade's detections, the units, the second cascade's detections)
-        for (int attempt = 0; attempt < (dev ? 5 : 2); ++attempt) {
-            if ((rc = d_det.ensure((size_t)det_cap * det_bytes))) return rc;
-            HIP_TRY(hipMemsetAsync(d_counts.p, 0, counts_bytes, e->stream));
-            CvArgs a;
-            memset(&a, 0, sizeof(a));
-            a.sum = (const uint32_t*)e->d_sum.p;
-            a.sqsum = (const uint64_t*)e->d_sqsum.p;
-            a.tilted = has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
-            a.n_order = pl->n_order;
-            a.table = (const uint32_t*)pl->d_table.p;
-            a.scales = (const CvScaleDev*)pl->d_scales.p;
-            a.stages = (const StageDev*)pl->d_stages.p;
-            a.rows = (const UnitDev*)pl->d_rows.p;
-            a.n_rows = pl->n_rows;
-            a.n_frames = (uint32_t)nf;
-            a.n_stages = pl->n_stages;
-            a.frame_elems = frame_elems;
-            a.stride = stride;
-            a.sum_h = (uint32_t)IH + 1u;
-            a.det = (CvDet*)d_det.p;
-            a.det_count = (uint32_t*)((unsigned long long*)d_counts.p + 2 * VJ_MAX_STAGES);
-            a.det_cap = det_cap;
-            a.stage_entered = (unsigned long long*)d_counts.p;
-            a.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
-            a.tree2 = pl->tree2 && !is_tree && !has_tilted && e->cv_tree2 ? 1u : 0u;
-            if (pl->prune) {
-                a.edge_sum = (const uint32_t*)e->d_edge_sum.p;
-                a.prune = (const CvPruneDev*)pl->d_prune.p;
-            }
-            if (is_tree && pl->chains.n != 0u && !count && e->cv_tree_chains) {   // the rows kernel sweeps the chains too (cv_chain_sweep): a fail list per wave
-                a.chains = pl->chains;
-                const size_t waves = (size_t)std::max(1, e->n_cu * 4) * CV_WAVES_PER_BLOCK;
-                if ((rc = e->d_cv_fail_rows.ensure(waves * CV_QCAP * 16u))) return rc;
-                a.fail_scratch = e->d_cv_fail_rows.p;
-            }
-            HIP_TRY(hipEventRecord(e->lane0.ev[2], e->stream));
-            int hrc = 0;
-            // (a stage tree's tile path leaves no per-stage counts of the visited windows: counted calls walk the rows)
-            const bool tiles = pl->n_tile_scales != 0 && pl->class_first[2] != 0 && !(is_tree && (count || rows_only));
-            if (tiles && pl->prune && (rc = e->d_cv_prune_bits.ensure((size_t)pl->bits_frame_words * 8u * (size_t)nf))) return rc;
-            uint32_t tq_cap = 0;
-            if (tiles && is_tree) {
-                // Stage tree: the tiles run the linear prefix on every grid window (cv_tile_pass<2>), cv_tree_walk the rest of the
-                // tree for the survivors, skip_resolve + cv_tree_emit the sequential walk.  cv_profile_pass keeps the large scales.
-                const size_t bits_bytes = (size_t)pl->bits_frame_words * 8u * (size_t)nf;
-                if ((rc = e->d_skip_bits.ensure(bits_bytes))) return rc;
-                if ((rc = e->d_cv_accept.ensure(bits_bytes))) return rc;
-                // room for 1 / 2^shift of the tile windows (a few percent survive the prefix); an overflow halves the shift and
-                // runs the call again; a forced capacity (tests) falls back to the rows instead
-                // (the shift belongs to the PLAN: one survivor-heavy workload does not make every later call allocate more)
-                if (pl->tq_shift < 0) pl->tq_shift = e->cv_tq_shift;
-                const bool chain_pass = pl->chains.n != 0u && pl->n_tile_scales <= 64u && e->cv_tree_queue_cap <= 0 && e->cv_tree_chains;
-                // want(n) = ((tile_windows * n) >> shift) + fixed: the flat queue, or every scale's sub-queue end to end
-                const uint64_t fixed = chain_pass ? (uint64_t)pl->n_tile_scales * 4096u + 4096u : 4096u;
-                const uint64_t want = ((pl->tile_windows * (uint64_t)nf) >> pl->tq_shift) + fixed;
-                if (e->cv_tree_queue_cap <= 0 && want > CV_TQ_MAX) {
-                    // A queue of more than CV_TQ_MAX entries: fewer frames per sub-batch (a clamped queue would drop the entries of
-                    // the later scales' sub-queues, which lie past its end), the rows when not even one frame fits
-                    const uint64_t fit = pl->tile_windows ? (((CV_TQ_MAX - fixed + 1u) << pl->tq_shift) - 1u) / pl->tile_windows : 0u;
-                    if (fit == 0u) {
-                        rows_only = true;
-                        --attempt;
-                        continue;
-                    }
-                    max_frames = (int)std::min<uint64_t>(fit, (uint64_t)max_frames);
-                    pl->tq_split_frames = max_frames;
-                    resplit = true;
-                    break;
-                }
-                tq_cap = e->cv_tree_queue_cap > 0 ? (uint32_t)e->cv_tree_queue_cap : (uint32_t)want;
-                {   // never more than a quarter of what the device has free: beyond that the rows take the call
-                    size_t free_b = 0, total_b = 0;
-                    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)tq_cap * sizeof(CvTreeEntry) > e->d_cv_tq.cap &&
-                        (size_t)tq_cap * sizeof(CvTreeEntry) - e->d_cv_tq.cap > free_b / 4u) {
-                        rows_only = true;
-                        --attempt;
-                        continue;
-                    }
-                }
-                if ((rc = e->d_cv_tq.ensure((size_t)tq_cap * sizeof(CvTreeEntry)))) return rc;
-                HIP_TRY(hipMemsetAsync(e->d_skip_bits.p, 0, bits_bytes, e->stream));
-                HIP_TRY(hipMemsetAsync(e->d_cv_accept.p, 0, bits_bytes, e->stream));
-                const bool two = e->concurrent && pl->n_rows_rest != 0;
-                hipStream_t sB = two ? e->stream2 : e->stream;
-                if (two) {
-                    HIP_TRY(hipEventRecord(e->fork_ev, e->stream));
-                    HIP_TRY(hipStreamWaitEvent(e->stream2, e->fork_ev, 0));
-                }
-                if (pl->n_rows_rest != 0) {
-                    CvArgs b = a;
-                    b.rows = (const UnitDev*)pl->d_rows_rest.p;
-                    b.n_rows = pl->n_rows_rest;
-                    const int nb = std::max(1, e->n_cu * (two ? pl->row_blocks : 4));
-                    b.total_waves = (uint32_t)nb * CV_WAVES_PER_BLOCK;
-                    hrc = launch_cv_profile_pass(b, trees, false, true, nb, sB, pl->prune);
-                }
-                uint32_t* tickets = a.det_count + 4;
-                uint32_t* tq_count = tickets + 32;
-                CvTileArgs t;
-                memset(&t, 0, sizeof(t));
-                t.tq_shift = chain_pass ? (uint32_t)pl->tq_shift : 0xffffffffu;   // one sub-queue per scale, or one flat queue (cv_tree_walk)
-                t.sum = a.sum;
-                t.tilted = a.tilted;
-                t.sqsum = a.sqsum;
-                t.table = a.table;
-                t.scales = a.scales;
-                t.stages = a.stages;
-                t.n_frames = (uint32_t)nf;
-                t.n_stages = pl->tree_prefix;        // the tiles stop after the prefix
-                t.frame_elems = frame_elems;
-                t.stride = stride;
-                t.sum_h = a.sum_h;
-                t.bits = (unsigned long long*)e->d_skip_bits.p;
-                t.bits_frame_words = pl->bits_frame_words;
-                t.repack_mask = ~3ull;
-                t.ws_begin = 0xffffffffu;            // no finish: whoever survives the prefix leaves the tile
-                t.ws_max = 0;
-                t.det = a.det;
-                t.det_count = a.det_count;
-                t.det_cap = det_cap;
-                t.tq = (CvTreeEntry*)e->d_cv_tq.p;
-                t.tq_count = tq_count;
-                t.tq_cap = tq_cap;
-                for (int cls = 0; cls < 2 && !hrc; ++cls) {
-                    const uint32_t n_cls = pl->class_first[cls + 1] - pl->class_first[cls];
-                    if (!n_cls) continue;
-                    CvTileArgs ta = t;
-                    ta.tiles = (const UnitDev*)pl->d_tiles.p + pl->class_first[cls];
-                    ta.n_tiles = n_cls;
-                    ta.lds_bytes = pl->class_lds[cls];
-                    ta.ticket = tickets + 8 * cls;
-                    const int per_cu = std::max(1, std::min(2, (int)((160u * 1024u - (uint32_t)pl->row_blocks * 20u * 1024u) / ta.lds_bytes)));
-                    const int tb = (int)std::min<uint64_t>((uint64_t)n_cls * (uint64_t)nf, (uint64_t)e->n_cu * (uint64_t)per_cu);
-                    hrc = launch_cv_tile_pass(ta, 2, false, false, std::max(1, tb), e->stream);
-                }
-                CvTreeArgs w;
-                memset(&w, 0, sizeof(w));
-                w.sum = a.sum;
-                w.table = a.table;
-                w.scales = a.scales;
-                w.stages = a.stages;
-                w.n_order = pl->n_order;
-                w.prefix = pl->tree_prefix;
-                w.sum_bytes = (uint32_t)((uint64_t)frame_elems * 4u * (uint64_t)nf);
-                w.tq = (const CvTreeEntry*)e->d_cv_tq.p;
-                w.tq_count = tq_count;
-                w.tq_cap = tq_cap;
-                w.reject = (unsigned long long*)e->d_skip_bits.p;
-                w.accept = (unsigned long long*)e->d_cv_accept.p;
-                w.bits_frame_words = pl->bits_frame_words;
-                w.n_frames = (uint32_t)nf;
-                w.segs = (const UnitDev*)pl->d_bit_segs.p;
-                w.n_segs = pl->n_bit_segs;
-                w.det = a.det;
-                w.det_count = a.det_count;
-                w.det_cap = det_cap;
-                if (chain_pass) {
-                    // the tree is made of chains: chunks of one scale's survivors, swept like a linear cascade (cv_chain_sweep)
-                    const int wb = std::max(1, e->n_cu * std::max(1, std::min(e->cv_tree_chain_blocks, 4)));
-                    w.tq_shift = (uint32_t)pl->tq_shift;
-                    w.n_scales = (uint32_t)scales.size();
-                    w.ticket = tq_count + 64;
-                    w.chains = pl->chains;
-                    w.total_waves = (uint32_t)wb * 4u;
-                    w.chunk = (uint32_t)std::max(64, std::min(e->cv_tree_chunk, (int)CV_TQ_CHUNK));
-                    if ((rc = e->d_cv_fail_walk.ensure((size_t)w.total_waves * CV_TQ_CHUNK * sizeof(CvTreeEntry)))) return rc;
-                    w.fail_scratch = e->d_cv_fail_walk.p;
-                    if (!hrc) hrc = launch_cv_tree_chain_pass(w, wb, e->stream);
-                } else if (!hrc) {
-                    hrc = launch_cv_tree_walk(w, std::max(1, e->n_cu * 4), e->stream);
-                }
-                if (!hrc && pl->prune) {   // pruned windows: rejects of the walk, never accepted
-                    CvPruneArgs pa = prune_args(e, pl, a, nf, nullptr);
-                    pa.accept = (unsigned long long*)e->d_cv_accept.p;
-                    hrc = launch_cv_prune_mark(pa, (int)std::max<uint32_t>(1u, (pa.n_segs * pa.n_frames + 3u) / 4u), e->stream);
-                }
-                if (!hrc) {
-                    CascadeArgs ra;
-                    memset(&ra, 0, sizeof(ra));
-                    ra.skip_bits = (unsigned long long*)e->d_skip_bits.p;
-                    ra.skip_frame_words = pl->bits_frame_words;
-                    ra.skip_segs = (const UnitDev*)pl->d_bit_segs.p;
-                    ra.n_skip_segs = pl->n_bit_segs;
-                    ra.n_frames = (uint32_t)nf;
-                    hrc = launch_skip_resolve(ra, std::max(1, e->n_cu * 2), e->stream);
-                }
-                if (!hrc) hrc = launch_cv_tree_emit(w, std::max(1, e->n_cu * 2), e->stream);
-                if (two) {
-                    HIP_TRY(hipEventRecord(e->join_ev, e->stream2));
-                    HIP_TRY(hipStreamWaitEvent(e->stream, e->join_ev, 0));
-                }
-            } else if (tiles && si) {
-                // CV_HAAR_SCALE_IMAGE: the levels whose grid fills a tile on cv_tile_pass<3> — one launch per LDS class, every grid window,
-                // no bitmap passes —, the small levels on the exhaustive-grid row kernel, concurrently on two streams as below
-                const bool two = e->concurrent && pl->n_rows_rest != 0;
-                hipStream_t sB = two ? e->stream2 : e->stream;
-                if (two) {
-                    HIP_TRY(hipEventRecord(e->fork_ev, e->stream));
-                    HIP_TRY(hipStreamWaitEvent(e->stream2, e->fork_ev, 0));
-                }
-                if (pl->n_rows_rest != 0) {
-                    CvArgs b = a;
-                    b.rows = (const UnitDev*)pl->d_rows_rest.p;
-                    b.n_rows = pl->n_rows_rest;
-                    const int nb = std::max(1, e->n_cu * (two ? pl->row_blocks : 4));
-                    b.total_waves = (uint32_t)nb * CV_WAVES_PER_BLOCK;
-                    hrc = launch_cv_profile_pass(b, trees, count, false, nb, sB, false, true);
-                }
-                CvTileArgs t;
-                memset(&t, 0, sizeof(t));
-                t.sum = a.sum;
-                t.tilted = a.tilted;
-                t.sqsum = a.sqsum;
-                t.table = a.table;
-                t.scales = a.scales;
-                t.stages = a.stages;
-                t.n_frames = (uint32_t)nf;
-                t.n_stages = pl->n_stages;
-                t.frame_elems = frame_elems;
-                t.stride = stride;
-                t.sum_h = a.sum_h;
-                t.repack_mask = ~3ull;
-                t.ws_begin = 3;
-                t.ws_max = (uint32_t)e->cv_tile_ws_max;
-                t.det = a.det;
-                t.det_count = a.det_count;
-                t.det_cap = det_cap;
-                t.stage_entered = a.stage_entered;
-                uint32_t* tickets = a.det_count + 4;
-                for (int cls = 0; cls < 2 && !hrc; ++cls) {
-                    const uint32_t n_cls = pl->class_first[cls + 1] - pl->class_first[cls];
-                    if (!n_cls) continue;
-                    CvTileArgs ta = t;
-                    ta.tiles = (const UnitDev*)pl->d_tiles.p + pl->class_first[cls];
-                    ta.n_tiles = n_cls;
-                    ta.lds_bytes = pl->class_lds[cls];
-                    ta.ticket = tickets + 8 * cls;
-                    const int per_cu = std::max(1, std::min(2, (int)((160u * 1024u - (uint32_t)pl->row_blocks * 20u * 1024u) / ta.lds_bytes)));
-                    const int tb = (int)std::min<uint64_t>((uint64_t)n_cls * (uint64_t)nf, (uint64_t)e->n_cu * (uint64_t)per_cu);
-                    hrc = launch_cv_tile_pass(ta, 3, count, pl->tree2, std::max(1, tb), e->stream);
-                }
-                if (two) {
-                    HIP_TRY(hipEventRecord(e->join_ev, e->stream2));
-                    HIP_TRY(hipStreamWaitEvent(e->stream, e->join_ev, 0));
-                }
-            } else if (tiles) {
-                // The small scales on LDS tiles (vj_cv_tile.hip), the rest on cv_profile_pass, concurrently on two streams:
-                // the row kernel is bound by the texture-address unit, the tile kernel by LDS and VALU.  The row kernel is
-                // launched first with one workgroup per CU so that the tile workgroups find their LDS share next to it.
-                if ((rc = e->d_skip_bits.ensure((size_t)pl->bits_frame_words * 8u * (size_t)nf))) return rc;
-                HIP_TRY(hipMemsetAsync(e->d_skip_bits.p, 0, (size_t)pl->bits_frame_words * 8u * (size_t)nf, e->stream));
-                const bool two = e->concurrent && pl->n_rows_rest != 0;
-                hipStream_t sB = two ? e->stream2 : e->stream;
-                if (two) {
-                    HIP_TRY(hipEventRecord(e->fork_ev, e->stream));
-                    HIP_TRY(hipStreamWaitEvent(e->stream2, e->fork_ev, 0));
-                }
-                if (pl->n_rows_rest != 0) {
-                    CvArgs b = a;
-                    b.rows = (const UnitDev*)pl->d_rows_rest.p;
-                    b.n_rows = pl->n_rows_rest;
-                    const int nb = std::max(1, e->n_cu * (two ? pl->row_blocks : 4));
-                    b.total_waves = (uint32_t)nb * CV_WAVES_PER_BLOCK;
-                    hrc = launch_cv_profile_pass(b, trees, count, is_tree, nb, sB, pl->prune);
-                }
-                CvTileArgs t;
-                memset(&t, 0, sizeof(t));
-                t.sum = a.sum;
-                t.tilted = a.tilted;
-                t.sqsum = a.sqsum;
-                t.table = a.table;
-                t.scales = a.scales;
-                t.stages = a.stages;
-                t.n_frames = (uint32_t)nf;
-                t.n_stages = pl->n_stages;
-                t.frame_elems = frame_elems;
-                t.stride = stride;
-                t.sum_h = a.sum_h;
-                t.bits = (unsigned long long*)e->d_skip_bits.p;
-                t.bits_frame_words = pl->bits_frame_words;
-                t.repack_mask = ~3ull;        // before every stage from 2 on (as the clod profile's tiles)
-                t.ws_begin = 3;
-                t.ws_max = (uint32_t)e->cv_tile_ws_max;
-                t.det = a.det;
-                t.det_count = a.det_count;
-                t.det_cap = det_cap;
-                t.stage_entered = a.stage_entered;
-                uint32_t* tickets = a.det_count + 4;
-                for (int mode = 0; mode < 2 && !hrc; ++mode) {
-                    for (int cls = 0; cls < 2 && !hrc; ++cls) {
-                        const uint32_t n_cls = pl->class_first[cls + 1] - pl->class_first[cls];
-                        if (!n_cls) continue;
-                        CvTileArgs ta = t;
-                        ta.tiles = (const UnitDev*)pl->d_tiles.p + pl->class_first[cls];
-                        ta.n_tiles = n_cls;
-                        ta.lds_bytes = pl->class_lds[cls];
-                        ta.ticket = tickets + 8 * (mode * 2 + cls);
-                        const int per_cu = std::max(1, std::min(2, (int)((160u * 1024u - (uint32_t)pl->row_blocks * 20u * 1024u) / ta.lds_bytes)));
-                        const int tb = (int)std::min<uint64_t>((uint64_t)n_cls * (uint64_t)nf, (uint64_t)e->n_cu * (uint64_t)per_cu);
-                        hrc = launch_cv_tile_pass(ta, mode, count, pl->tree2, std::max(1, tb), e->stream);
-                    }
-                    if (mode == 0 && !hrc && pl->prune) {   // pruned windows are "zeros" of the walk (prune bitmap: cv_prune_mark)
-                        // one wave per window row of a tile scale: the rows' words are latency-bound gathers, thousands of waves hide them
-                        const CvPruneArgs pa = prune_args(e, pl, a, nf, nullptr);
-                        hrc = launch_cv_prune_mark(pa, (int)std::max<uint32_t>(1u, (pa.n_segs * pa.n_frames + 3u) / 4u), e->stream);
-                    }
-                    if (mode == 0 && !hrc) {   // reject bits -> visited bits, one recurrence domain per window row (skip_resolve)
-                        CascadeArgs ra;
-                        memset(&ra, 0, sizeof(ra));
-                        ra.skip_bits = (unsigned long long*)e->d_skip_bits.p;
-                        ra.skip_frame_words = pl->bits_frame_words;
-                        ra.skip_segs = (const UnitDev*)pl->d_bit_segs.p;
-                        ra.n_skip_segs = pl->n_bit_segs;
-                        ra.n_frames = (uint32_t)nf;
-                        hrc = launch_skip_resolve(ra, std::max(1, e->n_cu * 2), e->stream);
-                    }
-                    if (mode == 0 && !hrc && pl->prune) {   // ... visited but not evaluated: out of the visited bits, into counts.windows
-                        CvPruneArgs pa = prune_args(e, pl, a, nf, count ? a.stage_entered + VJ_MAX_STAGES : nullptr);
-                        hrc = launch_cv_prune_visited(pa, std::max(1, e->n_cu * 2), e->stream);
-                    }
-                }
-                if (two) {
-                    HIP_TRY(hipEventRecord(e->join_ev, e->stream2));
-                    HIP_TRY(hipStreamWaitEvent(e->stream, e->join_ev, 0));
-                }
-            } else {
-                // four workgroups (16 waves) per CU: every wave walks its own window row, and the rows in flight on an XCD
-                // should stay inside its 4 MiB L2 (64 x 1080p: 376 / 235 / 179 / 153 / 173 / 194 / 193 ms for 1 / 2 / 3 / 4 / 5 / 6 / 8)
-                const int n_blocks = std::max(1, e->n_cu * 4);
-                a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
-                hrc = launch_cv_profile_pass(a, trees, count, is_tree, n_blocks, e->stream, pl->prune, si, roc != nullptr);
-            }
-            if (hrc) {
-                set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
-                return VJ_ERR_HIP;
-            }
-            HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
-            if (dev && (rc = dev->enqueue(nf, pl, a, det_cap))) return rc;   // (stream2 has joined: every branch above ends on e->stream)
-            std::vector<unsigned long long> h((counts_bytes + 7) / 8);
-            HIP_TRY(hipMemcpyAsync(h.data(), d_counts.p, counts_bytes, hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            const uint32_t n_det = (uint32_t)(h[2 * VJ_MAX_STAGES] & 0xffffffffull);
-            bool tq_overflow = false;
-            if (tq_cap != 0u) {   // more prefix survivors than the tree queue (or one scale's sub-queue) holds?
-                const uint32_t* tqc = (const uint32_t*)(h.data() + 2 * VJ_MAX_STAGES) + 4 + 32;
-                const bool per_scale = pl->chains.n != 0u && pl->n_tile_scales <= 64u && e->cv_tree_queue_cap <= 0 && e->cv_tree_chains;
-                if (!per_scale) {
-                    tq_overflow = tqc[0] > tq_cap;
-                } else {
-                    for (const CvScaleDev& sd : scales)
-                        if (sd.tile_th != 0u && (uint64_t)tqc[sd.tq_slot] > cv_tq_cap(sd.end_x, sd.end_y, (uint32_t)nf, (uint32_t)pl->tq_shift)) tq_overflow = true;
-                }
-            }
-            if (tq_overflow) {
-                if (e->cv_tree_queue_cap > 0 || pl->tq_shift <= 0) rows_only = true;
-                else pl->tq_shift = std::max(0, pl->tq_shift - 2);      // 1/16 -> 1/4 -> every window, for THIS plan
-                --attempt;
-                continue;
-            }
-            if (n_det > det_cap) {   // overflow: grow and redo this sub-batch's cascade
-                det_cap = grown_cap(det_cap, n_det);
-                if (dev) e->cv_chain_info.reruns += 1;
-                continue;
-            }
-            if (dev) {
-                bool again = false;
-                if ((rc = dev->check(&again))) return rc;
-                if (again) continue;
-            }
-            float ms_i = 0, ms_c = 0, ms_t = 0;
-            HIP_TRY(hipEventElapsedTime(&ms_i, e->lane0.ev[0], e->lane0.ev[1]));
-            HIP_TRY(hipEventElapsedTime(&ms_c, e->lane0.ev[2], e->lane0.ev[3]));
-            HIP_TRY(hipEventElapsedTime(&ms_t, e->lane0.ev[0], e->lane0.ev[3]));
-            out->timing.integral_ms += ms_i;
-            out->timing.cascade_ms += ms_c;
-            out->timing.total_ms += ms_t;
-            out->timing.n_cascade_launches = 1;
-            if (count) {
-                for (size_t s = 0; s < pl->n_stages; ++s) out->counters.stage_entered[s] += h[s];
-                out->counters.windows += h[VJ_MAX_STAGES];
-            }
-            if (roc) {
-                std::vector<CvRocDet> rraw(n_det);
-                if (n_det) HIP_TRY(hipMemcpy(rraw.data(), d_det.p, (size_t)n_det * sizeof(CvRocDet), hipMemcpyDeviceToHost));
-                for (const CvRocDet& d : rraw) {
-                    all.push_back(vj_rect{cv_round((double)d.x * pl->level_factor[d.slot]), cv_round((double)d.y * pl->level_factor[d.slot]),
-                                          (int32_t)scales[d.slot].win_w, (int32_t)scales[d.slot].win_h, 0.0f, f0 + (int32_t)d.frame,
-                                          (int32_t)scales[d.slot].scale_idx});
-                    all_levels.push_back((int32_t)d.level);
-                    all_weights.push_back(d.weight);
-                }
-                done = true;
-                break;
-            }
-            if (dev && dev->grouped && !dev->fallback) {   // the grouped rectangles are read back instead (CvChainDevice::finish)
-                done = true;
-                break;
-            }
-            std::vector<CvDet> raw(n_det);
-            if (n_det) HIP_TRY(hipMemcpy(raw.data(), d_det.p, (size_t)n_det * sizeof(CvDet), hipMemcpyDeviceToHost));
-            for (const CvDet& d : raw)
-                if (si)   // Rect(cvRound(x * factor), cvRound(y * factor), winSize) (tempcv.cpp:1099-1100)
-                    all.push_back(vj_rect{cv_round((double)d.x * pl->level_factor[d.slot]), cv_round((double)d.y * pl->level_factor[d.slot]),
-                                          (int32_t)scales[d.slot].win_w, (int32_t)scales[d.slot].win_h, 0.0f, f0 + (int32_t)d.frame,
-                                          (int32_t)scales[d.slot].scale_idx});
-                else
-                all.push_back(vj_rect{(int32_t)d.x, (int32_t)d.y, (int32_t)scales[d.slot].win_w, (int32_t)scales[d.slot].win_h,
-                                      0.0f, f0 + (int32_t)d.frame, (int32_t)scales[d.slot].scale_idx});
-            done = true;
-            break;
-        }
-        if (resplit) {   // the same frames again, in sub-batches of max_frames
-            nf = 0;
+        uint32_t n_det = 0;
+        if (at.outcome == CvAttempt::LAUNCHED && (rc = read_cv_counts(e, CV_COUNTS_BYTES, &h, &n_det))) return rc;
+        if (at.outcome == CvAttempt::ROWS_ONLY || cv_tq_overflowed(cc, at, h)) {   // (neither consumes an attempt)
+            if (at.outcome == CvAttempt::ROWS_ONLY || e->cv_tree_queue_cap > 0 || pl->tq_shift <= 0) rows_only = true;
+            else pl->tq_shift = std::max(0, pl->tq_shift - 2);      // 1/16 -> 1/4 -> every window, for THIS plan
+            --attempt;
             continue;
         }
-        if (!done) {   // (cannot happen: the counts of a repeated pass are the counts that sized its buffers)
-            set_error("vj_detect_opencv: the detection buffer overflowed twice");
-            return VJ_ERR_LIMIT;
+        if (n_det > cc.det_cap) {   // overflow: grow and redo this sub-batch's cascade
+            cc.det_cap = grown_cap(cc.det_cap, n_det);
+            if (dev) e->cv_chain_info.reruns += 1;
+            continue;
         }
         if (dev) {
-            if ((rc = dev->finish(f0, nf, all.data() + sub_first, all.size() - sub_first, sub_first))) return rc;
-        } else if (hook && (rc = (*hook)(f0, nf, all.data() + sub_first, all.size() - sub_first))) return rc;
+            bool again = false;
+            if ((rc = dev->check(&again))) return rc;
+            if (again) continue;
+        }
+        float ms_i = 0, ms_c = 0, ms_t = 0;
+        HIP_TRY(hipEventElapsedTime(&ms_i, e->lane0.ev[0], e->lane0.ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms_c, e->lane0.ev[2], e->lane0.ev[3]));
+        HIP_TRY(hipEventElapsedTime(&ms_t, e->lane0.ev[0], e->lane0.ev[3]));
+        out->timing.integral_ms += ms_i;
+        out->timing.cascade_ms += ms_c;
+        out->timing.total_ms += ms_t;
+        out->timing.n_cascade_launches = 1;
+        if (cc.count) add_cv_counters(h, pl->n_stages, &out->counters);
+        done = true;
+        const CvScaleDev* scales = pl->scales.data();
+        const double* level_factor = pl->scale_image ? pl->level_factor.data() : nullptr;
+        if (cc.roc) {
+            std::vector<CvRocDet> raw;
+            if ((rc = read_cv_dets(e, n_det, &raw))) return rc;
+            for (const CvRocDet& d : raw) {
+                cc.all.push_back(cv_rect_of(scales, level_factor, d, f0));
+                cc.all_levels.push_back((int32_t)d.level);
+                cc.all_weights.push_back(d.weight);
+            }
+        } else if (!(dev && dev->grouped && !dev->fallback)) {   // (else the grouped rectangles are read back instead: CvChainDevice::finish)
+            std::vector<CvDet> raw;
+            if ((rc = read_cv_dets(e, n_det, &raw))) return rc;
+            for (const CvDet& d : raw) cc.all.push_back(cv_rect_of(scales, level_factor, d, f0));
+        }
     }
+    if (!done) {   // (cannot happen: the counts of a repeated pass are the counts that sized its buffers)
+        set_error("vj_detect_opencv: the detection buffer overflowed twice");
+        return VJ_ERR_LIMIT;
+    }
+    if (dev) return dev->finish(f0, nf, cc.all.data() + sub_first, cc.all.size() - sub_first, sub_first);
+    if (cc.hook) return (*cc.hook)(f0, nf, cc.all.data() + sub_first, cc.all.size() - sub_first);
+    return VJ_OK;
+}
+
+// The call's candidates as its result: in order, grouped, the counters' totals
+static int collect_cv_result(CvCall& cc) {
+    std::vector<vj_rect>& all = cc.all;
+    const CvRocCall* roc = cc.roc;
     // the device grouped every frame (or, where it could not, the host hook did): the regions of all sub-batches ARE the result
-    const bool pre_grouped = dev && dev->grouped;
-    if (pre_grouped) all = *dev->regions;
+    const bool pre_grouped = cc.dev && cc.dev->grouped;
+    if (pre_grouped) all = *cc.dev->regions;
     if (roc) {   // the key is unique (one report per grid position of a level): levels and weights follow their rectangles
         std::vector<size_t> idx(all.size());
         for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
-        std::sort(idx.begin(), idx.end(), [&](size_t i, size_t j) {
-            return std::tie(all[i].frame, all[i].scale_idx, all[i].y, all[i].x) < std::tie(all[j].frame, all[j].scale_idx, all[j].y, all[j].x);
-        });
+        std::sort(idx.begin(), idx.end(), [&](size_t i, size_t j) { return cv_rect_before(all[i], all[j]); });
         std::vector<vj_rect> sorted(all.size());
         roc->levels->resize(all.size());
         roc->weights->resize(all.size());
         for (size_t i = 0; i < idx.size(); ++i) {
             sorted[i] = all[idx[i]];
-            (*roc->levels)[i] = all_levels[idx[i]];
-            (*roc->weights)[i] = all_weights[idx[i]];
+            (*roc->levels)[i] = cc.all_levels[idx[i]];
+            (*roc->weights)[i] = cc.all_weights[idx[i]];
         }
         all.swap(sorted);
-    } else if (!pre_grouped)
-    std::sort(all.begin(), all.end(), [](const vj_rect& a, const vj_rect& b) {
-        return std::tie(a.frame, a.scale_idx, a.y, a.x) < std::tie(b.frame, b.scale_idx, b.y, b.x);
-    });
-    out->count = (uint32_t)all.size();
-    if (!all.empty()) {
-        out->rects = (vj_rect*)malloc(all.size() * sizeof(vj_rect));
-        if (!out->rects) return VJ_ERR_NOMEM;
-        memcpy(out->rects, all.data(), all.size() * sizeof(vj_rect));
+    } else if (!pre_grouped) {
+        std::sort(all.begin(), all.end(), cv_rect_before);
     }
-    if (!roc && !pre_grouped && p->min_neighbors != 0 && out->count) {   // groupRectangles(rectList, max(minNeighbors, 1), GROUP_EPS)
-        rc = vj_group_rectangles(out->rects, &out->count, (int)std::max<uint32_t>(p->min_neighbors, 1u), 0.2);
-        if (rc) return rc;
-    }
-    if (count) {
-        vj_counters& k = out->counters;
-        uint64_t rect_evals = 0;
-        for (size_t s = 0; s < pl->n_stages; ++s) {
-            k.stump_evals += k.stage_entered[s] * prog.n_nodes[s];
-            rect_evals += k.stage_entered[s] * prog.n_rects[s];
-        }
-        k.gather_bytes = 48ull * k.stage_entered[0] + 16ull * rect_evals;
-    }
+    const int rc = cv_result_epilogue(all, cc.count ? &cc.pl->prog : nullptr, cc.out);
+    if (rc) return rc;
+    // groupRectangles(rectList, max(minNeighbors, 1), GROUP_EPS)
+    if (!roc && !pre_grouped && cc.p->min_neighbors != 0 && cc.out->count)
+        return vj_group_rectangles(cc.out->rects, &cc.out->count, (int)std::max<uint32_t>(cc.p->min_neighbors, 1u), 0.2);
     return VJ_OK;
+}
+
+// vj_detect_opencv.  need_tilted: compute the tilted integral even when `c` has no tilted feature (someone after it reads it).
+// roc: vj_detect_opencv_roc's scale-image call — the kernels report CvRocDet records; the rectangles come back raw (ungrouped),
+// sorted, with their levels and weights in roc's vectors.
+int detect_opencv_impl(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_cv_params* p, vj_result* out,
+                       bool need_tilted, const CvSubBatchHook* hook, const CvRocCall* roc = nullptr, CvChainDevice* dev = nullptr) {
+    if (!e || !c || !p || !out || n_frames < 0 || (n_frames > 0 && !frames)) return VJ_ERR_ARG;
+    memset(out, 0, sizeof(*out));
+    if (n_frames == 0) return VJ_OK;
+    CvCall cc{};
+    int rc = check_cv_call(frames, n_frames, p, &cc.W, &cc.H, &cc.CH);
+    if (rc) return rc;
+    // VJ_FLAG_EQUALIZE_HIST is read here and nowhere else: the plan, its key and the kernels see the parameters without it
+    vj_cv_params p_plain = *p;
+    p_plain.flags &= ~(uint32_t)VJ_FLAG_EQUALIZE_HIST;
+    cc.e = e;
+    cc.frames = frames;
+    cc.p = &p_plain;
+    cc.out = out;
+    cc.equalize = (p->flags & VJ_FLAG_EQUALIZE_HIST) != 0u;
+    cc.need_tilted = need_tilted;
+    cc.count = (p->flags & VJ_FLAG_COUNTERS) != 0;
+    cc.hook = hook;
+    cc.roc = roc;
+    cc.dev = dev;
+    HIP_TRY(hipSetDevice(e->device));
+    if ((rc = get_cv_plan(e, c, cc.W, cc.H, cc.p, n_frames, &cc.pl, roc))) return rc;
+    const CvPlan* pl = cc.pl;
+    if (pl->find_biggest) return detect_biggest(e, c, cc.pl, frames, n_frames, cc.W, cc.H, cc.CH, cc.p, cc.equalize, out);
+    // CV_HAAR_SCALE_IMAGE: the integral images are those of the canvas that holds the pyramid's levels
+    const int IW = pl->scale_image ? (int)pl->canvas_w : cc.W;
+    cc.IH = pl->scale_image ? (int)pl->canvas_h : cc.H;
+    cc.stride = (uint32_t)IW + 1u;
+    cc.frame_elems = frame_elems_for(IW, cc.IH);
+    if ((rc = e->d_cv_counts.ensure(CV_COUNTS_BYTES))) return rc;
+    cc.max_frames = cv_max_frames(e, n_frames, cc.frame_elems);
+    {   // the detection counter is 32-bit: a sub-batch holds fewer than 2^32 windows, so it cannot wrap
+        uint64_t frame_windows = 0;
+        for (const CvScaleDev& sd : pl->scales) frame_windows += (uint64_t)sd.end_x * sd.end_y;
+        if (frame_windows > 0xffffffffull) {
+            set_error("vj_detect_opencv: %llu windows per frame, more than a 32-bit detection count holds",
+                      (unsigned long long)frame_windows);
+            return VJ_ERR_LIMIT;
+        }
+        if (frame_windows) cc.max_frames = (int)std::min<uint64_t>((uint64_t)cc.max_frames, 0xffffffffull / frame_windows);
+    }
+    // (a ROC call reports several times as many windows: its buffer starts at the configured "det_cap" and grows the same way)
+    // (the chain's device hand-off too: its buffers all start at "det_cap", so that a small value drives every regrow path)
+    cc.det_cap = roc || dev ? std::max(1u, e->det_cap_init) : 1u << 16;
+    for (int f0 = 0, nf = 0; f0 < n_frames && pl->n_rows != 0; f0 += nf) {
+        nf = std::min(cc.max_frames, n_frames - f0);
+        bool resplit = false;
+        if ((rc = run_cv_subbatch(cc, f0, nf, &resplit))) return rc;
+        if (resplit) nf = 0;   // the same frames again, in sub-batches of cc.max_frames
+    }
+    return collect_cv_result(cc);
 }
 
 // ------------------------------------------------------------------------ a cascade inside regions
@@ -1240,68 +1274,31 @@ int run_cv_roi_pass(vj_env* e, const vj_cascade* c, int W, int H, int nf, const 
     const size_t counts_bytes = 2 * VJ_MAX_STAGES * sizeof(uint64_t) + 16;   // stage_entered | visited ... | detection count
     if ((rc = d_counts.ensure(counts_bytes))) return rc;
     uint32_t det_cap = 1u << 16;
-    for (int attempt = 0;; ++attempt) {
-        if (attempt == 2) {   // (cannot happen: the count of a repeated pass is the count that sized its buffer)
-            set_error("vj_detect_opencv_rois: the detection buffer overflowed twice");
-            return VJ_ERR_LIMIT;
-        }
-        if ((rc = d_det.ensure((size_t)det_cap * sizeof(CvDet)))) return rc;
-        HIP_TRY(hipMemsetAsync(d_counts.p, 0, counts_bytes, e->stream));
+    std::vector<unsigned long long> h;
+    uint32_t n_det = 0;
+    rc = run_cv_pass_until_fit(e, counts_bytes, &det_cap, "vj_detect_opencv_rois: the detection buffer overflowed twice", [&](uint32_t cap) {
         CvRoiArgs ra;
         memset(&ra, 0, sizeof(ra));
         CvArgs& a = ra.cv;
-        a.sum = (const uint32_t*)e->d_sum.p;
-        a.sqsum = (const uint64_t*)e->d_sqsum.p;
-        a.tilted = pl->has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
-        a.n_order = pl->n_order;
-        a.table = (const uint32_t*)pl->d_table.p;
-        a.scales = (const CvScaleDev*)pl->d_scales.p;
-        a.stages = (const StageDev*)pl->d_stages.p;
-        a.n_frames = (uint32_t)nf;
-        a.n_stages = pl->n_stages;
-        a.frame_elems = frame_elems;
-        a.stride = stride;
-        a.sum_h = (uint32_t)H + 1u;
-        a.det = (CvDet*)d_det.p;
-        a.det_count = (uint32_t*)((unsigned long long*)d_counts.p + 2 * VJ_MAX_STAGES);
-        a.det_cap = det_cap;
-        a.stage_entered = (unsigned long long*)d_counts.p;
-        a.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
-        a.tree2 = pl->tree2 && !pl->is_tree && !pl->has_tilted && e->cv_tree2 ? 1u : 0u;
+        a = cv_base_args(e, facts_of(*pl), tables_of(pl), CvGeom{frame_elems, stride, (uint32_t)H + 1u, (uint32_t)nf}, d_det.p, cap, d_counts.p);
         ra.rois = (const CvRoiDev*)e->d_cv_rois.p;
         ra.units = (const CvRoiUnit*)e->d_cv_roi_units.p;
         ra.n_units = (uint32_t)units.size();
         // one wave per unit, at most four workgroups (16 waves) per CU; the rest by stride
         const int n_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((units.size() + CV_WAVES_PER_BLOCK - 1) / CV_WAVES_PER_BLOCK, (uint64_t)std::max(1, e->n_cu * 4)));
         a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
-        HIP_TRY(hipEventRecord(e->lane0.ev[2], e->stream));
-        const int hrc = launch_cv_roi_pass(ra, pl->trees, count, pl->is_tree, n_blocks, e->stream);
-        if (hrc) {
-            set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
-            return VJ_ERR_HIP;
-        }
-        HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
-        std::vector<unsigned long long> h((counts_bytes + 7) / 8);
-        HIP_TRY(hipMemcpyAsync(h.data(), d_counts.p, counts_bytes, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        const uint32_t n_det = (uint32_t)(h[2 * VJ_MAX_STAGES] & 0xffffffffull);
-        if (n_det > det_cap) {   // overflow: grow and run the pass again
-            det_cap = grown_cap(det_cap, n_det);
-            continue;
-        }
-        float ms_c = 0;
-        HIP_TRY(hipEventElapsedTime(&ms_c, e->lane0.ev[2], e->lane0.ev[3]));
-        out->timing.cascade_ms += ms_c;
-        out->timing.total_ms += ms_c;
-        out->timing.n_cascade_launches += 1;
-        if (count) {
-            for (size_t s = 0; s < pl->n_stages; ++s) out->counters.stage_entered[s] += h[s];
-            out->counters.windows += h[VJ_MAX_STAGES];
-        }
-        std::vector<CvDet> raw(n_det);
-        if (n_det) HIP_TRY(hipMemcpy(raw.data(), d_det.p, (size_t)n_det * sizeof(CvDet), hipMemcpyDeviceToHost));
-        return cv_roi_rects_of(raw.data(), raw.size(), pl->factors, regs, all);
-    }
+        return cascade_launched(launch_cv_roi_pass(ra, pl->trees, count, pl->is_tree, n_blocks, e->stream));
+    }, &h, &n_det);
+    if (rc) return rc;
+    float ms_c = 0;
+    HIP_TRY(hipEventElapsedTime(&ms_c, e->lane0.ev[2], e->lane0.ev[3]));
+    out->timing.cascade_ms += ms_c;
+    out->timing.total_ms += ms_c;
+    out->timing.n_cascade_launches += 1;
+    if (count) add_cv_counters(h, pl->n_stages, &out->counters);
+    std::vector<CvDet> raw;
+    if ((rc = read_cv_dets(e, n_det, &raw))) return rc;
+    return cv_roi_rects_of(raw.data(), raw.size(), pl->factors, regs, all);
 }
 
 // ------------------------------------------------------------------------ the chain's device hand-off
@@ -1394,35 +1391,14 @@ int CvChainDevice::enqueue(int nf, const CvPlan* pl, const CvArgs& a, uint32_t d
     CvRoiArgs ra;
     memset(&ra, 0, sizeof(ra));
     CvArgs& b = ra.cv;
-    b.sum = (const uint32_t*)e->d_sum.p;
-    b.sqsum = (const uint64_t*)e->d_sqsum.p;
-    b.tilted = rp->has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
-    b.n_order = rp->n_order;
-    b.table = (const uint32_t*)rp->d_table.p;
-    b.scales = (const CvScaleDev*)rp->d_scales.p;
-    b.stages = (const StageDev*)rp->d_stages.p;
-    b.n_frames = (uint32_t)nf;
-    b.n_stages = rp->n_stages;
-    b.frame_elems = frame_elems;
-    b.stride = stride;
-    b.sum_h = (uint32_t)H + 1u;
-    b.det = (CvDet*)e->d_cv_det2.p;
-    b.det_count = (uint32_t*)((unsigned long long*)e->d_cv_counts2.p + 2 * VJ_MAX_STAGES);
-    b.det_cap = det2_cap;
-    b.stage_entered = (unsigned long long*)e->d_cv_counts2.p;
-    b.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
-    b.tree2 = rp->tree2 && !rp->is_tree && !rp->has_tilted && e->cv_tree2 ? 1u : 0u;
+    b = cv_base_args(e, facts_of(*rp), tables_of(rp), CvGeom{frame_elems, stride, (uint32_t)H + 1u, (uint32_t)nf}, e->d_cv_det2.p, det2_cap, e->d_cv_counts2.p);
     ra.rois = (const CvRoiDev*)e->d_cv_rois.p;
     ra.units = (const CvRoiUnit*)e->d_cv_roi_units.p;
     ra.n_units_dev = &g.state->n_units_run;
     // (the host does not know the unit count: the full four workgroups per CU; the units go round by stride)
     const int n_blocks = std::max(1, e->n_cu * 4);
     b.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
-    hrc = launch_cv_roi_pass(ra, rp->trees, (p_second->flags & VJ_FLAG_COUNTERS) != 0, rp->is_tree, n_blocks, e->stream);
-    if (hrc) {
-        set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
-        return VJ_ERR_HIP;
-    }
+    if (const int rc2 = cascade_launched(launch_cv_roi_pass(ra, rp->trees, (p_second->flags & VJ_FLAG_COUNTERS) != 0, rp->is_tree, n_blocks, e->stream))) return rc2;
     HIP_TRY(hipEventRecord(e->cv_chain_ev[2], e->stream));
     HIP_TRY(hipMemcpyAsync(&h_state, g.state, sizeof(CvChainState), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(h_counts2.data(), e->d_cv_counts2.p, counts2_bytes, hipMemcpyDeviceToHost, e->stream));
@@ -1526,9 +1502,7 @@ struct CvPoints {
         return pc.has_tilted ? enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH) : VJ_OK;
     }
     static void fill_args(const vj_env* e, const PointCascade& pc, uint32_t, CvPointArgs* a) {
-        a->tilted = pc.has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
-        a->tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
-        a->tree2 = pc.tree2 && !pc.is_tree && !pc.has_tilted && e->cv_tree2 ? 1u : 0u;
+        fill_shape_args(e, facts_of(pc), a);
     }
     static int launch(const CvPointArgs& a, const PointCascade& pc, int n_blocks, void* stream) {
         return launch_cv_points_pass(a, pc.trees, pc.is_tree, n_blocks, stream);
@@ -1557,7 +1531,6 @@ int run_cv_rois_levels(vj_env* e, const vj_cascade* c, const vj_image* frames, i
     int rc = cv_cascade_host(c, &ch);
     if (rc) return rc;
     *prog_out = ch.prog;
-    const StageProgram& prog = *prog_out;
     const std::vector<uint32_t>& order = ch.order;
     const CvShape& shape = ch.shape;
     const std::vector<StageDev>& stages = ch.stages;
@@ -1569,9 +1542,7 @@ int run_cv_rois_levels(vj_env* e, const vj_cascade* c, const vj_image* frames, i
     DevBuf& d_counts = e->d_cv_counts;
     const size_t counts_bytes = 2 * VJ_MAX_STAGES * sizeof(uint64_t) + 16;   // stage_entered | visited ... | detection count
     if ((rc = d_counts.ensure(counts_bytes))) return rc;
-    const uint64_t frame_bytes = (uint64_t)frame_elems_for(W, H) * 4u;
-    int max_frames = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_frames, 0xfffffff0ull / frame_bytes));
-    if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
+    const int max_frames = cv_max_frames(e, n_frames, frame_elems_for(W, H));
     const std::vector<int> by_frame = cv_rois_by_frame(rois, n_rois);
     std::vector<CvRoiHost> regs;
     CvTapCache taps;
@@ -1691,80 +1662,41 @@ int run_cv_rois_levels(vj_env* e, const vj_cascade* c, const vj_image* frames, i
         if ((rc = enqueue_integral(e, d_canvas, canvas_bytes, (int)cv.pitch, IW, IH, 1, 1))) return rc;
         if (shape.has_tilted && (rc = enqueue_tilted(e, d_canvas, canvas_bytes, (int)cv.pitch, IW, IH, 1, 1))) return rc;
         HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
-        for (int attempt = 0;; ++attempt) {
-            if (attempt == 2) {   // (cannot happen: the count of a repeated pass is the count that sized its buffer)
-                set_error("vj_detect_opencv_rois: the detection buffer overflowed twice");
-                return VJ_ERR_LIMIT;
-            }
-            if ((rc = d_det.ensure((size_t)det_cap * sizeof(CvDet)))) return rc;
-            HIP_TRY(hipMemsetAsync(d_counts.p, 0, counts_bytes, e->stream));
-            CvArgs a;
-            memset(&a, 0, sizeof(a));
-            a.sum = (const uint32_t*)e->d_sum.p;
-            a.sqsum = (const uint64_t*)e->d_sqsum.p;
-            a.tilted = shape.has_tilted ? (const uint32_t*)e->d_tilted.p : nullptr;
-            a.n_order = (uint32_t)order.size();
-            a.table = (const uint32_t*)e->d_cv_rl_table.p;
-            a.scales = (const CvScaleDev*)e->d_cv_rl_scales.p;
-            a.stages = (const StageDev*)e->d_cv_rl_stages.p;
+        std::vector<unsigned long long> h;
+        uint32_t n_det = 0;
+        rc = run_cv_pass_until_fit(e, counts_bytes, &det_cap, "vj_detect_opencv_rois: the detection buffer overflowed twice", [&](uint32_t cap) {
+            const CvTables tables{e->d_cv_rl_table.p, e->d_cv_rl_scales.p, e->d_cv_rl_stages.p, (uint32_t)order.size(), (uint32_t)c->stages.size()};
+            CvArgs a = cv_base_args(e, facts_of(shape), tables, CvGeom{frame_elems, stride, (uint32_t)IH + 1u, 1u}, d_det.p, cap, d_counts.p);
             a.rows = (const UnitDev*)e->d_cv_rl_rows.p;
             a.n_rows = (uint32_t)rows.size();
-            a.n_frames = 1u;
-            a.n_stages = (uint32_t)c->stages.size();
-            a.frame_elems = frame_elems;
-            a.stride = stride;
-            a.sum_h = (uint32_t)IH + 1u;
-            a.det = (CvDet*)d_det.p;
-            a.det_count = (uint32_t*)((unsigned long long*)d_counts.p + 2 * VJ_MAX_STAGES);
-            a.det_cap = det_cap;
-            a.stage_entered = (unsigned long long*)d_counts.p;
-            a.tail_max = (uint32_t)std::max(0, std::min(e->cv_tail_max, (int)CV_TAIL_MAX));
-            a.tree2 = shape.tree2 && !shape.is_tree && !shape.has_tilted && e->cv_tree2 ? 1u : 0u;
             // one wave per row unit, at most four workgroups (16 waves) per CU; the rest by stride
             // (a stage tree walks every position to the end of the tree: a.chains stays empty, the per-lane target-stage sweep)
             const int n_blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((rows.size() + CV_WAVES_PER_BLOCK - 1) / CV_WAVES_PER_BLOCK, (uint64_t)std::max(1, e->n_cu * 4)));
             a.total_waves = (uint32_t)n_blocks * CV_WAVES_PER_BLOCK;
-            HIP_TRY(hipEventRecord(e->lane0.ev[2], e->stream));
-            hrc = launch_cv_profile_pass(a, shape.trees, count, shape.is_tree, n_blocks, e->stream, false, true);
-            if (hrc) {
-                set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
+            return cascade_launched(launch_cv_profile_pass(a, shape.trees, count, shape.is_tree, n_blocks, e->stream, false, true));
+        }, &h, &n_det);
+        if (rc) return rc;
+        float ms_p = 0, ms_i = 0, ms_c = 0;
+        HIP_TRY(hipEventElapsedTime(&ms_p, e->lane0.ev[0], e->cv_rois_ev[0]));
+        HIP_TRY(hipEventElapsedTime(&ms_i, e->lane0.ev[0], e->lane0.ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms_c, e->lane0.ev[2], e->lane0.ev[3]));
+        out->timing.integral_ms += ms_i;
+        out->timing.cascade_ms += ms_c;
+        out->timing.total_ms += ms_i + ms_c;
+        out->timing.n_cascade_launches += 1;
+        info.pyramid_ms += ms_p;
+        if (count) add_cv_counters(h, c->stages.size(), &out->counters);
+        std::vector<CvDet> raw;
+        if ((rc = read_cv_dets(e, n_det, &raw))) return rc;
+        for (const CvDet& d : raw) {
+            if (d.slot >= cv.levels.size()) {
+                set_error("the level pass returned a detection outside its level images");
                 return VJ_ERR_HIP;
             }
-            HIP_TRY(hipEventRecord(e->lane0.ev[3], e->stream));
-            std::vector<unsigned long long> h((counts_bytes + 7) / 8);
-            HIP_TRY(hipMemcpyAsync(h.data(), d_counts.p, counts_bytes, hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            const uint32_t n_det = (uint32_t)(h[2 * VJ_MAX_STAGES] & 0xffffffffull);
-            if (n_det > det_cap) {   // overflow: grow and run the pass again
-                det_cap = grown_cap(det_cap, n_det);
-                continue;
-            }
-            float ms_p = 0, ms_i = 0, ms_c = 0;
-            HIP_TRY(hipEventElapsedTime(&ms_p, e->lane0.ev[0], e->cv_rois_ev[0]));
-            HIP_TRY(hipEventElapsedTime(&ms_i, e->lane0.ev[0], e->lane0.ev[1]));
-            HIP_TRY(hipEventElapsedTime(&ms_c, e->lane0.ev[2], e->lane0.ev[3]));
-            out->timing.integral_ms += ms_i;
-            out->timing.cascade_ms += ms_c;
-            out->timing.total_ms += ms_i + ms_c;
-            out->timing.n_cascade_launches += 1;
-            info.pyramid_ms += ms_p;
-            if (count) {
-                for (size_t s = 0; s < c->stages.size(); ++s) out->counters.stage_entered[s] += h[s];
-                out->counters.windows += h[VJ_MAX_STAGES];
-            }
-            std::vector<CvDet> raw(n_det);
-            if (n_det) HIP_TRY(hipMemcpy(raw.data(), d_det.p, (size_t)n_det * sizeof(CvDet), hipMemcpyDeviceToHost));
-            for (const CvDet& d : raw) {
-                if (d.slot >= cv.levels.size()) {
-                    set_error("the level pass returned a detection outside its level images");
-                    return VJ_ERR_HIP;
-                }
-                // Rect(cvRound(x * factor), cvRound(y * factor), winSize) (tempcv.cpp:1099-1100), relative to the region
-                const CvRegionLevel& L = cv.levels[d.slot];
-                all->push_back(vj_rect{cv_round((double)d.x * L.lv.factor), cv_round((double)d.y * L.lv.factor), L.lv.win_w, L.lv.win_h, 0.0f,
-                                       regs[(size_t)L.region].id, L.lv.idx});
-            }
-            break;
+            // Rect(cvRound(x * factor), cvRound(y * factor), winSize) (tempcv.cpp:1099-1100), relative to the region
+            const CvRegionLevel& L = cv.levels[d.slot];
+            all->push_back(vj_rect{cv_round((double)d.x * L.lv.factor), cv_round((double)d.y * L.lv.factor), L.lv.win_w, L.lv.win_h, 0.0f,
+                                   regs[(size_t)L.region].id, L.lv.idx});
         }
         info.canvases += 1;
         info.level_images += cv.levels.size();
@@ -1926,9 +1858,7 @@ int vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames
         const std::vector<int> by_frame = cv_rois_by_frame(rois, n_rois);
         bool has_tilted = false;
         for (const auto& nd : c->nodes) has_tilted |= nd.tilted != 0;
-        const uint64_t frame_bytes = (uint64_t)frame_elems_for(W, H) * 4u;
-        int max_frames = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_frames, 0xfffffff0ull / frame_bytes));
-        if (e->max_subbatch > 0) max_frames = std::min(max_frames, e->max_subbatch);
+        const int max_frames = cv_max_frames(e, n_frames, frame_elems_for(W, H));
         std::vector<vj_rect> all;
         std::vector<CvRoiHost> regs;
         CvRoiPlan* pl = nullptr;
@@ -1938,15 +1868,7 @@ int vj_detect_opencv_rois(vj_env* e, const vj_cascade* c, const vj_image* frames
             const int nf = std::min(max_frames, n_frames - f0);
             cv_rois_of_subbatch(rois, by_frame, &next, f0, nf, &regs);
             if (regs.empty()) continue;   // (a sub-batch no region looks at is not uploaded; within one, every frame is)
-            if ((rc = ensure_image_buffers(e, W, H, nf, true, CH))) return rc;
-            const uint8_t* d_gray;
-            size_t gray_frame_bytes;
-            int gray_stride;
-            if ((rc = stage_frames(e, frames + f0, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride))) return rc;
-            HIP_TRY(hipEventRecord(e->lane0.ev[0], e->stream));
-            if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
-            if (has_tilted && (rc = enqueue_tilted(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, CH))) return rc;
-            HIP_TRY(hipEventRecord(e->lane0.ev[1], e->stream));
+            if ((rc = enqueue_cv_ingest(e, frames + f0, nf, W, H, CH, false, nullptr, has_tilted))) return rc;
             uint64_t n_windows = 0;
             if ((rc = run_cv_roi_pass(e, c, W, H, nf, regs, p, &all, out, &pl, nullptr, &n_windows))) return rc;   // (ends in a stream synchronise)
             e->cv_rois_info.windows += n_windows;

@@ -11,15 +11,6 @@ namespace vj {
 
 namespace {
 int channels_of(const vj_image& im) { return im.channels <= 1 ? 1 : im.channels; }
-
-int copy_rects(const std::vector<vj_rect>& all, vj_result* out) {
-    out->count = (uint32_t)all.size();
-    if (all.empty()) return VJ_OK;
-    out->rects = (vj_rect*)malloc(all.size() * sizeof(vj_rect));
-    if (!out->rects) return VJ_ERR_NOMEM;
-    memcpy(out->rects, all.data(), all.size() * sizeof(vj_rect));
-    return VJ_OK;
-}
 }  // namespace
 
 CvRoiFactor cv_roi_factor(int win_w, int win_h, double factor) {
@@ -123,17 +114,14 @@ int cv_roi_rects_of(const CvDet* raw, size_t n_raw, const std::vector<CvRoiFacto
     return VJ_OK;
 }
 
-int finish_cv_roi_result(std::vector<vj_rect>& all, const StageProgram* prog, const vj_cv_params* p, vj_result* out) {
-    std::sort(all.begin(), all.end(), [](const vj_rect& a, const vj_rect& b) {
-        return std::tie(a.frame, a.scale_idx, a.y, a.x) < std::tie(b.frame, b.scale_idx, b.y, b.x);
-    });
-    int rc = copy_rects(all, out);
-    if (rc) return rc;
-    if (p->min_neighbors != 0 && out->count) {   // groupRectangles(rectList, max(minNeighbors, 1), GROUP_EPS), a region at a time
-        rc = vj_group_rectangles(out->rects, &out->count, (int)std::max<uint32_t>(p->min_neighbors, 1u), 0.2);
-        if (rc) return rc;
+int cv_result_epilogue(const std::vector<vj_rect>& all, const StageProgram* prog, vj_result* out) {
+    out->count = (uint32_t)all.size();
+    if (!all.empty()) {
+        out->rects = (vj_rect*)malloc(all.size() * sizeof(vj_rect));
+        if (!out->rects) return VJ_ERR_NOMEM;
+        memcpy(out->rects, all.data(), all.size() * sizeof(vj_rect));
     }
-    if ((p->flags & VJ_FLAG_COUNTERS) != 0 && prog) {
+    if (prog) {
         vj_counters& k = out->counters;
         uint64_t rect_evals = 0;
         for (size_t s = 0; s < prog->n_nodes.size() && s < (size_t)VJ_MAX_STAGES; ++s) {
@@ -142,6 +130,15 @@ int finish_cv_roi_result(std::vector<vj_rect>& all, const StageProgram* prog, co
         }
         k.gather_bytes = 48ull * k.stage_entered[0] + 16ull * rect_evals;
     }
+    return VJ_OK;
+}
+
+int finish_cv_roi_result(std::vector<vj_rect>& all, const StageProgram* prog, const vj_cv_params* p, vj_result* out) {
+    std::sort(all.begin(), all.end(), cv_rect_before);
+    const int rc = cv_result_epilogue(all, (p->flags & VJ_FLAG_COUNTERS) != 0 ? prog : nullptr, out);
+    if (rc) return rc;
+    // groupRectangles(rectList, max(minNeighbors, 1), GROUP_EPS), a region at a time
+    if (p->min_neighbors != 0 && out->count) return vj_group_rectangles(out->rects, &out->count, (int)std::max<uint32_t>(p->min_neighbors, 1u), 0.2);
     return VJ_OK;
 }
 
@@ -185,7 +182,7 @@ int cv_roi_take_part(const vj_result& part, const std::vector<int>& idx, std::ve
 
 int cv_roi_emit_parts(std::vector<vj_rect>& all, vj_result* out) {
     std::stable_sort(all.begin(), all.end(), [](const vj_rect& a, const vj_rect& b) { return a.frame < b.frame; });
-    return copy_rects(all, out);
+    return cv_result_epilogue(all, nullptr, out);
 }
 
 int cv_chain_regions(const vj_rect* raw, size_t n_raw, uint32_t min_neighbors, int W, int H, int f0, int nf,

@@ -6,6 +6,7 @@
 #include "vj_cv_roi_units.hpp"
 
 #include <cmath>
+#include <tuple>
 
 namespace vj {
 
@@ -42,6 +43,15 @@ int cv_roi_build_units(const std::vector<CvRoiHost>& regs, int win_w, int win_h,
 // The pass's detections as rectangles: rect.frame = the region's id, x / y relative to the region
 int cv_roi_rects_of(const CvDet* raw, size_t n_raw, const std::vector<CvRoiFactor>& factors, const std::vector<CvRoiHost>& regs,
                     std::vector<vj_rect>* all);
+
+// The order of a result of the profile: (frame, scale_idx, y, x)
+inline bool cv_rect_before(const vj_rect& a, const vj_rect& b) {
+    return std::tie(a.frame, a.scale_idx, a.y, a.x) < std::tie(b.frame, b.scale_idx, b.y, b.x);
+}
+
+// The end of every call of the profile: `all` into out->rects / out->count, and the counters' derived fields (stump_evals,
+// gather_bytes) from the per-stage counts already in out->counters (prog null: an uncounted call, or no pass ran).
+int cv_result_epilogue(const std::vector<vj_rect>& all, const StageProgram* prog, vj_result* out);
 
 // `all` into *out as vj_detect_opencv shapes a result: sorted by (region, scale_idx, y, x), grouped per region when min_neighbors != 0;
 // the counters' derived fields from the stage program (null: no pass ran).
