@@ -1,9 +1,6 @@
-// Host driver of the HIP path: device buffers, per-(cascade, size, params) plans and
-// the launch sequence of one vj_detect call.  It replaces clodInitEnvironment /
-// clodInitBuffers / clodDetectObjectsOpenCL (clod.cpp:72-163, 1176-1336): where the
-// reference does, per frame, one blocking launch + count read-back per (scale, stage)
-// — up to 924 round trips at 1080p — this driver enqueues 3 integral launches and a
-// handful of cascade passes for the WHOLE batch and synchronises once.
+// The environment of the HIP path: its life cycle, device buffers and frame staging, the per-(cascade, size, params) plan cache
+// with the chain-balance search, the configure table and the image entry points.  It replaces clodInitEnvironment /
+// clodInitBuffers (clod.cpp:72-163); the detect drivers that launch on it are vj_detect.cpp and vj_detect_regions.cpp.
 #include "vj_internal.hpp"
 #include "vj_device.hpp"
 
@@ -22,7 +19,6 @@
 #include <tuple>
 
 #include "vj_slice.hpp"
-#include "vj_grid_parts.hpp"
 #include "vj_atlas_units.hpp"
 
 using namespace vj;
@@ -62,7 +58,7 @@ static int upload_plan(Plan* pl, const PlanTables& tab) {
 }
 
 // The plan of a call of n_frames frames under the environment's settings (plan_clod, vj_clod_plan.cpp), then its device copies.
-static int plan_and_upload(const vj_env* e, const vj_cascade& c, int W, int H, const vj_params& p, Plan* pl, float tile_split,
+int plan_and_upload(const vj_env* e, const vj_cascade& c, int W, int H, const vj_params& p, Plan* pl, float tile_split,
                            const TileThresholds& thresholds, int n_frames, bool one_pass) {
     PlanTables tab;
     const int rc = plan_clod(*e, e->tile_group, e->sq32, c, W, H, p, tile_split, thresholds, n_frames, one_pass, false, pl, &tab);
@@ -70,7 +66,7 @@ static int plan_and_upload(const vj_env* e, const vj_cascade& c, int W, int H, c
 }
 
 // (Re)lay out the per-scale queue segments for `frames` frames in flight.
-static int layout_queues(Plan* pl, int frames, uint64_t* total_entries) {
+int layout_queues(Plan* pl, int frames, uint64_t* total_entries) {
     // a scale's segment: Q_PARTS parts, part x takes the windows of frames with frame * Q_PARTS / frames == x,
     // i.e. at most ceil(frames / Q_PARTS) frames (fewer frames than parts: one part per frame, the rest unused)
     const uint64_t frames_per_part = frames >= (int)Q_PARTS ? ((uint64_t)frames + Q_PARTS - 1) / Q_PARTS : 1;
@@ -100,7 +96,7 @@ static vj_env::BalanceKey balance_key(const vj_env* e, const vj_cascade* c, int 
                               e->balance_class(n_frames));
 }
 
-static vj_env::Balance* balance_of(vj_env* e, const vj_cascade* c, int W, int H, const vj_params& p, int n_frames, bool create) {
+vj_env::Balance* balance_of(vj_env* e, const vj_cascade* c, int W, int H, const vj_params& p, int n_frames, bool create) {
     // (calls of at least eight frames or sixteen megapixels: below that a call is a millisecond and its time says little)
     if (!e->auto_balance || e->tile_split_set || !e->concurrent || n_frames >= (1 << 20) ||
         (n_frames < 8 && (uint64_t)W * (uint64_t)H * (uint64_t)n_frames < 16000000ull))
@@ -127,12 +123,7 @@ static vj_env::Balance* balance_of(vj_env* e, const vj_cascade* c, int W, int H,
 
 // What a call of n_frames frames runs: the candidate under test when it is one of the workload's sampling calls (the class's
 // reference size, search not finished), else the best split known.
-struct BalanceChoice {
-    float split;
-    int thr;
-    bool candidate;
-};
-static BalanceChoice balance_choice(const vj_env::Balance* b, int n_frames) {
+BalanceChoice balance_choice(const vj_env::Balance* b, int n_frames) {
     if (b->phase != 3 && n_frames == b->n_ref) return BalanceChoice{b->cur, b->thr, b->cur != b->best || b->phase == 4};
     return BalanceChoice{b->best, b->phase == 4 ? 0 : b->thr, false};
 }
@@ -140,7 +131,7 @@ static BalanceChoice balance_choice(const vj_env::Balance* b, int n_frames) {
 // Called once per vj_detect / vj_detect_chain call of a balanced workload, before its plan is looked up: bookkeeping, and the
 // reference size follows the traffic (a class whose reference size stopped coming — 32 calls of other sizes — restarts the
 // measurement of its current best at the size that does come; what was found so far stays the starting point).
-static void balance_touch(vj_env::Balance* b, int n_frames) {
+void balance_touch(vj_env::Balance* b, int n_frames) {
     ++b->calls_total;
     if (b->phase == 3) return;
     if (n_frames == b->n_ref) {
@@ -161,7 +152,7 @@ static void balance_touch(vj_env::Balance* b, int n_frames) {
 // device idled), the faster of the other two counts — or two when both the unrated call and the first rated one were already
 // more than 3 % slower than the best: such a candidate is dropped at once.  Steps of a quarter of a scale; a move needs 0.7 %;
 // at most 40 calls per workload.
-static void balance_report(vj_env::Balance* b, float ms, bool try_thresholds) {
+void balance_report(vj_env::Balance* b, float ms, bool try_thresholds) {
     if (!b || b->phase == 3 || !(ms > 0.0f)) return;
     ++b->calls;
     bool early_drop = false;
@@ -295,7 +286,7 @@ static int balance_import(vj_env* e, const char* path) {
     return VJ_OK;
 }
 
-static int get_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_params& p, Plan** out, int n_frames = 1 << 20) {
+int get_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_params& p, Plan** out, int n_frames) {
     const vj_env::Balance* bal = balance_of(e, c, W, H, p, n_frames, false);
     const BalanceChoice choice = bal ? balance_choice(bal, n_frames) : BalanceChoice{e->split_for(n_frames, p, linear_stumps(*c)), 0, false};
     const float split = choice.split;
@@ -632,554 +623,7 @@ int enqueue_equalize(vj_env* e, Lane* lane, const uint8_t** d_gray, size_t* fram
     return VJ_OK;
 }
 
-struct RawDet {
-    int frame;
-    uint32_t slot, x, y;
-};
-
-// Where the counters of one batch live: [MAX_PASSES][MAX_SCALES][Q_PARTS] queue counts | det_count | pad | one
-// stage_entered[VJ_MAX_STAGES] (u64) array per kernel launch (array 0 is spare) | the counters of a region-of-interest
-// pass (vj_detect_chain): regions, units, invalid regions, unit ticket, detections, pad | its stage_entered array | the queue
-// counts of the tiles' own queue set (stage trees, enqueue_cascade).
-struct CountsLayout {
-    static constexpr size_t q_counts = (size_t)MAX_SCALES * Q_PARTS;   // counters of one queue: [scale][part]
-    static constexpr size_t stage_off_u32 = MAX_PASSES * q_counts + 2;
-    static constexpr size_t roi_off_u32 = stage_off_u32 + (size_t)(1 + VJ_MAX_LAUNCHES) * VJ_MAX_STAGES * 2;
-    static constexpr size_t q2_off_u32 = roi_off_u32 + 8 + (size_t)VJ_MAX_STAGES * 2;   // second set of queue counters (stage trees)
-    static constexpr size_t bytes = (q2_off_u32 + MAX_PASSES * q_counts) * sizeof(uint32_t);
-    // Queue 0 does not exist, so its q_counts counters serve as tickets, zeroed with the block once per enqueue_cascade.  From
-    // the front: pass ps draws from [ps * Q_PARTS, (ps + 1) * Q_PARTS) — pass 0 is the grid pass, whose GRID_PARTS parts of the
-    // (frame, unit) list take the first range (one grid launch per zeroing); from the back: tile class c at
-    // q_counts - 8 (c + 1), the region pass's tiles at q_counts - 40.
-    static constexpr size_t pass_tickets_end = (size_t)MAX_PASSES * Q_PARTS;
-    static constexpr size_t tile_tickets_begin = q_counts - 8u * TILE_CLASSES;
-    static constexpr size_t roi_tickets_begin = q_counts - 40u;
-};
-static_assert(GRID_PARTS == Q_PARTS, "the grid pass's tickets are pass 0's range of queue 0's counters");
-static_assert(CountsLayout::pass_tickets_end <= CountsLayout::roi_tickets_begin, "pass tickets (the grid pass's among them) end before the region pass's");
-static_assert(CountsLayout::roi_tickets_begin + 8u <= CountsLayout::tile_tickets_begin, "the region pass's tile tickets end before the tile classes'");
-
-// Upload (or adopt) the frames of one batch and enqueue its integral images.  `copy_stream` != null: the upload runs
-// on that stream and the integral waits for it (vj_stream); else everything is ordered on the environment's stream.
-static int enqueue_prepare(vj_env* e, Lane* L, Plan* pl, const vj_image* frames, int nf, int W, int H, bool fixed_queue_layout,
-                           hipStream_t copy_stream, bool equalize = false, bool sq_u32 = false) {
-    int rc;
-    int channels = image_channels(frames[0]);
-    if ((rc = ensure_image_buffers(e, W, H, nf, true, channels, L))) return rc;
-    uint64_t q_entries = 0;
-    if (!fixed_queue_layout) {
-        if ((rc = layout_queues(pl, nf, &q_entries))) return rc;
-        const size_t n_pass = pl->pass_bounds.size() - 1;
-        for (size_t ps = 1; ps < n_pass; ++ps)
-            if ((rc = e->d_q[ps].ensure(std::max<uint64_t>(q_entries, 1) * sizeof(QEntry)))) return rc;
-    }
-    if ((rc = L->d_counts.ensure(CountsLayout::bytes))) return rc;
-    if (L->det_cap == 0) {
-        L->det_cap = e->det_cap_init;
-        if ((rc = L->d_det.ensure((size_t)L->det_cap * sizeof(DetEntry)))) return rc;
-    }
-    const uint8_t* d_gray;
-    size_t gray_frame_bytes;
-    int gray_stride;
-    if ((rc = stage_frames(e, frames, nf, W, H, &d_gray, &gray_frame_bytes, &gray_stride, L, copy_stream))) return rc;
-    if (copy_stream) {
-        HIP_TRY(hipEventRecord(L->upload_done, copy_stream));
-        HIP_TRY(hipStreamWaitEvent(e->stream, L->upload_done, 0));
-    }
-    HIP_TRY(hipEventRecord(L->ev[0], e->stream));
-    // VJ_FLAG_EQUALIZE_HIST: from here on the batch is the lane's equalized gray frames (a redo integrates those again)
-    if (equalize && (rc = enqueue_equalize(e, L, &d_gray, &gray_frame_bytes, &gray_stride, &channels, W, H, nf))) return rc;
-    L->src_gray = d_gray;
-    L->src_frame_bytes = gray_frame_bytes;
-    L->src_stride = gray_stride;
-    L->src_channels = channels;
-    // (a variance rectangle wider than SQ32_MAX_AREA pixels has no strip height: such frames keep the u64 layout)
-    L->sq_u32 = sq_u32 && e->sq32 && e->sq_u32 && (uint32_t)W <= SQ32_MAX_AREA;
-    if ((rc = enqueue_integral(e, d_gray, gray_frame_bytes, gray_stride, W, H, nf, channels, L->sq_u32))) return rc;
-    HIP_TRY(hipEventRecord(L->ev[1], e->stream));
-    HIP_TRY(hipEventRecord(L->integral_done, e->stream));   // the lane's frame buffer may be overwritten from here on
-    L->nf = nf;
-    return VJ_OK;
-}
-
-// Enqueue every cascade launch of the batch whose integral images are (being) computed, then the asynchronous
-// read-back of its counters and first detections.  Nothing here waits for the device.
-static int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, int /*H*/, const vj_params& p) {
-    int rc;
-    const int nf = L->nf;
-    const size_t n_pass = pl->pass_bounds.size() - 1;
-    const size_t counts_bytes = CountsLayout::bytes;
-    constexpr size_t q_counts = CountsLayout::q_counts;
-    uint32_t* d_qcount[MAX_PASSES];
-    for (int ps = 0; ps < MAX_PASSES; ++ps) d_qcount[ps] = (uint32_t*)L->d_counts.p + ps * q_counts;
-    uint32_t* d_qcount2[MAX_PASSES];   // the tiles' own queue set (stage trees: see split_sets below)
-    for (int ps = 0; ps < MAX_PASSES; ++ps) d_qcount2[ps] = (uint32_t*)L->d_counts.p + CountsLayout::q2_off_u32 + ps * q_counts;
-    uint32_t* d_det_count = (uint32_t*)L->d_counts.p + MAX_PASSES * q_counts;
-    unsigned long long* d_stage_entered = (unsigned long long*)((uint32_t*)L->d_counts.p + CountsLayout::stage_off_u32);
-    const bool count = (p.flags & VJ_FLAG_COUNTERS) != 0;
-    const int n_blocks = std::max(1, e->n_cu * e->blocks_per_cu);
-    {
-        HIP_TRY(hipMemsetAsync(L->d_counts.p, 0, counts_bytes, e->stream));
-        HIP_TRY(hipEventRecord(L->ev[2], e->stream));
-        CascadeArgs ca;
-        memset(&ca, 0, sizeof(ca));
-        ca.sum = (const uint32_t*)e->d_sum.p;
-        ca.sqsum = (const uint64_t*)e->d_sqsum.p;
-        ca.sq_u32 = L->sq_u32 ? 1u : 0u;
-        ca.table = (const uint32_t*)pl->d_table.p;
-        ca.scales = (const ScaleDev*)pl->d_scales.p;
-        ca.stages = (const StageDev*)pl->d_stages.p;
-        ca.units = (const UnitDev*)pl->d_units.p;
-        ca.n_units = (uint32_t)pl->units.size();
-        ca.tile_units = (const UnitDev*)pl->d_tile_units.p;
-        ca.n_tile_units = (uint32_t)pl->tile_units.size();
-        ca.n_frames = (uint32_t)nf;
-        ca.n_scales = (uint32_t)pl->scales.size();
-        ca.frame_elems = pl->frame_elems;
-        ca.sum_bytes = (uint32_t)((uint64_t)pl->frame_elems * 4u * (uint64_t)nf);
-        ca.stride = (uint32_t)W + 1u;
-        // waves per workgroup of the gather chain: four for batches, three for single frames and for stage trees (their
-        // workgroups carry a second LDS array); the launchers clamp, the kernels read blockDim.  The waves of a linear launch
-        // divide one 16 KiB array (vj_gather_queue.hpp), and the plan's units must fit a wave's share: a plan cut for fewer
-        // waves than this call would run (a stream's plan, a sub-batch) keeps the call at the waves it was cut for
-        ca.gather_waves = gather_waves_fitting((uint32_t)e->gather_waves_for(nf, pl->general, pl->trees), pl->unit_cap);
-        ca.q_cap = pl->general ? (uint32_t)UNIT_WINDOWS : gather_queue_cap(ca.gather_waves);
-        ca.total_waves = (uint32_t)n_blocks * ca.gather_waves;
-        ca.det = (DetEntry*)L->d_det.p;
-        ca.det_count = d_det_count;
-        ca.det_cap = L->det_cap;
-        ca.signed_mean = (p.flags & VJ_FLAG_SIGNED_MEAN) ? 1u : 0u;
-        ca.stage_entered = d_stage_entered;
-        ca.tree_ctr = d_stage_entered;       // array 0 is spare: [0], [1] = the first cascade's visited child nodes / their rectangles
-        ca.n_pass = (uint32_t)n_pass;
-        for (size_t ps = 0; ps <= n_pass; ++ps) ca.pass_begin[ps] = pl->pass_bounds[ps];
-        for (size_t ps = 1; ps < n_pass; ++ps) {
-            ca.q_pass[ps] = (QEntry*)e->d_q[ps].p;
-            ca.q_pass_count[ps] = d_qcount[ps];
-        }
-        // linear cascades: the kernel sees the configured tile_end, not the plan's clamped pl->tile_end; a tile leaves at the first pass boundary
-        // at or beyond it, and `banded` / `handover` below compare it with pass_bounds[1]
-        ca.tile_end = pl->general ? pl->general_prefix : (uint32_t)e->tile_end;   // stage trees: tiles run the linear prefix only
-        ca.tile_min_lanes = (uint32_t)e->tile_min_lanes;
-        ca.tile_repack_mask = e->tile_repack_mask;
-        ca.tile_sp_begin = (!pl->general && (pl->wave_tail || pl->tree2)) ? (uint32_t)e->tile_sp_begin : 0xffffffffu;   // the finishes walk positions linearly: never on a stage tree
-        ca.tree2 = pl->tree2 ? 1u : 0u;
-        ca.identity_order = pl->general ? 0u : 1u;
-        ca.n_seg = e->tile_segments ? pl->tile_n_seg : 0u;
-        for (int k = 0; k < 4; ++k) ca.seg_end[k] = pl->tile_seg_end[k];
-        ca.seg_chain = pl->tile_seg_chain;
-        ca.sp_blocks = (const SpBlock*)pl->d_sp_blocks.p;
-        ca.n_sp_blocks = pl->n_sp_blocks;
-        ca.tile_ws_min = pl->wave_tail ? (uint32_t)e->tile_ws_min : 0u;   // no wave-independent tail: wave-split to the end
-        ca.tile_ws_max = (uint32_t)std::min(e->tile_ws_max, (int)TILE_WS_MAX_WINDOWS);
-        ca.pos_mode = pl->pos_mode;
-        ca.pos_tab = (const uint32_t*)pl->d_pos_tab.p;
-        ca.gather_pairs = e->pairs_for(nf);
-        ca.sp_tail_max = (uint32_t)std::max(0, std::min(e->sp_tail_max, (int)gather_tail_max(ca.q_cap)));
-        ca.max_stage_nodes = pl->max_stage_nodes;
-        if (pl->skip_mode && pl->n_skip_units) {
-            // the windows the reference's sequential CPU loop visits, as a bitmap: stage-0 verdict of every grid window,
-            // then the parity recurrence; the passes below drop the unvisited windows while they enumerate the grid
-            if ((rc = e->d_skip_bits.ensure((size_t)pl->skip_frame_words * 8u * (size_t)nf))) return rc;
-            ca.skip_bits = (unsigned long long*)e->d_skip_bits.p;
-            ca.skip_frame_words = pl->skip_frame_words;
-            ca.skip_units = (const UnitDev*)pl->d_skip_units.p;
-            ca.n_skip_units = pl->n_skip_units;
-            ca.skip_segs = (const UnitDev*)pl->d_skip_segs.p;
-            ca.n_skip_segs = pl->n_skip_segs;
-            const int hrc = launch_skip_bitmap(ca, pl->trees, std::max(1, e->n_cu * 4), e->stream);
-            if (hrc) {
-                set_error("skip bitmap launch failed: %s", hipGetErrorString((hipError_t)hrc));
-                return VJ_ERR_HIP;
-            }
-        }
-        int launches = 0;
-        std::vector<vj_launch>& linfo = L->linfo;
-        linfo.clear();
-        // every launch is bracketed by its own pair of events on the stream it runs on
-        auto begin_launch = [&](int kind, int cls, uint32_t sb, uint32_t se, uint32_t lds, hipStream_t st) -> int {
-            if (linfo.size() < VJ_MAX_LAUNCHES) HIP_TRY(hipEventRecord(L->launch_ev[2 * linfo.size()], st));
-            vj_launch li;
-            memset(&li, 0, sizeof(li));
-            li.kind = kind;
-            li.lds_class = cls;
-            li.stage_begin = (int32_t)sb;
-            li.stage_end = (int32_t)se;
-            li.lds_bytes = lds;
-            for (uint32_t slot = 0; slot < pl->scales.size(); ++slot) {
-                const ScaleDev& sd = pl->scales[slot];
-                const bool in = kind == VJ_LAUNCH_QUEUE ||
-                                (kind == VJ_LAUNCH_TILE && sd.tile_rw && sd.tile_row_end > 0 && (int)pl->scales[pl->tile_lead[slot]].tile_class == cls) ||
-                                (kind == VJ_LAUNCH_GRID && sd.tile_row_end < sd.ny);
-                if (in && sd.scale_idx < 128) li.scale_mask[sd.scale_idx >> 6] |= 1ull << (sd.scale_idx & 63);
-            }
-            linfo.push_back(li);
-            return VJ_OK;
-        };
-        // the launch just begun counts into its own array
-        auto launch_counters = [&]() -> unsigned long long* {
-            return d_stage_entered + std::min<size_t>(linfo.size(), VJ_MAX_LAUNCHES) * VJ_MAX_STAGES;
-        };
-        auto end_launch = [&](hipStream_t st) -> int {
-            if (linfo.size() <= VJ_MAX_LAUNCHES) HIP_TRY(hipEventRecord(L->launch_ev[2 * linfo.size() - 1], st));
-            return VJ_OK;
-        };
-        auto pass_is_last = [&](size_t ps) { return pl->seg_last.empty() ? ps + 1 == n_pass : pl->seg_last[ps] != 0; };
-        const bool general_kernel = pl->general && pl->seg_last.empty();   // run_stages_general finishes the tree
-        // Band-major queue pass: a batch of a linear cascade whose gather chain is grid pass + ONE queue pass that only the grid
-        // pass feeds.  It reads nothing but the runs the grid pass records in run_table, so the tiles must not feed that queue:
-        // they run the whole cascade themselves only when tile_end lies BEYOND the boundary (at tile_end == pass_bounds[1] they
-        // hand their survivors to q_pass[1], and the chunked pass, which sweeps the whole sub-queue, takes the batch)
-        const bool banded = e->q_band_px > 0 && !pl->unit_groups.empty() && !pl->general && n_pass == 2 && nf >= e->q_band_min_frames &&
-                            e->tile_min_lanes == 0 && (uint32_t)e->tile_end > pl->pass_bounds[1];
-        if (banded) {
-            if ((rc = e->d_run_table.ensure((size_t)nf * pl->units.size() * 8u))) return rc;
-            ca.run_table = (uint32_t*)e->d_run_table.p;
-        }
-        auto queue_args = [&](size_t ps, int set = 0) {
-            CascadeArgs qa = ca;
-            DevBuf* dq = set ? e->d_q2 : e->d_q;
-            uint32_t** qc = set ? d_qcount2 : d_qcount;
-            qa.stage_begin = pl->pass_bounds[ps];
-            qa.stage_end = pl->pass_bounds[ps + 1];
-            const bool last = pass_is_last(ps);
-            // pass ps reads queue ps (filled by pass ps-1 and by tiles that left at this boundary)
-            // and appends its survivors to queue ps+1
-            qa.q_in = (const QEntry*)dq[ps].p;
-            qa.q_in_count = qc[ps];
-            qa.q_ticket = qc[0] + ps * Q_PARTS;   // queue 0 does not exist: its counters serve as tickets
-            // frame-major order inside a part: one slice per frame of the part's frame group (-1), or as configured
-            qa.q_slices = e->q_slices >= 0 ? (uint32_t)std::max(1, e->q_slices)
-                                           : (uint32_t)std::max(1, std::min(16, (nf + (int)Q_PARTS - 1) / (int)Q_PARTS));
-            qa.min_chunk = (uint32_t)e->min_chunk;
-            qa.wide_tail = (e->wide_tail < 0 ? nf <= 4 : e->wide_tail != 0) ? 1u : 0u;
-            qa.q_out = last ? nullptr : (QEntry*)dq[ps + 1].p;
-            qa.q_out_count = last ? nullptr : qc[ps + 1];
-            if (banded && ps == 1) {
-                qa.q_groups = (const UnitDev*)pl->d_unit_groups.p;
-                qa.n_q_groups = (uint32_t)pl->unit_groups.size();
-            }
-            if (!pl->seg_fail.empty() && pl->seg_fail[ps] != 0) {   // stage tree: this segment's rejects continue
-                qa.q_fail = (QEntry*)dq[pl->seg_fail[ps]].p;
-                qa.q_fail_count = qc[pl->seg_fail[ps]];
-            }
-            return qa;
-        };
-        if (ca.n_units + ca.n_tile_units > 0) {
-            int hrc = 0;
-            // Two chains share the first part of the cascade and run CONCURRENTLY on two streams:
-            //   A (e->stream) : the LDS-tile launches (LDS-bound)
-            //   B (e->stream2): the global-gather first pass and the queue passes that only it feeds
-            //                   (texture-address-bound) — every pass that begins before the stage at
-            //                   which tiles hand over (tiles leave at one boundary when tile_min_lanes = 0)
-            // then B joins A and the remaining queue passes run on A.
-            const uint32_t handover = pl->general ? pl->general_prefix : std::max<uint32_t>(ca.tile_end, pl->pass_bounds[1]);
-            size_t first_joint_pass = 1;
-            if (e->tile_min_lanes == 0)
-                while (first_joint_pass < n_pass && pl->pass_bounds[first_joint_pass] < handover) ++first_joint_pass;
-            const bool two_streams = e->concurrent && ca.n_tile_units > 0 && ca.n_units > 0;
-            // Stage tree in chains (seg_last): the chains' queue passes would have to wait for BOTH the grid pass and the
-            // tiles, because a crowded tile hands its windows to the same queues — and the tiles take longer than the grid
-            // pass (4096 x 4096: 7.8 vs 4.8 ms, then 7.8 ms of queue passes).  So the tiles get a queue set of their own:
-            // the grid pass's survivors go down the tree on stream B while the tiles still run, and after the join the same
-            // passes run once more on what the tiles left (usually little: thin passes).
-            const bool split_sets = two_streams && pl->general && !pl->seg_last.empty() && e->tree_split_queues;
-            if (split_sets) {
-                for (size_t ps = 1; ps < n_pass; ++ps) {
-                    if ((rc = e->d_q2[ps].ensure(e->d_q[ps].cap))) return rc;
-                    ca.q_pass[ps] = (QEntry*)e->d_q2[ps].p;        // (the grid and queue passes take theirs from queue_args)
-                    ca.q_pass_count[ps] = d_qcount2[ps];
-                }
-                first_joint_pass = n_pass;
-            }
-            hipStream_t sB = two_streams ? e->stream2 : e->stream;
-            if (two_streams) {
-                HIP_TRY(hipEventRecord(e->fork_ev, e->stream));
-                HIP_TRY(hipStreamWaitEvent(e->stream2, e->fork_ev, 0));
-            }
-            HIP_TRY(hipEventRecord(L->pass_ev[0], e->stream));
-            // chain A: tile launches
-            auto chain_a = [&]() -> int {
-            for (uint32_t ci = 0; ci < TILE_CLASSES && !hrc && ca.n_tile_units > 0; ++ci) {
-                // largest LDS first: the one-workgroup-per-CU class suffers most from the gather chain, whose first pass is
-                // the heavier one (measured: 48.3 -> 47.2 ms)
-                const uint32_t cls = TILE_CLASSES - 1u - ci;
-                const uint32_t n_cls = pl->class_first[cls + 1] - pl->class_first[cls];
-                if (!n_cls) continue;
-                CascadeArgs ta = ca;
-                ta.tile_units = (const UnitDev*)pl->d_tile_units.p + pl->class_first[cls];
-                ta.n_tile_units = n_cls;
-                ta.tile_lds_bytes = pl->class_lds[cls];
-                ta.tile_ticket = d_qcount[0] + (q_counts - 8u * (cls + 1u));   // queue 0 does not exist: its counters are free
-                // workgroups per CU: what the LDS allows (160 KiB per CU), at most 4 x 8 waves
-                const int per_cu = std::max(1, std::min(32 / TILE_WAVES, (int)(160u * 1024u / ta.tile_lds_bytes)));
-                const int tb = (int)std::min<uint64_t>((uint64_t)n_cls * (uint64_t)nf, (uint64_t)e->n_cu * (uint64_t)per_cu);
-                const uint32_t deepest = std::min<uint32_t>((uint32_t)pl->stages.size(), handover);
-                if ((rc = begin_launch(VJ_LAUNCH_TILE, (int)cls, 0, deepest, ta.tile_lds_bytes, e->stream))) return rc;
-                ta.stage_entered = launch_counters();
-                hrc = launch_cascade_tile_pass(ta, pl->trees, count, std::max(1, tb), e->stream);
-                if ((rc = end_launch(e->stream))) return rc;
-            }
-                return VJ_OK;
-            };
-            // chain B: grid pass, then the queue passes fed by it alone.  When the chains overlap it goes
-            // first, with one small workgroup per CU (the texture-address unit it is bound by saturates at
-            // one wave per SIMD), so that the tile workgroups find their LDS share next to it.
-            const int b_blocks = two_streams ? std::max(1, e->n_cu * e->concurrent_blocks_per_cu) : n_blocks;
-            auto chain_b = [&]() -> int {
-            if (!hrc && ca.n_units > 0) {
-                CascadeArgs ga = queue_args(0);   // (q_ticket: pass 0's range — the tickets of the unit list's parts)
-                if ((rc = begin_launch(VJ_LAUNCH_GRID, 0, ga.stage_begin, ga.stage_end, 0, sB))) return rc;
-                ga.stage_entered = launch_counters();
-                hrc = launch_cascade_pass(ga, true, pl->trees, n_pass == 1, count, general_kernel && n_pass == 1, b_blocks, sB);
-                if ((rc = end_launch(sB))) return rc;
-                for (size_t ps = 1; ps < first_joint_pass && !hrc; ++ps) {
-                    CascadeArgs qa = queue_args(ps);
-                    // (next to the tiles one workgroup per CU; a stage tree's chains are latency-bound: all of them)
-                    const int qb = split_sets ? n_blocks : b_blocks;
-                    qa.total_waves = (uint32_t)qb * qa.gather_waves;
-                    if ((rc = begin_launch(VJ_LAUNCH_QUEUE, 0, qa.stage_begin, qa.stage_end, 0, sB))) return rc;
-                    qa.stage_entered = launch_counters();
-                    hrc = launch_cascade_pass(qa, false, pl->trees, pass_is_last(ps), count, false, qb, sB);
-                    if ((rc = end_launch(sB))) return rc;
-                }
-            } else {
-                first_joint_pass = 1;
-            }
-                return VJ_OK;
-            };
-            if (two_streams) {
-                if ((rc = chain_b())) return rc;
-                if ((rc = chain_a())) return rc;
-            } else {
-                if ((rc = chain_a())) return rc;
-                if ((rc = chain_b())) return rc;
-            }
-            if (two_streams) {
-                HIP_TRY(hipEventRecord(e->join_ev, e->stream2));
-                HIP_TRY(hipStreamWaitEvent(e->stream, e->join_ev, 0));
-            }
-            for (size_t ps = 1; ps < n_pass && ps < VJ_MAX_PASSES && ps <= first_joint_pass; ++ps)
-                HIP_TRY(hipEventRecord(L->pass_ev[ps], e->stream));
-            // joint passes (split_sets: all of them once more, on the tiles' queue set)
-            for (size_t ps = split_sets ? 1 : first_joint_pass; ps < n_pass && !hrc; ++ps) {
-                if (ps > first_joint_pass && ps < VJ_MAX_PASSES) HIP_TRY(hipEventRecord(L->pass_ev[ps], e->stream));
-                CascadeArgs qa = queue_args(ps, split_sets ? 1 : 0);
-                if ((rc = begin_launch(VJ_LAUNCH_QUEUE, 0, qa.stage_begin, qa.stage_end, 0, e->stream))) return rc;
-                qa.stage_entered = launch_counters();
-                hrc = launch_cascade_pass(qa, false, pl->trees, pass_is_last(ps), count, general_kernel, n_blocks, e->stream);
-                if ((rc = end_launch(e->stream))) return rc;
-            }
-            if (hrc) {
-                set_error("cascade launch failed: %s", hipGetErrorString((hipError_t)hrc));
-                return VJ_ERR_HIP;
-            }
-            launches = (int)n_pass;
-        }
-        if (n_pass <= VJ_MAX_PASSES && launches) HIP_TRY(hipEventRecord(L->pass_ev[n_pass], e->stream));
-        HIP_TRY(hipEventRecord(L->ev[3], e->stream));
-        L->launches = launches;
-    }
-    L->n_pass = n_pass;
-    L->count = count;
-    // read back the counters block and the first detections (nearly always all of them)
-    HIP_TRY(hipMemcpyAsync(L->h_pinned, L->d_counts.p, counts_bytes, hipMemcpyDeviceToHost, e->stream));
-    const size_t room = (L->h_pinned_bytes - ((counts_bytes + 255) & ~(size_t)255)) / sizeof(DetEntry);
-    L->det_copied = (uint32_t)std::min<size_t>(room, L->det_cap);
-    HIP_TRY(hipMemcpyAsync((char*)L->h_pinned + ((counts_bytes + 255) & ~(size_t)255), L->d_det.p, (size_t)L->det_copied * sizeof(DetEntry),
-                           hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipEventRecord(L->done, e->stream));
-    L->pending = true;
-    return VJ_OK;
-}
-
-// Wait for the batch on lane L and decode it: detections appended to `dets` with frame numbers offset by f0.  When the
-// detection buffer overflowed it is grown and the cascade passes run again — on the integral images still in place for a
-// blocking call, after recomputing them from the lane's frames for a stream lane (the two lanes of a vj_stream share
-// the environment's integral images, and the next batch's have replaced this one's by now).  The redo is ordered on the
-// environment's stream behind everything already queued, and finished synchronously here.
-static int finish_batch(vj_env* e, Lane* L, Plan* pl, int f0, int W, int H, const vj_params& p, std::vector<RawDet>* dets,
-                        vj_counters* ctr, vj_timing* tm, std::vector<DetEntry>* raw_out = nullptr) {
-    int rc;
-    constexpr size_t q_counts = CountsLayout::q_counts;
-    const size_t counts_bytes = CountsLayout::bytes;
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        HIP_TRY(hipEventSynchronize(L->done));
-        L->pending = false;
-        const size_t n_pass = L->n_pass;
-        const int launches = L->launches;
-        const bool count = L->count;
-        const std::vector<vj_launch>& linfo = L->linfo;
-        const uint32_t n_det = ((const uint32_t*)L->h_pinned)[MAX_PASSES * q_counts];
-        float ms_i = 0, ms_c = 0, ms_t = 0;
-        HIP_TRY(hipEventElapsedTime(&ms_i, L->ev[0], L->ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms_c, L->ev[2], L->ev[3]));
-        HIP_TRY(hipEventElapsedTime(&ms_t, L->ev[0], L->ev[3]));
-        if (n_det > L->det_cap) {  // detections overflowed: grow and redo the cascade passes
-            const uint32_t want = grown_cap(L->det_cap, n_det);
-            if ((rc = L->d_det.ensure((size_t)want * sizeof(DetEntry)))) return rc;
-            L->det_cap = want;
-            if (L->shared_integrals) {
-                HIP_TRY(hipEventRecord(L->ev[0], e->stream));
-                if ((rc = enqueue_integral(e, L->src_gray, L->src_frame_bytes, L->src_stride, W, H, L->nf, L->src_channels, L->sq_u32))) return rc;
-                HIP_TRY(hipEventRecord(L->ev[1], e->stream));
-            }
-            if ((rc = enqueue_cascade(e, L, pl, W, H, p))) return rc;
-            continue;
-        }
-        if (attempt == 0) tm->integral_ms += ms_i;
-        tm->cascade_ms += ms_c;
-        tm->total_ms += ms_t;
-        if (launches && n_pass <= VJ_MAX_PASSES)
-            for (size_t ps = 0; ps < n_pass; ++ps) {
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, L->pass_ev[ps], L->pass_ev[ps + 1]));
-                tm->pass_ms[ps] += ms;
-                tm->pass_stage_begin[ps] = (int32_t)pl->pass_bounds[ps];
-                tm->pass_stage_end[ps] = (int32_t)pl->pass_bounds[ps + 1];
-            }
-        tm->n_cascade_launches = std::max(tm->n_cascade_launches, launches);
-        const unsigned long long* se_all = (const unsigned long long*)((const uint32_t*)L->h_pinned + CountsLayout::stage_off_u32);
-        if (linfo.size() <= VJ_MAX_LAUNCHES) {
-            for (size_t i = 0; i < linfo.size(); ++i) {
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, L->launch_ev[2 * i], L->launch_ev[2 * i + 1]));
-                vj_launch acc = tm->launch[i];   // sums over sub-batches: time and counters
-                tm->launch[i] = linfo[i];
-                tm->launch[i].ms = acc.ms + ms;
-                const unsigned long long* se = se_all + (1 + i) * VJ_MAX_STAGES;
-                for (size_t s = 0; s < (size_t)VJ_MAX_STAGES; ++s)
-                    tm->launch[i].stage_entered[s] = acc.stage_entered[s] + (count ? se[s] : 0ull);
-            }
-            tm->n_launches = (int32_t)linfo.size();
-        }
-#ifdef VJ_STAMPS
-        if (getenv("VJ_DEBUG_STAMPS")) {  // diagnostic build (-DVJ_STAMPS=1): phase cycle sums of the tile kernel
-            const unsigned long long* se = se_all;
-            for (size_t l = 0; l < linfo.size(); ++l)
-                fprintf(stderr, "vj launch %zu kind %d class %d: max resident workgroups %llu\n", l, linfo[l].kind, linfo[l].lds_class,
-                        se[(1 + l) * VJ_MAX_STAGES + 39]);
-            for (size_t l = 0; l < linfo.size(); ++l)   // queue passes: chunk time sum / max / chunks; stump-parallel tail: A, B, pairs, stages
-                if (linfo[l].kind == 1)
-                    fprintf(stderr, "vj queue launch %zu [%d,%d): chunks %llu sum %llu max %llu | tail A %llu B %llu pairs %llu stages %llu\n", l,
-                            linfo[l].stage_begin, linfo[l].stage_end, se[(1 + l) * VJ_MAX_STAGES + 50], se[(1 + l) * VJ_MAX_STAGES + 48],
-                            se[(1 + l) * VJ_MAX_STAGES + 49], se[(1 + l) * VJ_MAX_STAGES + 51], se[(1 + l) * VJ_MAX_STAGES + 52],
-                            se[(1 + l) * VJ_MAX_STAGES + 53], se[(1 + l) * VJ_MAX_STAGES + 54]);
-            for (size_t l = 0; l < linfo.size(); ++l)   // grid pass: when the waves leave the unit loop (vj_kernels.hip, slots 40..45)
-                if (linfo[l].kind == VJ_LAUNCH_GRID) {
-                    const unsigned long long* g = se + (1 + l) * VJ_MAX_STAGES + 40;
-                    const double wgs = (double)std::max(1ull, g[5]), span = (double)(g[3] - ~g[4]);
-                    fprintf(stderr, "vj grid launch %zu: workgroups %llu span %.0f ticks | per workgroup last - mean wave end: mean %.0f (%.2f %%) max %llu (%.2f %%) | "
-                            "launch end - mean last wave end %.0f (%.2f %%)\n", l, g[5], span, (double)g[0] / wgs, 100.0 * (double)g[0] / wgs / span, g[1],
-                            100.0 * (double)g[1] / span, (double)g[3] - (double)g[2] / wgs, 100.0 * ((double)g[3] - (double)g[2] / wgs) / span);
-                }
-            fprintf(stderr, "vj stamps:");
-            for (int i = 40; i < 63; ++i) {   // (60 .. 62: the dense sweep's groups, its lone chunks, how many lone chunks)
-                unsigned long long v = 0;
-                for (int l = 1; l <= VJ_MAX_LAUNCHES; ++l) v += se[l * VJ_MAX_STAGES + i];
-                fprintf(stderr, " %llu", v);
-            }
-            fprintf(stderr, "\n");
-        }
-#endif
-        if (count) {
-            for (size_t s = 0; s < pl->stages.size(); ++s)
-                for (int l = 1; l <= VJ_MAX_LAUNCHES; ++l) ctr->stage_entered[s] += se_all[(size_t)l * VJ_MAX_STAGES + s];
-            // multi-node trees: nodes below the roots that the walks visited, and their rectangles — parked in the two derived
-            // fields until fill_counters prices the roots (every entering window evaluates those) and adds these
-            ctr->stump_evals += se_all[0];
-            ctr->gather_bytes += se_all[1];
-        }
-        std::vector<DetEntry> raw(n_det);
-        const uint32_t have = std::min(n_det, L->det_copied);
-        if (have) memcpy(raw.data(), (const char*)L->h_pinned + ((counts_bytes + 255) & ~(size_t)255), (size_t)have * sizeof(DetEntry));
-        if (n_det > have)
-            HIP_TRY(hipMemcpy(raw.data() + have, (const DetEntry*)L->d_det.p + have, (size_t)(n_det - have) * sizeof(DetEntry),
-                              hipMemcpyDeviceToHost));
-        const uint32_t stride = (uint32_t)W + 1u;
-        const uint64_t fbytes = (uint64_t)pl->frame_elems * 4u;
-        for (const DetEntry& d : raw) {
-            const uint32_t f = (uint32_t)(d.off / fbytes);
-            const uint32_t el = (uint32_t)((d.off - (uint64_t)f * fbytes) / 4u);
-            dets->push_back(RawDet{f0 + (int)f, d.scale, el % stride, el / stride});
-        }
-        if (raw_out) *raw_out = std::move(raw);
-        return VJ_OK;
-    }
-    set_error("detection buffer overflow persisted");
-    return VJ_ERR_LIMIT;
-}
-
-// One sub-batch: frames [f0, f0+nf).  Appends decoded detections to `dets`.
-static int detect_subbatch(vj_env* e, Plan* pl, const vj_image* frames, int f0, int nf, int W, int H,
-                           const vj_params& p, bool equalize, std::vector<RawDet>* dets, vj_counters* ctr, vj_timing* tm) {
-    int rc;
-    Lane* L = &e->lane0;
-    if ((rc = enqueue_prepare(e, L, pl, frames + f0, nf, W, H, false, nullptr, equalize, true))) return rc;
-    if ((rc = enqueue_cascade(e, L, pl, W, H, p))) return rc;
-    return finish_batch(e, L, pl, f0, W, H, p, dets, ctr, tm);
-}
-
-// Sort, widen and (optionally) group the decoded detections of a whole call; fill the counters.
-static void fill_counters(Plan* pl, int n_frames, const vj_params& p, vj_result* out) {
-    if (!(p.flags & VJ_FLAG_COUNTERS)) return;
-    vj_counters& k = out->counters;
-    k.windows = pl->windows_per_frame * (uint64_t)n_frames;
-    // node evaluations as the oracle counts them: every node a window's walk visits.  Stumps: every node of an
-    // entered stage.  Multi-node trees: the root of every tree of an entered stage + the nodes below the roots that the
-    // counted kernels saw visited (finish_batch parked those in the two derived fields).
-    const uint64_t child_nodes = k.stump_evals, child_rects = k.gather_bytes;
-    uint64_t rect_evals = pl->trees ? child_rects : 0;
-    k.stump_evals = pl->trees ? child_nodes : 0;
-    for (size_t s = 0; s < pl->stages.size(); ++s) {
-        k.stump_evals += k.stage_entered[s] * (pl->trees ? pl->prog.n_roots[s] : pl->prog.n_nodes[s]);
-        rect_evals += k.stage_entered[s] * (pl->trees ? pl->prog.n_root_rects[s] : pl->prog.n_rects[s]);
-    }
-    k.gather_bytes = 48ull * k.windows + 16ull * rect_evals;
-}
-
-static int build_result(Plan* pl, std::vector<RawDet>& dets, int n_frames, const vj_params& p, vj_result* out) {
-    // deterministic order: (frame, scale_idx, y, x)
-    std::sort(dets.begin(), dets.end(), [](const RawDet& a, const RawDet& b) {
-        return std::tie(a.frame, a.slot, a.y, a.x) < std::tie(b.frame, b.slot, b.y, b.x);
-    });
-    out->count = (uint32_t)dets.size();
-    if (!dets.empty()) {
-        out->rects = (vj_rect*)malloc(dets.size() * sizeof(vj_rect));
-        if (!out->rects) return VJ_ERR_NOMEM;
-        for (size_t i = 0; i < dets.size(); ++i) {
-            const vj_scale_info& si = pl->scales_info[dets[i].slot];
-            out->rects[i] = vj_rect{(int32_t)dets[i].x, (int32_t)dets[i].y, si.win_w, si.win_h, 0.0f, dets[i].frame,
-                                    si.scale_idx};
-        }
-    }
-    if (p.min_neighbors != 0 && out->count) {  // clod.cpp:1325-1326: filterResult(matches, n, MAX(min_neighbors, 1), EPS)
-        const int rc = vj_group_rectangles(out->rects, &out->count, (int)std::max<uint32_t>(p.min_neighbors, 1u), 0.2);
-        if (rc) return rc;
-    }
-    fill_counters(pl, n_frames, p, out);
-    return VJ_OK;
-}
-
-// Frames per sub-batch so that 32-bit byte offsets into the batch sum image never wrap and the worst-case survivor
-// queues stay within a fixed budget.
-static uint64_t max_frames_per_subbatch(const vj_env* e, const Plan* pl) {
-    const uint64_t frame_bytes = (uint64_t)pl->frame_elems * 4u;
-    uint64_t max_frames = (0xffffffffull - (uint64_t)pl->max_reach_elems * 4u - 16u) / frame_bytes;
-    const uint64_t q_budget = 6ull << 30;  // bytes per queue
-    // a queue holds Q_PARTS parts of ceil(frames / Q_PARTS) frames' worth of windows each (layout_queues)
-    auto fit_parts = [](uint64_t frames_worth) {
-        return frames_worth >= Q_PARTS ? frames_worth / Q_PARTS * Q_PARTS : std::max<uint64_t>(1, frames_worth);
-    };
-    if (pl->windows_per_frame) {
-        max_frames = std::min<uint64_t>(max_frames, fit_parts(q_budget / (pl->windows_per_frame * sizeof(QEntry))));
-        max_frames = std::min<uint64_t>(max_frames, fit_parts(0xffffffffull / pl->windows_per_frame));
-    }
-    if (e->max_subbatch > 0) max_frames = std::min<uint64_t>(max_frames, (uint64_t)e->max_subbatch);
-    return max_frames;
-}
-
-static int check_frames(const vj_image* frames, int n_frames, int* W_, int* H_, int* CH_) {
+int check_frames(const vj_image* frames, int n_frames, int* W_, int* H_, int* CH_) {
     const int W = frames[0].width, H = frames[0].height;
     if (W <= 0 || H <= 0) return VJ_ERR_ARG;
     const int CH = image_channels(frames[0]);
@@ -1207,236 +651,7 @@ static int check_frames(const vj_image* frames, int n_frames, int* W_, int* H_, 
 }  // namespace vj
 
 extern "C" {
-static void drop_plans(vj_env* e);   // (defined inside the extern "C" block below: the same language linkage here)
-}
-
-// Arguments of the region pass (roi_plan_units + cascade_roi_pass): `second` inside regions of the nf frames whose integral
-// images sit in e->d_sum / e->d_sqsum.  The region list is e->d_rois (max_rois entries), its length on the device at
-// roi_counts[0]; the counters live in the lane's counts block.
-static void fill_region_args(vj_env* e, Lane* L, Plan* pl2, const vj_cascade* second, const vj_params& p_second, int W, int H, int nf,
-                             uint32_t max_rois, RoiArgs* ra_, CascadeArgs* ca_) {
-    uint32_t* roi_counts = (uint32_t*)L->d_counts.p + CountsLayout::roi_off_u32;
-    const uint32_t stride = (uint32_t)W + 1u;
-    RoiArgs& ra = *ra_;
-    memset(&ra, 0, sizeof(ra));
-    ra.frame_bytes = pl2->frame_elems * 4u;
-    ra.stride = stride;
-    ra.rois = (RoiDev*)e->d_rois.p;
-    ra.n_rois = roi_counts + 0;
-    ra.max_rois = max_rois;
-    ra.n_frames = (uint32_t)nf;
-    ra.frame_w = W;
-    ra.frame_h = H;
-    ra.win_w0 = second->win_w;
-    ra.win_h0 = second->win_h;
-    ra.units = (RoiUnit*)e->d_roi_units.p;
-    ra.n_units = roi_counts + 1;   // (+2: invalid regions)
-    ra.max_units = e->roi_unit_cap;
-    ra.ticket = roi_counts + 3;
-    ra.det = (RoiDet*)e->d_roi_det.p;
-    ra.det_count = roi_counts + 4;
-    ra.det_cap = e->roi_det_cap;
-    CascadeArgs& ca = *ca_;
-    memset(&ca, 0, sizeof(ca));
-    ca.sum = (const uint32_t*)e->d_sum.p;
-    ca.sqsum = (const uint64_t*)e->d_sqsum.p;
-    ca.table = (const uint32_t*)pl2->d_table.p;
-    ca.scales = (const ScaleDev*)pl2->d_scales.p;
-    ca.stages = (const StageDev*)pl2->d_stages.p;
-    ca.n_frames = (uint32_t)nf;
-    ca.n_scales = (uint32_t)pl2->scales.size();
-    ca.frame_elems = pl2->frame_elems;
-    ca.sum_bytes = (uint32_t)((uint64_t)pl2->frame_elems * 4u * (uint64_t)nf);
-    ca.stride = stride;
-    ca.gather_waves = (uint32_t)std::min(e->gather_waves_for(nf, pl2->general, pl2->trees), (int)GATHER_WAVES_FULL);   // the region pass keeps full queues
-    ca.q_cap = (uint32_t)UNIT_WINDOWS;
-    ca.stage_begin = 0;
-    ca.stage_end = pl2->general ? pl2->pass_bounds.back() : (uint32_t)pl2->stages.size();   // stage trees: positions in the sweep order
-    ca.identity_order = pl2->general ? 0u : 1u;
-    ca.tree2 = 0u;
-    ca.signed_mean = (p_second.flags & VJ_FLAG_SIGNED_MEAN) ? 1u : 0u;
-    ca.pos_mode = pl2->pos_mode;   // (0 on this path: check_params sends the f64 grids through the per-size plans; bound all the same)
-    ca.pos_tab = (const uint32_t*)pl2->d_pos_tab.p;
-    ca.gather_pairs = 2u;   // regions are small: thin waves, latency-bound
-    ca.sp_tail_max = (uint32_t)std::max(0, std::min(e->sp_tail_max, (int)gather_tail_max(ca.q_cap)));
-    ca.max_stage_nodes = pl2->max_stage_nodes;
-    ca.stage_entered = (unsigned long long*)(roi_counts + 8);
-    ca.tree_ctr = (unsigned long long*)((uint32_t*)L->d_counts.p + CountsLayout::stage_off_u32) + 2;   // the spare array's [2], [3]: the region pass's
-    // Regions with large grids at the small scales (many raw candidates, big faces) run those grids on the tile kernel
-    // (cascade_tile_roi_pass: tiles of the second cascade's two-per-CU tile scales, laid inside the region): stump cascades
-    // whose plan has such tiles.  The caller sizes e->d_roi_tiles and zeroes the eight ticket counters.
-    if (e->roi_tile_min_windows > 0 && !pl2->general && !pl2->trees && pl2->wave_tail && pl2->class_first[1] > pl2->class_first[0] &&
-        e->roi_tile_cap != 0u) {
-        ra.tiles = (RoiTile*)e->d_roi_tiles.p;
-        ra.n_tiles = roi_counts + 6;
-        ra.max_tiles = e->roi_tile_cap;
-        ra.tile_min_windows = (uint32_t)e->roi_tile_min_windows;
-        ca.tile_lds_bytes = pl2->class_lds[0];
-        const int per_cu = std::max(1, std::min(32 / TILE_WAVES, (int)(160u * 1024u / ca.tile_lds_bytes)));
-        ra.tile_blocks = (uint32_t)std::max(1, e->n_cu * per_cu);
-        ca.tile_ticket = (uint32_t*)L->d_counts.p + (CountsLayout::q_counts - 40u);
-        ca.n_pass = 1;                       // the whole cascade inside the tile: survivors are detections
-        ca.pass_begin[0] = 0;
-        ca.pass_begin[1] = (uint32_t)pl2->stages.size();
-        ca.tile_end = (uint32_t)pl2->stages.size();
-        ca.tile_min_lanes = 0;
-        ca.tile_repack_mask = e->tile_repack_mask;
-        ca.tile_sp_begin = (uint32_t)e->tile_sp_begin;
-        ca.sp_blocks = (const SpBlock*)pl2->d_sp_blocks.p;
-        ca.n_sp_blocks = pl2->n_sp_blocks;
-        ca.tile_ws_min = (uint32_t)e->tile_ws_min;
-        ca.tile_ws_max = (uint32_t)std::min(e->tile_ws_max, (int)TILE_WS_MAX_WINDOWS);
-    }
-}
-
-// vj_detect_rois on frames of one size with a linear cascade: one integral per frame and ONE region pass for regions of
-// any sizes (the machinery of vj_detect_chain's second half, the region list uploaded instead of built on the device) —
-// not one plan and one vj_detect call per distinct region size.
-static int detect_rois_on_device(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_roi* rois, int n_rois,
-                                 const vj_params* p, int W, int H, vj_result* out) {
-    int rc;
-    Plan* pl2;
-    if ((rc = get_plan(e, c, W, H, *p, &pl2))) return rc;
-    const uint64_t max_frames = max_frames_per_subbatch(e, pl2);
-    if (max_frames == 0) {
-        set_error("a single frame exceeds the 32-bit offset range");
-        return VJ_ERR_LIMIT;
-    }
-    {
-        uint64_t dummy = 0;
-        if (pl2->frames_q == 0 && (rc = layout_queues(pl2, 1, &dummy))) return rc;
-    }
-    Lane* L = &e->lane0;
-    const bool count2 = (p->flags & VJ_FLAG_COUNTERS) != 0;
-    const uint32_t stride = (uint32_t)W + 1u;
-    const uint64_t fbytes = (uint64_t)pl2->frame_elems * 4u;
-    struct Det2 { int roi; uint32_t slot, x, y; };
-    std::vector<Det2> dets2;
-    uint64_t child2_nodes = 0, child2_rects = 0;   // counted calls, multi-node trees: visited nodes below the roots (second cascade)
-    for (int f0 = 0; f0 < n_frames; f0 += (int)max_frames) {
-        const int nf = (int)std::min<uint64_t>(max_frames, (uint64_t)(n_frames - f0));
-        std::vector<RoiDev> regions;
-        std::vector<int> index;   // position in `regions` -> the caller's region
-        for (int i = 0; i < n_rois; ++i)
-            if (rois[i].frame >= f0 && rois[i].frame < f0 + nf) {
-                regions.push_back(RoiDev{rois[i].frame - f0, rois[i].x, rois[i].y, rois[i].w, rois[i].h});
-                index.push_back(i);
-            }
-        if (regions.empty()) continue;
-        if ((rc = enqueue_prepare(e, L, pl2, frames + f0, nf, W, H, false, nullptr))) return rc;
-        if (e->roi_unit_cap == 0) e->roi_unit_cap = 1u << 18;
-        if (e->roi_det_cap == 0) e->roi_det_cap = 1u << 16;
-        const uint32_t n_reg = (uint32_t)regions.size();
-        if ((rc = e->d_rois.ensure((size_t)n_reg * sizeof(RoiDev)))) return rc;
-        HIP_TRY(hipMemcpyAsync(e->d_rois.p, regions.data(), (size_t)n_reg * sizeof(RoiDev), hipMemcpyHostToDevice, e->stream));
-        uint32_t n_units = 0, n_det2 = 0;
-        float ms_roi = 0;
-        bool ok = false;
-        for (int attempt = 0; attempt < 6 && !ok; ++attempt) {
-            if ((rc = e->d_roi_units.ensure((size_t)e->roi_unit_cap * sizeof(RoiUnit)))) return rc;
-            if ((rc = e->d_roi_det.ensure((size_t)e->roi_det_cap * sizeof(RoiDet)))) return rc;
-            if (e->roi_tile_cap == 0) e->roi_tile_cap = 1u << 16;
-            if ((rc = e->d_roi_tiles.ensure((size_t)e->roi_tile_cap * sizeof(RoiTile)))) return rc;
-            HIP_TRY(hipMemsetAsync((uint32_t*)L->d_counts.p + (CountsLayout::q_counts - 40u), 0, 8 * 4, e->stream));   // tile tickets of the region pass
-            uint32_t* roi_counts = (uint32_t*)L->d_counts.p + CountsLayout::roi_off_u32;
-            HIP_TRY(hipMemsetAsync(roi_counts, 0, (8 + (size_t)VJ_MAX_STAGES * 2) * 4, e->stream));
-            HIP_TRY(hipMemsetAsync((uint32_t*)L->d_counts.p + CountsLayout::stage_off_u32 + 4, 0, 16, e->stream));   // the region pass's tree counters
-            HIP_TRY(hipMemcpyAsync(roi_counts, &n_reg, 4, hipMemcpyHostToDevice, e->stream));
-            RoiArgs ra;
-            CascadeArgs ca;
-            fill_region_args(e, L, pl2, c, *p, W, H, nf, n_reg, &ra, &ca);
-            HIP_TRY(hipEventRecord(L->launch_ev[2 * VJ_MAX_LAUNCHES - 2], e->stream));
-            const int hrc = launch_roi_chain(ra, ca, false, pl2->trees, count2, pl2->general, std::max(1, e->n_cu * e->blocks_per_cu), e->stream,
-                                             e->concurrent ? e->stream2 : nullptr, e->fork_ev, e->join_ev);
-            if (hrc) {
-                set_error("region pass launch failed: %s", hipGetErrorString((hipError_t)hrc));
-                return VJ_ERR_HIP;
-            }
-            HIP_TRY(hipEventRecord(L->launch_ev[2 * VJ_MAX_LAUNCHES - 1], e->stream));
-            HIP_TRY(hipMemcpyAsync((uint32_t*)L->h_pinned + CountsLayout::roi_off_u32, roi_counts, (8 + (size_t)VJ_MAX_STAGES * 2) * 4,
-                                   hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipMemcpyAsync((uint32_t*)L->h_pinned + CountsLayout::stage_off_u32 + 4, (uint32_t*)L->d_counts.p + CountsLayout::stage_off_u32 + 4, 16,
-                                   hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipEventRecord(L->done, e->stream));
-            HIP_TRY(hipEventSynchronize(L->done));
-            const uint32_t* hc = (const uint32_t*)L->h_pinned;
-            n_units = hc[CountsLayout::roi_off_u32 + 1];
-            n_det2 = hc[CountsLayout::roi_off_u32 + 4];
-            if (hc[CountsLayout::roi_off_u32 + 2] != 0) {
-                set_error("internal error: %u regions outside their frames", hc[CountsLayout::roi_off_u32 + 2]);
-                return VJ_ERR_HIP;
-            }
-            const uint32_t n_tiles2 = hc[CountsLayout::roi_off_u32 + 6];
-            if (n_units > e->roi_unit_cap || n_det2 > e->roi_det_cap || n_tiles2 > e->roi_tile_cap) {
-                e->roi_unit_cap = grown_cap(e->roi_unit_cap, n_units);
-                e->roi_det_cap = grown_cap(e->roi_det_cap, n_det2);
-                e->roi_tile_cap = grown_cap(e->roi_tile_cap, n_tiles2);
-                continue;
-            }
-            HIP_TRY(hipEventElapsedTime(&ms_roi, L->launch_ev[2 * VJ_MAX_LAUNCHES - 2], L->launch_ev[2 * VJ_MAX_LAUNCHES - 1]));
-            ok = true;
-        }
-        if (!ok) {
-            set_error("region buffers kept overflowing");
-            return VJ_ERR_LIMIT;
-        }
-        float ms_i = 0;
-        HIP_TRY(hipEventElapsedTime(&ms_i, L->ev[0], L->ev[1]));
-        out->timing.integral_ms += ms_i;
-        out->timing.cascade_ms += ms_roi;
-        out->timing.total_ms += ms_i + ms_roi;
-        out->timing.n_cascade_launches = 1;
-        std::vector<RoiDet> raw2(n_det2);
-        if (n_det2) HIP_TRY(hipMemcpy(raw2.data(), e->d_roi_det.p, (size_t)n_det2 * sizeof(RoiDet), hipMemcpyDeviceToHost));
-        for (const RoiDet& d : raw2) {
-            const uint32_t f = (uint32_t)(d.off / fbytes);
-            const uint32_t el = (uint32_t)((d.off - (uint64_t)f * fbytes) / 4u);
-            const RoiDev& r1 = regions[d.roi];
-            dets2.push_back(Det2{index[d.roi], d.slot, el % stride - (uint32_t)r1.x, el / stride - (uint32_t)r1.y});
-        }
-        if (count2) {
-            const unsigned long long* se = (const unsigned long long*)((const uint32_t*)L->h_pinned + CountsLayout::roi_off_u32 + 8);
-            const unsigned long long* tc = (const unsigned long long*)((const uint32_t*)L->h_pinned + CountsLayout::stage_off_u32) + 2;
-            child2_nodes += tc[0];
-            child2_rects += tc[1];
-            for (size_t s2 = 0; s2 < pl2->stages.size(); ++s2) out->counters.stage_entered[s2] += se[s2];
-        }
-    }
-    std::sort(dets2.begin(), dets2.end(), [](const Det2& a, const Det2& b) {
-        return std::make_tuple(a.roi, a.slot, a.y, a.x) < std::make_tuple(b.roi, b.slot, b.y, b.x);
-    });
-    out->count = (uint32_t)dets2.size();
-    if (!dets2.empty()) {
-        out->rects = (vj_rect*)malloc(dets2.size() * sizeof(vj_rect));
-        if (!out->rects) return VJ_ERR_NOMEM;
-        for (size_t i = 0; i < dets2.size(); ++i) {
-            const vj_scale_info& si = pl2->scales_info[dets2[i].slot];
-            out->rects[i] = vj_rect{(int32_t)dets2[i].x, (int32_t)dets2[i].y, si.win_w, si.win_h, 0.0f, dets2[i].roi, si.scale_idx};
-        }
-    }
-    if (p->min_neighbors != 0 && out->count) {
-        rc = vj_group_rectangles(out->rects, &out->count, (int)std::max<uint32_t>(p->min_neighbors, 1u), 0.2);
-        if (rc) return rc;
-    }
-    if (count2) {
-        vj_counters& k = out->counters;
-        k.windows = k.stage_entered[0];
-        uint64_t rect_evals = 0;
-        for (size_t s2 = 0; s2 < pl2->stages.size(); ++s2) {   // (as fill_counters: roots on the host, visited child nodes from the device)
-            k.stump_evals += k.stage_entered[s2] * (pl2->trees ? pl2->prog.n_roots[s2] : pl2->prog.n_nodes[s2]);
-            rect_evals += k.stage_entered[s2] * (pl2->trees ? pl2->prog.n_root_rects[s2] : pl2->prog.n_rects[s2]);
-        }
-        if (pl2->trees) {
-            k.stump_evals += child2_nodes;
-            rect_evals += child2_rects;
-        }
-        k.gather_bytes = 48ull * k.windows + 16ull * rect_evals;
-    }
-    return VJ_OK;
-}
-
-
-extern "C" {
+static void drop_plans(vj_env* e);   // (defined below)
 
 int vj_env_create(int device_index, vj_env** out) {
     if (!out) return VJ_ERR_ARG;
@@ -2022,574 +1237,6 @@ int vj_integral(vj_env* e, const uint8_t* gray, int w, int h, int stride, uint32
     if (!e || !gray || !sum || !sqsum || w <= 0 || h <= 0 || stride < w) return VJ_ERR_ARG;
     vj_image im{gray, w, h, stride, 0, 1};
     return vj_integral_image(e, &im, sum, sqsum);
-}
-
-int vj_detect(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_params* p,
-              vj_result* out) {
-    if (!e || !c || !p || !out || n_frames < 0 || (n_frames > 0 && !frames)) return VJ_ERR_ARG;
-    memset(out, 0, sizeof(*out));
-    if (n_frames == 0) return VJ_OK;
-    // VJ_FLAG_EQUALIZE_HIST is read here and nowhere else: plans, balance entries and kernels see the parameters without it
-    const bool equalize = (p->flags & VJ_FLAG_EQUALIZE_HIST) != 0u;
-    vj_params q = *p;
-    q.flags &= ~(uint32_t)VJ_FLAG_EQUALIZE_HIST;
-    p = &q;
-    int rc = check_params(*p);
-    if (rc) return rc;
-    int W, H, CH;
-    rc = check_frames(frames, n_frames, &W, &H, &CH);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    Plan* pl;
-    vj_env::Balance* bal = balance_of(e, c, W, H, *p, n_frames, true);   // (created before the plan is looked up: it names the split)
-    if (bal) balance_touch(bal, n_frames);
-    rc = get_plan(e, c, W, H, *p, &pl, n_frames);
-    if (rc) return rc;
-    const uint64_t max_frames = max_frames_per_subbatch(e, pl);
-    if (max_frames == 0) {
-        set_error("a single frame exceeds the 32-bit offset range");
-        return VJ_ERR_LIMIT;
-    }
-    std::vector<RawDet> dets;
-    for (int f0 = 0; f0 < n_frames; f0 += (int)max_frames) {
-        const int nf = (int)std::min<uint64_t>(max_frames, (uint64_t)(n_frames - f0));
-        rc = detect_subbatch(e, pl, frames, f0, nf, W, H, *p, equalize, &dets, &out->counters, &out->timing);
-        if (rc) return rc;
-    }
-    // feedback for the chain balance: only the timed (uncounted) kernel variants.  A plan none of whose scales can run on tiles
-    // has nothing to balance; a CANDIDATE split that leaves one chain only (every tile moved to the gathers, or a share of
-    // the scales without large ones) is measured like any other — the search must be able to step back from it
-    if (bal && bal->phase != 3) {
-        bool any_tile_scale = false;
-        for (const ScaleDev& sd : pl->scales) any_tile_scale |= sd.tile_rw != 0;
-        if (!any_tile_scale) {
-            bal->cur = bal->best;
-            bal->phase = 3;
-        } else if (!(p->flags & VJ_FLAG_COUNTERS) && (uint64_t)n_frames <= max_frames && n_frames == bal->n_ref) {
-            balance_report(bal, out->timing.cascade_ms / (float)n_frames, !e->tile_thresholds_set);
-        }
-    }
-    out->timing.tile_split = pl->tile_split;
-    out->timing.balance_state = !bal ? 0 : bal->phase == 3 ? 2 : 1;
-    out->timing.balance_calls = bal ? bal->calls : 0;
-    return build_result(pl, dets, n_frames, *p, out);
-}
-
-// Second cascade on regions of interest (config 5: eyes inside faces).  A ROI is a view —
-// pointer + stride — into its frame, as the reference's callers would pass a sub-image header; detection windows
-// come in few distinct sizes, so the ROIs are grouped by size and every group is ONE batched vj_detect pass.
-int vj_detect_rois(vj_env* e, const vj_cascade* c, const vj_image* frames, int n_frames, const vj_roi* rois, int n_rois,
-                   const vj_params* p, vj_result* out) {
-    if (!e || !c || !p || !out || n_frames < 0 || n_rois < 0 || (n_rois > 0 && (!frames || !rois))) return VJ_ERR_ARG;
-    memset(out, 0, sizeof(*out));
-    if (refuse_equalize(p->flags, "vj_detect_rois")) return VJ_ERR_UNSUPPORTED;
-    {
-        const int prc = check_params(*p);
-        if (prc) return prc;
-    }
-    std::map<std::pair<int, int>, std::vector<int>> by_size;   // (w, h) -> ROI indices
-    for (int i = 0; i < n_rois; ++i) {
-        const vj_roi& r = rois[i];
-        if (r.frame < 0 || r.frame >= n_frames || !frames[r.frame].data || r.w <= 0 || r.h <= 0 || r.x < 0 || r.y < 0 ||
-            r.x + r.w > frames[r.frame].width || r.y + r.h > frames[r.frame].height) {
-            set_error("roi %d lies outside its frame", i);
-            return VJ_ERR_ARG;
-        }
-        by_size[{r.w, r.h}].push_back(i);
-    }
-    // frames of one size, a linear cascade, the exhaustive grid: every region in one pass on the frames' own integral images
-    // (a scale mask selects among the plan's scales; every region still enumerates its own prefix of them)
-    if (n_rois > 0 && n_frames > 0 && !(p->flags & (VJ_FLAG_SKIP_LIST | VJ_FLAG_SKIP_ROW)) && p->scale_factor > 1.0f && e->rois_on_device) {
-        bool same = true;
-        for (int i = 0; i < n_frames && same; ++i)
-            same = frames[i].data && frames[i].width == frames[0].width && frames[i].height == frames[0].height &&
-                   image_channels(frames[i]) == image_channels(frames[0]) && frames[i].stride >= frames[i].width * image_channels(frames[i]);
-        int W = 0, H = 0, CH = 0;
-        if (same && check_frames(frames, n_frames, &W, &H, &CH) == VJ_OK) {
-            HIP_TRY(hipSetDevice(e->device));
-            return detect_rois_on_device(e, c, frames, n_frames, rois, n_rois, p, W, H, out);
-        }
-    }
-    std::vector<vj_rect> all;
-    for (const auto& kv : by_size) {
-        std::vector<vj_image> views;
-        int ch0 = -1;
-        for (int i : kv.second) {
-            const vj_roi& r = rois[i];
-            const vj_image& f = frames[r.frame];
-            const int ch = image_channels(f);
-            if (ch0 < 0) ch0 = ch;
-            if (ch != ch0) {
-                set_error("ROIs of one size must come from frames with the same channel count");
-                return VJ_ERR_ARG;
-            }
-            views.push_back(vj_image{f.data + (size_t)r.y * (size_t)f.stride + (size_t)r.x * (size_t)ch, r.w, r.h, f.stride,
-                                     f.on_device, f.channels});
-        }
-        vj_result part;
-        int rc = vj_detect(e, c, views.data(), (int)views.size(), p, &part);
-        if (rc) {
-            vj_result_free(&part);
-            return rc;
-        }
-        for (uint32_t k = 0; k < part.count; ++k) {
-            vj_rect rr = part.rects[k];
-            rr.frame = kv.second[(size_t)rr.frame];   // index in the batch -> ROI index
-            all.push_back(rr);
-        }
-        // counters and times add up over the groups
-        out->counters.windows += part.counters.windows;
-        out->counters.stump_evals += part.counters.stump_evals;
-        out->counters.gather_bytes += part.counters.gather_bytes;
-        for (int s2 = 0; s2 < VJ_MAX_STAGES; ++s2) out->counters.stage_entered[s2] += part.counters.stage_entered[s2];
-        out->timing.integral_ms += part.timing.integral_ms;
-        out->timing.cascade_ms += part.timing.cascade_ms;
-        out->timing.total_ms += part.timing.total_ms;
-        vj_result_free(&part);
-    }
-    std::stable_sort(all.begin(), all.end(), [](const vj_rect& a, const vj_rect& b) { return a.frame < b.frame; });
-    out->count = (uint32_t)all.size();
-    if (!all.empty()) {
-        out->rects = (vj_rect*)malloc(all.size() * sizeof(vj_rect));
-        if (!out->rects) return VJ_ERR_NOMEM;
-        memcpy(out->rects, all.data(), all.size() * sizeof(vj_rect));
-    }
-    return VJ_OK;
-}
-
-
-// ------------------------------------------------------------------ two cascades, hand-off on the device
-int vj_detect_chain(vj_env* e, const vj_cascade* first, const vj_cascade* second, const vj_image* frames, int n_frames,
-                    const vj_params* p_first, const vj_params* p_second, vj_result* out_first, vj_result* out_second) {
-    if (!e || !first || !second || !p_first || !p_second || !out_first || !out_second || n_frames < 0 || (n_frames > 0 && !frames))
-        return VJ_ERR_ARG;
-    memset(out_first, 0, sizeof(*out_first));
-    memset(out_second, 0, sizeof(*out_second));
-    if (refuse_equalize(p_first->flags | p_second->flags, "vj_detect_chain")) return VJ_ERR_UNSUPPORTED;
-    if (n_frames == 0) return VJ_OK;
-    for (const vj_params* pp : {p_first, p_second}) {
-        const int prc = check_params(*pp);
-        if (prc) return prc;
-    }
-    if ((p_first->flags | p_second->flags) & (VJ_FLAG_SKIP_LIST | VJ_FLAG_SKIP_ROW)) {
-        // the CPU variants' skip rules make a window's fate depend on its row's history inside ITS image: the first cascade runs
-        // as vj_detect does, the second one per region size on the sub-images (vj_detect_rois' path for these modes) — the
-        // hand-off goes through the host, the results are the ones the definition above gives
-        int rc = vj_detect(e, first, frames, n_frames, p_first, out_first);
-        if (rc) return rc;
-        std::vector<vj_roi> regions(out_first->count);
-        for (uint32_t i = 0; i < out_first->count; ++i) {
-            const vj_rect& q = out_first->rects[i];
-            regions[i] = vj_roi{(int32_t)q.frame, q.x, q.y, q.w, q.h};
-        }
-        if (regions.empty()) return VJ_OK;
-        return vj_detect_rois(e, second, frames, n_frames, regions.data(), (int)regions.size(), p_second, out_second);
-    }
-    const bool grouped = p_first->min_neighbors != 0;   // the regions are the GROUPED candidates (grouped on the device)
-    int W, H, CH;
-    int rc = check_frames(frames, n_frames, &W, &H, &CH);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    Plan *pl1, *pl2;
-    // (the first cascade's chain balance is found by feedback as in vj_detect: its kernels run before the region pass starts)
-    vj_env::Balance* bal = balance_of(e, first, W, H, *p_first, n_frames, true);
-    if (bal) balance_touch(bal, n_frames);
-    if ((rc = get_plan(e, first, W, H, *p_first, &pl1, n_frames))) return rc;
-    // the second cascade is planned for the frame's stride and every scale a region as large as the frame could use;
-    // each region picks its own scales and grid on the device
-    if ((rc = get_plan(e, second, W, H, *p_second, &pl2))) return rc;
-    if ((rc = get_plan(e, first, W, H, *p_first, &pl1, n_frames))) return rc;   // (the cache may have evicted it for pl2: look it up again)
-    const uint64_t max_frames = std::min(max_frames_per_subbatch(e, pl1), max_frames_per_subbatch(e, pl2));
-    if (max_frames == 0) {
-        set_error("a single frame exceeds the 32-bit offset range");
-        return VJ_ERR_LIMIT;
-    }
-    {   // the second plan's scale records go to the device with a queue layout (none is used by the region pass)
-        uint64_t dummy = 0;
-        if (pl2->frames_q == 0 && (rc = layout_queues(pl2, 1, &dummy))) return rc;
-    }
-    Lane* L = &e->lane0;
-    std::vector<RawDet> dets1;
-    std::vector<vj_rect> grouped1;       // grouped mode: the first result, as the device grouped it
-    struct Det2 { int roi; uint32_t slot, x, y; };
-    std::vector<Det2> dets2;
-    uint64_t child2_nodes = 0, child2_rects = 0;   // counted calls, multi-node trees: visited nodes below the roots (second cascade)
-    const bool count2 = (p_second->flags & VJ_FLAG_COUNTERS) != 0;
-    const uint32_t stride = (uint32_t)W + 1u;
-    const uint64_t fbytes = (uint64_t)pl1->frame_elems * 4u;
-    for (int f0 = 0; f0 < n_frames; f0 += (int)max_frames) {
-        const int nf = (int)std::min<uint64_t>(max_frames, (uint64_t)(n_frames - f0));
-        if ((rc = enqueue_prepare(e, L, pl1, frames + f0, nf, W, H, false, nullptr))) return rc;
-        if (e->roi_unit_cap == 0) e->roi_unit_cap = 1u << 18;
-        if (e->roi_det_cap == 0) e->roi_det_cap = 1u << 16;
-        uint32_t n_det1 = 0, n_units = 0, n_det2 = 0;
-        size_t roi_weight_off = 0;   // grouped mode: where the groups' member counts sit in d_group
-        float ms_roi = 0;
-        bool ok = false;
-        for (int attempt = 0; attempt < 6 && !ok; ++attempt) {
-            if ((rc = enqueue_cascade(e, L, pl1, W, H, *p_first))) return rc;
-            if ((rc = e->d_rois.ensure((size_t)L->det_cap * sizeof(RoiDev)))) return rc;
-            GroupArgs ga;
-            memset(&ga, 0, sizeof(ga));
-            if (grouped) {
-                // one buffer: keys (u64) | grouped | the zeroed counter block | frame_first | weights
-                const size_t cap = L->det_cap, nfz = (size_t)nf;
-                const size_t o_keys = 0, o_grouped = o_keys + cap * 8u, o_zero = o_grouped + cap * sizeof(RoiDev),
-                             o_first = o_zero + (3u * nfz + 1u) * 4u, o_gw = o_first + (nfz + 1u) * 4u, o_rw = o_gw + cap * 4u,
-                             total = o_rw + cap * 4u;
-                if ((rc = e->d_group.ensure(total))) return rc;
-                char* gb = (char*)e->d_group.p;
-                ga.det = (const DetEntry*)L->d_det.p;
-                ga.det_count = (const uint32_t*)L->d_counts.p + MAX_PASSES * CountsLayout::q_counts;
-                ga.det_cap = L->det_cap;
-                ga.scales = (const ScaleDev*)pl1->d_scales.p;
-                ga.frame_bytes = pl1->frame_elems * 4u;
-                ga.stride = stride;
-                ga.n_frames = (uint32_t)nf;
-                ga.threshold = (int32_t)std::max<uint32_t>(p_first->min_neighbors, 1u);   // clod.cpp:1326
-                ga.eps = 0.2;                                                               // clod.cpp:11
-                ga.keys = (uint64_t*)(gb + o_keys);
-                ga.grouped = (RoiDev*)(gb + o_grouped);
-                ga.frame_count = (uint32_t*)(gb + o_zero);
-                ga.frame_cursor = ga.frame_count + nfz;
-                ga.grouped_count = ga.frame_cursor + nfz;
-                ga.overflow = ga.grouped_count + nfz;
-                ga.frame_first = (uint32_t*)(gb + o_first);
-                ga.grouped_weight = (uint32_t*)(gb + o_gw);
-                ga.roi_weight = (uint32_t*)(gb + o_rw);
-                roi_weight_off = o_rw;
-                ga.rois = (RoiDev*)e->d_rois.p;
-                ga.max_rois = L->det_cap;
-                ga.group_max = (uint32_t)e->group_max;
-            }
-            if ((rc = e->d_roi_units.ensure((size_t)e->roi_unit_cap * sizeof(RoiUnit)))) return rc;
-            if ((rc = e->d_roi_det.ensure((size_t)e->roi_det_cap * sizeof(RoiDet)))) return rc;
-            if (e->roi_tile_cap == 0) e->roi_tile_cap = 1u << 16;
-            if ((rc = e->d_roi_tiles.ensure((size_t)e->roi_tile_cap * sizeof(RoiTile)))) return rc;
-            uint32_t* roi_counts = (uint32_t*)L->d_counts.p + CountsLayout::roi_off_u32;   // zeroed with the block by enqueue_cascade (the tile tickets too)
-            RoiArgs ra;
-            CascadeArgs ca;
-            fill_region_args(e, L, pl2, second, *p_second, W, H, nf, L->det_cap, &ra, &ca);
-            ra.det_in = (const DetEntry*)L->d_det.p;
-            ra.det_in_count = (const uint32_t*)L->d_counts.p + MAX_PASSES * CountsLayout::q_counts;
-            ra.det_in_cap = L->det_cap;
-            ra.scales_in = (const ScaleDev*)pl1->d_scales.p;
-            HIP_TRY(hipEventRecord(L->launch_ev[2 * VJ_MAX_LAUNCHES - 2], e->stream));
-            if (grouped) {
-                ga.n_rois = ra.n_rois;
-                const int grc = launch_group_rois(ga, e->stream);
-                if (grc) {
-                    set_error("grouping launch failed: %s", hipGetErrorString((hipError_t)grc));
-                    return VJ_ERR_HIP;
-                }
-                HIP_TRY(hipMemcpyAsync((uint32_t*)L->h_pinned + CountsLayout::roi_off_u32 + 5, ga.overflow, 4, hipMemcpyDeviceToHost, e->stream));
-            }
-            const int hrc = launch_roi_chain(ra, ca, !grouped, pl2->trees, count2, pl2->general, std::max(1, e->n_cu * e->blocks_per_cu), e->stream,
-                                             e->concurrent ? e->stream2 : nullptr, e->fork_ev, e->join_ev);
-            if (hrc) {
-                set_error("region pass launch failed: %s", hipGetErrorString((hipError_t)hrc));
-                return VJ_ERR_HIP;
-            }
-            HIP_TRY(hipEventRecord(L->launch_ev[2 * VJ_MAX_LAUNCHES - 1], e->stream));
-            // the region counters join the block enqueue_cascade already copies; copy them again now that they are final
-            HIP_TRY(hipMemcpyAsync((uint32_t*)L->h_pinned + CountsLayout::roi_off_u32, roi_counts, 5 * 4, hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipMemcpyAsync((uint32_t*)L->h_pinned + CountsLayout::roi_off_u32 + 6, roi_counts + 6, 4, hipMemcpyDeviceToHost, e->stream));   // region tiles
-            HIP_TRY(hipMemcpyAsync((uint32_t*)L->h_pinned + CountsLayout::roi_off_u32 + 8, roi_counts + 8, (size_t)VJ_MAX_STAGES * 2 * 4,
-                                   hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipMemcpyAsync((uint32_t*)L->h_pinned + CountsLayout::stage_off_u32 + 4, (uint32_t*)L->d_counts.p + CountsLayout::stage_off_u32 + 4, 16,
-                                   hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipEventRecord(L->done, e->stream));
-            HIP_TRY(hipEventSynchronize(L->done));
-            const uint32_t* hc = (const uint32_t*)L->h_pinned;
-            n_det1 = hc[MAX_PASSES * CountsLayout::q_counts];
-            n_units = hc[CountsLayout::roi_off_u32 + 1];
-            n_det2 = hc[CountsLayout::roi_off_u32 + 4];
-            if (hc[CountsLayout::roi_off_u32 + 2] != 0) {
-                set_error("internal error: %u regions outside their frames", hc[CountsLayout::roi_off_u32 + 2]);
-                return VJ_ERR_HIP;
-            }
-            if (n_det1 > L->det_cap) {   // as finish_batch would: grow, and run both cascades again
-                const uint32_t want = grown_cap(L->det_cap, n_det1);
-                if ((rc = L->d_det.ensure((size_t)want * sizeof(DetEntry)))) return rc;
-                L->det_cap = want;
-                continue;
-            }
-            if (grouped && hc[CountsLayout::roi_off_u32 + 5] != 0) {
-                // a frame with more raw candidates than the device kernel groups: the same result the long way round
-                // (group on the host, hand the regions back as a list)
-                vj_result_free(out_first);
-                vj_result_free(out_second);
-                if ((rc = vj_detect(e, first, frames, n_frames, p_first, out_first))) return rc;
-                std::vector<vj_roi> rois(out_first->count);
-                for (uint32_t i = 0; i < out_first->count; ++i) {
-                    const vj_rect& r = out_first->rects[i];
-                    rois[i] = vj_roi{r.frame, r.x, r.y, r.w, r.h};
-                }
-                return vj_detect_rois(e, second, frames, n_frames, rois.data(), (int)rois.size(), p_second, out_second);
-            }
-            const uint32_t n_tiles2 = hc[CountsLayout::roi_off_u32 + 6];
-            if (n_units > e->roi_unit_cap || n_det2 > e->roi_det_cap || n_tiles2 > e->roi_tile_cap) {
-                e->roi_unit_cap = grown_cap(e->roi_unit_cap, n_units);
-                e->roi_det_cap = grown_cap(e->roi_det_cap, n_det2);
-                e->roi_tile_cap = grown_cap(e->roi_tile_cap, n_tiles2);
-                continue;
-            }
-            HIP_TRY(hipEventElapsedTime(&ms_roi, L->launch_ev[2 * VJ_MAX_LAUNCHES - 2], L->launch_ev[2 * VJ_MAX_LAUNCHES - 1]));
-            ok = true;
-        }
-        if (!ok) {
-            set_error("region buffers kept overflowing");
-            return VJ_ERR_LIMIT;
-        }
-        // first cascade: decode (device order kept in raw1 for the region numbers)
-        const size_t base1 = dets1.size();
-        std::vector<DetEntry> raw1;
-        if ((rc = finish_batch(e, L, pl1, f0, W, H, *p_first, &dets1, &out_first->counters, &out_first->timing, &raw1))) return rc;
-        // second cascade
-        std::vector<RoiDet> raw2(n_det2);
-        if (n_det2) HIP_TRY(hipMemcpy(raw2.data(), e->d_roi_det.p, (size_t)n_det2 * sizeof(RoiDet), hipMemcpyDeviceToHost));
-        std::vector<RoiDev> regions;
-        size_t base_g = grouped1.size();
-        if (grouped) {   // the first result is the region list itself
-            const uint32_t n_rois = ((const uint32_t*)L->h_pinned)[CountsLayout::roi_off_u32 + 0];
-            regions.resize(n_rois);
-            std::vector<uint32_t> weights(n_rois);
-            if (n_rois) {
-                HIP_TRY(hipMemcpy(regions.data(), e->d_rois.p, (size_t)n_rois * sizeof(RoiDev), hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(weights.data(), (const char*)e->d_group.p + roi_weight_off, (size_t)n_rois * 4u, hipMemcpyDeviceToHost));
-            }
-            for (uint32_t i = 0; i < n_rois; ++i)
-                grouped1.push_back(vj_rect{regions[i].x, regions[i].y, regions[i].w, regions[i].h, (float)weights[i], regions[i].frame + f0, -1});
-        }
-        for (const RoiDet& d : raw2) {
-            const uint32_t f = (uint32_t)(d.off / fbytes);
-            const uint32_t el = (uint32_t)((d.off - (uint64_t)f * fbytes) / 4u);
-            if (grouped) {
-                const RoiDev& r1 = regions[d.roi];
-                dets2.push_back(Det2{(int)(base_g + d.roi), d.slot, el % stride - (uint32_t)r1.x, el / stride - (uint32_t)r1.y});
-            } else {
-                const RawDet& r1 = dets1[base1 + d.roi];
-                dets2.push_back(Det2{(int)(base1 + d.roi), d.slot, el % stride - r1.x, el / stride - r1.y});
-            }
-        }
-        out_second->timing.cascade_ms += ms_roi;
-        out_second->timing.total_ms += ms_roi;
-        out_second->timing.n_cascade_launches = 1;
-        if (count2) {
-            const unsigned long long* se = (const unsigned long long*)((const uint32_t*)L->h_pinned + CountsLayout::roi_off_u32 + 8);
-            const unsigned long long* tc = (const unsigned long long*)((const uint32_t*)L->h_pinned + CountsLayout::stage_off_u32) + 2;
-            child2_nodes += tc[0];
-            child2_rects += tc[1];
-            for (size_t s2 = 0; s2 < pl2->stages.size(); ++s2) out_second->counters.stage_entered[s2] += se[s2];
-        }
-    }
-    if (bal && bal->phase != 3) {   // (as vj_detect: one sub-batch, timed kernel variants only)
-        bool any_tile_scale = false;
-        for (const ScaleDev& sd : pl1->scales) any_tile_scale |= sd.tile_rw != 0;
-        if (!any_tile_scale) {
-            bal->cur = bal->best;
-            bal->phase = 3;
-        } else if (!(p_first->flags & VJ_FLAG_COUNTERS) && (uint64_t)n_frames <= max_frames && n_frames == bal->n_ref) {
-            balance_report(bal, out_first->timing.cascade_ms / (float)n_frames, !e->tile_thresholds_set);
-        }
-    }
-    out_first->timing.tile_split = pl1->tile_split;
-    out_first->timing.balance_state = !bal ? 0 : bal->phase == 3 ? 2 : 1;
-    out_first->timing.balance_calls = bal ? bal->calls : 0;
-    // the first result in its sorted order; regions are numbered by their position in it
-    std::vector<uint32_t> rank;
-    if (grouped) {   // frames in order, groups in cv::partition's class order: already the result's order
-        rank.resize(grouped1.size());
-        for (size_t i = 0; i < rank.size(); ++i) rank[i] = (uint32_t)i;
-        out_first->count = (uint32_t)grouped1.size();
-        if (!grouped1.empty()) {
-            out_first->rects = (vj_rect*)malloc(grouped1.size() * sizeof(vj_rect));
-            if (!out_first->rects) return VJ_ERR_NOMEM;
-            memcpy(out_first->rects, grouped1.data(), grouped1.size() * sizeof(vj_rect));
-        }
-        fill_counters(pl1, n_frames, *p_first, out_first);
-    } else {
-        std::vector<uint32_t> order(dets1.size());
-        for (size_t i = 0; i < order.size(); ++i) order[i] = (uint32_t)i;
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-            return std::tie(dets1[a].frame, dets1[a].slot, dets1[a].y, dets1[a].x) < std::tie(dets1[b].frame, dets1[b].slot, dets1[b].y, dets1[b].x);
-        });
-        rank.resize(dets1.size());
-        for (size_t i = 0; i < order.size(); ++i) rank[order[i]] = (uint32_t)i;
-        if ((rc = build_result(pl1, dets1, n_frames, *p_first, out_first))) return rc;
-    }
-    std::sort(dets2.begin(), dets2.end(), [&](const Det2& a, const Det2& b) {
-        return std::make_tuple(rank[a.roi], a.slot, a.y, a.x) < std::make_tuple(rank[b.roi], b.slot, b.y, b.x);
-    });
-    out_second->count = (uint32_t)dets2.size();
-    if (!dets2.empty()) {
-        out_second->rects = (vj_rect*)malloc(dets2.size() * sizeof(vj_rect));
-        if (!out_second->rects) return VJ_ERR_NOMEM;
-        for (size_t i = 0; i < dets2.size(); ++i) {
-            const vj_scale_info& si = pl2->scales_info[dets2[i].slot];
-            out_second->rects[i] = vj_rect{(int32_t)dets2[i].x, (int32_t)dets2[i].y, si.win_w, si.win_h, 0.0f, (int32_t)rank[dets2[i].roi],
-                                           si.scale_idx};
-        }
-    }
-    if (p_second->min_neighbors != 0 && out_second->count) {
-        rc = vj_group_rectangles(out_second->rects, &out_second->count, (int)std::max<uint32_t>(p_second->min_neighbors, 1u), 0.2);
-        if (rc) return rc;
-    }
-    if (count2) {
-        vj_counters& k = out_second->counters;
-        k.windows = k.stage_entered[0];
-        uint64_t rect_evals = 0;
-        for (size_t s2 = 0; s2 < pl2->stages.size(); ++s2) {   // (as fill_counters: roots on the host, visited child nodes from the device)
-            k.stump_evals += k.stage_entered[s2] * (pl2->trees ? pl2->prog.n_roots[s2] : pl2->prog.n_nodes[s2]);
-            rect_evals += k.stage_entered[s2] * (pl2->trees ? pl2->prog.n_root_rects[s2] : pl2->prog.n_rects[s2]);
-        }
-        if (pl2->trees) {
-            k.stump_evals += child2_nodes;
-            rect_evals += child2_rects;
-        }
-        k.gather_bytes = 48ull * k.windows + 16ull * rect_evals;
-    }
-    return VJ_OK;
-}
-
-// ------------------------------------------------------------------ frame streams
-struct vj_stream {
-    vj_env* e = nullptr;
-    vj_params p;
-    int W = 0, H = 0, CH = 1, max_batch = 0;
-    std::unique_ptr<Plan> plan;     // private: its queue layout must not change while a batch is in flight
-    Lane lanes[2];
-    hipStream_t copy = nullptr;
-    int fifo[2] = {0, 0};           // lanes holding submitted batches, oldest first
-    int n_pending = 0;
-    int n_frames_of[2] = {0, 0};
-};
-
-int vj_stream_create(vj_env* e, const vj_cascade* c, int width, int height, int channels, int max_batch, const vj_params* p,
-                     vj_stream** out) {
-    if (!out) return VJ_ERR_ARG;
-    *out = nullptr;
-    if (!e || !c || !p || width <= 0 || height <= 0 || max_batch <= 0) return VJ_ERR_ARG;
-    const int CH = channels <= 1 ? 1 : channels;
-    if (CH != 1 && CH != 3 && CH != 4) return VJ_ERR_ARG;
-    if (refuse_equalize(p->flags, "vj_stream_create")) return VJ_ERR_UNSUPPORTED;
-    if (check_params(*p)) return VJ_ERR_ARG;
-    if ((uint64_t)(width + 1) * (uint64_t)(height + 3) >= (1ull << 30)) {
-        set_error("image too large");
-        return VJ_ERR_LIMIT;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    auto s = std::make_unique<vj_stream>();
-    s->e = e;
-    s->p = *p;
-    s->W = width;
-    s->H = height;
-    s->CH = CH;
-    s->max_batch = max_batch;
-    s->plan = std::make_unique<Plan>();
-    struct Guard {   // releases what was created when a later step fails
-        vj_stream* s;
-        ~Guard() { if (s) vj_stream_destroy(s); }
-    } guard{nullptr};
-    // (a chain balance already found for this workload by vj_detect's feedback is taken over; a stream does not search itself)
-    const vj_env::Balance* bal = balance_of(e, c, width, height, *p, max_batch, false);
-    const bool lower_thresholds = bal && balance_choice(bal, -1).thr == 1 && !e->tile_thresholds_set;
-    int rc = plan_and_upload(e, *c, width, height, *p, s->plan.get(), bal ? bal->best : e->split_for(max_batch, *p, linear_stumps(*c)),
-                             thresholds_for(*e, lower_thresholds ? 3 : 0), max_batch, false);
-    if (rc) {
-        s->plan->release_device();
-        return rc;
-    }
-    vj_stream* raw = s.release();
-    guard.s = raw;
-    if ((uint64_t)max_batch > max_frames_per_subbatch(e, raw->plan.get())) {
-        set_error("max_batch %d exceeds what one launch sequence can address at this frame size (%llu frames)", max_batch,
-                  (unsigned long long)max_frames_per_subbatch(e, raw->plan.get()));
-        return VJ_ERR_LIMIT;
-    }
-    for (Lane& L : raw->lanes) {
-        if ((rc = L.create())) return rc;
-        L.shared_integrals = true;
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&raw->copy, hipStreamNonBlocking));
-    // every buffer at its final size now: nothing is (re)allocated while batches are in flight
-    for (Lane& L : raw->lanes)
-        if ((rc = ensure_image_buffers(e, width, height, max_batch, true, CH, &L))) return rc;
-    uint64_t q_entries = 0;
-    if ((rc = layout_queues(raw->plan.get(), max_batch, &q_entries))) return rc;
-    const size_t n_pass = raw->plan->pass_bounds.size() - 1;
-    for (size_t ps = 1; ps < n_pass; ++ps)
-        if ((rc = e->d_q[ps].ensure(std::max<uint64_t>(q_entries, 1) * sizeof(QEntry)))) return rc;
-    guard.s = nullptr;
-    *out = raw;
-    return VJ_OK;
-}
-
-int vj_stream_submit(vj_stream* s, const vj_image* frames, int n_frames) {
-    if (!s || !frames || n_frames <= 0 || n_frames > s->max_batch) return VJ_ERR_ARG;
-    if (s->n_pending >= 2) {
-        set_error("two batches are pending: collect one before submitting the next");
-        return VJ_ERR_LIMIT;
-    }
-    int W, H, CH;
-    int rc = check_frames(frames, n_frames, &W, &H, &CH);
-    if (rc) return rc;
-    if (W != s->W || H != s->H || CH != s->CH) {
-        set_error("frames do not have the stream's size / channel count");
-        return VJ_ERR_ARG;
-    }
-    vj_env* e = s->e;
-    HIP_TRY(hipSetDevice(e->device));
-    const int lane = s->n_pending == 0 ? 0 : 1 - s->fifo[0];
-    Lane* L = &s->lanes[lane];
-    // the lane's frame buffer is free once the integral kernels of its previous batch have read it
-    HIP_TRY(hipEventSynchronize(L->integral_done));
-    if ((rc = enqueue_prepare(e, L, s->plan.get(), frames, n_frames, W, H, true, s->copy, false, true))) return rc;
-    if ((rc = enqueue_cascade(e, L, s->plan.get(), W, H, s->p))) return rc;
-    s->fifo[s->n_pending] = lane;
-    s->n_frames_of[lane] = n_frames;
-    s->n_pending++;
-    return VJ_OK;
-}
-
-int vj_stream_collect(vj_stream* s, vj_result* out) {
-    if (!s || !out) return VJ_ERR_ARG;
-    memset(out, 0, sizeof(*out));
-    if (s->n_pending == 0) {
-        set_error("no batch is pending");
-        return VJ_ERR_ARG;
-    }
-    vj_env* e = s->e;
-    HIP_TRY(hipSetDevice(e->device));
-    const int lane = s->fifo[0];
-    s->fifo[0] = s->fifo[1];
-    s->n_pending--;
-    Lane* L = &s->lanes[lane];
-    std::vector<RawDet> dets;
-    int rc = finish_batch(e, L, s->plan.get(), 0, s->W, s->H, s->p, &dets, &out->counters, &out->timing);
-    if (rc) return rc;
-    return build_result(s->plan.get(), dets, s->n_frames_of[lane], s->p, out);
-}
-
-void vj_stream_destroy(vj_stream* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->e->device);
-    if (s->e->stream) (void)hipStreamSynchronize(s->e->stream);
-    if (s->e->stream2) (void)hipStreamSynchronize(s->e->stream2);
-    if (s->copy) {
-        (void)hipStreamSynchronize(s->copy);
-        (void)hipStreamDestroy(s->copy);
-    }
-    for (Lane& L : s->lanes) L.destroy();
-    if (s->plan) s->plan->release_device();
-    delete s;
-}
-
-void vj_result_free(vj_result* r) {
-    if (!r) return;
-    free(r->rects);
-    r->rects = nullptr;
-    r->count = 0;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// Internals of the host driver shared by its translation units (vj_env.cpp: the clod arithmetic profile;
-// vj_cv.cpp: the OpenCV arithmetic profile).  Not part of the C ABI.
+// Internals of the host driver shared by its translation units (vj_env.cpp: the environment; vj_detect*.cpp: the
+// clod arithmetic profile's drivers; vj_cv.cpp: the OpenCV arithmetic profile).  Not part of the C ABI.
 #pragma once
 #include "vj_internal.hpp"
 #include "vj_device.hpp"
@@ -9,6 +9,7 @@
 #include "vj_cv_roi_host.hpp"
 #include "vj_cv_points_host.hpp"
 #include "vj_points_host.hpp"
+#include "vj_detect_host.hpp"
 
 #include <hip/hip_runtime_api.h>
 
@@ -316,6 +317,7 @@ int enqueue_integral(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int s
                      int channels = 1, bool sq_u32 = false);
 int stage_frames(vj_env* e, const vj_image* frames, int n, int W, int H, const uint8_t** d_ptr, size_t* frame_bytes,
                  int* stride, Lane* lane = nullptr, hipStream_t copy_stream = nullptr);
+int check_frames(const vj_image* frames, int n_frames, int* W, int* H, int* CH);   // a batch: frames of one size and channel count
 int enqueue_tilted(vj_env* e, const uint8_t* d_gray, size_t frame_bytes, int stride, int W, int H, int frames, int channels);
 // VJ_FLAG_EQUALIZE_HIST, right after stage_frames: the `frames` staged frames (what stage_frames returned) equalized into the lane's
 // gray batch — one memset and three launches on the environment's stream, nothing waited for — and *d_gray, *frame_bytes, *stride,
@@ -326,6 +328,37 @@ int enqueue_equalize(vj_env* e, Lane* lane, const uint8_t** d_gray, size_t* fram
 int enqueue_equalize_tables(vj_env* e, Lane* lane, const void* d_frame_recs, uint32_t n_frames, uint32_t n_hist_units, const uint8_t** lut);
 // What an entry point that does not equalize answers to the flag: VJ_ERR_UNSUPPORTED, vj_last_error names both; else VJ_OK.
 int refuse_equalize(uint32_t flags, const char* entry_point);
+
+// The clod profile's plans and chain-balance search (vj_env.cpp), for its drivers (vj_detect*.cpp).
+int get_plan(vj_env* e, const vj_cascade* c, int W, int H, const vj_params& p, Plan** out, int n_frames = 1 << 20);   // the cached plan
+int plan_and_upload(const vj_env* e, const vj_cascade& c, int W, int H, const vj_params& p, Plan* pl, float tile_split,
+                    const TileThresholds& thresholds, int n_frames, bool one_pass);   // a plan outside the cache (a stream's own)
+int layout_queues(Plan* pl, int frames, uint64_t* total_entries);
+struct BalanceChoice { float split; int thr; bool candidate; };
+vj_env::Balance* balance_of(vj_env* e, const vj_cascade* c, int W, int H, const vj_params& p, int n_frames, bool create);
+BalanceChoice balance_choice(const vj_env::Balance* b, int n_frames);
+void balance_touch(vj_env::Balance* b, int n_frames);
+void balance_report(vj_env::Balance* b, float ms, bool try_thresholds);
+
+// What the clod profile's detect drivers share (vj_detect.cpp: batches through the cascade, blocking and streamed; vj_detect_regions.cpp: a second cascade inside regions).
+struct RawDet { int frame; uint32_t slot, x, y; };
+int ensure_queues(vj_env* e, Plan* pl, int frames);   // lay out the plan's queues for `frames` frames in flight, ensure d_q[1 .. n_pass)
+// Upload (or adopt) the frames of one batch and enqueue its integral images.  `copy_stream` != null (vj_stream): the upload runs on that stream and the integral waits for it.
+int enqueue_prepare(vj_env* e, Lane* L, Plan* pl, const vj_image* frames, int nf, int W, int H, bool fixed_queue_layout,
+                    hipStream_t copy_stream, bool equalize = false, bool sq_u32 = false);
+// Enqueue every cascade launch of the batch whose integral images are (being) computed, then the asynchronous read-back.  Nothing here waits for the device.
+int enqueue_cascade(vj_env* e, Lane* L, Plan* pl, int W, const vj_params& p);
+// What every cascade launch on `pl` reads of the plan, the lane and the integral images of nf frames (the rest zeroed).
+void fill_plan_args(const vj_env* e, const Lane* L, const Plan* pl, int nf, int W, const vj_params& p, CascadeArgs& ca);
+int finish_batch(vj_env* e, Lane* L, Plan* pl, int f0, int W, int H, const vj_params& p, std::vector<RawDet>* dets,
+                 vj_counters* ctr, vj_timing* tm);
+// Sort, widen and (optionally) group the decoded detections of a whole call (a region pass: `frame` is the region), then fill_counters: the derived counters for `windows` windows.
+int build_result(const Plan* pl, std::vector<RawDet>& dets, uint64_t windows, const vj_params& p, vj_result* out);
+void fill_counters(const Plan* pl, uint64_t windows, const vj_params& p, vj_counters* k);
+int rects_to_result(const std::vector<vj_rect>& rects, vj_result* out);
+uint64_t max_frames_per_subbatch(const vj_env* e, const Plan* pl);
+int subbatch_frames(const vj_env* e, const Plan* pl, const Plan* pl2, uint64_t* max_frames);   // ... of every plan of a call: VJ_ERR_LIMIT at 0
+void balance_feedback(vj_env::Balance* bal, const vj_env* e, const Plan* pl, const vj_params& p, int n_frames, uint64_t max_frames, vj_timing* timing);
 
 // Room for one more entry in a plan cache bounded by plan_cache_max: the least recently used go first and release their tables (the
 // caller has synchronised the stream that may still read them).  An entry with last_used >= keep_tick stays: the run-windows calls

@@ -1,7 +1,7 @@
 // The LDS queues of the gather chain's linear kernels (cascade_pass without stage trees, vj_kernels.hip): one
 // array of GATHER_LDS_ENTRIES entries per workgroup — the 16 KiB the tile classes leave free — divided among the waves the
 // launch runs.  More waves get shorter queues out of the same array.  Plain integer arithmetic without HIP, shared by the kernel,
-// the host code that cuts the first-pass units and clamps the tunables (vj_env.cpp) and a CPU test of its own
+// the host code that cuts the first-pass units and clamps the tunables (vj_clod_plan.cpp, vj_detect.cpp) and a CPU test of its own
 // (tests/gather_queue_driver.cpp); constexpr, so the same functions serve host and device code.
 #pragma once
 #include <stdint.h>

@@ -1,6 +1,6 @@
 // The parts of the grid pass's (frame, unit) list (cascade_pass<FROM_GRID>, vj_kernels.hip): GRID_PARTS contiguous
 // ranges, one ticket counter each, that the pass's waves draw their units from.  Plain integer arithmetic without HIP, shared by
-// the kernel, the host code that lays the counters out (vj_env.cpp) and a CPU test of its own (tests/grid_parts_driver.cpp);
+// the kernel, the host code that lays the counters out (vj_detect_host.hpp) and a CPU test of its own (tests/grid_parts_driver.cpp);
 // constexpr, so the same functions serve host and device code.
 #pragma once
 #include <stdint.h>

@@ -3,7 +3,7 @@
 // rectangles of up to SQ32_MAX_AREA pixels.  A larger window of w <= SQ32_MAX_AREA columns is cut into horizontal strips of
 // floor(SQ32_MAX_AREA / w) rows: each strip's sum is exact from the mod-2^32 image, and the strips add up in 64 bits to the exact
 // value.  A strip's bottom corners are the next strip's top corners, so k strips cost 2 + 2 k loads.  Plain integer arithmetic
-// without HIP, shared by the kernels (vj_kernels.hip), the host that gives every scale its strip height (vj_env.cpp) and a CPU
+// without HIP, shared by the kernels (vj_kernels.hip), the host that gives every scale its strip height (vj_clod_plan.cpp) and a CPU
 // test of its own (tests/sq_strips_driver.cpp).
 #pragma once
 #include <stdint.h>
