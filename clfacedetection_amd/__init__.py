@@ -17,6 +17,6 @@ from .api import (  # noqa: F401
     AFFINE_DTYPE, AffineParams, affine_from_eyes, affine_from_rect, align_transforms, extract_affine_layout,
     PaintParams, VJ_PAINT_FILL, VJ_PAINT_OUTLINE, VJ_PAINT_PIXELATE, VJ_PAINT_BLUR, VJ_PAINT_ELLIPSE, paint_layout,
     YuvFrames, YuvParams, VJ_YUV_NV12, VJ_YUV_NV21, VJ_YUV_I420, VJ_YUV_RGB_ORDER, yuv_to_bgr_layout, bgr_to_yuv_layout,
-    paint_yuv_layout,
+    paint_yuv_layout, extract_yuv_layout, extract_affine_yuv_layout,
     TrackParams, TRACK_RESULT_DTYPE, track_layout, bridge_detections,
 )

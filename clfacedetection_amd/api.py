@@ -362,6 +362,15 @@ _SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "vj_paint_yuv": (C.c_int, [C.c_void_p, C.POINTER(_YuvImage), C.c_int, C.c_void_p, C.c_int, C.POINTER(PaintParams)]),
     "vj_paint_yuv_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "vj_extract_yuv_layout": (C.c_int, [C.POINTER(_YuvImage), C.c_int, C.c_void_p, C.c_int, C.POINTER(ExtractParams), C.POINTER(YuvParams),
+                                        C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "vj_extract_yuv": (C.c_int, [C.c_void_p, C.POINTER(_YuvImage), C.c_int, C.c_void_p, C.c_int, C.POINTER(ExtractParams), C.POINTER(YuvParams),
+                                 C.c_void_p, C.c_uint64]),
+    "vj_extract_affine_yuv_layout": (C.c_int, [C.POINTER(_YuvImage), C.c_int, C.c_void_p, C.c_int, C.POINTER(AffineParams), C.POINTER(YuvParams),
+                                               C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "vj_extract_affine_yuv": (C.c_int, [C.c_void_p, C.POINTER(_YuvImage), C.c_int, C.c_void_p, C.c_int, C.POINTER(AffineParams), C.POINTER(YuvParams),
+                                        C.c_void_p, C.c_uint64]),
+    "vj_extract_yuv_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "vj_track_default": (None, [C.POINTER(TrackParams)]),
     "vj_track_layout": (C.c_int, [C.POINTER(_Image), C.c_int, C.c_void_p, C.c_int, C.POINTER(TrackParams), C.c_void_p, C.c_void_p,
                                   C.POINTER(C.c_uint64)]),
@@ -1547,6 +1556,100 @@ class Environment:
         _check(load_library().vj_extract_affine_timing(self._h, C.byref(ms)), "vj_extract_affine_timing")
         return float(ms.value)
 
+    @staticmethod
+    def _extract_yuv_args(frames, rects, size, scale, margin, gray, planar, alpha, rgb, layout):
+        """-> (ctypes array of vj_yuv_image, n, arrays to keep alive, (n, 5) int32 regions, vj_extract_params, vj_yuv_params).
+        frames: as yuv_to_bgr(); rects: as extract(), in luma pixels."""
+        imgs, n, keep = Environment._yuv_images(frames, layout)
+        _, _, _, r, p = Environment._extract_args(np.zeros((0, 1, 1), np.uint8), rects, size, scale, margin, gray, planar, False)
+        return imgs, n, keep, r, p, Environment._yuv_params(4 if alpha else 3, rgb)
+
+    @staticmethod
+    def extract_yuv_layout(frames, rects, size, scale=(1.0, 1.0), margin: float = 0.0, gray: bool = False, planar: bool = False,
+                           alpha: bool = False, rgb: bool = False, layout="nv12"):
+        """vj_extract_yuv_layout (host only): what extract_yuv() will cut -> ((n, 5) int32 rows of the mapped source regions
+        (frame, x, y, w, h) in luma pixels, which may lie outside their frames; channels of the output; bytes of the output)."""
+        imgs, n, keep, r, p, yp = Environment._extract_yuv_args(frames, rects, size, scale, margin, gray, planar, alpha, rgb, layout)
+        src = np.zeros((len(r), 5), np.int32)
+        ch, nbytes = C.c_int(0), C.c_uint64(0)
+        _check(load_library().vj_extract_yuv_layout(imgs, n, r.ctypes.data, len(r), C.byref(p), C.byref(yp), src.ctypes.data, C.byref(ch),
+                                                    C.byref(nbytes)), "vj_extract_yuv_layout")
+        return src, int(ch.value), int(nbytes.value)
+
+    def _crops_out(self, out, n, ch, p, planar, nbytes):
+        """The destination tensor of extract_yuv() / extract_affine_yuv(), as extract()'s -> (tensor, shape)."""
+        import torch
+        shape = (n, ch, p.out_h, p.out_w) if planar else (n, p.out_h, p.out_w, ch)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", self._device))
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
+            raise ValueError("out must be a contiguous torch.uint8 tensor in device memory")
+        if out.numel() != int(nbytes):
+            raise ValueError(f"out must hold {int(nbytes)} bytes, the shape {shape}; it holds {out.numel()}")
+        return out, shape
+
+    def extract_yuv(self, frames, rects, size, scale=(1.0, 1.0), margin: float = 0.0, gray: bool = False, planar: bool = False,
+                    alpha: bool = False, rgb: bool = False, out=None, layout="nv12"):
+        """vj_extract_yuv: extract() of yuv_to_bgr(frames, alpha, rgb), byte for byte, without the BGR copy of the frames (DESIGN.md
+        §4.25): every tap is decoded from the 4:2:0 planes where they lie (nearest chroma, BT.601 limited range), then resized per
+        channel.  frames: as yuv_to_bgr() — YuvFrames, stacked host arrays, tuples of planes or a list of these; layout names the
+        layout of host arrays.  rects, size, scale, margin, planar: as extract(), the rectangles in luma pixels.  alpha=True: four
+        channels, alpha 255; rgb=True: RGB order; gray=True: one channel, BGR2GRAY of every decoded tap (crops of the Y plane itself
+        are extract(yuv.luma(), ...), which differ in range).  Returns a torch.uint8 device tensor (n, h, w, C), or (n, C, h, w) with
+        planar=True.  out: as extract()."""
+        imgs, n, keep, r, p, yp = self._extract_yuv_args(frames, rects, size, scale, margin, gray, planar, alpha, rgb, layout)
+        lib = load_library()
+        src = np.zeros((len(r), 5), np.int32)
+        ch, nbytes = C.c_int(0), C.c_uint64(0)
+        _check(lib.vj_extract_yuv_layout(imgs, n, r.ctypes.data, len(r), C.byref(p), C.byref(yp), src.ctypes.data, C.byref(ch), C.byref(nbytes)),
+               "vj_extract_yuv_layout")
+        out, shape = self._crops_out(out, len(r), ch.value, p, planar, nbytes.value)
+        _order_after_torch(self._device)       # after the allocation, as in preprocess()
+        _check(lib.vj_extract_yuv(self._h, imgs, n, r.ctypes.data, len(r), C.byref(p), C.byref(yp), C.c_void_p(out.data_ptr()), out.numel()),
+               "vj_extract_yuv")
+        return out.view(shape)
+
+    @staticmethod
+    def _affine_yuv_args(frames, affines, size, gray, planar, alpha, rgb, layout):
+        """-> (ctypes array of vj_yuv_image, n, arrays to keep alive, AFFINE_DTYPE array, vj_affine_params, vj_yuv_params)."""
+        imgs, n, keep = Environment._yuv_images(frames, layout)
+        _, _, _, a, p = Environment._affine_args(np.zeros((0, 1, 1), np.uint8), affines, size, gray, planar, False)
+        return imgs, n, keep, a, p, Environment._yuv_params(4 if alpha else 3, rgb)
+
+    @staticmethod
+    def extract_affine_yuv_layout(frames, affines, size, gray: bool = False, planar: bool = False, alpha: bool = False, rgb: bool = False,
+                                  layout="nv12"):
+        """vj_extract_affine_yuv_layout (host only): what extract_affine_yuv() will write -> (channels, bytes of the output)."""
+        imgs, n, keep, a, p, yp = Environment._affine_yuv_args(frames, affines, size, gray, planar, alpha, rgb, layout)
+        ch, nbytes = C.c_int(0), C.c_uint64(0)
+        _check(load_library().vj_extract_affine_yuv_layout(imgs, n, a.ctypes.data, len(a), C.byref(p), C.byref(yp), C.byref(ch), C.byref(nbytes)),
+               "vj_extract_affine_yuv_layout")
+        return int(ch.value), int(nbytes.value)
+
+    def extract_affine_yuv(self, frames, affines, size, gray: bool = False, planar: bool = False, alpha: bool = False, rgb: bool = False,
+                           out=None, layout="nv12"):
+        """vj_extract_affine_yuv: extract_affine() of yuv_to_bgr(frames, alpha, rgb), byte for byte, without the BGR copy (DESIGN.md
+        §4.25): the four taps of every output pixel are decoded from the 4:2:0 planes, then blended per channel.  frames, alpha, rgb,
+        gray, layout: as extract_yuv(); affines, size, planar, out and the result: as extract_affine(), source coordinates in luma
+        pixels (align_transforms' rows fit as they are)."""
+        imgs, n, keep, a, p, yp = self._affine_yuv_args(frames, affines, size, gray, planar, alpha, rgb, layout)
+        lib = load_library()
+        ch, nbytes = C.c_int(0), C.c_uint64(0)
+        _check(lib.vj_extract_affine_yuv_layout(imgs, n, a.ctypes.data, len(a), C.byref(p), C.byref(yp), C.byref(ch), C.byref(nbytes)),
+               "vj_extract_affine_yuv_layout")
+        out, shape = self._crops_out(out, len(a), ch.value, p, planar, nbytes.value)
+        _order_after_torch(self._device)       # after the allocation, as in preprocess()
+        _check(lib.vj_extract_affine_yuv(self._h, imgs, n, a.ctypes.data, len(a), C.byref(p), C.byref(yp), C.c_void_p(out.data_ptr()),
+                                         out.numel()), "vj_extract_affine_yuv")
+        return out.view(shape)
+
+    def extract_yuv_timing(self) -> float:
+        """vj_extract_yuv_timing: device time of the last extract_yuv() or extract_affine_yuv() call (events around its copies and
+        launches), ms."""
+        ms = C.c_float(0)
+        _check(load_library().vj_extract_yuv_timing(self._h, C.byref(ms)), "vj_extract_yuv_timing")
+        return float(ms.value)
+
     def mixed_info(self) -> MixedInfo:
         """vj_mixed_info_get: atlases (count and the largest one's size), batched calls on original frames, frames by route, grid
         positions of the atlas passes and the pack launches' device time of the last detect_mixed / detect_opencv_mixed call."""
@@ -1747,6 +1850,19 @@ def paint_yuv_layout(frames, rects, mode="blur", size: int = 0, rel: float = 0.2
     """vj_paint_yuv_layout: the host-only twin of Environment.paint_yuv (no environment, no device) ->
     (K rows, Kc rows, luma sizes, chroma sizes, scratch bytes)."""
     return Environment.paint_yuv_layout(frames, rects, mode, size, rel, scale, margin, ellipse, layout)
+
+
+def extract_yuv_layout(frames, rects, size, scale=(1.0, 1.0), margin: float = 0.0, gray: bool = False, planar: bool = False,
+                       alpha: bool = False, rgb: bool = False, layout="nv12"):
+    """vj_extract_yuv_layout: the host-only twin of Environment.extract_yuv (no environment, no device) ->
+    (mapped source regions in luma pixels, channels, bytes)."""
+    return Environment.extract_yuv_layout(frames, rects, size, scale, margin, gray, planar, alpha, rgb, layout)
+
+
+def extract_affine_yuv_layout(frames, affines, size, gray: bool = False, planar: bool = False, alpha: bool = False, rgb: bool = False,
+                              layout="nv12"):
+    """vj_extract_affine_yuv_layout: the host-only twin of Environment.extract_affine_yuv -> (channels, bytes)."""
+    return Environment.extract_affine_yuv_layout(frames, affines, size, gray, planar, alpha, rgb, layout)
 
 
 def track_layout(frames, rows, tmpl: int = 32, radius: int = 8, scale=(1.0, 1.0), color: bool = False):

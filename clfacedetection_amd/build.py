@@ -15,9 +15,9 @@ import sys
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libvjhip.so")
-SOURCES = ["vj_cascade.cpp", "vj_plan.cpp", "vj_clod_plan.cpp", "vj_group.cpp", "vj_env.cpp", "vj_detect.cpp", "vj_detect_regions.cpp", "vj_cv.cpp", "vj_cv_plan.cpp", "vj_cv_roi_host.cpp", "vj_cv_roi_levels_host.cpp", "vj_cv_points_host.cpp", "vj_points_host.cpp", "vj_points_driver.cpp", "vj_atlas_host.cpp", "vj_mixed.cpp", "vj_prep_host.cpp", "vj_preprocess.cpp", "vj_extract_host.cpp", "vj_extract.cpp", "vj_affine_host.cpp", "vj_extract_affine.cpp", "vj_paint_host.cpp", "vj_paint.cpp", "vj_yuv_host.cpp", "vj_yuv.cpp", "vj_paint_yuv_host.cpp", "vj_paint_yuv.cpp", "vj_track_host.cpp", "vj_track.cpp", "vj_kernels.hip",
-           "vj_cv_profile.hip", "vj_cv_tile.hip", "vj_group_dev.hip", "vj_canny.hip", "vj_pyramid.hip", "vj_cv_biggest.hip", "vj_cv_roi.hip", "vj_cv_chain.hip", "vj_cv_points.hip", "vj_points.hip", "vj_atlas.hip", "vj_equalize.hip", "vj_prep.hip", "vj_extract.hip", "vj_affine.hip", "vj_paint.hip", "vj_yuv.hip", "vj_paint_yuv.hip", "vj_track.hip"]
-HEADERS = ["vj_internal.hpp", "vj_device.hpp", "vj_env_internal.hpp", "vj_detect_host.hpp", "vj_tunables.hpp", "vj_clod_plan.hpp", "vj_cv_plan.hpp", "vj_devutil.hpp", "vj_cv_window.hpp", "vj_group_frame.hpp", "vj_cv_roi_units.hpp", "vj_cv_roi_host.hpp", "vj_cv_roi_levels_host.hpp", "vj_cv_tq_host.hpp", "vj_cv_points_units.hpp", "vj_cv_points_host.hpp", "vj_points_units.hpp", "vj_points_host.hpp", "vj_points_driver.hpp", "vj_clod_window.hpp", "vj_grid_parts.hpp", "vj_gather_queue.hpp", "vj_sq_strips.hpp", "vj_atlas_units.hpp", "vj_atlas_host.hpp", "vj_prep_units.hpp", "vj_prep_host.hpp", "vj_extract_units.hpp", "vj_extract_host.hpp", "vj_affine_units.hpp", "vj_affine_host.hpp", "vj_paint_units.hpp", "vj_paint_host.hpp", "vj_yuv_units.hpp", "vj_yuv_host.hpp", "vj_paint_yuv_units.hpp", "vj_paint_yuv_host.hpp", "vj_track_units.hpp", "vj_track_host.hpp", "vj_stage_host.hpp", "vj_slice.hpp", os.path.join("..", "..", "include", "vj.h")]
+SOURCES = ["vj_cascade.cpp", "vj_plan.cpp", "vj_clod_plan.cpp", "vj_group.cpp", "vj_env.cpp", "vj_detect.cpp", "vj_detect_regions.cpp", "vj_cv.cpp", "vj_cv_plan.cpp", "vj_cv_roi_host.cpp", "vj_cv_roi_levels_host.cpp", "vj_cv_points_host.cpp", "vj_points_host.cpp", "vj_points_driver.cpp", "vj_atlas_host.cpp", "vj_mixed.cpp", "vj_prep_host.cpp", "vj_preprocess.cpp", "vj_extract_host.cpp", "vj_extract.cpp", "vj_affine_host.cpp", "vj_extract_affine.cpp", "vj_paint_host.cpp", "vj_paint.cpp", "vj_yuv_host.cpp", "vj_yuv.cpp", "vj_paint_yuv_host.cpp", "vj_paint_yuv.cpp", "vj_extract_yuv_host.cpp", "vj_extract_yuv.cpp", "vj_track_host.cpp", "vj_track.cpp", "vj_kernels.hip",
+           "vj_cv_profile.hip", "vj_cv_tile.hip", "vj_group_dev.hip", "vj_canny.hip", "vj_pyramid.hip", "vj_cv_biggest.hip", "vj_cv_roi.hip", "vj_cv_chain.hip", "vj_cv_points.hip", "vj_points.hip", "vj_atlas.hip", "vj_equalize.hip", "vj_prep.hip", "vj_extract.hip", "vj_affine.hip", "vj_paint.hip", "vj_yuv.hip", "vj_paint_yuv.hip", "vj_extract_yuv.hip", "vj_track.hip"]
+HEADERS = ["vj_internal.hpp", "vj_device.hpp", "vj_env_internal.hpp", "vj_detect_host.hpp", "vj_tunables.hpp", "vj_clod_plan.hpp", "vj_cv_plan.hpp", "vj_devutil.hpp", "vj_cv_window.hpp", "vj_group_frame.hpp", "vj_cv_roi_units.hpp", "vj_cv_roi_host.hpp", "vj_cv_roi_levels_host.hpp", "vj_cv_tq_host.hpp", "vj_cv_points_units.hpp", "vj_cv_points_host.hpp", "vj_points_units.hpp", "vj_points_host.hpp", "vj_points_driver.hpp", "vj_clod_window.hpp", "vj_grid_parts.hpp", "vj_gather_queue.hpp", "vj_sq_strips.hpp", "vj_atlas_units.hpp", "vj_atlas_host.hpp", "vj_prep_units.hpp", "vj_prep_host.hpp", "vj_extract_units.hpp", "vj_extract_host.hpp", "vj_affine_units.hpp", "vj_affine_host.hpp", "vj_paint_units.hpp", "vj_paint_host.hpp", "vj_yuv_units.hpp", "vj_yuv_host.hpp", "vj_paint_yuv_units.hpp", "vj_paint_yuv_host.hpp", "vj_extract_yuv_units.hpp", "vj_extract_yuv_host.hpp", "vj_track_units.hpp", "vj_track_host.hpp", "vj_stage_host.hpp", "vj_slice.hpp", os.path.join("..", "..", "include", "vj.h")]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950",
          "-Wall", "-Wno-unused-function", "-fvisibility=hidden", "-DVJ_BUILDING"] + \
     (["-DVJ_STAMPS=1"] if os.environ.get("VJ_STAMPS") else []) + \

@@ -295,9 +295,10 @@ struct vj_env : vj::Tunables {
     vj::DevBuf d_prep;      // vj_preprocess (§4.16): [frame records | the records equalize_lut reads | taps | frames]; histograms
                             // and tables: lane0's d_eq_hist / d_eq_lut
     vj::DevBuf d_extract;   // vj_extract (§4.17): [region records | taps | frames]; vj_extract_affine (§4.19): [region records | frames];
+                            // vj_extract_yuv / vj_extract_affine_yuv (§4.25): [region records | taps | planes];
                             // vj_paint (§4.20) and vj_paint_yuv (§4.23): [records | overlap lists | touched rows | scratch]
     vj::DevBuf d_yuv;       // vj_yuv_to_bgr / vj_bgr_to_yuv (§4.21): [frame records | planes]
-    float prep_ms = 0, extract_ms = 0, affine_ms = 0, paint_ms = 0, paint_yuv_ms = 0, yuv_ms = 0;
+    float prep_ms = 0, extract_ms = 0, affine_ms = 0, paint_ms = 0, paint_yuv_ms = 0, yuv_ms = 0, extract_yuv_ms = 0;
     // vj_track (vj_track.cpp): its scratch — the templates, the search patches, the match records (grows, reused);
     // its slices come through d_extract like vj_extract's —, events around a call [0, 1] and around a match launch [2, 3], their times
     vj::DevBuf d_track;

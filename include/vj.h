@@ -938,6 +938,7 @@ int  vj_paint_timing(const vj_env* e, float* ms);
 /* Hardware decoders write 4:2:0 YCbCr and encoders read it; vj_extract and vj_paint work on interleaved BGR.  These two batched
  * calls close the loop on the device:
  *   decoder -> vj_yuv_luma -> vj_preprocess / detect -> vj_yuv_to_bgr -> vj_extract / vj_paint -> vj_bgr_to_yuv -> encoder.
+ * (vj_paint_yuv and vj_extract_yuv / vj_extract_affine_yuv below do the painting and the cropping on the 4:2:0 frames directly.)
  * The arithmetic is OpenCV imgproc's 8-bit fixed-point BT.601 limited-range pair, cvtColor(COLOR_YUV2BGR_NV12 / _NV21 / _I420) and
  * cvtColor(COLOR_BGR2YUV_I420); parity is unpinned at the OpenCV boundary, the definition here and in DESIGN.md 4.21 is
  * authoritative.  All values are int32, >> is the arithmetic (flooring) shift, sat(t) = min(max(t, 0), 255), H = 1 << 19.
@@ -1050,6 +1051,44 @@ int  vj_paint_yuv_layout(const vj_yuv_image* frames, int n_frames, const vj_roi*
 int  vj_paint_yuv(vj_env* e, const vj_yuv_image* frames, int n_frames, const vj_roi* regions, int n_regions, const vj_paint_params* p);
 /* Device time of the environment's last vj_paint_yuv call: events around its copies and launches, in ms.  A null argument: VJ_ERR_ARG. */
 int  vj_paint_yuv_timing(const vj_env* e, float* ms);
+
+/* ------------------------------------------------- crops cut straight out of 4:2:0 frames, on the device */
+/* Colour crops for a network without the BGR copy of the whole batch.  ONE sentence defines both calls:
+ *   vj_extract_yuv(env, frames, n_frames, regions, n_regions, p, yp, d_dst, dst_bytes) writes exactly the bytes that vj_extract
+ *   writes for the same `regions` and `p` when its frames are what vj_yuv_to_bgr(frames, yp) returns.
+ *   vj_extract_affine_yuv(env, frames, n_frames, affines, n, p, yp, d_dst, dst_bytes) relates to vj_extract_affine in the same way.
+ * Nothing new is stated: the arithmetic is the decode above, then vj_extract's or vj_extract_affine's steps on the decoded bytes;
+ * parity stays unpinned at the OpenCV boundary, as for those.  Spelled out:
+ *   - frames: as vj_yuv_to_bgr takes them — NV12, NV21, I420, host or device-resident, any strides, any addresses, sizes and
+ *     layouts may differ within a call.  regions and the affines' source coordinates are in LUMA pixels.
+ *   - p is vj_extract's / vj_extract_affine's struct; yp is vj_yuv_to_bgr's: channels 3 or 4 and VJ_YUV_RGB_ORDER.
+ *   - A tap at the clamped source pixel (cx, cy) is decode(Y[cy][cx], U[cy >> 1][cx >> 1], V[cy >> 1][cx >> 1]), through sat, with
+ *     alpha 255 when channels = 4.  The crop-edge clamp (vj_extract's steps 2 and 3) and the frame clamp act on the luma
+ *     coordinate; the chroma sample follows from the clamped coordinate.
+ *   - DECODE FIRST, then the resize per channel on the decoded bytes (the 2 x 2 mean, the bilinear integer arithmetic or the
+ *     copy), or vj_extract_affine's blend.  Blending Y, U and V and decoding afterwards is a different function.
+ *   - VJ_EXTRACT_GRAY is the composition too: the ingest BGR2GRAY of each decoded tap (its three bytes in the order yp gives
+ *     them), then the blend, C = 1.  Crops of the Y plane itself are vj_extract on vj_yuv_luma's images, which differ in range.
+ *   - C = 1 with VJ_EXTRACT_GRAY, else yp->channels; VJ_EXTRACT_PLANAR and the dense layout are vj_extract's; d_dst at any address. */
+/* Host only, no environment: as vj_extract_layout / vj_extract_affine_layout.  Errors as below.                                 */
+int  vj_extract_yuv_layout(const vj_yuv_image* frames, int n_frames, const vj_roi* regions, int n_regions, const vj_extract_params* p,
+                           const vj_yuv_params* yp, vj_roi* src_regions, int* channels, uint64_t* bytes);
+int  vj_extract_affine_yuv_layout(const vj_yuv_image* frames, int n_frames, const vj_affine* affines, int n, const vj_affine_params* p,
+                                  const vj_yuv_params* yp, int* channels, uint64_t* bytes);
+/* d_dst: as vj_extract.  Return after the work is complete.  All checks come before the device is used.  VJ_ERR_ARG, with
+ * vj_last_error naming the frame, the row or the field: null arguments (yp included); the frame errors of vj_yuv_to_bgr (a null
+ * plane that the layout needs, odd or non-positive sizes, a stride below the plane's row bytes, an unknown layout); yp->channels
+ * not 3 or 4, unknown flag bits or reserved != 0 in yp; the region, affine and parameter errors of vj_extract / vj_extract_affine;
+ * dst_bytes below the layout's bytes; a device-resident source plane that overlaps [d_dst, d_dst + bytes).  VJ_ERR_LIMIT: a frame
+ * side above 65534; the mapping and output limits of vj_extract / vj_extract_affine.  n == 0 is VJ_OK.  With "max_subbatch"
+ * configured a call runs in slices of regions that name at most that many frames, like vj_extract's.                            */
+int  vj_extract_yuv(vj_env* e, const vj_yuv_image* frames, int n_frames, const vj_roi* regions, int n_regions,
+                    const vj_extract_params* p, const vj_yuv_params* yp, uint8_t* d_dst, uint64_t dst_bytes);
+int  vj_extract_affine_yuv(vj_env* e, const vj_yuv_image* frames, int n_frames, const vj_affine* affines, int n,
+                           const vj_affine_params* p, const vj_yuv_params* yp, uint8_t* d_dst, uint64_t dst_bytes);
+/* Device time of the environment's last vj_extract_yuv or vj_extract_affine_yuv call: events around its copies and launches, in
+ * ms.  A null argument: VJ_ERR_ARG.                                                                                             */
+int  vj_extract_yuv_timing(const vj_env* e, float* ms);
 
 /* ------------------------------------------------- boxes carried from frame to frame, on the device */
 /* A cascade drops a face for a frame or two; every video pipeline bridges that by looking for the box of frame f in frame f +- 1.
